@@ -17,15 +17,24 @@ data-path collective; "weak" scaling); with configs 3 / 4 the ONE job is sharded
 contigs by longest-processing-time; the single contig in 2048-aligned windows with a read-length halo;
 "strong" scaling).  The polished bytes are gathered to rank 0 inside the timed step.
 
-Rank 0 prints ONE JSON line with metric/value/unit, plus
+Rank 0 prints ONE JSON line with metric/value/unit/ms_per_step, plus
   roofline     achieved HBM GB/s of the dominant kernel = algorithmic bytes per launch / mean launch
-               duration measured with HIP events on the library's stream
+               duration measured with HIP events on the library's stream (inside the timed steps)
+A plain run does nothing else: it sets the job up, warms up, times the steps and, with --dump-outputs DIR, writes what the
+timed path returned in its last step (dump_outputs).  --full adds every other leg, each of which costs runs of its own:
+  kernel_ms_per_step, work   a few untimed steps with every kernel group under HIP events
+  roofline.traffic   HBM bytes of the dominant kernel from two rocprofv3 --pmc child passes (--no-live-traffic: not run)
+  roofline_file_order_seq    the same job in the layout of rounds 1-3 (--no-second-layout: not run), and roofline_filter
+  planted_errors_recovered   the polished contigs against the truth; N>1: gather_verified, per_rank, multi_gpu_split
   cpu_baseline the single-threaded C oracle (kind "port": the Rust reference cannot be built here) timed on
-               a bounded sample of the same workload, with a live parity check
+               a bounded sample of the same workload, with a live parity check (--no-cpu-baseline: not run)
+  first_job_ms, foreign_mirror_check_ms   a fresh context's first job; the check of a mirror not taken on trust
+  other_configs      configs[2], [3], [4] and the step without its steady-state shortcuts, as child runs (--no-other-configs)
   e2e          (N=1) the drop-in CLI from SAM TEXT to FASTA on files of the configuration's shape generated on the
                box: wall seconds of `polypolish polish` (device tokenizer and host ingest), `filter`, `filter-polish`
                (configs[2]: real all-hits files, and `filter` followed by `polish`; configs[3], [4]: polish on 13 / 33 GB
-               of text), the oracle's CLI on one core on the same files, and whether the output bytes are identical.
+               of text), the oracle's CLI on one core on the same files, and whether the output bytes are identical
+               (--no-e2e: not run).
 
 Synthetic data: SURVEY.md section 8d's recipe (tools/synthjob.py) -- assembly errors 1/3 substitutions, 1/3 1-bp
 deletions, 1/3 1-bp insertions (half of the indels in homopolymers), reads aligned to the ASSEMBLY with the resulting
@@ -174,7 +183,7 @@ def live_traffic(argv_tail, kernel):
         d = tempfile.mkdtemp(prefix="pp_pmc_", dir="/tmp")
         try:
             cmd = [exe, "--pmc", counter, "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-                   "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--no-live-traffic", "--no-second-layout", "--no-other-configs"] + argv_tail
+                   "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-e2e", "--no-live-traffic", "--no-second-layout", "--no-other-configs"] + argv_tail
             r = subprocess.run(cmd, capture_output=True, timeout=240, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"))
             if r.returncode != 0:
                 return None
@@ -422,6 +431,31 @@ def _error_line(world, args, msg):
                        "config": {"workload": f"configs[{args.config}]"}, "error": msg})
 
 
+DUMP_WHOLE_BP = 12_000_000   # polished bases written whole up to this many (48 MB as float32) ...
+DUMP_SAMPLE_BP = 4_000_000   # ... past it a fixed, seeded sample of this many positions (16 MB + 32 MB of positions)
+
+
+def dump_outputs(out_dir, polished, offs, stats):
+    """--dump-outputs DIR: what the timed path returned in its last step, as pp_polish_result hands it to a caller -- the
+    polished bases (byte values, float32), the contigs' offsets into them and their per-contig figures (polished_len,
+    changed, zero_depth, depth_sum; float64, exact for counts below 2^53).  A job of more than DUMP_WHOLE_BP polished bases
+    is sampled at DUMP_SAMPLE_BP positions drawn with a fixed seed (polished_index.npy: the positions, float64), so that
+    the files stay under 64 MB and two runs with the same arguments write the same positions."""
+    os.makedirs(out_dir, exist_ok=True)
+    got = np.frombuffer(polished, dtype=np.uint8)
+    index_path = os.path.join(out_dir, "polished_index.npy")
+    if got.size > DUMP_WHOLE_BP:
+        idx = np.sort(np.random.default_rng(4242).integers(0, got.size, DUMP_SAMPLE_BP))
+        np.save(index_path, idx.astype(np.float64))
+        got = got[idx]
+    elif os.path.exists(index_path):   # (left by an earlier run of a larger job in the same directory)
+        os.remove(index_path)
+    np.save(os.path.join(out_dir, "polished.npy"), got.astype(np.float32))
+    np.save(os.path.join(out_dir, "offsets.npy"), np.asarray(offs).astype(np.float64))
+    np.save(os.path.join(out_dir, "contig_stats.npy"),
+            np.array([[s["polished_len"], s["changed"], s["zero_depth"], s["depth_sum"]] for s in stats], dtype=np.float64).reshape(-1, 4))
+
+
 class _Watchdog:
     """A collective that hangs (one rank gone, a fabric problem) cannot be caught: a timer thread prints the error line on
     rank 0 and ends the process.  arm(seconds, what) before the risky stretch, disarm() after it."""
@@ -458,6 +492,13 @@ def main():
     ap.add_argument("--coverage", type=int, default=None, help="override the configuration's coverage")
     ap.add_argument("--cpu-sample", type=int, default=5_000_000,
                     help="bp of one contig given to the CPU oracle (default: the whole 5 Mbp job of config 1, ~12 s)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other leg too: per-kernel breakdown, counter passes, the second layout, "
+                         "the planted-error and gather checks, the CPU baseline, the other configurations, the end-to-end leg "
+                         "(the --no-* options below leave single legs out of a --full run)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned (polished bases, contig offsets, per-contig "
+                         "figures) as DIR/<name>.npy, float32 / float64 (rank 0's own result when N > 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--seq-pitch", type=int, default=-1,
                     help="bytes of the seq array per record: -1 (default) = as the product's ingests lay it out, every record's SEQ on a "
@@ -684,20 +725,25 @@ def main():
     dog.disarm()
     if world > 1:
         dog.arm(args.collective_timeout + 60.0, "the untimed steps and the verification of the gathered bytes")
-    ctx.set_profiling(1)
+    # what the last timed step computed, as the path's caller receives it (this rank's own result)
+    polished, offs, stats = ctx.result()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, polished, offs, stats)
     all_ms, n_break, work = {}, 5, {}
-    for _ in range(n_break):
-        step()
-        kt = ctx.kernel_times()
-        work = {"work_items": kt["n_entries"], "positions_replayed_exactly": kt["n_flagged"], "pipeline_passes": kt["n_passes"]}
-        for k, v in kt["ms"].items():
-            all_ms[k] = all_ms.get(k, 0.0) + v
-    ctx.set_profiling(0)
+    if args.full:
+        ctx.set_profiling(1)
+        for _ in range(n_break):
+            step()
+            kt = ctx.kernel_times()
+            work = {"work_items": kt["n_entries"], "positions_replayed_exactly": kt["n_flagged"], "pipeline_passes": kt["n_passes"]}
+            for k, v in kt["ms"].items():
+                all_ms[k] = all_ms.get(k, 0.0) + v
+        ctx.set_profiling(0)
 
     gather_ok = None
     per_rank = None
     one_gpu_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         # what every rank did, so that a multi-GPU record can be read: its kernels, and its steps split into compute (begin /
         # add / finish: ends in a stream synchronisation) and the gather
         mine_diag = {"rank": rank, "records": job["part"].n_aln if strong else job["n_aln"],
@@ -733,7 +779,6 @@ def main():
                 for _ in range(3):
                     run_job(ctx, pp, full)
                 one_gpu_ms = 1e3 * (time.perf_counter() - t1) / 3
-                run_job(ctx, pp, job)  # leave the rank's own result in the context for the report below
     G_all_ranks = G_total
     if world > 1 and not strong:  # weak scaling: every rank's own contig (their lengths differ by the planted indels)
         t = torch.tensor([G_total], dtype=torch.int64, device=gdev)
@@ -755,15 +800,14 @@ def main():
     dom_avg_ms = float(np.mean(dom_ms)) if dom_ms else 0.0
     achieved = b_alg / (dom_avg_ms * 1e-3) / 1e9 if dom_avg_ms > 0 else 0.0
     peak = 8000.0
-    polished, offs, stats = ctx.result()
     recovered = None
-    if not strong and not repeat:  # (repeat copies that differ by SNPs are out-voted by their siblings' reads: not expected)
+    if args.full and not strong and not repeat:  # (repeat copies that differ by SNPs are out-voted by their siblings' reads: not expected)
         recovered = synthjob.recovered(job, polished, offs)
 
     # HBM traffic of the dominant kernel (PMC counters): measured in this run by two rocprofv3 child passes of this very
-    # command (N = 1); failing that, the committed figure of the same workload (profiles/traffic.json), else null.
+    # command (N = 1, --full); failing that, the committed figure of the same workload (profiles/traffic.json), else null.
     traffic = traffic_source = None
-    if world == 1 and dom_name and not args.no_live_traffic:
+    if args.full and world == 1 and dom_name and not args.no_live_traffic:
         tail = ["--config", str(args.config), "--seq-pitch", str(args.seq_pitch), "--seq4", args.seq4, "--wo", args.wo, "--seq-layout", args.seq_layout, "--recipe", args.recipe, "--indel-frac", repr(args.indel_frac), "--sub-rate", repr(args.sub_rate),
                 "--n-rate", repr(args.n_rate), "--read-len", str(args.read_len), "--repeat-bp", str(args.repeat_bp), "--nd-frac", repr(args.nd_frac)]
         if args.genome is not None:
@@ -784,7 +828,7 @@ def main():
             traffic_source = "profiles/traffic.json (committed rocprofv3 --pmc passes of this command, not this run)"
 
     second = None
-    if world == 1 and args.seq_layout == "window" and args.seq4 == "on" and args.wo == "on" and args.seq_pitch < 0 and not args.no_second_layout:
+    if args.full and world == 1 and args.seq_layout == "window" and args.seq4 == "on" and args.wo == "on" and args.seq_pitch < 0 and not args.no_second_layout:
         # The same job as rounds 1-3 measured it (and as the ingests still deliver it with PP_SEQ_LAYOUT=file PP_SEQ4=0): SEQ bytes
         # in the order of the records, no 4-bit mirror -- the lane-group plain class over the bytes.  Measured like the headline.
         def other_layout(wj, what, tail):
@@ -871,6 +915,14 @@ def main():
                               "k_tile_direct (a window's bulk straight from the mirror) -- no bucketing pass, no work items for 93 % of the records"
                               if direct_path else "bucketing: k_prep -> k_scan_cols / k_scan / k_fill (16-byte work items) -> k_tile"),
                      "whole_path_frac": round(b_alg / (ms_per_step * 1e-3) / 1e9 / peak, 4) if world == 1 else None},
+        "changed_positions": int(sum(s["changed"] for s in stats)),
+    }
+    if not args.full:
+        print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    out.update({
         "roofline_file_order_seq": second,
         "kernel_ms_per_step": {k: round(v / max(n_break, 1), 4) for k, v in sorted(all_ms.items())},
         "work": work,
@@ -884,8 +936,7 @@ def main():
             "compute_only_speedup": None if one_gpu_ms is None else round(one_gpu_ms / max(max(r["compute_ms_per_step"] for r in per_rank), 1e-9), 3),
             "note": "strong scaling: the whole job on rank 0's GPU alone (after the timed region) over the slowest rank's compute half of a "
                     "step -- the curve without the gather; the driver computes the efficiency with the gather from `value`"},
-        "changed_positions": int(sum(s["changed"] for s in stats)),
-    }
+    })
 
     if not args.no_cpu_baseline and world == 1:
         from oracle import orc  # the checker / reported baseline -- never the measured product path
@@ -956,7 +1007,7 @@ def main():
         # (3) the other GPU configurations, compact and driver-timed: child runs of this command (their jobs do not fit next to
         # this one's), and configs[1] once more without the two steady-state shortcuts (PP_SPECULATE=0 PP_INIT_AHEAD=0)
         def child(extra, env=None):
-            cmd = [sys.executable, os.path.abspath(__file__), "--no-e2e", "--no-cpu-baseline", "--no-live-traffic", "--no-second-layout",
+            cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-e2e", "--no-cpu-baseline", "--no-live-traffic", "--no-second-layout",
                    "--no-other-configs", "--steps", "10", "--warmup", "3"] + extra
             try:
                 r = subprocess.run(cmd, capture_output=True, timeout=400, env=dict(os.environ, **(env or {})))

@@ -1402,7 +1402,7 @@ def test_bench_shards_the_real_configs_across_ranks(tmp_path, config):
     port = 35000 + os.getpid() % 2000 + config
     r = subprocess.run(["python", "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--config", str(config),
-                        "--genome", "3000000", "--steps", "2", "--warmup", "1"], capture_output=True, env=env, cwd=ROOT,
+                        "--genome", "3000000", "--steps", "2", "--warmup", "1", "--full"], capture_output=True, env=env, cwd=ROOT,
                        timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])

@@ -47,7 +47,7 @@ def traffic_json(out_path, bench_dirs, calib_dirs):
         kernels[k] = {"fetch_raw_bytes": round(fr), "write_raw_bytes": round(wr),
                       "hbm_bytes": round(fr * fetch_factor + wr * write_factor)}
     doc = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on "
-                     "`python bench.py --steps 10 --warmup 2 --no-cpu-baseline`; mean per dispatch",
+                     "`python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline`; mean per dispatch",
            "fetch_factor": fetch_factor, "write_factor": write_factor,
            "calibration": {"kernel": ck, "copied_bytes": n, "fetch_raw_bytes": round(f_raw), "write_raw_bytes": round(w_raw),
                            "fetch_measured_factor": round(n / f_raw, 3) if f_raw else None},

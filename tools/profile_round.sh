@@ -8,7 +8,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-live-traffic --no-second-layout"
+BENCH="python $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-e2e --no-live-traffic --no-second-layout"
 cd /tmp
 timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_trace -- $BENCH > "$OUT/bench_under_trace.json" 2> "$OUT/trace.log"
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d /tmp/p_fetch -- $BENCH > /dev/null 2> "$OUT/fetch.log"
@@ -19,6 +19,6 @@ cd "$ROOT"
 python tools/prof_summary.py /tmp/p_trace /tmp/p_fetch /tmp/p_write /tmp/c_fetch /tmp/c_write > "$OUT/rocprofv3_summary.txt"
 python tools/prof_summary.py --traffic-json "$OUT/traffic.json" --bench /tmp/p_fetch /tmp/p_write --calib /tmp/c_fetch /tmp/c_write
 find /tmp/p_trace -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats.csv" \;
-python bench.py > "$OUT/bench.json" 2> "$OUT/bench.log"
+python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.log"
 tail -c 1500 "$OUT/bench.json"
 cat "$OUT/traffic.json"
