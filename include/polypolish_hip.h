@@ -271,6 +271,17 @@ typedef struct {
 int pp_polish_debug_extra(pp_ctx *ctx, pp_debug_extra *out);
 void pp_debug_extra_free(pp_debug_extra *d);
 
+/* The --debug TSV itself (src/polish.rs:257-266, without its header line), formatted on the device: the lines of the
+ * positions [pos_lo, pos_hi) (concatenated assembly coordinates) in position order, into `out` (PP_MEM_HOST or
+ * PP_MEM_DEVICE, cap bytes).  Valid after pp_polish_finish with pp_polish_set_debug(ctx, 1); a context with
+ * pp_polish_set_emit writes the lines of the positions it emits and skips the others.  contig_names: one NUL-terminated
+ * name per contig (read on the first call after a job).  Writes whole lines only: *len = bytes written, *pos_next = the
+ * first position not written (pos_hi when the range is done; call again from there).  PP_ERR_ARG, and nothing written,
+ * when cap is smaller than the first line.  Device memory: 4 bytes per assembly position and a bounded staging area,
+ * whatever the TSV's size. */
+int pp_polish_debug_tsv(pp_ctx *ctx, const char *const *contig_names, uint64_t pos_lo, uint64_t pos_hi, uint8_t *out,
+                        int out_mem, uint64_t cap, uint64_t *len, uint64_t *pos_next);
+
 /* Per-kernel device time of the last pp_polish_finish, measured with HIP events on the context's
  * stream when profiling is enabled.  names[i] are static strings. */
 #define PP_MAX_KERNELS 16

@@ -178,7 +178,7 @@ EXPORTS = [
     "pp_comm_unique_id", "pp_comm_init", "pp_comm_destroy", "pp_polish_gather", "pp_polish_files_multi",
     "pp_shard_split", "pp_shard_part_batch", "pp_shard_part_mem", "pp_shard_part_free", "pp_shard_count",
     "pp_polish_error_record", "pp_polish_error_text", "pp_dev_ingest_set_seq_layout", "pp_dev_ingest_expect",
-    "pp_ingest_set_seq_layout",
+    "pp_ingest_set_seq_layout", "pp_polish_debug_tsv",
 ]
 
 _lib = None
@@ -216,6 +216,7 @@ def lib():
         L.pp_polish_set_debug.argtypes = [vp, C.c_int]
         L.pp_polish_set_emit.argtypes = [vp, vp, vp]
         L.pp_polish_positions.argtypes = [vp, C.POINTER(PositionsOut)]
+        L.pp_polish_debug_tsv.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_int, C.c_uint64, u64p, u64p]
         L.pp_ctx_set_profiling.argtypes = [vp, C.c_int]
         L.pp_polish_kernel_times.argtypes = [vp, C.POINTER(KernelTimes)]
         L.pp_polish_took_direct_path.argtypes = [vp]
@@ -840,6 +841,26 @@ class Context:
         self._chk(lib().pp_polish_positions(self._h, C.byref(po)))
         return arrs
 
+    def debug_tsv(self, contig_names, lo=0, hi=None, chunk=64 << 20) -> bytes:
+        """The --debug TSV lines (no header) of positions [lo, hi) of the last job, formatted on the device
+        (pp_polish_debug_tsv): the job must have run with per-position records (polish_records(..., positions=True)).
+        A context with emit ranges gives the lines of the positions it emits.  Fetched `chunk` bytes at a time."""
+        names = [n.encode() if isinstance(n, str) else bytes(n) for n in contig_names]
+        if len(names) != self._n_contigs:
+            raise PolypolishError(ERR_ARG, "debug_tsv: one name per contig")
+        arr = (C.c_char_p * max(len(names), 1))(*names)
+        hi = self._G if hi is None else int(hi)
+        buf = np.empty(max(int(chunk), 1), dtype=np.uint8)
+        n, nxt = C.c_uint64(), C.c_uint64()
+        parts, p = [], int(lo)
+        while True:
+            self._chk(lib().pp_polish_debug_tsv(self._h, C.cast(arr, C.c_void_p), p, hi, buf.ctypes.data, MEM_HOST, len(buf),
+                                                C.byref(n), C.byref(nxt)))
+            parts.append(buf[:n.value].tobytes())
+            if nxt.value >= hi or nxt.value == p:
+                return b"".join(parts)
+            p = nxt.value
+
     def set_emit(self, emit):
         """emit: None or an (n_contigs, 2) array of [lo, hi) positions each contig emits (pp_polish_set_emit)."""
         if emit is None:
@@ -866,14 +887,15 @@ class Context:
         return lens, offs
 
     def polish_records(self, contig_off, bases, recs, min_depth=5, fraction_valid=0.5, fraction_invalid=0.2,
-                       positions=False, emit=None, cuts=None):
+                       positions=False, emit=None, cuts=None, debug=False):
         """Host numpy SoA (field names of pp_aln_batch) -> polished bytes, offsets, stats.
         cuts: optional record indices at which the records are cut into several pp_polish_add batches.
         positions: True = the per-position records of --debug; 3 = the records of what the pileup kernel itself decides
-        (test hook: positions with inexact depth shares settled by its interval test are not replayed)."""
+        (test hook: positions with inexact depth shares settled by its interval test are not replayed).
+        debug: True = the job keeps the --debug records on the device for debug_tsv() without fetching them."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
         keep = {k: np.ascontiguousarray(recs[k], dtype=dt) for k, dt in REC_FIELDS}
-        lib().pp_polish_set_debug(self._h, int(positions))
+        lib().pp_polish_set_debug(self._h, int(positions) if positions else int(bool(debug)))
         self.polish_begin(contig_off, bases.ctypes.data, MEM_HOST, min_depth, fraction_valid, fraction_invalid)
         if emit is not None:
             self.set_emit(emit)

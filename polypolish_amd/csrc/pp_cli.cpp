@@ -252,13 +252,13 @@ int main(int argc, char **argv) {
         const char *assembly = P.positional.empty() ? nullptr : P.positional[0];
         std::vector<const char *> sams(P.positional.begin() + (P.positional.empty() ? 0 : 1), P.positional.end());
         if (!assembly) return usage_error("the following required arguments were not provided:\n  <ASSEMBLY>");
-        // Several GPUs polish (contigs / windows of a large contig shard across them) when PP_GPUS=n asks for them; never
-        // with --debug.  On small jobs one GPU is the faster choice end to end: the polish itself is a millisecond per 5 Mbp,
+        // Several GPUs polish (contigs / windows of a large contig shard across them) when PP_GPUS=n asks for them, --debug
+        // included (every context formats the lines of the positions it emits).  On small jobs one GPU is the faster choice end to end: the polish itself is a millisecond per 5 Mbp,
         // what a second context adds is its start-up.  (Until round 4 the CLI switched by itself from 8 GiB of SAM text on;
         // the path has only ever run with several contexts on ONE device -- PP_SHARE_GPU=n, tests on a one-GPU box -- so it
         // stays opt-in until it has been run on a multi-GPU node.)
         const bool few = !getenv("PP_GPUS") && !getenv("PP_SHARE_GPU");
-        std::vector<int> devs = polish_devices(device, opt.debug_path != nullptr || few);
+        std::vector<int> devs = polish_devices(device, few);
         if (devs.size() > 1) {
             std::vector<pp_ctx *> cs(devs.size(), nullptr);
             for (size_t d = 0; d < devs.size(); d++)

@@ -75,75 +75,42 @@ extern "C" void pp_bytes_free(pp_bytes *b) {
     b->len = 0;
 }
 
-// write_debug_line (polish.rs:257-266) + get_debug_line / get_count_str (pileup.rs:137-166) for every
-// position, from the device's per-position records
-static int write_debug_tsv(pp_ctx *ctx, FILE *f, const pp_assembly *a, const pp_aln_batch *batch) {
-    const uint32_t nc = pp_assembly_n_contigs(a);
-    const uint64_t *off = pp_assembly_offsets(a);
-    const uint8_t *bases = pp_assembly_bases(a);
-    const uint64_t G = off[nc];
-    std::vector<double> depth(G ? G : 1);
-    std::vector<uint32_t> ca(G ? G : 1), cc(G ? G : 1), cg(G ? G : 1), ct(G ? G : 1), vt(G ? G : 1), it(G ? G : 1);
-    std::vector<uint8_t> st(G ? G : 1);
-    pp_positions pos{depth.data(), ca.data(), cc.data(), cg.data(), ct.data(), nullptr, vt.data(), it.data(), st.data()};
-    int rc = pp_polish_positions(ctx, &pos);
-    if (rc) return rc;
-    pp_debug_extra x;
-    rc = pp_polish_debug_extra(ctx, &x);
-    if (rc) return rc;
-    // key records and multi-byte winners, grouped by position
-    std::vector<uint64_t> korder(x.n_keys), morder(x.n_multi);
-    for (uint64_t i = 0; i < x.n_keys; i++) korder[i] = i;
-    for (uint64_t i = 0; i < x.n_multi; i++) morder[i] = i;
-    std::sort(korder.begin(), korder.end(), [&](uint64_t l, uint64_t r) { return x.key_pos[l] < x.key_pos[r]; });
-    std::sort(morder.begin(), morder.end(), [&](uint64_t l, uint64_t r) { return x.multi_pos[l] < x.multi_pos[r]; });
-    static const char *STATUS[6] = {"kept", "changed", "low_depth", "none", "multiple", "too_close"};
-    uint64_t ki = 0, mi = 0;
-    std::string line;
-    std::vector<std::string> items;
-    char num[64];
-    for (uint32_t c = 0; c < nc; c++) {
-        const char *name = pp_assembly_name(a, c);
-        for (uint64_t gp = off[c]; gp < off[c + 1]; gp++) {
-            items.clear();
-            if (ca[gp]) { snprintf(num, sizeof num, "Ax%u", ca[gp]); items.push_back(num); }
-            if (cc[gp]) { snprintf(num, sizeof num, "Cx%u", cc[gp]); items.push_back(num); }
-            if (cg[gp]) { snprintf(num, sizeof num, "Gx%u", cg[gp]); items.push_back(num); }
-            if (ct[gp]) { snprintf(num, sizeof num, "Tx%u", ct[gp]); items.push_back(num); }
-            for (; ki < x.n_keys && x.key_pos[korder[ki]] == gp; ki++) {
-                const uint64_t r = korder[ki];
-                std::string key = x.key_len[r] ? std::string((const char *)batch->seq + x.key_off[r], x.key_len[r]) : std::string("-");
-                snprintf(num, sizeof num, "x%u", x.key_count[r]);
-                items.push_back(key + num);
-            }
-            std::sort(items.begin(), items.end());
-            const uint8_t e = x.emit[gp];
-            std::string new_base;
-            if (e == 0) new_base = st[gp] == PP_ST_CHANGED ? std::string("-") : std::string(1, (char)bases[gp]);
-            else if (e < 0x80) new_base = std::string(1, (char)e);
-            else {
-                while (mi < x.n_multi && x.multi_pos[morder[mi]] < gp) mi++;
-                if (mi < x.n_multi && x.multi_pos[morder[mi]] == gp)
-                    new_base = std::string((const char *)batch->seq + x.multi_off[morder[mi]], x.multi_len[morder[mi]]);
-            }
-            line.assign(name);
-            snprintf(num, sizeof num, "\t%llu\t%c\t%.1f\t%u\t%u\t", (unsigned long long)(gp - off[c]), (char)bases[gp],
-                     depth[gp], it[gp], vt[gp]);
-            line += num;
-            for (size_t i = 0; i < items.size(); i++) { if (i) line += ','; line += items[i]; }
-            line += '\t';
-            line += STATUS[st[gp] < 6 ? st[gp] : 0];
-            line += '\t';
-            line += new_base;
-            line += '\n';
-            if (fwrite(line.data(), 1, line.size(), f) != line.size()) {
-                pp_debug_extra_free(&x);
-                return pp_ctx_set_error_(ctx, PP_ERR_QUIT, "unable to write to the --debug file");
-            }
-        }
+extern "C" void *pp_host_pinned_alloc_(pp_ctx *ctx, uint64_t bytes);
+extern "C" void pp_host_pinned_free_(void *p);
+
+// write_debug_line (polish.rs:257-266) for the positions [lo, hi) of ctx's job: formatted on its device (pp_polish_debug_tsv,
+// pp_k_debug.h) a chunk at a time into two pinned buffers in turn -- the fwrite of one chunk runs on a helper thread while
+// the next one is formatted and copied out.  Host memory: two chunks, whatever the TSV's size.
+static int write_debug_tsv(pp_ctx *ctx, FILE *f, const std::vector<const char *> &names, uint64_t lo, uint64_t hi) {
+    constexpr uint64_t CHUNK = 32ull << 20;
+    uint8_t *buf[2] = {nullptr, nullptr};
+    bool pinned[2] = {false, false};
+    for (int k = 0; k < 2; k++) {
+        buf[k] = (uint8_t *)pp_host_pinned_alloc_(ctx, CHUNK);
+        pinned[k] = buf[k] != nullptr;
+        if (!buf[k]) buf[k] = (uint8_t *)malloc(CHUNK);
     }
-    pp_debug_extra_free(&x);
-    return PP_OK;
+    int rc = buf[0] && buf[1] ? PP_OK : pp_ctx_set_error_(ctx, PP_ERR_HIP, "out of host memory for the --debug file");
+    std::future<bool> pending;  // the fwrite of the chunk before
+    auto written = [&]() { return !pending.valid() || pending.get(); };
+    for (uint64_t p = lo; rc == PP_OK && p < hi;) {
+        uint8_t *const b = buf[0];
+        uint64_t n = 0, next = p;
+        rc = pp_polish_debug_tsv(ctx, names.data(), p, hi, b, PP_MEM_HOST, CHUNK, &n, &next);
+        if (rc == PP_OK && next == p) rc = pp_ctx_set_error_(ctx, PP_ERR_HIP, "the --debug formatter made no progress");
+        if (!written() && rc == PP_OK) rc = pp_ctx_set_error_(ctx, PP_ERR_QUIT, "unable to write to the --debug file");
+        if (rc) break;
+        if (n) pending = std::async(std::launch::async, [f, b, n] { return fwrite(b, 1, n, f) == n; });
+        std::swap(buf[0], buf[1]);
+        std::swap(pinned[0], pinned[1]);
+        p = next;
+    }
+    if (!written() && rc == PP_OK) rc = pp_ctx_set_error_(ctx, PP_ERR_QUIT, "unable to write to the --debug file");
+    for (int k = 0; k < 2; k++) {
+        if (pinned[k]) pp_host_pinned_free_(buf[k]);
+        else free(buf[k]);
+    }
+    return rc;
 }
 
 static int polish_files_impl(pp_ctx *const *ctxs, int n_ctx, const char *assembly, const char *const *sams, int n_sams,
@@ -291,7 +258,6 @@ static int polish_files_impl(pp_ctx *const *ctxs, int n_ctx, const char *assembl
     pp_ctx *const ctx = ctxs[0];  // carries the error text
     if (!ctx || !assembly || !opt || !fasta || (n_sams > 0 && !sams)) return PP_ERR_ARG;
     const bool multi = n_ctx > 1;
-    if (multi && opt->debug_path) return set_err(ctx, PP_ERR_ARG, "--debug needs a single GPU");
     fasta->data = nullptr;
     fasta->len = 0;
     // resume_log_at >= 0: the second look at an input the device tokenizer handed back (a defect in the text, or bytes
@@ -326,7 +292,7 @@ static int polish_files_impl(pp_ctx *const *ctxs, int n_ctx, const char *assembl
     // Several contexts: every GPU uploads and tokenizes its own slice of each file (`sharded`), so a byte of text crosses
     // PCIe once; the host ingest (PP_DEVICE_INGEST=0, or a file the tokenizer handed back) parses once and sends every
     // context the records that reach its units.
-    const bool dev_ingest = !host_ingest_only && !(getenv("PP_DEVICE_INGEST") && atoi(getenv("PP_DEVICE_INGEST")) == 0) && !opt->debug_path;
+    const bool dev_ingest = !host_ingest_only && !(getenv("PP_DEVICE_INGEST") && atoi(getenv("PP_DEVICE_INGEST")) == 0);
     if (dev_ingest)
         for (int i = 0; i < n_sams; i++) pph::prefetch_file(sams[i], ctx);
     struct DropPrefetched { const void *owner; ~DropPrefetched() { pph::prefetch_drop_all(owner); } } drop_prefetched{ctx};
@@ -372,16 +338,16 @@ static int polish_files_impl(pp_ctx *const *ctxs, int n_ctx, const char *assembl
     // (every way out of this function: the helper joined first, then the buffer released unless it went to the caller)
     struct OutGuard { std::thread &t; uint8_t *&p; ~OutGuard() { if (t.joinable()) t.join(); free(p); } } out_guard{out_toucher, out};
     // load_alignments, polish.rs:109-134 -- by the device tokenizer (pp_tokenize.hip), or on the host (multi-threaded
-    // parse) with PP_DEVICE_INGEST=0 and with --debug (the TSV needs the read bytes on the host)
+    // parse) with PP_DEVICE_INGEST=0
     log("Loading alignments\n");
     pp_ingest *g = nullptr;
     pp_dev_ingest *dg = nullptr;
     std::vector<pp_dev_ingest *> dgs((size_t)(multi && dev_ingest ? n_ctx : 0), nullptr);  // sharded ingest: one per context
-    // Host ingest without --debug: one ingest object per SAM file, and (one context) the batch of file i goes to the device
-    // (pp_polish_begin + pp_polish_add on a helper thread) while file i+1 is parsed -- the reference streams its files
-    // one after the other as well (alignment.rs:238-265).  --debug keeps ONE host batch (the TSV indexes its SEQ bytes).
-    // Several contexts: the files' batches wait until the plan is known, then every context is sent its part.
-    const bool per_file = !dev_ingest && !opt->debug_path && (multi || !(getenv("PP_STREAM_ADDS") && atoi(getenv("PP_STREAM_ADDS")) == 0));
+    // Host ingest: one ingest object per SAM file, and (one context) the batch of file i goes to the device (pp_polish_begin +
+    // pp_polish_add on a helper thread) while file i+1 is parsed -- the reference streams its files one after the other as
+    // well (alignment.rs:238-265).  Several contexts: the files' batches wait until the plan is known, then every context is
+    // sent its part.
+    const bool per_file = !dev_ingest && (multi || !(getenv("PP_STREAM_ADDS") && atoi(getenv("PP_STREAM_ADDS")) == 0));
     const bool stream_adds = per_file && !multi;
     std::vector<pp_ingest *> gs;
     std::vector<std::future<int>> pending;  // the upload of the file before
@@ -590,21 +556,26 @@ static int polish_files_impl(pp_ctx *const *ctxs, int n_ctx, const char *assembl
         }
         fputs("name\tpos\tbase\tdepth\tinvalid\tvalid\tpileup\tstatus\tnew_base\n", dbg);
     }
-    pp_polish_set_debug(ctx, dbg ? 1 : 0);
+    for (int d = 0; d < n_ctx; d++) pp_polish_set_debug(ctxs[d], dbg ? 1 : 0);
+    std::vector<const char *> names(nc);
+    for (uint32_t c = 0; c < nc; c++) names[c] = pp_assembly_name(a, c);
     uint64_t total = 0;
     bool direct_fetch = false;
     std::vector<uint8_t> polished(1);
     std::vector<uint64_t> out_off(nc + 1);
     std::vector<pp_contig_stats> stats(nc);
     if (!multi) {
-        if (!begun) {  // one batch (device tokenizer, --debug), or no SAM files at all
+        if (!begun) {  // one batch (device tokenizer), or no SAM files at all
             rc = pp_polish_begin(ctx, nc, off, pp_assembly_bases(a), PP_MEM_HOST, &prm);
             if (rc == PP_OK && (dev_ingest || g)) rc = pp_polish_add(ctx, &batch, dev_ingest ? PP_MEM_DEVICE : PP_MEM_HOST);
         }
         if (rc == PP_OK) rc = pp_polish_finish(ctx);
         lap("uploaded + polished on device");
-        if (rc == PP_OK && dbg) rc = write_debug_tsv(ctx, dbg, a, &batch);
-        if (dbg) fclose(dbg);
+        if (rc == PP_OK && dbg) {
+            rc = write_debug_tsv(ctx, dbg, names, 0, off[nc]);
+            lap("--debug file written");
+        }
+        if (dbg && fclose(dbg) && rc == PP_OK) rc = set_err(ctx, PP_ERR_QUIT, "unable to write to the --debug file");
         pp_polish_set_debug(ctx, 0);
         if (rc == PP_OK) rc = pp_polish_result_size(ctx, &total);
         // offsets and statistics now; the bytes go straight into the FASTA buffer below (contig by contig) when that is a
@@ -791,6 +762,23 @@ static int polish_files_impl(pp_ctx *const *ctxs, int n_ctx, const char *assembl
             }
         }
         lap("uploaded + polished on the devices");
+        // --debug: the plan's units in order (contig by contig, a tiled contig's windows in position order), each formatted by
+        // the context that emits it -- neighbouring units of one context in one go
+        for (uint32_t u = 0; dbg && rc == PP_OK && u < plan->n_units;) {
+            const uint32_t r = plan->rank[u];
+            const uint64_t lo = off[plan->contig[u]] + plan->lo[u];
+            uint64_t hi = off[plan->contig[u]] + plan->hi[u];
+            for (u++; u < plan->n_units && plan->rank[u] == r && off[plan->contig[u]] + plan->lo[u] == hi; u++) hi = off[plan->contig[u]] + plan->hi[u];
+            if (r >= (uint32_t)n_ctx) { rc = set_err(ctx, PP_ERR_HIP, "a unit of the plan names no context"); break; }
+            rc = write_debug_tsv(ctxs[r], dbg, names, lo, hi);
+            if (rc && r) set_err(ctx, rc, pp_last_error(ctxs[r]));
+        }
+        if (dbg) {
+            if (fclose(dbg) && rc == PP_OK) rc = set_err(ctx, PP_ERR_QUIT, "unable to write to the --debug file");
+            dbg = nullptr;
+            lap("--debug file written");
+        }
+        for (int d = 0; d < n_ctx; d++) pp_polish_set_debug(ctxs[d], 0);
         if (rc == PP_OK) {
             std::vector<const uint8_t *> bp((size_t)n_ctx);
             std::vector<const uint64_t *> op((size_t)n_ctx);

@@ -206,6 +206,11 @@ struct pp_ctx {
     pp::DevBuf b_sub_bases;             // ... and its assembly bytes
     size_t cap_ent = 0, cap_scr = 0, cap_multi = 0, cap_out = 0, cap_flag = 0, cap_slabs = 0, cap_ents = 0, cap_keys = 0;  // element capacities of the optimistic buffers
     pp::DevBuf b_dbg_depth, b_dbg_counts, b_dbg_status;
+    bool job_debug = false;             // the finished job kept its per-position records (pp_polish_set_debug before pp_polish_finish)
+    bool dfmt_ready = false;            // ... and the --debug formatter's tables below are built for it (pp_polish_debug_tsv)
+    pp::DevBuf b_dfmt_idx, b_dfmt_rec;  // key records + multi-byte winners grouped by position: per position the end of its entries | record ids
+    pp::DevBuf b_dfmt_names, b_dfmt_noff, b_dfmt_emit;  // contig names (bytes | offsets), emit ranges
+    pp::DevBuf b_dfmt_len, b_dfmt_bsum, b_dfmt_boff, b_dfmt_res, b_dfmt_stage;  // a chunk: line lengths, workgroup sums / offsets, result, staging
 
     // ---- multi-GPU gather (pp_comm.hip) ----
     void *comm = nullptr;  // ncclComm_t

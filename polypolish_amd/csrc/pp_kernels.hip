@@ -45,6 +45,7 @@
 #include "pp_k_tile.h"
 #include "pp_k_exact.h"
 #include "pp_k_emit.h"
+#include "pp_k_debug.h"
 #include <hip/hip_ext.h>
 
 // =============================================================================================
@@ -219,6 +220,8 @@ extern "C" int pp_polish_begin(pp_ctx *ctx, uint32_t n_contigs, const uint64_t *
     }
     ctx->job_open = true;
     ctx->job_done = false;
+    ctx->job_debug = false;
+    ctx->dfmt_ready = false;
     ctx->have_batch = false;
     ctx->batch_borrowed = false;
     ctx->acc_n = ctx->acc_seq = ctx->acc_cig = 0;
@@ -1129,6 +1132,8 @@ extern "C" int pp_polish_finish(pp_ctx *ctx) {
     if (int rdy = pp_ctx_wait(ctx)) return rdy;
     if (!ctx->job_open) return ctx->fail(PP_ERR_ARG, "pp_polish_finish without pp_polish_begin");
     ctx->last_dev_error = ~0ull;
+    ctx->job_debug = false;
+    ctx->dfmt_ready = false;
     PP_HIPCHK(ctx, hipSetDevice(ctx->device));
     const uint64_t G = ctx->G;
     const uint32_t nc = ctx->n_contigs;
@@ -1238,6 +1243,7 @@ extern "C" int pp_polish_finish(pp_ctx *ctx) {
         ctx->last_times.n_passes = (uint64_t)attempt + 1;
     }
     ctx->job_done = true;
+    ctx->job_debug = ctx->debug;
     ctx->job_open = false;
     return PP_OK;
 }
@@ -1333,6 +1339,146 @@ extern "C" void pp_debug_extra_free(pp_debug_extra *d) {
     free(d->emit); free(d->multi_pos); free(d->multi_len); free(d->multi_off);
     free(d->key_pos); free(d->key_len); free(d->key_count); free(d->key_off);
     memset(d, 0, sizeof *d);
+}
+
+// ---- the --debug TSV on the device (pp_k_debug.h) ----------------------------------------------------------------------
+constexpr uint64_t DFMT_STAGE = 64ull << 20;     // device staging of a chunk that goes to host memory
+constexpr uint64_t DFMT_MAX_POS = 1ull << 22;    // positions per chunk (and so the room of its length array)
+
+// the formatter's tables of the finished job: contig names and emit ranges on the device, key records and multi-byte winners
+// grouped by position
+static int dfmt_prepare(pp_ctx *ctx, const char *const *names) {
+    if (ctx->dfmt_ready) return PP_OK;
+    hipStream_t st = ctx->stream;
+    const uint32_t nc = ctx->n_contigs;
+    const uint64_t G = ctx->G;
+    std::vector<uint64_t> noff((size_t)nc + 1, 0);
+    for (uint32_t c = 0; c < nc; c++) {
+        if (!names[c]) return ctx->fail(PP_ERR_ARG, "pp_polish_debug_tsv: contig name %u is NULL", c);
+        noff[c + 1] = noff[c] + strlen(names[c]);
+    }
+    std::vector<uint8_t> nb(noff[nc] ? noff[nc] : 1);
+    for (uint32_t c = 0; c < nc; c++) memcpy(nb.data() + noff[c], names[c], noff[c + 1] - noff[c]);
+    int rc;
+    if ((rc = dev_ensure(ctx, ctx->b_dfmt_names, nb.size())) || (rc = dev_ensure(ctx, ctx->b_dfmt_noff, noff.size() * 8)) ||
+        (rc = dev_ensure(ctx, ctx->b_dfmt_emit, (size_t)nc * 8)))
+        return rc;
+    PP_HIPCHK(ctx, hipMemcpyAsync(ctx->b_dfmt_names.p, nb.data(), nb.size(), hipMemcpyHostToDevice, st));
+    PP_HIPCHK(ctx, hipMemcpyAsync(ctx->b_dfmt_noff.p, noff.data(), noff.size() * 8, hipMemcpyHostToDevice, st));
+    if (!ctx->emit.empty()) PP_HIPCHK(ctx, hipMemcpyAsync(ctx->b_dfmt_emit.p, ctx->emit.data(), (size_t)nc * 8, hipMemcpyHostToDevice, st));
+    const uint64_t nk = ctx->n_keys, nm = ctx->n_multi, nr = nk + nm;
+    if (nr >= 0xFFFFFFFFull) return ctx->fail(PP_ERR_LIMIT, "more than 2^32-1 key records in one --debug job");
+    if ((rc = dev_ensure(ctx, ctx->b_dfmt_idx, G * 4)) || (rc = dev_ensure(ctx, ctx->b_dfmt_rec, nr * 4))) return rc;
+    PP_HIPCHK(ctx, hipMemsetAsync(ctx->b_dfmt_idx.p, 0, G * 4, st));
+    if (nr) {
+        const uint64_t per_blk = 256ull * DFMT_SCAN_PER, nb_scan = (G + per_blk - 1) / per_blk;
+        if ((rc = dev_ensure(ctx, ctx->b_dfmt_bsum, nb_scan * 8)) || (rc = dev_ensure(ctx, ctx->b_dfmt_boff, (nb_scan + 1) * 8))) return rc;
+        const unsigned g = (unsigned)((nr + 255) / 256);
+        u32 *idx = (u32 *)ctx->b_dfmt_idx.p;
+        hipLaunchKernelGGL(k_dfmt_count, dim3(g), dim3(256), 0, st, (const KeyRec *)ctx->b_keys.p, (u32)nk, (const MultiEnt *)ctx->b_multi.p,
+                           (u32)nm, (u64)G, idx);
+        hipLaunchKernelGGL(k_dfmt_bsum, dim3((unsigned)nb_scan), dim3(256), 0, st, (const u32 *)idx, (u64)G, (u64 *)ctx->b_dfmt_bsum.p);
+        hipLaunchKernelGGL(k_dfmt_scan1, dim3(1), dim3(1024), 0, st, (const u64 *)ctx->b_dfmt_bsum.p, (u64)nb_scan, (u64 *)ctx->b_dfmt_boff.p);
+        hipLaunchKernelGGL(k_dfmt_apply, dim3((unsigned)nb_scan), dim3(256), 0, st, idx, (u64)G, (const u64 *)ctx->b_dfmt_boff.p);
+        hipLaunchKernelGGL(k_dfmt_scatter, dim3(g), dim3(256), 0, st, (const KeyRec *)ctx->b_keys.p, (u32)nk, (const MultiEnt *)ctx->b_multi.p,
+                           (u32)nm, (u64)G, idx, (u32 *)ctx->b_dfmt_rec.p);
+        PP_HIPCHK(ctx, hipGetLastError());
+    }
+    ctx->dfmt_ready = true;
+    return PP_OK;
+}
+
+extern "C" int pp_polish_debug_tsv(pp_ctx *ctx, const char *const *contig_names, uint64_t pos_lo, uint64_t pos_hi, uint8_t *out,
+                                   int out_mem, uint64_t cap, uint64_t *len, uint64_t *pos_next) {
+    if (!ctx) return PP_ERR_ARG;
+    if (len) *len = 0;
+    if (pos_next) *pos_next = pos_lo;
+    if (!ctx->job_done || !ctx->job_debug || !ctx->b_dbg_depth.p)
+        return ctx->fail(PP_ERR_ARG, "the --debug TSV needs pp_polish_set_debug(1) before pp_polish_finish");
+    if (!contig_names || !out || !len || !pos_next || cap == 0 || (out_mem != PP_MEM_HOST && out_mem != PP_MEM_DEVICE))
+        return ctx->fail(PP_ERR_ARG, "pp_polish_debug_tsv: null argument, cap 0 or unknown memory kind");
+    if (pos_lo > pos_hi || pos_hi > ctx->G)
+        return ctx->fail(PP_ERR_ARG, "pp_polish_debug_tsv: positions [%llu, %llu) are not inside the assembly",
+                         (unsigned long long)pos_lo, (unsigned long long)pos_hi);
+    PP_HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (int rc = dfmt_prepare(ctx, contig_names)) return rc;
+    hipStream_t st = ctx->stream;
+    DfmtJob J;
+    J.depth = (const double *)ctx->b_dbg_depth.p;
+    J.counts = (const u32 *)ctx->b_dbg_counts.p;
+    J.status = (const u8 *)ctx->b_dbg_status.p;
+    J.code = (const u8 *)ctx->b_code.p;
+    J.bases = ctx->d_bases;
+    J.seq = ctx->have_batch ? ctx->dbatch.seq : nullptr;
+    J.contig_off = (const u64 *)ctx->b_contig_off.p;
+    J.nc = ctx->n_contigs;
+    J.n_keys = (u32)ctx->n_keys;
+    J.names = (const u8 *)ctx->b_dfmt_names.p;
+    J.name_off = (const u64 *)ctx->b_dfmt_noff.p;
+    J.emit = ctx->emit.empty() ? nullptr : (const u32 *)ctx->b_dfmt_emit.p;
+    J.keys = (const KeyRec *)ctx->b_keys.p;
+    J.multi = (const MultiEnt *)ctx->b_multi.p;
+    J.rec_end = (const u32 *)ctx->b_dfmt_idx.p;
+    J.rec = (const u32 *)ctx->b_dfmt_rec.p;
+    J.G = ctx->G;
+    const bool host = out_mem == PP_MEM_HOST;
+    int rc;
+    if (host && (rc = dev_ensure(ctx, ctx->b_dfmt_stage, (size_t)std::min<uint64_t>(cap, DFMT_STAGE)))) return rc;
+    if ((rc = dev_ensure(ctx, ctx->b_dfmt_res, 16))) return rc;
+    uint64_t written = 0, p = pos_lo;
+    // Chunks of at most DFMT_MAX_POS positions (and no more than the room could take at 16 bytes a line -- a line has 22 at
+    // least): size pass, scan of the workgroups' sums, write pass, then how far it got.  To host memory through the staging
+    // buffer, DFMT_STAGE bytes at a time.
+    while (p < pos_hi && written < cap) {
+        const uint64_t caller_room = cap - written;
+        const uint64_t room = host ? std::min<uint64_t>(caller_room, DFMT_STAGE) : caller_room;
+        const uint32_t N = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(pos_hi - p, room / 16 + 1), DFMT_MAX_POS);
+        const uint32_t nb = (N + DFMT_THREADS - 1) / DFMT_THREADS;
+        if ((rc = dev_ensure(ctx, ctx->b_dfmt_len, (size_t)N * 4)) || (rc = dev_ensure(ctx, ctx->b_dfmt_bsum, (size_t)nb * 8)) ||
+            (rc = dev_ensure(ctx, ctx->b_dfmt_boff, ((size_t)nb + 1) * 8)))
+            return rc;
+        u8 *dst = host ? (u8 *)ctx->b_dfmt_stage.p : out + written;
+        PP_HIPCHK(ctx, hipMemsetAsync(ctx->b_dfmt_res.p, 0, 16, st));
+        hipLaunchKernelGGL(k_dfmt_len, dim3(nb), dim3(DFMT_THREADS), 0, st, J, (u64)p, N, (u32 *)ctx->b_dfmt_len.p, (u64 *)ctx->b_dfmt_bsum.p);
+        hipLaunchKernelGGL(k_dfmt_scan1, dim3(1), dim3(1024), 0, st, (const u64 *)ctx->b_dfmt_bsum.p, (u64)nb, (u64 *)ctx->b_dfmt_boff.p);
+        hipLaunchKernelGGL(k_dfmt_write, dim3(nb), dim3(DFMT_THREADS), 0, st, J, (u64)p, N, (const u32 *)ctx->b_dfmt_len.p,
+                           (const u64 *)ctx->b_dfmt_boff.p, (u64)room, dst, (u64 *)ctx->b_dfmt_res.p);
+        PP_HIPCHK(ctx, hipGetLastError());
+        uint64_t res[2] = {0, 0};
+        PP_HIPCHK(ctx, hipMemcpyAsync(res, ctx->b_dfmt_res.p, 16, hipMemcpyDeviceToHost, st));
+        PP_HIPCHK(ctx, hipStreamSynchronize(st));
+        const uint64_t n_fit = res[0], bytes = res[1];
+        if (bytes == 0 && n_fit < N) {  // the next line does not fit
+            if (room == caller_room && written == 0)
+                return ctx->fail(PP_ERR_ARG, "pp_polish_debug_tsv: %llu bytes of room do not take the line of position %llu",
+                                 (unsigned long long)cap, (unsigned long long)(p + n_fit));
+            if (room == caller_room) {
+                p += n_fit;
+                break;
+            }
+            return ctx->fail(PP_ERR_LIMIT, "a --debug line longer than %llu bytes", (unsigned long long)DFMT_STAGE);
+        }
+        if (host && bytes) {
+            PP_HIPCHK(ctx, hipMemcpyAsync(out + written, ctx->b_dfmt_stage.p, bytes, hipMemcpyDeviceToHost, st));
+            PP_HIPCHK(ctx, hipStreamSynchronize(st));
+        }
+        written += bytes;
+        p += n_fit;
+        if (n_fit < N && room == caller_room) break;  // the caller's buffer is full
+    }
+    *len = written;
+    *pos_next = p;
+    return PP_OK;
+}
+
+// (internal, the drivers) pinned host memory for the --debug TSV's chunks
+extern "C" void *pp_host_pinned_alloc_(pp_ctx *ctx, uint64_t bytes) {
+    void *p = nullptr;
+    if (!ctx || pp_ctx_wait(ctx) != PP_OK || hipSetDevice(ctx->device) != hipSuccess) return nullptr;
+    return hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess ? p : nullptr;
+}
+extern "C" void pp_host_pinned_free_(void *p) {
+    if (p) (void)hipHostFree(p);
 }
 
 extern "C" int pp_ctx_set_profiling(pp_ctx *ctx, int enable) {
@@ -1433,6 +1579,8 @@ extern "C" void pp_ctx_destroy(pp_ctx *ctx) {
                      &ctx->b_win_heavy, &ctx->b_hslab, &ctx->b_sub_bases,
                      &ctx->b_runs, &ctx->b_first, &ctx->b_xcnt, &ctx->b_xent, &ctx->b_need_win, &ctx->b_win_lo, &ctx->b_win_hi, &ctx->b_later,
                      &ctx->b_out, &ctx->b_emit_done, &ctx->b_wincoarse, &ctx->b_dbg_depth, &ctx->b_dbg_counts, &ctx->b_dbg_status,
+                     &ctx->b_dfmt_idx, &ctx->b_dfmt_rec, &ctx->b_dfmt_names, &ctx->b_dfmt_noff, &ctx->b_dfmt_emit, &ctx->b_dfmt_len,
+                     &ctx->b_dfmt_bsum, &ctx->b_dfmt_boff, &ctx->b_dfmt_res, &ctx->b_dfmt_stage,
                      &ctx->f_refend[0], &ctx->f_refend[1], &ctx->f_pass[0], &ctx->f_pass[1], &ctx->f_orient, &ctx->f_poisoned,
                      &ctx->f_insert, &ctx->f_list, &ctx->f_blkcnt};
     for (DevBuf *b : all) dev_free(*b);

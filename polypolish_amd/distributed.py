@@ -38,15 +38,51 @@ def gather_objects(polished: bytes, offs, rank: int, world: int):
     return [g[0] for g in got], [g[1] for g in got]
 
 
+DEBUG_HEADER = b"name\tpos\tbase\tdepth\tinvalid\tvalid\tpileup\tstatus\tnew_base\n"  # src/polish.rs:230-245
+
+
+def write_debug_parts(path, plan, rank, world, fmt, at=len(DEBUG_HEADER)):
+    """--debug across ranks: every rank formats the lines of the plan's units it owns (`fmt(lo, hi)` -> bytes, positions of
+    the concatenated assembly), the ranks' lengths are all-gathered, and every rank writes its parts with pwrite at their
+    places behind the first `at` bytes of the file (rank 0 created it and wrote the header).  Units come contig by contig,
+    a tiled contig's windows in position order: the file is in assembly order, every position once."""
+    import os
+    off = np.asarray(plan.contig_off, dtype=np.uint64)
+    units = range(len(plan.unit_rank))
+    mine = {u: fmt(int(off[plan.unit_contig[u]] + plan.unit_lo[u]), int(off[plan.unit_contig[u]] + plan.unit_hi[u]))
+            for u in units if int(plan.unit_rank[u]) == rank}
+    lens = {u: len(b) for u, b in mine.items()}
+    if world > 1:
+        import torch.distributed as dist
+        seen = [None] * world
+        dist.all_gather_object(seen, lens)
+        for s in seen:
+            lens.update(s)
+    where = {}
+    for u in units:
+        where[u] = at
+        at += lens.get(u, 0)
+    fd = os.open(path, os.O_WRONLY)
+    try:
+        for u, b in mine.items():
+            view, o = memoryview(b), where[u]
+            while len(view):
+                k = os.pwrite(fd, view, o)
+                view, o = view[k:], o + k
+    finally:
+        os.close(fd)
+
+
 def polish_sharded(engine, names, descs, contig_off, bases, recs, rank, world, gather=None, min_window=0, locate=None,
-                   **params):
+                   after=None, **params):
     """Sharded polish.  `engine(contig_off, bases, recs, emit=..., **params)` polishes the records it is given restricted
     to the emit ranges and returns {"polished": bytes, "offsets": array} (Context.polish_records on a GPU; the oracle in
     the CPU tests).  A rank gives it only the records that reach its units (pp_shard_split).  `gather(polished, offsets)`
     collects every rank's result on rank 0 (default: gloo objects).  `locate(exc)` (optional) returns the rank-local
     number of the record an engine failure is about: the ranks then agree on the job's FIRST bad record (the reference
-    streams, so that is the one it reports) and all of them raise.  Rank 0 returns the FASTA text of the whole assembly
-    (src/polish.rs:196-203), other ranks None."""
+    streams, so that is the one it reports) and all of them raise.  `after(plan)` (optional) runs on every rank once every
+    engine has succeeded, before the gather (the --debug TSV: write_debug_parts).  Rank 0 returns the FASTA text of the
+    whole assembly (src/polish.rs:196-203), other ranks None."""
     import polypolish_amd as pp
     contig_off = np.asarray(contig_off, dtype=np.uint64)
     n_contigs = len(contig_off) - 1
@@ -72,6 +108,8 @@ def polish_sharded(engine, names, descs, contig_off, bases, recs, rank, world, g
             raise pp.PolypolishError(s[3], s[2])
     elif failure is not None:
         raise failure[1]
+    if after is not None:
+        after(plan)
     if gather is None:
         gather = lambda b, o: gather_objects(b, o, rank, world)  # noqa: E731
     all_bytes, all_offs = gather(res["polished"], res["offsets"])
@@ -91,10 +129,12 @@ def main(argv=None):
         python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
             -m polypolish_amd.distributed polish [options] assembly.fasta a_1.sam a_2.sam > polished.fasta
 
-    Options as the reference's (src/main.rs:78-108) except --debug.  Every rank runs the host ingest (the 1/k shares
-    are fixed before anything is partitioned), polishes its contigs / windows on its own GPU, the polished bytes go
-    to rank 0 over RCCL and rank 0 prints the FASTA.  PP_SHARE_GPU=1 (testing on a one-GPU box): all ranks use GPU 0
-    and the bytes travel over gloo."""
+    Options as the reference's (src/main.rs:78-108).  Every rank runs the host ingest (the 1/k shares are fixed before
+    anything is partitioned), polishes its contigs / windows on its own GPU, the polished bytes go to rank 0 over RCCL
+    and rank 0 prints the FASTA.  --debug PATH: rank 0 creates the file and writes its header before polishing; every
+    rank formats the TSV lines of the positions it emits on its GPU (Context.debug_tsv), the ranks' lengths are
+    all-gathered and every rank writes its lines at their offset (pwrite) -- no TSV travels between ranks.
+    PP_SHARE_GPU=1 (testing on a one-GPU box): all ranks use GPU 0 and the bytes travel over gloo."""
     import argparse
     import ctypes as C
     import os
@@ -109,6 +149,7 @@ def main(argv=None):
     ap.add_argument("-m", "--max_errors", type=int, default=10)
     ap.add_argument("-d", "--min_depth", type=int, default=5)
     ap.add_argument("--careful", action="store_true")
+    ap.add_argument("--debug", default=None)
     ap.add_argument("assembly")
     ap.add_argument("sam", nargs="*")
     a = ap.parse_args(argv)
@@ -128,7 +169,27 @@ def main(argv=None):
         dist.init_process_group("gloo")  # control plane only: the unique id and (shared-GPU runs) the bytes
     try:
         names, descs, off, bases, recs, _ = pp.ingest(a.assembly, a.sam, max_errors=a.max_errors, careful=a.careful)
+        after = None
+        if a.debug:  # create_debug_file, src/polish.rs:230-245: created (header written) before polishing, by rank 0
+            created = True
+            if rank == 0:
+                try:
+                    with open(a.debug, "wb") as f:
+                        f.write(DEBUG_HEADER)
+                except OSError:
+                    created = False
+            if world > 1:
+                flag = [created]
+                dist.broadcast_object_list(flag, src=0)
+                created = flag[0]
+            if not created:
+                if rank != 0:
+                    raise SystemExit(1)
+                raise pp.PolypolishError(pp.ERR_QUIT, f'unable to create "{a.debug}"')
         ctx = pp.Context(dev)
+        if a.debug:
+            def after(plan):
+                write_debug_parts(a.debug, plan, rank, world, lambda lo, hi: ctx.debug_tsv(names, lo, hi))
         gather = None
         if world > 1 and not share:
             ident = [pp.comm_unique_id() if rank == 0 else None]
@@ -148,7 +209,8 @@ def main(argv=None):
             rec, kind = C.c_uint64(), C.c_uint32()
             return int(rec.value) if pp.lib().pp_polish_error_record(ctx._h, C.byref(rec), C.byref(kind)) else None
         out = polish_sharded(ctx.polish_records, names, descs, off, bases, recs, rank, world, gather=gather, locate=locate,
-                             min_depth=a.min_depth, fraction_valid=a.fraction_valid, fraction_invalid=a.fraction_invalid)
+                             after=after, min_depth=a.min_depth, fraction_valid=a.fraction_valid,
+                             fraction_invalid=a.fraction_invalid, debug=bool(a.debug))
     except pp.PolypolishError as e:
         sys.stderr.write(f"\nError: {e.msg}\n")
         raise SystemExit(101 if e.code == pp.ERR_PANIC else 1)
