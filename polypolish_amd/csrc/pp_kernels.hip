@@ -999,6 +999,7 @@ PrepdArgs PA;
         ctx->h_meta = nullptr;
         ctx->h_meta_words = 0;
         PP_HIPCHK(ctx, hipHostMalloc((void **)&ctx->h_meta, (meta_words + 64) * 8, hipHostMallocCoherent));  // (fine-grained: what the kernel writes is seen while it runs -- the polling below -- whatever HIP_HOST_COHERENT says)
+        memset(ctx->h_meta, 0, (meta_words + 64) * 8);
         ctx->h_meta_words = meta_words + 64;
         PP_HIPCHK(ctx, hipHostGetDevicePointer((void **)&ctx->d_hmeta, ctx->h_meta, 0));
     }
@@ -1021,6 +1022,13 @@ PrepdArgs PA;
     const bool sync_by_poll = !env_sync_wait && d_hmeta;
     uint32_t emit_round = 0;
     auto launch_emit = [&]() {
+    // The words behind the copy are cleared before every launch: where this job polls, an earlier job with more contigs left a
+    // word of its own copy (a contig's stats, a heavy-window ticket) that could equal this launch's serial -- the host would take
+    // that job's metadata for this one's.  (The serial before was consumed by its read-back: nothing writes here until this launch.)
+    if (d_hmeta) {
+        ctx->h_meta[meta_words] = 0;
+        __atomic_store_n(&ctx->h_meta[meta_words + 1], 0ull, __ATOMIC_RELEASE);
+    }
     timer_begin(ctx, "emit");
     EmitTail Z{};
     Z.meta = d_meta; Z.words = (u32)meta_words; Z.host = d_hmeta; Z.serial = ++ctx->emit_serial; Z.done = (u64 *)ctx->b_emit_done.p;
