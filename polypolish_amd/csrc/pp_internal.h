@@ -103,10 +103,54 @@ enum DevErr : uint32_t {
                             // -> the host runs the job over the bucketing path (always reported at the largest index, so
                             // that the error of any record wins)
     DE_SEQ_RANGE = 18,      // a record's SEQ bytes do not lie inside the batch's seq array (seq_off + seq_len > seq_bytes)
-    DE_GW_HINT = 17,        // k_tile: the instance the host launched does not take the job's longest fast-class read (meta
-                            // word 9) -> the host reruns with the one that does (same index as DE_MIRROR_ORDER)
+    DE_GW_HINT = 17,        // k_tile: the instance the host launched does not take the job's longest fast-class read
+                            // (MW_MAXLEN) -> the host reruns with the one that does (same index as DE_MIRROR_ORDER)
 };
 
+
+// ---- the job's metadata block ---------------------------------------------------------------
+// The one block of u64 words the device hands to the host per job: k_meta_init sets word MW_STATUS to "no error" (all ones) and
+// every other word to zero, the kernels count into it, k_emit's last workgroup copies it into pinned host memory (EmitTail,
+// pp_k_emit.h: two more words behind the copy there -- "set up again for the next job" and the launch's serial).
+// A slot marked unused keeps its place: the position of every other word, and the block's size, are part of what k_meta_init
+// and EmitTail see.
+enum MetaWord : uint32_t {
+    MW_STATUS = 0,        // ~0: no error; else (record or window index << 8 | DevErr), combined with atomicMin
+    MW_COUNTERS = 1,      // words 1-2: four u32 counters, see MetaCounter
+    MW_ITEMS = 3,         // work items of the job (bucketing path: k_scan's total; direct path: k_winplan's count)
+    MW_SCRATCH = 4,       // unused (replay scratch elements; they are counted in MW_SCR_NEED as the positions are listed)
+    MW_OUT_BYTES = 5,     // polished bytes
+    MW_REPLAY_ITEMS = 6,  // ordered replay items (k_exact2's cursor)
+    //             7         unused
+    MW_KEYS = 8,          // key records (--debug)
+    MW_MAXLEN = 9,        // the job's longest fast-class read (u32; picks k_tile's instance, DE_GW_HINT)
+    MW_SCR_NEED = 10,     // replay scratch the listed positions need (counted past the capacity too)
+    //             11        unused
+    MW_X_NEED = 12,       // direct path: the most extras any window needs (DE_CAPACITY: the host grows the windows' room)
+    MW_N_NEED = 13,       // direct path: windows that need a replay (k_tile lists them for k_xmat)
+    MW_XMAT_ITEMS = 14,   // direct path: work items k_xmat has written out (its cursor, counted past the capacity too)
+    //             15        unused
+    MW_CTG_OUT = 16,      // first of the contig output offsets: nc + 1 words, then the statistics, then the heavy-window list
+};
+enum MetaCounter : uint32_t {  // index into the four u32 counters at MW_COUNTERS
+    MC_LISTED = 0,   // positions listed for k_exact (counted past cap_flag too)
+    MC_MULTI = 1,    // multi-byte winners
+    MC_FLAGGED = 2,  // positions flagged in all (listed or left to k_exact2)
+    MC_SLABS = 3,    // tally slabs handed out (one per window with a position for k_exact2)
+};
+// behind the contig offsets: per-contig statistics (ContigStatsDev: 3 words per contig of the run) ...
+constexpr size_t meta_stats_at(size_t nc) { return (size_t)MW_CTG_OUT + nc + 1; }
+// ... then the heavy-window list (HEAVY_WORDS u32: count, windows, arrival tickets)
+constexpr size_t meta_heavy_at(size_t nc) { return meta_stats_at(nc) + 3 * nc; }
+constexpr size_t meta_words(size_t nc) { return meta_heavy_at(nc) + (HEAVY_WORDS + 1) / 2; }
+
+// the host's view of a block that has been read back
+struct MetaView {
+    const uint64_t *w;
+    uint64_t operator[](MetaWord i) const { return w[i]; }
+    uint32_t counter(MetaCounter c) const { return (uint32_t)(w[MW_COUNTERS + c / 2] >> (32 * (c & 1))); }
+    bool ok() const { return w[MW_STATUS] == ~0ull; }
+};
 
 struct DevBuf {
     void *p = nullptr;
@@ -137,7 +181,7 @@ struct pp_ctx {
     bool timer_open = false;
     std::vector<hipEvent_t> event_pool;
     bool debug = false;
-    int debug_level = 0;  // what pp_polish_set_debug was given (3: see run_pipeline)
+    int debug_level = 0;  // what pp_polish_set_debug was given (3: see tile_args, pp_kernels.hip)
     std::vector<pp::KernelTimer> timers;
     pp_kernel_times last_times{};
 
@@ -168,7 +212,7 @@ struct pp_ctx {
     pp::DevBuf b_win_heavy, b_hslab;  // heavy windows: slot + 1 per window (u8) | the helpers' partial tallies
     // ---- the direct path (pp_k_direct.h) ----
     std::vector<uint64_t> wo_runs;      // ends of the runs of the job's window-order mirror (pp_aln_batch.wo_run_end, rebased); empty = not known
-    pp::DevBuf b_runs, b_first, b_xcnt, b_xent, b_need_win, b_win_lo, b_win_hi, b_later;
+    pp::DevBuf b_runs, b_first, b_xcnt, b_xent, b_need_win, b_win_lo, b_win_hi;
     std::vector<uint32_t> runs_on_dev;  // what b_runs holds (identical tables are not uploaded again)
     size_t xcap = 0;                    // room for extras per window (grow-only)
     bool no_direct = false;             // this job is being rerun over the bucketing path (DE_MIRROR_ORDER)
@@ -176,7 +220,7 @@ struct pp_ctx {
     bool trust_all = false;             // pp_ctx_trust_mirrors_: every mirror is taken as the library's own (bench / tests that lay a batch out as the ingests do)
     bool no_wo = false;                 // this job is being rerun without its mirror (it did not stand the check)
     size_t xcap_limit = ~(size_t)0;     // the most room for extras a window of this job can be given (run_pipeline): beyond it, the bucketing path
-    uint32_t maxlen_hint = 0;           // the longest fast-class read of the context's last job (meta word 9): picks k_tile's instance for the next one (DE_GW_HINT)
+    uint32_t maxlen_hint = 0;           // the longest fast-class read of the context's last job (MW_MAXLEN): picks k_tile's instance for the next one (DE_GW_HINT)
     bool last_direct = false;           // the last pass over the pipeline took the direct path
     bool nothing_flagged_last = false;  // the job before had no position flagged for the exact replays (run_pipeline: their launches are then left out until this job's metadata say otherwise)
     std::vector<uint32_t> emit;  // pp_polish_set_emit: (lo, hi) per contig, empty = everything

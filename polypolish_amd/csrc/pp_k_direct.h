@@ -16,7 +16,7 @@
 //   k_tile     (pp_k_tile.h, DIRECT) the window's mirror entries through the plain class, then its extras like any items
 //   k_xmat     the few windows with positions left for the exact replays get their items written out (k_exact / k_exact2
 //              read items, as before)
-// A rank of a sharded job (pp_polish_set_emit) takes this path as well, over the job's own coordinates: k_prepd / k_prepg /
+// A rank of a sharded job (pp_polish_set_emit) takes this path as well, over the job's own coordinates: k_prepd /
 // k_winplan see all windows (a few words each), k_tile works on the rank's.
 // An entry order that is not what the run table promises (any permutation is a valid mirror) makes k_prepd raise
 // DE_MIRROR_ORDER: every later kernel returns at once and the host runs the job over the bucketing path.
@@ -45,7 +45,7 @@ __device__ __forceinline__ uint4 wo_item(u64 so, u32 len, u32 kc, u64 g, u32 w, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// k_prepd / k_prepg
+// k_prepd
 // ---------------------------------------------------------------------------------------------------------------------
 // A workgroup's extras are STAGED in LDS and get their slots in the windows' rooms at the end, one returning global atomic
 // per window of the workgroup instead of one per wave, window and trip through the loop (a wave waited out thirteen of
@@ -159,9 +159,7 @@ struct PrepdArgs {
     u32 xcap;
     u32 *maxlen;
     u64 *x_need;
-    uint4 *g_later;      // the entries that are not bulk, for k_prepg: copies of them, two 16-byte words each (file index NOIDX: none) ...
-    u64 *g_nlater;       // ... how many (counted past the capacity too) ...
-    u64 cap_later;       // ... and the room
+    u64 unused_[3];      // (not read: keeps the arguments behind it where they were -- k_prepd's register allocation moves with their offsets)
     u64 seq_bytes;       // bytes of the seq array: a record's SEQ has to lie inside it
     u64 *status;
 };
@@ -171,10 +169,7 @@ struct PrepdArgs {
 // Two round trips: (1) the run count and where the runs are, and the read's last eight bytes (the trims look at the read
 // from its end and rarely further); (2) the first eight runs.  (A record of one run has it in its mirror entry.)  Anything
 // beyond is read where it is needed, as in k_prep.
-// RUNS_IN_REGS = false (k_prepd's own fallback, a workgroup whose noted records do not fit the lists): the runs are read where
-// they are needed -- the eight-run cache is an indexed array, and in k_prepd's loop it went to scratch memory (48 bytes a
-// lane reserved for every wave of the streaming kernel).
-template <bool RUNS_IN_REGS = true, typename CTG>
+template <typename CTG>
 __device__ __forceinline__ void general_record(const pp_wo_rec &r, const PrepdArgs &P, CTG ctg, const XSink &X) {
     u32 g_out = 0, nk_out = 0;
     u8 fl_out = 0;
@@ -192,26 +187,19 @@ __device__ __forceinline__ void general_record(const pp_wo_rec &r, const PrepdAr
         u32 nc = 1;
         u64 co = 0;
         if (multi) { nc = P.n_cig[fi]; co = P.cig_off[fi]; }
-#ifdef PP_PREP_STAMPS
-        if constexpr (RUNS_IN_REGS) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); PP_STAMP(1, 5); }
-#endif
         if (nc == 0) report(P.status, fi, DE_BAD_RUN);
         else {
             const u32 *const cg = P.cigar + co;
             // (eight scalars, not an array: indexed, the array went to scratch memory -- a memory round trip per run in the
             // kernel whose time is its chain of round trips)
             u32 r0 = r.op0, r1 = 0, r2 = 0, r3 = 0, r4 = 0, r5 = 0, r6 = 0, r7 = 0;
-            if (RUNS_IN_REGS && multi) {
+            if (multi) {
                 r0 = cg[0];
                 r1 = cg[min(1u, nc - 1u)]; r2 = cg[min(2u, nc - 1u)]; r3 = cg[min(3u, nc - 1u)]; r4 = cg[min(4u, nc - 1u)];
                 r5 = cg[min(5u, nc - 1u)]; r6 = cg[min(6u, nc - 1u)]; r7 = cg[min(7u, nc - 1u)];
             }
-#ifdef PP_PREP_STAMPS
-            if constexpr (RUNS_IN_REGS) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); PP_STAMP(1, 6); }
-#endif
             prep_general_t(fi, r.ref_start, sl, nc,
                            [&](u32 i) -> u32 {
-                               if (!RUNS_IN_REGS) return multi ? cg[i] : r.op0;
                                if (i >= 8u) return cg[i];
                                const u32 a = (i & 1u) ? r1 : r0, b = (i & 1u) ? r3 : r2, c = (i & 1u) ? r5 : r4, d = (i & 1u) ? r7 : r6;
                                const u32 ab = (i & 2u) ? b : a, cd = (i & 2u) ? d : c;
@@ -222,9 +210,6 @@ __device__ __forceinline__ void general_record(const pp_wo_rec &r, const PrepdAr
         }
     }
     const u32 word = nk_out | ((u32)fl_out << 30);
-#ifdef PP_PREP_STAMPS
-    if constexpr (RUNS_IN_REGS) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); PP_STAMP(1, 7); }
-#endif
     if (!word) return;
     const u32 kc = kclass_of(r.k);
     const u32 cls = word >> 30, ia = (word >> 9) & 0xFFu, idel = (word >> 17) & 1u;
@@ -249,28 +234,19 @@ __device__ __forceinline__ void general_record(const pp_wo_rec &r, const PrepdAr
     });
 }
 
-constexpr u32 NOIDX = 0xFFFFFFFFu;
-// PP_PREPD_TAIL (the default since the end of round 6): k_prepd works its noted records off ITSELF, one lane each out of the list in
-// LDS, behind its loop -- no list in memory, no k_prepg.  Round 5 had moved them out ("their chain of round trips kept the chip from
-// streaming"): then a workgroup in its chain held a slot that a waiting workgroup would have streamed in.  With 1.5 rounds of
-// workgroups or more (768 for the 5 Mbp job, 8,700 entries each) the chains of one round run under the streaming of the next, and
-// a latency-bound kernel of 27 us (k_prepg: 130 k records, a chain of five round trips each) is gone: prep 0.072 -> 0.069 on
-// configs[1], 0.30 -> 0.26 on configs[3], 0.74 -> 0.62-0.68 on configs[4] (`profiles/r6zz_prepd_tail_ab.txt`).  With ONE round
-// (512 workgroups) it loses (0.079), and the 512-thread instance is erratic (0.066-0.15 from one workgroup count to the next).
-// -DPP_PREPD_TAIL=0: the two kernels.
-#ifndef PP_PREPD_TAIL
-#define PP_PREPD_TAIL 1
-#endif
-
-// k_prepd: the streaming pass.  The records that are not bulk are only NOTED -- first in LDS, then, one stretch per
-// workgroup, in a list in memory that k_prepg works off with a lane per record: here, between the loop and the end of a
-// workgroup, their chain of round trips kept the chip from streaming (a workgroup: 21 us of loop, 15 us of waiting).
-// A workgroup whose records do not fit the lists (a job of reads with indels throughout) handles them itself.
+// k_prepd: the streaming pass.  The records that are not bulk are only NOTED in the loop, in a list in LDS, and worked off behind
+// it, one lane each: inside the loop their chains of round trips kept the waves from streaming.  Behind the loop a workgroup in
+// its chain holds a slot that a waiting workgroup would stream in, so the grid is 1.5 rounds of workgroups or more (768 for the
+// 5 Mbp job, 8,700 entries each): the chains of one round run under the streaming of the next.  With ONE round (512 workgroups)
+// it loses (prep 0.079 ms against 0.069 on configs[1]), and the 512-thread instance is erratic (0.066-0.15 from one workgroup
+// count to the next).  (Until the end of round 6 a second kernel worked the noted records off from a list in memory, 27 us of
+// latency-bound work for 130 k records; the A/B that retired it is `profiles/r6zz_prepd_tail_ab.txt`.)
+// A workgroup whose records do not fit the list (a job of reads with indels throughout) walks its entries once more.
 template <int THREADS>
 __global__ __launch_bounds__(THREADS, PP_PREP_WAVES) void k_prepd(u64 chunk, PrepdArgs P) {
     constexpr u32 LATER_MAX = THREADS >= 1024 ? 768 : 320, XSTAGE = 2 * THREADS;  // (73 KB / 40 KB of LDS in all: two / four workgroups per CU)
-    __shared__ uint4 later[2 * LATER_MAX];  // the noted entries themselves (k_prepg then starts from the entry, not from its index)
-    __shared__ u32 n_later, s_later_at, s_unit;
+    __shared__ uint4 later[2 * LATER_MAX];  // the noted entries themselves
+    __shared__ u32 n_later, s_unit;
     __shared__ uint4 st_item[XSTAGE];
     __shared__ u32 st_key[XSTAGE], l_cnt[XLOCAL], l_base[XLOCAL], l_nb[XLOCAL], n_st, s_wbase;
     __shared__ u64 s_ctg[CTG_LDS + 1];  // the contig table when it has up to CTG_LDS contigs: a record's two offsets are then LDS reads, not a dependent trip to memory
@@ -333,24 +309,6 @@ __global__ __launch_bounds__(THREADS, PP_PREP_WAVES) void k_prepd(u64 chunk, Pre
     const uint4 *wq = (const uint4 *)wo;
     const u64 trip = (u64)WU * blockDim.x;
     const u64 span = (hi - lo + trip - 1) / trip * trip;  // whole waves and whole trips: the ballots below need every lane
-#ifdef PP_EXP_PREPD_EXTRA_STREAM
-    // (experiment build: one more pass over the block's entries that only loads them -- what the streaming alone costs)
-    {
-        u32 acc = 0;
-        for (u64 a0 = lo + threadIdx.x; a0 < lo + span; a0 += trip) {
-            uint4 xa[WU], xb[WU];
-#pragma unroll
-            for (int u = 0; u < WU; u++) {
-                const u64 a = min(a0 + (u64)u * blockDim.x, n - 1);
-                xa[u] = wq[2 * a];
-                xb[u] = wq[2 * a + 1];
-            }
-#pragma unroll
-            for (int u = 0; u < WU; u++) acc ^= xa[u].x ^ xa[u].y ^ xa[u].z ^ xa[u].w ^ xb[u].x ^ xb[u].y ^ xb[u].z ^ xb[u].w;
-        }
-        if (acc == 0x12345679u && n == 1) first[0] = acc;
-    }
-#endif
     // The loads run AHEAD of the work, in the registers the work has just left (PP_PREPD_ROLL, the default): a trip's WU sets of
     // loads are asked for one by one, set u of the NEXT trip as soon as set u of this one has been worked off -- while a wave
     // computes, one set is always on its way.  Asked for all at the top of a trip and waited for together, nothing of the wave's
@@ -443,16 +401,12 @@ __global__ __launch_bounds__(THREADS, PP_PREP_WAVES) void k_prepd(u64 chunk, Pre
             }
             // a bulk read that reaches into the next window: one extra there
             const u32 w1 = bulk ? (u32)((g + seq_len - 1u) / (u64)TILE) : 0u;
-#ifndef PP_EXP_PREPD_NOEMIT
             if (bulk && w1 > h) X.emit(w1, wo_item(seq_off, seq_len, kclass_of(k), g, w1, file_idx));
-#endif
             if (bulk) fast_len = max(fast_len, seq_len);
-#ifndef PP_EXP_PREPD_NOLATER
             else if (in) {
                 const u32 slot = atomicAdd(&n_later, 1u);
                 if (slot < LATER_MAX) { later[2u * slot] = qa[u]; later[2u * slot + 1u] = qb[u]; }
             }
-#endif
             if (PP_PREPD_ROLL) ask(u, a0_next, more);
         }
         unit = unit_next;
@@ -460,11 +414,9 @@ __global__ __launch_bounds__(THREADS, PP_PREP_WAVES) void k_prepd(u64 chunk, Pre
     PP_STAMP(0, 2);
     __syncthreads();
     PP_STAMP(0, 3);
-    // the noted records: a stretch of the list in memory -- or, when there are more of them than either list holds, worked
-    // off here, from the block's entries once more (then the stretch, as far as it lies inside the list, is marked empty)
+    // the noted records, one lane each out of the list in LDS -- or, when there are more of them than the list holds, from the
+    // block's entries once more
     const u32 n_noted = n_later;
-#if PP_PREPD_TAIL
-    // the noted records worked off here, one lane each out of the list in LDS (see PP_PREPD_TAIL above)
     const bool listed = n_noted <= LATER_MAX;
     if (listed) {
         for (u32 i = threadIdx.x; i < n_noted; i += blockDim.x) {
@@ -475,19 +427,11 @@ __global__ __launch_bounds__(THREADS, PP_PREP_WAVES) void k_prepd(u64 chunk, Pre
             general_record(r, P, ctg, X);
         }
     }
-#else
-    if (threadIdx.x == 0) s_later_at = n_noted ? (u32)min(atomicAdd(P.g_nlater, (u64)n_noted), (u64)NOIDX) : 0u;
-    __syncthreads();
-    const u64 at = s_later_at;
-    const bool listed = n_noted <= LATER_MAX && at + n_noted <= P.cap_later;
-    for (u32 i = threadIdx.x; i < 2u * n_noted; i += blockDim.x)
-        if (at + (i >> 1) < P.cap_later) P.g_later[2ull * at + i] = listed ? later[i] : make_uint4(NOIDX, NOIDX, NOIDX, NOIDX);
-#endif
     if (!listed && n_noted) {
         for (u64 a = lo + threadIdx.x; a < hi; a += blockDim.x) {
             const pp_wo_rec r = wo[a];
             const u32 cc = min(r.contig, n_contigs - 1u);
-            if (!wo_bulk(r.contig < n_contigs, r.ref_start, r.seq_len, r.op0, ctg(cc + 1u) - ctg(cc))) general_record<PP_PREPD_TAIL != 0>(r, P, ctg, X);  // (runs in registers where the tail above has them anyway: with every run read where it is needed a workgroup of a job with indels in 30 % of its reads took 0.8 ms here)
+            if (!wo_bulk(r.contig < n_contigs, r.ref_start, r.seq_len, r.op0, ctg(cc + 1u) - ctg(cc))) general_record(r, P, ctg, X);  // (runs in registers, as in the tail above: with every run read where it is needed a workgroup of a job with indels in 30 % of its reads took 0.8 ms here)
         }
     }
     PP_STAMP(0, 4);
@@ -499,61 +443,6 @@ __global__ __launch_bounds__(THREADS, PP_PREP_WAVES) void k_prepd(u64 chunk, Pre
         if (lane == 0 && fast_len > __hip_atomic_load(P.maxlen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(P.maxlen, fast_len);
     }
     PP_STAMP(0, 6);
-}
-
-// k_prepg: the records k_prepd noted, one lane each (a few per cent of a short-read job: all of their round trips at once)
-// LDS: 13 KB a workgroup -- a stage of two extras a thread (a workgroup has a record for two of three threads and most records
-// are three pieces; what does not fit takes its slot on the spot), a contig table of PREPG_CTG_LDS entries.  With four a thread and
-// k_prepd's table of 1,024 contigs (29 KB) five workgroups fit a CU, 1,280 the chip, and the 1,628 of a 5 Mbp job started over
-// 16 us (block timeline, `profiles/r6zz_prepg_trips_and_rounds.txt`); with all of them resident at once the kernel takes the
-// same 27 us (A/B in the same file: the chains of round trips are slower the more of them run at a time) -- kept for the room it
-// leaves, not for a gain.
-#ifndef PP_PREPG_XSTAGE
-#define PP_PREPG_XSTAGE 2
-#endif
-#ifndef PP_PREPG_CTG
-#define PP_PREPG_CTG 256
-#endif
-constexpr u32 PREPG_CTG_LDS = PP_PREPG_CTG;
-template <int THREADS>
-__global__ __launch_bounds__(THREADS) void k_prepg(PrepdArgs P) {
-    constexpr u32 XSTAGE = PP_PREPG_XSTAGE * THREADS;
-    __shared__ uint4 st_item[XSTAGE];
-    __shared__ u32 st_key[XSTAGE], l_cnt[XLOCAL], l_base[XLOCAL], l_nb[XLOCAL], n_st;
-    __shared__ u64 s_ctg[PREPG_CTG_LDS + 1];
-    PP_STAMP(1, 0);
-    if (*P.status != ~0ull) return;
-    const u64 total = min(*P.g_nlater, P.cap_later);
-    const u64 per = (total + gridDim.x - 1) / gridDim.x;
-    const u64 i0 = min(total, (u64)blockIdx.x * per), i1 = min(total, i0 + per);
-    if (i0 >= i1) return;
-    const bool ctg_lds = P.n_contigs <= PREPG_CTG_LDS;
-    // One round trip for everything that is known now: the contig table, the stretch's first entry (every thread asks for the
-    // same one: the window the local counters start at), this thread's own first entry.  (Thread 0 alone looking at the first
-    // entry and then at its contig's offset, and every thread asking for its entry behind the barrier, were three trips.)
-    if (ctg_lds)
-        for (u32 i = threadIdx.x; i <= P.n_contigs; i += blockDim.x) s_ctg[i] = P.contig_off[i];
-    const uint4 q0 = P.g_later[2ull * i0];
-    const u64 i_first = i0 + threadIdx.x, i_mine = min(i_first, i1 - 1);
-    uint4 qa = P.g_later[2ull * i_mine], qb = P.g_later[2ull * i_mine + 1];
-    XSink X{st_item, st_key, l_cnt, l_base, l_nb, &n_st, XSTAGE, 0u, P.xcap, P.x_cnt, P.x_nb, P.xent, P.x_need, P.status};
-    X.clear();
-    __syncthreads();
-    PP_STAMP(1, 1);
-    const CtgTab ctg{s_ctg, P.contig_off, ctg_lds};
-    X.wbase = q0.x < P.n_contigs ? wo_home(ctg(q0.x), q0.y, P.nwin) : 0u;  // (the same in every thread)
-    for (u64 i = i_first; i < i1; i += blockDim.x) {
-        if (i != i_first) { qa = P.g_later[2ull * i]; qb = P.g_later[2ull * i + 1]; }
-        pp_wo_rec r;
-        r.contig = qa.x; r.ref_start = qa.y; r.k = qa.z; r.seq_len = qa.w;
-        r.seq_off = (u64)qb.x | ((u64)qb.y << 32); r.op0 = qb.z; r.file_idx = qb.w;
-        if (!(qa.x == NOIDX && qb.w == NOIDX)) general_record(r, P, ctg, X);
-    }
-    PP_STAMP(1, 2);
-    __syncthreads();
-    PP_STAMP(1, 3);
-    X.flush();
-    PP_STAMP(1, 4);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -128,7 +128,7 @@ __device__ __forceinline__ void compact_window(u32 w, const u8 *__restrict__ cod
         o0 = win_out[w];
         o1 = win_out[w + 1];
     }
-    const u32 n_multi = counters[1];
+    const u32 n_multi = counters[MC_MULTI];
     asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w));
     if ((st != ~0ull) | (o1 == o0)) return;  // the job is off / nothing to emit (a window of another rank, or all deletions)
     u8 c[EMIT_PPT];
@@ -190,7 +190,7 @@ __device__ __forceinline__ void finalize_entries(u32 first_wave, u32 n_waves, co
                                                  const u8 *__restrict__ seq,
                                                  const u64 *__restrict__ contig_off, u32 n_contigs,
                                                  u8 *__restrict__ out, u64 *__restrict__ ctg_out) {
-    const u32 n_multi = counters[1];
+    const u32 n_multi = counters[MC_MULTI];
     const u32 lane = threadIdx.x & 63u;
     const u32 n_todo = n_multi + n_contigs + 1u;
     // where window w's bytes begin: the scan's, or (fused form, win_len != nullptr) added up by the wave
@@ -279,17 +279,17 @@ __device__ __forceinline__ void emit_tail(const EmitTail &Z) {
     if (!s_last) return;
     // (one round trip: what every thread has to know, and its first word of the block)
     const u32 i0 = threadIdx.x;
-    const u64 st = __hip_atomic_load(Z.meta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const u64 c01 = __hip_atomic_load(Z.meta + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const u64 c23 = __hip_atomic_load(Z.meta + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const u64 st = __hip_atomic_load(Z.meta + MW_STATUS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const u64 c01 = __hip_atomic_load(Z.meta + MW_COUNTERS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const u64 c23 = __hip_atomic_load(Z.meta + MW_COUNTERS + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     u64 v = __hip_atomic_load(Z.meta + min(i0, Z.words - 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool flagged = (u32)c01 != 0u || (u32)c23 != 0u;  // (counters 0 and 2: listed for k_exact, flagged in all)
+    const bool flagged = (u32)c01 != 0u || (u32)c23 != 0u;  // (the low halves: MC_LISTED and MC_FLAGGED)
     const bool again = st == ~0ull && (Z.reinit == 2u || (Z.reinit == 1u && !flagged));
-    __syncthreads();  // (every wave has looked at words 0-2 before their owner resets them)
+    __syncthreads();  // (every wave has looked at the status and the counters before their owner resets them)
     for (u32 i = i0; i < Z.words; i += blockDim.x) {
         if (i != i0) v = __hip_atomic_load(Z.meta + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(Z.host + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (again) Z.meta[i] = i == 0 ? ~0ull : 0ull;
+        if (again) Z.meta[i] = i == MW_STATUS ? ~0ull : 0ull;
     }
     if (!Z.ordered && threadIdx.x == 0) {  // (a host that waits for the kernel's end: nothing to order)
         __hip_atomic_store(Z.host + Z.words, again ? 1ull : 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

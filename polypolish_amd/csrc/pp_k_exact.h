@@ -138,7 +138,7 @@ __global__ __launch_bounds__(EXW_THREADS) void k_exact(ExactArgs A) {
         if (blockIdx.x == 0 && threadIdx.x == 0) report(A.status, *A.scr_need, DE_CAPACITY);
         return;
     }
-    const u32 n_flagged = A.counters[0];
+    const u32 n_flagged = A.counters[MC_LISTED];
     for (u32 f = blockIdx.x; f < n_flagged; f += gridDim.x) {
         const u32 cap = A.flag_cov[f];
         if (cap <= EXW_MAX) exact_block(A, f, cap, cov, rcp, kw, &s_n);
@@ -356,7 +356,7 @@ __device__ void exact_block(const ExactArgs &A, u32 f, u32 cap, ulonglong2 *cov,
         else if (eff == 1 && only < 0x80u) { A.code[gp] = only; }
         else {
             A.code[gp] = (eff <= 126u) ? (u8)(0x80u | eff) : (u8)0xFFu;
-            const u32 slot = atomicAdd(&A.counters[1], 1u);
+            const u32 slot = atomicAdd(&A.counters[MC_MULTI], 1u);
             if (slot < A.cap_multi) {
                 MultiEnt m;
                 m.off = win_off; m.pos = gp; m.len = win_len; m.eff = eff; m.pad = 0;
@@ -521,7 +521,7 @@ __device__ void exact_one(const ExactArgs &A, u32 f) {
         else if (eff == 1 && only < 0x80u) { A.code[gp] = only; }
         else {
             A.code[gp] = (eff <= 126u) ? (u8)(0x80u | eff) : (u8)0xFFu;
-            const u32 slot = atomicAdd(&A.counters[1], 1u);
+            const u32 slot = atomicAdd(&A.counters[MC_MULTI], 1u);
             if (slot < A.cap_multi) {
                 MultiEnt m;
                 m.off = win_off; m.pos = gp; m.len = win_len; m.eff = eff; m.pad = 0;
@@ -596,7 +596,7 @@ __global__ __launch_bounds__(1024, (SUB == 1 && SMAX <= SORT_SMALL) ? 8 : 4) voi
                 }
             return;
         }
-        if (blockIdx.x >= min(A.counters[3], A.cap_slabs)) return;
+        if (blockIdx.x >= min(A.counters[MC_SLABS], A.cap_slabs)) return;
         w = A.slab_win[blockIdx.x];
     } else {
         const u32 hs = blockIdx.x / SUB;
@@ -663,7 +663,7 @@ __global__ __launch_bounds__(1024, (SUB == 1 && SMAX <= SORT_SMALL) ? 8 : 4) voi
                 if (!((A.flag_bits[(u64)w * (TILE / 32) + (p >> 5)] >> (p & 31u)) & 1u)) continue;
                 const u32 ntot = tal0[0 * TILE + p] + tal0[1 * TILE + p] + tal0[2 * TILE + p] + tal0[3 * TILE + p] +
                                  tal0[4 * TILE + p] + tal0[5 * TILE + p];
-                const u32 slot = atomicAdd(&A.counters[0], 1u);
+                const u32 slot = atomicAdd(&A.counters[MC_LISTED], 1u);
                 const u64 scr_at = atomicAdd(A.scr_need, (u64)ntot);
                 if (slot < A.cap_flag) { A.flag_pos_w[slot] = w * (u32)TILE + p; A.flag_cov_w[slot] = ntot; A.flag_scr_w[slot] = scr_at; }
                 else report(A.status, slot, DE_CAPACITY_LATE);
@@ -897,7 +897,7 @@ __global__ __launch_bounds__(1024, (SUB == 1 && SMAX <= SORT_SMALL) ? 8 : 4) voi
         const VoteOut vo = vote5(nA, nC, nG, nT, nDel, depth, orig, A.min_depth, A.fv, A.fi);
         if (vo.status != PP_ST_LOW_DEPTH && nOth > 0 && nOth >= vo.ithr) {
             // a string-keyed tally could reach a threshold: full replay by the thread-serial kernel
-            const u32 slot = atomicAdd(&A.counters[0], 1u);
+            const u32 slot = atomicAdd(&A.counters[MC_LISTED], 1u);
             const u64 scr_at = atomicAdd(A.scr_need, (u64)ntot);
             if (slot < A.cap_flag) { A.flag_pos_w[slot] = gp; A.flag_cov_w[slot] = ntot; A.flag_scr_w[slot] = scr_at; }
             else report(A.status, slot, DE_CAPACITY_LATE);

@@ -30,7 +30,7 @@ struct TileArgs {
     u32 *counters;  // [0] positions on the global replay list, [1] n_multi, [2] all flagged positions
     u32 cap_flag;
     const u32 *vote_tab;  // (valid, invalid) thresholds per integer depth below VOTE_TAB_N (k_meta_init)
-    MultiEnt *multi;  // positions whose polished string has two or more bytes (counters[1] of them; k_exact adds its own)
+    MultiEnt *multi;  // positions whose polished string has two or more bytes (counters[MC_MULTI] of them; k_exact adds its own)
     u32 cap_multi;
     u32 *flag_bits;   // per window: 2048-bit map of flagged positions (64 words)
     u32 *win_nflag;   // per window: number of flagged positions
@@ -704,12 +704,7 @@ __device__ __forceinline__ void wide4_pass(u32 *cnt, u32 *ndbits, const TileShar
         const int P0 = relc + 32 * c;  // window position of the chunk's nibble 0
         // (clamped only for a chunk with nothing in range; one add and one v_med3 on the dword index -- the clamp on the
         // nibble index was seven instructions per chunk)
-#ifndef PP_WIDE4_OLD_CLAMP
         const u32 *ap = asm4 + min(max(dw0 + 4 * c, 0), ASM4_WORDS - 5);
-#else
-        const u32 ai = (u32)min(max(P0 + ASM4_PAD, 0), 8 * (ASM4_WORDS - 5));
-        const u32 *ap = asm4 + (ai >> 3);
-#endif
         const u32 a0 = ap[0], a1 = ap[1], a2 = ap[2], a3 = ap[3], a4 = ap[4];
         u32 F = nz_perm(W[c].x ^ __builtin_amdgcn_alignbit(a1, a0, sh), W[c].y ^ __builtin_amdgcn_alignbit(a2, a1, sh),
                         W[c].z ^ __builtin_amdgcn_alignbit(a3, a2, sh), W[c].w ^ __builtin_amdgcn_alignbit(a4, a3, sh));
@@ -1136,47 +1131,21 @@ __device__ __forceinline__ void tile_items(const TileArgs &A, u32 *cnt, u32 *s_n
 struct BulkRuns {  // the window's stretches of the mirror in two registers: lane r holds pre[r] (its entries in the runs before r; lane R: all of them) and first[r]
     u32 pre_v, first_v, R;
 };
-// -DPP_TILE_SLOAD (measured, not the default: k_tile_direct 0.1925 vs 0.1952 ms on configs[1], nothing on configs[4] --
-// inside the noise, not worth inline assembly in the product): a handful of uniform words at the top of a workgroup -- the
-// window's stretch of every run, its extras' count -- come through the SCALAR cache (s_load_dword, inline: the compiler only uses scalar loads for memory it can prove nobody writes): as vector
-// loads they queue behind everything else the CU's vector memory pipeline has in flight (2 us of every workgroup's chain
-// entries -> chunks -> first pass).  What the words hold was written by the kernels before this one (the scalar cache is
-// invalidated at the start of a kernel).  All requests go out before the one wait.
-// (one asm statement: the requests and the wait together -- between two statements the compiler may copy a destination register
-// that the load has not written yet)
-constexpr u32 SLOAD_RUNS = 2;  // runs whose stretches are fetched this way (a job of more SAM files: vector loads, as before)
-__device__ __forceinline__ void sload5(const u32 *p0, const u32 *p1, const u32 *p2, u32 &a0, u32 &a1, u32 &b0, u32 &b1, u32 &c) {
-    asm volatile("s_load_dword %0, %5, 0x0\n\ts_load_dword %1, %5, 0x4\n\ts_load_dword %2, %6, 0x0\n\ts_load_dword %3, %6, 0x4\n\t"
-                 "s_load_dword %4, %7, 0x0\n\ts_waitcnt lgkmcnt(0)"
-                 : "=&s"(a0), "=&s"(a1), "=&s"(b0), "=&s"(b1), "=&s"(c)
-                 : "s"(p0), "s"(p1), "s"(p2)
-                 : "memory");
-}
+// (The window's stretch of every run and its extras' count through the scalar cache, by inline assembly, measured inside the
+// noise -- k_tile_direct 0.1925 vs 0.1952 ms on configs[1], nothing on configs[4] -- and was not kept.)
 struct BulkRunsRaw {  // as loaded: lane r's stretch of the window in run r, and the window's count of extras
     u32 f0, len, n_extras;
 };
 __device__ __forceinline__ BulkRunsRaw bulk_runs_load(const TileArgs &A, u32 w, u32 lane) {
     BulkRunsRaw raw{0u, 0u, 0u};
     const u32 R = A.n_runs;
-#ifdef PP_TILE_SLOAD
-    if (R <= SLOAD_RUNS) {
-        u32 a0, a1, b0, b1, xc;
-        const u32 *const row0 = A.first + w, *const row1 = A.first + (u64)(R - 1u) * (A.nwin + 1u) + w;  // (one run: its row twice)
-        sload5(row0, row1, A.x_cnt + w, a0, a1, b0, b1, xc);
-        raw.n_extras = xc;
-        if (lane == 0) { raw.f0 = a0; raw.len = a1 - a0; }
-        if (lane == 1 && R > 1u) { raw.f0 = b0; raw.len = b1 - b0; }
-    } else
-#endif
-    {
-        // (no load under a condition -- a lane past the last run reads the last run's words and drops them: a conditional load
-        // is waited for where its branch ends, and the words asked for in front of it with it)
-        const u32 r = min(lane, R - 1u);
-        const u32 xc = A.x_cnt[w], a = A.first[(u64)r * (A.nwin + 1u) + w], b = A.first[(u64)r * (A.nwin + 1u) + w + 1u];
-        raw.n_extras = xc;
-        raw.f0 = lane < R ? a : 0u;
-        raw.len = lane < R ? b - a : 0u;
-    }
+    // (no load under a condition -- a lane past the last run reads the last run's words and drops them: a conditional load
+    // is waited for where its branch ends, and the words asked for in front of it with it)
+    const u32 r = min(lane, R - 1u);
+    const u32 xc = A.x_cnt[w], a = A.first[(u64)r * (A.nwin + 1u) + w], b = A.first[(u64)r * (A.nwin + 1u) + w + 1u];
+    raw.n_extras = xc;
+    raw.f0 = lane < R ? a : 0u;
+    raw.len = lane < R ? b - a : 0u;
     return raw;
 }
 __device__ __forceinline__ BulkRuns bulk_runs_scan(const TileArgs &A, const BulkRunsRaw &raw, u32 lane) {
@@ -1189,29 +1158,12 @@ __device__ __forceinline__ BulkRuns bulk_runs_scan(const TileArgs &A, const Bulk
     B.R = R;
     return B;
 }
-// (experiment builds, tools/exp_variants.sh: -DPP_EXP_NOLOAD = the chunks are not loaded, the pass works on a constant;
-// -DPP_EXP_NOCOMPARE = they are loaded and waited for, nothing is compared)
-#ifdef PP_EXP_NOLOAD
-#define PP_EXP_LOAD16(p) make_uint4((u32)(uintptr_t)(p), 0x01230123u, 0x32103210u, 0x11112222u)
-#else
-#define PP_EXP_LOAD16(p) load16_unaligned(p)
-#endif
-#ifndef PP_GROUP_SPLIT
-#define PP_GROUP_SPLIT 5
-#endif
-// -DPP_EXP_COALESCED: chunk c of a pass's 64 reads is loaded as ONE contiguous kilobyte (lane l: 16 bytes at 1024 c + 16 l from
-// where lane 0's read lies -- the same 5 KB the pass touches, wrong bytes in every lane but one: what a wave-interleaved
-// layout of the reads would cost the memory pipeline)
-#ifdef PP_EXP_COALESCED
-#define PP_EXP_CHUNK(q, c, lane) ((const u8 *)(((uintptr_t)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(uintptr_t)(q)) | ((uintptr_t)(u32)__builtin_amdgcn_readfirstlane((int)(u32)((uintptr_t)(q) >> 32)) << 32)) & ~(uintptr_t)15) + 1024 * (c) + 16 * (lane))
-#else
-#define PP_EXP_CHUNK(q, c, lane) ((q) + 16 * (c))
-#endif
 template <int NCH>
 struct DirectBulk {
+    static constexpr int GROUP_SPLIT = 5;  // chunks of the next pass asked for in the first of two groups (run, below)
     BulkRuns B;
     u32 v0, nv, pm;       // the mirror entries this workgroup takes: [v0, v0 + nv) of the window's (v0: a multiple of 64), in pm passes
-    const uint4 *items;   // ... and its extras: items[x0 .. x0 + nx) (16-byte work items, k_prepd / k_prepg), in px passes behind them
+    const uint4 *items;   // ... and its extras: items[x0 .. x0 + nx) (16-byte work items, k_prepd), in px passes behind them
     u32 x0, nx, px;
     u32 pass;             // this wave's next pass (uniform): < pm one over mirror entries, else one over extras
     uint4 ea, eb;         // its sources: a mirror entry (contig, ref_start, k, seq_len | seq_off (two words), op0, file index) or an item (ea)
@@ -1341,7 +1293,7 @@ struct DirectBulk {
         tail = load4_unaligned(A.seq4 + ((ld ? so + (L - 1u) : 7ull) >> 1) - 3);
         const u8 *const q = A.seq4 + ((ld ? so : 0ull) >> 1);
 #pragma unroll
-        for (int c = 0; c < NCH; c++) W[c] = PP_EXP_LOAD16(PP_EXP_CHUNK(q, c, lane));
+        for (int c = 0; c < NCH; c++) W[c] = load16_unaligned(q + 16 * c);
     }
     // (3) behind the prologue's barrier: the passes.  `defer`: the list for the extras' slow items (ItemList::defer)
     __device__ __forceinline__ void run(const TileArgs &A, u32 *cnt, u32 *ndbits, const TileShare &S, const u32 *asm_w, const u32 *asm4, const RecMap &M,
@@ -1368,19 +1320,13 @@ struct DirectBulk {
                 }
                 // a slow item (indels in several runs, a long read): listed for the slow round (tile_window), or -- no room --
                 // counted for a round over all of the window's extras
-#ifndef PP_EXP_NOSLOW
                 if (cur.pack & LN_SLOW) {
                     const u32 slot = atomicAdd(defer_n, 1u);
                     if (slot < defer_cap) defer[slot] = src;
                 }
-#endif
                 // the entry AT a read's single indel (ENT_POINT): one tally -- the two-byte key of an insertion is counted by
                 // string (pileup.rs:56-63), the empty slot of a deletion is the "-" key
-#ifdef PP_EXP_NOPOINT
-                if (false) {
-#else
                 if ((cur.pack & LN_POINT) && rel_r >= 0) {
-#endif
                     tile_add(cnt, (my.y >> 24) ? ROW_OTH : ROW_DEL, rel_r);
                     share_range(cnt, ndbits, S, rel_r, rel_r + 1, (my.y >> 8) & 0xFFu, my.w);
                     if ((my.y >> 24) == 2u) pt_insert(S.pt, S.pt_over, rel_r, A.seq, (u64)my.x | ((u64)(my.y & 0xFFu) << 32));
@@ -1388,9 +1334,6 @@ struct DirectBulk {
                 // a fast-class read the pass does not take (fewer than 8 bases; the last reads of the seq array; an odd-start flank
                 // that fills its last chunk): one item per pass, as the fast class that is not plain in tile_items
                 u64 rest = __ballot((cur.pack & (LN_FAST | LN_PLAIN | LN_POINT)) == LN_FAST);
-#ifdef PP_EXP_NOREST
-                rest = 0;
-#endif
                 while (rest) {
                     const u32 j = (u32)__ffsll((long long)rest) - 1u;
                     rest &= rest - 1;
@@ -1451,12 +1394,6 @@ struct DirectBulk {
                 u32 F = nz_perm(Wc.x ^ __builtin_amdgcn_alignbit(a1, a0, sh), Wc.y ^ __builtin_amdgcn_alignbit(a2, a1, sh),
                                 Wc.z ^ __builtin_amdgcn_alignbit(a3, a2, sh), Wc.w ^ __builtin_amdgcn_alignbit(a4, a3, sh));
                 F &= mhi[PMASK_BASE - 32 * c] & ~mlo[PMASK_BASE - 32 * c];
-#ifdef PP_EXP_NOCOMPARE
-                F = (Wc.x + Wc.y + Wc.z + Wc.w == 0x12345u && F) ? 1u : 0u;  // (experiment: the loads are waited for, nothing is tallied)
-#endif
-#ifdef PP_EXP_NOLOAD
-                F = (lane == 13u * c && live) ? 1u : (F & 0u);  // (experiment: one trip of the loop below per chunk, as the real data make it)
-#endif
                 while (F) {  // one trip per differing base: bit t = 4k + d <=> nibble k of dword d
                     const u32 t = (u32)__ffs((int)F) - 1u;
                     F &= F - 1u;
@@ -1468,24 +1405,20 @@ struct DirectBulk {
                     atomicAdd(&cnt[row_of_code8(code) * TILE + p], 1u);
                     atomicAdd(&cnt[ROW_MIS * TILE + p], 1u);
                 }
-#if PP_GROUP_SPLIT > 0
-                // The next pass's chunks in two groups, each back to back -- chunks 0 .. PP_GROUP_SPLIT - 1 when this pass's chunk
-                // PP_GROUP_SPLIT - 1 is through, the others at the end: one by one (each into the registers its predecessor had just
+                // The next pass's chunks in two groups, each back to back -- chunks 0 .. GROUP_SPLIT - 1 when this pass's chunk
+                // GROUP_SPLIT - 1 is through, the others at the end: one by one (each into the registers its predecessor had just
                 // left) every load was an L1 miss of its own, the loads of a read's neighbouring 16 bytes far apart in time (17.8 M
-                // L1 -> L2 read requests per launch for 6.9 M L2 -> HBM ones, profiles/r6i_*; k_tile_direct 0.236 -> 0.217 ms).
-                if (c == PP_GROUP_SPLIT - 1) {
+                // L1 -> L2 read requests per launch for 6.9 M L2 -> HBM ones, profiles/r6i_*; k_tile_direct 0.236 -> 0.217 ms;
+                // where to split: `profiles/r6o_load_grouping_sweep.txt`).
+                if (c == GROUP_SPLIT - 1) {
 #pragma unroll
-                    for (int cc = 0; cc < PP_GROUP_SPLIT; cc++) W[cc] = PP_EXP_LOAD16(PP_EXP_CHUNK(q_next, cc, lane));
+                    for (int cc = 0; cc < GROUP_SPLIT; cc++) W[cc] = load16_unaligned(q_next + 16 * cc);
                 }
-                if (c == NCH - 1 && PP_GROUP_SPLIT < NCH) {
+                if (c == NCH - 1 && GROUP_SPLIT < NCH) {
 #pragma unroll
-                    for (int cc = PP_GROUP_SPLIT; cc < NCH; cc++) W[cc] = PP_EXP_LOAD16(PP_EXP_CHUNK(q_next, cc, lane));
+                    for (int cc = GROUP_SPLIT; cc < NCH; cc++) W[cc] = load16_unaligned(q_next + 16 * cc);
                 }
                 if (c == NCH - 1) tail = load4_unaligned(t_next);  // (its tail bytes with them: the line its last chunk is in)
-#else
-                W[c] = PP_EXP_LOAD16(PP_EXP_CHUNK(q_next, c, lane));  // (experiment: the next pass's chunk c, into the registers this pass's has just left)
-                if (c == NCH - 1) tail = load4_unaligned(t_next);
-#endif
             }
             cur = nxt;
         }
@@ -1496,9 +1429,6 @@ constexpr u32 HSLAB_WORDS = (u32)(N_ROWS * TILE + TILE / 32);  // the nine count
 static_assert(HSLAB_WORDS % 4 == 0 && (N_ROWS * TILE) % 4 == 0 && TILE % 128 == 0, "the partial tallies move as 16-byte words");
 constexpr u32 HEAVY_BLOCKS = HEAVY_SLOTS * HEAVY_PARTS;      // helper blocks at the front of k_tile's grid (a multiple of 8)
 
-#ifndef PP_TILE_LAZY_ARGS
-#define PP_TILE_LAZY_ARGS 1
-#endif
 // Profiling builds only (make variant NAME=stopK DEFS=-DPP_TILE_STOP=K, tools/exp_tile_phases.sh): an ordinary window's
 // workgroup ends behind phase K -- 9 at its start, 8 the first entries asked for, 1 prologue, 2 items, 3 prefix sums, 4 vote pass 1,
 // 5 vote pass 2 -- so that the counters
@@ -1724,9 +1654,7 @@ __device__ __forceinline__ void tile_window(const TileArgs &A) {
             s_run[48] = (u32)lo64; s_run[49] = (u32)(lo64 >> 32); s_run[50] = (u32)len64; s_run[51] = (u32)(len64 >> 32);
         }
     }
-#ifndef PP_EXP_STAGE_LATE
     if constexpr (BULK) D.stage(A, lane);  // the first pass's chunks and the second's entries: asked for in front of the barrier
-#endif
     __syncthreads();
     PP_STOP_AFTER(1)
 
@@ -1774,11 +1702,8 @@ __device__ __forceinline__ void tile_window(const TileArgs &A) {
             // then its extras [i0, i1) in the same pipeline.  Every pass but the last of either kind is full: at 50x a window
             // is 11 + 1 passes where a sixteenth of one list per wave made 16 of them, two thirds full.  The extras' SLOW items
             // are only listed there (the list lives behind the tables in s_dirty's space) and tallied in a round of their own
-            // below, a sixteenth per wave, through tile_items: k_prepg's pieces sit at the tail of a window's extras, hundreds
+            // below, a sixteenth per wave, through tile_items: the pieces of the records that are not bulk sit at the tail of a window's extras, hundreds
             // of them in a window whose reads cross two planted indels, a memory round trip each.
-#ifdef PP_EXP_STAGE_LATE
-            D.stage(A, lane);  // (experiment: behind the barrier)
-#endif
             D.run(A, cnt, s_ndbits, S, asm_w, asm4, M, s_slow, &s_nslow, SLOW_CAP, lane);
             __syncthreads();
             const u32 n_slow = s_nslow;
@@ -2030,11 +1955,11 @@ __device__ __forceinline__ void tile_window(const TileArgs &A) {
                 atomicOr(&s_fbits[p >> 5], 1u << (p & 31u));
                 atomicAdd(&s_nflag, 1u);
             } else {
-                atomicAdd(&A.counters[2], 1u);
+                atomicAdd(&A.counters[MC_FLAGGED], 1u);
             }
             if (to_list) {
                 // bucket too large for the wave-per-position replay: global list for k_exact
-                const u32 slot = atomicAdd(&A.counters[0], 1u);
+                const u32 slot = atomicAdd(&A.counters[MC_LISTED], 1u);
                 const u64 scr_at = atomicAdd(A.scr_need, (u64)ntot);  // its stretch of the replay scratch
                 if (slot < A.cap_flag) {
                     A.flag_pos[slot] = (u32)gp;
@@ -2051,7 +1976,7 @@ __device__ __forceinline__ void tile_window(const TileArgs &A) {
         if (multi_eff) {  // the winner has two bytes: k_emit takes them from the seq array (as for k_exact's multi-byte winners)
             l = multi_eff;
             A.code[gp] = (u8)(0x80u | multi_eff);
-            const u32 slot = atomicAdd(&A.counters[1], 1u);
+            const u32 slot = atomicAdd(&A.counters[MC_MULTI], 1u);
             if (slot < A.cap_multi) {
                 MultiEnt m;
                 m.off = multi_off; m.pos = (u32)gp; m.len = 2u; m.eff = multi_eff; m.pad = 0;
@@ -2108,7 +2033,7 @@ __device__ __forceinline__ void tile_window(const TileArgs &A) {
                 u32 nA, nC, nG, nT, nDel, nOth;
                 position_tallies(cnt, ((const u8 *)asm_w)[ASM_PAD + p], p, nA, nC, nG, nT, nDel, nOth);
                 const u32 ntot = nA + nC + nG + nT + nDel + nOth;
-                const u32 slot = atomicAdd(&A.counters[0], 1u);
+                const u32 slot = atomicAdd(&A.counters[MC_LISTED], 1u);
                 const u64 scr_at = atomicAdd(A.scr_need, (u64)ntot);
                 if (slot < A.cap_flag) {
                     A.flag_pos[slot] = (u32)(w0 + p);
@@ -2121,14 +2046,14 @@ __device__ __forceinline__ void tile_window(const TileArgs &A) {
             s_fbits[tid] = 0;
         }
         __syncthreads();
-        if (tid == 0) { atomicAdd(&A.counters[2], s_nflag); s_nflag = 0; }
+        if (tid == 0) { atomicAdd(&A.counters[MC_FLAGGED], s_nflag); s_nflag = 0; }
         __syncthreads();
     }
     if (tid < (u32)(TILE / 32)) A.flag_bits[(u64)w * (TILE / 32) + tid] = s_fbits[tid];
     if (s_nflag && (n_items <= SORT_MAX || heavy)) {
         // the ordered-depth replay needs this window's integer tallies: save them (rare windows only)
         if (tid == 0) {
-            const u32 slab = atomicAdd(&A.counters[3], 1u);
+            const u32 slab = atomicAdd(&A.counters[MC_SLABS], 1u);
             if (slab >= A.cap_slabs) report(A.status, slab, DE_CAPACITY_LATE);
             s_c1 = slab;
             A.win_slab[w] = slab;
@@ -2152,7 +2077,7 @@ __device__ __forceinline__ void tile_window(const TileArgs &A) {
     if (tid == 0) {
         if (DIRECT && s_need) A.need_win[atomicAdd(A.n_need, 1ull)] = w;  // (every window at most once: room for all of them)
         A.win_nflag[w] = s_nflag;
-        if (s_nflag) atomicAdd(&A.counters[2], s_nflag);
+        if (s_nflag) atomicAdd(&A.counters[MC_FLAGGED], s_nflag);
         A.win_len[w] = s_len;
         if (s_len) note_out_len(A.win_coarse, A.win_coarse2, w, s_len);
         if (s_changed) atomicAdd(&A.stats[s_c0].changed, (u64)s_changed);
@@ -2166,19 +2091,11 @@ __device__ __forceinline__ void tile_window(const TileArgs &A) {
 // SGPR spills, and a v_readlane per spilled dword in front of every use: a fifth of the item loop's VALU issue.
 template <int GW, bool P4>
 __global__ __launch_bounds__(TILE_THREADS, 8) void k_tile(TileArgs A_in_kernarg) {
-#if PP_TILE_LAZY_ARGS
     tile_window<false, GW, P4>(*(const TileArgs *)__builtin_amdgcn_kernarg_segment_ptr());
-#else
-    tile_window<false, GW, P4>(A_in_kernarg);
-#endif
 }
 template <int GW, bool P4>
 __global__ __launch_bounds__(TILE_THREADS, 8) void k_tile_direct(TileArgs A_in_kernarg) {
-#if PP_TILE_LAZY_ARGS
     tile_window<true, GW, P4>(*(const TileArgs *)__builtin_amdgcn_kernarg_segment_ptr());
-#else
-    tile_window<true, GW, P4>(A_in_kernarg);
-#endif
 }
 
 }  // namespace pp

@@ -16,7 +16,7 @@ for f in glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True):
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), n))
 rows.sort()
 print(len(rows), "kernel launches in the trace")
-ours = ("k_meta_init", "k_prepd", "k_prepg", "k_winplan", "k_tile_direct", "k_scan", "k_emit", "k_xmat", "k_exact")
+ours = ("k_meta_init", "k_prepd", "k_winplan", "k_tile_direct", "k_scan", "k_emit", "k_xmat", "k_exact")
 # jobs: from a k_prepd to the next k_prepd
 starts = [i for i, r in enumerate(rows) if r[2].startswith("k_prepd")]
 jobs = [rows[a:b] for a, b in zip(starts[:-1], starts[1:])]
