@@ -464,7 +464,9 @@ int pp_ingest_sam(pp_ingest *g, const char *path, pp_sam_counts *counts, char *e
 /* Same, with the filter's verdicts handed over in memory instead of as "ZP:Z:fail" tags in a rewritten
  * file (fused filter -> polish): pass[i] == 0 fails the i-th ALIGNED record of the file (file order, the
  * numbering of pp_filter_file), exactly as if the tag had been appended to its line (src/alignment.rs:72-74).
- * n_pass must equal the number of aligned records. */
+ * pass == NULL: no verdicts (n_pass is not looked at).  Otherwise n_pass must equal the number of aligned records -- zero
+ * verdicts for a file with aligned records included --, or the call ends with PP_ERR_ARG once the text has been found free of
+ * defects.  pp_dev_ingest_sam_filtered follows the same rule. */
 int pp_ingest_sam_filtered(pp_ingest *g, const char *path, const uint8_t *pass, uint64_t n_pass,
                            pp_sam_counts *counts, char *err, size_t errlen);
 void pp_ingest_batch(const pp_ingest *g, pp_aln_batch *out); /* borrowed view, host memory */

@@ -273,6 +273,7 @@ def lib():
         L.pp_dev_ingest_sam.argtypes = [vp, C.c_char_p, C.POINTER(SamCounts)]
         L.pp_dev_ingest_sam_filtered.argtypes = [vp, C.c_char_p, vp, C.c_uint64, C.POINTER(SamCounts)]
         L.pp_dev_ingest_set_seq_layout.argtypes = [vp, C.c_int]
+        L.pp_dev_ingest_expect.argtypes = [vp, C.c_uint64]
         L.pp_ingest_set_seq_layout.argtypes = [vp, C.c_int]
         L.pp_dev_ingest_batch.argtypes = [vp, C.POINTER(AlnBatch)]
         L.pp_dev_ingest_batch.restype = None
@@ -333,10 +334,22 @@ def split_records(recs, cuts):
     return out
 
 
-def ingest(assembly, sams, max_errors=10, careful=False, seq_layout=None):
+def _verdict_args(verdicts, i):
+    """(pointer, count, the array it points into) of file i's filter verdicts: one byte per aligned record.  No verdicts for
+    the file (None): (None, 0, None).  An empty array is a real pointer with a count of zero."""
+    if verdicts is None or verdicts[i] is None:
+        return None, 0, None
+    v = np.ascontiguousarray(verdicts[i], dtype=np.uint8)
+    buf = np.zeros(max(len(v), 1), dtype=np.uint8)
+    buf[:len(v)] = v
+    return buf.ctypes.data, len(v), buf
+
+
+def ingest(assembly, sams, max_errors=10, careful=False, seq_layout=None, verdicts=None):
     """Host ingest only (no GPU needed): FASTA + SAM text -> (names, descs, contig_off, bases, recs, counts).
     seq_layout: None = the library's default (window-grouped unless PP_SEQ_LAYOUT=file), 0 = SEQ bytes in file order,
-    1 = window-grouped (pp_ingest_set_seq_layout)."""
+    1 = window-grouped (pp_ingest_set_seq_layout).  verdicts: per file None or the filter's verdict byte of every aligned
+    record (pp_ingest_sam_filtered)."""
     L = lib()
     err = C.create_string_buffer(1024)
     a = C.c_void_p()
@@ -356,7 +369,11 @@ def ingest(assembly, sams, max_errors=10, careful=False, seq_layout=None):
         counts = []
         for s in sams:
             c = SamCounts()
-            rc = L.pp_ingest_sam(g, str(s).encode(), C.byref(c), err, 1024)
+            vp, nv, _keep = _verdict_args(verdicts, len(counts))
+            if _keep is not None:
+                rc = L.pp_ingest_sam_filtered(g, str(s).encode(), vp, nv, C.byref(c), err, 1024)
+            else:
+                rc = L.pp_ingest_sam(g, str(s).encode(), C.byref(c), err, 1024)
             if rc:
                 raise PolypolishError(rc, err.value.decode())
             counts.append((c.alignments, c.used, c.reads))
@@ -399,10 +416,12 @@ def pack_seq4(seq):
     return out
 
 
-def ingest_device(ctx, assembly, sams, max_errors=10, careful=False, seq_layout=None):
+def ingest_device(ctx, assembly, sams, max_errors=10, careful=False, seq_layout=None, expect=None, verdicts=None):
     """The device tokenizer (pp_dev_ingest_*): same return value as ingest(), the records copied back from HBM.
     seq_layout: None = the library's default (window-grouped unless PP_SEQ_LAYOUT=file), 0 = SEQ bytes in file order,
-    1 = window-grouped (pp_dev_ingest_set_seq_layout)."""
+    1 = window-grouped (pp_dev_ingest_set_seq_layout).  expect: the text bytes of all the files, announced before the first
+    one (pp_dev_ingest_expect).  verdicts: per file None or the filter's verdict byte of every aligned record
+    (pp_dev_ingest_sam_filtered)."""
     L = lib()
     err = C.create_string_buffer(1024)
     a = C.c_void_p()
@@ -419,10 +438,16 @@ def ingest_device(ctx, assembly, sams, max_errors=10, careful=False, seq_layout=
         ctx._chk(L.pp_dev_ingest_create(ctx._h, a, max_errors, int(careful), C.byref(g)))
         if seq_layout is not None:
             ctx._chk(L.pp_dev_ingest_set_seq_layout(g, int(seq_layout)))
+        if expect is not None:
+            ctx._chk(L.pp_dev_ingest_expect(g, int(expect)))
         counts = []
         for s in sams:
             c = SamCounts()
-            ctx._chk(L.pp_dev_ingest_sam(g, str(s).encode(), C.byref(c)))
+            vp, nv, _keep = _verdict_args(verdicts, len(counts))
+            if _keep is not None:
+                ctx._chk(L.pp_dev_ingest_sam_filtered(g, str(s).encode(), vp, nv, C.byref(c)))
+            else:
+                ctx._chk(L.pp_dev_ingest_sam(g, str(s).encode(), C.byref(c)))
             counts.append((c.alignments, c.used, c.reads))
         b = AlnBatch()
         L.pp_dev_ingest_batch(g, C.byref(b))

@@ -611,9 +611,6 @@ static int ingest_impl(pp_ingest *I, const char *path, const char *ext_text, siz
             }
         });
         lap("flatten");
-        if (pass && !prefix_mode && n_chunks_ok == threads && n_pass != total_recs)
-            fail(PP_ERR_ARG, "%llu filter verdicts for the %llu aligned records of \"%s\"", (unsigned long long)n_pass,
-                 (unsigned long long)total_recs, path);
         const bool parse_failed = n_chunks_ok < threads;  // the group pending at the failing line is never processed
         auto is_start = [&](size_t i) {
             if (i == 0) return true;
@@ -715,6 +712,12 @@ static int ingest_impl(pp_ingest *I, const char *path, const char *ext_text, siz
             if (ch.err_what == NOT_UTF8) fail(ch.err_code, "unable to load alignments from \"%s\"", path);
             fail(ch.err_code, "%s", ch.err_what.c_str());
         }
+        // a verdict array that is there must have one byte per aligned record (pass == NULL: no verdicts, whatever n_pass says).
+        // Said once the text has been found free of defects -- the verdicts that are there were applied, a record beyond them
+        // passes --, the order the device tokenizer reports in as well (pp_tokenize.hip)
+        if (pass && !prefix_mode && n_pass != total_recs)
+            fail(PP_ERR_ARG, "%llu filter verdicts for the %llu aligned records of \"%s\"", (unsigned long long)n_pass,
+                 (unsigned long long)total_recs, path);
         if (total_recs == 0 && prefix_mode) {  // nothing had been processed before the failure
             cleanup();
             if (counts) *counts = c;

@@ -877,16 +877,17 @@ static int ingest_text(pp_dev_ingest *D, const char *path, const char *text, u64
     // ---- read groups and gates ----
     u32 n_groups = 0;
     const u8 *d_pass = nullptr;
+    // one rule with the host ingest (pp_ingest.cpp): a verdict array that is there (pass != NULL) must have one byte per aligned
+    // record; the verdicts it does have are applied -- a record beyond them passes -- so that the read groups, and with them the
+    // first event of the text, are the host's, and a wrong count is PP_ERR_ARG once the text has been found free of defects
     if (pass && n_aln) {
-        if (n_pass != n_aln)  // cannot be a parse error's doing: those are reported first, below
-            pass = nullptr;
-        else {
-            ENS(d_pass, n_aln);
-            PP_HIPCHK(ctx, hipMemcpyAsync(D->d_pass.p, pass, n_aln, hipMemcpyHostToDevice, st));
-            d_pass = (const u8 *)D->d_pass.p;
-        }
+        ENS(d_pass, n_aln);
+        PP_HIPCHK(ctx, hipMemsetAsync(D->d_pass.p, 1, n_aln, st));
+        const u64 n_copy = std::min<u64>(n_pass, n_aln);
+        if (n_copy) PP_HIPCHK(ctx, hipMemcpyAsync(D->d_pass.p, pass, n_copy, hipMemcpyHostToDevice, st));
+        d_pass = (const u8 *)D->d_pass.p;
     }
-    const bool pass_mismatch = n_pass && !d_pass && n_aln;
+    const bool pass_mismatch = pass && n_pass != n_aln;
     const bool window_layout = D->seq_layout == PP_SEQ_WINDOW_GROUPED;
     const u64 G_asm = pp_assembly_offsets(D->asmb)[pp_assembly_n_contigs(D->asmb)];
     const u32 n_win = (u32)std::max<u64>(1, (G_asm + pp::TILE - 1) / pp::TILE);

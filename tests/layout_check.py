@@ -1,5 +1,7 @@
 """Invariants of a batch's seq array as the library's ingests lay it out (include/polypolish_hip.h: PP_SEQ_ALIGN,
 PP_SEQ_WINDOW_GROUPED), shared by the CPU and the GPU tests.  Test infrastructure."""
+import os
+
 import numpy as np
 
 WINDOW = 2048  # the pileup kernel's window (pp::TILE)
@@ -101,3 +103,51 @@ def check_window_order_mirror(recs, contig_off, used_per_file, file_order_inside
     if "wo_runs" in recs:
         want = [int(e) for e, c in zip(np.cumsum(used_per_file), used_per_file) if c]
         assert [int(e) for e in recs["wo_runs"]] == want, (recs["wo_runs"], want)
+
+
+def same_ingest(pp, ctx, fasta, sams, **kw):
+    """The device tokenizer against the host ingest on the same files: the same error (code and message), or the same counts
+    and records -- array by array in file order, the same records and a valid layout when window-grouped -- with the 4-bit
+    mirror and the window-order mirror of both checked.  Returns (the host ingest's result, its error)."""
+    try:
+        want = pp.ingest(fasta, sams, **kw)
+        we = None
+    except pp.PolypolishError as e:
+        want, we = None, (e.code, e.msg)
+    try:
+        got = pp.ingest_device(ctx, fasta, sams, **kw)
+        ge = None
+    except pp.PolypolishError as e:
+        got, ge = None, (e.code, e.msg)
+    assert ge == we, (ge, we)
+    if want is not None:
+        assert got[5] == want[5], (got[5], want[5])
+        grouped = kw.get("seq_layout", None) != 0 and os.environ.get("PP_SEQ_LAYOUT") != "file"
+        if grouped:  # window-grouped: the same records, the same layout up to the order inside a window
+            same_records(want[4], got[4])
+            used = [c[1] for c in want[5]]
+            check_seq_layout(want[4], want[2], used, grouped=True, file_order_inside=True)
+            check_seq_layout(got[4], want[2], used, grouped=True)
+        else:
+            for k in want[4]:
+                if k != "wo":  # (inside a window the tokenizer's mirror is in the order of its atomics)
+                    assert np.array_equal(got[4][k], want[4][k]), k
+        # the 4-bit mirror the tokenizer hands over with its batch (pp_aln_batch.seq4): base i of the seq ARRAY in nibble i
+        check_seq4_mirror(pp, got[4], expect=os.environ.get("PP_SEQ4") != "0")
+        # the window-order mirror of the records (pp_aln_batch.wo) of both ingests
+        if len(want[4]["contig"]):
+            check_window_order_mirror(want[4], want[2], [c[1] for c in want[5]], file_order_inside=True)
+            check_window_order_mirror(got[4], want[2], [c[1] for c in want[5]])
+    return want, we
+
+
+def check_seq4_mirror(pp, recs, expect):
+    """The 4-bit mirror the tokenizer hands over with its batch (pp_aln_batch.seq4): base i of the seq ARRAY in nibble i."""
+    assert ("seq4" in recs) == expect
+    if expect:
+        n = len(recs["seq"])
+        assert len(recs["seq4"]) == (n + 1) // 2
+        ref4 = pp.pack_seq4(recs["seq"])
+        assert np.array_equal(recs["seq4"][:n // 2], ref4[:n // 2])
+        if n & 1:
+            assert (recs["seq4"][n // 2] & 15) == (ref4[n // 2] & 15)

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import synth
-from layout_check import check_seq_layout, check_window_order_mirror, same_records
+from layout_check import check_seq4_mirror, check_seq_layout, check_window_order_mirror, same_ingest, same_records
 
 pytestmark = pytest.mark.gpu
 C_u64 = ctypes.c_uint64
@@ -777,11 +777,11 @@ def test_window_grouped_seq_layout_of_the_tokenizer(ctx, pp, orc, tmp_path):
     for g in (got, got1):
         same_records(want, g)
         check_seq_layout(g, off, used, grouped=True)
-        _check_mirror(pp, g, expect=True)   # the batch brings the 4-bit mirror of its seq array
+        check_seq4_mirror(pp, g, expect=True)   # the batch brings the 4-bit mirror of its seq array
     _, _, _, _, flat_h, _ = pp.ingest(ds["fasta"], sams, seq_layout=0)
     _, _, _, _, flat_d, _ = pp.ingest_device(ctx, ds["fasta"], sams, seq_layout=0)
     check_seq_layout(flat_d, off, used, grouped=False)
-    _check_mirror(pp, flat_d, expect=True)
+    check_seq4_mirror(pp, flat_d, expect=True)
     for k in flat_h:
         if k != "wo":
             assert np.array_equal(flat_h[k], flat_d[k]), k
@@ -814,51 +814,6 @@ def test_multi_process_driver_on_one_gpu(orc, tmp_path):
     assert r.stdout == orc.polish_files(ds["fasta"], sams)["fasta"]
 
 
-def _same_ingest(pp, ctx, fasta, sams, **kw):
-    try:
-        want = pp.ingest(fasta, sams, **kw)
-        we = None
-    except pp.PolypolishError as e:
-        want, we = None, (e.code, e.msg)
-    try:
-        got = pp.ingest_device(ctx, fasta, sams, **kw)
-        ge = None
-    except pp.PolypolishError as e:
-        got, ge = None, (e.code, e.msg)
-    assert ge == we, (ge, we)
-    if want is not None:
-        assert got[5] == want[5], (got[5], want[5])
-        grouped = kw.get("seq_layout", None) != 0 and os.environ.get("PP_SEQ_LAYOUT") != "file"
-        if grouped:  # window-grouped: the same records, the same layout up to the order inside a window
-            same_records(want[4], got[4])
-            used = [c[1] for c in want[5]]
-            check_seq_layout(want[4], want[2], used, grouped=True, file_order_inside=True)
-            check_seq_layout(got[4], want[2], used, grouped=True)
-        else:
-            for k in want[4]:
-                if k != "wo":  # (inside a window the tokenizer's mirror is in the order of its atomics)
-                    assert np.array_equal(got[4][k], want[4][k]), k
-        # the 4-bit mirror the tokenizer hands over with its batch (pp_aln_batch.seq4): base i of the seq ARRAY in nibble i
-        _check_mirror(pp, got[4], expect=os.environ.get("PP_SEQ4") != "0")
-        # the window-order mirror of the records (pp_aln_batch.wo) of both ingests
-        if len(want[4]["contig"]):
-            check_window_order_mirror(want[4], want[2], [c[1] for c in want[5]], file_order_inside=True)
-            check_window_order_mirror(got[4], want[2], [c[1] for c in want[5]])
-    return want, we
-
-
-def _check_mirror(pp, recs, expect):
-    """The 4-bit mirror the tokenizer hands over with its batch (pp_aln_batch.seq4): base i of the seq ARRAY in nibble i."""
-    assert ("seq4" in recs) == expect
-    if expect:
-        n = len(recs["seq"])
-        assert len(recs["seq4"]) == (n + 1) // 2
-        ref4 = pp.pack_seq4(recs["seq"])
-        assert np.array_equal(recs["seq4"][:n // 2], ref4[:n // 2])
-        if n & 1:
-            assert (recs["seq4"][n // 2] & 15) == (ref4[n // 2] & 15)
-
-
 @pytest.mark.parametrize("case", FILE_CASES, ids=[f"seed{c['seed']}" for c in FILE_CASES])
 @pytest.mark.parametrize("careful", [False, True])
 def test_device_tokenizer_equals_host_ingest(pp, ctx, tmp_path, case, careful, monkeypatch):
@@ -870,7 +825,7 @@ def test_device_tokenizer_equals_host_ingest(pp, ctx, tmp_path, case, careful, m
     if careful:
         monkeypatch.setenv("PP_SEQ_LAYOUT", "file")
     ds = synth.rich_dataset(str(tmp_path), lowercase_frac=0.2, **case)
-    want, err = _same_ingest(pp, ctx, ds["fasta"], [ds["sam1"], ds["sam2"]], max_errors=10, careful=careful)
+    want, err = same_ingest(pp, ctx, ds["fasta"], [ds["sam1"], ds["sam2"]], max_errors=10, careful=careful)
     assert err is None and len(want[4]["contig"]) > 0
 
 
@@ -889,7 +844,7 @@ def test_device_tokenizer_details_and_errors(pp, ctx, orc, tmp_path):
             + line("r6", 0, "c", 3, "5M", ref[2:7]) + line("r5", 0, "e", 1, "2M1I1M", "GGAG", "NM:i:1\tNM:i:0\t").rstrip("\n"))
     sam = tmp_path / "a.sam"
     sam.write_text(good)
-    want, err = _same_ingest(pp, ctx, str(fa), [str(sam)])
+    want, err = same_ingest(pp, ctx, str(fa), [str(sam)])
     assert err is None and list(want[4]["k"]) == [2, 2, 2, 2, 1]   # the empty QNAME pulls r6 into its group
     many = "".join(line(f"q{i}", 0, "c", 1 + i % 10, "12M", ref[i % 10:i % 10 + 12]) for i in range(3000))
     cases = [
@@ -911,22 +866,22 @@ def test_device_tokenizer_details_and_errors(pp, ctx, orc, tmp_path):
     for i, text in enumerate(cases):
         p = tmp_path / f"e{i}.sam"
         p.write_text(text)
-        _, err = _same_ingest(pp, ctx, str(fa), [str(p)])
+        _, err = same_ingest(pp, ctx, str(fa), [str(p)])
         assert err is not None, i
         seen.add(err[0])
     assert seen == {1, 101}
     # two files: the batch grows across calls
-    want, err = _same_ingest(pp, ctx, str(fa), [str(sam), str(sam)])
+    want, err = same_ingest(pp, ctx, str(fa), [str(sam), str(sam)])
     assert err is None and len(want[4]["contig"]) == 10
     # CRLF line ends, with and without a final newline; a file that is one line without newline
     crlf = tmp_path / "crlf.sam"
     crlf.write_bytes(good.replace("\n", "\r\n").encode())
-    want, err = _same_ingest(pp, ctx, str(fa), [str(crlf)])
+    want, err = same_ingest(pp, ctx, str(fa), [str(crlf)])
     assert err is None and len(want[4]["contig"]) == 5
     crlf.write_bytes((good + "\n").replace("\n", "\r\n").encode())
-    assert _same_ingest(pp, ctx, str(fa), [str(crlf)])[1] is None
+    assert same_ingest(pp, ctx, str(fa), [str(crlf)])[1] is None
     crlf.write_text(line("solo", 0, "e", 1, "4M", "GGGG").rstrip("\n"))
-    want, err = _same_ingest(pp, ctx, str(fa), [str(crlf)])
+    want, err = same_ingest(pp, ctx, str(fa), [str(crlf)])
     assert err is None and list(want[4]["seq_len"]) == [4]
     # `polish` without any SAM file is legal (every position low_depth): the CLI through either ingest
     want_fasta = orc.polish_files(str(fa), [])["fasta"]
@@ -974,7 +929,7 @@ def test_fuzz_device_parsers_against_the_host_parsers(pp, ctx, tmp_path):
         open(f1, "w").write(synth.mutate_sam(base1, rng, int(rng.integers(1, 5))))
         open(f2, "w").write(synth.mutate_sam(base2, rng, int(rng.integers(0, 3))))
         careful = bool(trial % 5 == 0)
-        want, err = _same_ingest(pp, ctx, ds["fasta"], [f1, f2], max_errors=int(rng.choice([0, 2, 10])), careful=careful)
+        want, err = same_ingest(pp, ctx, ds["fasta"], [f1, f2], max_errors=int(rng.choice([0, 2, 10])), careful=careful)
         outcomes["error" if err else "ok"] += 1
         # the filter's loaders
         try:
