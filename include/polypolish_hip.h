@@ -148,8 +148,8 @@ typedef struct {
      * parts of pp_shard_split, or a part of one of those) is compared with the arrays on the device before anything reads the
      * records through it -- every entry a record of the batch, none twice, contig / ref_start / k / seq_off / seq_len / first
      * run the record's -- and one that does not stand the comparison is left aside: the job runs without it and gives the
-     * same bytes.  The comparison is a scattered read of the arrays (about 1 ms per 6.7 M records): a caller whose mirror is
-     * not worth that should not pass one. */
+     * same bytes.  The comparison is a scattered read of the arrays (about 1 ms per 6.7 M records): a caller who has no cheap
+     * mirror of its own hands the batch to pp_batch_prepare (below) instead, whose result is one of the library's own. */
     const struct pp_wo_rec *wo;
     /* Optional with wo (0 / NULL = not known): the mirror as RUNS.  wo_n_runs stretches of entries, one behind the other
      * (one per SAM file, as the library's ingests write it), each of them window-grouped IN ASCENDING WINDOW ORDER;
@@ -187,6 +187,37 @@ typedef struct pp_wo_rec {
 #define PP_SEQ4_N 4
 #define PP_SEQ4_DASH 5
 #define PP_SEQ4_OTHER 15
+
+/* ANY valid batch laid out as the library's ingests lay theirs out, on the device: the way to the direct path
+ * (pp_polish_took_direct_path) for a caller who holds alignments but no SAM text -- a binding that parses SAM or BAM itself,
+ * anything that edits or filters records.  The result is a batch of the library's own (pp_prepared_batch: DEVICE memory of the
+ * context's device, owned by the object, valid until pp_prepared_free): the records in the SAME order as in `batch` (file
+ * order: it fixes the f64 depth and the "first offending record"); contig / ref_start / k / seq_len / cig_off / n_cig / cigar
+ * copied as they are; every record's SEQ bytes in a room of its own of (seq_len + 31) & ~31 bytes -- the rooms tile the new
+ * seq array, WINDOW-GROUPED (PP_SEQ_WINDOW_GROUPED), zeros behind a read up to the boundary -- and seq_off rewritten; seq4 = the
+ * 4-bit mirror of the new seq array with the slack it needs; wo = the window-order mirror as ONE run (wo_n_runs = 1, wo_run_end =
+ * {n_aln}: the windows ascend over the whole batch, inside a window in any order -- the kernels order a position's alignments
+ * by the file index the entries carry, so the records of several SAM files need no runs of their own).  A record whose contig
+ * index is out of range goes with the last window.  pp_polish_add takes the mirror unchecked; a prepared batch that is its
+ * job's only batch is polished in place, job after job.
+ *   contig_off   HOST, n_contigs + 1, as for pp_polish_begin (the windows are those of this assembly)
+ *   mem          PP_MEM_HOST or PP_MEM_DEVICE (where `batch` lives); its seq4 / wo / wo_run_end are ignored: the result is a
+ *                function of the nine arrays alone.  The source may be released when the call returns (the context's stream
+ *                has been synchronised).
+ * Nothing is validated that the polish reports later; the call is memory-safe for any contents of the arrays: a record whose
+ * [seq_off, seq_off + seq_len) does not lie inside the source's seq array is not read, gets no bytes and keeps a seq_off outside
+ * the prepared array, so pp_polish_finish names the same record with the same message as on `batch` itself.
+ * PP_ERR_ARG: null arguments, n_contigs == 0, descending contig_off, PP_MEM_PEER, a null array in a non-empty batch;
+ * PP_ERR_LIMIT: the limits of pp_polish_begin / pp_polish_add (assembly < 2^32-4096 bp, < 2^32-1 records, < 2^40 SEQ bytes --
+ * of rooms, too) and 2^24 records that start in one window.  An empty batch prepares to an empty batch. */
+typedef struct pp_prepared pp_prepared;
+int pp_batch_prepare(pp_ctx *ctx, uint32_t n_contigs, const uint64_t *contig_off, const pp_aln_batch *batch, int mem,
+                     pp_prepared **out);
+void pp_prepared_batch(const pp_prepared *p, pp_aln_batch *out); /* borrowed view, DEVICE memory */
+/* HIP-event time of the prepare's kernels (placement + copy; not the upload of a host batch); PP_ERR_ARG unless the context
+ * had profiling on (pp_ctx_set_profiling) when the batch was prepared */
+int pp_prepared_kernel_ms(const pp_prepared *p, float *ms);
+void pp_prepared_free(pp_prepared *p);
 
 /* Per-contig figures the reference prints to stderr (src/polish.rs:206-227). */
 typedef struct {

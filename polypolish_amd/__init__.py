@@ -179,6 +179,7 @@ EXPORTS = [
     "pp_shard_split", "pp_shard_part_batch", "pp_shard_part_mem", "pp_shard_part_free", "pp_shard_count",
     "pp_polish_error_record", "pp_polish_error_text", "pp_dev_ingest_set_seq_layout", "pp_dev_ingest_expect",
     "pp_ingest_set_seq_layout", "pp_polish_debug_tsv",
+    "pp_batch_prepare", "pp_prepared_batch", "pp_prepared_kernel_ms", "pp_prepared_free",
 ]
 
 _lib = None
@@ -299,6 +300,12 @@ def lib():
         L.pp_shard_count.argtypes = [vp, C.POINTER(AlnBatch), C.c_int, C.c_uint32, vp]
         L.pp_polish_error_record.argtypes = [vp, u64p, C.POINTER(C.c_uint32)]
         L.pp_polish_error_text.argtypes = [vp, C.c_uint32, C.c_uint64]
+        L.pp_batch_prepare.argtypes = [vp, C.c_uint32, vp, C.POINTER(AlnBatch), C.c_int, C.POINTER(vp)]
+        L.pp_prepared_batch.argtypes = [vp, C.POINTER(AlnBatch)]
+        L.pp_prepared_batch.restype = None
+        L.pp_prepared_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.pp_prepared_free.argtypes = [vp]
+        L.pp_prepared_free.restype = None
         _lib = L
     return _lib
 
@@ -608,6 +615,85 @@ def shard_split_host(plan, dest, recs):
         out[0]["wo_runs"] = part.ptrs["wo_runs"]
     part.close()
     return out
+
+
+class PreparedBatch:
+    """pp_batch_prepare: any valid batch (raw pointers `ptrs`: field name -> address, host or device as `mem` says) laid out
+    on the device as the library's ingests lay theirs out -- window-grouped SEQ rooms, the 4-bit mirror, the window-order mirror
+    as one run -- and owned by this object: the way to the direct path for a batch the caller made.
+      .n_aln, .seq_bytes, .n_cig_total
+      .ptrs()       what Context.polish_add_ptrs / prepared_job take, with mem = MEM_DEVICE (valid until close())
+      .host()       numpy copies of every array, "wo", "wo_runs" and "seq4" included
+      .kernel_ms()  HIP-event time of the prepare's kernels (the context had set_profiling on)"""
+
+    def __init__(self, ctx, contig_off, n_aln, ptrs, seq_bytes, n_cig_total, mem):
+        L = lib()
+        off = np.ascontiguousarray(contig_off, dtype=np.uint64)
+        b = aln_batch(n_aln, ptrs, seq_bytes, n_cig_total)
+        self._p = C.c_void_p()
+        self._ctx = ctx  # keeps the context (and with it the batch's device memory) alive
+        ctx._chk(L.pp_batch_prepare(ctx._h, len(off) - 1, off.ctypes.data, C.byref(b), mem, C.byref(self._p)))
+        out = AlnBatch()
+        L.pp_prepared_batch(self._p, C.byref(out))
+        self.mem = MEM_DEVICE
+        self.n_aln, self.seq_bytes, self.n_cig_total = int(out.n_aln), int(out.seq_bytes), int(out.n_cig_total)
+        self._ptrs = {name: (C.cast(getattr(out, name), C.c_void_p).value or 0) for name, _ in REC_FIELDS}
+        if out.seq4:
+            self._ptrs["seq4"] = out.seq4
+        if out.wo:
+            self._ptrs["wo"] = out.wo
+            self._ptrs["wo_runs"] = _runs_of(out)
+
+    def ptrs(self):
+        return dict(self._ptrs)
+
+    def host(self):
+        L, ctx = lib(), self._ctx
+        sizes = {"seq": self.seq_bytes, "cigar": self.n_cig_total}
+        recs = {}
+        for name, dt in REC_FIELDS:
+            arr = np.zeros(int(sizes.get(name, self.n_aln)), dtype=dt)
+            if arr.size and self._ptrs[name]:
+                ctx._chk(L.pp_ctx_download(ctx._h, arr.ctypes.data, self._ptrs[name], arr.nbytes))
+            recs[name] = arr
+        m = np.zeros((self.seq_bytes + 1) // 2, dtype=np.uint8)
+        if m.size and self._ptrs.get("seq4"):
+            ctx._chk(L.pp_ctx_download(ctx._h, m.ctypes.data, self._ptrs["seq4"], m.nbytes))
+        recs["seq4"] = m
+        w = np.zeros(self.n_aln, dtype=WO_DTYPE)
+        if self.n_aln and self._ptrs.get("wo"):
+            ctx._chk(L.pp_ctx_download(ctx._h, w.ctypes.data, self._ptrs["wo"], w.nbytes))
+        recs["wo"] = w
+        recs["wo_runs"] = np.array(self._ptrs.get("wo_runs", []), dtype=np.uint64)
+        return recs
+
+    def kernel_ms(self):
+        ms = C.c_float()
+        self._ctx._chk(lib().pp_prepared_kernel_ms(self._p, C.byref(ms)))
+        return float(ms.value)
+
+    def close(self):
+        if self._p:
+            lib().pp_prepared_free(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def prepare_batch(ctx, contig_off, n_aln, ptrs, seq_bytes, n_cig_total, mem):
+    """pp_batch_prepare on a batch given by pointers: returns a PreparedBatch."""
+    return PreparedBatch(ctx, contig_off, n_aln, ptrs, seq_bytes, n_cig_total, mem)
+
+
+def prepare_records(ctx, contig_off, recs):
+    """pp_batch_prepare on host numpy records (field names of pp_aln_batch, REC_FIELDS), as Context.polish_records takes them."""
+    keep = {k: np.ascontiguousarray(recs[k], dtype=dt) for k, dt in REC_FIELDS}
+    ptrs = {k: v.ctypes.data for k, v in keep.items()}
+    return PreparedBatch(ctx, contig_off, len(keep["contig"]), ptrs, len(keep["seq"]), len(keep["cigar"]), MEM_HOST)
 
 
 def shard_count(ctx, n_aln, contig_ptr, mem, n_contigs, ptrs=None):

@@ -246,6 +246,25 @@ __device__ __forceinline__ int op_code(u8 c) {
     }
 }
 
+// ---- the 4-bit mirror of SEQ bytes (pp_aln_batch.seq4), packed while the bytes are in registers (the tokenizer's k_tok_seq,
+// pp_batch_prepare's k_prep_copy) ----------------------------------------------------------------------
+__device__ __forceinline__ u32 seq4_code(u32 c) {
+    const u32 t = (c >> 1) & 3u;  // A->0 C->1 T->2 G->3: the counter rows
+    const u32 expect = (0x47544341u >> (t * 8u)) & 0xFFu;
+    return c == expect ? t : (c == (u32)'N' ? (u32)PP_SEQ4_N : (c == (u32)'-' ? (u32)PP_SEQ4_DASH : (u32)PP_SEQ4_OTHER));
+}
+__device__ __forceinline__ uint2 pack4_16(const u32 w[4]) {  // 16 bytes -> 16 nibbles
+    u32 o[2];
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        u32 v = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) v |= seq4_code((w[2 * q + (j >> 2)] >> (8 * (j & 3))) & 0xFFu) << (4 * j);
+        o[q] = v;
+    }
+    return make_uint2(o[0], o[1]);
+}
+
 // grow a device buffer keeping its first `used` bytes
 int dev_grow(pp_ctx *ctx, pp::DevBuf &b, size_t need, size_t used) {
     if (need == 0) need = 16;

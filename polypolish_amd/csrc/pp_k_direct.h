@@ -22,13 +22,11 @@
 // DE_MIRROR_ORDER: every later kernel returns at once and the host runs the job over the bucketing path.
 #pragma once
 
+#include "pp_wo_home.h"  // wo_home(): the window a record starts in -- shared with the producer pp_batch_prepare (pp_prepare.hip)
+
 namespace pp {
 
 constexpr u32 NOHOME = 0xFFFFFFFFu;
-// the window a record starts in -- the producers' rule (pp_ingest.cpp window_of, pp_tokenize.hip k_tok_meta): clamped
-__device__ __forceinline__ u32 wo_home(u64 c_lo, u32 ref_start, u32 nwin) {
-    return (u32)min((c_lo + ref_start) / (u64)TILE, (u64)(nwin - 1u));
-}
 // "bulk": one M run over the whole read, 1..FAST_MAX_LEN bases, inside its contig (clen = the contig's length).  k_prepd
 // and k_tile must agree on it: a bulk record is tallied from the mirror, every other record through extras.
 __device__ __forceinline__ bool wo_bulk(bool contig_ok, u32 ref_start, u32 seq_len, u32 op0, u64 clen) {

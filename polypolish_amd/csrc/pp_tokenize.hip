@@ -327,23 +327,7 @@ __device__ __forceinline__ u8 comp_upper(u8 c) {  // misc.rs:170-182 on the uppe
 // packed into the mirror (base i of the ARRAY in bits 4*(i&1).. of seq4[i >> 1]: a room starts on a multiple of 32 bytes,
 // so a chunk's eight mirror bytes are its own).  A "*" record takes the group's sequence, reverse-complemented when the
 // strands differ (alignment.rs:161-167, 288-296).  Round 3 packed the mirror in a kernel of its own that read the seq
-// array back (0.4 ms per 2.4 GB of text); here it costs the stores.
-__device__ __forceinline__ u32 seq4_code(u32 c) {
-    const u32 t = (c >> 1) & 3u;  // A->0 C->1 T->2 G->3: the counter rows
-    const u32 expect = (0x47544341u >> (t * 8u)) & 0xFFu;
-    return c == expect ? t : (c == (u32)'N' ? (u32)PP_SEQ4_N : (c == (u32)'-' ? (u32)PP_SEQ4_DASH : (u32)PP_SEQ4_OTHER));
-}
-__device__ __forceinline__ uint2 pack4_16(const u32 w[4]) {  // 16 bytes -> 16 nibbles
-    u32 o[2];
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-        u32 v = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) v |= seq4_code((w[2 * q + (j >> 2)] >> (8 * (j & 3))) & 0xFFu) << (4 * j);
-        o[q] = v;
-    }
-    return make_uint2(o[0], o[1]);
-}
+// array back (0.4 ms per 2.4 GB of text); here it costs the stores.  (seq4_code / pack4_16: pp_devtext.h)
 __global__ __launch_bounds__(256) void k_tok_seq(const u8 *__restrict__ text, const u64 *__restrict__ nl_pos,
                                                  const LineRec *__restrict__ rec, const u32 *__restrict__ rec_line,
                                                  u32 n_aln, const u32 *__restrict__ good, const u32 *__restrict__ src_rec,
