@@ -13,7 +13,6 @@
 
 #include "polypolish_hip.h"
 #include "pp_host.h"
-extern "C" void pp_process_leaving_soon_(int yes);
 
 static const char *HELP =
     "Polypolish (MI355X/gfx950 implementation, parity target v0.6.1)\n"

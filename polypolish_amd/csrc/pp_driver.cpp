@@ -9,7 +9,6 @@
 #include <functional>
 #include <future>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,45 +23,18 @@
 
 namespace {
 
-struct Log {
-    bool quiet;
-    void operator()(const char *fmt, ...) const {
-        if (quiet) return;
-        va_list ap;
-        va_start(ap, fmt);
-        vfprintf(stderr, fmt, ap);
-        va_end(ap);
-    }
-};
-
-// num-format's Locale::en grouping (polish.rs:99 etc.)
-std::string commas(uint64_t v) {
-    std::string s = std::to_string(v), out;
-    int n = (int)s.size();
-    for (int i = 0; i < n; i++) {
-        out.push_back(s[i]);
-        int left = n - 1 - i;
-        if (left > 0 && left % 3 == 0) out.push_back(',');
-    }
-    return out;
-}
+using pph::commas;
+using pph::format_duration;
+using pph::Log;
+using pph::qscore;
 
 bool exists(const char *p) {
     struct stat st;
     return stat(p, &st) == 0;
 }
 
-using pph::format_duration;
-using pph::qscore;
-
-int set_err(pp_ctx *ctx, int code, const char *msg);
-
-}  // namespace
-
-// pp_ctx is opaque here; error text is stored through a tiny hook exported by pp_kernels.hip
-extern "C" int pp_ctx_set_error_(pp_ctx *ctx, int code, const char *msg);
-namespace {
 int set_err(pp_ctx *ctx, int code, const char *msg) { return pp_ctx_set_error_(ctx, code, msg); }
+
 }  // namespace
 
 // (internal, bin/polypolish only) the process exits right after the command: see pph::process_leaving_soon
@@ -74,9 +46,6 @@ extern "C" void pp_bytes_free(pp_bytes *b) {
     b->data = nullptr;
     b->len = 0;
 }
-
-extern "C" void *pp_host_pinned_alloc_(pp_ctx *ctx, uint64_t bytes);
-extern "C" void pp_host_pinned_free_(void *p);
 
 // write_debug_line (polish.rs:257-266) for the positions [lo, hi) of ctx's job: formatted on its device (pp_polish_debug_tsv,
 // pp_k_debug.h) a chunk at a time into two pinned buffers in turn -- the fwrite of one chunk runs on a helper thread while
@@ -112,49 +81,6 @@ static int write_debug_tsv(pp_ctx *ctx, FILE *f, const std::vector<const char *>
     }
     return rc;
 }
-
-static int polish_files_impl(pp_ctx *const *ctxs, int n_ctx, const char *assembly, const char *const *sams, int n_sams,
-                             const pp_polish_options *opt, pp_bytes *fasta, const uint8_t *const *pass,
-                             const uint64_t *n_pass, int resume_log_at = -1);
-extern "C" int pp_dev_ingest_reserve_text_(pp_dev_ingest *D, uint64_t bytes);
-extern "C" void pp_dev_ingest_prefetch_(pp_dev_ingest *D, const char *path, uint64_t second_buffer_bytes);
-extern "C" int pp_ingest_fail_cut_(const pp_ingest *I, uint64_t *cut);
-extern "C" int pp_ingest_sam_prefix_(pp_ingest *I, const char *path, uint64_t cut, const uint8_t *pass, uint64_t n_pass,
-                                     pp_sam_counts *counts, char *err, size_t errlen);
-
-extern "C" int pp_polish_files_filtered_(pp_ctx *ctx, const char *assembly, const char *const *sams, int n_sams,
-                                         const pp_polish_options *opt, pp_bytes *fasta,
-                                         const uint8_t *const *pass, const uint64_t *n_pass) {
-    return polish_files_impl(&ctx, 1, assembly, sams, n_sams, opt, fasta, pass, n_pass);
-}
-
-extern "C" int pp_polish_files(pp_ctx *ctx, const char *assembly, const char *const *sams, int n_sams,
-                               const pp_polish_options *opt, pp_bytes *fasta) {
-    return polish_files_impl(&ctx, 1, assembly, sams, n_sams, opt, fasta, nullptr, nullptr);
-}
-
-// One process, several GPUs (polish::polish has no counterpart: src/polish.rs:137-154 is one thread): every context
-// uploads and tokenizes its own slice of every SAM file (or the host ingest parses once), the records are partitioned --
-// a context is sent the records that reach its units (pp_shard_split) -- the contexts polish side by side on their own
-// threads, and every device copies its own share of the polished bytes out for the host to put together -- or, with
-// PP_GATHER=rccl, the bytes meet on the first context's GPU in ONE RCCL gather over xGMI (pp_polish_gather: the north
-// star's "single RCCL gather for the final FASTA") followed by one device-to-host copy.  The RCCL route of THIS driver is
-// opt-in until it has run on a multi-GPU node (see below); it cannot run without librccl or with two contexts on one
-// device (PP_SHARE_GPU, tests).  PP_TIMING prints the route that was taken.
-extern "C" int pp_polish_files_multi(pp_ctx *const *ctxs, int n_ctx, const char *assembly, const char *const *sams,
-                                     int n_sams, const pp_polish_options *opt, pp_bytes *fasta) {
-    if (!ctxs || n_ctx < 1) return PP_ERR_ARG;
-    for (int i = 0; i < n_ctx; i++)
-        if (!ctxs[i]) return PP_ERR_ARG;
-    return polish_files_impl(ctxs, n_ctx, assembly, sams, n_sams, opt, fasta, nullptr, nullptr);
-}
-
-extern "C" void pp_ctx_enable_peers_(pp_ctx *const *ctxs, int n);
-extern "C" int pp_ctx_device_(const pp_ctx *ctx);
-extern "C" int pp_shard_split_view_(pp_ctx *ctx, const pp_shard_plan *plan, uint32_t dest, const pp_aln_batch *batch, int mem,
-                                    uint32_t wo_idx_base, pp_shard_part **out);
-extern "C" int pp_polish_gather_to_host_(pp_ctx *ctx, uint8_t *host_out, uint64_t cap, uint64_t *rank_len, uint64_t *rank_contig_off);
-extern "C" int pp_dev_ingest_slice_(pp_dev_ingest *D, const char *path, const char *text, uint64_t size, pp_sam_counts *counts);
 
 namespace {
 
@@ -246,582 +172,691 @@ uint64_t job_record_of(pp_ctx *cd, pp_ctx *const *ctxs, const std::vector<Piece>
     return ~0ull;
 }
 
-}  // namespace
+// ---- the polish command: one job object, stages over it ----------------------------------------------------------------
+// a source batch of the multi-context job, in file order: sharded -> a (file, slice) piece living on a context's GPU; host
+// ingest -> a file
+struct Src { pp_aln_batch view; int owner; uint64_t base; uint32_t wo_base; std::vector<uint64_t> runs; };
+// what a context brought back
+struct RankResult {
+    int rc = PP_OK;
+    uint64_t total = 0;
+    std::vector<uint8_t> bytes;
+    std::vector<uint64_t> off;
+    std::vector<pp_contig_stats> stats;
+};
 
-// (tests) where the multi-GPU driver would cut `text` at or after `from`
-extern "C" uint64_t pp_sam_group_cut_(const char *text, uint64_t size, uint64_t from) { return group_cut(text, (size_t)size, (size_t)from); }
+// what an ingest_file_* returns for a file the host ingest must look at again (not a PP_ERR_* code); the caller decides
+constexpr int HAND_BACK = -1;
+int hand_back_if_text_defect(int rc) { return rc == PP_ERR_QUIT || rc == PP_ERR_PANIC || rc == PP_ERR_NOT_ASCII ? HAND_BACK : rc; }
 
-// pass / n_pass: optional per-file filter verdicts (pp_ingest_sam_filtered), used by pp_filter_polish_files
-static int polish_files_impl(pp_ctx *const *ctxs, int n_ctx, const char *assembly, const char *const *sams, int n_sams,
-                             const pp_polish_options *opt, pp_bytes *fasta, const uint8_t *const *pass,
-                             const uint64_t *n_pass, int resume_log_at) {
-    pp_ctx *const ctx = ctxs[0];  // carries the error text
-    if (!ctx || !assembly || !opt || !fasta || (n_sams > 0 && !sams)) return PP_ERR_ARG;
-    const bool multi = n_ctx > 1;
-    fasta->data = nullptr;
-    fasta->len = 0;
-    // resume_log_at >= 0: the second look at an input the device tokenizer handed back (a defect in the text, or bytes
-    // outside ASCII that the host parsers must judge), on the host ingest only.  The banner, the assembly section and the
-    // lines of the files before that one are on stderr already: the log resumes at that file.
-    const bool host_ingest_only = resume_log_at >= 0;
-    Log log{opt->quiet != 0 || host_ingest_only};
-    auto t0 = std::chrono::steady_clock::now();
-    char err[1024] = "";
-
-    // check_option_values (polish.rs:277-287) is repeated by pp_polish_begin; do it first as the reference does
-    if (opt->fraction_valid <= 0.0 || opt->fraction_valid >= 1.0)
-        return set_err(ctx, PP_ERR_QUIT, "--fraction_valid must be between 0 and 1 (exclusive)");
-    if (opt->fraction_invalid <= 0.0 || opt->fraction_invalid >= 1.0)
-        return set_err(ctx, PP_ERR_QUIT, "--fraction_invalid must be between 0 and 1 (exclusive)");
-    if (opt->fraction_invalid >= opt->fraction_valid)
-        return set_err(ctx, PP_ERR_QUIT, "--fraction_invalid must be less than --fraction_valid");
-    // check_inputs_exist, polish.rs:269-274
-    if (!exists(assembly)) {
-        snprintf(err, sizeof err, "\"%s\" file does not exist", assembly);
-        return set_err(ctx, PP_ERR_QUIT, err);
-    }
-    for (int i = 0; i < n_sams; i++)
-        if (!exists(sams[i])) {
-            snprintf(err, sizeof err, "\"%s\" file does not exist", sams[i]);
-            return set_err(ctx, PP_ERR_QUIT, err);
-        }
-
-    // The device tokenizer uploads the SAM text as it is: map the files and pre-fault the mappings NOW, on background
-    // threads, while the HIP runtime is still initialising (a copy out of an untouched mapping runs at a quarter of
-    // the link's rate).
+// Everything one `polish` command allocates, opens or starts.  release() gives all of it back -- uploads in flight are joined
+// before the batches they read are freed, the FASTA buffer's toucher before the buffer -- and the destructor calls it: every
+// way out of the driver is a plain return.
+struct PolishJob {
+    pp_ctx *const *ctxs;
+    int n_ctx;
+    const char *assembly;
+    const char *const *sams;
+    int n_sams;
+    const pp_polish_options *opt;
+    // optional per-file filter verdicts (pp_ingest_sam_filtered), used by pp_filter_polish_files
+    const uint8_t *const *pass;
+    const uint64_t *n_pass;
+    // resume_log_at >= 0: the second look at an input the device tokenizer handed back, on the host ingest only.  The banner,
+    // the assembly section and the lines of the files before that one are on stderr already: the log resumes at that file.
+    int resume_log_at;
+    int handed_back_at = -1;  // the file at which this look ended with HAND_BACK
+    pp_ctx *ctx = ctxs[0];    // carries the error text
     // Several contexts: every GPU uploads and tokenizes its own slice of each file (`sharded`), so a byte of text crosses
     // PCIe once; the host ingest (PP_DEVICE_INGEST=0, or a file the tokenizer handed back) parses once and sends every
     // context the records that reach its units.
-    const bool dev_ingest = !host_ingest_only && !(getenv("PP_DEVICE_INGEST") && atoi(getenv("PP_DEVICE_INGEST")) == 0);
-    if (dev_ingest)
-        for (int i = 0; i < n_sams; i++) pph::prefetch_file(sams[i], ctx);
-    struct DropPrefetched { const void *owner; ~DropPrefetched() { pph::prefetch_drop_all(owner); } } drop_prefetched{ctx};
-
-    // starting_message, polish.rs:41-73
-    log("\nStarting Polypolish polish\n%s\n\nInput assembly:\n  %s\n\nInput short-read alignments:\n", pp_version(), assembly);
-    for (int i = 0; i < n_sams; i++) log("  %s\n", sams[i]);
-    log("\nSettings:\n  --fraction_invalid %g\n  --fraction_valid %g\n  --max_errors %u\n  --min_depth %u\n",
-        opt->fraction_invalid, opt->fraction_valid, opt->max_errors, opt->min_depth);
-    if (opt->careful) log("  --careful\n");
-    if (opt->debug_path) log("  --debug %s\n\n", opt->debug_path);
-    else log("  not logging debugging information\n\n");
-
-    const bool timing = getenv("PP_TIMING") != nullptr;
-    // PP_TIMING=1: "[timing] <stage>  <seconds since the driver was entered>  (<seconds since the process started>)"
-    auto lap = [&](const char *what) {
-        if (timing) fprintf(stderr, "[timing] %-36s %8.3f s  (process %7.3f s)\n", what,
-                            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), pph::seconds_since_process_start());
-    };
-    lap("driver entered");
-    // load_assembly, polish.rs:93-106
-    log("Loading assembly\n");
-    pp_assembly *a = nullptr;
-    int rc = pp_assembly_load(assembly, &a, err, sizeof err);
-    if (rc) return set_err(ctx, rc, err);
-    const uint32_t nc = pp_assembly_n_contigs(a);
-    const uint64_t *off = pp_assembly_offsets(a);
-    for (uint32_t c = 0; c < nc; c++) log("%s (%s bp)\n", pp_assembly_name(a, c), commas(off[c + 1] - off[c]).c_str());
-    log("\n");
-
-    lap("assembly loaded");
-    // The FASTA that will be returned: headers + polished bytes.  Its buffer is allocated for an upper bound NOW and touched
-    // by a helper thread while the alignments are loaded -- the polished bytes then come off the device straight into their
-    // place in it (a fresh 250 MB destination took 30 ms of page faults inside the copy, and assembling the FASTA from a
-    // second buffer another 40 ms of memcpy).
-    size_t fasta_cap = 0;
-    for (uint32_t c = 0; c < nc; c++) fasta_cap += strlen(pp_assembly_name(a, c)) + strlen(pp_assembly_description(a, c)) + 16;
-    const size_t header_bytes = fasta_cap;
-    fasta_cap += (size_t)(off[nc] + off[nc] / 8) + 2 * (size_t)nc + 65536;  // (every planted insertion adds a byte: far below 1/8)
-    uint8_t *out = (uint8_t *)malloc(fasta_cap);
-    std::thread out_toucher;
-    if (out) out_toucher = std::thread([out, fasta_cap] { for (size_t q = 0; q < fasta_cap; q += 4096) out[q] = 0; });
-    // (every way out of this function: the helper joined first, then the buffer released unless it went to the caller)
-    struct OutGuard { std::thread &t; uint8_t *&p; ~OutGuard() { if (t.joinable()) t.join(); free(p); } } out_guard{out_toucher, out};
-    // load_alignments, polish.rs:109-134 -- by the device tokenizer (pp_tokenize.hip), or on the host (multi-threaded
-    // parse) with PP_DEVICE_INGEST=0
-    log("Loading alignments\n");
-    pp_ingest *g = nullptr;
-    pp_dev_ingest *dg = nullptr;
-    std::vector<pp_dev_ingest *> dgs((size_t)(multi && dev_ingest ? n_ctx : 0), nullptr);  // sharded ingest: one per context
-    // Host ingest: one ingest object per SAM file, and (one context) the batch of file i goes to the device (pp_polish_begin +
-    // pp_polish_add on a helper thread) while file i+1 is parsed -- the reference streams its files one after the other as
-    // well (alignment.rs:238-265).  Several contexts: the files' batches wait until the plan is known, then every context is
-    // sent its part.
-    const bool per_file = !dev_ingest && (multi || !(getenv("PP_STREAM_ADDS") && atoi(getenv("PP_STREAM_ADDS")) == 0));
-    const bool stream_adds = per_file && !multi;
-    std::vector<pp_ingest *> gs;
-    std::vector<std::future<int>> pending;  // the upload of the file before
-    std::vector<uint64_t> per_contig(nc, 0);  // alignment records per contig (the planner's weights)
-    bool begun = false;
+    // Host ingest: one ingest object per SAM file (`per_file`), and (one context: `stream_adds`) the batch of file i goes to the
+    // device (pp_polish_begin + pp_polish_add on a helper thread) while file i+1 is parsed -- the reference streams its files
+    // one after the other as well (alignment.rs:238-265).  Several contexts: the files' batches wait until the plan is known,
+    // then every context is sent its part.
+    static bool off_by_env(const char *name) { return getenv(name) && atoi(getenv(name)) == 0; }
+    bool multi = n_ctx > 1;
+    bool dev_ingest = resume_log_at < 0 && !off_by_env("PP_DEVICE_INGEST");
+    bool sharded = multi && dev_ingest;
+    bool per_file = !dev_ingest && (multi || !off_by_env("PP_STREAM_ADDS"));
+    bool stream_adds = per_file && !multi;
+    Log log{opt->quiet != 0 || resume_log_at >= 0};
+    pph::Lap lap{"", 36, true};  // "[timing] <stage>  <seconds since the driver was entered>  (process <seconds>)"
     pp_params prm{opt->min_depth, opt->fraction_valid, opt->fraction_invalid};
-    auto wait_pending = [&]() {
+    char err[1024] = "";
+    pp_assembly *a = nullptr;
+    uint32_t nc = 0;
+    const uint64_t *off = nullptr;
+    std::vector<const char *> names;
+    uint8_t *out = nullptr;  // the FASTA that will be returned (reserve_fasta)
+    size_t fasta_cap = 0;
+    size_t header_bytes = 0;
+    std::thread out_toucher;
+    std::vector<uint64_t> sam_bytes;  // the SAM files' sizes on disk (0: not a regular file)
+    pp_ingest *g = nullptr;           // host ingest, all files in one ...
+    std::vector<pp_ingest *> gs;      // ... or one per file
+    pp_dev_ingest *dg = nullptr;
+    std::vector<pp_dev_ingest *> dgs;       // sharded ingest: one per context
+    std::vector<std::future<int>> pending;  // the upload of the file before
+    bool begun = false;                     // pp_polish_begin has run on ctx
+    uint64_t alignment_total = 0;
+    uint64_t used_total = 0;
+    // sharded: the records of file i's slice on context s are records [slice_end[i-1][s], slice_end[i][s]) of its batch
+    std::vector<std::vector<uint64_t>> slice_end;
+    std::vector<Src> srcs;
+    pp_shard_plan *plan = nullptr;
+    std::vector<std::vector<Piece>> pieces;  // [context][source]: the parts (owned here from the split on) in file order
+    bool use_rccl = false;                   // the gather route
+    bool comms = false;                      // the communicators exist
+    std::vector<RankResult> ranks;
+    std::vector<uint8_t> gathered;
+    FILE *dbg = nullptr;
+    bool debug_set = false;  // pp_polish_set_debug was called on the contexts
+    uint64_t total = 0;
+    bool direct_fetch = false;
+    std::vector<uint8_t> polished = std::vector<uint8_t>(1);
+    std::vector<uint64_t> out_off;
+    std::vector<pp_contig_stats> stats;
+
+    // (an input that is handed back keeps its pre-faulted mappings: the host ingest of the second look takes them)
+    ~PolishJob() {
+        release();
+        if (handed_back_at < 0) pph::prefetch_drop_all(ctx);
+    }
+    int wait_pending() {
         int r = PP_OK;
-        for (size_t i = 0; i < pending.size(); i++) {
-            const int ri = pending[i].get();
-            if (ri && !r) r = ri;
-        }
+        for (auto &p : pending)
+            if (const int ri = p.get()) r = r ? r : ri;
         pending.clear();
         return r;
-    };
-    std::vector<std::vector<Piece>> pieces((size_t)n_ctx);  // multi: what every context was sent, in file order
-    auto free_all = [&]() {
+    }
+    // the communicators, the plan and what the contexts brought back: not needed once the FASTA's bytes are in `polished`
+    void release_exchange() {
+        for (int d = 0; comms && d < n_ctx; d++) pp_comm_destroy(ctxs[d]);
+        comms = false;
+        pp_shard_plan_free(plan);
+        plan = nullptr;
+        ranks = {};
+        gathered = {};
+    }
+    void release() {
         (void)wait_pending();
+        if (dbg) fclose(dbg);
+        for (int d = 0; debug_set && d < n_ctx; d++) pp_polish_set_debug(ctxs[d], 0);
+        release_exchange();
         for (auto &v : pieces)
             for (Piece &pc : v) pp_shard_part_free(pc.part);
-        pieces.clear();
         for (pp_ingest *x : gs) pp_ingest_free(x);
         pp_ingest_free(g);
         pp_dev_ingest_free(dg);
         for (pp_dev_ingest *x : dgs) pp_dev_ingest_free(x);
         pp_assembly_free(a);
-    };
-    // run f(d) for every context on its own thread; the first failure (lowest d) is returned, its text put on ctxs[0]
-    auto on_all = [&](const std::function<int(int)> &f) {
-        std::vector<std::future<int>> jobs;
-        for (int d = 0; d < n_ctx; d++) jobs.push_back(std::async(std::launch::async, f, d));
-        int r = PP_OK;
-        for (int d = 0; d < n_ctx; d++) {
-            const int rd = jobs[(size_t)d].get();
-            if (rd && !r) {
-                r = rd;
-                if (d) set_err(ctx, rd, pp_last_error(ctxs[d]));
-            }
-        }
-        return r;
-    };
-    const bool sharded = multi && dev_ingest;
-    if (multi) pp_ctx_enable_peers_(ctxs, n_ctx);
-    if (sharded) rc = on_all([&](int d) { return pp_dev_ingest_create(ctxs[d], a, opt->max_errors, opt->careful, &dgs[(size_t)d]); });
-    else rc = dev_ingest ? pp_dev_ingest_create(ctx, a, opt->max_errors, opt->careful, &dg)
-                         : (per_file ? PP_OK : pp_ingest_create(a, opt->max_errors, opt->careful, &g));
-    uint64_t largest_sam = 0;
-    if (rc == PP_OK && dev_ingest && !sharded) {
-        uint64_t largest = 0, total = 0;
-        for (int i = 0; i < n_sams; i++) {
-            struct stat st;
-            if (stat(sams[i], &st) == 0 && S_ISREG(st.st_mode)) {
-                largest = std::max<uint64_t>(largest, (uint64_t)st.st_size);
-                total += (uint64_t)st.st_size;
-            }
-        }
-        largest_sam = largest;
-        if (largest) rc = pp_dev_ingest_reserve_text_(dg, largest);
-        if (rc == PP_OK && n_sams > 1) rc = pp_dev_ingest_expect(dg, total);  // the batch's arrays sized once, for all the files
-    }
-    if (dev_ingest) lap("device ready, tokenizer created");  // (pp_dev_ingest_create waits for the HIP runtime's start-up)
-    uint64_t alignment_total = 0, used_total = 0;
-    // sharded: the records of file i's slice on context s are records [slice_end[i-1][s], slice_end[i][s]) of its batch
-    std::vector<std::vector<uint64_t>> slice_end;
-    for (int i = 0; rc == PP_OK && i < n_sams; i++) {
-        pp_sam_counts c{0, 0, 0};
-        if (i == resume_log_at) log.quiet = opt->quiet != 0;
-        if (sharded) {
-            // cut the file into one slice per context at read-group boundaries; every context uploads and tokenizes its own
-            pph::FileText F;
-            if (!F.open_file(sams[i])) {
-                snprintf(err, sizeof err, "unable to load alignments from \"%s\"", sams[i]);
-                rc = set_err(ctx, PP_ERR_QUIT, err);
-                break;
-            }
-            std::vector<size_t> cut((size_t)n_ctx + 1, F.size);
-            cut[0] = 0;
-            for (int d = 1; d < n_ctx; d++) cut[(size_t)d] = std::max(cut[(size_t)d - 1], group_cut(F.text, F.size, F.size / (size_t)n_ctx * (size_t)d));
-            std::vector<pp_sam_counts> cs((size_t)n_ctx);
-            int rs = on_all([&](int d) {
-                return pp_dev_ingest_slice_(dgs[(size_t)d], sams[i], F.text + cut[(size_t)d], cut[(size_t)d + 1] - cut[(size_t)d], &cs[(size_t)d]);
-            });
-            for (auto &x : cs) { c.alignments += x.alignments; c.used += x.used; c.reads += x.reads; }
-            if (rs == PP_OK && c.alignments == 0) rs = PP_ERR_PANIC;  // a file without aligned records: the host path has the message
-            if (rs == PP_ERR_QUIT || rs == PP_ERR_PANIC || rs == PP_ERR_NOT_ASCII) {
-                free_all();  // as for one context: the host ingest works out what the reference reports first
-                return polish_files_impl(ctxs, n_ctx, assembly, sams, n_sams, opt, fasta, pass, n_pass, i);
-            }
-            if ((rc = rs)) break;
-            std::vector<uint64_t> ends((size_t)n_ctx);
-            for (int d = 0; d < n_ctx; d++) {
-                pp_aln_batch bd;
-                pp_dev_ingest_batch(dgs[(size_t)d], &bd);
-                ends[(size_t)d] = bd.n_aln;
-            }
-            slice_end.push_back(ends);
-        } else if (dev_ingest) {
-            // the text of the NEXT file goes up (second text buffer, upload stream) while this one is tokenized
-            if (i + 1 < n_sams) pp_dev_ingest_prefetch_(dg, sams[i + 1], largest_sam);
-            rc = pass ? pp_dev_ingest_sam_filtered(dg, sams[i], pass[i], n_pass[i], &c) : pp_dev_ingest_sam(dg, sams[i], &c);
-            if (rc == PP_ERR_QUIT || rc == PP_ERR_PANIC || rc == PP_ERR_NOT_ASCII) {
-                // A defect in the text.  Which defect the reference reports FIRST also depends on what its CIGAR walk
-                // makes of the records before it: the host ingest works that out (below), on this rare path.
-                free_all();
-                return polish_files_impl(ctxs, n_ctx, assembly, sams, n_sams, opt, fasta, pass, n_pass, i);
-            }
-            if (rc) break;
-        } else {
-            pp_ingest *gi = g;
-            if (per_file) {
-                rc = pp_ingest_create(a, opt->max_errors, opt->careful, &gi);
-                if (rc) break;
-                gs.push_back(gi);
-            }
-            rc = pass ? pp_ingest_sam_filtered(gi, sams[i], pass[i], n_pass[i], &c, err, sizeof err)
-                      : pp_ingest_sam(gi, sams[i], &c, err, sizeof err);
-            if (rc) {
-                set_err(ctx, rc, err);
-                // The reference streams: every read group before the failing point had already gone through
-                // add_alignment (alignment.rs:297-303), so a record there that only the CIGAR walk rejects (unexpected
-                // op, CIGAR / SEQ length mismatch, past the contig end) is what it reports.  Run the device over exactly
-                // those records: the earlier files and this file up to the group that was pending.
-                uint64_t cut = 0;
-                if (pp_ingest_fail_cut_(gi, &cut) && wait_pending() == PP_OK) {
-                    int rd = begun ? PP_OK : pp_polish_begin(ctx, nc, off, pp_assembly_bases(a), PP_MEM_HOST, &prm);
-                    begun = true;
-                    pp_aln_batch bi;
-                    if (rd == PP_OK && !per_file && g) {
-                        pp_ingest_batch(g, &bi);
-                        if (bi.n_aln) rd = pp_polish_add(ctx, &bi, PP_MEM_HOST);
-                    }
-                    if (multi)  // (the earlier files' batches have not gone anywhere yet: the first context takes them whole)
-                        for (size_t q = 0; rd == PP_OK && q + 1 < gs.size(); q++) {
-                            pp_ingest_batch(gs[q], &bi);
-                            if (bi.n_aln) rd = pp_polish_add(ctx, &bi, PP_MEM_HOST);
-                        }
-                    pp_ingest *gp = nullptr;
-                    char err2[256];
-                    pp_sam_counts c2;
-                    if (rd == PP_OK && cut > 0 && pp_ingest_create(a, opt->max_errors, opt->careful, &gp) == PP_OK &&
-                        pp_ingest_sam_prefix_(gp, sams[i], cut, pass ? pass[i] : nullptr, pass ? n_pass[i] : 0, &c2, err2,
-                                              sizeof err2) == PP_OK) {
-                        pp_ingest_batch(gp, &bi);
-                        if (bi.n_aln) rd = pp_polish_add(ctx, &bi, PP_MEM_HOST);
-                    }
-                    if (rd == PP_OK) rd = pp_polish_finish(ctx);
-                    pp_ingest_free(gp);
-                    if (rd == PP_ERR_QUIT || rd == PP_ERR_PANIC) rc = rd;  // the device's message stands
-                    else set_err(ctx, rc, err);
-                }
-                break;
-            }
-            if (stream_adds) {
-                if ((rc = wait_pending())) break;  // the upload of the file before
-                const bool first = !begun;
-                begun = true;
-                // room for all files at once: this file's batch scaled by the files' sizes on disk
-                double scale = 1.0;
-                if (first && n_sams > 1) {
-                    struct stat st0;
-                    double all_bytes = 0, this_bytes = 0;
-                    for (int q = 0; q < n_sams; q++)
-                        if (stat(sams[q], &st0) == 0 && S_ISREG(st0.st_mode)) { all_bytes += (double)st0.st_size; if (q == i) this_bytes = (double)st0.st_size; }
-                    if (this_bytes > 0) scale = std::min(64.0, all_bytes / this_bytes * 1.02);
-                }
-                pending.push_back(std::async(std::launch::async, [ctx, gi, first, nc, off, a, prm, scale]() {
-                    int r = first ? pp_polish_begin(ctx, nc, off, pp_assembly_bases(a), PP_MEM_HOST, &prm) : PP_OK;
-                    pp_aln_batch bi;
-                    pp_ingest_batch(gi, &bi);
-                    if (r == PP_OK && first && scale > 1.0)
-                        r = pp_polish_reserve(ctx, (uint64_t)((double)bi.n_aln * scale) + 1024, (uint64_t)((double)bi.seq_bytes * scale) + 4096,
-                                              (uint64_t)((double)bi.n_cig_total * scale) + 1024);
-                    if (r == PP_OK) r = pp_polish_add(ctx, &bi, PP_MEM_HOST);
-                    return r;
-                }));
-            }
-        }
-        log("%s: %s alignments from %s reads\n", sams[i], commas(c.alignments).c_str(), commas(c.reads).c_str());
-        if (timing) { char what[64]; snprintf(what, sizeof what, "file %d ingested", i + 1); lap(what); }
-        alignment_total += c.alignments;
-        used_total += c.used;
-    }
-    if (rc == PP_OK) rc = wait_pending();
-    if (rc) {
-        free_all();
-        return rc;
-    }
-    log("\nFiltering for high-quality end-to-end alignments%s:\n  %s alignments kept\n  %s alignments discarded\n\n",
-        opt->careful ? " from reads with only one alignment" : "", commas(used_total).c_str(),
-        commas(alignment_total - used_total).c_str());
-
-    lap("alignments ingested");
-    // polish_sequences, polish.rs:137-154 -- on the device
-    log("Polishing assembly sequences\n");
-    pp_aln_batch batch;
-    memset(&batch, 0, sizeof batch);
-    if (dev_ingest && !sharded) pp_dev_ingest_batch(dg, &batch); else if (g) pp_ingest_batch(g, &batch);
-    // create_debug_file, polish.rs:230-245: the file is created (and the header written) before polishing
-    FILE *dbg = nullptr;
-    if (opt->debug_path) {
-        dbg = fopen(opt->debug_path, "wb");
-        if (!dbg) {
-            snprintf(err, sizeof err, "unable to create \"%s\"", opt->debug_path);
-            free_all();
-            return set_err(ctx, PP_ERR_QUIT, err);
-        }
-        fputs("name\tpos\tbase\tdepth\tinvalid\tvalid\tpileup\tstatus\tnew_base\n", dbg);
-    }
-    for (int d = 0; d < n_ctx; d++) pp_polish_set_debug(ctxs[d], dbg ? 1 : 0);
-    std::vector<const char *> names(nc);
-    for (uint32_t c = 0; c < nc; c++) names[c] = pp_assembly_name(a, c);
-    uint64_t total = 0;
-    bool direct_fetch = false;
-    std::vector<uint8_t> polished(1);
-    std::vector<uint64_t> out_off(nc + 1);
-    std::vector<pp_contig_stats> stats(nc);
-    if (!multi) {
-        if (!begun) {  // one batch (device tokenizer), or no SAM files at all
-            rc = pp_polish_begin(ctx, nc, off, pp_assembly_bases(a), PP_MEM_HOST, &prm);
-            if (rc == PP_OK && (dev_ingest || g)) rc = pp_polish_add(ctx, &batch, dev_ingest ? PP_MEM_DEVICE : PP_MEM_HOST);
-        }
-        if (rc == PP_OK) rc = pp_polish_finish(ctx);
-        lap("uploaded + polished on device");
-        if (rc == PP_OK && dbg) {
-            rc = write_debug_tsv(ctx, dbg, names, 0, off[nc]);
-            lap("--debug file written");
-        }
-        if (dbg && fclose(dbg) && rc == PP_OK) rc = set_err(ctx, PP_ERR_QUIT, "unable to write to the --debug file");
-        pp_polish_set_debug(ctx, 0);
-        if (rc == PP_OK) rc = pp_polish_result_size(ctx, &total);
-        // offsets and statistics now; the bytes go straight into the FASTA buffer below (contig by contig) when that is a
-        // handful of copies, else through one copy of everything
-        direct_fetch = rc == PP_OK && out && nc <= 256 && header_bytes + total + nc <= fasta_cap;
-        if (!direct_fetch) polished.resize(total ? total : 1);
-        if (rc == PP_OK) rc = pp_polish_result(ctx, direct_fetch ? nullptr : polished.data(), PP_MEM_HOST, out_off.data(), stats.data());
-    } else {
-        // ---- the plan, from the alignment counts per contig ----
-        // source batches in file order: sharded -> (file, slice) pieces living on the contexts' GPUs; host ingest -> files
-        struct Src { pp_aln_batch view; int mem; int owner; uint64_t base; uint32_t wo_base; std::vector<uint64_t> runs; };
-        std::vector<Src> srcs;
-        uint64_t base = 0;
-        if (sharded) {
-            std::vector<pp_aln_batch> whole((size_t)n_ctx);
-            for (int d = 0; d < n_ctx; d++) pp_dev_ingest_batch(dgs[(size_t)d], &whole[(size_t)d]);
-            for (size_t f = 0; f < slice_end.size(); f++)
-                for (int sidx = 0; sidx < n_ctx; sidx++) {
-                    const uint64_t lo = f ? slice_end[f - 1][(size_t)sidx] : 0, hi = slice_end[f][(size_t)sidx];
-                    pp_aln_batch v = whole[(size_t)sidx];  // seq / cigar: the whole arrays (seq_off / cig_off are absolute)
-                    v.n_aln = hi - lo;
-                    v.contig += lo; v.ref_start += lo; v.k += lo; v.seq_off += lo; v.seq_len += lo; v.cig_off += lo; v.n_cig += lo;
-                    if (v.wo) v.wo += lo;  // (a slice's entries of the window-order mirror are its own stretch; they count from lo)
-                    // the slice's runs: the whole batch's, cut to [lo, hi) and counted from lo (the tokenizer ends a run with every
-                    // file: one run, the slice itself) -- with them a part of the slice takes the direct path like any other
-                    std::vector<uint64_t> runs;
-                    const pp_aln_batch &wb = whole[(size_t)sidx];
-                    for (uint32_t r = 0; v.wo && wb.wo_run_end && r < wb.wo_n_runs; r++) {
-                        const uint64_t e = std::min(std::max(wb.wo_run_end[r], lo), hi) - lo;
-                        if (e > (runs.empty() ? 0 : runs.back())) runs.push_back(e);
-                    }
-                    if (runs.empty() || runs.back() != hi - lo) runs.clear();  // (not known: the bucketing path)
-                    v.wo_n_runs = 0;
-                    v.wo_run_end = nullptr;
-                    srcs.push_back(Src{v, PP_MEM_DEVICE, sidx, base, (uint32_t)lo, std::move(runs)});
-                    srcs.back().view.wo_n_runs = (uint32_t)srcs.back().runs.size();
-                    srcs.back().view.wo_run_end = srcs.back().runs.empty() ? nullptr : srcs.back().runs.data();
-                    base += hi - lo;
-                }
-            // (one context after the other: a histogram kernel each, they add into the same host array)
-            for (int d = 0; rc == PP_OK && d < n_ctx; d++) {
-                rc = pp_shard_count(ctxs[d], &whole[(size_t)d], PP_MEM_DEVICE, nc, per_contig.data());
-                if (rc && d) set_err(ctx, rc, pp_last_error(ctxs[d]));
-            }
-        } else {
-            for (pp_ingest *gi : gs) {
-                pp_aln_batch v;
-                pp_ingest_batch(gi, &v);
-                srcs.push_back(Src{v, PP_MEM_HOST, -1, base, 0u, {}});
-                base += v.n_aln;
-                pp_shard_count(nullptr, &v, PP_MEM_HOST, nc, per_contig.data());
-            }
-        }
-        pp_shard_plan *plan = nullptr;
-        if (rc == PP_OK) rc = pp_shard_plan_create(nc, off, per_contig.data(), (uint32_t)n_ctx, 0, &plan);
-        // ---- every source batch is split once per destination (on the GPU that holds it, or on the host) ----
-        std::vector<std::vector<pp_shard_part *>> parts(srcs.size(), std::vector<pp_shard_part *>((size_t)n_ctx, nullptr));
-        if (rc == PP_OK) {
-            if (sharded)
-                rc = on_all([&](int sidx) {  // a context splits the pieces it holds, for every destination
-                    for (size_t q = 0; q < srcs.size(); q++) {
-                        if (srcs[q].owner != sidx) continue;
-                        for (int d = 0; d < n_ctx; d++)
-                            if (int r = pp_shard_split_view_(ctxs[sidx], plan, (uint32_t)d, &srcs[q].view, PP_MEM_DEVICE, srcs[q].wo_base, &parts[q][(size_t)d])) return r;
-                    }
-                    return (int)PP_OK;
-                });
-            else
-                rc = on_all([&](int d) {
-                    for (size_t q = 0; q < srcs.size(); q++)
-                        if (int r = pp_shard_split(nullptr, plan, (uint32_t)d, &srcs[q].view, PP_MEM_HOST, &parts[q][(size_t)d])) {
-                            set_err(ctxs[d], r, "splitting the records failed");
-                            return r;
-                        }
-                    return (int)PP_OK;
-                });
-        }
-        for (size_t q = 0; q < srcs.size(); q++)
-            for (int d = 0; d < n_ctx; d++)
-                if (parts[q][(size_t)d]) {
-                    pp_aln_batch v;
-                    pp_shard_part_batch(parts[q][(size_t)d], &v, nullptr);
-                    pieces[(size_t)d].push_back(Piece{parts[q][(size_t)d], srcs[q].owner, srcs[q].base, v.n_aln});
-                }
-        // the tokenizers' batches (and their text buffers) are not needed once every part has been cut out of them
-        for (pp_dev_ingest *&x : dgs) { pp_dev_ingest_free(x); x = nullptr; }
-        lap("records split");
-        // every context: its records, the ranges of its units, finish, its own bytes to the host -- side by side
-        // ---- how the polished bytes will reach the host: one RCCL gather to the first context's GPU, or every device by itself ----
-        // The RCCL route is OPT-IN (PP_GATHER=rccl) in this one-process driver: it has only ever run with world = 1 -- the boxes
-        // this was built on have one GPU, and RCCL refuses two ranks on one device -- and a rank that fails inside
-        // ncclCommInitRank leaves the other threads waiting there.  The default is the route every test runs: each device
-        // copies its share out and the FASTA is assembled on the host.  (One process per GPU -- python -m
-        // polypolish_amd.distributed, bench.py --gpus N -- gathers over RCCL, behind a watchdog.)
-        bool use_rccl = getenv("PP_GATHER") && !strcmp(getenv("PP_GATHER"), "rccl");
-        for (int d = 0; d < n_ctx && use_rccl && !getenv("PP_RCCL_LIB"); d++)  // (a stand-in library, tests: it takes several ranks on one device)
-            for (int e = 0; e < d; e++)
-                if (pp_ctx_device_(ctxs[d]) == pp_ctx_device_(ctxs[e])) use_rccl = false;  // RCCL refuses two ranks on one device
-        if (use_rccl && rc == PP_OK) {
-            uint8_t id[PP_COMM_ID_BYTES];
-            if (pp_comm_unique_id(id) != PP_OK) use_rccl = false;  // librccl not loadable
-            else if (on_all([&](int d) { return pp_comm_init(ctxs[d], d, n_ctx, id); }) != PP_OK) {
-                for (int d = 0; d < n_ctx; d++) pp_comm_destroy(ctxs[d]);
-                use_rccl = false;
-            }
-        }
-        if (timing) fprintf(stderr, "[timing] polished bytes -> host: %s\n", use_rccl ? "ONE RCCL gather (ncclSend/ncclRecv over xGMI) to the first GPU + one D2H"
-                                                                                    : "every device copies its share out, assembled on the host (the default; PP_GATHER=rccl asks for the RCCL gather -- not with two contexts on one device or without librccl)");
-        std::vector<uint8_t> gathered;
-        std::vector<uint64_t> r_total((size_t)n_ctx, 0);
-        std::vector<std::vector<uint8_t>> r_bytes((size_t)n_ctx);
-        std::vector<std::vector<uint64_t>> r_off((size_t)n_ctx, std::vector<uint64_t>(nc + 1, 0));
-        std::vector<std::vector<pp_contig_stats>> r_stats((size_t)n_ctx, std::vector<pp_contig_stats>(nc));
-        std::vector<int> r_rc((size_t)n_ctx, PP_OK);
-        if (rc == PP_OK) {
-            (void)on_all([&](int d) {
-                pp_ctx *cd = ctxs[d];
-                int r = pp_polish_begin(cd, nc, off, pp_assembly_bases(a), PP_MEM_HOST, &prm);
-                uint64_t tn = 0, ts = 0, tc = 0;
-                for (const Piece &pc : pieces[(size_t)d]) {
-                    pp_aln_batch v;
-                    pp_shard_part_batch(pc.part, &v, nullptr);
-                    tn += v.n_aln; ts += v.seq_bytes; tc += v.n_cig_total;
-                }
-                if (r == PP_OK) r = pp_polish_reserve(cd, tn + 16, ts + 64, tc + 16);
-                bool first = true;
-                for (const Piece &pc : pieces[(size_t)d]) {
-                    if (r) break;
-                    pp_aln_batch v;
-                    pp_shard_part_batch(pc.part, &v, nullptr);
-                    if (v.n_aln == 0) continue;
-                    // (a part on this context's own GPU is device memory; the FIRST batch of a job would be used in place,
-                    // which is fine -- the parts live until every context has finished)
-                    const int pm = pp_shard_part_mem(pc.part);
-                    r = pp_polish_add(cd, &v, pm == PP_MEM_HOST ? PP_MEM_HOST : (pc.src == d && !first ? PP_MEM_DEVICE : PP_MEM_PEER));
-                    first = false;
-                }
-                std::vector<uint64_t> lo(nc), hi(nc);
-                if (r == PP_OK) r = pp_shard_emit_ranges(plan, (uint32_t)d, lo.data(), hi.data());
-                if (r == PP_OK) r = pp_polish_set_emit(cd, lo.data(), hi.data());
-                if (r == PP_OK) r = pp_polish_finish(cd);
-                uint64_t t = 0;
-                if (r == PP_OK) r = pp_polish_result_size(cd, &t);
-                r_total[(size_t)d] = t;
-                // offsets and statistics now; the bytes follow over RCCL, or (host route) with this very call
-                if (r == PP_OK && !use_rccl) r_bytes[(size_t)d].resize(t ? t : 1);
-                if (r == PP_OK) r = pp_polish_result(cd, use_rccl ? nullptr : r_bytes[(size_t)d].data(), PP_MEM_HOST, r_off[(size_t)d].data(), r_stats[(size_t)d].data());
-                r_rc[(size_t)d] = r;
-                return r;
-            });
-            bool all_ok = true;
-            for (int d = 0; d < n_ctx; d++) all_ok = all_ok && r_rc[(size_t)d] == PP_OK;
-            if (all_ok && use_rccl) {
-                // the one exchange of the job: every context's bytes to the first context's GPU, then one copy to the host
-                uint64_t sum = 0;
-                for (uint64_t t : r_total) sum += t;
-                gathered.resize(sum ? sum : 1);
-                std::vector<uint64_t> lens((size_t)n_ctx, 0);
-                const auto tg = std::chrono::steady_clock::now();
-                const int rg = on_all([&](int d) {
-                    return pp_polish_gather_to_host_(ctxs[d], d == 0 ? gathered.data() : nullptr, d == 0 ? sum : 0, d == 0 ? lens.data() : nullptr, nullptr);
-                });
-                if (timing) fprintf(stderr, "[timing] RCCL gather of %llu bytes from %d contexts + one D2H: %.3f ms\n", (unsigned long long)sum, n_ctx,
-                                    1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - tg).count());
-                if (rg) rc = rg;
-                else
-                    for (int d = 0; d < n_ctx; d++)
-                        if (lens[(size_t)d] != r_total[(size_t)d]) rc = set_err(ctx, PP_ERR_HIP, "the RCCL gather delivered a rank's bytes short");
-            }
-            // The job's error is the one about its FIRST bad record in file order (the reference streams,
-            // src/alignment.rs:238-303): a context numbers the records it was sent, the parts know where those came from.
-            uint64_t best = ~0ull;
-            int best_d = -1;
-            uint32_t best_kind = 0;
-            for (int d = 0; d < n_ctx; d++) {
-                if (r_rc[(size_t)d] == PP_OK) continue;
-                uint32_t kind = 0;
-                const uint64_t jr = job_record_of(ctxs[d], ctxs, pieces[(size_t)d], &kind);
-                if (best_d < 0 || jr < best) { best = jr; best_d = d; best_kind = kind; }
-            }
-            if (best_d >= 0) {
-                if (best != ~0ull) rc = pp_polish_error_text(ctx, best_kind, best);
-                else { rc = r_rc[(size_t)best_d]; if (best_d) set_err(ctx, rc, pp_last_error(ctxs[best_d])); }
-            }
-        }
-        lap("uploaded + polished on the devices");
-        // --debug: the plan's units in order (contig by contig, a tiled contig's windows in position order), each formatted by
-        // the context that emits it -- neighbouring units of one context in one go
-        for (uint32_t u = 0; dbg && rc == PP_OK && u < plan->n_units;) {
-            const uint32_t r = plan->rank[u];
-            const uint64_t lo = off[plan->contig[u]] + plan->lo[u];
-            uint64_t hi = off[plan->contig[u]] + plan->hi[u];
-            for (u++; u < plan->n_units && plan->rank[u] == r && off[plan->contig[u]] + plan->lo[u] == hi; u++) hi = off[plan->contig[u]] + plan->hi[u];
-            if (r >= (uint32_t)n_ctx) { rc = set_err(ctx, PP_ERR_HIP, "a unit of the plan names no context"); break; }
-            rc = write_debug_tsv(ctxs[r], dbg, names, lo, hi);
-            if (rc && r) set_err(ctx, rc, pp_last_error(ctxs[r]));
-        }
-        if (dbg) {
-            if (fclose(dbg) && rc == PP_OK) rc = set_err(ctx, PP_ERR_QUIT, "unable to write to the --debug file");
-            dbg = nullptr;
-            lap("--debug file written");
-        }
-        for (int d = 0; d < n_ctx; d++) pp_polish_set_debug(ctxs[d], 0);
-        if (rc == PP_OK) {
-            std::vector<const uint8_t *> bp((size_t)n_ctx);
-            std::vector<const uint64_t *> op((size_t)n_ctx);
-            uint64_t at = 0;
-            for (int d = 0; d < n_ctx; d++) {
-                bp[(size_t)d] = use_rccl ? gathered.data() + at : r_bytes[(size_t)d].data();
-                at += r_total[(size_t)d];
-                op[(size_t)d] = r_off[(size_t)d].data();
-            }
-            rc = pp_shard_assemble(plan, bp.data(), op.data(), nullptr, out_off.data());
-            total = out_off[nc];
-            polished.resize(total ? total : 1);
-            if (rc == PP_OK) rc = pp_shard_assemble(plan, bp.data(), op.data(), polished.data(), out_off.data());
-            for (uint32_t c = 0; c < nc; c++) {  // a position is counted by the rank that emits it
-                stats[c] = pp_contig_stats{out_off[c + 1] - out_off[c], 0, 0, 0.0};
-                for (int d = 0; d < n_ctx; d++) {
-                    stats[c].changed += r_stats[(size_t)d][c].changed;
-                    stats[c].zero_depth += r_stats[(size_t)d][c].zero_depth;
-                    stats[c].depth_sum += r_stats[(size_t)d][c].depth_sum;
-                }
-            }
-        }
-        if (use_rccl)
-            for (int d = 0; d < n_ctx; d++) pp_comm_destroy(ctxs[d]);
-        pp_shard_plan_free(plan);
-    }
-    if (rc) {
-        free_all();
-        return rc;
-    }
-
-    lap(direct_fetch ? "result: offsets fetched" : "result fetched");
-    // print_seq_to_stdout (polish.rs:196-203), one contig after the other in FASTA order
-    if (out_toucher.joinable()) out_toucher.join();
-    if (!out || header_bytes + total + nc > fasta_cap) {  // (a job whose polished bytes outgrow the bound: a buffer of the exact size)
+        if (out_toucher.joinable()) out_toucher.join();
         free(out);
-        out = (uint8_t *)malloc(header_bytes + total + nc + 1);
-        if (!out) { free_all(); return set_err(ctx, PP_ERR_HIP, "out of host memory for the FASTA"); }
+        pieces.clear();
+        gs.clear();
+        dgs.clear();
+        dbg = nullptr;
+        g = nullptr;
+        dg = nullptr;
+        a = nullptr;
+        out = nullptr;
+        debug_set = false;
     }
-    const uint8_t *d_polished = direct_fetch ? pp_polish_result_device(ctx) : nullptr;
+};
+
+// run f(d) for every context on its own thread; the first failure (lowest d) is returned, its text put on ctxs[0]
+int on_all(PolishJob &J, const std::function<int(int)> &f) {
+    std::vector<std::future<int>> jobs;
+    for (int d = 0; d < J.n_ctx; d++) jobs.push_back(std::async(std::launch::async, f, d));
+    int r = PP_OK;
+    for (int d = 0; d < J.n_ctx; d++) {
+        const int rd = jobs[(size_t)d].get();
+        if (rd && !r) {
+            r = rd;
+            if (d) set_err(J.ctx, rd, pp_last_error(J.ctxs[d]));
+        }
+    }
+    return r;
+}
+
+int check_options_and_inputs(PolishJob &J) {
+    const pp_polish_options *opt = J.opt;
+    // check_option_values (polish.rs:277-287) is repeated by pp_polish_begin; do it first as the reference does
+    if (opt->fraction_valid <= 0.0 || opt->fraction_valid >= 1.0)
+        return set_err(J.ctx, PP_ERR_QUIT, "--fraction_valid must be between 0 and 1 (exclusive)");
+    if (opt->fraction_invalid <= 0.0 || opt->fraction_invalid >= 1.0)
+        return set_err(J.ctx, PP_ERR_QUIT, "--fraction_invalid must be between 0 and 1 (exclusive)");
+    if (opt->fraction_invalid >= opt->fraction_valid)
+        return set_err(J.ctx, PP_ERR_QUIT, "--fraction_invalid must be less than --fraction_valid");
+    // check_inputs_exist, polish.rs:269-274
+    for (int i = -1; i < J.n_sams; i++) {
+        const char *path = i < 0 ? J.assembly : J.sams[i];
+        if (exists(path)) continue;
+        snprintf(J.err, sizeof J.err, "\"%s\" file does not exist", path);
+        return set_err(J.ctx, PP_ERR_QUIT, J.err);
+    }
+    // The device tokenizer uploads the SAM text as it is: map the files and pre-fault the mappings NOW, on background
+    // threads, while the HIP runtime is still initialising (a copy out of an untouched mapping runs at a quarter of
+    // the link's rate).
+    for (int i = 0; J.dev_ingest && i < J.n_sams; i++) pph::prefetch_file(J.sams[i], J.ctx);
+    J.sam_bytes.assign((size_t)J.n_sams, 0);
+    for (int i = 0; i < J.n_sams; i++) {
+        struct stat st;
+        if (stat(J.sams[i], &st) == 0 && S_ISREG(st.st_mode)) J.sam_bytes[(size_t)i] = (uint64_t)st.st_size;
+    }
+    return PP_OK;
+}
+
+// starting_message, polish.rs:41-73
+void log_banner(const PolishJob &J) {
+    const pp_polish_options *opt = J.opt;
+    J.log("\nStarting Polypolish polish\n%s\n\nInput assembly:\n  %s\n\nInput short-read alignments:\n", pp_version(), J.assembly);
+    for (int i = 0; i < J.n_sams; i++) J.log("  %s\n", J.sams[i]);
+    J.log("\nSettings:\n  --fraction_invalid %g\n  --fraction_valid %g\n  --max_errors %u\n  --min_depth %u\n",
+          opt->fraction_invalid, opt->fraction_valid, opt->max_errors, opt->min_depth);
+    if (opt->careful) J.log("  --careful\n");
+    if (opt->debug_path) J.log("  --debug %s\n\n", opt->debug_path);
+    else J.log("  not logging debugging information\n\n");
+}
+
+// load_assembly, polish.rs:93-106
+int load_assembly(PolishJob &J) {
+    J.log("Loading assembly\n");
+    if (int rc = pp_assembly_load(J.assembly, &J.a, J.err, sizeof J.err)) return set_err(J.ctx, rc, J.err);
+    J.nc = pp_assembly_n_contigs(J.a);
+    J.off = pp_assembly_offsets(J.a);
+    J.names.resize(J.nc);
+    for (uint32_t c = 0; c < J.nc; c++) {
+        J.names[c] = pp_assembly_name(J.a, c);
+        J.log("%s (%s bp)\n", J.names[c], commas(J.off[c + 1] - J.off[c]).c_str());
+    }
+    J.log("\n");
+    J.out_off.resize(J.nc + 1);
+    J.stats.resize(J.nc);
+    return PP_OK;
+}
+
+// The FASTA that will be returned: headers + polished bytes.  Its buffer is allocated for an upper bound NOW and touched
+// by a helper thread while the alignments are loaded -- the polished bytes then come off the device straight into their
+// place in it (a fresh 250 MB destination took 30 ms of page faults inside the copy, and assembling the FASTA from a
+// second buffer another 40 ms of memcpy).
+void reserve_fasta(PolishJob &J) {
+    size_t cap = 0;
+    for (uint32_t c = 0; c < J.nc; c++) cap += strlen(J.names[c]) + strlen(pp_assembly_description(J.a, c)) + 16;
+    J.header_bytes = cap;
+    cap += (size_t)(J.off[J.nc] + J.off[J.nc] / 8) + 2 * (size_t)J.nc + 65536;  // (every planted insertion adds a byte: far below 1/8)
+    J.fasta_cap = cap;
+    uint8_t *out = J.out = (uint8_t *)malloc(cap);
+    if (out) J.out_toucher = std::thread([out, cap] { for (size_t q = 0; q < cap; q += 4096) out[q] = 0; });
+}
+
+// the ingest objects of the job's route -- the device tokenizer (pp_tokenize.hip), one per context when sharded, or the host's
+// (multi-threaded parse) with PP_DEVICE_INGEST=0
+int create_ingests(PolishJob &J) {
+    const pp_polish_options *opt = J.opt;
+    int rc = PP_OK;
+    if (J.multi) pp_ctx_enable_peers_(J.ctxs, J.n_ctx);
+    if (J.sharded) {
+        J.dgs.assign((size_t)J.n_ctx, nullptr);
+        rc = on_all(J, [&](int d) { return pp_dev_ingest_create(J.ctxs[d], J.a, opt->max_errors, opt->careful, &J.dgs[(size_t)d]); });
+    } else if (J.dev_ingest) {
+        rc = pp_dev_ingest_create(J.ctx, J.a, opt->max_errors, opt->careful, &J.dg);
+        uint64_t largest = 0, total = 0;
+        for (uint64_t b : J.sam_bytes) { largest = std::max(largest, b); total += b; }
+        if (rc == PP_OK && largest) rc = pp_dev_ingest_reserve_text_(J.dg, largest);
+        if (rc == PP_OK && J.n_sams > 1) rc = pp_dev_ingest_expect(J.dg, total);  // the batch's arrays sized once, for all the files
+    } else if (!J.per_file) {
+        rc = pp_ingest_create(J.a, opt->max_errors, opt->careful, &J.g);
+    }
+    if (J.dev_ingest) J.lap("device ready, tokenizer created");  // (pp_dev_ingest_create waits for the HIP runtime's start-up)
+    return rc;
+}
+
+// cut the file into one slice per context at read-group boundaries; every context uploads and tokenizes its own
+int ingest_file_sharded(PolishJob &J, int i, pp_sam_counts &c) {
+    const size_t n = (size_t)J.n_ctx;
+    pph::FileText F;
+    if (!F.open_file(J.sams[i])) {
+        snprintf(J.err, sizeof J.err, "unable to load alignments from \"%s\"", J.sams[i]);
+        return set_err(J.ctx, PP_ERR_QUIT, J.err);
+    }
+    std::vector<size_t> cut(n + 1, F.size);
+    cut[0] = 0;
+    for (size_t d = 1; d < n; d++) cut[d] = std::max(cut[d - 1], group_cut(F.text, F.size, F.size / n * d));
+    std::vector<pp_sam_counts> cs(n);
+    int rs = on_all(J, [&](int d) {
+        const size_t s = (size_t)d;
+        return pp_dev_ingest_slice_(J.dgs[s], J.sams[i], F.text + cut[s], cut[s + 1] - cut[s], &cs[s]);
+    });
+    for (auto &x : cs) { c.alignments += x.alignments; c.used += x.used; c.reads += x.reads; }
+    if (rs == PP_OK && c.alignments == 0) rs = PP_ERR_PANIC;  // a file without aligned records: the host path has the message
+    if (rs) return hand_back_if_text_defect(rs);  // as for one context
+    std::vector<uint64_t> ends(n);
+    for (size_t d = 0; d < n; d++) {
+        pp_aln_batch bd;
+        pp_dev_ingest_batch(J.dgs[d], &bd);
+        ends[d] = bd.n_aln;
+    }
+    J.slice_end.push_back(ends);
+    return PP_OK;
+}
+
+int ingest_file_device(PolishJob &J, int i, pp_sam_counts &c) {
+    // the text of the NEXT file goes up (second text buffer, upload stream) while this one is tokenized
+    if (i + 1 < J.n_sams) pp_dev_ingest_prefetch_(J.dg, J.sams[i + 1], *std::max_element(J.sam_bytes.begin(), J.sam_bytes.end()));
+    return hand_back_if_text_defect(J.pass ? pp_dev_ingest_sam_filtered(J.dg, J.sams[i], J.pass[i], J.n_pass[i], &c)
+                                           : pp_dev_ingest_sam(J.dg, J.sams[i], &c));
+}
+
+// The host ingest `gi` refused file i with (rc, J.err).  The reference streams: every read group before the failing point
+// had already gone through add_alignment (alignment.rs:297-303), so a record there that only the CIGAR walk rejects
+// (unexpected op, CIGAR / SEQ length mismatch, past the contig end) is what it reports.  Run the device over exactly those
+// records: the earlier files and this file up to the group that was pending.  Returns the error that stands.
+int replay_records_before_defect(PolishJob &J, int i, const pp_ingest *gi, int rc) {
+    pp_ctx *const ctx = J.ctx;
+    uint64_t cut = 0;
+    if (!pp_ingest_fail_cut_(gi, &cut) || J.wait_pending() != PP_OK) return rc;
+    int rd = J.begun ? PP_OK : pp_polish_begin(ctx, J.nc, J.off, pp_assembly_bases(J.a), PP_MEM_HOST, &J.prm);
+    J.begun = true;
+    auto add = [&](const pp_ingest *x) {
+        pp_aln_batch b;
+        pp_ingest_batch(x, &b);
+        if (rd == PP_OK && b.n_aln) rd = pp_polish_add(ctx, &b, PP_MEM_HOST);
+    };
+    if (!J.per_file && J.g) add(J.g);
+    if (J.multi)  // (the earlier files' batches have not gone anywhere yet: the first context takes them whole)
+        for (size_t q = 0; q + 1 < J.gs.size(); q++) add(J.gs[q]);
+    pp_ingest *gp = nullptr;
+    char err2[256];
+    pp_sam_counts c2;
+    if (rd == PP_OK && cut > 0 && pp_ingest_create(J.a, J.opt->max_errors, J.opt->careful, &gp) == PP_OK &&
+        pp_ingest_sam_prefix_(gp, J.sams[i], cut, J.pass ? J.pass[i] : nullptr, J.pass ? J.n_pass[i] : 0, &c2, err2, sizeof err2) == PP_OK)
+        add(gp);
+    if (rd == PP_OK) rd = pp_polish_finish(ctx);
+    pp_ingest_free(gp);
+    if (rd == PP_ERR_QUIT || rd == PP_ERR_PANIC) return rd;  // the device's message stands
+    return set_err(ctx, rc, J.err);
+}
+
+int ingest_file_host(PolishJob &J, int i, pp_sam_counts &c) {
+    pp_ctx *const ctx = J.ctx;
+    pp_ingest *gi = J.g;
+    if (J.per_file) {
+        if (int rc = pp_ingest_create(J.a, J.opt->max_errors, J.opt->careful, &gi)) return rc;
+        J.gs.push_back(gi);
+    }
+    int rc = J.pass ? pp_ingest_sam_filtered(gi, J.sams[i], J.pass[i], J.n_pass[i], &c, J.err, sizeof J.err)
+                    : pp_ingest_sam(gi, J.sams[i], &c, J.err, sizeof J.err);
+    if (rc) {
+        set_err(ctx, rc, J.err);
+        return replay_records_before_defect(J, i, gi, rc);
+    }
+    if (!J.stream_adds) return PP_OK;
+    if ((rc = J.wait_pending())) return rc;  // the upload of the file before
+    const bool first = !J.begun;
+    J.begun = true;
+    // room for all files at once: this file's batch scaled by the files' sizes on disk
+    double scale = 1.0, all_bytes = 0;
+    for (uint64_t b : J.sam_bytes) all_bytes += (double)b;
+    if (first && J.n_sams > 1 && J.sam_bytes[(size_t)i] > 0) scale = std::min(64.0, all_bytes / (double)J.sam_bytes[(size_t)i] * 1.02);
+    J.pending.push_back(std::async(std::launch::async, [ctx, gi, first, scale, nc = J.nc, off = J.off, a = J.a, prm = J.prm]() {
+        int r = first ? pp_polish_begin(ctx, nc, off, pp_assembly_bases(a), PP_MEM_HOST, &prm) : PP_OK;
+        pp_aln_batch bi;
+        pp_ingest_batch(gi, &bi);
+        if (r == PP_OK && first && scale > 1.0)
+            r = pp_polish_reserve(ctx, (uint64_t)((double)bi.n_aln * scale) + 1024, (uint64_t)((double)bi.seq_bytes * scale) + 4096,
+                                  (uint64_t)((double)bi.n_cig_total * scale) + 1024);
+        if (r == PP_OK) r = pp_polish_add(ctx, &bi, PP_MEM_HOST);
+        return r;
+    }));
+    return PP_OK;
+}
+
+// load_alignments, polish.rs:109-134.  A device tokenizer that meets a defect in the text (or bytes outside ASCII, which the
+// host parsers must judge) only says so: which defect the reference reports FIRST also depends on what its CIGAR walk makes of
+// the records before it, and the host ingest works that out (replay_records_before_defect): HAND_BACK, at J.handed_back_at.
+int load_alignments(PolishJob &J) {
+    J.log("Loading alignments\n");
+    if (int rc = create_ingests(J)) return rc;
+    for (int i = 0; i < J.n_sams; i++) {
+        pp_sam_counts c{0, 0, 0};
+        if (i == J.resume_log_at) J.log.quiet = J.opt->quiet != 0;
+        const int rc = J.sharded ? ingest_file_sharded(J, i, c) : J.dev_ingest ? ingest_file_device(J, i, c) : ingest_file_host(J, i, c);
+        if (rc == HAND_BACK) J.handed_back_at = i;
+        if (rc) return rc;
+        J.log("%s: %s alignments from %s reads\n", J.sams[i], commas(c.alignments).c_str(), commas(c.reads).c_str());
+        if (J.lap.on) { char what[64]; snprintf(what, sizeof what, "file %d ingested", i + 1); J.lap(what); }
+        J.alignment_total += c.alignments;
+        J.used_total += c.used;
+    }
+    if (int rc = J.wait_pending()) return rc;
+    J.log("\nFiltering for high-quality end-to-end alignments%s:\n  %s alignments kept\n  %s alignments discarded\n\n",
+          J.opt->careful ? " from reads with only one alignment" : "", commas(J.used_total).c_str(),
+          commas(J.alignment_total - J.used_total).c_str());
+    J.lap("alignments ingested");
+    return PP_OK;
+}
+
+// create_debug_file, polish.rs:230-245: the file is created (and the header written) before polishing
+int create_debug_file(PolishJob &J) {
+    if (J.opt->debug_path) {
+        J.dbg = fopen(J.opt->debug_path, "wb");
+        if (!J.dbg) {
+            snprintf(J.err, sizeof J.err, "unable to create \"%s\"", J.opt->debug_path);
+            return set_err(J.ctx, PP_ERR_QUIT, J.err);
+        }
+        fputs("name\tpos\tbase\tdepth\tinvalid\tvalid\tpileup\tstatus\tnew_base\n", J.dbg);
+    }
+    J.debug_set = true;
+    for (int d = 0; d < J.n_ctx; d++) pp_polish_set_debug(J.ctxs[d], J.dbg ? 1 : 0);
+    return PP_OK;
+}
+// ... and closed once the contexts have written their lines; they keep no per-position records from here on
+int close_debug_file(PolishJob &J, int rc, bool say) {
+    FILE *f = J.dbg;
+    J.dbg = nullptr;
+    if (f && fclose(f) && rc == PP_OK) rc = set_err(J.ctx, PP_ERR_QUIT, "unable to write to the --debug file");
+    if (f && say) J.lap("--debug file written");
+    for (int d = 0; d < J.n_ctx; d++) pp_polish_set_debug(J.ctxs[d], 0);
+    J.debug_set = false;
+    return rc;
+}
+
+int polish_on_one_context(PolishJob &J) {
+    pp_ctx *const ctx = J.ctx;
+    int rc = PP_OK;
+    if (!J.begun) {  // one batch (device tokenizer), or no SAM files at all
+        pp_aln_batch batch{};
+        if (J.dev_ingest) pp_dev_ingest_batch(J.dg, &batch); else if (J.g) pp_ingest_batch(J.g, &batch);
+        rc = pp_polish_begin(ctx, J.nc, J.off, pp_assembly_bases(J.a), PP_MEM_HOST, &J.prm);
+        if (rc == PP_OK && (J.dev_ingest || J.g)) rc = pp_polish_add(ctx, &batch, J.dev_ingest ? PP_MEM_DEVICE : PP_MEM_HOST);
+    }
+    if (rc == PP_OK) rc = pp_polish_finish(ctx);
+    J.lap("uploaded + polished on device");
+    if (rc == PP_OK && J.dbg) {
+        rc = write_debug_tsv(ctx, J.dbg, J.names, 0, J.off[J.nc]);
+        J.lap("--debug file written");
+    }
+    rc = close_debug_file(J, rc, false);
+    if (rc == PP_OK) rc = pp_polish_result_size(ctx, &J.total);
+    // offsets and statistics now; the bytes go straight into the FASTA buffer below (contig by contig) when that is a
+    // handful of copies, else through one copy of everything
+    J.direct_fetch = rc == PP_OK && J.out && J.nc <= 256 && J.header_bytes + J.total + J.nc <= J.fasta_cap;
+    if (!J.direct_fetch) J.polished.resize(J.total ? J.total : 1);
+    if (rc == PP_OK) rc = pp_polish_result(ctx, J.direct_fetch ? nullptr : J.polished.data(), PP_MEM_HOST, J.out_off.data(), J.stats.data());
+    return rc;
+}
+
+// ---- the plan, from the alignment counts per contig ----
+// source batches in file order: sharded -> (file, slice) pieces living on the contexts' GPUs; host ingest -> files
+int collect_sources(PolishJob &J, std::vector<uint64_t> &per_contig) {
+    uint64_t base = 0;
+    if (!J.sharded) {
+        for (pp_ingest *gi : J.gs) {
+            pp_aln_batch v;
+            pp_ingest_batch(gi, &v);
+            J.srcs.push_back(Src{v, -1, base, 0u, {}});
+            base += v.n_aln;
+            pp_shard_count(nullptr, &v, PP_MEM_HOST, J.nc, per_contig.data());
+        }
+        return PP_OK;
+    }
+    std::vector<pp_aln_batch> whole((size_t)J.n_ctx);
+    for (int d = 0; d < J.n_ctx; d++) pp_dev_ingest_batch(J.dgs[(size_t)d], &whole[(size_t)d]);
+    for (size_t f = 0; f < J.slice_end.size(); f++)
+        for (int sidx = 0; sidx < J.n_ctx; sidx++) {
+            const uint64_t lo = f ? J.slice_end[f - 1][(size_t)sidx] : 0, hi = J.slice_end[f][(size_t)sidx];
+            const pp_aln_batch &wb = whole[(size_t)sidx];
+            pp_aln_batch v = wb;  // seq / cigar: the whole arrays (seq_off / cig_off are absolute)
+            v.n_aln = hi - lo;
+            v.contig += lo; v.ref_start += lo; v.k += lo; v.seq_off += lo; v.seq_len += lo; v.cig_off += lo; v.n_cig += lo;
+            if (v.wo) v.wo += lo;  // (a slice's entries of the window-order mirror are its own stretch; they count from lo)
+            // the slice's runs: the whole batch's, cut to [lo, hi) and counted from lo (the tokenizer ends a run with every
+            // file: one run, the slice itself) -- with them a part of the slice takes the direct path like any other
+            std::vector<uint64_t> runs;
+            for (uint32_t r = 0; v.wo && wb.wo_run_end && r < wb.wo_n_runs; r++) {
+                const uint64_t e = std::min(std::max(wb.wo_run_end[r], lo), hi) - lo;
+                if (e > (runs.empty() ? 0 : runs.back())) runs.push_back(e);
+            }
+            if (runs.empty() || runs.back() != hi - lo) runs.clear();  // (not known: the bucketing path)
+            J.srcs.push_back(Src{v, sidx, base, (uint32_t)lo, std::move(runs)});
+            Src &s = J.srcs.back();
+            s.view.wo_n_runs = (uint32_t)s.runs.size();
+            s.view.wo_run_end = s.runs.empty() ? nullptr : s.runs.data();
+            base += hi - lo;
+        }
+    // (one context after the other: a histogram kernel each, they add into the same host array)
+    for (int d = 0; d < J.n_ctx; d++)
+        if (int rc = pp_shard_count(J.ctxs[d], &whole[(size_t)d], PP_MEM_DEVICE, J.nc, per_contig.data())) {
+            if (d) set_err(J.ctx, rc, pp_last_error(J.ctxs[d]));
+            return rc;
+        }
+    return PP_OK;
+}
+
+// ---- every source batch is split once per destination (on the GPU that holds it, or on the host) ----
+int plan_and_split(PolishJob &J) {
+    std::vector<uint64_t> per_contig(J.nc, 0);  // alignment records per contig (the planner's weights)
+    int rc = collect_sources(J, per_contig);
+    if (rc == PP_OK) rc = pp_shard_plan_create(J.nc, J.off, per_contig.data(), (uint32_t)J.n_ctx, 0, &J.plan);
+    const size_t nq = J.srcs.size();
+    J.pieces.assign((size_t)J.n_ctx, std::vector<Piece>(nq, Piece{nullptr, 0, 0, 0}));
+    for (auto &v : J.pieces)
+        for (size_t q = 0; q < nq; q++) { v[q].src = J.srcs[q].owner; v[q].base = J.srcs[q].base; }
+    if (rc == PP_OK && J.sharded)
+        rc = on_all(J, [&](int sidx) {  // a context splits the pieces it holds, for every destination
+            for (size_t q = 0; q < nq; q++)
+                for (int d = 0; J.srcs[q].owner == sidx && d < J.n_ctx; d++)
+                    if (int r = pp_shard_split_view_(J.ctxs[sidx], J.plan, (uint32_t)d, &J.srcs[q].view, PP_MEM_DEVICE,
+                                                     J.srcs[q].wo_base, &J.pieces[(size_t)d][q].part))
+                        return r;
+            return (int)PP_OK;
+        });
+    else if (rc == PP_OK)
+        rc = on_all(J, [&](int d) {
+            for (size_t q = 0; q < nq; q++)
+                if (int r = pp_shard_split(nullptr, J.plan, (uint32_t)d, &J.srcs[q].view, PP_MEM_HOST, &J.pieces[(size_t)d][q].part)) {
+                    set_err(J.ctxs[d], r, "splitting the records failed");
+                    return r;
+                }
+            return (int)PP_OK;
+        });
+    for (auto &v : J.pieces)
+        for (Piece &pc : v)
+            if (pc.part) {
+                pp_aln_batch b;
+                pp_shard_part_batch(pc.part, &b, nullptr);
+                pc.n = b.n_aln;
+            }
+    // the tokenizers' batches (and their text buffers) are not needed once every part has been cut out of them
+    for (pp_dev_ingest *&x : J.dgs) { pp_dev_ingest_free(x); x = nullptr; }
+    J.lap("records split");
+    return rc;
+}
+
+// ---- how the polished bytes will reach the host: one RCCL gather to the first context's GPU, or every device by itself ----
+// The RCCL route is OPT-IN (PP_GATHER=rccl) in this one-process driver: it has only ever run with world = 1 -- the boxes
+// this was built on have one GPU, and RCCL refuses two ranks on one device -- and a rank that fails inside
+// ncclCommInitRank leaves the other threads waiting there.  The default is the route every test runs: each device
+// copies its share out and the FASTA is assembled on the host.  (One process per GPU -- python -m
+// polypolish_amd.distributed, bench.py --gpus N -- gathers over RCCL, behind a watchdog.)
+void choose_gather_route(PolishJob &J, int rc) {
+    bool use_rccl = getenv("PP_GATHER") && !strcmp(getenv("PP_GATHER"), "rccl");
+    for (int d = 0; d < J.n_ctx && use_rccl && !getenv("PP_RCCL_LIB"); d++)  // (a stand-in library, tests: it takes several ranks on one device)
+        for (int e = 0; e < d; e++)
+            if (pp_ctx_device_(J.ctxs[d]) == pp_ctx_device_(J.ctxs[e])) use_rccl = false;  // RCCL refuses two ranks on one device
+    if (use_rccl && rc == PP_OK) {
+        uint8_t id[PP_COMM_ID_BYTES];
+        if (pp_comm_unique_id(id) != PP_OK) use_rccl = false;  // librccl not loadable
+        else {
+            J.comms = true;
+            if (on_all(J, [&](int d) { return pp_comm_init(J.ctxs[d], d, J.n_ctx, id); }) != PP_OK) {
+                for (int d = 0; d < J.n_ctx; d++) pp_comm_destroy(J.ctxs[d]);
+                J.comms = use_rccl = false;
+            }
+        }
+    }
+    J.use_rccl = use_rccl;
+    if (J.lap.on)
+        fprintf(stderr, "[timing] polished bytes -> host: %s\n",
+                use_rccl ? "ONE RCCL gather (ncclSend/ncclRecv over xGMI) to the first GPU + one D2H"
+                         : "every device copies its share out, assembled on the host (the default; PP_GATHER=rccl asks for "
+                           "the RCCL gather -- not with two contexts on one device or without librccl)");
+}
+
+// one context: its records, the ranges of its units, finish, its own bytes to the host
+int polish_rank(PolishJob &J, int d) {
+    pp_ctx *cd = J.ctxs[d];
+    RankResult &R = J.ranks[(size_t)d];
+    int r = pp_polish_begin(cd, J.nc, J.off, pp_assembly_bases(J.a), PP_MEM_HOST, &J.prm);
+    uint64_t tn = 0, ts = 0, tc = 0;
+    for (const Piece &pc : J.pieces[(size_t)d]) {
+        pp_aln_batch v;
+        pp_shard_part_batch(pc.part, &v, nullptr);  // (every part exists: the split went through)
+        tn += v.n_aln; ts += v.seq_bytes; tc += v.n_cig_total;
+    }
+    if (r == PP_OK) r = pp_polish_reserve(cd, tn + 16, ts + 64, tc + 16);
+    bool first = true;
+    for (const Piece &pc : J.pieces[(size_t)d]) {
+        if (r) break;
+        pp_aln_batch v;
+        pp_shard_part_batch(pc.part, &v, nullptr);
+        if (v.n_aln == 0) continue;
+        // (a part on this context's own GPU is device memory; the FIRST batch of a job would be used in place,
+        // which is fine -- the parts live until every context has finished)
+        const int pm = pp_shard_part_mem(pc.part);
+        r = pp_polish_add(cd, &v, pm == PP_MEM_HOST ? PP_MEM_HOST : (pc.src == d && !first ? PP_MEM_DEVICE : PP_MEM_PEER));
+        first = false;
+    }
+    std::vector<uint64_t> lo(J.nc), hi(J.nc);
+    if (r == PP_OK) r = pp_shard_emit_ranges(J.plan, (uint32_t)d, lo.data(), hi.data());
+    if (r == PP_OK) r = pp_polish_set_emit(cd, lo.data(), hi.data());
+    if (r == PP_OK) r = pp_polish_finish(cd);
+    if (r == PP_OK) r = pp_polish_result_size(cd, &R.total);
+    // offsets and statistics now; the bytes follow over RCCL, or (host route) with this very call
+    if (r == PP_OK && !J.use_rccl) R.bytes.resize(R.total ? R.total : 1);
+    if (r == PP_OK) r = pp_polish_result(cd, J.use_rccl ? nullptr : R.bytes.data(), PP_MEM_HOST, R.off.data(), R.stats.data());
+    return R.rc = r;
+}
+
+// the one exchange of the job: every context's bytes to the first context's GPU, then one copy to the host
+int gather_over_rccl(PolishJob &J) {
+    uint64_t sum = 0;
+    for (const RankResult &R : J.ranks) sum += R.total;
+    J.gathered.resize(sum ? sum : 1);
+    std::vector<uint64_t> lens((size_t)J.n_ctx, 0);
+    const auto tg = std::chrono::steady_clock::now();
+    int rc = on_all(J, [&](int d) {
+        return pp_polish_gather_to_host_(J.ctxs[d], d == 0 ? J.gathered.data() : nullptr, d == 0 ? sum : 0,
+                                         d == 0 ? lens.data() : nullptr, nullptr);
+    });
+    if (J.lap.on) fprintf(stderr, "[timing] RCCL gather of %llu bytes from %d contexts + one D2H: %.3f ms\n", (unsigned long long)sum, J.n_ctx,
+                          1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - tg).count());
+    for (int d = 0; rc == PP_OK && d < J.n_ctx; d++)
+        if (lens[(size_t)d] != J.ranks[(size_t)d].total) rc = set_err(J.ctx, PP_ERR_HIP, "the RCCL gather delivered a rank's bytes short");
+    return rc;
+}
+
+// The job's error is the one about its FIRST bad record in file order (the reference streams,
+// src/alignment.rs:238-303): a context numbers the records it was sent, the parts know where those came from.
+int first_error_of_job(PolishJob &J, int rc) {
+    uint64_t best = ~0ull;
+    int best_d = -1;
+    uint32_t best_kind = 0;
+    for (int d = 0; d < J.n_ctx; d++) {
+        if (J.ranks[(size_t)d].rc == PP_OK) continue;
+        uint32_t kind = 0;
+        const uint64_t jr = job_record_of(J.ctxs[d], J.ctxs, J.pieces[(size_t)d], &kind);
+        if (best_d < 0 || jr < best) { best = jr; best_d = d; best_kind = kind; }
+    }
+    if (best_d < 0) return rc;
+    if (best != ~0ull) return pp_polish_error_text(J.ctx, best_kind, best);
+    rc = J.ranks[(size_t)best_d].rc;
+    if (best_d) set_err(J.ctx, rc, pp_last_error(J.ctxs[best_d]));
+    return rc;
+}
+
+// every context polishes its share, side by side
+int polish_on_all_contexts(PolishJob &J) {
+    J.ranks.assign((size_t)J.n_ctx, RankResult{});
+    for (RankResult &R : J.ranks) { R.off.assign(J.nc + 1, 0); R.stats.resize(J.nc); }
+    (void)on_all(J, [&](int d) { return polish_rank(J, d); });
+    bool all_ok = true;
+    for (const RankResult &R : J.ranks) all_ok = all_ok && R.rc == PP_OK;
+    return first_error_of_job(J, all_ok && J.use_rccl ? gather_over_rccl(J) : PP_OK);
+}
+
+// --debug: the plan's units in order (contig by contig, a tiled contig's windows in position order), each formatted by
+// the context that emits it -- neighbouring units of one context in one go
+int write_debug_by_units(PolishJob &J) {
+    const pp_shard_plan *plan = J.plan;
+    const uint64_t *off = J.off;
+    int rc = PP_OK;
+    for (uint32_t u = 0; rc == PP_OK && u < plan->n_units;) {
+        const uint32_t r = plan->rank[u];
+        const uint64_t lo = off[plan->contig[u]] + plan->lo[u];
+        uint64_t hi = off[plan->contig[u]] + plan->hi[u];
+        for (u++; u < plan->n_units && plan->rank[u] == r && off[plan->contig[u]] + plan->lo[u] == hi; u++) hi = off[plan->contig[u]] + plan->hi[u];
+        if (r >= (uint32_t)J.n_ctx) return set_err(J.ctx, PP_ERR_HIP, "a unit of the plan names no context");
+        rc = write_debug_tsv(J.ctxs[r], J.dbg, J.names, lo, hi);
+        if (rc && r) set_err(J.ctx, rc, pp_last_error(J.ctxs[r]));
+    }
+    return rc;
+}
+
+int assemble_from_ranks(PolishJob &J) {
+    std::vector<const uint8_t *> bp((size_t)J.n_ctx);
+    std::vector<const uint64_t *> op((size_t)J.n_ctx);
+    uint64_t at = 0;
+    for (int d = 0; d < J.n_ctx; d++) {
+        const RankResult &R = J.ranks[(size_t)d];
+        bp[(size_t)d] = J.use_rccl ? J.gathered.data() + at : R.bytes.data();
+        at += R.total;
+        op[(size_t)d] = R.off.data();
+    }
+    int rc = pp_shard_assemble(J.plan, bp.data(), op.data(), nullptr, J.out_off.data());
+    J.total = J.out_off[J.nc];
+    J.polished.resize(J.total ? J.total : 1);
+    if (rc == PP_OK) rc = pp_shard_assemble(J.plan, bp.data(), op.data(), J.polished.data(), J.out_off.data());
+    for (uint32_t c = 0; c < J.nc; c++) {  // a position is counted by the rank that emits it
+        J.stats[c] = pp_contig_stats{J.out_off[c + 1] - J.out_off[c], 0, 0, 0.0};
+        for (const RankResult &R : J.ranks) {
+            J.stats[c].changed += R.stats[c].changed;
+            J.stats[c].zero_depth += R.stats[c].zero_depth;
+            J.stats[c].depth_sum += R.stats[c].depth_sum;
+        }
+    }
+    return rc;
+}
+
+int polish_on_several_contexts(PolishJob &J) {
+    int rc = plan_and_split(J);
+    choose_gather_route(J, rc);
+    if (rc == PP_OK) rc = polish_on_all_contexts(J);
+    J.lap("uploaded + polished on the devices");
+    if (J.dbg && rc == PP_OK) rc = write_debug_by_units(J);
+    rc = close_debug_file(J, rc, true);
+    if (rc == PP_OK) rc = assemble_from_ranks(J);
+    J.release_exchange();
+    return rc;
+}
+
+// print_seq_to_stdout (polish.rs:196-203), one contig after the other in FASTA order, with print_polishing_info's lines
+int write_fasta_and_log(PolishJob &J, pp_bytes *fasta) {
+    const uint32_t nc = J.nc;
+    const uint64_t *off = J.off, *out_off = J.out_off.data();
+    if (J.out_toucher.joinable()) J.out_toucher.join();
+    if (!J.out || J.header_bytes + J.total + nc > J.fasta_cap) {  // (a job whose polished bytes outgrow the bound: a buffer of the exact size)
+        free(J.out);
+        J.out = (uint8_t *)malloc(J.header_bytes + J.total + nc + 1);
+        if (!J.out) return set_err(J.ctx, PP_ERR_HIP, "out of host memory for the FASTA");
+    }
+    uint8_t *out = J.out;
+    const uint8_t *d_polished = J.direct_fetch ? pp_polish_result_device(J.ctx) : nullptr;
     size_t w = 0;
     for (uint32_t c = 0; c < nc; c++) {
-        const char *name = pp_assembly_name(a, c), *desc = pp_assembly_description(a, c);
+        const char *name = J.names[c], *desc = pp_assembly_description(J.a, c);
         out[w++] = '>';
         memcpy(out + w, name, strlen(name)); w += strlen(name);
         if (desc[0]) {
@@ -829,37 +864,104 @@ static int polish_files_impl(pp_ctx *const *ctxs, int n_ctx, const char *assembl
             memcpy(out + w, desc, strlen(desc)); w += strlen(desc);
         }
         memcpy(out + w, " polypolish\n", 12); w += 12;
-        if (direct_fetch) {
-            if (int rd = pp_ctx_download(ctx, out + w, d_polished + out_off[c], out_off[c + 1] - out_off[c])) { free_all(); return rd; }
-        } else memcpy(out + w, polished.data() + out_off[c], out_off[c + 1] - out_off[c]);
+        if (J.direct_fetch) {
+            if (int rd = pp_ctx_download(J.ctx, out + w, d_polished + out_off[c], out_off[c + 1] - out_off[c])) return rd;
+        } else memcpy(out + w, J.polished.data() + out_off[c], out_off[c + 1] - out_off[c]);
         w += out_off[c + 1] - out_off[c];
         out[w++] = '\n';
         // print_polishing_info, polish.rs:206-227
+        const pp_contig_stats &s = J.stats[c];
         const double len = (double)(off[c + 1] - off[c]);
-        const double changed_pct = 100.0 * (double)stats[c].changed / len;
-        log("Polishing %s (%s bp):\n  mean read depth: %.1fx\n  %s bp %s a depth of zero (%.4f%% coverage)\n"
-            "  %s %s changed (%.4f%% of total positions)\n  estimated pre-polishing sequence accuracy: %.4f%% (%s)\n\n",
-            name, commas(off[c + 1] - off[c]).c_str(), stats[c].depth_sum / len, commas(stats[c].zero_depth).c_str(),
-            stats[c].zero_depth == 1 ? "has" : "have", 100.0 * (len - (double)stats[c].zero_depth) / len,
-            commas(stats[c].changed).c_str(), stats[c].changed == 1 ? "position" : "positions", changed_pct,
-            100.0 - changed_pct, qscore(100.0 - changed_pct).c_str());
+        const double changed_pct = 100.0 * (double)s.changed / len;
+        J.log("Polishing %s (%s bp):\n  mean read depth: %.1fx\n  %s bp %s a depth of zero (%.4f%% coverage)\n"
+              "  %s %s changed (%.4f%% of total positions)\n  estimated pre-polishing sequence accuracy: %.4f%% (%s)\n\n",
+              name, commas(off[c + 1] - off[c]).c_str(), s.depth_sum / len, commas(s.zero_depth).c_str(),
+              s.zero_depth == 1 ? "has" : "have", 100.0 * (len - (double)s.zero_depth) / len,
+              commas(s.changed).c_str(), s.changed == 1 ? "position" : "positions", changed_pct,
+              100.0 - changed_pct, qscore(100.0 - changed_pct).c_str());
     }
     fasta->data = out;
     fasta->len = w;
-    out = nullptr;  // the caller's now (pp_bytes_free)
-    lap("FASTA assembled");
-
-    // finished_message, polish.rs:76-90
-    log("Finished!\nPolished sequence (to stdout):\n");
-    for (uint32_t c = 0; c < nc; c++)
-        log("  %s_polypolish (%s bp)\n", pp_assembly_name(a, c), commas(stats[c].polished_len).c_str());
-    double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    log("\nTime to run: %s\n\n", format_duration(secs).c_str());
-    free_all();
-    lap("device and host buffers released");
+    J.out = nullptr;  // the caller's now (pp_bytes_free)
+    J.lap("FASTA assembled");
     return PP_OK;
 }
 
+// finished_message, polish.rs:76-90
+void log_finished(const PolishJob &J) {
+    J.log("Finished!\nPolished sequence (to stdout):\n");
+    for (uint32_t c = 0; c < J.nc; c++) J.log("  %s_polypolish (%s bp)\n", J.names[c], commas(J.stats[c].polished_len).c_str());
+    J.log("\nTime to run: %s\n\n", format_duration(J.lap.seconds()).c_str());
+}
+
+// polish::polish (src/polish.rs:26-38) for one look at the input.  HAND_BACK: nothing was polished, the host ingest is to
+// take the input, its log resuming at file J.handed_back_at.
+int polish_once(PolishJob &J, pp_bytes *fasta) {
+    if (int rc = check_options_and_inputs(J)) return rc;
+    log_banner(J);
+    J.lap("driver entered");
+    if (int rc = load_assembly(J)) return rc;
+    J.lap("assembly loaded");
+    reserve_fasta(J);
+    if (int rc = load_alignments(J)) return rc;
+    // polish_sequences, polish.rs:137-154 -- on the device
+    J.log("Polishing assembly sequences\n");
+    if (int rc = create_debug_file(J)) return rc;
+    if (int rc = J.multi ? polish_on_several_contexts(J) : polish_on_one_context(J)) return rc;
+    J.lap(J.direct_fetch ? "result: offsets fetched" : "result fetched");
+    if (int rc = write_fasta_and_log(J, fasta)) return rc;
+    log_finished(J);
+    J.release();
+    J.lap("device and host buffers released");
+    return PP_OK;
+}
+
+}  // namespace
+
+// (tests) where the multi-GPU driver would cut `text` at or after `from`
+extern "C" uint64_t pp_sam_group_cut_(const char *text, uint64_t size, uint64_t from) { return group_cut(text, (size_t)size, (size_t)from); }
+
+static int polish_files_impl(pp_ctx *const *ctxs, int n_ctx, const char *assembly, const char *const *sams, int n_sams,
+                             const pp_polish_options *opt, pp_bytes *fasta, const uint8_t *const *pass, const uint64_t *n_pass) {
+    if (!ctxs[0] || !assembly || !opt || !fasta || (n_sams > 0 && !sams)) return PP_ERR_ARG;
+    fasta->data = nullptr;
+    fasta->len = 0;
+    // The second look, if the device tokenizer hands a file back: a job of its own on the host ingest, after everything of
+    // the first has been released.
+    for (int resume_log_at = -1;;) {
+        PolishJob job{ctxs, n_ctx, assembly, sams, n_sams, opt, pass, n_pass, resume_log_at};
+        const int rc = polish_once(job, fasta);
+        if (rc != HAND_BACK) return rc;
+        resume_log_at = job.handed_back_at;
+    }
+}
+
+extern "C" int pp_polish_files_filtered_(pp_ctx *ctx, const char *assembly, const char *const *sams, int n_sams,
+                                         const pp_polish_options *opt, pp_bytes *fasta,
+                                         const uint8_t *const *pass, const uint64_t *n_pass) {
+    return polish_files_impl(&ctx, 1, assembly, sams, n_sams, opt, fasta, pass, n_pass);
+}
+
+extern "C" int pp_polish_files(pp_ctx *ctx, const char *assembly, const char *const *sams, int n_sams,
+                               const pp_polish_options *opt, pp_bytes *fasta) {
+    return polish_files_impl(&ctx, 1, assembly, sams, n_sams, opt, fasta, nullptr, nullptr);
+}
+
+// One process, several GPUs (polish::polish has no counterpart: src/polish.rs:137-154 is one thread): every context
+// uploads and tokenizes its own slice of every SAM file (or the host ingest parses once), the records are partitioned --
+// a context is sent the records that reach its units (pp_shard_split) -- the contexts polish side by side on their own
+// threads, and every device copies its own share of the polished bytes out for the host to put together -- or, with
+// PP_GATHER=rccl, the bytes meet on the first context's GPU in ONE RCCL gather over xGMI (pp_polish_gather: the north
+// star's "single RCCL gather for the final FASTA") followed by one device-to-host copy.  The RCCL route of THIS driver is
+// opt-in until it has run on a multi-GPU node (see below); it cannot run without librccl or with two contexts on one
+// device (PP_SHARE_GPU, tests).  PP_TIMING prints the route that was taken.
+extern "C" int pp_polish_files_multi(pp_ctx *const *ctxs, int n_ctx, const char *assembly, const char *const *sams,
+                                     int n_sams, const pp_polish_options *opt, pp_bytes *fasta) {
+    if (!ctxs || n_ctx < 1) return PP_ERR_ARG;
+    for (int i = 0; i < n_ctx; i++)
+        if (!ctxs[i]) return PP_ERR_ARG;
+    return polish_files_impl(ctxs, n_ctx, assembly, sams, n_sams, opt, fasta, nullptr, nullptr);
+}
 
 extern "C" int pp_log_text(int what, double value, char *out, size_t cap) {
     if (!out || cap == 0) return PP_ERR_ARG;

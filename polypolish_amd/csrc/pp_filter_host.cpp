@@ -17,8 +17,6 @@
 #include <algorithm>
 #include <array>
 #include <atomic>
-#include <chrono>
-#include <functional>
 #include <cmath>
 #include <cstdarg>
 #include <string>
@@ -30,33 +28,11 @@
 using pph::HugeBuf;
 using pph::parallel_for;
 
-extern "C" int pp_ctx_set_error_(pp_ctx *ctx, int code, const char *msg);
-
 namespace {
 
-struct Log {
-    bool quiet;
-    void operator()(const char *fmt, ...) const {
-        if (quiet) return;
-        va_list ap;
-        va_start(ap, fmt);
-        vfprintf(stderr, fmt, ap);
-        va_end(ap);
-    }
-};
-
-std::string commas(uint64_t v) {  // num-format's Locale::en grouping
-    std::string s = std::to_string(v), out;
-    const int n = (int)s.size();
-    for (int i = 0; i < n; i++) {
-        out.push_back(s[i]);
-        const int left = n - 1 - i;
-        if (left > 0 && left % 3 == 0) out.push_back(',');
-    }
-    return out;
-}
-
+using pph::commas;
 using pph::format_duration;
+using pph::Log;
 using pph::percentile_name;
 
 struct FilterErr {
@@ -331,12 +307,7 @@ extern "C" int pp_filter_load(const char *in1, const char *in2, pp_filter_loaded
     uint64_t &before = L->before;
     uint32_t &n_reads = L->n_reads;
     unsigned &threads = L->threads;
-    const bool timing = getenv("PP_TIMING") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (timing) fprintf(stderr, "[timing]   load: %-22s %8.3f s\n", what,
-                            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-    };
+    const pph::Lap lap{"  load: ", 22, false};
     try {
         // Both files are parsed before any name is interned (the table is sized from the exact record
         // count); what the reference would report while loading file 1 still comes first.
@@ -812,8 +783,8 @@ struct FilterRun {
 };
 
 // load_alignments + get_insert_size_thresholds + the pass/fail verdicts (filter.rs:26-34 without filter_sams)
-int filter_core(pp_ctx *ctx, const Log &log, const std::function<void(const char *)> &lap, const char *in1, const char *in2,
-                const char *orientation, double low, double high, FilterRun &R) {
+int filter_core(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char *in1, const char *in2, const char *orientation,
+                double low, double high, FilterRun &R) {
     auto set_err = [&](int code, const char *msg) { return pp_ctx_set_error_(ctx, code, msg); };
     log("Loading alignments\n");
     const char *ins[2] = {in1, in2};
@@ -995,12 +966,7 @@ extern "C" int pp_filter_files(pp_ctx *ctx, const char *in1, const char *in2, co
                                pp_filter_report *report) {
     if (!ctx || !in1 || !in2 || !out1 || !out2 || !orientation) return PP_ERR_ARG;
     Log log{quiet != 0};
-    const auto t0 = std::chrono::steady_clock::now();
-    const bool timing = getenv("PP_TIMING") != nullptr;
-    auto lap = [&](const char *what) {
-        if (timing) fprintf(stderr, "[timing] %-28s %8.3f s\n", what,
-                            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-    };
+    const pph::Lap lap{"", 28, false};
     const char *f4[4] = {in1, in2, out1, out2};
     if (int rc = check_filter_options(ctx, f4, 4, low, high)) return rc;
     log("\nStarting Polypolish filter\n%s\n\nInput alignments:\n  %s\n  %s\n\nOutput alignments:\n  %s\n  %s\n\n"
@@ -1019,15 +985,10 @@ extern "C" int pp_filter_files(pp_ctx *ctx, const char *in1, const char *in2, co
         report->orientation = R.correct;
         for (int o = 0; o < 4; o++) report->orientation_counts[o] = R.counts[o];
     }
-    const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     log("Finished!\nAlignments before filtering: %s\nAlignments after filtering:  %s\n\nTime to run: %s\n\n",
-        commas(R.before).c_str(), commas(after).c_str(), format_duration(secs).c_str());
+        commas(R.before).c_str(), commas(after).c_str(), format_duration(lap.seconds()).c_str());
     return PP_OK;
 }
-
-extern "C" int pp_polish_files_filtered_(pp_ctx *ctx, const char *assembly, const char *const *sams, int n_sams,
-                                         const pp_polish_options *opt, pp_bytes *fasta,
-                                         const uint8_t *const *pass, const uint64_t *n_pass);
 
 extern "C" int pp_filter_polish_files(pp_ctx *ctx, const char *assembly, const char *in1, const char *in2,
                                       const char *out1, const char *out2, const char *orientation, double low,
@@ -1037,12 +998,7 @@ extern "C" int pp_filter_polish_files(pp_ctx *ctx, const char *assembly, const c
     if ((out1 == nullptr) != (out2 == nullptr))
         return pp_ctx_set_error_(ctx, PP_ERR_ARG, "pp_filter_polish_files: give both --out1 and --out2 or neither");
     Log log{opt->quiet != 0};
-    const auto t0 = std::chrono::steady_clock::now();
-    const bool timing = getenv("PP_TIMING") != nullptr;
-    auto lap = [&](const char *what) {
-        if (timing) fprintf(stderr, "[timing] %-28s %8.3f s\n", what,
-                            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-    };
+    const pph::Lap lap{"", 28, false};
     const char *f4[4] = {in1, in2, out1, out2};
     if (int rc = check_filter_options(ctx, f4, out1 ? 4 : 2, low, high)) return rc;
     log("\nStarting Polypolish filter + polish (fused)\n%s\n\nInput alignments:\n  %s\n  %s\n\n"

@@ -1,5 +1,6 @@
-// pp_host.h -- host-side utilities shared by the SAM ingest (pp_ingest.cpp) and the filter driver
-// (pp_filter_host.cpp): huge-page growable arrays, a fork-join parallel_for, a read-only file mapping.
+// pp_host.h -- host-side utilities shared by the SAM ingest (pp_ingest.cpp) and the command drivers (pp_driver.cpp,
+// pp_filter_host.cpp): huge-page growable arrays, a fork-join parallel_for, a read-only file mapping, the run log's
+// helpers, and the declarations of the library's internal entry points.
 #pragma once
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -7,6 +8,8 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <chrono>
+#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -18,6 +21,34 @@
 #include <string>
 #include <thread>
 #include <vector>
+
+#include "polypolish_hip.h"
+
+// ---- internal entry points the host files share (the trailing underscore keeps them out of polypolish_hip.h) ----
+extern "C" {
+int pp_ctx_set_error_(pp_ctx *ctx, int code, const char *msg);  // pp_ctx is opaque to the host files: its error text is stored through this hook
+int pp_ctx_device_(const pp_ctx *ctx);                          // the device a context runs on
+void pp_ctx_enable_peers_(pp_ctx *const *ctxs, int n);          // peer access between the contexts' devices, best effort (PP_MEM_PEER copies)
+void *pp_host_pinned_alloc_(pp_ctx *ctx, uint64_t bytes);       // pinned host memory for the --debug TSV's chunks ...
+void pp_host_pinned_free_(void *p);                             // ... and its release
+void pp_process_leaving_soon_(int yes);                         // (bin/polypolish only) the process exits right after the command: pph::process_leaving_soon
+int pp_dev_ingest_reserve_text_(pp_dev_ingest *D, uint64_t bytes);  // room for the text of the job's largest file, once
+// the text of the file the next pp_dev_ingest_sam will take goes up while the one before is tokenized
+void pp_dev_ingest_prefetch_(pp_dev_ingest *D, const char *path, uint64_t second_buffer_bytes);
+// one context's slice of a SAM file (the multi-GPU driver cuts at read-group boundaries); any defect in the text only says so
+int pp_dev_ingest_slice_(pp_dev_ingest *D, const char *path, const char *text, uint64_t size, pp_sam_counts *counts);
+// did the last pp_ingest_sam fail where the records before are known?  *cut = bytes of the file holding exactly those groups
+int pp_ingest_fail_cut_(const pp_ingest *I, uint64_t *cut);
+// ingest only the first `cut` bytes of the file
+int pp_ingest_sam_prefix_(pp_ingest *I, const char *path, uint64_t cut, const uint8_t *pass, uint64_t n_pass, pp_sam_counts *counts, char *err, size_t errlen);
+// pp_polish_files with per-file filter verdicts (pp_filter_polish_files)
+int pp_polish_files_filtered_(pp_ctx *ctx, const char *assembly, const char *const *sams, int n_sams, const pp_polish_options *opt, pp_bytes *fasta,
+                              const uint8_t *const *pass, const uint64_t *n_pass);
+// pp_shard_split of a view on records [lo, hi) of a larger batch: wo_idx_base = what the file_idx of batch->wo count from
+int pp_shard_split_view_(pp_ctx *ctx, const pp_shard_plan *plan, uint32_t dest, const pp_aln_batch *batch, int mem, uint32_t wo_idx_base, pp_shard_part **out);
+// pp_polish_gather with the payload copied to rank 0's host_out in one transfer
+int pp_polish_gather_to_host_(pp_ctx *ctx, uint8_t *host_out, uint64_t cap, uint64_t *rank_len, uint64_t *rank_contig_off);
+}
 
 #ifndef PP_MIRROR_REGISTRY_DECLARED
 #define PP_MIRROR_REGISTRY_DECLARED
@@ -292,6 +323,47 @@ inline void line_slices(const char *text, size_t size, unsigned threads, std::ve
     }
     cut[threads] = end;
 }
+
+// ---- the run log on stderr ----
+struct Log {
+    bool quiet;
+    void operator()(const char *fmt, ...) const {
+        if (quiet) return;
+        va_list ap;
+        va_start(ap, fmt);
+        vfprintf(stderr, fmt, ap);
+        va_end(ap);
+    }
+};
+
+// num-format's Locale::en grouping (polish.rs:99 etc.)
+inline std::string commas(uint64_t v) {
+    std::string s = std::to_string(v), out;
+    const int n = (int)s.size();
+    for (int i = 0; i < n; i++) {
+        out.push_back(s[i]);
+        const int left = n - 1 - i;
+        if (left > 0 && left % 3 == 0) out.push_back(',');
+    }
+    return out;
+}
+
+// PP_TIMING=1: "[timing] <prefix><stage, padded to width>  <seconds since this was made>", and with since_process
+// "  (process <seconds since the process started>)" behind it
+struct Lap {
+    const char *prefix;
+    int width;
+    bool since_process;
+    bool on = getenv("PP_TIMING") != nullptr;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    double seconds() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+    void operator()(const char *what) const {
+        if (!on) return;
+        char tail[48] = "";
+        if (since_process) snprintf(tail, sizeof tail, "  (process %7.3f s)", seconds_since_process_start());
+        fprintf(stderr, "[timing] %s%-*s %8.3f s%s\n", prefix, width, what, seconds(), tail);
+    }
+};
 
 // ---- text of the run log (the reference pins these three with unit tests; exported as pp_log_text) ----
 // qscore, polish.rs:290-300

@@ -270,6 +270,18 @@ def test_debug_on_several_contexts_in_one_process(orc, tmp_path, n_ctx):
     assert got == want["debug"], _diff(got, want["debug"])
 
 
+def test_debug_file_that_cannot_be_created_on_several_contexts(tmp_path):
+    """create_debug_file (polish.rs:230-245) fails after the alignments are loaded: with two contexts the command leaves
+    then with the tokenizers of both still alive -- the reference's message, exit code 1, nothing on stdout."""
+    ds = synth.rich_dataset(str(tmp_path), seed=84, contig_lens=(30_000, 900), coverage=12, repeat_len=300, repeat_copies=3)
+    bad = str(tmp_path / "no" / "such" / "dir.tsv")
+    for ingest in ("1", "0"):
+        r = subprocess.run([EXE, "polish", "--debug", bad, ds["fasta"], ds["sam1"], ds["sam2"]], capture_output=True,
+                           timeout=300, env=dict(os.environ, PP_SHARE_GPU="2", PP_DEVICE_INGEST=ingest))
+        assert r.returncode == 1 and r.stdout == b"", (ingest, r.stderr.decode()[-2000:])
+        assert f'unable to create "{bad}"'.encode() in r.stderr, (ingest, r.stderr.decode()[-2000:])
+
+
 # ---- 6. the one-process-per-GPU launcher -------------------------------------------------------------------------------
 def test_debug_through_the_distributed_launcher(orc, tmp_path):
     ds = synth.rich_dataset(str(tmp_path), seed=81, contig_lens=(140_000, 900, 2_000), coverage=12, repeat_len=300,

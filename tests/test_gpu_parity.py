@@ -898,10 +898,11 @@ def test_cli_with_either_ingest(orc, tmp_path, case):
     ds = synth.rich_dataset(str(tmp_path), **case)
     sams = [ds["sam1"], ds["sam2"]]
     want = orc.polish_files(ds["fasta"], sams)
-    for mode in ("1", "0"):
+    # (the third: the host ingest with ONE ingest object for all files and no upload while the next file is parsed)
+    for env in (dict(PP_DEVICE_INGEST="1"), dict(PP_DEVICE_INGEST="0"), dict(PP_DEVICE_INGEST="0", PP_STREAM_ADDS="0")):
         r = subprocess.run([os.path.join(ROOT, "bin", "polypolish"), "polish", ds["fasta"], *sams], capture_output=True,
-                           env=dict(os.environ, PP_DEVICE_INGEST=mode))
-        assert r.returncode == 0 and r.stdout == want["fasta"], r.stderr.decode()[-800:]
+                           env=dict(os.environ, **env))
+        assert r.returncode == 0 and r.stdout == want["fasta"], (env, r.stderr.decode()[-800:])
         log = r.stderr.decode()
         assert f"{want['counts'][1]:,} alignments kept" in log
     # `polypolish filter` with the load on the device (default) and on the host
@@ -1538,6 +1539,7 @@ def test_several_contexts_report_the_first_bad_record_of_the_job(orc, tmp_path):
         return f"{name}\t0\t{ctg}\t{pos}\t60\t{cigar}\t*\t0\t0\t{ref[pos - 1:pos - 1 + n]}\t*\t{tags}\n"
     recs = [line(f"g{i}", "c" if i % 5 else "d", 1 + int(rng.integers(0, 2900 if i % 5 == 0 else 8700)), "40M", 40) for i in range(4000)]
     exe = os.path.join(ROOT, "bin", "polypolish")
+    err = lambda r: [l for l in r.stderr.decode().splitlines() if l.startswith("Error:")]
     for at in ((700, 3100), (3100, 700), (2000,)):
         lines = list(recs)
         for j, a in enumerate(at):
@@ -1550,8 +1552,23 @@ def test_several_contexts_report_the_first_bad_record_of_the_job(orc, tmp_path):
             multi = subprocess.run([exe, "polish", str(fa), str(sam)], capture_output=True,
                                    env=dict(os.environ, PP_SHARE_GPU="3", PP_DEVICE_INGEST=ingest))
             assert multi.returncode == 1 and multi.stdout == b""
-            err = lambda r: [l for l in r.stderr.decode().splitlines() if l.startswith("Error:")]
             assert err(multi) == err(single), (at, ingest, multi.stderr[-400:])
+    # The defect in a SECOND file: the 4000 good records in the first one, the bad record among a few hundred of the second
+    # -- and the same with a line the parsers refuse further down that file: the records in front of it are then replayed,
+    # the first context taking the first file's batch whole, and the walk's error about the bad record stands.
+    first, second = tmp_path / "first.sam", tmp_path / "second.sam"
+    first.write_text("".join(recs))
+    tail = list(recs[:300])
+    tail[120] = line("bad0", "c", 8000, "10M4N26M", 36)
+    for parse_bad in ("", "p\t0\tc\t9\t60\t40M\n"):
+        second.write_text("".join(tail[:200]) + parse_bad + "".join(tail[200:]))
+        cmd = [exe, "polish", str(fa), str(first), str(second)]
+        single = subprocess.run(cmd, capture_output=True, env=dict(os.environ, PP_DEVICE="0"))
+        assert single.returncode == 1 and len(err(single)) == 1 and "alignment record" in err(single)[0], single.stderr[-300:]
+        for ingest in ("1", "0"):
+            multi = subprocess.run(cmd, capture_output=True, env=dict(os.environ, PP_SHARE_GPU="3", PP_DEVICE_INGEST=ingest))
+            assert multi.returncode == 1 and multi.stdout == b""
+            assert err(multi) == err(single), (bool(parse_bad), ingest, multi.stderr[-400:])
 
 
 def test_two_defects_are_reported_in_streaming_order(orc, tmp_path):
@@ -1592,8 +1609,9 @@ def test_two_defects_are_reported_in_streaming_order(orc, tmp_path):
         assert want.returncode != 0, name
         want_kind = [k for k in kinds if k in want.stderr]
         assert len(want_kind) == 1, (name, want.stderr)
-        for ingest in ("1", "0"):
-            got = subprocess.run([exe, "polish", str(fa)] + paths, capture_output=True, env=dict(os.environ, PP_DEVICE_INGEST=ingest))
+        # (the third: the records in front of the defect, the earlier file's included, sit in ONE host ingest object)
+        for ingest in (dict(PP_DEVICE_INGEST="1"), dict(PP_DEVICE_INGEST="0"), dict(PP_DEVICE_INGEST="0", PP_STREAM_ADDS="0")):
+            got = subprocess.run([exe, "polish", str(fa)] + paths, capture_output=True, env=dict(os.environ, **ingest))
             assert got.returncode == want.returncode and got.stdout == b"", (name, ingest, got.stderr)
             assert want_kind[0] in got.stderr, (name, ingest, want.stderr, got.stderr)
 
