@@ -219,6 +219,63 @@ void pp_prepared_batch(const pp_prepared *p, pp_aln_batch *out); /* borrowed vie
 int pp_prepared_kernel_ms(const pp_prepared *p, float *ms);
 void pp_prepared_free(pp_prepared *p);
 
+/* The step in front of it for a caller who holds RAW records: process_one_read (src/alignment.rs:275-322) over the alignment
+ * records of ONE SAM file as Alignment::new leaves them, on the device -- what pp_ingest_sam / pp_dev_ingest_sam do behind the
+ * SAM text.  With it the record chain filter -> gate -> prepare -> polish needs nothing but this header.
+ *   flag       SAM FLAG; bit 4: the record takes part in nothing (alignment.rs:250), bit 16: the strand
+ *   read_id    QNAME as a number: adjacent ALIGNED records are one read <=> equal ids (alignment.rs:255; an unaligned record
+ *              between two of them does not part them)
+ *   contig, ref_start   as pp_aln_batch (copied, not looked at);  nm = NM:i
+ *   seq        seq_len[r] ASCII bytes, any case, at seq + seq_off[r], packed anywhere; seq_len 0 = SEQ "*" (BAM's l_seq 0)
+ *   cigar      n_cig[r] packed runs at cigar + cig_off[r]: any of the nine ops, every length >= 1 */
+typedef struct {
+    uint64_t n_rec;
+    const uint16_t *flag;
+    const uint64_t *read_id;
+    const uint32_t *contig, *ref_start, *nm;
+    const uint64_t *seq_off;
+    const uint32_t *seq_len;
+    const uint64_t *cig_off;
+    const uint32_t *n_cig;
+    const uint8_t *seq;
+    uint64_t seq_bytes;
+    const uint32_t *cigar;
+    uint64_t n_cig_total;
+} pp_raw_batch;
+/* A read group is a maximal run of adjacent aligned records with equal read_id.  With `careful` a group of more than one
+ * record is left out whole, unlooked at.  Every other group needs a source -- its first record with seq_len > 0 -- or the
+ * call ends with PP_ERR_QUIT ("no alignments for read record N contain sequence"), and none of its records may have
+ * n_cig == 0 (PP_ERR_PANIC, as the reference).  A record is GOOD when its first and its last run are each M or '=',
+ * nm <= max_errors and pass[a] != 0 (HOST memory whatever `mem`), a = its index among the ALIGNED records (the numbering of pp_filter_file and of
+ * pp_ingest_sam_filtered; pass == NULL: no verdicts, n_pass is not looked at; a line that carries ZP:Z:fail is a 0 there).
+ * The result holds the good records in file order: contig / ref_start / CIGAR runs as they came (the runs packed densely,
+ * cig_off rewritten), k = the good records of the group, the SEQ bytes ASCII-upper-cased in a room of (seq_len + 31) & ~31
+ * bytes each, rooms in record order (PP_SEQ_FILE_ORDER), zeros behind the read; a good record with seq_len == 0 takes its
+ * group's source, reverse-complemented (src/misc.rs:170-182) when bit 16 of the two flags differs.  No seq4, no wo: hand the
+ * batch to pp_polish_add, or to pp_batch_prepare (mem = PP_MEM_DEVICE) for the direct path.  orig[i] = the index of good
+ * record i in `raw`.  Byte for byte the batch pp_ingest_sam makes of the equivalent text in file order.
+ * Of several defects the one of the first group in file order is reported; *bad_record (may be NULL) = the index in `raw`
+ * of that group's first record.  n_pass other than the number of aligned records: PP_ERR_ARG, once the records have been
+ * found free of those defects.  One call per SAM file: groups never span files.
+ * PP_ERR_ARG: null arguments, PP_MEM_PEER, a null array in a non-empty batch, and a record of a group that is looked at
+ * whose SEQ or CIGAR range does not lie inside the arrays (found on the device before anything is read through it;
+ * *bad_record = that record).  PP_ERR_LIMIT: as pp_polish_add.  A batch without aligned records gates to an empty batch
+ * with counts {0, 0, 0}: "no alignments in file" is the caller's sentence.  A contig index out of range travels on and is
+ * reported by pp_polish_finish.  The context's stream has been synchronised when the call returns: `raw` may be released. */
+typedef struct {
+    uint64_t alignments; /* aligned records seen            (src/alignment.rs:252) */
+    uint64_t used;       /* good alignments kept            (src/alignment.rs:304) */
+    uint64_t reads;      /* read groups                     (src/alignment.rs:260,266) */
+} pp_sam_counts;  /* (what the ingests further down count, too) */
+typedef struct pp_gated pp_gated;
+int pp_batch_gate(pp_ctx *ctx, const pp_raw_batch *raw, int mem, uint32_t max_errors, int careful, const uint8_t *pass,
+                  uint64_t n_pass, pp_gated **out, uint64_t *bad_record);
+void pp_gated_batch(const pp_gated *g, pp_aln_batch *out, const uint32_t **orig); /* borrowed views, DEVICE memory */
+void pp_gated_counts(const pp_gated *g, pp_sam_counts *out); /* as add_to_pileup counts them (src/alignment.rs:252-266,304) */
+/* HIP-event time of the gate's kernels (not the upload of a host batch); PP_ERR_ARG unless the context had profiling on */
+int pp_gated_kernel_ms(const pp_gated *g, float *ms);
+void pp_gated_free(pp_gated *g);
+
 /* Per-contig figures the reference prints to stderr (src/polish.rs:206-227). */
 typedef struct {
     uint64_t polished_len;     /* bytes of the polished sequence                      */
@@ -480,12 +537,6 @@ const char *pp_assembly_name(const pp_assembly *a, uint32_t i);
 const char *pp_assembly_description(const pp_assembly *a, uint32_t i);
 const uint64_t *pp_assembly_offsets(const pp_assembly *a); /* n_contigs+1 */
 const uint8_t *pp_assembly_bases(const pp_assembly *a);
-
-typedef struct {
-    uint64_t alignments; /* aligned records seen            (src/alignment.rs:252) */
-    uint64_t used;       /* good alignments kept            (src/alignment.rs:304) */
-    uint64_t reads;      /* read groups                     (src/alignment.rs:260,266) */
-} pp_sam_counts;
 
 typedef struct pp_ingest pp_ingest;
 int pp_ingest_create(const pp_assembly *a, uint32_t max_errors, int careful, pp_ingest **out);

@@ -47,6 +47,19 @@ class AlnBatch(C.Structure):
                 ("wo_n_runs", C.c_uint32), ("wo_run_end", C.c_void_p)]  # optional: the mirror's runs (HOST array of u64 ends)
 
 
+class RawBatch(C.Structure):
+    """pp_raw_batch: the alignment records of one SAM file as Alignment::new leaves them (include/polypolish_hip.h)"""
+    _fields_ = [("n_rec", C.c_uint64), ("flag", C.c_void_p), ("read_id", C.c_void_p), ("contig", C.c_void_p),
+                ("ref_start", C.c_void_p), ("nm", C.c_void_p), ("seq_off", C.c_void_p), ("seq_len", C.c_void_p),
+                ("cig_off", C.c_void_p), ("n_cig", C.c_void_p), ("seq", C.c_void_p), ("seq_bytes", C.c_uint64),
+                ("cigar", C.c_void_p), ("n_cig_total", C.c_uint64)]
+
+
+RAW_FIELDS = (("flag", np.uint16), ("read_id", np.uint64), ("contig", np.uint32), ("ref_start", np.uint32), ("nm", np.uint32),
+              ("seq_off", np.uint64), ("seq_len", np.uint32), ("cig_off", np.uint64), ("n_cig", np.uint32), ("seq", np.uint8),
+              ("cigar", np.uint32))
+
+
 def _runs_of(b):
     """the run table of a batch's window-order mirror (pp_aln_batch.wo_run_end: HOST memory) as a numpy array"""
     if not b.wo_n_runs or not b.wo_run_end:
@@ -180,6 +193,7 @@ EXPORTS = [
     "pp_polish_error_record", "pp_polish_error_text", "pp_dev_ingest_set_seq_layout", "pp_dev_ingest_expect",
     "pp_ingest_set_seq_layout", "pp_polish_debug_tsv",
     "pp_batch_prepare", "pp_prepared_batch", "pp_prepared_kernel_ms", "pp_prepared_free",
+    "pp_batch_gate", "pp_gated_batch", "pp_gated_counts", "pp_gated_kernel_ms", "pp_gated_free",
 ]
 
 _lib = None
@@ -306,6 +320,14 @@ def lib():
         L.pp_prepared_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.pp_prepared_free.argtypes = [vp]
         L.pp_prepared_free.restype = None
+        L.pp_batch_gate.argtypes = [vp, C.POINTER(RawBatch), C.c_int, C.c_uint32, C.c_int, vp, C.c_uint64, C.POINTER(vp), u64p]
+        L.pp_gated_batch.argtypes = [vp, C.POINTER(AlnBatch), C.POINTER(vp)]
+        L.pp_gated_batch.restype = None
+        L.pp_gated_counts.argtypes = [vp, C.POINTER(SamCounts)]
+        L.pp_gated_counts.restype = None
+        L.pp_gated_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.pp_gated_free.argtypes = [vp]
+        L.pp_gated_free.restype = None
         _lib = L
     return _lib
 
@@ -696,6 +718,84 @@ def prepare_records(ctx, contig_off, recs):
     return PreparedBatch(ctx, contig_off, len(keep["contig"]), ptrs, len(keep["seq"]), len(keep["cigar"]), MEM_HOST)
 
 
+class GatedBatch:
+    """pp_batch_gate: the good records of one SAM file's raw records (process_one_read on the device), owned by this object.
+      .n_aln, .seq_bytes, .n_cig_total
+      .counts       (alignments, used, reads) as add_to_pileup counts them
+      .ptrs()       what Context.polish_add_ptrs / prepare_batch take, with mem = MEM_DEVICE (valid until close())
+      .host()       numpy copies of the nine arrays
+      .orig()       the index in the raw batch of every good record
+      .kernel_ms()  HIP-event time of the gate's kernels (the context had set_profiling on)"""
+
+    def __init__(self, ctx, raw, max_errors=10, careful=False, passed=None, mem=MEM_HOST):
+        L = lib()
+        if mem == MEM_HOST:
+            keep = {k: np.ascontiguousarray(raw[k], dtype=dt) for k, dt in RAW_FIELDS}
+            n_rec, seq_bytes, n_cig_total = len(keep["flag"]), len(keep["seq"]), len(keep["cigar"])
+            ptrs = {k: v.ctypes.data for k, v in keep.items()}
+        else:  # addresses of device memory, and the three sizes
+            ptrs, n_rec, seq_bytes, n_cig_total = raw, int(raw["n_rec"]), int(raw["seq_bytes"]), int(raw["n_cig_total"])
+        b = RawBatch(n_rec, ptrs["flag"], ptrs["read_id"], ptrs["contig"], ptrs["ref_start"], ptrs["nm"], ptrs["seq_off"], ptrs["seq_len"],
+                     ptrs["cig_off"], ptrs["n_cig"], ptrs["seq"], seq_bytes, ptrs["cigar"], n_cig_total)
+        v = None if passed is None else np.ascontiguousarray(passed, dtype=np.uint8)
+        self._p = C.c_void_p()
+        self._ctx = ctx
+        bad = C.c_uint64(0xFFFFFFFFFFFFFFFF)
+        rc = L.pp_batch_gate(ctx._h, C.byref(b), mem, max_errors, int(bool(careful)), v.ctypes.data if v is not None else None,
+                             len(v) if v is not None else 0, C.byref(self._p), C.byref(bad))
+        if rc:
+            e = PolypolishError(rc, L.pp_last_error(ctx._h).decode())
+            e.bad_record = None if bad.value == 0xFFFFFFFFFFFFFFFF else int(bad.value)
+            raise e
+        out, orig, cnt = AlnBatch(), C.c_void_p(), SamCounts()
+        L.pp_gated_batch(self._p, C.byref(out), C.byref(orig))
+        L.pp_gated_counts(self._p, C.byref(cnt))
+        self.mem = MEM_DEVICE
+        self.counts = (int(cnt.alignments), int(cnt.used), int(cnt.reads))
+        self.n_aln, self.seq_bytes, self.n_cig_total = int(out.n_aln), int(out.seq_bytes), int(out.n_cig_total)
+        self._ptrs = {name: (C.cast(getattr(out, name), C.c_void_p).value or 0) for name, _ in REC_FIELDS}
+        self._orig = orig.value or 0
+
+    def ptrs(self):
+        return dict(self._ptrs)
+
+    def _down(self, addr, n, dt):
+        arr = np.zeros(int(n), dtype=dt)
+        if arr.size and addr:
+            self._ctx._chk(lib().pp_ctx_download(self._ctx._h, arr.ctypes.data, addr, arr.nbytes))
+        return arr
+
+    def host(self):
+        sizes = {"seq": self.seq_bytes, "cigar": self.n_cig_total}
+        return {name: self._down(self._ptrs[name], sizes.get(name, self.n_aln), dt) for name, dt in REC_FIELDS}
+
+    def orig(self):
+        return self._down(self._orig, self.n_aln, np.uint32)
+
+    def kernel_ms(self):
+        ms = C.c_float()
+        self._ctx._chk(lib().pp_gated_kernel_ms(self._p, C.byref(ms)))
+        return float(ms.value)
+
+    def close(self):
+        if self._p:
+            lib().pp_gated_free(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def gate_records(ctx, raw: dict, max_errors=10, careful=False, passed=None, mem=MEM_HOST):
+    """pp_batch_gate on the raw records of ONE SAM file.  mem = MEM_HOST: raw = numpy arrays by the field names of pp_raw_batch
+    (RAW_FIELDS); MEM_DEVICE: raw = their device addresses plus "n_rec", "seq_bytes", "n_cig_total".  passed: None or the
+    filter's verdict byte of every aligned record (host).  A failing call raises PolypolishError with .bad_record."""
+    return GatedBatch(ctx, raw, max_errors, careful, passed, mem)
+
+
 def shard_count(ctx, n_aln, contig_ptr, mem, n_contigs, ptrs=None):
     """pp_shard_count: alignment records per contig of a batch given by pointers."""
     p = ptrs or {}
@@ -1025,6 +1125,31 @@ class Context:
         if positions:
             res["positions"] = self.positions()
         lib().pp_polish_set_debug(self._h, 0)
+        return res
+
+    def polish_raw(self, contig_off, bases, raws, max_errors=10, careful=False, passed=None, prepare=False, min_depth=5,
+                   fraction_valid=0.5, fraction_invalid=0.2, positions=False):
+        """The record chain gate -> (prepare) -> polish: raws = the raw records of every SAM file (host numpy, RAW_FIELDS), in
+        argv order; passed = None or one entry per file (None or the filter's verdicts).  Every file is gated on the device
+        (gate_records), the gated batches -- each through pp_batch_prepare when `prepare` -- are added one after the other.
+        Returns what polish_records returns, plus "counts": (alignments, used, reads) per file."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        gated = [gate_records(self, raw, max_errors, careful, None if passed is None else passed[f]) for f, raw in enumerate(raws)]
+        batches = [prepare_batch(self, contig_off, g.n_aln, g.ptrs(), g.seq_bytes, g.n_cig_total, MEM_DEVICE) for g in gated] if prepare else gated
+        lib().pp_polish_set_debug(self._h, int(positions) if positions else 0)
+        try:
+            self.polish_begin(contig_off, bases.ctypes.data, MEM_HOST, min_depth, fraction_valid, fraction_invalid)
+            for b in batches:
+                if b.n_aln:  # (a file without a good record adds nothing)
+                    self.polish_add_ptrs(b.n_aln, b.ptrs(), b.seq_bytes, b.n_cig_total, MEM_DEVICE)
+            self.polish_finish()
+            polished, offs, stats = self.result()
+            res = {"polished": polished, "offsets": offs, "stats": stats, "positions": self.positions() if positions else None,
+                   "counts": [g.counts for g in gated]}
+        finally:
+            lib().pp_polish_set_debug(self._h, 0)
+            for b in batches + gated:
+                b.close()
         return res
 
     # ---- whole commands -----------------------------------------------------------------------

@@ -246,6 +246,18 @@ __device__ __forceinline__ int op_code(u8 c) {
     }
 }
 
+// ---- the complement of an upper-cased base: the tokenizer's k_tok_seq and the record gate's k_gate_seq fill a "*" record on the other
+// strand with it ----------------------------------------------------------------------------------------
+__device__ __forceinline__ u8 comp_upper(u8 c) {  // misc.rs:170-182 on the upper-cased base
+    switch (c) {
+    case 'A': return 'T'; case 'T': return 'A'; case 'G': return 'C'; case 'C': return 'G';
+    case 'R': return 'Y'; case 'Y': return 'R'; case 'S': return 'S'; case 'W': return 'W';
+    case 'K': return 'M'; case 'M': return 'K'; case 'B': return 'V'; case 'V': return 'B';
+    case 'D': return 'H'; case 'H': return 'D'; case 'N': return 'N'; case '.': return '.';
+    case '-': return '-'; case '?': return '?'; default: return 'N';
+    }
+}
+
 // ---- the 4-bit mirror of SEQ bytes (pp_aln_batch.seq4), packed while the bytes are in registers (the tokenizer's k_tok_seq,
 // pp_batch_prepare's k_prep_copy) ----------------------------------------------------------------------
 __device__ __forceinline__ u32 seq4_code(u32 c) {

@@ -311,16 +311,6 @@ __global__ __launch_bounds__(256) void k_tok_meta(const u8 *__restrict__ text, c
     }
 }
 
-__device__ __forceinline__ u8 comp_upper(u8 c) {  // misc.rs:170-182 on the upper-cased base
-    switch (c) {
-    case 'A': return 'T'; case 'T': return 'A'; case 'G': return 'C'; case 'C': return 'G';
-    case 'R': return 'Y'; case 'Y': return 'R'; case 'S': return 'S'; case 'W': return 'W';
-    case 'K': return 'M'; case 'M': return 'K'; case 'B': return 'V'; case 'V': return 'B';
-    case 'D': return 'H'; case 'H': return 'D'; case 'N': return 'N'; case '.': return '.';
-    case '-': return '-'; case '?': return '?'; default: return 'N';
-    }
-}
-
 // ---- SEQ bytes and their 4-bit mirror (pp_aln_batch.seq4), one pass ------------------------------------------------
 // Eight lanes per good record, one 16-byte chunk of its room (SEQ bytes up to the next PP_SEQ_ALIGN boundary) per lane and
 // trip: upper-cased (alignment.rs:94), zeros past the read, and -- the bytes being in registers anyway -- their 4-bit codes
