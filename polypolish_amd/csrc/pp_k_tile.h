@@ -117,13 +117,13 @@ __device__ __forceinline__ void tile_add(u32 *cnt, int row, int p) { atomicAdd(&
 // ---- the two-byte keys of the window, tallied by string ---------------------------------------------------------------
 // An assembly that lacks a base makes every read over that spot vote for a two-byte key there (alignment.rs:175-201: the I
 // run extends the entry before it; pileup.rs:56-63 counts it by string) -- the sites polishing is about, and all of their
-// ~200 items are ENT_POINT items.  Their keys are tallied in a small LDS hash table, (position, two bytes) -> count and
-// where the bytes stand in the seq array, so that such a position is voted right here like any other instead of being
-// listed for k_exact (a workgroup per position that scans the window's items again: 0.05 ms per job for 167 sites).
-// Whatever else lands in the position's string-keyed row -- N, longer insertions, the same key from a read that took the
-// slow class -- is not in the table: the vote notices (the table's counts do not add up to the row) and lists the position
-// as before.  Entry: tag = 1 << 31 | position << 16 | bytes; count in bits 0..23 of the second word, bits 32..39 of the
-// offset above them; the offset's low word.
+// ~200 items are ENT_POINT items.  Their keys -- and the same key from a read that took the slow class (slow_short, the
+// run-by-run walk) -- are tallied in a small LDS hash table, (position, two bytes) -> count and where the bytes stand in the
+// seq array, so that such a position is voted right here like any other instead of being listed for k_exact (a workgroup
+// per position that scans the window's items again: 0.05 ms per job for 167 sites).  Whatever else lands in the position's
+// string-keyed row -- N, longer insertions -- is not in the table: the vote notices (the table's counts do not add up to the
+// row) and lists the position as before.  Entry: tag = 1 << 31 | position << 16 | bytes; count in bits 0..23 of the second
+// word, bits 32..39 of the offset above them; the offset's low word.
 constexpr u32 PT_SLOTS = 10;  // (a window has a planted site or two; more distinct keys than slots: listed as before)
 constexpr u32 FEW_FLAGGED = 4;  // windows with at most this many positions left for the ordered replay hand them to k_exact
 __device__ __noinline__ void pt_insert(u32 *pt, u32 *over, int p, const u8 *seq, u64 so) {  // (rare: kept out of the item loop's registers)

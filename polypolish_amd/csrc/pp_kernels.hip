@@ -624,7 +624,10 @@ static RunPlan plan_run(const pp_ctx *ctx) {
     } else {
         P.xcap = ctx->xcap;
         P.xcap_limit = ctx->xcap_limit;
-        P.cap_ent = std::max<size_t>(ctx->cap_ent, (size_t)(n + n / 4 + 4096));
+        // (a record is one item, two where it reaches into the next window; a read over ONE 1-base indel -- three CIGAR runs -- is
+        // cut into three, prep_general_t: a job whose reads all lie over planted indels needs 3 n, which the runs announce)
+        const uint64_t by_runs = std::min<uint64_t>(std::max<uint64_t>(n, B.n_cig_total), 3 * n);
+        P.cap_ent = std::max<size_t>(ctx->cap_ent, (size_t)(by_runs + n / 4 + 4096));
     }
     P.coarse1_words = ((uint64_t)nwin / WIN_COARSE + 1 + 3) / 4 * 4 + 4;
     P.coarse2_words = ((uint64_t)nwin / WIN_COARSE2 + 1 + 3) / 4 * 4 + 4;
@@ -1365,9 +1368,12 @@ extern "C" int pp_polish_finish(pp_ctx *ctx) {
                 grew = true;
             } else grow(ctx->xcap, x_need, "extras per window");
         }
+        // (while the list has no room k_exact votes nothing: every listed position may come back from it as one more multi-byte
+        // winner -- the room for them grows with the list, not one pass later)
+        const bool list_full = M.counter(MC_LISTED) > ctx->cap_flag;
         grow(ctx->cap_flag, std::min<uint64_t>(M.counter(MC_LISTED), G), "listed positions");
         grow(ctx->cap_scr, M[MW_SCR_NEED], "replay scratch");
-        grow(ctx->cap_multi, M.counter(MC_MULTI), "multi-byte winners");
+        grow(ctx->cap_multi, M.counter(MC_MULTI) + (list_full ? std::min<uint64_t>(M.counter(MC_LISTED), G) : 0), "multi-byte winners");
         grow(ctx->cap_slabs, M.counter(MC_SLABS), "tally slabs");
         grow(ctx->cap_ents, M[MW_REPLAY_ITEMS], "ordered replay items");
         if (ctx->debug) grow(ctx->cap_keys, M[MW_KEYS], "key records");
