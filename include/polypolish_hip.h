@@ -11,7 +11,7 @@
  *                    (src/polish.rs:170-187)              => pp_polish_begin / _add / _finish
  *   seam A (filter): filter_sam -> alignment_pass_qc (src/filter.rs:334) and the sampling loop of
  *                    get_insert_size_thresholds (src/filter.rs:155-167)
- *                                                         => pp_filter_samples / pp_filter_pairs
+ *                                                         => pp_filter_samples / pp_filter_thresholds / pp_filter_pairs
  *
  * plus the ingest either side of them (FASTA/SAM text -> the SoA above; src/misc.rs:38-167,
  * src/alignment.rs:49-128,225-322, src/filter.rs:91-145,309-349) that the `polypolish` CLI and any
@@ -621,6 +621,50 @@ typedef struct {
     int orientation; /* 0 fr 1 rf 2 ff 3 rr */
     uint64_t orientation_counts[4];
 } pp_filter_report;
+/* After pp_filter_begin: the rest of get_insert_size_thresholds (src/filter.rs:168-186, 221-259) on the samples the pass over
+ * the reads left in device memory -- pp_filter_samples's arrays never travel.  Runs that pass if it has not run yet (as
+ * pp_filter_pairs does), then, on the device: the four orientation counts; the correct orientation -- "auto": the unique
+ * maximum, any other string is looked up in fr / rf / ff / rr (an unknown one has no sizes, as in the reference) --; the two
+ * nearest-rank percentiles (rank = max(ceil(p / 100 * n) as usize, 1), computed on the host in double) of the insert sizes of
+ * that orientation, by an exact selection over all 32 bits.  Fills orientation_counts, orientation, low_threshold,
+ * high_threshold and before_count (the two files' n_aln); after_count stays 0.  Hand low_threshold / high_threshold /
+ * orientation to pp_filter_pairs.  Errors, in the reference's order: PP_ERR_QUIT "--low must be greater than 0 and less
+ * than 50" / "--high must be greater than 50 and less than 100"; PP_ERR_PANIC where the sampling loop needs an end that cannot
+ * be parsed (as pp_filter_samples); PP_ERR_QUIT "no one-alignment-per-read pairs available to determine orientation and insert
+ * size thresholds", "could not automatically determine read pair orientation" (a tie), "no read pairs available to determine
+ * insert size thresholds".  The counts known so far are in `report` when one of the last three is returned.
+ * pp_filter_kernel_times names its kernels "thr_count" and "thr_select". */
+int pp_filter_thresholds(pp_ctx *ctx, const char *orientation, double low, double high, pp_filter_report *report);
+
+/* filter::filter (src/filter.rs:26-37) between loading and writing, over the RAW records of the two SAM files: the first link
+ * of the record chain filter -> gate -> prepare -> polish.  raw[f] is the pp_raw_batch that pp_batch_gate takes next (the caller
+ * builds its arrays once); read here: flag, read_id, contig, ref_start, cig_off, n_cig, cigar -- nm and seq* are not looked at
+ * and may be NULL.  mem = PP_MEM_HOST or PP_MEM_DEVICE (both batches).
+ *   aligned records   a record with flag & 4 takes part in nothing; the others are numbered in file order -- the numbering of
+ *                     pp_filter_file and of pass[] in pp_batch_gate / pp_ingest_sam_filtered.  pass1 / pass2: HOST arrays over
+ *                     the aligned records of file 1 / file 2 (1 = pass), exactly what pp_batch_gate takes (may be NULL for a
+ *                     file without aligned records)
+ *   reads             ALL aligned records of the two files with equal read_id are one read, adjacent or not (the reference's
+ *                     HashMap; the gate joins adjacent records only); a read's records keep file order.  Any 64-bit value is an
+ *                     id: none is reserved
+ *   contig            the RNAME as an id, compared for EQUALITY only and not range-checked.  This differs from the gate's use:
+ *                     records whose RNAME is not in the assembly must carry DISTINCT ids per name (a BAM refID, or any value
+ *                     >= n_contigs) -- not one shared "no contig" value, or two unknown references compare equal where the
+ *                     reference compares their names
+ *   CIGAR             a record with a run of op PP_OP_UNPARSEABLE has the end PP_REF_END_UNPARSEABLE: fatal (PP_ERR_PANIC) only
+ *                     when a pair comparison needs it, as in pp_filter_file.  n_cig == 0: ref_end = ref_start
+ *   counts[f]         the aligned records of file f and the distinct ids among them (may be NULL): the context never sees a
+ *                     path, so the "N alignments from M reads" line is the caller's to print
+ *   report            complete (may be NULL); after_count = the 1s of the two pass arrays
+ * PP_ERR_ARG: null arguments, PP_MEM_PEER, a null array in a non-empty batch, a CIGAR range of an aligned record outside the cigar
+ * array (found on the device before anything is read through it).  PP_ERR_LIMIT: 2^32-1 or more records in a file, or aligned
+ * records in the two files together.  PP_ERR_QUIT "no alignments found in file 1": file 1 has no aligned record (the reference
+ * names the path; the caller has it).  Everything after that comes from pp_filter_thresholds and pp_filter_pairs.  The
+ * context's stream is synchronised on return: `raw` may be released; the context's filter job is closed (pp_filter_begin
+ * starts the next).  pp_filter_kernel_times also names the grouping kernels: "rec_compact", "rec_intern", "rec_groups". */
+int pp_filter_records(pp_ctx *ctx, const pp_raw_batch raw[2], int mem, const char *orientation, double low, double high,
+                      uint8_t *pass1, uint8_t *pass2, pp_filter_file_counts counts[2], pp_filter_report *report);
+
 /* filter::filter (src/filter.rs:26-37). */
 int pp_filter_files(pp_ctx *ctx, const char *in1, const char *in2, const char *out1,
                     const char *out2, const char *orientation, double low, double high, int quiet,

@@ -194,6 +194,7 @@ EXPORTS = [
     "pp_ingest_set_seq_layout", "pp_polish_debug_tsv",
     "pp_batch_prepare", "pp_prepared_batch", "pp_prepared_kernel_ms", "pp_prepared_free",
     "pp_batch_gate", "pp_gated_batch", "pp_gated_counts", "pp_gated_kernel_ms", "pp_gated_free",
+    "pp_filter_thresholds", "pp_filter_records",
 ]
 
 _lib = None
@@ -328,6 +329,9 @@ def lib():
         L.pp_gated_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.pp_gated_free.argtypes = [vp]
         L.pp_gated_free.restype = None
+        L.pp_filter_thresholds.argtypes = [vp, C.c_char_p, C.c_double, C.c_double, C.POINTER(FilterReport)]
+        L.pp_filter_records.argtypes = [vp, C.POINTER(RawBatch), C.c_int, C.c_char_p, C.c_double, C.c_double, vp, vp,
+                                        C.POINTER(FilterFileCounts), C.POINTER(FilterReport)]
         _lib = L
     return _lib
 
@@ -796,6 +800,43 @@ def gate_records(ctx, raw: dict, max_errors=10, careful=False, passed=None, mem=
     return GatedBatch(ctx, raw, max_errors, careful, passed, mem)
 
 
+def _report_dict(rep):
+    return {"before": int(rep.before_count), "after": int(rep.after_count), "low": int(rep.low_threshold), "high": int(rep.high_threshold),
+            "orientation": ("fr", "rf", "ff", "rr")[rep.orientation] if 0 <= rep.orientation < 4 else None,
+            "counts": [int(c) for c in rep.orientation_counts]}
+
+
+# the arrays of pp_raw_batch the filter reads (nm and seq* are not looked at and may be missing)
+FILTER_RAW_FIELDS = tuple((k, dt) for k, dt in RAW_FIELDS if k in ("flag", "read_id", "contig", "ref_start", "cig_off", "n_cig", "cigar"))
+
+
+def filter_records(ctx, raw1, raw2, orientation="auto", low=0.1, high=99.9, mem=MEM_HOST):
+    """pp_filter_records: the whole filter over the raw records of the two SAM files -- the dicts gate_records takes next
+    (MEM_HOST: numpy arrays by the field names of pp_raw_batch; MEM_DEVICE: their device addresses plus "n_rec", "seq_bytes",
+    "n_cig_total").  contig is the RNAME as an id, compared for equality only: names that are not in the assembly need distinct
+    ids.  Returns {"pass": (p1, p2), "counts": [(alignments, reads)] * 2, "report": dict}; p1 / p2 (uint8, one per aligned
+    record) are gate_records' `passed`."""
+    L = lib()
+    batches, keep, n_rec = (RawBatch * 2)(), [], []
+    for f, raw in enumerate((raw1, raw2)):
+        if mem != MEM_DEVICE:
+            arrs = {k: np.ascontiguousarray(raw[k], dtype=dt) for k, dt in FILTER_RAW_FIELDS}
+            keep.append(arrs)
+            n, n_cig_total = len(arrs["flag"]), len(arrs["cigar"])
+            ptrs = {k: v.ctypes.data for k, v in arrs.items()}
+        else:
+            ptrs, n, n_cig_total = raw, int(raw["n_rec"]), int(raw["n_cig_total"])
+        batches[f] = RawBatch(n, ptrs["flag"], ptrs["read_id"], ptrs["contig"], ptrs["ref_start"], ptrs.get("nm"), ptrs.get("seq_off"),
+                              ptrs.get("seq_len"), ptrs["cig_off"], ptrs["n_cig"], ptrs.get("seq"), int(raw["seq_bytes"]) if mem == MEM_DEVICE else 0,
+                              ptrs["cigar"], n_cig_total)
+        n_rec.append(n)
+    passed = [np.zeros(n, dtype=np.uint8) for n in n_rec]  # (room for every record: the aligned ones are a prefix of it)
+    cnt, rep = (FilterFileCounts * 2)(), FilterReport()
+    ctx._chk(L.pp_filter_records(ctx._h, batches, mem, orientation.encode(), low, high, passed[0].ctypes.data, passed[1].ctypes.data, cnt, C.byref(rep)))
+    return {"pass": tuple(p[:int(c.alignments)].copy() for p, c in zip(passed, cnt)),
+            "counts": [(int(c.alignments), int(c.reads)) for c in cnt], "report": _report_dict(rep)}
+
+
 def shard_count(ctx, n_aln, contig_ptr, mem, n_contigs, ptrs=None):
     """pp_shard_count: alignment records per contig of a batch given by pointers."""
     p = ptrs or {}
@@ -1151,6 +1192,13 @@ class Context:
             for b in batches + gated:
                 b.close()
         return res
+
+    def filter_thresholds(self, orientation="auto", low=0.1, high=99.9):
+        """pp_filter_thresholds after pp_filter_begin: orientation counts, the correct orientation and the two insert size
+        thresholds from the samples in device memory -> {"counts", "orientation", "low", "high", "before", "after": 0}."""
+        rep = FilterReport()
+        self._chk(lib().pp_filter_thresholds(self._h, orientation.encode(), low, high, C.byref(rep)))
+        return _report_dict(rep)
 
     # ---- whole commands -----------------------------------------------------------------------
     def polish_files(self, assembly, sams, fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5,

@@ -4,6 +4,7 @@
 // read, structure-of-arrays loads; HBM-bound.  Since round 5 ONE pass over the reads (k_filter_reads) and a pass over
 // the few reads whose verdicts need the thresholds (k_filter_listed).
 #include "pp_internal.h"
+#include "pp_host.h"
 
 #include <cstring>
 
@@ -180,6 +181,120 @@ __global__ __launch_bounds__(FILTER_RPB) void k_filter_listed(const u32 *__restr
     }
 }
 
+// ---- the reduction of the samples (pp_filter_thresholds): the rest of get_insert_size_thresholds, filter.rs:168-186 ----------
+// The four orientation counts, then an exact selection of TWO ranks at once among insert[r] with orient[r] == correct: a radix
+// select over the 32 bits of an insert size (the reference's usize difference `as u32`: any value occurs) in three digits of
+// 11, 11 and 10 bits from the top.  Per digit one pass over the samples (5 bytes a read) into an LDS histogram per workgroup
+// and rank, the nonzero bins added to the global one, and one workgroup that finds the bin each rank falls into, extends that
+// rank's prefix by the bin and takes the bins below off the rank -- no host in between.  While both ranks share their prefix
+// (always in the first pass, and until the last for the insert sizes of one library) ONE histogram serves both.
+// The device words (u32): the counts | prefix of either rank | what is left of either rank | two histograms.
+constexpr u32 THR_BINS = 2048;
+constexpr u32 THR_COUNTS = 0, THR_PREFIX = 4, THR_RANK = 6, THR_HIST = 8, THR_WORDS = THR_HIST + 2 * THR_BINS;
+constexpr u32 THR_DIGITS = 3;
+constexpr u32 THR_RPT = 16;  // reads per lane of the counting kernel
+static const u32 THR_SHIFT[THR_DIGITS] = {21, 10, 0}, THR_DIGIT_BITS[THR_DIGITS] = {11, 11, 10};
+
+// per-wave ballots, one LDS add per wave and orientation, one global add per workgroup and orientation
+__global__ __launch_bounds__(256) void k_thr_count(u32 n_reads, const u8 *__restrict__ orient, u32 *__restrict__ counts) {
+    __shared__ u32 s_c[4];
+    if (threadIdx.x < 4) s_c[threadIdx.x] = 0;
+    __syncthreads();
+    u32 c[4] = {0, 0, 0, 0};  // (wave-uniform)
+    const u64 base = (u64)blockIdx.x * (256u * THR_RPT) + threadIdx.x;
+#pragma unroll 4
+    for (u32 u = 0; u < THR_RPT; u++) {
+        const u64 r = base + (u64)u * 256u;
+        const u32 o = r < n_reads ? (u32)orient[r] : 255u;
+#pragma unroll
+        for (u32 k = 0; k < 4; k++) c[k] += (u32)__popcll(__ballot(o == k));
+    }
+    if ((threadIdx.x & 63u) == 0) {
+#pragma unroll
+        for (u32 k = 0; k < 4; k++)
+            if (c[k]) atomicAdd(&s_c[k], c[k]);
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 && s_c[threadIdx.x]) atomicAdd(&counts[threadIdx.x], s_c[threadIdx.x]);
+}
+
+// One digit of the wave's values into an LDS histogram.  The insert sizes of a library sit in a few hundred values: in the upper
+// digits every lane of the wave has the same bin, and 64 LDS atomics on one address are 64 turns.  Up to four distinct digits
+// of the wave go in as ONE add each (the lanes that share the leader's digit, counted with a ballot), the rest lane by lane.
+__device__ __forceinline__ void thr_hist_add(u32 *h, u32 d, bool on) {
+    const u32 lane = threadIdx.x & 63u;
+    u64 live = __ballot(on);
+    for (u32 t = 0; t < 4u && live; t++) {
+        const u32 lead = (u32)__ffsll((long long)live) - 1u;
+        const u32 dl = (u32)__shfl((int)d, (int)lead, 64);
+        const u64 m = __ballot(on && d == dl) & live;
+        if (lane == lead) atomicAdd(&h[dl], (u32)__popcll(m));
+        live &= ~m;
+    }
+    if ((live >> lane) & 1ull) atomicAdd(&h[d], 1u);
+}
+
+// digit [shift, shift + bits) of the sizes whose bits above it are a rank's prefix
+__global__ __launch_bounds__(256) void k_thr_hist(u32 n_reads, const u8 *__restrict__ orient, const u32 *__restrict__ insert, u32 correct,
+                                                  u32 shift, u32 bits, u32 *__restrict__ w) {
+    __shared__ u32 s_h[2 * THR_BINS];
+    for (u32 i = threadIdx.x; i < 2 * THR_BINS; i += 256u) s_h[i] = 0;
+    __syncthreads();
+    const u32 p0 = w[THR_PREFIX], p1 = w[THR_PREFIX + 1], mask = (1u << bits) - 1u, above = shift + bits;  // (above <= 32)
+    const bool two = p0 != p1;
+    for (u64 b = (u64)blockIdx.x * 256u; b < n_reads; b += (u64)gridDim.x * 256u) {  // (wave-uniform trips: ballots inside)
+        const u64 r = b + threadIdx.x;
+        const bool on = r < n_reads && (u32)orient[r] == correct;
+        const u32 v = on ? insert[r] : 0u;
+        const u32 hp = (u32)((u64)v >> above), d = (v >> shift) & mask;
+        thr_hist_add(s_h, d, on && hp == p0);
+        if (two) thr_hist_add(s_h + THR_BINS, d, on && hp == p1);
+    }
+    __syncthreads();
+    for (u32 i = threadIdx.x; i < 2 * THR_BINS; i += 256u) {
+        const u32 v = s_h[i];
+        if (v) atomicAdd(&w[THR_HIST + i], v);
+    }
+}
+
+// ONE workgroup: the bin either rank (1-based, among the sizes under its prefix) falls into; the histograms are zero again afterwards.
+// first: the ranks come from the host (r0, r1), the prefixes are empty.
+__global__ __launch_bounds__(1024) void k_thr_pick(u32 *__restrict__ w, u32 bits, u32 r0, u32 r1, int first) {
+    __shared__ u32 s_w[16];
+    const u32 t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    const u32 p[2] = {w[THR_PREFIX], w[THR_PREFIX + 1]};
+    const u32 rank[2] = {first ? r0 : w[THR_RANK], first ? r1 : w[THR_RANK + 1]};
+    const bool two = p[0] != p[1];
+    u32 bin[2] = {0, 0}, left[2] = {0, 0};
+    bool hit[2] = {false, false};
+#pragma unroll
+    for (u32 k = 0; k < 2; k++) {
+        const u32 *h = w + THR_HIST + ((k == 1 && two) ? THR_BINS : 0u);
+        const u32 a = h[2 * t], b = h[2 * t + 1], s = a + b;  // (all the sizes together are fewer than 2^32)
+        u32 inc = s;
+        for (int o = 1; o < 64; o <<= 1) {
+            const u32 x = (u32)__shfl_up((int)inc, o, 64);
+            if ((int)lane >= o) inc += x;
+        }
+        if (lane == 63u) s_w[wave] = inc;
+        __syncthreads();
+        u32 ex = inc - s;
+        for (u32 i = 0; i < wave; i++) ex += s_w[i];
+        __syncthreads();
+        if (ex < rank[k] && rank[k] - ex <= a) { hit[k] = true; bin[k] = 2 * t; left[k] = rank[k] - ex; }
+        else if (ex + a < rank[k] && rank[k] - ex - a <= b) { hit[k] = true; bin[k] = 2 * t + 1; left[k] = rank[k] - ex - a; }
+    }
+    __syncthreads();  // (every thread has read the state and the histograms)
+#pragma unroll
+    for (u32 k = 0; k < 2; k++)
+        if (hit[k]) {
+            w[THR_PREFIX + k] = (p[k] << bits) | bin[k];
+            w[THR_RANK + k] = left[k];
+        }
+#pragma unroll
+    for (u32 i = 0; i < 2 * THR_BINS / 1024u; i++) w[THR_HIST + i * 1024u + t] = 0;
+}
+
 }  // namespace pp
 
 using namespace pp;
@@ -213,6 +328,7 @@ extern "C" int pp_filter_begin(pp_ctx *ctx, const pp_filter_input *in, int mem) 
     timers_release(ctx);
     ctx->fdev = *in;
     ctx->filter_reads_done = false;
+    ctx->filter_times_partial = false;
     ctx->filter_n_listed = -1;
     for (int f = 0; f < 2; f++) {
         const pp_filter_file &s = in->file[f];
@@ -311,6 +427,91 @@ extern "C" int pp_filter_samples(pp_ctx *ctx, uint8_t *orient, uint32_t *insert)
     return check_poisoned(ctx);
 }
 
+// what pp_filter_thresholds collected stays in last_times; pp_filter_pairs of the same job adds its own to it
+static void times_merge(pp_kernel_times &into, const pp_kernel_times &add) {
+    for (int i = 0; i < add.n; i++) {
+        int k;
+        for (k = 0; k < into.n; k++)
+            if (into.name[k] == add.name[i]) break;
+        if (k == into.n) {
+            if (into.n == PP_MAX_KERNELS) continue;
+            into.name[k] = add.name[i];
+            into.ms[k] = 0.f;
+            into.n++;
+        }
+        into.ms[k] += add.ms[i];
+    }
+}
+
+extern "C" int pp_filter_thresholds(pp_ctx *ctx, const char *orientation, double low, double high, pp_filter_report *report) {
+    if (!ctx) return PP_ERR_ARG;
+    if (!orientation || !report) return ctx->fail(PP_ERR_ARG, "pp_filter_thresholds: null argument");
+    if (!ctx->filter_open) return ctx->fail(PP_ERR_ARG, "pp_filter_thresholds without pp_filter_begin");
+    if (const char *msg = pph::percentile_options_error(low, high)) return ctx->fail(PP_ERR_QUIT, "%s", msg);
+    memset(report, 0, sizeof *report);
+    report->orientation = -1;
+    report->before_count = ctx->fdev.file[0].n_aln + ctx->fdev.file[1].n_aln;
+    PP_HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!ctx->filter_reads_done)
+        if (int rc = filter_reads(ctx)) return rc;
+    if (int rc = dev_ensure(ctx, ctx->f_thr, (size_t)THR_WORDS * 4)) return rc;
+    u32 *const w = (u32 *)ctx->f_thr.p;
+    const u32 n = ctx->fdev.n_reads;
+    PP_HIPCHK(ctx, hipMemsetAsync(w, 0, (size_t)THR_WORDS * 4, ctx->stream));
+    if (n) {
+        timer_begin(ctx, "thr_count");
+        hipLaunchKernelGGL(k_thr_count, dim3((unsigned)(((u64)n + 256u * THR_RPT - 1u) / (256u * THR_RPT))), dim3(256), 0, ctx->stream, n,
+                           (const u8 *)ctx->f_orient.p, w + THR_COUNTS);
+        timer_end(ctx);
+        PP_HIPCHK(ctx, hipGetLastError());
+    }
+    u32 counts[4] = {0, 0, 0, 0};
+    PP_HIPCHK(ctx, hipMemcpyAsync(counts, w + THR_COUNTS, sizeof counts, hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = check_poisoned(ctx)) return rc;  // (the first of the two synchronisations: the counts are here too)
+    for (int o = 0; o < 4; o++) report->orientation_counts[o] = counts[o];
+    if ((u64)counts[0] + counts[1] + counts[2] + counts[3] == 0)
+        return ctx->fail(PP_ERR_QUIT, "no one-alignment-per-read pairs available to determine orientation and insert size thresholds");
+    static const char *ONAMES[4] = {"fr", "rf", "ff", "rr"};
+    int correct = -1;
+    if (strcmp(orientation, "auto") == 0) {  // auto_determine_orientation, filter.rs:238-246
+        u32 mx = 0;
+        int n_max = 0;
+        for (int o = 0; o < 4; o++) mx = counts[o] > mx ? counts[o] : mx;
+        for (int o = 0; o < 4; o++)
+            if (counts[o] == mx) { n_max++; correct = o; }
+        if (n_max != 1) return ctx->fail(PP_ERR_QUIT, "could not automatically determine read pair orientation");
+    } else {
+        for (int o = 0; o < 4; o++)
+            if (strcmp(orientation, ONAMES[o]) == 0) correct = o;
+    }
+    report->orientation = correct;
+    const u64 n_sizes = correct >= 0 ? counts[correct] : 0;
+    if (n_sizes == 0) return ctx->fail(PP_ERR_QUIT, "no read pairs available to determine insert size thresholds");
+    // get_percentile, filter.rs:249-259: element rank - 1 of the sorted sizes, 0 for a rank past them
+    const size_t rank[2] = {pph::percentile_rank(low, n_sizes), pph::percentile_rank(high, n_sizes)};
+    const bool past[2] = {rank[0] - 1 >= n_sizes, rank[1] - 1 >= n_sizes};
+    timer_begin(ctx, "thr_select");
+    const unsigned grid = (unsigned)std::min<u64>(((u64)n + 255u) / 256u, 1024u);
+    for (u32 d = 0; d < THR_DIGITS; d++) {
+        hipLaunchKernelGGL(k_thr_hist, dim3(grid), dim3(256), 0, ctx->stream, n, (const u8 *)ctx->f_orient.p, (const u32 *)ctx->f_insert.p,
+                           (u32)correct, THR_SHIFT[d], THR_DIGIT_BITS[d], w);
+        hipLaunchKernelGGL(k_thr_pick, dim3(1), dim3(1024), 0, ctx->stream, w, THR_DIGIT_BITS[d], past[0] ? 1u : (u32)rank[0],
+                           past[1] ? 1u : (u32)rank[1], d == 0 ? 1 : 0);
+    }
+    timer_end(ctx);
+    PP_HIPCHK(ctx, hipGetLastError());
+    u32 thr[2] = {0, 0};
+    PP_HIPCHK(ctx, hipMemcpyAsync(thr, w + THR_PREFIX, sizeof thr, hipMemcpyDeviceToHost, ctx->stream));
+    PP_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (the second)
+    report->low_threshold = past[0] ? 0u : thr[0];
+    report->high_threshold = past[1] ? 0u : thr[1];
+    if (ctx->profiling) {
+        timers_collect(ctx, &ctx->last_times);
+        ctx->filter_times_partial = true;
+    }
+    return PP_OK;
+}
+
 extern "C" int pp_filter_pairs(pp_ctx *ctx, uint32_t low, uint32_t high, uint8_t orientation,
                                uint8_t *pass1, uint8_t *pass2) {
     if (!ctx) return PP_ERR_ARG;
@@ -333,7 +534,16 @@ extern "C" int pp_filter_pairs(pp_ctx *ctx, uint32_t low, uint32_t high, uint8_t
         if (n) PP_HIPCHK(ctx, hipMemcpyAsync(outs[f], ctx->f_pass[f].p, n, hipMemcpyDeviceToHost, ctx->stream));
     }
     if (int rcp = check_poisoned(ctx)) return rcp;
-    if (ctx->profiling) timers_collect(ctx, &ctx->last_times);
+    if (ctx->profiling) {
+        if (ctx->filter_times_partial) {  // (pp_filter_thresholds of this job has collected its own and the pass over the reads)
+            pp_kernel_times mine{};
+            timers_collect(ctx, &mine);
+            times_merge(ctx->last_times, mine);
+            ctx->filter_times_partial = false;
+        } else {
+            timers_collect(ctx, &ctx->last_times);
+        }
+    }
     return PP_OK;
 }
 

@@ -9,6 +9,7 @@
 // equality matters).  As in pp_tokenize.hip the device only finds the first failing line; the message comes
 // from the host parser run on that line.
 #include "pp_devtext.h"
+#include "pp_filter_group.h"
 #include "pp_host.h"
 
 #include <chrono>
@@ -152,44 +153,6 @@ __global__ __launch_bounds__(256) void k_ht_find(u64 n, const NameRef *__restric
             return;
         }
         i = (i + 1) & mask;
-    }
-}
-
-// names of file 2 that file 1 holds as well (for the "alignments from N reads" line of file 2)
-__global__ __launch_bounds__(256) void k_mark_shared(u64 n0, u64 n, const u32 *__restrict__ rep, u32 *__restrict__ hit) {
-    const u64 i = n0 + (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && rep[i] < n0) hit[rep[i]] = 1;
-}
-
-__global__ __launch_bounds__(256) void k_assign(u32 n_aln, u64 base, const u32 *__restrict__ rep, const u32 *__restrict__ id_scan,
-                                                const u32 *__restrict__ rep_ref, u32 *__restrict__ read,
-                                                u32 *__restrict__ ref_id, u32 *__restrict__ grp_cnt) {
-    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_aln) return;
-    const u32 id = id_scan[rep[base + r]];
-    read[r] = id;
-    ref_id[r] = rep_ref[base + r];
-    atomicAdd(&grp_cnt[id], 1u);
-}
-
-__global__ __launch_bounds__(256) void k_grp_scatter(u32 n_aln, const u32 *__restrict__ read, const u32 *__restrict__ grp_off,
-                                                     u32 *__restrict__ cursor, u32 *__restrict__ grp_idx) {
-    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_aln) return;
-    const u32 id = read[r];
-    grp_idx[grp_off[id] + atomicAdd(&cursor[id], 1u)] = r;
-}
-
-// file order inside every group (the scatter's order is whatever the atomics made it)
-__global__ __launch_bounds__(256) void k_grp_sort(u32 n_reads, const u32 *__restrict__ grp_off, u32 *__restrict__ grp_idx) {
-    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_reads) return;
-    const u32 lo = grp_off[r], hi = grp_off[r + 1];
-    for (u32 i = lo + 1; i < hi; i++) {
-        const u32 v = grp_idx[i];
-        u32 j = i;
-        while (j > lo && grp_idx[j - 1] > v) { grp_idx[j] = grp_idx[j - 1]; j--; }
-        grp_idx[j] = v;
     }
 }
 
@@ -407,19 +370,10 @@ extern "C" int pp_filter_load_device(pp_ctx *ctx, const char *in1, const char *i
     ENS(D->cursor, std::max<u64>(1, (u64)n_reads) * 4);
     for (int f = 0; f < 2; f++) {
         DevFile &X = D->F[f];
-        const u32 n = X.n_aln;
         ENS(X.grp_off, ((u64)n_reads + 1) * 4);
-        PP_HIPCHK(ctx, hipMemsetAsync(D->cursor.p, 0, std::max<u64>(1, (u64)n_reads) * 4, st));
-        if (n)
-            hipLaunchKernelGGL(k_assign, dim3((n + 255) / 256), dim3(256), 0, st, n, f == 0 ? 0ull : n0, (const u32 *)D->rep.p,
-                               (const u32 *)D->id_scan.p, (const u32 *)D->rep_ref.p, (u32 *)X.read.p, (u32 *)X.ref_id.p, (u32 *)D->cursor.p);
-        if ((rc = scan_u32<u32>(ctx, D->d_sums, D->d_sumsoff, (const u32 *)D->cursor.p, (u64)n_reads, (u32 *)X.grp_off.p))) return rc;
-        PP_HIPCHK(ctx, hipMemsetAsync(D->cursor.p, 0, std::max<u64>(1, (u64)n_reads) * 4, st));
-        if (n) {
-            hipLaunchKernelGGL(k_grp_scatter, dim3((n + 255) / 256), dim3(256), 0, st, n, (const u32 *)X.read.p, (const u32 *)X.grp_off.p,
-                               (u32 *)D->cursor.p, (u32 *)X.grp_idx.p);
-            hipLaunchKernelGGL(k_grp_sort, dim3((n_reads + 255) / 256), dim3(256), 0, st, n_reads, (const u32 *)X.grp_off.p, (u32 *)X.grp_idx.p);
-        }
+        if ((rc = file_groups(ctx, X.n_aln, f == 0 ? 0ull : n0, n_reads, (const u32 *)D->rep.p, (const u32 *)D->id_scan.p, (const u32 *)D->rep_ref.p,
+                              (u32 *)X.read.p, (u32 *)X.ref_id.p, (u32 *)D->cursor.p, (u32 *)X.grp_off.p, (u32 *)X.grp_idx.p, D->d_sums, D->d_sumsoff)))
+            return rc;
     }
     PP_HIPCHK(ctx, hipStreamSynchronize(st));
     PP_HIPCHK(ctx, hipGetLastError());

@@ -272,10 +272,7 @@ struct NameTable {
 // get_percentile, filter.rs:249-259 (on unsorted data: only one order statistic is needed)
 uint32_t percentile(std::vector<uint32_t> &v, double p) {
     if (v.empty()) return 0;
-    const double fraction = p / 100.0;
-    const double r = ceil(fraction * (double)v.size());
-    size_t rank = r <= 0.0 ? 0 : (r >= 1.8e19 ? SIZE_MAX : (size_t)r);
-    if (rank < 1) rank = 1;
+    const size_t rank = pph::percentile_rank(p, v.size());
     if (rank - 1 >= v.size()) return 0;
     std::nth_element(v.begin(), v.begin() + (rank - 1), v.end());
     return v[rank - 1];
@@ -887,9 +884,7 @@ int filter_core(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char *in
         }
     }
     auto order_stat = [&](double p) -> uint32_t {  // = percentile() above on the gathered values
-        const double r = ceil(p / 100.0 * (double)n_sizes);
-        size_t rank = r <= 0.0 ? 0 : (r >= 1.8e19 ? SIZE_MAX : (size_t)r);
-        if (rank < 1) rank = 1;
+        const size_t rank = pph::percentile_rank(p, n_sizes);
         if (rank - 1 >= n_sizes) return 0;
         uint64_t seen = 0;
         for (uint32_t i = 0; i < HBINS; i++) {
@@ -954,8 +949,7 @@ int check_filter_options(pp_ctx *ctx, const char *const *names, int n_names, dou
         for (int j = i + 1; j < n_names; j++)
             if (strcmp(names[i], names[j]) == 0)
                 return pp_ctx_set_error_(ctx, PP_ERR_QUIT, "--in1, --in2, --out1 and --out2 must all have unique values");
-    if (low <= 0.0 || low >= 50.0) return pp_ctx_set_error_(ctx, PP_ERR_QUIT, "--low must be greater than 0 and less than 50");
-    if (high <= 50.0 || high >= 100.0) return pp_ctx_set_error_(ctx, PP_ERR_QUIT, "--high must be greater than 50 and less than 100");
+    if (const char *msg = pph::percentile_options_error(low, high)) return pp_ctx_set_error_(ctx, PP_ERR_QUIT, msg);
     return PP_OK;
 }
 

@@ -405,4 +405,20 @@ inline std::string percentile_name(double p) {
     return s + suffix + " percentile";
 }
 
+// The rank of get_percentile (filter.rs:249-259) among n values, 1-based: max(ceil(p / 100 * n) as usize, 1), in double as the
+// reference computes it (`as usize` saturates).  The value is element rank - 1 of the sorted values, or 0 when rank - 1 >= n.
+// One definition for the host reduction of the file drivers (pp_filter_host.cpp) and the device selection (pp_filter_thresholds).
+inline size_t percentile_rank(double p, uint64_t n) {
+    const double r = ceil(p / 100.0 * (double)n);
+    const size_t rank = r <= 0.0 ? 0 : (r >= 1.8e19 ? SIZE_MAX : (size_t)r);
+    return rank < 1 ? 1 : rank;
+}
+
+// the range checks of --low / --high (check_inputs, filter.rs:47-52): the message, or nullptr
+inline const char *percentile_options_error(double low, double high) {
+    if (low <= 0.0 || low >= 50.0) return "--low must be greater than 0 and less than 50";
+    if (high <= 50.0 || high >= 100.0) return "--high must be greater than 50 and less than 100";
+    return nullptr;
+}
+
 }  // namespace pph

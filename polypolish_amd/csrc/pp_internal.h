@@ -264,10 +264,13 @@ struct pp_ctx {
 
     // ---- filter job ----
     pp::DevBuf f_in[2][9], f_refend[2], f_pass[2], f_orient, f_insert, f_poisoned, f_list, f_blkcnt;
+    pp::DevBuf f_rec[48];  // pp_filter_records: the call's arrays and scratch, in the order it asks for them (pp_filter_rec.hip)
+    pp::DevBuf f_thr;  // pp_filter_thresholds: orientation counts | the selection's state | its two histograms (THR_WORDS u32)
     pp_filter_input fdev{};
     const uint64_t *f_refend_ptr[2] = {nullptr, nullptr};
     bool filter_open = false;
     bool filter_reads_done = false;  // the pass over the reads (k_filter_reads) of the open filter job has run
+    bool filter_times_partial = false;  // last_times holds what pp_filter_thresholds collected of the open job: pp_filter_pairs adds to it
     int64_t filter_n_listed = -1;    // whether it listed any read for k_filter_listed, once read back (-1: not known on the host)
 
     int fail(int code, const char *fmt, ...) {

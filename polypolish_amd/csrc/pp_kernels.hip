@@ -1753,11 +1753,12 @@ extern "C" void pp_ctx_destroy(pp_ctx *ctx) {
                      &ctx->b_dfmt_idx, &ctx->b_dfmt_rec, &ctx->b_dfmt_names, &ctx->b_dfmt_noff, &ctx->b_dfmt_emit, &ctx->b_dfmt_len,
                      &ctx->b_dfmt_bsum, &ctx->b_dfmt_boff, &ctx->b_dfmt_res, &ctx->b_dfmt_stage,
                      &ctx->f_refend[0], &ctx->f_refend[1], &ctx->f_pass[0], &ctx->f_pass[1], &ctx->f_orient, &ctx->f_poisoned,
-                     &ctx->f_insert, &ctx->f_list, &ctx->f_blkcnt};
+                     &ctx->f_insert, &ctx->f_list, &ctx->f_blkcnt, &ctx->f_thr};
     for (DevBuf *b : all) dev_free(*b);
     for (auto &b : ctx->b_in) dev_free(b);
     for (auto &b : ctx->b_split) dev_free(b);
     for (auto &f : ctx->f_in) for (auto &b : f) dev_free(b);
+    for (auto &b : ctx->f_rec) dev_free(b);
     timers_release(ctx);
     if (ctx->h_meta) (void)hipHostFree(ctx->h_meta);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
