@@ -276,6 +276,41 @@ void pp_gated_counts(const pp_gated *g, pp_sam_counts *out); /* as add_to_pileup
 int pp_gated_kernel_ms(const pp_gated *g, float *ms);
 void pp_gated_free(pp_gated *g);
 
+/* The step in front of the record chain for a caller who holds NAMES: pp_raw_batch.read_id is the QNAME and .contig the RNAME as
+ * a number, equal names <=> equal ids, exactly (a hash value is no id: two names that collide would be one read).  A pp_names is
+ * a set of byte strings with dense ids that lives on the device (the reference's HashMap<String, ..>), so that no host hash map
+ * is needed: one table seeded with the assembly's contig names gives `contig`, one table shared by both SAM files `read_id`.
+ *   pp_names_ids   name i = the len[i] bytes at bytes + off[i], compared as BYTES: NUL and bytes >= 0x80 are ordinary, a name of
+ *                  len 0 is a name like any other; ranges may overlap or repeat.  mem = PP_MEM_HOST or PP_MEM_DEVICE holds for
+ *                  bytes, off, len, id64 and id32; id64 or id32 may be NULL (not both), they carry the same values.
+ *   ids            dense and deterministic: a name's id = the number of distinct names in front of its first occurrence, over all
+ *                  calls on the object in call order and, inside a call, in index order.  So a first call with the contig names
+ *                  in FASTA order gives 0..n_contigs-1, and every RNAME met later that is not among them a DISTINCT id >=
+ *                  n_contigs (what pp_filter_records asks of such records); a name that comes twice in a call has the id of its
+ *                  first occurrence; file 2's QNAMEs get file 1's ids.  The ids depend neither on `expect`, nor on `mem`, nor
+ *                  on how the names are cut into calls, nor on how often the table grew.
+ *   ownership      the table keeps a copy of every distinct name's bytes; the context's stream has been synchronised when the
+ *                  call returns: the caller's arrays may be released or overwritten.
+ *   memory safety  a name's range is tested on the device before anything is read through it (without a sum that could wrap),
+ *                  and no byte outside [0, n_bytes) is ever loaded, by a wide load either: a PP_MEM_DEVICE array may end where
+ *                  its allocation ends.
+ * PP_ERR_ARG: null arguments, PP_MEM_PEER, a null array with n > 0, a name (len > 0) whose [off, off + len) does not lie inside
+ * [0, n_bytes): *bad (may be NULL) = the first such index, and the table is unchanged.  PP_ERR_LIMIT: 2^32-1 or more distinct
+ * names (the table keeps the names of the call that came before that one), n >= 2^32-1 in one call.  n == 0 succeeds and changes
+ * nothing.  `expect` sizes the first table (distinct names to come; a guess, 0 is fine): the table doubles when a call's names
+ * that are not yet in it, each counted as new, would take it past half its slots.
+ * pp_names_name copies a name to HOST memory (for messages): *len = its length; PP_ERR_ARG for an id the table does not have
+ * and for cap < *len (*len is set then, too).  pp_names_kernel_ms: HIP-event time of the kernels of the last pp_names_ids (not the
+ * upload of host arrays); PP_ERR_ARG unless the context had profiling on.  A table belongs to its context and is freed before it. */
+typedef struct pp_names pp_names;
+int pp_names_create(pp_ctx *ctx, uint64_t expect, pp_names **out);
+int pp_names_ids(pp_names *t, const uint8_t *bytes, uint64_t n_bytes, const uint64_t *off, const uint32_t *len, uint64_t n, int mem,
+                 uint64_t *id64, uint32_t *id32, uint64_t *bad);
+uint64_t pp_names_count(const pp_names *t); /* distinct names held */
+int pp_names_name(const pp_names *t, uint64_t id, uint8_t *out, uint32_t cap, uint32_t *len);
+int pp_names_kernel_ms(const pp_names *t, float *ms);
+void pp_names_free(pp_names *t);
+
 /* Per-contig figures the reference prints to stderr (src/polish.rs:206-227). */
 typedef struct {
     uint64_t polished_len;     /* bytes of the polished sequence                      */

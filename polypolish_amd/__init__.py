@@ -195,6 +195,7 @@ EXPORTS = [
     "pp_batch_prepare", "pp_prepared_batch", "pp_prepared_kernel_ms", "pp_prepared_free",
     "pp_batch_gate", "pp_gated_batch", "pp_gated_counts", "pp_gated_kernel_ms", "pp_gated_free",
     "pp_filter_thresholds", "pp_filter_records",
+    "pp_names_create", "pp_names_ids", "pp_names_count", "pp_names_name", "pp_names_kernel_ms", "pp_names_free",
 ]
 
 _lib = None
@@ -332,6 +333,14 @@ def lib():
         L.pp_filter_thresholds.argtypes = [vp, C.c_char_p, C.c_double, C.c_double, C.POINTER(FilterReport)]
         L.pp_filter_records.argtypes = [vp, C.POINTER(RawBatch), C.c_int, C.c_char_p, C.c_double, C.c_double, vp, vp,
                                         C.POINTER(FilterFileCounts), C.POINTER(FilterReport)]
+        L.pp_names_create.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
+        L.pp_names_ids.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_int, vp, vp, u64p]
+        L.pp_names_count.argtypes = [vp]
+        L.pp_names_count.restype = C.c_uint64
+        L.pp_names_name.argtypes = [vp, C.c_uint64, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.pp_names_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.pp_names_free.argtypes = [vp]
+        L.pp_names_free.restype = None
         _lib = L
     return _lib
 
@@ -798,6 +807,83 @@ def gate_records(ctx, raw: dict, max_errors=10, careful=False, passed=None, mem=
     (RAW_FIELDS); MEM_DEVICE: raw = their device addresses plus "n_rec", "seq_bytes", "n_cig_total".  passed: None or the
     filter's verdict byte of every aligned record (host).  A failing call raises PolypolishError with .bad_record."""
     return GatedBatch(ctx, raw, max_errors, careful, passed, mem)
+
+
+def pack_names(names):
+    """a list of bytes / str -> (bytes, off, len): the names back to back, as pp_names_ids takes them"""
+    raw = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+    ln = np.array([len(r) for r in raw], dtype=np.uint32)
+    off = (np.cumsum(ln, dtype=np.uint64) - ln).astype(np.uint64)
+    return np.frombuffer(b"".join(raw), dtype=np.uint8), off, ln
+
+
+class Names:
+    """pp_names: a set of byte strings with dense ids on the device -- QNAME -> pp_raw_batch.read_id, RNAME -> .contig.
+      .ids(names)   names = a list of bytes / str, or (bytes, off, len): numpy arrays (mem = MEM_HOST) or device addresses
+                    (MEM_DEVICE, with n = names, n_bytes = bytes of the array, out = device address of n uint64).  Returns the
+                    ids as a np.uint64 array: the number of distinct names in front of a name's first occurrence, over all calls.
+                    A name whose range lies outside the array raises PolypolishError with .bad = its index.
+      .count        distinct names held
+      .name(id)     the bytes of a name
+      .kernel_ms()  HIP-event time of the last ids() (the context had set_profiling on)"""
+
+    def __init__(self, ctx, expect=0):
+        self._p = C.c_void_p()
+        self._ctx = ctx
+        ctx._chk(lib().pp_names_create(ctx._h, int(expect), C.byref(self._p)))
+
+    def ids(self, names, mem=MEM_HOST, n=None, n_bytes=None, out=None):
+        L = lib()
+        if isinstance(names, tuple) and len(names) == 3 and mem != MEM_HOST:
+            bp, op, lp = names
+            n, n_bytes = int(n), int(n_bytes)
+            res, dst = np.zeros(n, dtype=np.uint64), out
+        else:
+            if not (isinstance(names, tuple) and len(names) == 3 and all(isinstance(a, np.ndarray) for a in names)):
+                names = pack_names(names)
+            b, o, ln = (np.ascontiguousarray(a, dtype=dt) for a, dt in zip(names, (np.uint8, np.uint64, np.uint32)))
+            n, n_bytes = len(o), len(b)
+            res = np.zeros(n, dtype=np.uint64)
+            bp, op, lp, dst = (b.ctypes.data if n_bytes else None), o.ctypes.data, ln.ctypes.data, res.ctypes.data
+        bad = C.c_uint64(0xFFFFFFFFFFFFFFFF)
+        rc = L.pp_names_ids(self._p, bp, n_bytes, op, lp, n, mem, dst, None, C.byref(bad))
+        if rc:
+            e = PolypolishError(rc, L.pp_last_error(self._ctx._h).decode())
+            e.bad = None if bad.value == 0xFFFFFFFFFFFFFFFF else int(bad.value)
+            raise e
+        if mem != MEM_HOST and n:
+            self._ctx._chk(L.pp_ctx_download(self._ctx._h, res.ctypes.data, dst, res.nbytes))
+        return res
+
+    @property
+    def count(self):
+        return int(lib().pp_names_count(self._p))
+
+    def name(self, id):  # noqa: A002 (the header's word)
+        ln = C.c_uint32(0)
+        buf = np.zeros(256, dtype=np.uint8)
+        rc = lib().pp_names_name(self._p, int(id), buf.ctypes.data, len(buf), C.byref(ln))
+        if rc and int(id) < self.count and ln.value > len(buf):     # a long name: once more with room for it
+            buf = np.zeros(ln.value, dtype=np.uint8)
+            rc = lib().pp_names_name(self._p, int(id), buf.ctypes.data, len(buf), C.byref(ln))
+        self._ctx._chk(rc)
+        return buf[:ln.value].tobytes()
+
+    def kernel_ms(self):
+        ms = C.c_float()
+        self._ctx._chk(lib().pp_names_kernel_ms(self._p, C.byref(ms)))
+        return float(ms.value)
+
+    def close(self):
+        if self._p:
+            lib().pp_names_free(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _report_dict(rep):
