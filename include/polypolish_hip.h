@@ -17,7 +17,10 @@
  * src/alignment.rs:49-128,225-322, src/filter.rs:91-145,309-349) that the `polypolish` CLI and any
  * binding share: as multi-threaded host code (pp_ingest_*, pp_filter_load / pp_filter_write) and as
  * device tokenizers over the uploaded text (pp_dev_ingest_*, pp_filter_load_device), and the whole
- * commands (pp_polish_files, pp_filter_files, pp_filter_polish_files).
+ * commands (pp_polish_files, pp_filter_files, pp_filter_polish_files).  A caller who holds alignment
+ * RECORDS, not SAM text, has the record chain, every link on the device: pp_bam_records (uncompressed
+ * BAM bytes -> raw records, the chain's front end) -> pp_names -> pp_filter_records -> pp_batch_gate ->
+ * pp_batch_prepare -> pp_polish_*.
  *
  * Conventions: plain pointers and sizes, no C++/torch types.  Every function returns PP_OK or a
  * PP_ERR_* code and never exits the process; pp_last_error() holds the message the reference
@@ -310,6 +313,75 @@ uint64_t pp_names_count(const pp_names *t); /* distinct names held */
 int pp_names_name(const pp_names *t, uint64_t id, uint8_t *out, uint32_t cap, uint32_t *len);
 int pp_names_kernel_ms(const pp_names *t, float *ms);
 void pp_names_free(pp_names *t);
+
+/* The FRONT END of the record chain for a caller who holds BAM: the alignment records of UNCOMPRESSED BAM bytes as a pp_raw_batch,
+ * decoded on the device.  Inflating BGZF stays the caller's job (htslib, zlib); no command reads BAM: the reference reads SAM text
+ * only, and so does the CLI.  A BAM CIGAR word is len << 4 | op with MIDNSHP=X -> 0..8, bit for bit pp_raw_batch.cigar; l_seq 0 is
+ * SEQ "*"; a record's read_name is an (off, len) range into the bytes, which is what pp_names_ids(..., PP_MEM_DEVICE) takes.
+ *
+ * Two HOST helpers need no device.  Both are memory-safe for any bytes, never read outside [0, n_bytes) and form no sum that could
+ * wrap; a failing one returns PP_ERR_ARG and leaves its message in pp_bam_last_error() (per thread; they have no context).
+ *   pp_bam_header  magic BAM\1, l_text, the text, n_ref, then l_name, name, l_ref per reference: name_off[i] / name_len[i] = the
+ *                  name's range in `bytes` (the length without its NUL), ref_len[i] = l_ref, *records_at = the offset of the first
+ *                  alignment record.  The arrays have `cap` entries; n_ref > cap: *n_ref is set all the same, the first cap entries are
+ *                  written and the call returns PP_ERR_ARG.  A truncated or inconsistent header (a length that runs past the bytes,
+ *                  l_name 0, a name without its NUL): PP_ERR_ARG.
+ *   pp_bam_walk    follows the block_size chain from `from`: rec_off[r] = the offset of record r's block_size word, *end = the first
+ *                  byte not consumed.  The walk stops cleanly at n_bytes -- and, with an array to fill, after `cap` records (*end
+ *                  is then where the next call goes on).  rec_off == NULL or cap == 0 only counts, to the end.  A block_size < 32, or
+ *                  a record (its block_size word, too) that runs past n_bytes: PP_ERR_ARG, *n_rec = the records in front of it, *end
+ *                  = its offset.  The chain is serial by the format, so it is walked on the host: a caller who inflates blocks meets
+ *                  every block_size anyway.
+ *
+ * pp_bam_records decodes the records at rec_off[0 .. n_rec) -- they need not be adjacent, ordered or distinct (a region subset
+ * works); output record r is input record r.
+ *   memory       mem = PP_MEM_HOST or PP_MEM_DEVICE holds for `bytes` and `rec_off`; rec_off is required with PP_MEM_DEVICE; with
+ *                PP_MEM_HOST and rec_off == NULL the library runs pp_bam_walk from offset 0 itself (n_rec is ignored then).  Host
+ *                bytes are uploaded and the device copy lives until pp_bam_free (the name ranges point into it); device bytes are
+ *                borrowed until pp_bam_free.  ref_map is HOST memory whatever `mem`.
+ *   flag         the record's flag;  ref_start = pos < 0 ? 0 : pos (the reference's POS 0, src/alignment.rs:58-61);  seq_len = l_seq
+ *   contig       ref_map[refID]; ref_map has n_ref + 1 entries, entry n_ref answers refID -1 (the "*"); ref_map == NULL: identity,
+ *                and 0xFFFFFFFF for -1.  A pp_names seeded with the FASTA names and asked for the header's names plus "*" yields
+ *                exactly such a map, with the distinct ids per unknown name that pp_filter_records asks for.
+ *   n_cig/cigar  the record's words copied as they are, packed densely in record order
+ *   seq          the nibbles expanded through =ACMGRSVTWYHKDBN, high nibble first; every record in a room of (seq_len + 31) & ~31
+ *                bytes, rooms in record order, zeros behind the read: seq_off is a multiple of PP_SEQ_ALIGN, l_seq 0 takes no room
+ *   read_id      zero until the caller fills it (pp_bam_read_id: DEVICE, n_rec entries), e.g. pp_names_ids over pp_bam_names with
+ *                PP_MEM_DEVICE and id64 = that array
+ *   nm           restates Alignment::new (src/alignment.rs:65-78): it starts at 0xFFFFFFFF; every aux field with tag NM and type
+ *                c C s S i I sets it, the last one wins; NM of any other type is ignored (as NM:Z: is in the text); a negative value
+ *                is PP_ERR_PANIC (the reference's parse::<u32>().unwrap()); behind the walk an ALIGNED record whose nm is still
+ *                0xFFFFFFFF is PP_ERR_QUIT "missing NM tag" -- a type-I value of 4294967295 included, as in the reference
+ *   ZP:Z:fail    tag bytes ZP ignoring ASCII case, type exactly Z, value exactly the four bytes "fail" ignoring case (src/alignment.rs:72)
+ *                clears the pass byte of that aligned record (pp_bam_pass: HOST, one byte per ALIGNED record, what pp_batch_gate
+ *                takes as `pass`, to be ANDed with the filter's verdicts)
+ *   aux walk     understands A c C s S i I f Z H and B with the sub-types c C s S i I f
+ *   ignored      mapq, bin, the mate fields, tlen, QUAL.  LIMIT: a CG:B:I long CIGAR is not interpreted; its placeholder CIGAR starts
+ *                with S, so the gate drops the record.
+ * Everything is validated on the device before anything is read through it, without sums that could wrap, and no byte outside
+ * [0, n_bytes) is ever loaded, by a wide load either: a PP_MEM_DEVICE array may end where its allocation ends.  PP_ERR_ARG with
+ * *bad_record (may be NULL) = the first such record in index order, and no object: a rec_off or record outside the array; block_size
+ * < 32 + l_read_name + 4 * n_cigar_op + (l_seq + 1) / 2 + l_seq; l_read_name == 0 or a name without its NUL; a CIGAR op above 8; a
+ * refID outside [-1, n_ref) (ref_map == NULL: below -1); an aux field that is cut, of unknown type, a Z / H without NUL inside the
+ * record, a B whose count runs past the record.  Only when no record has such a defect is the first QUIT / PANIC record in index order
+ * reported (*bad_record = it).  The reference streams: to get ITS order against the gate's own errors, gate the records in front of
+ * bad_record first.  Also PP_ERR_ARG: null arguments, PP_MEM_PEER, rec_off == NULL with PP_MEM_DEVICE, a chain that pp_bam_walk
+ * refuses (*bad_record = the records in front).  PP_ERR_LIMIT as for pp_polish_add (< 2^32-1 records, < 2^40 SEQ bytes of rooms).
+ * n_rec == 0 decodes to an empty batch.  The context's stream has been synchronised when the call returns: host inputs may be
+ * released.  pp_bam_kernel_ms: as pp_gated_kernel_ms.  The object belongs to its context and is freed before it. */
+typedef struct pp_bam pp_bam;
+int pp_bam_header(const uint8_t *bytes, uint64_t n_bytes, uint32_t cap, uint32_t *n_ref, uint64_t *name_off, uint32_t *name_len,
+                  uint32_t *ref_len, uint64_t *records_at);
+int pp_bam_walk(const uint8_t *bytes, uint64_t n_bytes, uint64_t from, uint64_t *rec_off, uint64_t cap, uint64_t *n_rec, uint64_t *end);
+const char *pp_bam_last_error(void);
+int pp_bam_records(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, const uint64_t *rec_off, uint64_t n_rec, int mem,
+                   const uint32_t *ref_map, uint32_t n_ref, pp_bam **out, uint64_t *bad_record);
+void pp_bam_raw(const pp_bam *b, pp_raw_batch *out); /* borrowed view, DEVICE memory; out->read_id = the array below */
+uint64_t *pp_bam_read_id(pp_bam *b);                 /* DEVICE, n_rec entries: zero until the caller fills it */
+void pp_bam_names(const pp_bam *b, const uint8_t **bytes_dev, uint64_t *n_bytes, const uint64_t **off, const uint32_t **len); /* DEVICE: what pp_names_ids takes */
+void pp_bam_pass(const pp_bam *b, const uint8_t **zp, uint64_t *n_aligned); /* HOST: one byte per ALIGNED record, 0 = carries ZP:Z:fail */
+int pp_bam_kernel_ms(const pp_bam *b, float *ms);
+void pp_bam_free(pp_bam *b);
 
 /* Per-contig figures the reference prints to stderr (src/polish.rs:206-227). */
 typedef struct {

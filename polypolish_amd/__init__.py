@@ -196,6 +196,8 @@ EXPORTS = [
     "pp_batch_gate", "pp_gated_batch", "pp_gated_counts", "pp_gated_kernel_ms", "pp_gated_free",
     "pp_filter_thresholds", "pp_filter_records",
     "pp_names_create", "pp_names_ids", "pp_names_count", "pp_names_name", "pp_names_kernel_ms", "pp_names_free",
+    "pp_bam_header", "pp_bam_walk", "pp_bam_last_error", "pp_bam_records", "pp_bam_raw", "pp_bam_read_id", "pp_bam_names", "pp_bam_pass",
+    "pp_bam_kernel_ms", "pp_bam_free",
 ]
 
 _lib = None
@@ -341,6 +343,21 @@ def lib():
         L.pp_names_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.pp_names_free.argtypes = [vp]
         L.pp_names_free.restype = None
+        L.pp_bam_header.argtypes = [vp, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32), vp, vp, vp, u64p]
+        L.pp_bam_walk.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, u64p, u64p]
+        L.pp_bam_last_error.restype = C.c_char_p
+        L.pp_bam_records.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, vp, C.c_uint32, C.POINTER(vp), u64p]
+        L.pp_bam_raw.argtypes = [vp, C.POINTER(RawBatch)]
+        L.pp_bam_raw.restype = None
+        L.pp_bam_read_id.argtypes = [vp]
+        L.pp_bam_read_id.restype = vp
+        L.pp_bam_names.argtypes = [vp, C.POINTER(vp), u64p, C.POINTER(vp), C.POINTER(vp)]
+        L.pp_bam_names.restype = None
+        L.pp_bam_pass.argtypes = [vp, C.POINTER(vp), u64p]
+        L.pp_bam_pass.restype = None
+        L.pp_bam_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.pp_bam_free.argtypes = [vp]
+        L.pp_bam_free.restype = None
         _lib = L
     return _lib
 
@@ -877,6 +894,138 @@ class Names:
     def close(self):
         if self._p:
             lib().pp_names_free(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _bam_bytes(data):
+    """uncompressed BAM bytes as a contiguous uint8 array (no copy of an array that already is one)"""
+    if isinstance(data, np.ndarray):
+        return np.ascontiguousarray(data, dtype=np.uint8)
+    return np.frombuffer(bytes(data), dtype=np.uint8)
+
+
+def bam_header(data):
+    """pp_bam_header (no device needed): {"names": [bytes], "name_off", "name_len", "ref_len": numpy arrays, "records_at": int} of
+    uncompressed BAM bytes; a truncated or inconsistent header raises PolypolishError(ERR_ARG)."""
+    L = lib()
+    b = _bam_bytes(data)
+    n_ref, at = C.c_uint32(0), C.c_uint64(0)
+    rc = L.pp_bam_header(b.ctypes.data if len(b) else None, len(b), 0, C.byref(n_ref), None, None, None, C.byref(at))
+    n = int(n_ref.value)
+    off, ln, rl = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    if n:
+        rc = L.pp_bam_header(b.ctypes.data, len(b), n, C.byref(n_ref), off.ctypes.data, ln.ctypes.data, rl.ctypes.data, C.byref(at))
+    if rc:
+        raise PolypolishError(rc, L.pp_bam_last_error().decode())
+    return {"names": [b[int(o):int(o) + int(k)].tobytes() for o, k in zip(off, ln)], "name_off": off, "name_len": ln, "ref_len": rl,
+            "records_at": int(at.value)}
+
+
+def bam_walk(data, start=0):
+    """pp_bam_walk (no device needed): (rec_off: np.uint64 array, end) -- the offset of every record's block_size word from `start`
+    on, and the first byte not consumed.  A chain that breaks raises PolypolishError(ERR_ARG) with .n_rec = the records in front
+    of the break and .end = its offset."""
+    L = lib()
+    b = _bam_bytes(data)
+    n, end = C.c_uint64(0), C.c_uint64(0)
+    bp = b.ctypes.data if len(b) else None
+    rc = L.pp_bam_walk(bp, len(b), int(start), None, 0, C.byref(n), C.byref(end))
+    if rc:
+        e = PolypolishError(rc, L.pp_bam_last_error().decode())
+        e.n_rec, e.end = int(n.value), int(end.value)
+        raise e
+    off = np.zeros(int(n.value), np.uint64)
+    if len(off):
+        rc = L.pp_bam_walk(bp, len(b), int(start), off.ctypes.data, len(off), C.byref(n), C.byref(end))
+        if rc:
+            raise PolypolishError(rc, L.pp_bam_last_error().decode())
+    return off, int(end.value)
+
+
+class BamRecords:
+    """pp_bam_records: the alignment records of uncompressed BAM bytes as a raw batch in DEVICE memory, owned by this object.
+      data, rec_off  mem = MEM_HOST: bytes / a uint8 array, and the records' offsets (None: the library walks the chain from offset 0);
+                     MEM_DEVICE: data = (device address, n_bytes), rec_off = (device address of n uint64, n)
+      ref_map        None, or n_ref + 1 contig ids (host): entry n_ref answers refID -1
+      .n_rec, .seq_bytes, .n_cig_total
+      .raw()         the device-address dict gate_records(..., mem=MEM_DEVICE) / filter_records(..., mem=MEM_DEVICE) take
+      .names()       keyword arguments for Names.ids(mem=MEM_DEVICE, out=.read_id_ptr): the QNAMEs' ranges in the device bytes
+      .read_id_ptr   device address of raw()["read_id"]: n_rec uint64, zero until filled
+      .zp            np.uint8, one per ALIGNED record, 0 = the record carries ZP:Z:fail: gate_records' `passed` (AND the filter's)
+      .host()        numpy copies of the arrays, and "name_off" / "name_len"
+      .kernel_ms()   HIP-event time of the decode's kernels (the context had set_profiling on)
+    A failing call raises PolypolishError with .bad_record."""
+
+    def __init__(self, ctx, data, rec_off=None, ref_map=None, mem=MEM_HOST):
+        L = lib()
+        if mem == MEM_HOST:
+            b = _bam_bytes(data)
+            bp, n_bytes = (b.ctypes.data if len(b) else None), len(b)
+            o = None if rec_off is None else np.ascontiguousarray(rec_off, dtype=np.uint64)
+            n = 0 if o is None else len(o)
+            if o is not None and n == 0:
+                o = np.zeros(1, dtype=np.uint64)     # (an array without records still is one: no walk)
+            op = None if o is None else o.ctypes.data
+        else:
+            bp, n_bytes = int(data[0]), int(data[1])
+            op, n = (None, 0) if rec_off is None else (int(rec_off[0]), int(rec_off[1]))
+        m = None if ref_map is None else np.ascontiguousarray(ref_map, dtype=np.uint32)
+        self._p = C.c_void_p()
+        self._ctx = ctx
+        bad = C.c_uint64(0xFFFFFFFFFFFFFFFF)
+        rc = L.pp_bam_records(ctx._h, bp, n_bytes, op, n, mem, m.ctypes.data if m is not None else None, len(m) - 1 if m is not None else 0,
+                              C.byref(self._p), C.byref(bad))
+        if rc:
+            e = PolypolishError(rc, L.pp_last_error(ctx._h).decode())
+            e.bad_record = None if bad.value == 0xFFFFFFFFFFFFFFFF else int(bad.value)
+            raise e
+        out = RawBatch()
+        L.pp_bam_raw(self._p, C.byref(out))
+        self.n_rec, self.seq_bytes, self.n_cig_total = int(out.n_rec), int(out.seq_bytes), int(out.n_cig_total)
+        self._ptrs = {name: (C.cast(getattr(out, name), C.c_void_p).value or 0) for name, _ in RAW_FIELDS}
+        self.read_id_ptr = L.pp_bam_read_id(self._p) or 0
+        nb, nbytes, no, nl = C.c_void_p(), C.c_uint64(0), C.c_void_p(), C.c_void_p()
+        L.pp_bam_names(self._p, C.byref(nb), C.byref(nbytes), C.byref(no), C.byref(nl))
+        self._names = (nb.value or 0, no.value or 0, nl.value or 0)
+        self.n_bytes = int(nbytes.value)
+        zp, n_al = C.c_void_p(), C.c_uint64(0)
+        L.pp_bam_pass(self._p, C.byref(zp), C.byref(n_al))
+        self.zp = (np.ctypeslib.as_array(C.cast(zp, C.POINTER(C.c_uint8)), shape=(int(n_al.value),)).copy() if n_al.value
+                   else np.zeros(0, np.uint8))
+
+    def raw(self):
+        return dict(self._ptrs, n_rec=self.n_rec, seq_bytes=self.seq_bytes, n_cig_total=self.n_cig_total)
+
+    def names(self):
+        return {"names": self._names, "n": self.n_rec, "n_bytes": self.n_bytes}
+
+    def _down(self, addr, n, dt):
+        arr = np.zeros(int(n), dtype=dt)
+        if arr.size and addr:
+            self._ctx._chk(lib().pp_ctx_download(self._ctx._h, arr.ctypes.data, addr, arr.nbytes))
+        return arr
+
+    def host(self):
+        sizes = {"seq": self.seq_bytes, "cigar": self.n_cig_total}
+        out = {name: self._down(self._ptrs[name], sizes.get(name, self.n_rec), dt) for name, dt in RAW_FIELDS}
+        out["name_off"] = self._down(self._names[1], self.n_rec, np.uint64)
+        out["name_len"] = self._down(self._names[2], self.n_rec, np.uint32)
+        return out
+
+    def kernel_ms(self):
+        ms = C.c_float()
+        self._ctx._chk(lib().pp_bam_kernel_ms(self._p, C.byref(ms)))
+        return float(ms.value)
+
+    def close(self):
+        if self._p:
+            lib().pp_bam_free(self._p)
             self._p = C.c_void_p()
 
     def __del__(self):
