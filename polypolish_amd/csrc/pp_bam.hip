@@ -11,7 +11,7 @@
 //                  is the reference's panic) and ZP:Z:fail.  A defect is status[0] = record << 8 | kind by atomicMin: the first
 //                  record in index order wins; QUIT / PANIC of Alignment::new (alignment.rs:65-78) the same way in status[1]
 //   k_bam_place    the SEQ rooms ((l_seq + 31) & ~31 bytes, in units of PP_SEQ_ALIGN), the CIGAR words and the numbering of the aligned
-//                  records by the DPP wave scan of pp_wave.h with a carry per workgroup: the workgroups' sums, k_bam_scan3 over them,
+//                  records by the workgroup scan of pp_dev.h (the DPP wave scan, a carry per workgroup): the workgroups' sums, k_colscan over them,
 //                  then seq_off, cig_off and the pass byte of every aligned record at its rank
 //   k_bam_expand   pass B, the hot kernel: eight lanes per record, 16 source bytes -> 32 ASCII bytes per lane and trip (four nibbles at
 //                  a time through two byte permutes over the table =ACMGRSVTWYHKDBN), two 16-byte aligned stores into the room, zeros
@@ -20,10 +20,7 @@
 // No byte outside [0, n_bytes) is loaded: a wide load is issued only where the array has that many bytes left (word_at's rule,
 // pp_names.hip); loads inside a record that pass A found inside the array need no second look.
 #include "pp_bam_host.h"
-#include "pp_devtext.h"
-#include "pp_wave.h"
-
-#include <vector>
+#include "pp_dev.h"
 
 struct pp_bam {
     pp_ctx *ctx = nullptr;
@@ -157,25 +154,6 @@ __global__ __launch_bounds__(256) void k_bam_scan(u32 n_rec, BamSrc S, BamRec O,
     O.zp[r] = (u8)zp_fail;
 }
 
-// Exclusive prefix of v over the workgroup's BAM_BLOCK threads (every thread calls it), *total = the workgroup's sum; v = hi << 16 |
-// lo scanned as two halves, so that sums past 32 bits (the rooms) hold.  As block_scan_excl64 of pp_gate.hip.
-__device__ __forceinline__ u64 block_scan_excl64(u32 v, u64 *s_w, u64 *total) {
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const u64 inc = ((u64)pp::wave_scan_incl(v >> 16) << 16) + (u64)pp::wave_scan_incl(v & 0xFFFFu);
-    if (lane == 63u) s_w[wave] = inc;
-    __syncthreads();
-    u64 before = 0, sum = 0;
-#pragma unroll
-    for (u32 i = 0; i < BAM_BLOCK / 64u; i++) {
-        const u64 w = s_w[i];
-        before += i < wave ? w : 0ull;
-        sum += w;
-    }
-    __syncthreads();  // (s_w is used again)
-    *total = sum;
-    return before + inc - (u64)v;
-}
-
 // PLACE == false: the workgroups' numbers of aligned records, room units (PP_SEQ_ALIGN bytes each) and CIGAR words (blk3: three
 // words per workgroup).  PLACE == true: blk3 holds their exclusive scan: seq_off, cig_off, and the pass byte at the aligned rank.
 template <bool PLACE>
@@ -187,13 +165,13 @@ __global__ __launch_bounds__(BAM_BLOCK) void k_bam_place(u32 n_rec, const uint16
     u32 al = 0, units = 0, nc = 0;
     if (r < n_rec) {
         al = (flag[r] & 4u) ? 0u : 1u;
-        units = (u32)(((u64)seq_len[r] + (u64)PP_SEQ_ALIGN - 1u) / (u64)PP_SEQ_ALIGN);
+        units = (u32)room_units(seq_len[r]);
         nc = n_cig[r];
     }
     u64 t_al, t_units, t_cig;
-    const u64 ex_al = block_scan_excl64(al, s_w, &t_al);
-    const u64 ex_units = block_scan_excl64(units, s_w, &t_units);
-    const u64 ex_cig = block_scan_excl64(nc, s_w, &t_cig);
+    const u64 ex_al = block_scan_excl64<BAM_BLOCK>(al, s_w, &t_al);
+    const u64 ex_units = block_scan_excl64<BAM_BLOCK>(units, s_w, &t_units);
+    const u64 ex_cig = block_scan_excl64<BAM_BLOCK>(nc, s_w, &t_cig);
     u64 *const mine = blk3 + 3ull * blockIdx.x;
     if (!PLACE) {
         if (threadIdx.x == 0) { mine[0] = t_al; mine[1] = t_units; mine[2] = t_cig; }
@@ -203,34 +181,6 @@ __global__ __launch_bounds__(BAM_BLOCK) void k_bam_place(u32 n_rec, const uint16
     seq_off[r] = (mine[1] + ex_units) * (u64)PP_SEQ_ALIGN;
     cig_off[r] = mine[2] + ex_cig;
     if (al) pass[mine[0] + ex_al] = zp[r] ? 0 : 1;
-}
-
-// exclusive scan of the workgroups' three sums, column by column (one workgroup; out: nb + 1 rows).  As k_gate_scan3.
-__global__ __launch_bounds__(1024) void k_bam_scan3(const u64 *__restrict__ in, u64 nb, u64 *__restrict__ out) {
-    __shared__ u64 part[1024];
-    const u32 t = threadIdx.x;
-    const u64 per = (nb + 1023) / 1024;
-    const u64 lo = min(nb, (u64)t * per), hi = min(nb, lo + per);
-    for (u32 c = 0; c < 3u; c++) {
-        u64 s = 0;
-        for (u64 i = lo; i < hi; i++) s += in[3 * i + c];
-        part[t] = s;
-        __syncthreads();
-        for (u32 off = 1; off < 1024; off <<= 1) {
-            const u64 v = (t >= off) ? part[t - off] : 0;
-            __syncthreads();
-            part[t] += v;
-            __syncthreads();
-        }
-        u64 run = part[t] - s;
-        for (u64 i = lo; i < hi; i++) {
-            const u64 v = in[3 * i + c];
-            out[3 * i + c] = run;
-            run += v;
-        }
-        if (t == 1023) out[3 * nb + c] = part[1023];
-        __syncthreads();
-    }
 }
 
 // Two source bytes (h: 16 bits) -> their four bases, high nibble first, as four ASCII bytes.  The nibbles go to a byte each; a
@@ -255,7 +205,7 @@ __global__ __launch_bounds__(256) void k_bam_expand(u32 n_rec, const u8 *__restr
     const u32 s = (u32)t & 7u;
     if ((t >> 3) >= n_rec) return;
     const u32 r = (u32)(t >> 3);
-    const u64 n = seq_len[r], room = (n + (u64)PP_SEQ_ALIGN - 1u) & ~((u64)PP_SEQ_ALIGN - 1u);
+    const u64 n = seq_len[r], room = room_bytes(n);
     const u32 nc = n_cig[r];
     const u64 cig_src = name_off[r] + name_len[r] + 1u, seq_src = cig_src + 4ull * nc;
     u8 *const out = seq + seq_off[r];  // a multiple of PP_SEQ_ALIGN
@@ -287,17 +237,6 @@ __global__ __launch_bounds__(256) void k_bam_expand(u32 n_rec, const u8 *__restr
     u32 *const cd = cigar + cig_off[r];
     for (u32 j = s; j < nc; j += 8u) cd[j] = ld32(B, cig_src + 4ull * j);
 }
-
-struct Scratch {  // device memory of one call, released when it returns
-    std::vector<void *> p;
-    ~Scratch() { for (void *q : p) (void)hipFree(q); }
-    int get(pp_ctx *ctx, void **out, size_t bytes) {
-        *out = nullptr;
-        PP_HIPCHK(ctx, hipMalloc(out, bytes ? bytes : 16));
-        p.push_back(*out);
-        return PP_OK;
-    }
-};
 
 thread_local char t_bam_msg[256] = "";
 
@@ -400,11 +339,9 @@ extern "C" int pp_bam_records(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_byte
 
     pp_bam *P = new pp_bam;
     P->ctx = ctx;
-    struct Guard {  // (every early return releases what was made so far)
-        pp_bam *p;
-        ~Guard() { if (p) pp_bam_free(p); }
-    } guard{P};
-    Scratch T;
+    std::unique_ptr<pp_bam, void (*)(pp_bam *)> guard(P, pp_bam_free);  // (every early return releases what was made so far)
+    CallScratch T;
+    StageTimer timer(ctx, ctx->profiling != 0);
     int rc;
     // ---- the bytes on the device ----
     BamSrc S{};
@@ -414,28 +351,19 @@ extern "C" int pp_bam_records(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_byte
         PP_HIPCHK(ctx, hipMalloc(&P->own_bytes, n_bytes ? (size_t)n_bytes : 16));
         if (n_bytes) PP_HIPCHK(ctx, hipMemcpyAsync(P->own_bytes, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, st));
         S.bytes = (const u8 *)P->own_bytes;
-        void *d_off;
-        if ((rc = T.get(ctx, &d_off, (size_t)n * 8))) return rc;
-        if (n) PP_HIPCHK(ctx, hipMemcpyAsync(d_off, rec_off, (size_t)n * 8, hipMemcpyHostToDevice, st));
-        S.rec_off = (const u64 *)d_off;
     } else {
         S.bytes = bytes;
-        S.rec_off = (const u64 *)rec_off;
     }
+    if ((rc = on_device(ctx, T, mem, (const u64 *)rec_off, n, &S.rec_off))) return rc;
     P->bytes = S.bytes;
     P->n_bytes = n_bytes;
     if (n == 0) {  // no records: an empty batch
         PP_HIPCHK(ctx, hipStreamSynchronize(st));
-        guard.p = nullptr;
+        guard.release();
         *out = P;
         return PP_OK;
     }
-    if (ref_map) {
-        void *d_map;
-        if ((rc = T.get(ctx, &d_map, ((size_t)n_ref + 1) * 4))) return rc;
-        PP_HIPCHK(ctx, hipMemcpyAsync(d_map, ref_map, ((size_t)n_ref + 1) * 4, hipMemcpyHostToDevice, st));
-        S.ref_map = (const u32 *)d_map;
-    }
+    if (ref_map && (rc = on_device(ctx, T, PP_MEM_HOST, ref_map, (size_t)n_ref + 1, &S.ref_map))) return rc;  // (host memory always)
 
     // ---- the per-record arrays ----
     const size_t rbytes[13] = {(size_t)n * 2, (size_t)n * 8, (size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)n * 8, (size_t)n * 4,
@@ -450,30 +378,16 @@ extern "C" int pp_bam_records(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_byte
         return rc;
     PP_HIPCHK(ctx, hipMemsetAsync(d_status, 0xFF, 16, st));
 
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct Events {
-        hipEvent_t *e;
-        ~Events() { for (int i = 0; i < 8; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
-    } events{ev};
-    const bool timed = ctx->profiling != 0;
-    if (timed)
-        for (int i = 0; i < 8; i++) PP_HIPCHK(ctx, hipEventCreate(&ev[i]));
-    auto mark = [&](int i) -> int {
-        if (timed) PP_HIPCHK(ctx, hipEventRecord(ev[i], st));
-        return PP_OK;
-    };
-
     // ---- pass A, and the sums ----
     BamRec O{(uint16_t *)P->d[0], (u32 *)P->d[2], (u32 *)P->d[3], (u32 *)P->d[4], (u32 *)P->d[6], (u32 *)P->d[8], (u32 *)P->d[12], (u64 *)P->d[11],
              (u8 *)d_zp};
-    if ((rc = mark(0))) return rc;
+    if ((rc = timer.begin(0))) return rc;
     hipLaunchKernelGGL(k_bam_scan, dim3((n + 255u) / 256u), dim3(256), 0, st, n, S, O, (u64 *)d_status);
-    if ((rc = mark(1))) return rc;
-    if ((rc = mark(2))) return rc;
+    if ((rc = timer.end()) || (rc = timer.begin(1))) return rc;
     hipLaunchKernelGGL(k_bam_place<false>, dim3(nb), dim3(BAM_BLOCK), 0, st, n, (const uint16_t *)P->d[0], (const u32 *)P->d[6], (const u32 *)P->d[8],
                        (const u8 *)d_zp, (u64 *)d_blk3, (u64 *)nullptr, (u64 *)nullptr, (u8 *)nullptr);
-    hipLaunchKernelGGL(k_bam_scan3, dim3(1), dim3(1024), 0, st, (const u64 *)d_blk3, (u64)nb, (u64 *)d_blk3off);
-    if ((rc = mark(3))) return rc;
+    hipLaunchKernelGGL(k_colscan<3>, dim3(1), dim3(1024), 0, st, (const u64 *)d_blk3, (u64)nb, (u64 *)d_blk3off);
+    if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     u64 status[2] = {~0ull, ~0ull}, totals[3] = {0, 0, 0};
     if ((rc = fetch(ctx, d_status, status, 2)) || (rc = fetch(ctx, (const u64 *)d_blk3off + 3ull * nb, totals, 3))) return rc;
@@ -493,28 +407,20 @@ extern "C" int pp_bam_records(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_byte
     PP_HIPCHK(ctx, hipMalloc(&P->d[9], (size_t)total + 64));
     PP_HIPCHK(ctx, hipMalloc(&P->d[10], n_cig_total ? (size_t)n_cig_total * 4 : 16));
     PP_HIPCHK(ctx, hipMemsetAsync((u8 *)P->d[9] + total, 0, 64, st));
-    if ((rc = mark(4))) return rc;
+    if ((rc = timer.begin(1))) return rc;
     hipLaunchKernelGGL(k_bam_place<true>, dim3(nb), dim3(BAM_BLOCK), 0, st, n, (const uint16_t *)P->d[0], (const u32 *)P->d[6], (const u32 *)P->d[8],
                        (const u8 *)d_zp, (u64 *)d_blk3off, (u64 *)P->d[5], (u64 *)P->d[7], (u8 *)d_pass);
-    if ((rc = mark(5))) return rc;
-    if ((rc = mark(6))) return rc;
+    if ((rc = timer.end()) || (rc = timer.begin(2))) return rc;
     hipLaunchKernelGGL(k_bam_expand, dim3((unsigned)(((u64)n * 8u + 255u) / 256u)), dim3(256), 0, st, n, S.bytes, n_bytes, (const u64 *)P->d[11],
                        (const u32 *)P->d[12], (const u32 *)P->d[6], (const u32 *)P->d[8], (const u64 *)P->d[5], (const u64 *)P->d[7], (u8 *)P->d[9],
                        (u32 *)P->d[10]);
-    if ((rc = mark(7))) return rc;
+    if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     P->pass.resize((size_t)n_al);
     if (n_al) PP_HIPCHK(ctx, hipMemcpyAsync(P->pass.data(), d_pass, (size_t)n_al, hipMemcpyDeviceToHost, st));
     PP_HIPCHK(ctx, hipStreamSynchronize(st));  // host inputs may be released, the scratch goes away
-    if (timed) {
-        float a = 0.f, b = 0.f, c = 0.f, d = 0.f;
-        PP_HIPCHK(ctx, hipEventElapsedTime(&a, ev[0], ev[1]));
-        PP_HIPCHK(ctx, hipEventElapsedTime(&b, ev[2], ev[3]));
-        PP_HIPCHK(ctx, hipEventElapsedTime(&c, ev[4], ev[5]));
-        PP_HIPCHK(ctx, hipEventElapsedTime(&d, ev[6], ev[7]));
-        P->ms[0] = a;
-        P->ms[1] = b + c;
-        P->ms[2] = d;
+    if (timer.on) {
+        if ((rc = timer.sums(P->ms, 3))) return rc;
         P->timed = true;
     }
     pp_raw_batch &V = P->view;
@@ -525,7 +431,7 @@ extern "C" int pp_bam_records(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_byte
     V.seq_bytes = total;
     V.cigar = (const u32 *)P->d[10];
     V.n_cig_total = n_cig_total;
-    guard.p = nullptr;
+    guard.release();
     *out = P;
     return PP_OK;
 }

@@ -1,20 +1,13 @@
 // pp_devtext.h -- device-side text utilities shared by the SAM tokenizers (pp_tokenize.hip: polish ingest;
-// pp_filter_dev.hip: the filter's quick parse): newline index, multi-block exclusive scan, tab search,
-// integer parsing, and small host helpers.  Everything lives in an anonymous namespace: each translation
-// unit gets its own copies of the kernels.
+// pp_filter_dev.hip: the filter's quick parse): newline index, tab search, integer parsing, the wave's lines through LDS.
+// What is not text -- typedefs, scans, the host helpers of a call -- is pp_dev.h's.  Everything lives in an anonymous
+// namespace: each translation unit gets its own copies of the kernels.
 #pragma once
-#include "pp_internal.h"
-
-#include <algorithm>
+#include "pp_dev.h"
 
 namespace {
 
-typedef unsigned long long u64;
-typedef uint32_t u32;
-typedef uint8_t u8;
-
 constexpr u32 NL_BLOCK = 1024 * 64;  // bytes of text per block of the newline kernels (64 per thread)
-__device__ __forceinline__ void report(u64 *status, u64 key) { atomicMin(status, key); }
 
 // ---- newline index -------------------------------------------------------------------------------
 __device__ __forceinline__ u32 count_nl16(uint4 v) {
@@ -82,78 +75,6 @@ __global__ __launch_bounds__(1024) void k_nl_write(const u8 *__restrict__ text, 
             }
         }
     }
-}
-
-// ---- exclusive scan: u32 in -> T out (n + 1 entries) -- block sums, a single-block scan of the sums,
-// then every block scans its own 8192 elements on top of its base ------------------------------------
-constexpr u32 SCAN_PER_BLOCK = 1024 * 8;
-
-__global__ __launch_bounds__(1024) void k_scan_sums(const u32 *__restrict__ in, u64 n, u32 *__restrict__ sums) {
-    __shared__ u32 s_sum;
-    if (threadIdx.x == 0) s_sum = 0;
-    __syncthreads();
-    const u64 base = (u64)blockIdx.x * SCAN_PER_BLOCK + (u64)threadIdx.x * 8u;
-    u32 v = 0;
-#pragma unroll
-    for (u32 i = 0; i < 8; i++)
-        if (base + i < n) v += in[base + i];
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63u) == 0 && v) atomicAdd(&s_sum, v);
-    __syncthreads();
-    if (threadIdx.x == 0) sums[blockIdx.x] = s_sum;
-}
-
-template <typename T>
-__global__ __launch_bounds__(1024) void k_tscan(const u32 *__restrict__ in, u64 n, T *__restrict__ out) {
-    __shared__ u64 part[1024];
-    const u32 t = threadIdx.x;
-    const u64 per = (n + 1023) / 1024;
-    const u64 lo = min(n, (u64)t * per), hi = min(n, lo + per);
-    u64 s = 0;
-    for (u64 i = lo; i < hi; i++) s += in[i];
-    part[t] = s;
-    __syncthreads();
-    for (u32 off = 1; off < 1024; off <<= 1) {
-        const u64 v = (t >= off) ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    u64 run = part[t] - s;
-    for (u64 i = lo; i < hi; i++) {
-        out[i] = (T)run;
-        run += in[i];
-    }
-    if (t == 1023) out[n] = (T)part[1023];
-}
-
-template <typename T>
-__global__ __launch_bounds__(1024) void k_scan_apply(const u32 *__restrict__ in, u64 n, const u64 *__restrict__ sums_off,
-                                                     T *__restrict__ out) {
-    __shared__ u32 s_w[16];
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const u64 base = (u64)blockIdx.x * SCAN_PER_BLOCK + (u64)threadIdx.x * 8u;
-    u32 v[8], sum = 0;
-#pragma unroll
-    for (u32 i = 0; i < 8; i++) {
-        v[i] = base + i < n ? in[base + i] : 0u;
-        sum += v[i];
-    }
-    u32 inc = sum;
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 t = __shfl_up(inc, o, 64);
-        if ((int)lane >= o) inc += t;
-    }
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    u64 run = sums_off[blockIdx.x] + (inc - sum);
-    for (u32 i = 0; i < wave; i++) run += s_w[i];
-#pragma unroll
-    for (u32 i = 0; i < 8; i++) {
-        if (base + i < n) out[base + i] = (T)run;
-        run += v[i];
-    }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) out[n] = (T)sums_off[gridDim.x];
 }
 
 __device__ __forceinline__ bool parse_u(const u8 *s, u32 n, u64 max, u64 &out) {  // str::parse::<uN>()
@@ -246,37 +167,6 @@ __device__ __forceinline__ int op_code(u8 c) {
     }
 }
 
-// ---- the complement of an upper-cased base: the tokenizer's k_tok_seq and the record gate's k_gate_seq fill a "*" record on the other
-// strand with it ----------------------------------------------------------------------------------------
-__device__ __forceinline__ u8 comp_upper(u8 c) {  // misc.rs:170-182 on the upper-cased base
-    switch (c) {
-    case 'A': return 'T'; case 'T': return 'A'; case 'G': return 'C'; case 'C': return 'G';
-    case 'R': return 'Y'; case 'Y': return 'R'; case 'S': return 'S'; case 'W': return 'W';
-    case 'K': return 'M'; case 'M': return 'K'; case 'B': return 'V'; case 'V': return 'B';
-    case 'D': return 'H'; case 'H': return 'D'; case 'N': return 'N'; case '.': return '.';
-    case '-': return '-'; case '?': return '?'; default: return 'N';
-    }
-}
-
-// ---- the 4-bit mirror of SEQ bytes (pp_aln_batch.seq4), packed while the bytes are in registers (the tokenizer's k_tok_seq,
-// pp_batch_prepare's k_prep_copy) ----------------------------------------------------------------------
-__device__ __forceinline__ u32 seq4_code(u32 c) {
-    const u32 t = (c >> 1) & 3u;  // A->0 C->1 T->2 G->3: the counter rows
-    const u32 expect = (0x47544341u >> (t * 8u)) & 0xFFu;
-    return c == expect ? t : (c == (u32)'N' ? (u32)PP_SEQ4_N : (c == (u32)'-' ? (u32)PP_SEQ4_DASH : (u32)PP_SEQ4_OTHER));
-}
-__device__ __forceinline__ uint2 pack4_16(const u32 w[4]) {  // 16 bytes -> 16 nibbles
-    u32 o[2];
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-        u32 v = 0;
-#pragma unroll
-        for (int j = 0; j < 8; j++) v |= seq4_code((w[2 * q + (j >> 2)] >> (8 * (j & 3))) & 0xFFu) << (4 * j);
-        o[q] = v;
-    }
-    return make_uint2(o[0], o[1]);
-}
-
 // grow a device buffer keeping its first `used` bytes
 int dev_grow(pp_ctx *ctx, pp::DevBuf &b, size_t need, size_t used) {
     if (need == 0) need = 16;
@@ -291,25 +181,6 @@ int dev_grow(pp_ctx *ctx, pp::DevBuf &b, size_t need, size_t used) {
     }
     b.p = q;
     b.cap = want;
-    return PP_OK;
-}
-
-// out[0..n] = exclusive scan of in[0..n); scratch: two small device buffers for the block sums
-template <typename T>
-int scan_u32(pp_ctx *ctx, pp::DevBuf &b_sums, pp::DevBuf &b_sums_off, const u32 *in, u64 n, T *out) {
-    const u64 nb = std::max<u64>(1, (n + SCAN_PER_BLOCK - 1) / SCAN_PER_BLOCK);
-    if (int rc = pp::dev_ensure(ctx, b_sums, nb * 4)) return rc;
-    if (int rc = pp::dev_ensure(ctx, b_sums_off, (nb + 1) * 8)) return rc;
-    hipLaunchKernelGGL(k_scan_sums, dim3((unsigned)nb), dim3(1024), 0, ctx->stream, in, n, (u32 *)b_sums.p);
-    hipLaunchKernelGGL(k_tscan<u64>, dim3(1), dim3(1024), 0, ctx->stream, (const u32 *)b_sums.p, nb, (u64 *)b_sums_off.p);
-    hipLaunchKernelGGL(k_scan_apply<T>, dim3((unsigned)nb), dim3(1024), 0, ctx->stream, in, n, (const u64 *)b_sums_off.p, out);
-    return PP_OK;
-}
-
-template <typename T>
-int fetch(pp_ctx *ctx, const void *dev, T *host, size_t n = 1) {
-    PP_HIPCHK(ctx, hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-    PP_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return PP_OK;
 }
 

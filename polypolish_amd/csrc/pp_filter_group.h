@@ -2,10 +2,10 @@
 // (names in the SAM text) and pp_filter_rec.hip (the 64-bit ids of raw records).  Either interns its keys through an open-
 // addressing table of record indices -- rep[i] = the first record, over both files, that carries record i's key -- and scans
 // "is its own representative" into id_scan; from there on nothing depends on what a key is: read numbers (the rank of a key's
-// first record), the files' group sizes, their scan, the scatter and the sort into file order.  Like pp_devtext.h, which it
+// first record), the files' group sizes, their scan, the scatter and the sort into file order.  Like pp_dev.h, which it
 // builds on, everything lives in an anonymous namespace: each translation unit gets its own copies of the kernels.
 #pragma once
-#include "pp_devtext.h"
+#include "pp_dev.h"
 
 namespace {
 

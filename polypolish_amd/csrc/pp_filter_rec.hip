@@ -19,8 +19,6 @@
 #include "pp_filter_group.h"
 #include "pp_host.h"
 
-#include <array>
-#include <vector>
 
 namespace {
 
@@ -30,9 +28,6 @@ struct RecRaw {  // what the filter reads of a raw batch (device memory)
     const u32 *contig, *ref_start, *n_cig, *cigar;
     u64 n_cig_total;
 };
-
-// does [off, off + len) lie inside an array of `size` elements?  (no sum that could wrap)
-__device__ __forceinline__ bool inside(u64 off, u32 len, u64 size) { return off <= size && (u64)len <= size - off; }
 
 __global__ __launch_bounds__(256) void k_rec_aligned(u32 n_rec, const uint16_t *__restrict__ flag, u32 *__restrict__ is_aln) {
     const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
@@ -113,7 +108,8 @@ __global__ __launch_bounds__(256) void k_rid_find(u64 n, const u64 *__restrict__
 }
 
 // The call's device memory: the context's grow-only buffers (pp_ctx::f_rec), handed out in the order of the requests -- the same
-// request of the next job finds its buffer again.  Nothing in them outlives the call: every table is set up afresh.
+// request of the next job finds its buffer again.  Nothing in them outlives the call: every table is set up afresh.  (Not
+// pp_dev.h's CallScratch, which allocates per call and frees at return; the same get(), so that on_device takes either.)
 struct Scratch {
     pp_ctx *ctx;
     size_t k = 2;  // ([0], [1]: scan_u32's block sums)
@@ -130,40 +126,6 @@ struct Scratch {
 
 enum : int { SPAN_COMPACT = 0, SPAN_INTERN = 1, SPAN_GROUPS = 2 };
 static const char *const SPAN_NAME[3] = {"rec_compact", "rec_intern", "rec_groups"};
-
-struct Spans {  // HIP-event time of the grouping's stages (pp_filter_begin starts the context's own timers afresh)
-    pp_ctx *ctx;
-    bool on;
-    std::vector<std::array<hipEvent_t, 2>> ev;
-    std::vector<int> kind;
-    ~Spans() {
-        for (auto &e : ev) { (void)hipEventDestroy(e[0]); (void)hipEventDestroy(e[1]); }
-    }
-    void begin(int k) {
-        if (!on) return;
-        std::array<hipEvent_t, 2> e;
-        if (hipEventCreate(&e[0]) != hipSuccess) return;
-        if (hipEventCreate(&e[1]) != hipSuccess) { (void)hipEventDestroy(e[0]); return; }
-        (void)hipEventRecord(e[0], ctx->stream);
-        ev.push_back(e);
-        kind.push_back(k);
-    }
-    void end() {
-        if (on && !ev.empty()) (void)hipEventRecord(ev.back()[1], ctx->stream);
-    }
-    void add_to(pp_kernel_times *out) {  // (the stream has been synchronised)
-        float ms[3] = {0.f, 0.f, 0.f};
-        for (size_t i = 0; i < ev.size(); i++) {
-            float t = 0.f;
-            if (hipEventElapsedTime(&t, ev[i][0], ev[i][1]) == hipSuccess) ms[kind[i]] += t;
-        }
-        for (int k = 0; k < 3 && on; k++) {
-            if (out->n == PP_MAX_KERNELS) break;
-            out->name[out->n] = SPAN_NAME[k];
-            out->ms[out->n++] = ms[k];
-        }
-    }
-};
 
 }  // namespace
 
@@ -193,7 +155,7 @@ extern "C" int pp_filter_records(pp_ctx *ctx, const pp_raw_batch raw[2], int mem
     uint8_t *const pass[2] = {pass1, pass2};
 
     Scratch T{ctx};
-    Spans spans{ctx, ctx->profiling != 0, {}, {}};
+    StageTimer spans(ctx, ctx->profiling != 0);  // (pp_filter_begin starts the context's own timers afresh)
     int rc;
     // ---- the source on the device ----
     RecRaw R[2];
@@ -202,18 +164,13 @@ extern "C" int pp_filter_records(pp_ctx *ctx, const pp_raw_batch raw[2], int mem
         const pp_raw_batch &B = raw[f];
         n_rec[f] = (u32)B.n_rec;
         R[f] = RecRaw{B.flag, (const u64 *)B.read_id, (const u64 *)B.cig_off, B.contig, B.ref_start, B.n_cig, B.cigar, B.n_cig_total};
-        if (mem == PP_MEM_HOST && n_rec[f]) {
-            const size_t n = n_rec[f];
-            const void *h[7] = {B.flag, B.read_id, B.cig_off, B.contig, B.ref_start, B.n_cig, B.cigar};
-            const size_t bytes[7] = {n * 2, n * 8, n * 8, n * 4, n * 4, n * 4, (size_t)B.n_cig_total * 4};
-            void *dv[7];
-            for (int i = 0; i < 7; i++) {
-                if ((rc = T.get(ctx, &dv[i], bytes[i]))) return rc;
-                if (bytes[i]) PP_HIPCHK(ctx, hipMemcpyAsync(dv[i], h[i], bytes[i], hipMemcpyHostToDevice, st));
-            }
-            R[f] = RecRaw{(const uint16_t *)dv[0], (const u64 *)dv[1], (const u64 *)dv[2], (const u32 *)dv[3], (const u32 *)dv[4],
-                          (const u32 *)dv[5], (const u32 *)dv[6], B.n_cig_total};
-        }
+        const size_t n = n_rec[f];
+        RecRaw &D = R[f];  // (a batch without records uploads nothing)
+        if (n && ((rc = on_device(ctx, T, mem, D.flag, n, &D.flag)) || (rc = on_device(ctx, T, mem, D.read_id, n, &D.read_id)) ||
+                  (rc = on_device(ctx, T, mem, D.cig_off, n, &D.cig_off)) || (rc = on_device(ctx, T, mem, D.contig, n, &D.contig)) ||
+                  (rc = on_device(ctx, T, mem, D.ref_start, n, &D.ref_start)) || (rc = on_device(ctx, T, mem, D.n_cig, n, &D.n_cig)) ||
+                  (rc = on_device(ctx, T, mem, D.cigar, (size_t)B.n_cig_total, &D.cigar))))
+            return rc;
     }
 
     // ---- the aligned records of either file, numbered in file order ----
@@ -223,10 +180,10 @@ extern "C" int pp_filter_records(pp_ctx *ctx, const pp_raw_batch raw[2], int mem
         if (!n_rec[f]) continue;
         void *d_isaln;
         if ((rc = T.get(ctx, &d_isaln, (size_t)n_rec[f] * 4)) || (rc = T.get(ctx, &d_rank[f], ((size_t)n_rec[f] + 1) * 4))) return rc;
-        spans.begin(SPAN_COMPACT);
+        if ((rc = spans.begin(SPAN_COMPACT))) return rc;
         hipLaunchKernelGGL(k_rec_aligned, dim3((n_rec[f] + 255u) / 256u), dim3(256), 0, st, n_rec[f], R[f].flag, (u32 *)d_isaln);
         if ((rc = scan_u32<u32>(ctx, T.sums(), T.sums_off(), (const u32 *)d_isaln, (u64)n_rec[f], (u32 *)d_rank[f]))) return rc;
-        spans.end();
+        if ((rc = spans.end())) return rc;
         PP_HIPCHK(ctx, hipGetLastError());
         if ((rc = fetch(ctx, (const u32 *)d_rank[f] + n_rec[f], &n_al[f]))) return rc;
     }
@@ -245,10 +202,10 @@ extern "C" int pp_filter_records(pp_ctx *ctx, const pp_raw_batch raw[2], int mem
             (rc = T.get(ctx, &d_end[f], n * 8)) || (rc = T.get(ctx, &d_read[f], n * 4)) || (rc = T.get(ctx, &d_grpidx[f], n * 4)))
             return rc;
         if (!n_al[f]) continue;
-        spans.begin(SPAN_COMPACT);
+        if ((rc = spans.begin(SPAN_COMPACT))) return rc;
         hipLaunchKernelGGL(k_rec_compact, dim3((n_rec[f] + 255u) / 256u), dim3(256), 0, st, n_rec[f], R[f], (const u32 *)d_rank[f], f == 0 ? 0ull : n0,
                            (u32)f, (u32 *)d_flags[f], (u32 *)d_start[f], (u32 *)d_refid[f], (u64 *)d_end[f], (u64 *)d_ids, (u64 *)d_status);
-        spans.end();
+        if ((rc = spans.end())) return rc;
     }
     PP_HIPCHK(ctx, hipGetLastError());
     u64 status = ~0ull;
@@ -267,7 +224,7 @@ extern "C" int pp_filter_records(pp_ctx *ctx, const pp_raw_batch raw[2], int mem
     if ((rc = T.get(ctx, &d_slots, (size_t)cap * 4)) || (rc = T.get(ctx, &d_rep, N * 4)) || (rc = T.get(ctx, &d_isrep, N * 4)) ||
         (rc = T.get(ctx, &d_idscan, (N + 1) * 4)))
         return rc;
-    spans.begin(SPAN_INTERN);
+    if ((rc = spans.begin(SPAN_INTERN))) return rc;
     PP_HIPCHK(ctx, hipMemsetAsync(d_slots, 0, (size_t)cap * 4, st));
     {
         const unsigned gb = (unsigned)((N + 255) / 256);
@@ -275,18 +232,18 @@ extern "C" int pp_filter_records(pp_ctx *ctx, const pp_raw_batch raw[2], int mem
         hipLaunchKernelGGL(k_rid_find, dim3(gb), dim3(256), 0, st, N, (const u64 *)d_ids, (const u32 *)d_slots, cap - 1, (u32 *)d_rep, (u32 *)d_isrep);
         if ((rc = scan_u32<u32>(ctx, T.sums(), T.sums_off(), (const u32 *)d_isrep, N, (u32 *)d_idscan))) return rc;
     }
-    spans.end();
+    if ((rc = spans.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     u32 ids_f1 = 0, n_reads = 0, shared = 0;
     if ((rc = fetch(ctx, (const u32 *)d_idscan + n0, &ids_f1)) || (rc = fetch(ctx, (const u32 *)d_idscan + N, &n_reads))) return rc;
     if (n1) {  // ids of file 2 that file 1 holds as well (file 2's count of distinct ids)
         void *d_hit, *d_hitscan;
         if ((rc = T.get(ctx, &d_hit, n0 * 4)) || (rc = T.get(ctx, &d_hitscan, (n0 + 1) * 4))) return rc;
-        spans.begin(SPAN_INTERN);
+        if ((rc = spans.begin(SPAN_INTERN))) return rc;
         PP_HIPCHK(ctx, hipMemsetAsync(d_hit, 0, n0 * 4, st));
         hipLaunchKernelGGL(k_mark_shared, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, st, n0, N, (const u32 *)d_rep, (u32 *)d_hit);
         if ((rc = scan_u32<u32>(ctx, T.sums(), T.sums_off(), (const u32 *)d_hit, n0, (u32 *)d_hitscan))) return rc;
-        spans.end();
+        if ((rc = spans.end())) return rc;
         if ((rc = fetch(ctx, (const u32 *)d_hitscan + n0, &shared))) return rc;
     }
     counts[0].reads = ids_f1;
@@ -297,14 +254,14 @@ extern "C" int pp_filter_records(pp_ctx *ctx, const pp_raw_batch raw[2], int mem
     // ---- read numbers and the per-file groups in file order ----
     void *d_cursor;
     if ((rc = T.get(ctx, &d_cursor, (size_t)n_reads * 4))) return rc;
-    spans.begin(SPAN_GROUPS);
+    if ((rc = spans.begin(SPAN_GROUPS))) return rc;
     for (int f = 0; f < 2; f++) {
         if ((rc = T.get(ctx, &d_grpoff[f], ((size_t)n_reads + 1) * 4))) return rc;
         if ((rc = file_groups(ctx, n_al[f], f == 0 ? 0ull : n0, n_reads, (const u32 *)d_rep, (const u32 *)d_idscan, (const u32 *)nullptr, (u32 *)d_read[f],
                               (u32 *)nullptr, (u32 *)d_cursor, (u32 *)d_grpoff[f], (u32 *)d_grpidx[f], T.sums(), T.sums_off())))
             return rc;
     }
-    spans.end();
+    if ((rc = spans.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
 
     // ---- the filter itself ----
@@ -329,6 +286,14 @@ extern "C" int pp_filter_records(pp_ctx *ctx, const pp_raw_batch raw[2], int mem
     if ((rc = pp_filter_pairs(ctx, report->low_threshold, report->high_threshold, (uint8_t)report->orientation, pass1, pass2))) return rc;
     for (int f = 0; f < 2; f++)
         for (u64 i = 0; i < n_al[f]; i++) report->after_count += pass[f][i] != 0;
-    if (ctx->profiling) spans.add_to(&ctx->last_times);
+    if (spans.on) {  // (the stream has been synchronised)
+        float ms[3];
+        if ((rc = spans.sums(ms, 3))) return rc;
+        pp_kernel_times &t = ctx->last_times;
+        for (int k = 0; k < 3 && t.n < PP_MAX_KERNELS; k++) {
+            t.name[t.n] = SPAN_NAME[k];
+            t.ms[t.n++] = ms[k];
+        }
+    }
     return PP_OK;
 }

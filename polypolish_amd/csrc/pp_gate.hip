@@ -7,8 +7,8 @@
 // the arrays of a pp_raw_batch, for a caller who parses SAM or BAM itself, holds an aligner's output, or comes out of seam A.
 // All of it is work per RECORD -- a read of thousands of alignments (all hits in a repeat) is no lane's loop:
 //   k_gate_aligned   rank of every record among the aligned ones (FLAG & 4 takes part in nothing): the workgroups' sums, a scan of
-//                    them, then the list rec_of[aligned rank] = raw index.  Every scan here is the DPP wave scan (pp_wave.h) with
-//                    a carry per workgroup through LDS
+//                    them, then the list rec_of[aligned rank] = raw index.  Every scan here is one of pp_dev.h's: the DPP wave
+//                    scan with a carry per workgroup through LDS, k_tscan / k_colscan over the workgroups' sums
 //   k_gate_groups    a record opens a group when its read_id differs from the aligned record in front: group of every record,
 //                    first record of every group, the same two passes
 //   k_gate_judge     the contract (SEQ / CIGAR range inside the arrays, before anything is read through it), the empty CIGAR,
@@ -23,10 +23,7 @@
 //                    the record's CIGAR runs.
 // The first failing group in file order wins (atomicMin on the raw index of the group's first record << 8 | kind, as the polish
 // reports its first offending record).
-#include "pp_devtext.h"
-#include "pp_wave.h"
-
-#include <vector>
+#include "pp_dev.h"
 
 struct pp_gated {
     pp_ctx *ctx = nullptr;
@@ -60,44 +57,6 @@ struct GateOut {
     u64 *seq_off, *cig_off, *desc;  // desc: where the source has the record's bytes | GATE_RC
 };
 
-// does [off, off + len) lie inside an array of `size` elements?  (no sum that could wrap)
-__device__ __forceinline__ bool inside(u64 off, u32 len, u64 size) { return off <= size && (u64)len <= size - off; }
-
-// Exclusive prefix of v over the workgroup's GATE_BLOCK threads (every thread calls it), *total = the workgroup's sum.
-__device__ __forceinline__ u32 block_scan_excl(u32 v, u32 *s_w, u32 *total) {
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const u32 inc = pp::wave_scan_incl(v);
-    if (lane == 63u) s_w[wave] = inc;
-    __syncthreads();
-    u32 before = 0, sum = 0;
-#pragma unroll
-    for (u32 i = 0; i < GATE_BLOCK / 64u; i++) {
-        const u32 w = s_w[i];
-        before += i < wave ? w : 0u;
-        sum += w;
-    }
-    __syncthreads();  // (s_w is used again)
-    *total = sum;
-    return before + inc - v;
-}
-// ... of values whose sum over a workgroup does not fit 32 bits (rooms, CIGAR runs): the two halves scanned apart
-__device__ __forceinline__ u64 block_scan_excl64(u32 v, u64 *s_w, u64 *total) {
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const u64 inc = ((u64)pp::wave_scan_incl(v >> 16) << 16) + (u64)pp::wave_scan_incl(v & 0xFFFFu);
-    if (lane == 63u) s_w[wave] = inc;
-    __syncthreads();
-    u64 before = 0, sum = 0;
-#pragma unroll
-    for (u32 i = 0; i < GATE_BLOCK / 64u; i++) {
-        const u64 w = s_w[i];
-        before += i < wave ? w : 0ull;
-        sum += w;
-    }
-    __syncthreads();
-    *total = sum;
-    return before + inc - (u64)v;
-}
-
 // blk_off == nullptr: the workgroups' numbers of aligned records; else rec_of[aligned rank] = raw index
 __global__ __launch_bounds__(GATE_BLOCK) void k_gate_aligned(u32 n_rec, const uint16_t *__restrict__ flag, const u32 *__restrict__ blk_off,
                                                              u32 *__restrict__ blk_sum, u32 *__restrict__ rec_of) {
@@ -105,7 +64,7 @@ __global__ __launch_bounds__(GATE_BLOCK) void k_gate_aligned(u32 n_rec, const ui
     const u64 r = (u64)blockIdx.x * GATE_BLOCK + threadIdx.x;
     const u32 al = (r < n_rec && !(flag[r] & 4u)) ? 1u : 0u;
     u32 total;
-    const u32 ex = block_scan_excl(al, s_w, &total);
+    const u32 ex = block_scan_excl<GATE_BLOCK>(al, s_w, &total);
     if (!blk_off) {
         if (threadIdx.x == 0) blk_sum[blockIdx.x] = total;
         return;
@@ -121,7 +80,7 @@ __global__ __launch_bounds__(GATE_BLOCK) void k_gate_groups(u32 n_al, const u32 
     const u64 a = (u64)blockIdx.x * GATE_BLOCK + threadIdx.x;
     const u32 start = (a < n_al && (a == 0 || read_id[rec_of[a]] != read_id[rec_of[a - 1]])) ? 1u : 0u;
     u32 total;
-    const u32 ex = block_scan_excl(start, s_w, &total);
+    const u32 ex = block_scan_excl<GATE_BLOCK>(start, s_w, &total);
     if (!blk_off) {
         if (threadIdx.x == 0) blk_sum[blockIdx.x] = total;
         return;
@@ -212,14 +171,14 @@ __global__ __launch_bounds__(GATE_BLOCK) void k_gate_place(u32 n_al, GateRaw R, 
                 src_a = g_src[g];
                 if (src_a != GATE_NONE) sl = R.seq_len[rec_of[src_a]];
             }
-            units = (u32)(((u64)sl + (u64)PP_SEQ_ALIGN - 1u) / (u64)PP_SEQ_ALIGN);
+            units = (u32)room_units(sl);
         }
     }
     u32 t_cnt;
     u64 t_units, t_cig;
-    const u32 ex_cnt = block_scan_excl(is_good, s_w, &t_cnt);
-    const u64 ex_units = block_scan_excl64(units, s_w64, &t_units);
-    const u64 ex_cig = block_scan_excl64(nc, s_w64, &t_cig);
+    const u32 ex_cnt = block_scan_excl<GATE_BLOCK>(is_good, s_w, &t_cnt);
+    const u64 ex_units = block_scan_excl64<GATE_BLOCK>(units, s_w64, &t_units);
+    const u64 ex_cig = block_scan_excl64<GATE_BLOCK>(nc, s_w64, &t_cig);
     u64 *const mine = blk3 + 3ull * blockIdx.x;
     if (!PLACE) {
         if (threadIdx.x == 0) { mine[0] = t_cnt; mine[1] = t_units; mine[2] = t_cig; }
@@ -240,34 +199,6 @@ __global__ __launch_bounds__(GATE_BLOCK) void k_gate_place(u32 n_al, GateRaw R, 
     O.desc[o] = R.seq_off[rs] | (rc ? GATE_RC : 0ull);
 }
 
-// exclusive scan of the workgroups' three sums, column by column (one workgroup; out: nb + 1 rows)
-__global__ __launch_bounds__(1024) void k_gate_scan3(const u64 *__restrict__ in, u64 nb, u64 *__restrict__ out) {
-    __shared__ u64 part[1024];
-    const u32 t = threadIdx.x;
-    const u64 per = (nb + 1023) / 1024;
-    const u64 lo = min(nb, (u64)t * per), hi = min(nb, lo + per);
-    for (u32 c = 0; c < 3u; c++) {
-        u64 s = 0;
-        for (u64 i = lo; i < hi; i++) s += in[3 * i + c];
-        part[t] = s;
-        __syncthreads();
-        for (u32 off = 1; off < 1024; off <<= 1) {
-            const u64 v = (t >= off) ? part[t - off] : 0;
-            __syncthreads();
-            part[t] += v;
-            __syncthreads();
-        }
-        u64 run = part[t] - s;
-        for (u64 i = lo; i < hi; i++) {
-            const u64 v = in[3 * i + c];
-            out[3 * i + c] = run;
-            run += v;
-        }
-        if (t == 1023) out[3 * nb + c] = part[1023];
-        __syncthreads();
-    }
-}
-
 // upper-cases the four ASCII bytes of a word: bit 7 of every byte in 'a'..'z', shifted down to the 0x20 that is taken off
 __device__ __forceinline__ u32 upper4(u32 w) {
     const u32 x = w & 0x7F7F7F7Fu;
@@ -286,7 +217,7 @@ __global__ __launch_bounds__(256) void k_gate_seq(u32 n_good, const u32 *__restr
     const u32 s = (u32)t & 7u;
     if ((t >> 3) >= n_good) return;
     const u32 o = (u32)(t >> 3);
-    const u64 n = seq_len[o], room = (n + (u64)PP_SEQ_ALIGN - 1u) & ~((u64)PP_SEQ_ALIGN - 1u);
+    const u64 n = seq_len[o], room = room_bytes(n);
     const u64 d = desc[o], at0 = d & ~GATE_RC;
     const bool rc = (d & GATE_RC) != 0;
     u8 *const out = seq + seq_off[o];  // a multiple of PP_SEQ_ALIGN
@@ -320,17 +251,6 @@ __global__ __launch_bounds__(256) void k_gate_seq(u32 n_good, const u32 *__restr
     u32 *const cd = cigar + cig_off[o];
     for (u32 j = s; j < nc; j += 8u) cd[j] = cs[j];
 }
-
-struct Scratch {  // device memory of one call, released when it returns
-    std::vector<void *> p;
-    ~Scratch() { for (void *q : p) (void)hipFree(q); }
-    int get(pp_ctx *ctx, void **out, size_t bytes) {
-        *out = nullptr;
-        PP_HIPCHK(ctx, hipMalloc(out, bytes ? bytes : 16));
-        p.push_back(*out);
-        return PP_OK;
-    }
-};
 
 }  // namespace
 
@@ -385,69 +305,43 @@ extern "C" int pp_batch_gate(pp_ctx *ctx, const pp_raw_batch *raw, int mem, uint
 
     pp_gated *P = new pp_gated;
     P->ctx = ctx;
-    struct Guard {  // (every early return releases what was made so far)
-        pp_gated *p;
-        ~Guard() { if (p) pp_gated_free(p); }
-    } guard{P};
+    std::unique_ptr<pp_gated, void (*)(pp_gated *)> guard(P, pp_gated_free);  // (every early return releases what was made so far)
     // a batch without aligned records gates to an empty batch -- unless it came with verdicts for records it does not have
     auto empty = [&]() -> int {
         PP_HIPCHK(ctx, hipStreamSynchronize(st));
         if (pass && n_pass != 0)
             return ctx->fail(PP_ERR_ARG, "pp_batch_gate: %llu filter verdicts for 0 aligned records", (unsigned long long)n_pass);
-        guard.p = nullptr;
+        guard.release();
         *out = P;
         return PP_OK;
     };
     if (n_rec == 0) return empty();
 
-    Scratch T;
+    CallScratch T;
+    StageTimer timer(ctx, ctx->profiling != 0);
     int rc;
     // ---- the source on the device ----
     GateRaw R{};
     R.seq_bytes = raw->seq_bytes;
     R.n_cig_total = raw->n_cig_total;
-    if (mem == PP_MEM_HOST) {
-        const void *h[11] = {raw->flag, raw->read_id, raw->contig, raw->ref_start, raw->nm, raw->seq_off, raw->seq_len, raw->cig_off, raw->n_cig,
-                             raw->seq, raw->cigar};
-        const size_t bytes[11] = {(size_t)n_rec * 2, (size_t)n_rec * 8, (size_t)n_rec * 4, (size_t)n_rec * 4, (size_t)n_rec * 4, (size_t)n_rec * 8,
-                                  (size_t)n_rec * 4, (size_t)n_rec * 8, (size_t)n_rec * 4, (size_t)raw->seq_bytes, (size_t)raw->n_cig_total * 4};
-        void *dv[11];
-        for (int i = 0; i < 11; i++) {
-            if ((rc = T.get(ctx, &dv[i], bytes[i]))) return rc;
-            if (bytes[i]) PP_HIPCHK(ctx, hipMemcpyAsync(dv[i], h[i], bytes[i], hipMemcpyHostToDevice, st));
-        }
-        R.flag = (const uint16_t *)dv[0]; R.read_id = (const u64 *)dv[1]; R.contig = (const u32 *)dv[2]; R.ref_start = (const u32 *)dv[3];
-        R.nm = (const u32 *)dv[4]; R.seq_off = (const u64 *)dv[5]; R.seq_len = (const u32 *)dv[6]; R.cig_off = (const u64 *)dv[7];
-        R.n_cig = (const u32 *)dv[8]; R.seq = (const u8 *)dv[9]; R.cigar = (const u32 *)dv[10];
-    } else {
-        R.flag = raw->flag; R.read_id = (const u64 *)raw->read_id; R.contig = raw->contig; R.ref_start = raw->ref_start; R.nm = raw->nm;
-        R.seq_off = (const u64 *)raw->seq_off; R.seq_len = raw->seq_len; R.cig_off = (const u64 *)raw->cig_off; R.n_cig = raw->n_cig;
-        R.seq = raw->seq; R.cigar = raw->cigar;
-    }
-
-    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    struct Events {
-        hipEvent_t *e;
-        ~Events() { for (int i = 0; i < 8; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
-    } events{ev};
-    const bool timed = ctx->profiling != 0;
-    if (timed)
-        for (int i = 0; i < 8; i++) PP_HIPCHK(ctx, hipEventCreate(&ev[i]));
-    auto mark = [&](int i) -> int {
-        if (timed) PP_HIPCHK(ctx, hipEventRecord(ev[i], st));
-        return PP_OK;
-    };
+    if ((rc = on_device(ctx, T, mem, raw->flag, n_rec, &R.flag)) || (rc = on_device(ctx, T, mem, (const u64 *)raw->read_id, n_rec, &R.read_id)) ||
+        (rc = on_device(ctx, T, mem, raw->contig, n_rec, &R.contig)) || (rc = on_device(ctx, T, mem, raw->ref_start, n_rec, &R.ref_start)) ||
+        (rc = on_device(ctx, T, mem, raw->nm, n_rec, &R.nm)) || (rc = on_device(ctx, T, mem, (const u64 *)raw->seq_off, n_rec, &R.seq_off)) ||
+        (rc = on_device(ctx, T, mem, raw->seq_len, n_rec, &R.seq_len)) || (rc = on_device(ctx, T, mem, (const u64 *)raw->cig_off, n_rec, &R.cig_off)) ||
+        (rc = on_device(ctx, T, mem, raw->n_cig, n_rec, &R.n_cig)) || (rc = on_device(ctx, T, mem, raw->seq, (size_t)raw->seq_bytes, &R.seq)) ||
+        (rc = on_device(ctx, T, mem, raw->cigar, (size_t)raw->n_cig_total, &R.cigar)))
+        return rc;
 
     // ---- the aligned records ----
     const u32 nb_r = (n_rec + GATE_BLOCK - 1u) / GATE_BLOCK;
     void *d_blk, *d_blkoff, *d_rec_of;
     if ((rc = T.get(ctx, &d_blk, (size_t)nb_r * 4)) || (rc = T.get(ctx, &d_blkoff, ((size_t)nb_r + 1) * 4)) || (rc = T.get(ctx, &d_rec_of, (size_t)n_rec * 4)))
         return rc;
-    if ((rc = mark(0))) return rc;
+    if ((rc = timer.begin(0))) return rc;
     hipLaunchKernelGGL(k_gate_aligned, dim3(nb_r), dim3(GATE_BLOCK), 0, st, n_rec, R.flag, (const u32 *)nullptr, (u32 *)d_blk, (u32 *)nullptr);
     hipLaunchKernelGGL(k_tscan<u32>, dim3(1), dim3(1024), 0, st, (const u32 *)d_blk, (u64)nb_r, (u32 *)d_blkoff);
     hipLaunchKernelGGL(k_gate_aligned, dim3(nb_r), dim3(GATE_BLOCK), 0, st, n_rec, R.flag, (const u32 *)d_blkoff, (u32 *)d_blk, (u32 *)d_rec_of);
-    if ((rc = mark(1))) return rc;
+    if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     u32 n_al = 0;
     if ((rc = fetch(ctx, (const u32 *)d_blkoff + nb_r, &n_al))) return rc;
@@ -456,17 +350,15 @@ extern "C" int pp_batch_gate(pp_ctx *ctx, const pp_raw_batch *raw, int mem, uint
     // ---- groups, gates, sums ----
     const u32 nb = (n_al + GATE_BLOCK - 1u) / GATE_BLOCK;
     const u64 n_pass_dev = pass ? std::min<u64>(n_pass, n_al) : 0;
-    void *d_gblk, *d_gblkoff, *d_grp_of, *d_grp_first, *d_good, *d_gcnt, *d_gsrc, *d_pass = nullptr, *d_blk3, *d_blk3off, *d_status;
+    void *d_gblk, *d_gblkoff, *d_grp_of, *d_grp_first, *d_good, *d_gcnt, *d_gsrc, *d_blk3, *d_blk3off, *d_status;
+    const u8 *d_pass = nullptr;  // (the verdicts are host memory whatever the batch is)
     if ((rc = T.get(ctx, &d_gblk, (size_t)nb * 4)) || (rc = T.get(ctx, &d_gblkoff, ((size_t)nb + 1) * 4)) || (rc = T.get(ctx, &d_grp_of, (size_t)n_al * 4)) ||
         (rc = T.get(ctx, &d_grp_first, ((size_t)n_al + 1) * 4)) || (rc = T.get(ctx, &d_good, (size_t)n_al)) || (rc = T.get(ctx, &d_gcnt, (size_t)n_al * 4)) ||
         (rc = T.get(ctx, &d_gsrc, (size_t)n_al * 4)) || (rc = T.get(ctx, &d_blk3, (size_t)nb * 24)) || (rc = T.get(ctx, &d_blk3off, ((size_t)nb + 1) * 24)) ||
         (rc = T.get(ctx, &d_status, 16)))
         return rc;
-    if (pass) {
-        if ((rc = T.get(ctx, &d_pass, (size_t)n_pass_dev))) return rc;
-        if (n_pass_dev) PP_HIPCHK(ctx, hipMemcpyAsync(d_pass, pass, (size_t)n_pass_dev, hipMemcpyHostToDevice, st));
-    }
-    if ((rc = mark(2))) return rc;
+    if (pass && (rc = on_device(ctx, T, PP_MEM_HOST, pass, (size_t)n_pass_dev, &d_pass))) return rc;
+    if ((rc = timer.begin(0))) return rc;
     PP_HIPCHK(ctx, hipMemsetAsync(d_gcnt, 0, (size_t)n_al * 4, st));
     PP_HIPCHK(ctx, hipMemsetAsync(d_gsrc, 0xFF, (size_t)n_al * 4, st));
     PP_HIPCHK(ctx, hipMemsetAsync(d_status, 0xFF, 16, st));
@@ -476,14 +368,14 @@ extern "C" int pp_batch_gate(pp_ctx *ctx, const pp_raw_batch *raw, int mem, uint
     hipLaunchKernelGGL(k_gate_groups, dim3(nb), dim3(GATE_BLOCK), 0, st, n_al, (const u32 *)d_rec_of, R.read_id, (const u32 *)d_gblkoff, (u32 *)d_gblk,
                        (u32 *)d_grp_of, (u32 *)d_grp_first);
     hipLaunchKernelGGL(k_gate_judge, dim3((n_al + 255u) / 256u), dim3(256), 0, st, n_al, R, (const u32 *)d_rec_of, (const u32 *)d_grp_of,
-                       (const u32 *)d_grp_first, (u32)max_errors, careful ? 1 : 0, (const u8 *)d_pass, n_pass_dev, (u8 *)d_good, (u32 *)d_gcnt,
+                       (const u32 *)d_grp_first, (u32)max_errors, careful ? 1 : 0, d_pass, n_pass_dev, (u8 *)d_good, (u32 *)d_gcnt,
                        (u32 *)d_gsrc, (u64 *)d_status);
     GateOut O{};
     hipLaunchKernelGGL(k_gate_place<false>, dim3(nb), dim3(GATE_BLOCK), 0, st, n_al, R, (const u32 *)d_rec_of, (const u32 *)d_grp_of,
                        (const u32 *)d_grp_first, (const u8 *)d_good, (const u32 *)d_gcnt, (const u32 *)d_gsrc, careful ? 1 : 0, (u64 *)d_blk3, O,
                        (u64 *)d_status);
-    hipLaunchKernelGGL(k_gate_scan3, dim3(1), dim3(1024), 0, st, (const u64 *)d_blk3, (u64)nb, (u64 *)d_blk3off);
-    if ((rc = mark(3))) return rc;
+    hipLaunchKernelGGL(k_colscan<3>, dim3(1), dim3(1024), 0, st, (const u64 *)d_blk3, (u64)nb, (u64 *)d_blk3off);
+    if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     u64 status[2] = {~0ull, ~0ull}, totals[3] = {0, 0, 0};
     u32 n_groups = 0;
@@ -521,29 +413,21 @@ extern "C" int pp_batch_gate(pp_ctx *ctx, const pp_raw_batch *raw, int mem, uint
     if ((rc = T.get(ctx, &d_desc, (size_t)n_good * 8))) return rc;
     O = GateOut{(u32 *)P->d[0], (u32 *)P->d[1], (u32 *)P->d[2], (u32 *)P->d[4], (u32 *)P->d[6], (u32 *)P->d[9], (u64 *)P->d[3], (u64 *)P->d[5],
                 (u64 *)d_desc};
-    if ((rc = mark(4))) return rc;
+    if ((rc = timer.begin(1))) return rc;
     if (n_good)
         hipLaunchKernelGGL(k_gate_place<true>, dim3(nb), dim3(GATE_BLOCK), 0, st, n_al, R, (const u32 *)d_rec_of, (const u32 *)d_grp_of,
                            (const u32 *)d_grp_first, (const u8 *)d_good, (const u32 *)d_gcnt, (const u32 *)d_gsrc, careful ? 1 : 0, (u64 *)d_blk3off, O,
                            (u64 *)d_status);
-    if ((rc = mark(5))) return rc;
-    if ((rc = mark(6))) return rc;
+    if ((rc = timer.end()) || (rc = timer.begin(2))) return rc;
     if (n_good)
         hipLaunchKernelGGL(k_gate_seq, dim3((unsigned)(((u64)n_good * 8u + 255u) / 256u)), dim3(256), 0, st, n_good, (const u32 *)P->d[4],
                            (const u64 *)P->d[3], (const u64 *)d_desc, (const u32 *)P->d[6], (const u64 *)P->d[5], (const u32 *)P->d[9], R.cig_off,
                            R.cigar, R.seq, R.seq_bytes, (u8 *)P->d[7], (u32 *)P->d[8]);
-    if ((rc = mark(7))) return rc;
+    if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     PP_HIPCHK(ctx, hipStreamSynchronize(st));  // the source may be released, the scratch goes away
-    if (timed) {
-        float a = 0.f, b = 0.f, c = 0.f, d = 0.f;
-        PP_HIPCHK(ctx, hipEventElapsedTime(&a, ev[0], ev[1]));
-        PP_HIPCHK(ctx, hipEventElapsedTime(&b, ev[2], ev[3]));
-        PP_HIPCHK(ctx, hipEventElapsedTime(&c, ev[4], ev[5]));
-        PP_HIPCHK(ctx, hipEventElapsedTime(&d, ev[6], ev[7]));
-        P->ms[0] = a + b;
-        P->ms[1] = c;
-        P->ms[2] = d;
+    if (timer.on) {
+        if ((rc = timer.sums(P->ms, 3))) return rc;
         P->timed = true;
     }
     pp_aln_batch &V = P->view;
@@ -553,7 +437,7 @@ extern "C" int pp_batch_gate(pp_ctx *ctx, const pp_raw_batch *raw, int mem, uint
     V.seq_bytes = total;
     V.cigar = (const u32 *)P->d[8];
     V.n_cig_total = n_cig_out;
-    guard.p = nullptr;
+    guard.release();
     *out = P;
     return PP_OK;
 }

@@ -15,16 +15,13 @@
 //                 candidate cannot be mistaken; a miss equals no resident name and skips those without a look at their bytes).
 //                 The bytes compared are the caller's.  Every miss notes the slot its name ended in.
 //   k_nm_rank     a miss whose slot holds its own index is a new representative.  Their ranks -- new id = count + rank -- and
-//                 the places of their bytes in the pool (a multiple of 8 each) by the DPP wave scan of pp_wave.h with a carry per
-//                 workgroup; second pass: the pool's entries, the slots pointed at the ids
+//                 the places of their bytes in the pool (a multiple of 8 each) by the workgroup scan of pp_dev.h and
+//                 k_colscan over the workgroups' sums; second pass: the pool's entries, the slots pointed at the ids
 //   k_nm_copy     eight lanes per new name: its bytes into the pool, zeros up to the next multiple of 8
 //   k_nm_out      the ids, 64 and 32 bits wide
 // No byte outside [0, n_bytes) is loaded: an 8-byte load is issued only where the array has eight bytes left, the last bytes of
 // the array are read byte by byte.  Bytes behind a name are masked off before they reach the hash or a comparison.
-#include "pp_devtext.h"
-#include "pp_wave.h"
-
-#include <vector>
+#include "pp_dev.h"
 
 namespace {
 
@@ -48,9 +45,6 @@ struct NmSrc {  // the caller's names (device memory)
     const u64 *off;
     const u32 *len;
 };
-
-// does [off, off + len) lie inside an array of `size` elements?  (no sum that could wrap; as pp_gate.hip)
-__device__ __forceinline__ bool inside(u64 off, u32 len, u64 size) { return off <= size && (u64)len <= size - off; }
 
 // The `live` (1..8) bytes at p + at as a little-endian word, zeros above them.  [at, at + live) lies inside [0, size): one
 // 8-byte load at any alignment where the array has eight bytes left, else -- the array's last seven bytes -- byte by byte.
@@ -166,25 +160,6 @@ __global__ __launch_bounds__(256) void k_nm_insert(u32 n, NmSrc S, const u32 *__
     slot_of[i] = s;
 }
 
-// Exclusive prefix of v over the workgroup's NM_BLOCK threads (every thread calls it), *total = the workgroup's sum; v = hi << 16 |
-// lo scanned as two halves, so that sums past 32 bits (the pool's words) hold.  As block_scan_excl64 of pp_gate.hip.
-__device__ __forceinline__ u64 block_scan_excl64(u32 v, u64 *s_w, u64 *total) {
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const u64 inc = ((u64)pp::wave_scan_incl(v >> 16) << 16) + (u64)pp::wave_scan_incl(v & 0xFFFFu);
-    if (lane == 63u) s_w[wave] = inc;
-    __syncthreads();
-    u64 before = 0, sum = 0;
-#pragma unroll
-    for (u32 i = 0; i < NM_BLOCK / 64u; i++) {
-        const u64 w = s_w[i];
-        before += i < wave ? w : 0ull;
-        sum += w;
-    }
-    __syncthreads();  // (s_w is used again)
-    *total = sum;
-    return before + inc - (u64)v;
-}
-
 // PLACE == false: rep[] of every miss, and the workgroups' numbers of new representatives and of their pool words (blk2: two
 // words per workgroup).  PLACE == true: blk2 holds their exclusive scan; every new representative gets its id and its entry,
 // its slot is pointed at the id, found[] of it becomes the id and src_of[rank] its index.
@@ -206,8 +181,8 @@ __global__ __launch_bounds__(NM_BLOCK) void k_nm_rank(u32 n, NmSrc S, const u32 
         }
     }
     u64 t_cnt, t_words;
-    const u64 ex_cnt = block_scan_excl64(is_rep, s_w, &t_cnt);
-    const u64 ex_words = block_scan_excl64(words, s_w, &t_words);
+    const u64 ex_cnt = block_scan_excl64<NM_BLOCK>(is_rep, s_w, &t_cnt);
+    const u64 ex_words = block_scan_excl64<NM_BLOCK>(words, s_w, &t_words);
     u64 *const mine = blk2 + 2ull * blockIdx.x;
     if (!PLACE) {
         if (threadIdx.x == 0) { mine[0] = t_cnt; mine[1] = t_words; }
@@ -219,34 +194,6 @@ __global__ __launch_bounds__(NM_BLOCK) void k_nm_rank(u32 n, NmSrc S, const u32 
     slots[slot_of[i]] = id + 1u;
     found[i] = id;
     src_of[rank] = (u32)i;
-}
-
-// exclusive scan of the workgroups' two sums, column by column (one workgroup; out: nb + 1 rows)
-__global__ __launch_bounds__(1024) void k_nm_scan2(const u64 *__restrict__ in, u64 nb, u64 *__restrict__ out) {
-    __shared__ u64 part[1024];
-    const u32 t = threadIdx.x;
-    const u64 per = (nb + 1023) / 1024;
-    const u64 lo = min(nb, (u64)t * per), hi = min(nb, lo + per);
-    for (u32 c = 0; c < 2u; c++) {
-        u64 s = 0;
-        for (u64 i = lo; i < hi; i++) s += in[2 * i + c];
-        part[t] = s;
-        __syncthreads();
-        for (u32 off = 1; off < 1024; off <<= 1) {
-            const u64 v = (t >= off) ? part[t - off] : 0;
-            __syncthreads();
-            part[t] += v;
-            __syncthreads();
-        }
-        u64 run = part[t] - s;
-        for (u64 i = lo; i < hi; i++) {
-            const u64 v = in[2 * i + c];
-            out[2 * i + c] = run;
-            run += v;
-        }
-        if (t == 1023) out[2 * nb + c] = part[1023];
-        __syncthreads();
-    }
 }
 
 // the table as it was: the slots of the call's new representatives emptied again (the table would pass its limit)
@@ -286,45 +233,26 @@ struct pp_names {
     u64 cap = 0, count = 0, pool_used = 0;
     // scratch of a call (grow-only): hash found rep src_of | slot_of | blk2 blk2off | status | a host array's copies
     pp::DevBuf hash, found, rep, src_of, slot_of, blk2, blk2off, status, up_bytes, up_off, up_len, dn64, dn32;
-    std::vector<hipEvent_t> ev;  // pairs around the last call's kernels ...
-    std::vector<int> ev_stage;   // ... and the stage each pair belongs to
     bool timed = false;
-    float ms[NM_STAGES] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    float ms[NM_STAGES] = {0.f, 0.f, 0.f, 0.f, 0.f};  // the last call's kernels by stage
 };
 
 namespace {
 
-void names_events_release(pp_names *T) {
-    for (hipEvent_t e : T->ev) (void)hipEventDestroy(e);
-    T->ev.clear();
-    T->ev_stage.clear();
-}
-
-// every span is two marks with its stage
-int names_mark(pp_names *T, bool timed, int stage) {
-    if (!timed) return PP_OK;
-    hipEvent_t e = nullptr;
-    PP_HIPCHK(T->ctx, hipEventCreate(&e));
-    T->ev.push_back(e);
-    T->ev_stage.push_back(stage);
-    PP_HIPCHK(T->ctx, hipEventRecord(e, T->ctx->stream));
-    return PP_OK;
-}
-
 // the table with room for `need` distinct names at no more than half its slots
-int names_reserve(pp_names *T, u64 need, bool timed) {
+int names_reserve(pp_names *T, u64 need, StageTimer &timer) {
     pp_ctx *ctx = T->ctx;
     u64 cap = T->cap;
     while (2 * need > cap) cap <<= 1;
     if (cap == T->cap) return PP_OK;
     pp::DevBuf grown;
     if (int rc = pp::dev_ensure(ctx, grown, (size_t)cap * 4)) return rc;
-    if (int rc = names_mark(T, timed, NM_T_REHASH)) return rc;
+    if (int rc = timer.begin(NM_T_REHASH)) return rc;
     PP_HIPCHK(ctx, hipMemsetAsync(grown.p, 0, (size_t)cap * 4, ctx->stream));
     if (T->count)
         hipLaunchKernelGGL(k_nm_rehash, dim3((unsigned)((T->count + 255) / 256)), dim3(256), 0, ctx->stream, (u32)T->count,
                            (const NmEntry *)T->entries.p, (u32 *)grown.p, cap - 1);
-    if (int rc = names_mark(T, timed, NM_T_REHASH)) return rc;
+    if (int rc = timer.end()) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     PP_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     pp::dev_free(T->slots);
@@ -335,7 +263,7 @@ int names_reserve(pp_names *T, u64 need, bool timed) {
 
 // One pass over the kernels: n <= NM_CHUNK names in device memory (base: the index of the chunk's first name in the call, for *bad).
 // The table's room is reserved for every miss as if it were a new name: known before the first slot is written.
-int names_chunk(pp_names *T, NmSrc S, u32 n, u64 base, u64 *id64, u32 *id32, bool timed, uint64_t *bad) {
+int names_chunk(pp_names *T, NmSrc S, u32 n, u64 base, u64 *id64, u32 *id32, StageTimer &timer, uint64_t *bad) {
     pp_ctx *ctx = T->ctx;
     hipStream_t st = ctx->stream;
     int rc;
@@ -351,10 +279,10 @@ int names_chunk(pp_names *T, NmSrc S, u32 n, u64 base, u64 *id64, u32 *id32, boo
     PP_HIPCHK(ctx, hipMemsetAsync(d_status + 1, 0, 8, st));
 
     // ---- among the resident names ----
-    if ((rc = names_mark(T, timed, NM_T_LOOKUP))) return rc;
+    if ((rc = timer.begin(NM_T_LOOKUP))) return rc;
     hipLaunchKernelGGL(k_nm_lookup, dim3(std::min(g256, NM_LOOKUP_BLOCKS)), dim3(256), 0, st, n, S, base, (const u32 *)T->slots.p, T->cap - 1,
                        (const NmEntry *)T->entries.p, (const u8 *)T->pool.p, d_hash, d_found, d_status);
-    if ((rc = names_mark(T, timed, NM_T_LOOKUP))) return rc;
+    if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     u64 status[2];
     if ((rc = fetch(ctx, d_status, status, 2))) return rc;
@@ -367,16 +295,16 @@ int names_chunk(pp_names *T, NmSrc S, u32 n, u64 base, u64 *id64, u32 *id32, boo
 
     if (n_miss) {
         // ---- the misses: candidates, representatives, ranks ----
-        if ((rc = names_reserve(T, std::min<u64>(T->count + n_miss, NM_MAX_NAMES), timed))) return rc;
+        if ((rc = names_reserve(T, std::min<u64>(T->count + n_miss, NM_MAX_NAMES), timer))) return rc;
         u32 *const d_slots = (u32 *)T->slots.p;
         const u32 count = (u32)T->count;
-        if ((rc = names_mark(T, timed, NM_T_INSERT))) return rc;
+        if ((rc = timer.begin(NM_T_INSERT))) return rc;
         hipLaunchKernelGGL(k_nm_insert, dim3(g256), dim3(256), 0, st, n, S, (const u32 *)d_hash, (const u32 *)d_found, d_slots, T->cap - 1, count,
                            d_slot_of);
         hipLaunchKernelGGL(k_nm_rank<false>, dim3(nb), dim3(NM_BLOCK), 0, st, n, S, (const u32 *)d_hash, d_found, d_slots, (const u64 *)d_slot_of,
                            count, T->pool_used, d_rep, (u64 *)T->blk2.p, (NmEntry *)nullptr, (u32 *)nullptr);
-        hipLaunchKernelGGL(k_nm_scan2, dim3(1), dim3(1024), 0, st, (const u64 *)T->blk2.p, (u64)nb, (u64 *)T->blk2off.p);
-        if ((rc = names_mark(T, timed, NM_T_INSERT))) return rc;
+        hipLaunchKernelGGL(k_colscan<2>, dim3(1), dim3(1024), 0, st, (const u64 *)T->blk2.p, (u64)nb, (u64 *)T->blk2off.p);
+        if ((rc = timer.end())) return rc;
         PP_HIPCHK(ctx, hipGetLastError());
         u64 totals[2];
         if ((rc = fetch(ctx, (const u64 *)T->blk2off.p + 2ull * nb, totals, 2))) return rc;
@@ -392,18 +320,18 @@ int names_chunk(pp_names *T, NmSrc S, u32 n, u64 base, u64 *id64, u32 *id32, boo
             (rc = pp::dev_grow_keep(ctx, T->pool, (size_t)(T->pool_used + new_bytes), (size_t)T->pool_used)))
             return rc;
         NmEntry *const d_entries = (NmEntry *)T->entries.p;
-        if ((rc = names_mark(T, timed, NM_T_PLACE))) return rc;
+        if ((rc = timer.begin(NM_T_PLACE))) return rc;
         hipLaunchKernelGGL(k_nm_rank<true>, dim3(nb), dim3(NM_BLOCK), 0, st, n, S, (const u32 *)d_hash, d_found, d_slots, (const u64 *)d_slot_of, count,
                            T->pool_used, d_rep, (u64 *)T->blk2off.p, d_entries, d_src_of);
         hipLaunchKernelGGL(k_nm_copy, dim3((unsigned)((n_new * 8u + 255u) / 256u)), dim3(256), 0, st, (u32)n_new, S, (const u32 *)d_src_of,
                            (const NmEntry *)(d_entries + count), (u8 *)T->pool.p);
-        if ((rc = names_mark(T, timed, NM_T_PLACE))) return rc;
+        if ((rc = timer.end())) return rc;
         T->count += n_new;
         T->pool_used += new_bytes;
     }
-    if ((rc = names_mark(T, timed, NM_T_OUT))) return rc;
+    if ((rc = timer.begin(NM_T_OUT))) return rc;
     hipLaunchKernelGGL(k_nm_out, dim3(g256), dim3(256), 0, st, n, (const u32 *)d_found, (const u32 *)d_rep, id64, id32);
-    if ((rc = names_mark(T, timed, NM_T_OUT))) return rc;
+    if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     return PP_OK;
 }
@@ -419,10 +347,7 @@ extern "C" int pp_names_create(pp_ctx *ctx, uint64_t expect, pp_names **out) {
     pp_names *T = new pp_names;
     T->ctx = ctx;
     T->device = ctx->device;
-    struct Guard {
-        pp_names *p;
-        ~Guard() { if (p) pp_names_free(p); }
-    } guard{T};
+    std::unique_ptr<pp_names, void (*)(pp_names *)> guard(T, pp_names_free);
     T->cap = NM_MIN_SLOTS;
     const u64 want = std::min<u64>(expect, NM_MAX_NAMES);
     while (2 * want > T->cap) T->cap <<= 1;
@@ -431,7 +356,7 @@ extern "C" int pp_names_create(pp_ctx *ctx, uint64_t expect, pp_names **out) {
         return rc;
     PP_HIPCHK(ctx, hipMemsetAsync(T->slots.p, 0, (size_t)T->cap * 4, ctx->stream));
     PP_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    guard.p = nullptr;
+    guard.release();
     *out = T;
     return PP_OK;
 }
@@ -439,7 +364,6 @@ extern "C" int pp_names_create(pp_ctx *ctx, uint64_t expect, pp_names **out) {
 extern "C" void pp_names_free(pp_names *T) {
     if (!T) return;
     (void)hipSetDevice(T->device);  // (every call ends with the stream synchronised: nothing of the table's is in flight)
-    names_events_release(T);
     pp::DevBuf *all[] = {&T->slots, &T->entries, &T->pool, &T->hash, &T->found, &T->rep, &T->src_of, &T->slot_of, &T->blk2, &T->blk2off,
                          &T->status, &T->up_bytes, &T->up_off, &T->up_len, &T->dn64, &T->dn32};
     for (pp::DevBuf *b : all) pp::dev_free(*b);
@@ -492,8 +416,7 @@ extern "C" int pp_names_ids(pp_names *T, const uint8_t *bytes, uint64_t n_bytes,
     if (n >= 0xFFFFFFFFull) return ctx->fail(PP_ERR_LIMIT, "pp_names_ids: 2^32-1 or more names in one call");
     PP_HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const bool timed = ctx->profiling != 0;
-    names_events_release(T);
+    StageTimer timer(ctx, ctx->profiling != 0);
     T->timed = false;
     int rc;
 
@@ -515,9 +438,9 @@ extern "C" int pp_names_ids(pp_names *T, const uint8_t *bytes, uint64_t n_bytes,
     if (n > NM_CHUNK) {  // several chunks: every range before the first of them reaches the table
         if ((rc = pp::dev_ensure(ctx, T->status, 16))) return rc;
         PP_HIPCHK(ctx, hipMemsetAsync(T->status.p, 0xFF, 8, st));
-        if ((rc = names_mark(T, timed, NM_T_LOOKUP))) return rc;
+        if ((rc = timer.begin(NM_T_LOOKUP))) return rc;
         hipLaunchKernelGGL(k_nm_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, S, (u64 *)T->status.p);
-        if ((rc = names_mark(T, timed, NM_T_LOOKUP))) return rc;
+        if ((rc = timer.end())) return rc;
         PP_HIPCHK(ctx, hipGetLastError());
         u64 first = ~0ull;
         if ((rc = fetch(ctx, T->status.p, &first))) return rc;
@@ -533,7 +456,7 @@ extern "C" int pp_names_ids(pp_names *T, const uint8_t *bytes, uint64_t n_bytes,
         NmSrc C = S;
         C.off += done;
         C.len += done;
-        if ((rc = names_chunk(T, C, (u32)m, done, d64 ? d64 + done : nullptr, d32 ? d32 + done : nullptr, timed, bad))) return rc;
+        if ((rc = names_chunk(T, C, (u32)m, done, d64 ? d64 + done : nullptr, d32 ? d32 + done : nullptr, timer, bad))) return rc;
         done += m;
     }
     if (mem == PP_MEM_HOST) {
@@ -541,13 +464,8 @@ extern "C" int pp_names_ids(pp_names *T, const uint8_t *bytes, uint64_t n_bytes,
         if (id32) PP_HIPCHK(ctx, hipMemcpyAsync(id32, T->dn32.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     }
     PP_HIPCHK(ctx, hipStreamSynchronize(st));  // the caller's arrays may be released
-    if (timed) {
-        for (float &m : T->ms) m = 0.f;
-        for (size_t i = 0; i + 1 < T->ev.size(); i += 2) {
-            float ms = 0.f;
-            PP_HIPCHK(ctx, hipEventElapsedTime(&ms, T->ev[i], T->ev[i + 1]));
-            T->ms[T->ev_stage[i]] += ms;
-        }
+    if (timer.on) {
+        if ((rc = timer.sums(T->ms, NM_STAGES))) return rc;
         T->timed = true;
     }
     return PP_OK;

@@ -23,10 +23,8 @@
 // position's alignments by file index -- which the entries carry -- so a batch of two SAM files needs no runs of its own.
 // Nothing is validated that the polish reports later: the call only has to be memory-safe, and a record it cannot read keeps
 // a seq_off outside the prepared array, so that pp_polish_finish names it exactly as on the plain batch.
-#include "pp_devtext.h"
+#include "pp_dev.h"
 #include "pp_wo_home.h"
-
-#include <vector>
 
 struct pp_prepared {
     pp_ctx *ctx = nullptr;
@@ -62,9 +60,6 @@ struct PrepOut {
     u64 *src_off, *dst_pos;  // per mirror entry: where the source has the record's bytes (PREP_NO_SRC: nowhere) | where its room starts
 };
 
-// does [so, so + sl) lie inside the source's seq array?  (no sum that could wrap)
-__device__ __forceinline__ bool seq_inside(u64 so, u32 sl, u64 seq_bytes) { return so <= seq_bytes && (u64)sl <= seq_bytes - so; }
-
 __global__ __launch_bounds__(256) void k_prep_home(u32 n, const u32 *__restrict__ contig, const u32 *__restrict__ ref_start,
                                                    const u64 *__restrict__ seq_off, const u32 *__restrict__ seq_len,
                                                    const u64 *__restrict__ contig_off, u32 n_contigs, u32 n_win, u64 seq_bytes,
@@ -79,7 +74,7 @@ __global__ __launch_bounds__(256) void k_prep_home(u32 n, const u32 *__restrict_
         // (a contig index out of range has no home: with the last window)
         win[r] = c < n_contigs ? pp::wo_home(contig_off[c], ref_start[r], n_win) : n_win - 1u;
         const u32 sl = seq_len[r];
-        if (seq_inside(seq_off[r], sl, seq_bytes)) u = ((u64)sl + (u64)PP_SEQ_ALIGN - 1u) / (u64)PP_SEQ_ALIGN;
+        if (inside(seq_off[r], sl, seq_bytes)) u = room_units(sl);
         units[r] = (u32)u;  // (<= 2^27)
     }
     for (int o = 32; o > 0; o >>= 1) u += (u64)__shfl_down((long long)u, o, 64);
@@ -164,18 +159,18 @@ __device__ __forceinline__ void prep_place_one(u64 r, u32 w, u64 old, const u64 
     const u64 pos = (wbase[w] + (old & PREP_UNITS_MASK)) * (u64)PP_SEQ_ALIGN;
     const u32 contig = S.contig[r], ref_start = S.ref_start[r], k = S.k[r], sl = S.seq_len[r], nc = S.n_cig[r];
     const u64 so = S.seq_off[r], co = S.cig_off[r];
-    const bool inside = seq_inside(so, sl, S.seq_bytes);
+    const bool readable = inside(so, sl, S.seq_bytes);
     // A record that cannot be read stays unreadable: beyond 2^40 where it was (the polish reports the overflow), else ending
     // exactly at 2^40 -- outside any prepared array, whatever is appended in front of it (it reports the range)
     const bool beyond = so > (1ull << 40) || so + sl > (1ull << 40);
-    const u64 new_so = inside ? pos : (beyond ? so : (1ull << 40) - sl);
+    const u64 new_so = readable ? pos : (beyond ? so : (1ull << 40) - sl);
     const u32 op0 = (nc == 1u && co < S.n_cig_total) ? S.cigar[co] : (u32)PP_WO_MULTI_RUN;
     O.contig[r] = contig; O.ref_start[r] = ref_start; O.k[r] = k; O.seq_len[r] = sl; O.n_cig[r] = nc;
     O.seq_off[r] = new_so; O.cig_off[r] = co;
     uint4 *const e = (uint4 *)(O.wo + slot);
     e[0] = make_uint4(contig, ref_start, k, sl);
     e[1] = make_uint4((u32)new_so, (u32)(new_so >> 32), op0, (u32)r);
-    O.src_off[slot] = (inside && sl) ? so : PREP_NO_SRC;
+    O.src_off[slot] = (readable && sl) ? so : PREP_NO_SRC;
     O.dst_pos[slot] = pos;
 }
 
@@ -220,7 +215,7 @@ __global__ __launch_bounds__(256) void k_prep_copy(u32 n, const pp_wo_rec *__res
         const u32 len = wo[e0 + t].seq_len;
         const u64 so = src_off[e0 + t], dp = dst_pos[e0 + t];
         s_len[t] = len; s_src[t] = so; s_dst[t] = dp;
-        if (t == cnt - 1u) s_dst[cnt] = dp + (so == PREP_NO_SRC ? 0ull : (((u64)len + (u64)PP_SEQ_ALIGN - 1u) & ~((u64)PP_SEQ_ALIGN - 1u)));
+        if (t == cnt - 1u) s_dst[cnt] = dp + (so == PREP_NO_SRC ? 0ull : room_bytes(len));
     }
     __syncthreads();
     const u64 d0 = s_dst[0], n_chunks = (s_dst[cnt] - d0) >> 4;
@@ -254,17 +249,6 @@ __global__ __launch_bounds__(256) void k_prep_copy(u32 n, const pp_wo_rec *__res
         *(uint2 *)(seq4 + (d >> 1)) = pack4_16(w);
     }
 }
-
-struct Scratch {  // device memory of one call, released when it returns
-    std::vector<void *> p;
-    ~Scratch() { for (void *q : p) (void)hipFree(q); }
-    int get(pp_ctx *ctx, void **out, size_t bytes) {
-        *out = nullptr;
-        PP_HIPCHK(ctx, hipMalloc(out, bytes ? bytes : 16));
-        p.push_back(*out);
-        return PP_OK;
-    }
-};
 
 }  // namespace
 
@@ -314,43 +298,31 @@ extern "C" int pp_batch_prepare(pp_ctx *ctx, uint32_t n_contigs, const uint64_t 
 
     pp_prepared *P = new pp_prepared;
     P->ctx = ctx;
-    struct Guard {  // (every early return releases what was made so far)
-        pp_prepared *p;
-        ~Guard() { if (p) pp_prepared_free(p); }
-    } guard{P};
+    std::unique_ptr<pp_prepared, void (*)(pp_prepared *)> guard(P, pp_prepared_free);  // (every early return releases what was made so far)
     pp_aln_batch &V = P->view;
     V.n_aln = n;
     V.n_cig_total = b->n_cig_total;
     if (n == 0) {  // an empty batch prepares to an empty batch
         PP_HIPCHK(ctx, hipStreamSynchronize(st));
-        guard.p = nullptr;
+        guard.release();
         *out = P;
         return PP_OK;
     }
 
-    Scratch T;
+    CallScratch T;
+    StageTimer timer(ctx, ctx->profiling != 0);
     int rc;
     // ---- the source on the device ----
     PrepSrc S{};
     S.seq_bytes = b->seq_bytes;
     S.n_cig_total = b->n_cig_total;
-    const u8 *src_seq = b->seq;
-    if (mem == PP_MEM_HOST) {
-        const void *h[9] = {b->contig, b->ref_start, b->k, b->seq_off, b->seq_len, b->cig_off, b->n_cig, b->seq, b->cigar};
-        const size_t bytes[9] = {(size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)n * 8, (size_t)n * 4, (size_t)n * 8, (size_t)n * 4,
-                                 (size_t)b->seq_bytes, (size_t)b->n_cig_total * 4};
-        void *dv[9];
-        for (int i = 0; i < 9; i++) {
-            if ((rc = T.get(ctx, &dv[i], bytes[i]))) return rc;
-            if (bytes[i]) PP_HIPCHK(ctx, hipMemcpyAsync(dv[i], h[i], bytes[i], hipMemcpyHostToDevice, st));
-        }
-        S.contig = (const u32 *)dv[0]; S.ref_start = (const u32 *)dv[1]; S.k = (const u32 *)dv[2]; S.seq_off = (const u64 *)dv[3];
-        S.seq_len = (const u32 *)dv[4]; S.cig_off = (const u64 *)dv[5]; S.n_cig = (const u32 *)dv[6]; src_seq = (const u8 *)dv[7];
-        S.cigar = (const u32 *)dv[8];
-    } else {
-        S.contig = b->contig; S.ref_start = b->ref_start; S.k = b->k; S.seq_off = (const u64 *)b->seq_off; S.seq_len = b->seq_len;
-        S.cig_off = (const u64 *)b->cig_off; S.n_cig = b->n_cig; S.cigar = b->cigar;
-    }
+    const u8 *src_seq;
+    if ((rc = on_device(ctx, T, mem, b->contig, n, &S.contig)) || (rc = on_device(ctx, T, mem, b->ref_start, n, &S.ref_start)) ||
+        (rc = on_device(ctx, T, mem, b->k, n, &S.k)) || (rc = on_device(ctx, T, mem, (const u64 *)b->seq_off, n, &S.seq_off)) ||
+        (rc = on_device(ctx, T, mem, b->seq_len, n, &S.seq_len)) || (rc = on_device(ctx, T, mem, (const u64 *)b->cig_off, n, &S.cig_off)) ||
+        (rc = on_device(ctx, T, mem, b->n_cig, n, &S.n_cig)) || (rc = on_device(ctx, T, mem, b->seq, (size_t)b->seq_bytes, &src_seq)) ||
+        (rc = on_device(ctx, T, mem, b->cigar, (size_t)b->n_cig_total, &S.cigar)))
+        return rc;
     // ---- the result's arrays (seq and seq4 once their size is known) ----
     const size_t obytes[11] = {(size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)n * 8, (size_t)n * 4, (size_t)n * 8, (size_t)n * 4, 0,
                                (size_t)b->n_cig_total * 4, 0, (size_t)n * sizeof(pp_wo_rec)};
@@ -375,16 +347,7 @@ extern "C" int pp_batch_prepare(pp_ctx *ctx, uint32_t n_contigs, const uint64_t 
     PrepOut O{(u32 *)P->d[0], (u32 *)P->d[1], (u32 *)P->d[2], (u32 *)P->d[4], (u32 *)P->d[6], (u64 *)P->d[3], (u64 *)P->d[5],
               (pp_wo_rec *)P->d[10], (u64 *)d_src, (u64 *)d_dst};
 
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    struct Events {
-        hipEvent_t *e;
-        ~Events() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); }
-    } events{ev};
-    const bool timed = ctx->profiling != 0;
-    if (timed) {
-        for (int i = 0; i < 4; i++) PP_HIPCHK(ctx, hipEventCreate(&ev[i]));
-        PP_HIPCHK(ctx, hipEventRecord(ev[0], st));
-    }
+    if ((rc = timer.begin(0))) return rc;
     // ---- placement ----
     const unsigned g256 = (unsigned)(((u64)n + 255u) / 256u);
     hipLaunchKernelGGL(k_prep_home, dim3(g256), dim3(256), 0, st, n, S.contig, S.ref_start, S.seq_off, S.seq_len, (const u64 *)d_cofs, n_contigs,
@@ -409,7 +372,7 @@ extern "C" int pp_batch_prepare(pp_ctx *ctx, uint32_t n_contigs, const uint64_t 
     else
         hipLaunchKernelGGL(k_prep_place_g, dim3(g256), dim3(256), 0, st, (const u32 *)d_win, (const u32 *)d_units, n, (u64 *)d_mat, (const u64 *)d_wbase,
                            (const u32 *)d_wcbase, (const u32 *)d_flag, S, O);
-    if (timed) PP_HIPCHK(ctx, hipEventRecord(ev[1], st));
+    if ((rc = timer.end())) return rc;
     u64 word[2] = {0, 0};
     if ((rc = fetch(ctx, d_word, word, 2))) return rc;
     const u32 flag = (u32)word[1];
@@ -422,18 +385,15 @@ extern "C" int pp_batch_prepare(pp_ctx *ctx, uint32_t n_contigs, const uint64_t 
     PP_HIPCHK(ctx, hipMalloc(&P->d[9], (size_t)(total / 2) + 96));
     PP_HIPCHK(ctx, hipMemsetAsync((u8 *)P->d[7] + total, 0, 64, st));
     PP_HIPCHK(ctx, hipMemsetAsync((u8 *)P->d[9] + total / 2, 0, 96, st));
-    if (timed) PP_HIPCHK(ctx, hipEventRecord(ev[2], st));
+    if ((rc = timer.begin(0))) return rc;
     if (total)
         hipLaunchKernelGGL(k_prep_copy, dim3((unsigned)(((u64)n + PREP_COPY_E - 1u) / PREP_COPY_E)), dim3(256), 0, st, n, (const pp_wo_rec *)P->d[10],
                            (const u64 *)d_src, (const u64 *)d_dst, src_seq, (u64)b->seq_bytes, (u8 *)P->d[7], (u8 *)P->d[9]);
-    if (timed) PP_HIPCHK(ctx, hipEventRecord(ev[3], st));
+    if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     PP_HIPCHK(ctx, hipStreamSynchronize(st));  // the source may be released, the scratch goes away
-    if (timed) {
-        float a = 0.f, c = 0.f;
-        PP_HIPCHK(ctx, hipEventElapsedTime(&a, ev[0], ev[1]));
-        PP_HIPCHK(ctx, hipEventElapsedTime(&c, ev[2], ev[3]));
-        P->ms = a + c;
+    if (timer.on) {
+        if ((rc = timer.sums(&P->ms, 1))) return rc;
         P->timed = true;
     }
     V.contig = (const u32 *)P->d[0]; V.ref_start = (const u32 *)P->d[1]; V.k = (const u32 *)P->d[2]; V.seq_off = (const uint64_t *)P->d[3];
@@ -446,7 +406,7 @@ extern "C" int pp_batch_prepare(pp_ctx *ctx, uint32_t n_contigs, const uint64_t 
     V.wo_n_runs = 1;
     V.wo_run_end = P->run_end;
     pp_mirror_register_(P, V.wo, (size_t)n * sizeof(pp_wo_rec));  // one of the library's own: pp_polish_add takes it unchecked
-    guard.p = nullptr;
+    guard.release();
     *out = P;
     return PP_OK;
 }

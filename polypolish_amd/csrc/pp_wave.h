@@ -1,5 +1,5 @@
-// pp_wave.h -- the wave-wide scan shared by the polish kernels (pp_kernels.hip, through pp_k_common.h) and the record gate
-// (pp_gate.hip).  Device code only.
+// pp_wave.h -- the wave-wide scan shared by the polish kernels (pp_kernels.hip, through pp_k_common.h) and the workgroup scans of
+// pp_dev.h (the record chain: pp_bam.hip, pp_names.hip, pp_gate.hip).  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 

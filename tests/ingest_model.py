@@ -48,7 +48,7 @@ def staging(text):
     consecutive lines, its stretch starts at a0 = (start of its first line) & ~15, and a line is staged when
     end - a0 + 8 <= TOK_STAGE + 16."""
     # Nothing on the GPU can observe `staged`: that a case straddles the boundary rests on this restatement alone.  It follows
-    # pp_devtext.h -- tok_stage_for (:200-203), and in stage_wave_lines l0 / s0 / a0 (:209-212) and the predicate (:233) -- and,
+    # pp_devtext.h -- tok_stage_for (:121-124), and in stage_wave_lines l0 / s0 / a0 (:130-133) and the predicate (:154) -- and,
     # for split_blocks below, per_block / nb in ingest_text of pp_tokenize.hip.  Whoever changes those changes these.
     starts, ends = line_spans(text)
     n = len(ends)

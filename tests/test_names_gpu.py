@@ -179,6 +179,34 @@ def test_more_names_than_one_sweep_of_the_lookup_kernel(pp, ctx, source):
 
 
 @pytest.mark.parametrize("source", SOURCES)
+@pytest.mark.parametrize("n", (1023, 1024, 1025))
+def test_distinct_new_names_around_one_workgroup_of_the_rank_scan(pp, ctx, source, n):
+    # k_nm_rank ranks 1,024 names per workgroup (block_scan_excl64<NM_BLOCK>): the new representatives end one short of a
+    # workgroup, fill it, and reach into a second one whose base is the column scan's
+    call = nm.pack([b"seam_%d" % i for i in range(n)], lead=3)
+    (got, again), table = run(pp, ctx, [call, call], source)
+    try:
+        assert got.tolist() == list(range(n)) and table.count == n
+        assert np.array_equal(again, got)
+    finally:
+        table.close()
+
+
+@pytest.mark.parametrize("source", SOURCES)
+def test_more_workgroups_than_the_column_scan_has_threads(pp, ctx, source):
+    # 1,025 workgroups of k_nm_rank: the smallest call at which a thread of the one-workgroup column scan owns two rows of
+    # sums (and the threads from 513 on none)
+    call, want = nm.numbered_case(1024 * 1024 + 1, 300000)
+    table = pp.Names(ctx)
+    try:
+        got = query(pp, table, call, source)
+        assert np.array_equal(got, want) and table.count == int(want.max()) + 1
+        assert np.array_equal(query(pp, table, call, source), want) and table.count == int(want.max()) + 1
+    finally:
+        table.close()
+
+
+@pytest.mark.parametrize("source", SOURCES)
 def test_the_table_grows_and_the_ids_stay(pp, ctx, source):
     calls = [nm.pack(c, lead=1) for c in nm.growth_calls()]
     table, state = pp.Names(ctx, 0), {}

@@ -2,7 +2,7 @@
 """What pp_bam_records costs on a configs[1]-shaped input: the records of tools/synthjob.py's SAM pair (make_job(pairs=True): every
 record, the ones the gates reject and the unaligned ones too, secondary records with l_seq 0) encoded to uncompressed BAM bytes by
 a vectorised numpy encoder, one byte array per file, resident in HBM (an allocation of exactly its length).  Prints one JSON line:
-  pass_a_ms / scans_ms / pass_b_ms   HIP-event time of k_bam_scan | k_bam_place x 2 + k_bam_scan3 | k_bam_expand, summed over the two
+  pass_a_ms / scans_ms / pass_b_ms   HIP-event time of k_bam_scan | k_bam_place x 2 + k_colscan<3> | k_bam_expand, summed over the two
                  files (best of --repeat)
   bam_bytes      the bytes of the two arrays;  pass_a_gbps = bam_bytes over pass A's time (it touches every record, not every byte)
   pass_b_bytes   what pass B reads and writes: SEQ nibbles in, rooms out, CIGAR words both ways, 44 bytes of per-record arrays
