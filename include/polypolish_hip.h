@@ -314,9 +314,62 @@ int pp_names_name(const pp_names *t, uint64_t id, uint8_t *out, uint32_t cap, ui
 int pp_names_kernel_ms(const pp_names *t, float *ms);
 void pp_names_free(pp_names *t);
 
+/* IN FRONT of the BAM front end: the BGZF blocks of a file inflated on the device, so that a caller uploads a BAM file as it is on
+ * disk and every later byte is produced and consumed in device memory.  A BGZF block is a gzip member of at most 64 KiB on either
+ * side: 1f 8b 08, a FLG with FEXTRA, XLEN, extra subfields among which BC (SLEN 2) holds BSIZE = the block's size - 1, one raw DEFLATE
+ * stream with no dictionary from the block in front, CRC32 and ISIZE.
+ *   pp_bgzf_walk      HOST, no context: the twin of pp_bam_walk.  Follows the BSIZE chain from `from`: blk_off[b] = the block's offset,
+ *                     out_off[b] = the sum of the ISIZEs in front of it, *end = the first byte not consumed.  blk_off has `cap`
+ *                     entries, out_off (may be NULL) cap + 1: one more entry, the sum of all, follows the last block written.  The
+ *                     walk stops cleanly at n_bytes -- and, with an array to fill, after `cap` blocks.  blk_off == NULL or cap == 0 only
+ *                     counts, to the end.  Per block it checks 1f 8b 08 and FEXTRA; XLEN against the bytes; the subfields against
+ *                     XLEN, walking them for BC (it need not be the first); BSIZE + 1 >= header + 8; the block against n_bytes; ISIZE
+ *                     <= 65536.  The 28-byte EOF block (ISIZE 0) is an ordinary block.  Memory-safe for any bytes, no sum that could
+ *                     wrap.  A block that fails: PP_ERR_ARG, *n_blk = the blocks in front of it, *end = its offset, the message in
+ *                     pp_bam_last_error().
+ *   pp_bgzf_inflate   inflates the blocks at blk_off[0 .. n_blk) into one dense DEVICE array, in index order; they need not be
+ *                     adjacent, ordered or distinct (a region subset works).  mem = PP_MEM_HOST or PP_MEM_DEVICE holds for `bytes`
+ *                     and `blk_off`; with PP_MEM_HOST and blk_off == NULL the library runs pp_bgzf_walk from offset 0 itself (n_blk
+ *                     is ignored then).  The compressed device copy of host bytes is released before the call returns: the object
+ *                     owns the inflated bytes only.  Everything is validated on the device before anything is read through it,
+ *                     without sums that could wrap, and no byte outside [0, n_bytes) is ever loaded, by a wide load either: a
+ *                     PP_MEM_DEVICE array may end where its allocation ends.  Stored, fixed and dynamic DEFLATE blocks, any number
+ *                     per BGZF block; each block's produced length is checked against ISIZE and its CRC32 against the footer, on the
+ *                     device.  A malformed stream ends with an error, never with a write outside the block's own room.
+ *                     PP_ERR_ARG with *bad_block (may be NULL) = the first such block in index order, and no object: a blk_off or
+ *                     block outside the array, a header pp_bgzf_walk would refuse; block type 3; LEN != ~NLEN; code lengths that are
+ *                     over-subscribed, incomplete where zlib refuses that, overrun HLIT + HDIST, repeat a length that is not there or
+ *                     leave out the end-of-block code; a code that stands for nothing, length symbol 286 / 287, distance symbol 30 /
+ *                     31; a distance beyond the bytes produced so far; output longer or shorter than ISIZE; a stream that runs past
+ *                     the payload; a CRC32 that is not the footer's.  Also PP_ERR_ARG: null arguments, PP_MEM_PEER, blk_off == NULL
+ *                     with PP_MEM_DEVICE, a chain that pp_bgzf_walk refuses (*bad_block = the blocks in front).  PP_ERR_LIMIT: 2^32-1
+ *                     or more blocks.  n_blk == 0 inflates to an empty object.  The context's stream has been synchronised when
+ *                     the call returns: host inputs may be released.
+ *   pp_bgzf_bytes     the inflated bytes (DEVICE, borrowed until pp_bgzf_free): what pp_bam_records(..., PP_MEM_DEVICE, ...) takes.
+ *                     The BAM header is read with pp_ctx_download of a prefix plus pp_bam_header.
+ *   pp_bgzf_bam_walk  the block_size chain of the inflated bytes from `from`, for a caller with no HIP of its own: the record
+ *                     offsets end up in DEVICE memory owned by the object (pp_bgzf_rec_off: *n_rec entries, valid until the next
+ *                     pp_bgzf_bam_walk on the object or pp_bgzf_free).  TODAY this downloads the inflated bytes through a pinned
+ *                     staging buffer, runs pp_bam_walk on the host and uploads the offsets; a device walk can replace it behind
+ *                     this signature.  Its failure contract is pp_bam_walk's: PP_ERR_ARG, *n_rec = the records in front, *end =
+ *                     the offending offset, the message in pp_bam_last_error() (and pp_last_error).
+ *   pp_bgzf_kernel_ms HIP-event time of the object's stages so far: the headers, the scan and the inflate | the CRC32 | the copies of
+ *                     pp_bgzf_bam_walk's staging; PP_ERR_ARG unless the context had profiling on at pp_bgzf_inflate.
+ * The object belongs to its context and is freed before it. */
+int pp_bgzf_walk(const uint8_t *bytes, uint64_t n_bytes, uint64_t from, uint64_t *blk_off, uint64_t *out_off, uint64_t cap, uint64_t *n_blk,
+                 uint64_t *end); /* HOST, no context */
+typedef struct pp_bgzf pp_bgzf;
+int pp_bgzf_inflate(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, const uint64_t *blk_off, uint64_t n_blk, int mem, pp_bgzf **out,
+                    uint64_t *bad_block);
+void pp_bgzf_bytes(const pp_bgzf *z, const uint8_t **dev, uint64_t *n_bytes); /* borrowed view, DEVICE memory */
+int pp_bgzf_bam_walk(pp_bgzf *z, uint64_t from, uint64_t *n_rec, uint64_t *end); /* the block_size chain of the inflated bytes */
+const uint64_t *pp_bgzf_rec_off(const pp_bgzf *z);                               /* DEVICE, n_rec entries */
+int pp_bgzf_kernel_ms(const pp_bgzf *z, float *ms);
+void pp_bgzf_free(pp_bgzf *z);
+
 /* The FRONT END of the record chain for a caller who holds BAM: the alignment records of UNCOMPRESSED BAM bytes as a pp_raw_batch,
- * decoded on the device.  Inflating BGZF stays the caller's job (htslib, zlib); no command reads BAM: the reference reads SAM text
- * only, and so does the CLI.  A BAM CIGAR word is len << 4 | op with MIDNSHP=X -> 0..8, bit for bit pp_raw_batch.cigar; l_seq 0 is
+ * decoded on the device.  A file's BGZF blocks are inflated by pp_bgzf_inflate above, whose bytes go in here as PP_MEM_DEVICE; no
+ * command reads BAM: the reference reads SAM text only, and so does the CLI.  A BAM CIGAR word is len << 4 | op with MIDNSHP=X -> 0..8, bit for bit pp_raw_batch.cigar; l_seq 0 is
  * SEQ "*"; a record's read_name is an (off, len) range into the bytes, which is what pp_names_ids(..., PP_MEM_DEVICE) takes.
  *
  * Two HOST helpers need no device.  Both are memory-safe for any bytes, never read outside [0, n_bytes) and form no sum that could

@@ -198,6 +198,7 @@ EXPORTS = [
     "pp_names_create", "pp_names_ids", "pp_names_count", "pp_names_name", "pp_names_kernel_ms", "pp_names_free",
     "pp_bam_header", "pp_bam_walk", "pp_bam_last_error", "pp_bam_records", "pp_bam_raw", "pp_bam_read_id", "pp_bam_names", "pp_bam_pass",
     "pp_bam_kernel_ms", "pp_bam_free",
+    "pp_bgzf_walk", "pp_bgzf_inflate", "pp_bgzf_bytes", "pp_bgzf_bam_walk", "pp_bgzf_rec_off", "pp_bgzf_kernel_ms", "pp_bgzf_free",
 ]
 
 _lib = None
@@ -358,6 +359,16 @@ def lib():
         L.pp_bam_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.pp_bam_free.argtypes = [vp]
         L.pp_bam_free.restype = None
+        L.pp_bgzf_walk.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, u64p, u64p]
+        L.pp_bgzf_inflate.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.POINTER(vp), u64p]
+        L.pp_bgzf_bytes.argtypes = [vp, C.POINTER(vp), u64p]
+        L.pp_bgzf_bytes.restype = None
+        L.pp_bgzf_bam_walk.argtypes = [vp, C.c_uint64, u64p, u64p]
+        L.pp_bgzf_rec_off.argtypes = [vp]
+        L.pp_bgzf_rec_off.restype = vp
+        L.pp_bgzf_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.pp_bgzf_free.argtypes = [vp]
+        L.pp_bgzf_free.restype = None
         _lib = L
     return _lib
 
@@ -946,6 +957,105 @@ def bam_walk(data, start=0):
         if rc:
             raise PolypolishError(rc, L.pp_bam_last_error().decode())
     return off, int(end.value)
+
+
+def bgzf_walk(data, start=0):
+    """pp_bgzf_walk (no device needed): (blk_off, out_off, end) -- the offset of every BGZF block from `start` on, the sum of the
+    ISIZEs in front of every block (one more entry: the sum of all), and the first byte not consumed.  A chain that breaks raises
+    PolypolishError(ERR_ARG) with .n_blk = the blocks in front of the break and .end = its offset."""
+    L = lib()
+    b = _bam_bytes(data)
+    n, end = C.c_uint64(0), C.c_uint64(0)
+    bp = b.ctypes.data if len(b) else None
+    rc = L.pp_bgzf_walk(bp, len(b), int(start), None, None, 0, C.byref(n), C.byref(end))
+    if rc:
+        e = PolypolishError(rc, L.pp_bam_last_error().decode())
+        e.n_blk, e.end = int(n.value), int(end.value)
+        raise e
+    off, out = np.zeros(int(n.value), np.uint64), np.zeros(int(n.value) + 1, np.uint64)
+    if len(off):
+        rc = L.pp_bgzf_walk(bp, len(b), int(start), off.ctypes.data, out.ctypes.data, len(off), C.byref(n), C.byref(end))
+        if rc:
+            raise PolypolishError(rc, L.pp_bam_last_error().decode())
+    return off, out, int(end.value)
+
+
+class Bgzf:
+    """pp_bgzf_inflate: the BGZF blocks of a file inflated into one dense array in DEVICE memory, owned by this object.
+      data, blk_off  mem = MEM_HOST: bytes / a uint8 array, and the blocks' offsets (None: the library walks the chain from offset 0);
+                     MEM_DEVICE: data = (device address, n_bytes), blk_off = (device address of n uint64, n)
+      .n_bytes, .bytes_ptr   the inflated bytes: BamRecords(ctx, (z.bytes_ptr, z.n_bytes), (rec_off_ptr, n_rec), ref_map, mem=MEM_DEVICE)
+      .host(lo, hi)  a numpy copy of the inflated bytes [lo, hi) (a download)
+      .bam_walk(start)   pp_bgzf_bam_walk: (rec_off_ptr, n_rec, end); a chain that breaks raises with .n_rec and .end
+      .kernel_ms()   HIP-event time of the stages so far (the context had set_profiling on); .stage_ms(): inflate | crc | staging
+    A failing call raises PolypolishError with .bad_block."""
+
+    def __init__(self, ctx, data, blk_off=None, mem=MEM_HOST):
+        L = lib()
+        if mem == MEM_HOST:
+            b = _bam_bytes(data)
+            bp, n_bytes = (b.ctypes.data if len(b) else None), len(b)
+            o = None if blk_off is None else np.ascontiguousarray(blk_off, dtype=np.uint64)
+            n = 0 if o is None else len(o)
+            if o is not None and n == 0:
+                o = np.zeros(1, dtype=np.uint64)     # (an array without blocks still is one: no walk)
+            op = None if o is None else o.ctypes.data
+        else:
+            bp, n_bytes = int(data[0]), int(data[1])
+            op, n = (None, 0) if blk_off is None else (int(blk_off[0]), int(blk_off[1]))
+        self._p = C.c_void_p()
+        self._ctx = ctx
+        bad = C.c_uint64(0xFFFFFFFFFFFFFFFF)
+        rc = L.pp_bgzf_inflate(ctx._h, bp, n_bytes, op, n, mem, C.byref(self._p), C.byref(bad))
+        if rc:
+            e = PolypolishError(rc, L.pp_last_error(ctx._h).decode())
+            e.bad_block = None if bad.value == 0xFFFFFFFFFFFFFFFF else int(bad.value)
+            raise e
+        dev, nb = C.c_void_p(), C.c_uint64(0)
+        L.pp_bgzf_bytes(self._p, C.byref(dev), C.byref(nb))
+        self.bytes_ptr, self.n_bytes = dev.value or 0, int(nb.value)
+
+    def host(self, lo=0, hi=None):
+        hi = self.n_bytes if hi is None else min(int(hi), self.n_bytes)
+        lo = min(int(lo), hi)
+        arr = np.zeros(hi - lo, np.uint8)
+        if arr.size:
+            self._ctx._chk(lib().pp_ctx_download(self._ctx._h, arr.ctypes.data, self.bytes_ptr + lo, arr.nbytes))
+        return arr
+
+    def bam_walk(self, start=0):
+        L = lib()
+        n, end = C.c_uint64(0), C.c_uint64(0)
+        rc = L.pp_bgzf_bam_walk(self._p, int(start), C.byref(n), C.byref(end))
+        if rc:
+            e = PolypolishError(rc, L.pp_last_error(self._ctx._h).decode())
+            e.n_rec, e.end = int(n.value), int(end.value)
+            raise e
+        return L.pp_bgzf_rec_off(self._p) or 0, int(n.value), int(end.value)
+
+    def kernel_ms(self):
+        ms = C.c_float()
+        self._ctx._chk(lib().pp_bgzf_kernel_ms(self._p, C.byref(ms)))
+        return float(ms.value)
+
+    def stage_ms(self):
+        f = lib().pp_bgzf_stage_ms_
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        ms = (C.c_float * 3)()
+        if f(self._p, ms):
+            raise PolypolishError(ERR_ARG, "the context had no profiling on when the blocks were inflated")
+        return {"inflate": float(ms[0]), "crc": float(ms[1]), "staging": float(ms[2])}
+
+    def close(self):
+        if self._p:
+            lib().pp_bgzf_free(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class BamRecords:

@@ -1,5 +1,6 @@
 // pp_bam.hip -- pp_bam_records: the alignment records of UNCOMPRESSED BAM bytes as a pp_raw_batch, decoded on the device: the front
-// end of the record chain names -> filter -> gate -> prepare -> polish for a caller who holds BAM (inflating BGZF is the caller's).
+// end of the record chain names -> filter -> gate -> prepare -> polish for a caller who holds BAM (a file's BGZF blocks are inflated
+// on the device by pp_bgzf_inflate, pp_bgzf.hip, whose bytes this takes as PP_MEM_DEVICE).
 //
 // A BAM record is block_size (4 bytes) | the fixed part (32 bytes: refID pos l_read_name mapq bin n_cigar_op flag l_seq next_refID
 // next_pos tlen) | read_name (NUL-terminated) | n_cigar_op words len << 4 | op -- the packing of pp_raw_batch.cigar -- | (l_seq+1)/2
@@ -254,6 +255,12 @@ const char *defect_text(u32 code) {
 }  // namespace
 
 extern "C" const char *pp_bam_last_error(void) { return t_bam_msg; }
+
+// (internal hook, not part of the header: pp_bgzf.hip) the same per-thread message, for the host helpers of the BGZF block
+extern "C" char *pp_bam_msg_buf_(size_t *cap) {
+    *cap = sizeof t_bam_msg;
+    return t_bam_msg;
+}
 
 extern "C" int pp_bam_header(const uint8_t *bytes, uint64_t n_bytes, uint32_t cap, uint32_t *n_ref, uint64_t *name_off, uint32_t *name_len,
                              uint32_t *ref_len, uint64_t *records_at) {
