@@ -349,12 +349,11 @@ void pp_names_free(pp_names *t);
  *                     The BAM header is read with pp_ctx_download of a prefix plus pp_bam_header.
  *   pp_bgzf_bam_walk  the block_size chain of the inflated bytes from `from`, for a caller with no HIP of its own: the record
  *                     offsets end up in DEVICE memory owned by the object (pp_bgzf_rec_off: *n_rec entries, valid until the next
- *                     pp_bgzf_bam_walk on the object or pp_bgzf_free).  TODAY this downloads the inflated bytes through a pinned
- *                     staging buffer, runs pp_bam_walk on the host and uploads the offsets; a device walk can replace it behind
- *                     this signature.  Its failure contract is pp_bam_walk's: PP_ERR_ARG, *n_rec = the records in front, *end =
- *                     the offending offset, the message in pp_bam_last_error() (and pp_last_error).
- *   pp_bgzf_kernel_ms HIP-event time of the object's stages so far: the headers, the scan and the inflate | the CRC32 | the copies of
- *                     pp_bgzf_bam_walk's staging; PP_ERR_ARG unless the context had profiling on at pp_bgzf_inflate.
+ *                     pp_bgzf_bam_walk on the object or pp_bgzf_free).  It is pp_bam_walk_device (below) over the inflated bytes: no
+ *                     byte leaves device memory.  Its failure contract is pp_bam_walk's: PP_ERR_ARG, *n_rec = the records in
+ *                     front, *end = the offending offset, the message in pp_bam_last_error() (and pp_last_error).
+ *   pp_bgzf_kernel_ms HIP-event time of the object's stages so far: the headers, the scan and the inflate | the CRC32 | the kernels of
+ *                     pp_bgzf_bam_walk; PP_ERR_ARG unless the context had profiling on at pp_bgzf_inflate.
  * The object belongs to its context and is freed before it. */
 int pp_bgzf_walk(const uint8_t *bytes, uint64_t n_bytes, uint64_t from, uint64_t *blk_off, uint64_t *out_off, uint64_t cap, uint64_t *n_blk,
                  uint64_t *end); /* HOST, no context */
@@ -385,6 +384,25 @@ void pp_bgzf_free(pp_bgzf *z);
  *                  a record (its block_size word, too) that runs past n_bytes: PP_ERR_ARG, *n_rec = the records in front of it, *end
  *                  = its offset.  The chain is serial by the format, so it is walked on the host: a caller who inflates blocks meets
  *                  every block_size anyway.
+ *
+ * pp_bam_walk_device is the same walk ON THE DEVICE, to the end, for bytes that are (or belong) in device memory: *n_rec, *end and
+ * the offsets (pp_bam_offs_dev: DEVICE, *n_rec entries, what pp_bam_records(..., PP_MEM_DEVICE, ...) takes as rec_off) are exactly
+ * what pp_bam_walk yields on the same bytes from the same `from`.  The chain is serial only along the true chain: chunks of the bytes
+ * are walked from every offset at once, and the chunks are chained through a small entry zone each.
+ *   memory       mem = PP_MEM_HOST: the bytes are uploaded and the copy is released before the call returns; PP_MEM_DEVICE: they are
+ *                borrowed for the call only.  The object owns nothing but the offsets (16 bytes for no records).  The context's
+ *                stream has been synchronised when the call returns.
+ *   a break      a chain that pp_bam_walk refuses: PP_ERR_ARG, no object, *n_rec = the records in front of the break, *end = the
+ *                offending offset, pp_bam_last_error() = the very string pp_bam_walk leaves on these bytes (the bytes end inside a
+ *                block_size, block_size < 32, a record runs past the end, the start lies behind the bytes), and pp_last_error(ctx)
+ *                the same string behind "pp_bam_walk_device: ".
+ *   also         PP_ERR_ARG: null arguments, PP_MEM_PEER, null bytes with n_bytes > 0.  PP_ERR_LIMIT: 2^32-1 or more records (as
+ *                pp_bam_records), n_bytes >= 2^40.  from == n_bytes: no records, PP_OK.
+ *   safety       every length is compared with what is left, no sum can wrap, and no byte outside [0, n_bytes) is loaded, by a wide
+ *                load either: a device array may end where its allocation ends.  Bytes in front of `from` and bytes off the chain
+ *                are arbitrary: they are read as data only and can neither fault nor change the result.  Every loop is bounded by
+ *                n_bytes whatever the bytes hold.
+ * pp_bam_offs_kernel_ms: as pp_gated_kernel_ms.  The object belongs to its context and is freed before it.
  *
  * pp_bam_records decodes the records at rec_off[0 .. n_rec) -- they need not be adjacent, ordered or distinct (a region subset
  * works); output record r is input record r.
@@ -427,6 +445,13 @@ int pp_bam_header(const uint8_t *bytes, uint64_t n_bytes, uint32_t cap, uint32_t
                   uint32_t *ref_len, uint64_t *records_at);
 int pp_bam_walk(const uint8_t *bytes, uint64_t n_bytes, uint64_t from, uint64_t *rec_off, uint64_t cap, uint64_t *n_rec, uint64_t *end);
 const char *pp_bam_last_error(void);
+typedef struct pp_bam_offs pp_bam_offs;
+int pp_bam_walk_device(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, uint64_t from, int mem, pp_bam_offs **out, uint64_t *n_rec,
+                       uint64_t *end);
+const uint64_t *pp_bam_offs_dev(const pp_bam_offs *o); /* DEVICE, n_rec entries: what pp_bam_records(..., PP_MEM_DEVICE, ...) takes */
+uint64_t pp_bam_offs_count(const pp_bam_offs *o);
+int pp_bam_offs_kernel_ms(const pp_bam_offs *o, float *ms);
+void pp_bam_offs_free(pp_bam_offs *o);
 int pp_bam_records(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, const uint64_t *rec_off, uint64_t n_rec, int mem,
                    const uint32_t *ref_map, uint32_t n_ref, pp_bam **out, uint64_t *bad_record);
 void pp_bam_raw(const pp_bam *b, pp_raw_batch *out); /* borrowed view, DEVICE memory; out->read_id = the array below */

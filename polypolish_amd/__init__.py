@@ -198,6 +198,7 @@ EXPORTS = [
     "pp_names_create", "pp_names_ids", "pp_names_count", "pp_names_name", "pp_names_kernel_ms", "pp_names_free",
     "pp_bam_header", "pp_bam_walk", "pp_bam_last_error", "pp_bam_records", "pp_bam_raw", "pp_bam_read_id", "pp_bam_names", "pp_bam_pass",
     "pp_bam_kernel_ms", "pp_bam_free",
+    "pp_bam_walk_device", "pp_bam_offs_dev", "pp_bam_offs_count", "pp_bam_offs_kernel_ms", "pp_bam_offs_free",
     "pp_bgzf_walk", "pp_bgzf_inflate", "pp_bgzf_bytes", "pp_bgzf_bam_walk", "pp_bgzf_rec_off", "pp_bgzf_kernel_ms", "pp_bgzf_free",
 ]
 
@@ -359,6 +360,14 @@ def lib():
         L.pp_bam_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.pp_bam_free.argtypes = [vp]
         L.pp_bam_free.restype = None
+        L.pp_bam_walk_device.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(vp), u64p, u64p]
+        L.pp_bam_offs_dev.argtypes = [vp]
+        L.pp_bam_offs_dev.restype = vp
+        L.pp_bam_offs_count.argtypes = [vp]
+        L.pp_bam_offs_count.restype = C.c_uint64
+        L.pp_bam_offs_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        L.pp_bam_offs_free.argtypes = [vp]
+        L.pp_bam_offs_free.restype = None
         L.pp_bgzf_walk.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, u64p, u64p]
         L.pp_bgzf_inflate.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.POINTER(vp), u64p]
         L.pp_bgzf_bytes.argtypes = [vp, C.POINTER(vp), u64p]
@@ -959,6 +968,90 @@ def bam_walk(data, start=0):
     return off, int(end.value)
 
 
+class BamOffsets:
+    """pp_bam_walk_device: the block_size chain of uncompressed BAM bytes walked on the device; the offsets stay in DEVICE memory,
+    owned by this object.
+      data           mem = MEM_HOST: bytes / a uint8 array; MEM_DEVICE: (device address, n_bytes), borrowed for the call
+      .ptr, .n_rec   BamRecords(ctx, (bytes_ptr, n_bytes), (offs.ptr, offs.n_rec), ref_map, mem=MEM_DEVICE)
+      .end           the first byte not consumed
+      .host()        a numpy copy of the offsets (a download)
+      .kernel_ms()   HIP-event time of the walk's kernels (the context had set_profiling on); .stage_ms(): tables | chain | offsets
+      .stats()       along the true chain: {"chain": chunks on it, "zone": entered through a zone table, "slow": walked record by
+                     record behind a zone, "pass": passed through}
+    A chain that breaks raises PolypolishError(ERR_ARG) with .n_rec = the records in front of the break and .end = its offset, as
+    bam_walk does; the text behind "pp_bam_walk_device: " is bam_walk's."""
+
+    def __init__(self, ctx, data, start=0, mem=MEM_HOST):
+        L = lib()
+        if mem == MEM_HOST:
+            b = _bam_bytes(data)
+            bp, n_bytes = (b.ctypes.data if len(b) else None), len(b)
+        else:
+            bp, n_bytes = int(data[0]) or None, int(data[1])
+        self._p = C.c_void_p()
+        self._ctx = ctx
+        n, end = C.c_uint64(0), C.c_uint64(0)
+        rc = L.pp_bam_walk_device(ctx._h, bp, n_bytes, int(start), mem, C.byref(self._p), C.byref(n), C.byref(end))
+        if rc:
+            e = PolypolishError(rc, L.pp_last_error(ctx._h).decode())
+            e.n_rec, e.end = int(n.value), int(end.value)
+            raise e
+        self.ptr, self.n_rec, self.end = L.pp_bam_offs_dev(self._p) or 0, int(L.pp_bam_offs_count(self._p)), int(end.value)
+
+    def host(self):
+        arr = np.zeros(self.n_rec, np.uint64)
+        if arr.size:
+            self._ctx._chk(lib().pp_ctx_download(self._ctx._h, arr.ctypes.data, self.ptr, arr.nbytes))
+        return arr
+
+    def kernel_ms(self):
+        ms = C.c_float()
+        self._ctx._chk(lib().pp_bam_offs_kernel_ms(self._p, C.byref(ms)))
+        return float(ms.value)
+
+    def stage_ms(self):
+        f = lib().pp_bam_offs_stage_ms_
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        ms = (C.c_float * 3)()
+        if f(self._p, ms):
+            raise PolypolishError(ERR_ARG, "the context had no profiling on when the chain was walked")
+        return {"tables": float(ms[0]), "chain": float(ms[1]), "offsets": float(ms[2])}
+
+    def stats(self):
+        f = lib().pp_bam_offs_stats_
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        out = (C.c_uint64 * 4)()
+        if f(self._p, out):
+            raise PolypolishError(ERR_ARG, "pp_bam_offs_stats_: no object")
+        return {"chain": int(out[0]), "zone": int(out[1]), "slow": int(out[2]), "pass": int(out[3])}
+
+    def close(self):
+        if self._p:
+            lib().pp_bam_offs_free(self._p)
+            self._p = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bam_walk_device(ctx, data, start=0, mem=MEM_HOST):
+    """pp_bam_walk_device: -> BamOffsets"""
+    return BamOffsets(ctx, data, start, mem)
+
+
+def bam_walk_geometry():
+    """(bytes per chunk, offsets of a chunk's entry zone, chunks per group) of the device walk: the seams its tests are built on"""
+    f = lib().pp_bam_walk_geometry_
+    f.argtypes = [C.POINTER(C.c_uint32)] * 3
+    f.restype = None
+    c, z, g = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    f(C.byref(c), C.byref(z), C.byref(g))
+    return int(c.value), int(z.value), int(g.value)
+
+
 def bgzf_walk(data, start=0):
     """pp_bgzf_walk (no device needed): (blk_off, out_off, end) -- the offset of every BGZF block from `start` on, the sum of the
     ISIZEs in front of every block (one more entry: the sum of all), and the first byte not consumed.  A chain that breaks raises
@@ -987,7 +1080,8 @@ class Bgzf:
       .n_bytes, .bytes_ptr   the inflated bytes: BamRecords(ctx, (z.bytes_ptr, z.n_bytes), (rec_off_ptr, n_rec), ref_map, mem=MEM_DEVICE)
       .host(lo, hi)  a numpy copy of the inflated bytes [lo, hi) (a download)
       .bam_walk(start)   pp_bgzf_bam_walk: (rec_off_ptr, n_rec, end); a chain that breaks raises with .n_rec and .end
-      .kernel_ms()   HIP-event time of the stages so far (the context had set_profiling on); .stage_ms(): inflate | crc | staging
+      .kernel_ms()   HIP-event time of the stages so far (the context had set_profiling on); .stage_ms(): inflate | crc | walk (the
+                     kernels of .bam_walk; "staging" is the same value under its earlier name)
     A failing call raises PolypolishError with .bad_block."""
 
     def __init__(self, ctx, data, blk_off=None, mem=MEM_HOST):
@@ -1044,7 +1138,7 @@ class Bgzf:
         ms = (C.c_float * 3)()
         if f(self._p, ms):
             raise PolypolishError(ERR_ARG, "the context had no profiling on when the blocks were inflated")
-        return {"inflate": float(ms[0]), "crc": float(ms[1]), "staging": float(ms[2])}
+        return {"inflate": float(ms[0]), "crc": float(ms[1]), "staging": float(ms[2]), "walk": float(ms[2])}
 
     def close(self):
         if self._p:

@@ -4,8 +4,9 @@
 //
 // A BAM record is block_size (4 bytes) | the fixed part (32 bytes: refID pos l_read_name mapq bin n_cigar_op flag l_seq next_refID
 // next_pos tlen) | read_name (NUL-terminated) | n_cigar_op words len << 4 | op -- the packing of pp_raw_batch.cigar -- | (l_seq+1)/2
-// bytes of 4-bit SEQ | l_seq bytes QUAL | typed aux fields up to the block's end.  The block_size chain is serial by the format
-// and is walked on the host (pp_bam_walk, pp_bam_host.h); everything per record runs here:
+// bytes of 4-bit SEQ | l_seq bytes QUAL | typed aux fields up to the block's end.  The block_size chain is serial by the format:
+// it is walked on the host (pp_bam_walk, pp_bam_host.h) or, chunk by chunk, on the device (pp_bam_walk_device, pp_bam_walk.hip);
+// everything per record runs here:
 //   k_bam_scan     pass A, one lane per record: the record's range, its block_size against the lengths it declares, the name's NUL,
 //                  the CIGAR ops, the refID -- each checked before anything is read through it, none with a sum that could wrap --
 //                  then the fixed fields, the name's range and the walk over the aux fields for NM (last one wins, a negative one

@@ -25,7 +25,6 @@
 //                   of x^(2^k)), lane 0 compares with the footer.  A kernel of its own: its time is a stage of pp_bgzf_kernel_ms.
 // No byte outside [0, n_bytes) is loaded: a wide load is issued only where the payload has that many bytes left.
 #include "pp_bgzf_host.h"
-#include "pp_bam_host.h"
 #include "pp_dev.h"
 
 extern "C" char *pp_bam_msg_buf_(size_t *cap);  // pp_bam.hip: the per-thread message behind pp_bam_last_error()
@@ -34,10 +33,9 @@ struct pp_bgzf {
     pp_ctx *ctx = nullptr;
     void *d_out = nullptr;      // DEVICE: the inflated bytes
     uint64_t n_out = 0;
-    void *d_rec_off = nullptr;  // DEVICE: pp_bgzf_bam_walk's record offsets
-    uint64_t n_rec = 0;
+    pp_bam_offs *offs = nullptr;  // pp_bgzf_bam_walk's record offsets (DEVICE)
     bool timed = false;
-    float ms[3] = {0.f, 0.f, 0.f};  // header, scan and inflate | CRC | the staging of pp_bgzf_bam_walk
+    float ms[3] = {0.f, 0.f, 0.f};  // header, scan and inflate | CRC | the kernels of pp_bgzf_bam_walk
 };
 
 namespace {
@@ -459,14 +457,6 @@ const char *defect_text(u32 code) {
     }
 }
 
-void set_bam_msg(const char *msg) {
-    size_t cap = 0;
-    char *buf = pp_bam_msg_buf_(&cap);
-    snprintf(buf, cap, "%s", msg);
-}
-
-constexpr size_t STAGE_BYTES = 32u << 20;  // pinned staging of pp_bgzf_bam_walk's download
-
 }  // namespace
 
 extern "C" int pp_bgzf_walk(const uint8_t *bytes, uint64_t n_bytes, uint64_t from, uint64_t *blk_off, uint64_t *out_off, uint64_t cap,
@@ -481,7 +471,7 @@ extern "C" void pp_bgzf_free(pp_bgzf *z) {
     if (!z) return;
     if (z->ctx) (void)hipSetDevice(z->ctx->device);
     if (z->d_out) (void)hipFree(z->d_out);
-    if (z->d_rec_off) (void)hipFree(z->d_rec_off);
+    pp_bam_offs_free(z->offs);
     delete z;
 }
 
@@ -490,7 +480,7 @@ extern "C" void pp_bgzf_bytes(const pp_bgzf *z, const uint8_t **dev, uint64_t *n
     if (n_bytes) *n_bytes = z ? z->n_out : 0;
 }
 
-extern "C" const uint64_t *pp_bgzf_rec_off(const pp_bgzf *z) { return z ? (const uint64_t *)z->d_rec_off : nullptr; }
+extern "C" const uint64_t *pp_bgzf_rec_off(const pp_bgzf *z) { return z ? pp_bam_offs_dev(z->offs) : nullptr; }
 
 extern "C" int pp_bgzf_kernel_ms(const pp_bgzf *z, float *ms) {
     if (!z || !ms) return PP_ERR_ARG;
@@ -499,7 +489,7 @@ extern "C" int pp_bgzf_kernel_ms(const pp_bgzf *z, float *ms) {
     return PP_OK;
 }
 
-// (internal hook, not part of the header: tools/bgzf_timing.py) the same time by stage: header, scan and inflate | CRC | pp_bgzf_bam_walk's staging
+// (internal hook, not part of the header: tools/bgzf_timing.py) the same time by stage: header, scan and inflate | CRC | pp_bgzf_bam_walk's kernels
 extern "C" int pp_bgzf_stage_ms_(const pp_bgzf *z, float *ms3) {
     if (!z || !ms3 || !z->timed) return PP_ERR_ARG;
     for (int i = 0; i < 3; i++) ms3[i] = z->ms[i];
@@ -608,59 +598,21 @@ extern "C" int pp_bgzf_inflate(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_byt
     return PP_OK;
 }
 
-// Today: the inflated bytes come down through a pinned staging buffer, pp_bam_walk runs over them on the host, the offsets go up.
+// The device walk (pp_bam_walk.hip) over the inflated bytes: they stay where they are, the object keeps the offsets.
 extern "C" int pp_bgzf_bam_walk(pp_bgzf *z, uint64_t from, uint64_t *n_rec, uint64_t *end) {
     if (!z || !z->ctx) return PP_ERR_ARG;
     pp_ctx *ctx = z->ctx;
     if (n_rec) *n_rec = 0;
     if (end) *end = from;
     if (!n_rec || !end) return ctx->fail(PP_ERR_ARG, "pp_bgzf_bam_walk: null argument");
-    PP_HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    if (z->d_rec_off) {
-        PP_HIPCHK(ctx, hipFree(z->d_rec_off));
-        z->d_rec_off = nullptr;
-        z->n_rec = 0;
+    pp_bam_offs_free(z->offs);
+    z->offs = nullptr;
+    const int rc = pp_bam_walk_device(ctx, (const uint8_t *)z->d_out, z->n_out, from, PP_MEM_DEVICE, &z->offs, n_rec, end);
+    if (rc) {
+        const char *msg = pp_bam_last_error();
+        return rc == PP_ERR_ARG && msg[0] ? ctx->fail(rc, "pp_bgzf_bam_walk: %s", msg) : rc;  // (a chain that breaks: pp_bam_walk's words)
     }
-    StageTimer timer(ctx, z->timed);
-    int rc;
-    std::vector<uint8_t> host((size_t)z->n_out);
-    if (z->n_out) {
-        void *stage = nullptr;
-        const size_t room = (size_t)std::min<uint64_t>(z->n_out, STAGE_BYTES);
-        PP_HIPCHK(ctx, hipHostMalloc(&stage, room, hipHostMallocDefault));
-        std::unique_ptr<void, void (*)(void *)> unpin(stage, [](void *p) { (void)hipHostFree(p); });
-        for (uint64_t lo = 0; lo < z->n_out; lo += room) {
-            const size_t piece = (size_t)std::min<uint64_t>(room, z->n_out - lo);
-            if ((rc = timer.begin(2))) return rc;
-            PP_HIPCHK(ctx, hipMemcpyAsync(stage, (const u8 *)z->d_out + lo, piece, hipMemcpyDeviceToHost, st));
-            if ((rc = timer.end())) return rc;
-            PP_HIPCHK(ctx, hipStreamSynchronize(st));
-            memcpy(host.data() + lo, stage, piece);
-        }
-    }
-    char msg[256] = "";
-    uint64_t n = 0, e = from;
-    if (pp_bam_host::walk(host.data(), z->n_out, from, nullptr, 0, (uint64_t *)&n, (uint64_t *)&e, msg, sizeof msg)) {
-        *n_rec = n;
-        *end = e;
-        set_bam_msg(msg);
-        return ctx->fail(PP_ERR_ARG, "pp_bgzf_bam_walk: %s", msg);
-    }
-    std::vector<uint64_t> off((size_t)n);
-    if (n) (void)pp_bam_host::walk(host.data(), z->n_out, from, (uint64_t *)off.data(), n, (uint64_t *)&n, (uint64_t *)&e, msg, sizeof msg);
-    PP_HIPCHK(ctx, hipMalloc(&z->d_rec_off, n ? (size_t)n * 8 : 16));
-    if ((rc = timer.begin(2))) return rc;
-    if (n) PP_HIPCHK(ctx, hipMemcpyAsync(z->d_rec_off, off.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
-    if ((rc = timer.end())) return rc;
-    PP_HIPCHK(ctx, hipStreamSynchronize(st));
-    if (timer.on) {
-        float ms[3];
-        if ((rc = timer.sums(ms, 3))) return rc;
-        z->ms[2] = ms[2];
-    }
-    z->n_rec = n;
-    *n_rec = n;
-    *end = e;
+    float ms = 0.f;
+    if (z->timed) z->ms[2] = ctx->profiling && pp_bam_offs_kernel_ms(z->offs, &ms) == PP_OK ? ms : 0.f;
     return PP_OK;
 }

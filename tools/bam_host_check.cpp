@@ -5,13 +5,38 @@
 //   ./bam_host_check small.bam.raw
 // Every prefix of the file goes to both functions in a heap block of EXACTLY its length (so that a read past the cut is a read
 // past the allocation), then every prefix with one byte flipped; the program checks what tests/test_bam_model_cpu.py checks -- a
-// cut is refused or stops the walk at the cut, no record runs past it -- and the sanitizer checks every load.
+// cut is refused or stops the walk at the cut, no record runs past it -- and the sanitizer checks every load.  step(), the one
+// record of the chain that the device walk's kernels run as well (pp_bam_walk.hip), is called at EVERY offset of every prefix, on
+// the chain or not, and every verdict is worded by walk_message() into a buffer of exactly the message's size.
 #include "pp_bam_host.h"
 
 #include <cstdlib>
 #include <vector>
 
+// step() at every offset of the prefix: a good record ends inside the prefix, a refused one names why, the message fits
+static int check_steps(const uint8_t *p, uint64_t n) {
+    for (uint64_t at = 0; at <= n; at++) {
+        uint64_t next = ~0ull;
+        uint32_t bs = ~0u;
+        const uint32_t kind = pp_bam_host::step(p, n, at, &next, &bs);
+        if (kind == pp_bam_host::W_OK ? (next < at + 36 || next > n || bs != next - at - 4) : (next != ~0ull || kind > pp_bam_host::W_PAST))
+            return fprintf(stderr, "step at %llu of %llu bytes: kind %u, next %llu\n", (unsigned long long)at, (unsigned long long)n, kind, (unsigned long long)next), 1;
+        if (kind != pp_bam_host::step_kind(n - at, bs)) return fprintf(stderr, "step and step_kind disagree at %llu\n", (unsigned long long)at), 1;
+        if ((kind == pp_bam_host::W_CUT) != (n - at < 4)) return fprintf(stderr, "a cut block_size at %llu of %llu bytes\n", (unsigned long long)at, (unsigned long long)n), 1;
+        char probe[256];
+        pp_bam_host::walk_message(probe, sizeof probe, kind, at, at, bs, n);
+        const size_t len = strlen(probe);
+        char *exact = (char *)malloc(len + 1);  // exactly the message: one byte more is not ours
+        pp_bam_host::walk_message(exact, len + 1, kind, at, at, bs, n);
+        const bool same = strcmp(exact, probe) == 0 && (kind == pp_bam_host::W_OK) == (len == 0);
+        free(exact);
+        if (!same) return fprintf(stderr, "walk_message of kind %u\n", kind), 1;
+    }
+    return 0;
+}
+
 static int check(const uint8_t *p, uint64_t n, uint64_t *walked_ok) {
+    if (check_steps(p, n)) return 1;
     uint32_t n_ref = 0;
     uint64_t at = 0, name_off[4];
     uint32_t name_len[4], ref_len[4];

@@ -9,7 +9,8 @@ bytes resident in HBM (an allocation of exactly their length).  Prints one JSON 
                          wall time, best of two -- the comparison that matters is the device stages against the 16 threads
 and once (level 6):
   h2d_ms                 the copy of the compressed bytes from pinned host memory (events), for comparison
-  bam_walk_staging_ms    the copies of pp_bgzf_bam_walk (events), and bam_walk_wall_ms around the whole call (host walk included)
+  bam_walk_staging_ms    the kernels of pp_bgzf_bam_walk (events; until the device walk existed: the copies of its staging), and
+                         bam_walk_wall_ms around the whole call.  tools/bam_walk_timing.py takes the walk apart
   bam_records_ms         pp_bam_records on the inflated bytes and the walked offsets (the next link)
   equal                  the inflated bytes are the encoder's bytes
 --out FILE writes the line to FILE as well.  Measurement only: no threshold is attached to any of it."""
