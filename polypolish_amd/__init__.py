@@ -17,6 +17,9 @@ import os
 
 import numpy as np
 
+from ._abi import (COMM_ID_BYTES, HOOKS, PP_MAX_KERNELS, SIGNATURES, AlnBatch, Bytes, ContigStats, FilterFile, FilterFileCounts,  # noqa: F401
+                   FilterInput, FilterReport, KernelTimes, Params, PolishOptions, PositionsOut, RawBatch, SamCounts, ShardPlan)
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_PATH = os.environ.get("PP_LIB_PATH") or os.path.join(HERE, "_build", "libpolypolish_hip.so")  # PP_LIB_PATH: kernel experiments
@@ -34,25 +37,24 @@ class PolypolishError(RuntimeError):
         self.code, self.msg = code, msg
 
 
-class Params(C.Structure):
-    _fields_ = [("min_depth", C.c_uint32), ("fraction_valid", C.c_double), ("fraction_invalid", C.c_double)]
+_NONE = 0xFFFFFFFFFFFFFFFF  # what the C side leaves in a "which one was bad" output when there is none
 
 
-class AlnBatch(C.Structure):
-    _fields_ = [("n_aln", C.c_uint64), ("contig", C.c_void_p), ("ref_start", C.c_void_p), ("k", C.c_void_p),
-                ("seq_off", C.c_void_p), ("seq_len", C.c_void_p), ("cig_off", C.c_void_p), ("n_cig", C.c_void_p),
-                ("seq", C.c_void_p), ("seq_bytes", C.c_uint64), ("cigar", C.c_void_p), ("n_cig_total", C.c_uint64),
-                ("seq4", C.c_void_p),  # optional 4-bit mirror of seq (include/polypolish_hip.h); None = none
-                ("wo", C.c_void_p),    # optional window-order mirror of the records (pp_wo_rec[n_aln]); None = none
-                ("wo_n_runs", C.c_uint32), ("wo_run_end", C.c_void_p)]  # optional: the mirror's runs (HOST array of u64 ends)
+def _no_index():
+    return C.c_uint64(_NONE)
 
 
-class RawBatch(C.Structure):
-    """pp_raw_batch: the alignment records of one SAM file as Alignment::new leaves them (include/polypolish_hip.h)"""
-    _fields_ = [("n_rec", C.c_uint64), ("flag", C.c_void_p), ("read_id", C.c_void_p), ("contig", C.c_void_p),
-                ("ref_start", C.c_void_p), ("nm", C.c_void_p), ("seq_off", C.c_void_p), ("seq_len", C.c_void_p),
-                ("cig_off", C.c_void_p), ("n_cig", C.c_void_p), ("seq", C.c_void_p), ("seq_bytes", C.c_uint64),
-                ("cigar", C.c_void_p), ("n_cig_total", C.c_uint64)]
+def _index(v):
+    """a "which one was bad" output of a failed call: None when the C side named none"""
+    return None if v.value == _NONE else int(v.value)
+
+
+def _raise(rc, msg, **attrs):
+    """raise PolypolishError(rc, msg) carrying the failed call's outputs as attributes (.bad_record, .n_rec, .end, ...)"""
+    e = PolypolishError(rc, msg)
+    for k, v in attrs.items():
+        setattr(e, k, v)
+    raise e
 
 
 RAW_FIELDS = (("flag", np.uint16), ("read_id", np.uint64), ("contig", np.uint32), ("ref_start", np.uint32), ("nm", np.uint32),
@@ -109,98 +111,8 @@ def window_order_mirror(recs, contig_off, used_per_file=None, window=2048):
     return wo
 
 
-class ContigStats(C.Structure):
-    _fields_ = [("polished_len", C.c_uint64), ("changed", C.c_uint64), ("zero_depth", C.c_uint64),
-                ("depth_sum", C.c_double)]
-
-
-class PositionsOut(C.Structure):
-    _fields_ = [("depth", C.c_void_p), ("count_a", C.c_void_p), ("count_c", C.c_void_p), ("count_g", C.c_void_p),
-                ("count_t", C.c_void_p), ("count_other", C.c_void_p), ("valid_thr", C.c_void_p),
-                ("invalid_thr", C.c_void_p), ("status", C.c_void_p)]
-
-
-PP_MAX_KERNELS = 16
-
-
-class KernelTimes(C.Structure):
-    _fields_ = [("n", C.c_int), ("name", C.c_char_p * PP_MAX_KERNELS), ("ms", C.c_float * PP_MAX_KERNELS),
-                ("n_entries", C.c_uint64), ("n_flagged", C.c_uint64), ("n_passes", C.c_uint64)]
-
-    def as_dict(self):
-        d = {self.name[i].decode(): float(self.ms[i]) for i in range(self.n)}
-        return {"ms": d, "n_entries": int(self.n_entries), "n_flagged": int(self.n_flagged),
-                "n_passes": int(self.n_passes)}
-
-
-class SamCounts(C.Structure):
-    _fields_ = [("alignments", C.c_uint64), ("used", C.c_uint64), ("reads", C.c_uint64)]
-
-
-class PolishOptions(C.Structure):
-    _fields_ = [("fraction_invalid", C.c_double), ("fraction_valid", C.c_double), ("max_errors", C.c_uint32),
-                ("min_depth", C.c_uint32), ("careful", C.c_int), ("debug_path", C.c_char_p), ("quiet", C.c_int)]
-
-
-class Bytes(C.Structure):
-    _fields_ = [("data", C.c_void_p), ("len", C.c_uint64)]
-
-
-class FilterReport(C.Structure):
-    _fields_ = [("before_count", C.c_uint64), ("after_count", C.c_uint64), ("low_threshold", C.c_uint32),
-                ("high_threshold", C.c_uint32), ("orientation", C.c_int), ("orientation_counts", C.c_uint64 * 4)]
-
-
-class FilterFile(C.Structure):
-    _fields_ = [("n_aln", C.c_uint64), ("ref_id", C.c_void_p), ("ref_start", C.c_void_p), ("flags", C.c_void_p),
-                ("cig_off", C.c_void_p), ("n_cig", C.c_void_p), ("cigar", C.c_void_p), ("n_cig_total", C.c_uint64),
-                ("read", C.c_void_p), ("grp_off", C.c_void_p), ("grp_idx", C.c_void_p), ("ref_end", C.c_void_p)]
-
-
-class FilterInput(C.Structure):
-    _fields_ = [("n_reads", C.c_uint32), ("file", FilterFile * 2)]
-
-
-class ShardPlan(C.Structure):
-    _fields_ = [("n_units", C.c_uint32), ("world", C.c_uint32), ("n_contigs", C.c_uint32), ("contig", C.POINTER(C.c_uint32)),
-                ("lo", C.POINTER(C.c_uint64)), ("hi", C.POINTER(C.c_uint64)), ("rank", C.POINTER(C.c_uint32))]
-
-
-COMM_ID_BYTES = 128
-
-
-class FilterFileCounts(C.Structure):
-    _fields_ = [("alignments", C.c_uint64), ("reads", C.c_uint64), ("loaded", C.c_int)]
-
-
 # every symbol include/polypolish_hip.h declares (tests check that the library exports them all)
-EXPORTS = [
-    "pp_device_count", "pp_ctx_create", "pp_ctx_create_async", "pp_ctx_wait", "pp_ctx_destroy", "pp_last_error", "pp_ctx_sync", "pp_ctx_stream", "pp_ctx_download", "pp_version", "pp_log_text",
-    "pp_polish_begin", "pp_polish_add", "pp_polish_reserve", "pp_polish_finish", "pp_polish_result_size", "pp_polish_result",
-    "pp_polish_result_device", "pp_polish_set_emit", "pp_polish_set_debug", "pp_polish_positions", "pp_polish_debug_extra",
-    "pp_debug_extra_free", "pp_ctx_set_profiling",
-    "pp_polish_kernel_times", "pp_polish_took_direct_path", "pp_filter_begin", "pp_filter_samples", "pp_filter_pairs",
-    "pp_filter_kernel_times", "pp_filter_load", "pp_filter_loaded_input", "pp_filter_write", "pp_filter_loaded_free",
-    "pp_filter_load_device", "pp_filter_dev_input", "pp_filter_dev_text", "pp_filter_dev_free", "pp_filter_write_text",
-    "pp_assembly_load", "pp_assembly_free", "pp_assembly_n_contigs",
-    "pp_assembly_name", "pp_assembly_description", "pp_assembly_offsets", "pp_assembly_bases",
-    "pp_ingest_create", "pp_ingest_sam", "pp_ingest_batch", "pp_ingest_read_name", "pp_ingest_free",
-    "pp_bytes_free", "pp_polish_files", "pp_filter_files", "pp_filter_polish_files", "pp_ingest_sam_filtered",
-    "pp_dev_ingest_create", "pp_dev_ingest_sam", "pp_dev_ingest_sam_filtered", "pp_dev_ingest_batch", "pp_dev_ingest_free",
-    "pp_shard_plan_create", "pp_shard_plan_free", "pp_shard_emit_ranges", "pp_shard_assemble",
-    "pp_comm_unique_id", "pp_comm_init", "pp_comm_destroy", "pp_polish_gather", "pp_polish_files_multi",
-    "pp_shard_split", "pp_shard_part_batch", "pp_shard_part_mem", "pp_shard_part_free", "pp_shard_count",
-    "pp_polish_error_record", "pp_polish_error_text", "pp_dev_ingest_set_seq_layout", "pp_dev_ingest_expect",
-    "pp_ingest_set_seq_layout", "pp_polish_debug_tsv",
-    "pp_batch_prepare", "pp_prepared_batch", "pp_prepared_kernel_ms", "pp_prepared_free",
-    "pp_batch_gate", "pp_gated_batch", "pp_gated_counts", "pp_gated_kernel_ms", "pp_gated_free",
-    "pp_filter_thresholds", "pp_filter_records",
-    "pp_names_create", "pp_names_ids", "pp_names_count", "pp_names_name", "pp_names_kernel_ms", "pp_names_free",
-    "pp_bam_header", "pp_bam_walk", "pp_bam_last_error", "pp_bam_records", "pp_bam_raw", "pp_bam_read_id", "pp_bam_names", "pp_bam_pass",
-    "pp_bam_kernel_ms", "pp_bam_free",
-    "pp_bam_walk_device", "pp_bam_offs_dev", "pp_bam_offs_count", "pp_bam_offs_kernel_ms", "pp_bam_offs_free",
-    "pp_bgzf_walk", "pp_bgzf_inflate", "pp_bgzf_bytes", "pp_bgzf_bam_walk", "pp_bgzf_rec_off", "pp_bgzf_kernel_ms", "pp_bgzf_free",
-]
+EXPORTS = list(SIGNATURES)
 
 _lib = None
 
@@ -213,171 +125,11 @@ def lib():
             raise ImportError(f"{LIB_PATH} is missing: run `make` (or __graft_entry__.build()) first; "
                               "polypolish_amd has no pure-Python or CPU path")
         L = C.CDLL(LIB_PATH)
-        vp, u64p = C.c_void_p, C.POINTER(C.c_uint64)
-        L.pp_ctx_create.argtypes = [C.c_int, C.POINTER(vp)]
-        L.pp_ctx_create_async.argtypes = [C.c_int, C.POINTER(vp)]
-        L.pp_ctx_wait.argtypes = [vp]
-        L.pp_ctx_destroy.argtypes = [vp]
-        L.pp_ctx_destroy.restype = None
-        L.pp_last_error.argtypes = [vp]
-        L.pp_last_error.restype = C.c_char_p
-        L.pp_ctx_sync.argtypes = [vp]
-        L.pp_ctx_download.argtypes = [vp, vp, vp, C.c_uint64]
-        L.pp_ctx_stream.argtypes = [vp]
-        L.pp_ctx_stream.restype = vp
-        L.pp_version.restype = C.c_char_p
-        L.pp_log_text.argtypes = [C.c_int, C.c_double, C.c_char_p, C.c_size_t]
-        L.pp_polish_begin.argtypes = [vp, C.c_uint32, vp, vp, C.c_int, C.POINTER(Params)]
-        L.pp_polish_add.argtypes = [vp, C.POINTER(AlnBatch), C.c_int]
-        L.pp_polish_finish.argtypes = [vp]
-        L.pp_polish_result_size.argtypes = [vp, u64p]
-        L.pp_polish_result.argtypes = [vp, vp, C.c_int, vp, vp]
-        L.pp_polish_result_device.argtypes = [vp]
-        L.pp_polish_result_device.restype = vp
-        L.pp_polish_set_debug.argtypes = [vp, C.c_int]
-        L.pp_polish_set_emit.argtypes = [vp, vp, vp]
-        L.pp_polish_positions.argtypes = [vp, C.POINTER(PositionsOut)]
-        L.pp_polish_debug_tsv.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, C.c_int, C.c_uint64, u64p, u64p]
-        L.pp_ctx_set_profiling.argtypes = [vp, C.c_int]
-        L.pp_polish_kernel_times.argtypes = [vp, C.POINTER(KernelTimes)]
-        L.pp_polish_took_direct_path.argtypes = [vp]
-        L.pp_filter_begin.argtypes = [vp, C.POINTER(FilterInput), C.c_int]
-        L.pp_filter_samples.argtypes = [vp, vp, vp]
-        L.pp_filter_pairs.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint8, vp, vp]
-        L.pp_filter_kernel_times.argtypes = [vp, C.POINTER(KernelTimes)]
-        L.pp_filter_load.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(vp), C.POINTER(FilterFileCounts), C.c_char_p, C.c_size_t]
-        L.pp_filter_loaded_input.argtypes = [vp, C.POINTER(FilterInput)]
-        L.pp_filter_loaded_input.restype = None
-        L.pp_filter_write.argtypes = [vp, C.c_int, vp, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
-                                      C.c_char_p, C.c_size_t]
-        L.pp_filter_loaded_free.argtypes = [vp]
-        L.pp_filter_loaded_free.restype = None
-        L.pp_filter_load_device.argtypes = [vp, C.c_char_p, C.c_char_p, C.POINTER(vp), C.POINTER(FilterFileCounts)]
-        L.pp_filter_dev_input.argtypes = [vp, C.POINTER(FilterInput)]
-        L.pp_filter_dev_input.restype = None
-        L.pp_filter_dev_text.argtypes = [vp, C.c_int, C.POINTER(C.c_uint64)]
-        L.pp_filter_dev_text.restype = vp
-        L.pp_filter_dev_free.argtypes = [vp]
-        L.pp_filter_dev_free.restype = None
-        L.pp_filter_write_text.argtypes = [vp, C.c_uint64, vp, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
-                                           C.c_char_p, C.c_size_t]
-        L.pp_assembly_load.argtypes = [C.c_char_p, C.POINTER(vp), C.c_char_p, C.c_size_t]
-        L.pp_assembly_free.argtypes = [vp]
-        L.pp_assembly_free.restype = None
-        L.pp_assembly_n_contigs.argtypes = [vp]
-        L.pp_assembly_n_contigs.restype = C.c_uint32
-        L.pp_assembly_name.argtypes = [vp, C.c_uint32]
-        L.pp_assembly_name.restype = C.c_char_p
-        L.pp_assembly_description.argtypes = [vp, C.c_uint32]
-        L.pp_assembly_description.restype = C.c_char_p
-        L.pp_assembly_offsets.argtypes = [vp]
-        L.pp_assembly_offsets.restype = u64p
-        L.pp_assembly_bases.argtypes = [vp]
-        L.pp_assembly_bases.restype = C.POINTER(C.c_uint8)
-        L.pp_ingest_create.argtypes = [vp, C.c_uint32, C.c_int, C.POINTER(vp)]
-        L.pp_ingest_sam.argtypes = [vp, C.c_char_p, C.POINTER(SamCounts), C.c_char_p, C.c_size_t]
-        L.pp_ingest_batch.argtypes = [vp, C.POINTER(AlnBatch)]
-        L.pp_ingest_batch.restype = None
-        L.pp_ingest_read_name.argtypes = [vp, C.c_uint64]
-        L.pp_ingest_read_name.restype = C.c_char_p
-        L.pp_ingest_free.argtypes = [vp]
-        L.pp_ingest_free.restype = None
-        L.pp_bytes_free.argtypes = [C.POINTER(Bytes)]
-        L.pp_bytes_free.restype = None
-        L.pp_polish_files.argtypes = [vp, C.c_char_p, C.POINTER(C.c_char_p), C.c_int, C.POINTER(PolishOptions),
-                                      C.POINTER(Bytes)]
-        L.pp_filter_files.argtypes = [vp] + [C.c_char_p] * 5 + [C.c_double, C.c_double, C.c_int,
-                                                                C.POINTER(FilterReport)]
-        L.pp_filter_polish_files.argtypes = [vp] + [C.c_char_p] * 6 + [C.c_double, C.c_double, C.POINTER(PolishOptions),
-                                                                       C.POINTER(FilterReport), C.POINTER(Bytes)]
-        L.pp_dev_ingest_create.argtypes = [vp, vp, C.c_uint32, C.c_int, C.POINTER(vp)]
-        L.pp_dev_ingest_sam.argtypes = [vp, C.c_char_p, C.POINTER(SamCounts)]
-        L.pp_dev_ingest_sam_filtered.argtypes = [vp, C.c_char_p, vp, C.c_uint64, C.POINTER(SamCounts)]
-        L.pp_dev_ingest_set_seq_layout.argtypes = [vp, C.c_int]
-        L.pp_dev_ingest_expect.argtypes = [vp, C.c_uint64]
-        L.pp_ingest_set_seq_layout.argtypes = [vp, C.c_int]
-        L.pp_dev_ingest_batch.argtypes = [vp, C.POINTER(AlnBatch)]
-        L.pp_dev_ingest_batch.restype = None
-        L.pp_dev_ingest_free.argtypes = [vp]
-        L.pp_dev_ingest_free.restype = None
-        L.pp_ingest_sam_filtered.argtypes = [vp, C.c_char_p, vp, C.c_uint64, C.POINTER(SamCounts), C.c_char_p, C.c_size_t]
-        L.pp_shard_plan_create.argtypes = [C.c_uint32, vp, vp, C.c_uint32, C.c_uint64, C.POINTER(C.POINTER(ShardPlan))]
-        L.pp_shard_plan_free.argtypes = [C.POINTER(ShardPlan)]
-        L.pp_shard_plan_free.restype = None
-        L.pp_shard_emit_ranges.argtypes = [C.POINTER(ShardPlan), C.c_uint32, vp, vp]
-        L.pp_shard_assemble.argtypes = [C.POINTER(ShardPlan), vp, vp, vp, vp]
-        L.pp_comm_unique_id.argtypes = [vp]
-        L.pp_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
-        L.pp_comm_destroy.argtypes = [vp]
-        L.pp_comm_destroy.restype = None
-        L.pp_polish_gather.argtypes = [vp, vp, C.c_uint64, vp, vp]
-        L.pp_shard_split.argtypes = [vp, C.POINTER(ShardPlan), C.c_uint32, C.POINTER(AlnBatch), C.c_int, C.POINTER(vp)]
-        L.pp_shard_part_batch.argtypes = [vp, C.POINTER(AlnBatch), C.POINTER(vp)]
-        L.pp_shard_part_batch.restype = None
-        L.pp_shard_part_mem.argtypes = [vp]
-        L.pp_shard_part_free.argtypes = [vp]
-        L.pp_shard_part_free.restype = None
-        L.pp_shard_count.argtypes = [vp, C.POINTER(AlnBatch), C.c_int, C.c_uint32, vp]
-        L.pp_polish_error_record.argtypes = [vp, u64p, C.POINTER(C.c_uint32)]
-        L.pp_polish_error_text.argtypes = [vp, C.c_uint32, C.c_uint64]
-        L.pp_batch_prepare.argtypes = [vp, C.c_uint32, vp, C.POINTER(AlnBatch), C.c_int, C.POINTER(vp)]
-        L.pp_prepared_batch.argtypes = [vp, C.POINTER(AlnBatch)]
-        L.pp_prepared_batch.restype = None
-        L.pp_prepared_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
-        L.pp_prepared_free.argtypes = [vp]
-        L.pp_prepared_free.restype = None
-        L.pp_batch_gate.argtypes = [vp, C.POINTER(RawBatch), C.c_int, C.c_uint32, C.c_int, vp, C.c_uint64, C.POINTER(vp), u64p]
-        L.pp_gated_batch.argtypes = [vp, C.POINTER(AlnBatch), C.POINTER(vp)]
-        L.pp_gated_batch.restype = None
-        L.pp_gated_counts.argtypes = [vp, C.POINTER(SamCounts)]
-        L.pp_gated_counts.restype = None
-        L.pp_gated_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
-        L.pp_gated_free.argtypes = [vp]
-        L.pp_gated_free.restype = None
-        L.pp_filter_thresholds.argtypes = [vp, C.c_char_p, C.c_double, C.c_double, C.POINTER(FilterReport)]
-        L.pp_filter_records.argtypes = [vp, C.POINTER(RawBatch), C.c_int, C.c_char_p, C.c_double, C.c_double, vp, vp,
-                                        C.POINTER(FilterFileCounts), C.POINTER(FilterReport)]
-        L.pp_names_create.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
-        L.pp_names_ids.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_int, vp, vp, u64p]
-        L.pp_names_count.argtypes = [vp]
-        L.pp_names_count.restype = C.c_uint64
-        L.pp_names_name.argtypes = [vp, C.c_uint64, vp, C.c_uint32, C.POINTER(C.c_uint32)]
-        L.pp_names_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
-        L.pp_names_free.argtypes = [vp]
-        L.pp_names_free.restype = None
-        L.pp_bam_header.argtypes = [vp, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32), vp, vp, vp, u64p]
-        L.pp_bam_walk.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, u64p, u64p]
-        L.pp_bam_last_error.restype = C.c_char_p
-        L.pp_bam_records.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, vp, C.c_uint32, C.POINTER(vp), u64p]
-        L.pp_bam_raw.argtypes = [vp, C.POINTER(RawBatch)]
-        L.pp_bam_raw.restype = None
-        L.pp_bam_read_id.argtypes = [vp]
-        L.pp_bam_read_id.restype = vp
-        L.pp_bam_names.argtypes = [vp, C.POINTER(vp), u64p, C.POINTER(vp), C.POINTER(vp)]
-        L.pp_bam_names.restype = None
-        L.pp_bam_pass.argtypes = [vp, C.POINTER(vp), u64p]
-        L.pp_bam_pass.restype = None
-        L.pp_bam_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
-        L.pp_bam_free.argtypes = [vp]
-        L.pp_bam_free.restype = None
-        L.pp_bam_walk_device.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(vp), u64p, u64p]
-        L.pp_bam_offs_dev.argtypes = [vp]
-        L.pp_bam_offs_dev.restype = vp
-        L.pp_bam_offs_count.argtypes = [vp]
-        L.pp_bam_offs_count.restype = C.c_uint64
-        L.pp_bam_offs_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
-        L.pp_bam_offs_free.argtypes = [vp]
-        L.pp_bam_offs_free.restype = None
-        L.pp_bgzf_walk.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, C.c_uint64, u64p, u64p]
-        L.pp_bgzf_inflate.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, C.c_int, C.POINTER(vp), u64p]
-        L.pp_bgzf_bytes.argtypes = [vp, C.POINTER(vp), u64p]
-        L.pp_bgzf_bytes.restype = None
-        L.pp_bgzf_bam_walk.argtypes = [vp, C.c_uint64, u64p, u64p]
-        L.pp_bgzf_rec_off.argtypes = [vp]
-        L.pp_bgzf_rec_off.restype = vp
-        L.pp_bgzf_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
-        L.pp_bgzf_free.argtypes = [vp]
-        L.pp_bgzf_free.restype = None
+        for table, declared in ((SIGNATURES, True), (HOOKS, False)):
+            for name, (restype, argtypes) in table.items():
+                if declared or hasattr(L, name):  # (a declared symbol that is missing raises here)
+                    f = getattr(L, name)
+                    f.restype, f.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -385,6 +137,76 @@ def lib():
 REC_FIELDS = (("contig", np.uint32), ("ref_start", np.uint32), ("k", np.uint32), ("seq_off", np.uint64),
               ("seq_len", np.uint32), ("cig_off", np.uint64), ("n_cig", np.uint32), ("seq", np.uint8),
               ("cigar", np.uint32))
+
+
+def _host(addr, n, dtype):
+    """a numpy copy of n items of HOST memory at addr; no address or nothing there: an empty array"""
+    dt = np.dtype(dtype)
+    if not n or not addr:
+        return np.zeros(0, dtype=dt)
+    return np.ctypeslib.as_array(C.cast(addr, C.POINTER(C.c_uint8)), shape=(int(n) * dt.itemsize,)).copy().view(dt)
+
+
+def _read_batch(b, fields, ctx=None, mirrors=(), full=False):
+    """A batch view (AlnBatch / RawBatch) as {field: numpy array} over `fields` (REC_FIELDS / RAW_FIELDS): HOST pointers are
+    copied (ctx None: an empty array where there is no pointer), DEVICE pointers downloaded through ctx (zeros where there is
+    none).  mirrors: which of "seq4", "wo", "wo_runs" of an AlnBatch come along -- when the view has them, or always
+    (zero-filled at their full size) with `full`."""
+    get = _host if ctx is None else ctx.download
+    n = int(b.n_rec if isinstance(b, RawBatch) else b.n_aln)
+    sizes = {"seq": int(b.seq_bytes), "cigar": int(b.n_cig_total)}
+    recs = {name: get(getattr(b, name), sizes.get(name, n), dt) for name, dt in fields}
+    if "seq4" in mirrors and (full or b.seq4):  # the 4-bit mirror of the seq array (two bases per byte)
+        recs["seq4"] = get(b.seq4, (sizes["seq"] + 1) // 2, np.uint8)
+    if "wo" in mirrors and (full or (b.wo and n)):  # the window-order mirror of the records (pp_aln_batch.wo)
+        recs["wo"] = get(b.wo, n, WO_DTYPE)
+        if "wo_runs" in mirrors:
+            recs["wo_runs"] = _runs_of(b) if b.wo else np.zeros(0, dtype=np.uint64)
+    return recs
+
+
+def _ptrs_of(b, fields, mirrors=False):
+    """field name -> address (0 = none) of a batch view; mirrors: an AlnBatch's "seq4", "wo" and "wo_runs" (the run ends
+    themselves, as aln_batch takes them) where it has them"""
+    ptrs = {name: getattr(b, name) or 0 for name, _ in fields}
+    if mirrors and b.seq4:
+        ptrs["seq4"] = b.seq4
+    if mirrors and b.wo:
+        ptrs["wo"], ptrs["wo_runs"] = b.wo, _runs_of(b)
+    return ptrs
+
+
+class _Owned:
+    """An object of the library that the Python object owns: ._p its handle, ._ctx the context it lives on (kept alive with
+    it; None for host objects).  Subclasses name the symbol that frees it and, where there is one, its pp_*_kernel_ms."""
+    _free = None
+    _kernel_ms = None
+
+    def __init__(self, ctx=None, handle=C.c_void_p):
+        self._p, self._ctx = handle(), ctx
+
+    def close(self):
+        if self._p:
+            getattr(lib(), self._free)(self._p)
+            self._p = type(self._p)()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def kernel_ms(self):
+        ms = C.c_float()
+        self._ctx._chk(getattr(lib(), self._kernel_ms)(self._p, C.byref(ms)))
+        return float(ms.value)
+
+    def _stage_ms(self, hook, names, when=""):
+        """the per-stage HIP-event times an internal hook (HOOKS) reports, one float per name"""
+        ms = (C.c_float * len(names))()
+        if getattr(lib(), hook)(self._p, ms):
+            raise PolypolishError(ERR_ARG, "the context had no profiling on" + when)
+        return {k: float(v) for k, v in zip(names, ms)}
 
 
 def split_records(recs, cuts):
@@ -424,58 +246,55 @@ def _verdict_args(verdicts, i):
     return buf.ctypes.data, len(v), buf
 
 
-def ingest(assembly, sams, max_errors=10, careful=False, seq_layout=None, verdicts=None):
-    """Host ingest only (no GPU needed): FASTA + SAM text -> (names, descs, contig_off, bases, recs, counts).
-    seq_layout: None = the library's default (window-grouped unless PP_SEQ_LAYOUT=file), 0 = SEQ bytes in file order,
-    1 = window-grouped (pp_ingest_set_seq_layout).  verdicts: per file None or the filter's verdict byte of every aligned
-    record (pp_ingest_sam_filtered)."""
+def _ingest(ctx, assembly, sams, max_errors, careful, seq_layout, expect, verdicts):
+    """ingest() (ctx None: pp_ingest_*, errors in a text buffer) and ingest_device() (pp_dev_ingest_*, errors on the context)"""
     L = lib()
     err = C.create_string_buffer(1024)
-    a = C.c_void_p()
-    rc = L.pp_assembly_load(str(assembly).encode(), C.byref(a), err, 1024)
-    if rc:
-        raise PolypolishError(rc, err.value.decode())
-    g = C.c_void_p()
+
+    def chk_err(rc):
+        if rc:
+            raise PolypolishError(rc, err.value.decode())
+    if ctx is None:  # only the host ingest's file calls report: a create that failed shows at the first file
+        fn, head, tail, chk, chk_setup, mirrors = "pp_ingest_", (), (err, 1024), chk_err, (lambda rc: None), ("wo", "wo_runs")
+    else:
+        fn, head, tail, chk, chk_setup, mirrors = "pp_dev_ingest_", (ctx._h,), (), ctx._chk, ctx._chk, ("seq4", "wo", "wo_runs")
+    a, g = C.c_void_p(), C.c_void_p()
+    chk_err(L.pp_assembly_load(str(assembly).encode(), C.byref(a), err, 1024))
     try:
         n = L.pp_assembly_n_contigs(a)
         names = [L.pp_assembly_name(a, i).decode() for i in range(n)]
         descs = [L.pp_assembly_description(a, i).decode() for i in range(n)]
         off = np.ctypeslib.as_array(L.pp_assembly_offsets(a), shape=(n + 1,)).copy()
         bases = np.ctypeslib.as_array(L.pp_assembly_bases(a), shape=(int(off[-1]),)).copy()
-        L.pp_ingest_create(a, max_errors, int(careful), C.byref(g))
+        chk_setup(getattr(L, fn + "create")(*head, a, max_errors, int(careful), C.byref(g)))
         if seq_layout is not None:
-            L.pp_ingest_set_seq_layout(g, int(seq_layout))
+            chk_setup(getattr(L, fn + "set_seq_layout")(g, int(seq_layout)))
+        if expect is not None:
+            chk_setup(L.pp_dev_ingest_expect(g, int(expect)))
         counts = []
         for s in sams:
             c = SamCounts()
             vp, nv, _keep = _verdict_args(verdicts, len(counts))
             if _keep is not None:
-                rc = L.pp_ingest_sam_filtered(g, str(s).encode(), vp, nv, C.byref(c), err, 1024)
+                chk(getattr(L, fn + "sam_filtered")(g, str(s).encode(), vp, nv, C.byref(c), *tail))
             else:
-                rc = L.pp_ingest_sam(g, str(s).encode(), C.byref(c), err, 1024)
-            if rc:
-                raise PolypolishError(rc, err.value.decode())
+                chk(getattr(L, fn + "sam")(g, str(s).encode(), C.byref(c), *tail))
             counts.append((c.alignments, c.used, c.reads))
         b = AlnBatch()
-        L.pp_ingest_batch(g, C.byref(b))
-        sizes = {"seq": b.seq_bytes, "cigar": b.n_cig_total}
-        recs = {}
-        for name, dt in REC_FIELDS:
-            cnt = int(sizes.get(name, b.n_aln))
-            ptr = getattr(b, name)
-            if cnt and ptr:
-                arr = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dt))), shape=(cnt,)).copy()
-            else:
-                arr = np.zeros(0, dtype=dt)
-            recs[name] = arr
-        if b.wo and b.n_aln:  # the window-order mirror of the records (pp_aln_batch.wo)
-            recs["wo"] = np.ctypeslib.as_array(C.cast(b.wo, C.POINTER(C.c_uint8)), shape=(int(b.n_aln) * WO_DTYPE.itemsize,)).copy().view(WO_DTYPE)
-            recs["wo_runs"] = _runs_of(b)
-        return names, descs, off, bases, recs, counts
+        getattr(L, fn + "batch")(g, C.byref(b))
+        return names, descs, off, bases, _read_batch(b, REC_FIELDS, ctx, mirrors), counts
     finally:
         if g:
-            L.pp_ingest_free(g)
+            getattr(L, fn + "free")(g)
         L.pp_assembly_free(a)
+
+
+def ingest(assembly, sams, max_errors=10, careful=False, seq_layout=None, verdicts=None):
+    """Host ingest only (no GPU needed): FASTA + SAM text -> (names, descs, contig_off, bases, recs, counts).
+    seq_layout: None = the library's default (window-grouped unless PP_SEQ_LAYOUT=file), 0 = SEQ bytes in file order,
+    1 = window-grouped (pp_ingest_set_seq_layout).  verdicts: per file None or the filter's verdict byte of every aligned
+    record (pp_ingest_sam_filtered)."""
+    return _ingest(None, assembly, sams, max_errors, careful, seq_layout, None, verdicts)
 
 
 _SEQ4_LUT = np.full(256, 15, dtype=np.uint8)
@@ -501,71 +320,20 @@ def ingest_device(ctx, assembly, sams, max_errors=10, careful=False, seq_layout=
     1 = window-grouped (pp_dev_ingest_set_seq_layout).  expect: the text bytes of all the files, announced before the first
     one (pp_dev_ingest_expect).  verdicts: per file None or the filter's verdict byte of every aligned record
     (pp_dev_ingest_sam_filtered)."""
-    L = lib()
-    err = C.create_string_buffer(1024)
-    a = C.c_void_p()
-    rc = L.pp_assembly_load(str(assembly).encode(), C.byref(a), err, 1024)
-    if rc:
-        raise PolypolishError(rc, err.value.decode())
-    g = C.c_void_p()
-    try:
-        n = L.pp_assembly_n_contigs(a)
-        names = [L.pp_assembly_name(a, i).decode() for i in range(n)]
-        descs = [L.pp_assembly_description(a, i).decode() for i in range(n)]
-        off = np.ctypeslib.as_array(L.pp_assembly_offsets(a), shape=(n + 1,)).copy()
-        bases = np.ctypeslib.as_array(L.pp_assembly_bases(a), shape=(int(off[-1]),)).copy()
-        ctx._chk(L.pp_dev_ingest_create(ctx._h, a, max_errors, int(careful), C.byref(g)))
-        if seq_layout is not None:
-            ctx._chk(L.pp_dev_ingest_set_seq_layout(g, int(seq_layout)))
-        if expect is not None:
-            ctx._chk(L.pp_dev_ingest_expect(g, int(expect)))
-        counts = []
-        for s in sams:
-            c = SamCounts()
-            vp, nv, _keep = _verdict_args(verdicts, len(counts))
-            if _keep is not None:
-                ctx._chk(L.pp_dev_ingest_sam_filtered(g, str(s).encode(), vp, nv, C.byref(c)))
-            else:
-                ctx._chk(L.pp_dev_ingest_sam(g, str(s).encode(), C.byref(c)))
-            counts.append((c.alignments, c.used, c.reads))
-        b = AlnBatch()
-        L.pp_dev_ingest_batch(g, C.byref(b))
-        sizes = {"seq": b.seq_bytes, "cigar": b.n_cig_total}
-        recs = {}
-        for name, dt in REC_FIELDS:
-            cnt = int(sizes.get(name, b.n_aln))
-            ptr = getattr(b, name)
-            arr = np.zeros(cnt, dtype=dt)
-            if cnt and ptr:
-                ctx._chk(L.pp_ctx_download(ctx._h, arr.ctypes.data, ptr, arr.nbytes))
-            recs[name] = arr
-        if b.seq4:  # the 4-bit mirror of the seq array (two bases per byte), as the tokenizer hands it to the polish
-            m = np.zeros((int(b.seq_bytes) + 1) // 2, dtype=np.uint8)
-            if m.size:
-                ctx._chk(L.pp_ctx_download(ctx._h, m.ctypes.data, b.seq4, m.nbytes))
-            recs["seq4"] = m
-        if b.wo and b.n_aln:
-            w = np.zeros(int(b.n_aln), dtype=WO_DTYPE)
-            ctx._chk(L.pp_ctx_download(ctx._h, w.ctypes.data, b.wo, w.nbytes))
-            recs["wo"] = w
-            recs["wo_runs"] = _runs_of(b)
-        return names, descs, off, bases, recs, counts
-    finally:
-        if g:
-            L.pp_dev_ingest_free(g)
-        L.pp_assembly_free(a)
+    return _ingest(ctx, assembly, sams, max_errors, careful, seq_layout, expect, verdicts)
 
 
-class Plan:
+class Plan(_Owned):
     """pp_shard_plan: which rank polishes which contig / window of a contig (no GPU needed).
     aln_per_contig: alignment records per contig (e.g. np.bincount(recs["contig"], minlength=n_contigs))."""
+    _free = "pp_shard_plan_free"
 
     def __init__(self, contig_off, aln_per_contig, world, min_window=0):
         self.contig_off = np.ascontiguousarray(contig_off, dtype=np.uint64)
         self.n_contigs = len(self.contig_off) - 1
         cnt = np.ascontiguousarray(aln_per_contig, dtype=np.uint64)
         assert len(cnt) == self.n_contigs
-        self._p = C.POINTER(ShardPlan)()
+        super().__init__(None, C.POINTER(ShardPlan))
         rc = lib().pp_shard_plan_create(self.n_contigs, self.contig_off.ctypes.data, cnt.ctypes.data, world, min_window,
                                         C.byref(self._p))
         if rc:
@@ -603,71 +371,36 @@ class Plan:
             raise PolypolishError(rc, "pp_shard_assemble failed")
         return out[:int(out_off[-1])].tobytes(), out_off
 
-    def close(self):
-        if self._p:
-            lib().pp_shard_plan_free(self._p)
-            self._p = C.POINTER(ShardPlan)()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ShardPart:
+class ShardPart(_Owned):
     """pp_shard_split: the records of a batch that rank `dest` of a plan needs (its contigs' records; on a tiled contig
     its window's records plus those that reach in from the neighbours).  The batch is given as raw pointers
     (`ptrs`: field name -> address, host or device as `mem` says); `ctx` may be None for host memory.
       .n_aln, .seq_bytes, .n_cig_total, .ptrs (field name -> address of the part's arrays, same memory kind), .orig_ptr
       .host() -> (recs dict of numpy arrays, orig) for a host part."""
+    _free = "pp_shard_part_free"
 
     def __init__(self, ctx, plan, dest, n_aln, ptrs, seq_bytes, n_cig_total, mem):
         L = lib()
         b = aln_batch(n_aln, ptrs, seq_bytes, n_cig_total)  # (ptrs["wo_runs"]: the mirror's runs go along, restricted)
-        self._p = C.c_void_p()
-        self._ctx = ctx  # keeps the context (and with it the part's device memory) alive
+        super().__init__(ctx)  # (the context, and with it the part's device memory, stays alive)
         rc = L.pp_shard_split(ctx._h if ctx is not None else None, plan._p, dest, C.byref(b), mem, C.byref(self._p))
         if rc:
             raise PolypolishError(rc, L.pp_last_error(ctx._h).decode() if ctx is not None else "pp_shard_split failed")
         out, orig = AlnBatch(), C.c_void_p()
         L.pp_shard_part_batch(self._p, C.byref(out), C.byref(orig))
-        self.mem = mem
+        self.mem, self._view = mem, out
         self.n_aln, self.seq_bytes, self.n_cig_total = int(out.n_aln), int(out.seq_bytes), int(out.n_cig_total)
-        self.ptrs = {name: (C.cast(getattr(out, name), C.c_void_p).value or 0) for name, _ in REC_FIELDS}
-        if out.seq4:  # a device part brings the 4-bit mirror of its seq array
-            self.ptrs["seq4"] = out.seq4
-        if out.wo:    # ... and every part the window-order mirror of its records, when the source batch has one
-            self.ptrs["wo"] = out.wo
-            runs = _runs_of(out)
-            if len(runs):  # ... with its runs, when the source's are known: the part takes the direct path too
-                self.ptrs["wo_runs"] = runs
+        # a device part brings the 4-bit mirror of its seq array, and every part the window-order mirror of its records when the
+        # source batch has one -- with its runs, when the source's are known: the part takes the direct path too
+        self.ptrs = _ptrs_of(out, REC_FIELDS, mirrors=True)
+        if "wo_runs" in self.ptrs and not len(self.ptrs["wo_runs"]):
+            del self.ptrs["wo_runs"]
         self.orig_ptr = orig.value or 0
 
     def host(self):
         assert self.mem == MEM_HOST
-        sizes = {"seq": self.seq_bytes, "cigar": self.n_cig_total}
-        recs = {}
-        for name, dt in REC_FIELDS:
-            cnt = int(sizes.get(name, self.n_aln))
-            recs[name] = (np.ctypeslib.as_array(C.cast(self.ptrs[name], C.POINTER(np.ctypeslib.as_ctypes_type(dt))), shape=(cnt,)).copy()
-                          if cnt and self.ptrs[name] else np.zeros(0, dtype=dt))
-        orig = (np.ctypeslib.as_array(C.cast(self.orig_ptr, C.POINTER(C.c_uint32)), shape=(self.n_aln,)).copy()
-                if self.n_aln else np.zeros(0, np.uint32))
-        if self.ptrs.get("wo") and self.n_aln:
-            recs["wo"] = np.ctypeslib.as_array(C.cast(self.ptrs["wo"], C.POINTER(C.c_uint8)), shape=(self.n_aln * WO_DTYPE.itemsize,)).copy().view(WO_DTYPE)
-        return recs, orig
-
-    def close(self):
-        if self._p:
-            lib().pp_shard_part_free(self._p)
-            self._p = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _read_batch(self._view, REC_FIELDS, None, ("wo",)), _host(self.orig_ptr, self.n_aln, np.uint32)
 
 
 def shard_split_host(plan, dest, recs):
@@ -689,7 +422,7 @@ def shard_split_host(plan, dest, recs):
     return out
 
 
-class PreparedBatch:
+class PreparedBatch(_Owned):
     """pp_batch_prepare: any valid batch (raw pointers `ptrs`: field name -> address, host or device as `mem` says) laid out
     on the device as the library's ingests lay theirs out -- window-grouped SEQ rooms, the 4-bit mirror, the window-order mirror
     as one run -- and owned by this object: the way to the direct path for a batch the caller made.
@@ -697,63 +430,25 @@ class PreparedBatch:
       .ptrs()       what Context.polish_add_ptrs / prepared_job take, with mem = MEM_DEVICE (valid until close())
       .host()       numpy copies of every array, "wo", "wo_runs" and "seq4" included
       .kernel_ms()  HIP-event time of the prepare's kernels (the context had set_profiling on)"""
+    _free, _kernel_ms = "pp_prepared_free", "pp_prepared_kernel_ms"
 
     def __init__(self, ctx, contig_off, n_aln, ptrs, seq_bytes, n_cig_total, mem):
         L = lib()
         off = np.ascontiguousarray(contig_off, dtype=np.uint64)
         b = aln_batch(n_aln, ptrs, seq_bytes, n_cig_total)
-        self._p = C.c_void_p()
-        self._ctx = ctx  # keeps the context (and with it the batch's device memory) alive
+        super().__init__(ctx)  # (the context, and with it the batch's device memory, stays alive)
         ctx._chk(L.pp_batch_prepare(ctx._h, len(off) - 1, off.ctypes.data, C.byref(b), mem, C.byref(self._p)))
         out = AlnBatch()
         L.pp_prepared_batch(self._p, C.byref(out))
-        self.mem = MEM_DEVICE
+        self.mem, self._view = MEM_DEVICE, out
         self.n_aln, self.seq_bytes, self.n_cig_total = int(out.n_aln), int(out.seq_bytes), int(out.n_cig_total)
-        self._ptrs = {name: (C.cast(getattr(out, name), C.c_void_p).value or 0) for name, _ in REC_FIELDS}
-        if out.seq4:
-            self._ptrs["seq4"] = out.seq4
-        if out.wo:
-            self._ptrs["wo"] = out.wo
-            self._ptrs["wo_runs"] = _runs_of(out)
+        self._ptrs = _ptrs_of(out, REC_FIELDS, mirrors=True)
 
     def ptrs(self):
         return dict(self._ptrs)
 
     def host(self):
-        L, ctx = lib(), self._ctx
-        sizes = {"seq": self.seq_bytes, "cigar": self.n_cig_total}
-        recs = {}
-        for name, dt in REC_FIELDS:
-            arr = np.zeros(int(sizes.get(name, self.n_aln)), dtype=dt)
-            if arr.size and self._ptrs[name]:
-                ctx._chk(L.pp_ctx_download(ctx._h, arr.ctypes.data, self._ptrs[name], arr.nbytes))
-            recs[name] = arr
-        m = np.zeros((self.seq_bytes + 1) // 2, dtype=np.uint8)
-        if m.size and self._ptrs.get("seq4"):
-            ctx._chk(L.pp_ctx_download(ctx._h, m.ctypes.data, self._ptrs["seq4"], m.nbytes))
-        recs["seq4"] = m
-        w = np.zeros(self.n_aln, dtype=WO_DTYPE)
-        if self.n_aln and self._ptrs.get("wo"):
-            ctx._chk(L.pp_ctx_download(ctx._h, w.ctypes.data, self._ptrs["wo"], w.nbytes))
-        recs["wo"] = w
-        recs["wo_runs"] = np.array(self._ptrs.get("wo_runs", []), dtype=np.uint64)
-        return recs
-
-    def kernel_ms(self):
-        ms = C.c_float()
-        self._ctx._chk(lib().pp_prepared_kernel_ms(self._p, C.byref(ms)))
-        return float(ms.value)
-
-    def close(self):
-        if self._p:
-            lib().pp_prepared_free(self._p)
-            self._p = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return _read_batch(self._view, REC_FIELDS, self._ctx, ("seq4", "wo", "wo_runs"), full=True)
 
 
 def prepare_batch(ctx, contig_off, n_aln, ptrs, seq_bytes, n_cig_total, mem):
@@ -768,7 +463,22 @@ def prepare_records(ctx, contig_off, recs):
     return PreparedBatch(ctx, contig_off, len(keep["contig"]), ptrs, len(keep["seq"]), len(keep["cigar"]), MEM_HOST)
 
 
-class GatedBatch:
+def _raw_batch(raw, host, fields):
+    """(RawBatch, what it points into) of raw records.  host: raw = numpy arrays by the names of `fields` -- those of RAW_FIELDS the
+    callee reads; without "seq" among them seq_bytes is 0.  Else raw = device addresses, those of `fields` at least, plus "n_rec",
+    "seq_bytes" and "n_cig_total"."""
+    if host:
+        keep = {k: np.ascontiguousarray(raw[k], dtype=dt) for k, dt in fields}
+        ptrs = {k: v.ctypes.data for k, v in keep.items()}
+        n_rec, seq_bytes, n_cig_total = len(keep["flag"]), len(keep["seq"]) if "seq" in keep else 0, len(keep["cigar"])
+    else:
+        keep, ptrs, n_rec, seq_bytes, n_cig_total = None, raw, int(raw["n_rec"]), int(raw["seq_bytes"]), int(raw["n_cig_total"])
+    need = {k for k, _ in fields}
+    arrays = {k: ptrs[k] if k in need else ptrs.get(k) for k, _ in RAW_FIELDS}
+    return RawBatch(n_rec=n_rec, seq_bytes=seq_bytes, n_cig_total=n_cig_total, **arrays), keep
+
+
+class GatedBatch(_Owned):
     """pp_batch_gate: the good records of one SAM file's raw records (process_one_read on the device), owned by this object.
       .n_aln, .seq_bytes, .n_cig_total
       .counts       (alignments, used, reads) as add_to_pileup counts them
@@ -776,67 +486,35 @@ class GatedBatch:
       .host()       numpy copies of the nine arrays
       .orig()       the index in the raw batch of every good record
       .kernel_ms()  HIP-event time of the gate's kernels (the context had set_profiling on)"""
+    _free, _kernel_ms = "pp_gated_free", "pp_gated_kernel_ms"
 
     def __init__(self, ctx, raw, max_errors=10, careful=False, passed=None, mem=MEM_HOST):
         L = lib()
-        if mem == MEM_HOST:
-            keep = {k: np.ascontiguousarray(raw[k], dtype=dt) for k, dt in RAW_FIELDS}
-            n_rec, seq_bytes, n_cig_total = len(keep["flag"]), len(keep["seq"]), len(keep["cigar"])
-            ptrs = {k: v.ctypes.data for k, v in keep.items()}
-        else:  # addresses of device memory, and the three sizes
-            ptrs, n_rec, seq_bytes, n_cig_total = raw, int(raw["n_rec"]), int(raw["seq_bytes"]), int(raw["n_cig_total"])
-        b = RawBatch(n_rec, ptrs["flag"], ptrs["read_id"], ptrs["contig"], ptrs["ref_start"], ptrs["nm"], ptrs["seq_off"], ptrs["seq_len"],
-                     ptrs["cig_off"], ptrs["n_cig"], ptrs["seq"], seq_bytes, ptrs["cigar"], n_cig_total)
+        b, _keep = _raw_batch(raw, mem == MEM_HOST, RAW_FIELDS)
         v = None if passed is None else np.ascontiguousarray(passed, dtype=np.uint8)
-        self._p = C.c_void_p()
-        self._ctx = ctx
-        bad = C.c_uint64(0xFFFFFFFFFFFFFFFF)
+        super().__init__(ctx)
+        bad = _no_index()
         rc = L.pp_batch_gate(ctx._h, C.byref(b), mem, max_errors, int(bool(careful)), v.ctypes.data if v is not None else None,
                              len(v) if v is not None else 0, C.byref(self._p), C.byref(bad))
         if rc:
-            e = PolypolishError(rc, L.pp_last_error(ctx._h).decode())
-            e.bad_record = None if bad.value == 0xFFFFFFFFFFFFFFFF else int(bad.value)
-            raise e
+            _raise(rc, L.pp_last_error(ctx._h).decode(), bad_record=_index(bad))
         out, orig, cnt = AlnBatch(), C.c_void_p(), SamCounts()
         L.pp_gated_batch(self._p, C.byref(out), C.byref(orig))
         L.pp_gated_counts(self._p, C.byref(cnt))
-        self.mem = MEM_DEVICE
+        self.mem, self._view = MEM_DEVICE, out
         self.counts = (int(cnt.alignments), int(cnt.used), int(cnt.reads))
         self.n_aln, self.seq_bytes, self.n_cig_total = int(out.n_aln), int(out.seq_bytes), int(out.n_cig_total)
-        self._ptrs = {name: (C.cast(getattr(out, name), C.c_void_p).value or 0) for name, _ in REC_FIELDS}
+        self._ptrs = _ptrs_of(out, REC_FIELDS)
         self._orig = orig.value or 0
 
     def ptrs(self):
         return dict(self._ptrs)
 
-    def _down(self, addr, n, dt):
-        arr = np.zeros(int(n), dtype=dt)
-        if arr.size and addr:
-            self._ctx._chk(lib().pp_ctx_download(self._ctx._h, arr.ctypes.data, addr, arr.nbytes))
-        return arr
-
     def host(self):
-        sizes = {"seq": self.seq_bytes, "cigar": self.n_cig_total}
-        return {name: self._down(self._ptrs[name], sizes.get(name, self.n_aln), dt) for name, dt in REC_FIELDS}
+        return _read_batch(self._view, REC_FIELDS, self._ctx)
 
     def orig(self):
-        return self._down(self._orig, self.n_aln, np.uint32)
-
-    def kernel_ms(self):
-        ms = C.c_float()
-        self._ctx._chk(lib().pp_gated_kernel_ms(self._p, C.byref(ms)))
-        return float(ms.value)
-
-    def close(self):
-        if self._p:
-            lib().pp_gated_free(self._p)
-            self._p = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._ctx.download(self._orig, self.n_aln, np.uint32)
 
 
 def gate_records(ctx, raw: dict, max_errors=10, careful=False, passed=None, mem=MEM_HOST):
@@ -854,7 +532,7 @@ def pack_names(names):
     return np.frombuffer(b"".join(raw), dtype=np.uint8), off, ln
 
 
-class Names:
+class Names(_Owned):
     """pp_names: a set of byte strings with dense ids on the device -- QNAME -> pp_raw_batch.read_id, RNAME -> .contig.
       .ids(names)   names = a list of bytes / str, or (bytes, off, len): numpy arrays (mem = MEM_HOST) or device addresses
                     (MEM_DEVICE, with n = names, n_bytes = bytes of the array, out = device address of n uint64).  Returns the
@@ -863,10 +541,10 @@ class Names:
       .count        distinct names held
       .name(id)     the bytes of a name
       .kernel_ms()  HIP-event time of the last ids() (the context had set_profiling on)"""
+    _free, _kernel_ms = "pp_names_free", "pp_names_kernel_ms"
 
     def __init__(self, ctx, expect=0):
-        self._p = C.c_void_p()
-        self._ctx = ctx
+        super().__init__(ctx)
         ctx._chk(lib().pp_names_create(ctx._h, int(expect), C.byref(self._p)))
 
     def ids(self, names, mem=MEM_HOST, n=None, n_bytes=None, out=None):
@@ -882,15 +560,11 @@ class Names:
             n, n_bytes = len(o), len(b)
             res = np.zeros(n, dtype=np.uint64)
             bp, op, lp, dst = (b.ctypes.data if n_bytes else None), o.ctypes.data, ln.ctypes.data, res.ctypes.data
-        bad = C.c_uint64(0xFFFFFFFFFFFFFFFF)
+        bad = _no_index()
         rc = L.pp_names_ids(self._p, bp, n_bytes, op, lp, n, mem, dst, None, C.byref(bad))
         if rc:
-            e = PolypolishError(rc, L.pp_last_error(self._ctx._h).decode())
-            e.bad = None if bad.value == 0xFFFFFFFFFFFFFFFF else int(bad.value)
-            raise e
-        if mem != MEM_HOST and n:
-            self._ctx._chk(L.pp_ctx_download(self._ctx._h, res.ctypes.data, dst, res.nbytes))
-        return res
+            _raise(rc, L.pp_last_error(self._ctx._h).decode(), bad=_index(bad))
+        return res if mem == MEM_HOST else self._ctx.download(dst, n, np.uint64)
 
     @property
     def count(self):
@@ -905,22 +579,6 @@ class Names:
             rc = lib().pp_names_name(self._p, int(id), buf.ctypes.data, len(buf), C.byref(ln))
         self._ctx._chk(rc)
         return buf[:ln.value].tobytes()
-
-    def kernel_ms(self):
-        ms = C.c_float()
-        self._ctx._chk(lib().pp_names_kernel_ms(self._p, C.byref(ms)))
-        return float(ms.value)
-
-    def close(self):
-        if self._p:
-            lib().pp_names_free(self._p)
-            self._p = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _bam_bytes(data):
@@ -947,28 +605,48 @@ def bam_header(data):
             "records_at": int(at.value)}
 
 
-def bam_walk(data, start=0):
-    """pp_bam_walk (no device needed): (rec_off: np.uint64 array, end) -- the offset of every record's block_size word from `start`
-    on, and the first byte not consumed.  A chain that breaks raises PolypolishError(ERR_ARG) with .n_rec = the records in front
-    of the break and .end = its offset."""
+def _walk_host(fn, data, start, extra, count):
+    """The two passes of a host chain walk (pp_bam_walk, pp_bgzf_walk): count the links, then fill one uint64 array per entry of
+    `extra`, of links + extra entries.  -> (arrays, end).  A chain that breaks raises with .<count> = the links in front of the
+    break and .end = its offset."""
     L = lib()
     b = _bam_bytes(data)
     n, end = C.c_uint64(0), C.c_uint64(0)
     bp = b.ctypes.data if len(b) else None
-    rc = L.pp_bam_walk(bp, len(b), int(start), None, 0, C.byref(n), C.byref(end))
+    rc = fn(bp, len(b), int(start), *[None] * len(extra), 0, C.byref(n), C.byref(end))
     if rc:
-        e = PolypolishError(rc, L.pp_bam_last_error().decode())
-        e.n_rec, e.end = int(n.value), int(end.value)
-        raise e
-    off = np.zeros(int(n.value), np.uint64)
-    if len(off):
-        rc = L.pp_bam_walk(bp, len(b), int(start), off.ctypes.data, len(off), C.byref(n), C.byref(end))
+        _raise(rc, L.pp_bam_last_error().decode(), **{count: int(n.value), "end": int(end.value)})
+    out = [np.zeros(int(n.value) + x, np.uint64) for x in extra]
+    if n.value:
+        rc = fn(bp, len(b), int(start), *[a.ctypes.data for a in out], int(n.value), C.byref(n), C.byref(end))
         if rc:
             raise PolypolishError(rc, L.pp_bam_last_error().decode())
-    return off, int(end.value)
+    return out, int(end.value)
 
 
-class BamOffsets:
+def bam_walk(data, start=0):
+    """pp_bam_walk (no device needed): (rec_off: np.uint64 array, end) -- the offset of every record's block_size word from `start`
+    on, and the first byte not consumed.  A chain that breaks raises PolypolishError(ERR_ARG) with .n_rec = the records in front
+    of the break and .end = its offset."""
+    (off,), end = _walk_host(lib().pp_bam_walk, data, start, (0,), "n_rec")
+    return off, end
+
+
+def _bytes_and_offsets(data, off, mem):
+    """(bytes_ptr, n_bytes, off_ptr, n, what the pointers point into) of "bytes plus optional offsets".  MEM_HOST: data = bytes /
+    a uint8 array, off = None or the offsets; else data = (device address, n_bytes), off = None or (device address of n uint64, n)."""
+    if mem != MEM_HOST:
+        op, n = (None, 0) if off is None else (int(off[0]), int(off[1]))
+        return int(data[0]) or None, int(data[1]), op, n, None
+    b = _bam_bytes(data)
+    o = None if off is None else np.ascontiguousarray(off, dtype=np.uint64)
+    n = 0 if o is None else len(o)
+    if o is not None and n == 0:
+        o = np.zeros(1, dtype=np.uint64)     # (an array without entries still is one: no walk)
+    return (b.ctypes.data if len(b) else None), len(b), (None if o is None else o.ctypes.data), n, (b, o)
+
+
+class BamOffsets(_Owned):
     """pp_bam_walk_device: the block_size chain of uncompressed BAM bytes walked on the device; the offsets stay in DEVICE memory,
     owned by this object.
       data           mem = MEM_HOST: bytes / a uint8 array; MEM_DEVICE: (device address, n_bytes), borrowed for the call
@@ -980,61 +658,29 @@ class BamOffsets:
                      record behind a zone, "pass": passed through}
     A chain that breaks raises PolypolishError(ERR_ARG) with .n_rec = the records in front of the break and .end = its offset, as
     bam_walk does; the text behind "pp_bam_walk_device: " is bam_walk's."""
+    _free, _kernel_ms = "pp_bam_offs_free", "pp_bam_offs_kernel_ms"
 
     def __init__(self, ctx, data, start=0, mem=MEM_HOST):
         L = lib()
-        if mem == MEM_HOST:
-            b = _bam_bytes(data)
-            bp, n_bytes = (b.ctypes.data if len(b) else None), len(b)
-        else:
-            bp, n_bytes = int(data[0]) or None, int(data[1])
-        self._p = C.c_void_p()
-        self._ctx = ctx
+        bp, n_bytes, _, _, _keep = _bytes_and_offsets(data, None, mem)
+        super().__init__(ctx)
         n, end = C.c_uint64(0), C.c_uint64(0)
         rc = L.pp_bam_walk_device(ctx._h, bp, n_bytes, int(start), mem, C.byref(self._p), C.byref(n), C.byref(end))
         if rc:
-            e = PolypolishError(rc, L.pp_last_error(ctx._h).decode())
-            e.n_rec, e.end = int(n.value), int(end.value)
-            raise e
+            _raise(rc, L.pp_last_error(ctx._h).decode(), n_rec=int(n.value), end=int(end.value))
         self.ptr, self.n_rec, self.end = L.pp_bam_offs_dev(self._p) or 0, int(L.pp_bam_offs_count(self._p)), int(end.value)
 
     def host(self):
-        arr = np.zeros(self.n_rec, np.uint64)
-        if arr.size:
-            self._ctx._chk(lib().pp_ctx_download(self._ctx._h, arr.ctypes.data, self.ptr, arr.nbytes))
-        return arr
-
-    def kernel_ms(self):
-        ms = C.c_float()
-        self._ctx._chk(lib().pp_bam_offs_kernel_ms(self._p, C.byref(ms)))
-        return float(ms.value)
+        return self._ctx.download(self.ptr, self.n_rec, np.uint64)
 
     def stage_ms(self):
-        f = lib().pp_bam_offs_stage_ms_
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        ms = (C.c_float * 3)()
-        if f(self._p, ms):
-            raise PolypolishError(ERR_ARG, "the context had no profiling on when the chain was walked")
-        return {"tables": float(ms[0]), "chain": float(ms[1]), "offsets": float(ms[2])}
+        return self._stage_ms("pp_bam_offs_stage_ms_", ("tables", "chain", "offsets"), " when the chain was walked")
 
     def stats(self):
-        f = lib().pp_bam_offs_stats_
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         out = (C.c_uint64 * 4)()
-        if f(self._p, out):
+        if lib().pp_bam_offs_stats_(self._p, out):
             raise PolypolishError(ERR_ARG, "pp_bam_offs_stats_: no object")
         return {"chain": int(out[0]), "zone": int(out[1]), "slow": int(out[2]), "pass": int(out[3])}
-
-    def close(self):
-        if self._p:
-            lib().pp_bam_offs_free(self._p)
-            self._p = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def bam_walk_device(ctx, data, start=0, mem=MEM_HOST):
@@ -1044,11 +690,8 @@ def bam_walk_device(ctx, data, start=0, mem=MEM_HOST):
 
 def bam_walk_geometry():
     """(bytes per chunk, offsets of a chunk's entry zone, chunks per group) of the device walk: the seams its tests are built on"""
-    f = lib().pp_bam_walk_geometry_
-    f.argtypes = [C.POINTER(C.c_uint32)] * 3
-    f.restype = None
     c, z, g = C.c_uint32(), C.c_uint32(), C.c_uint32()
-    f(C.byref(c), C.byref(z), C.byref(g))
+    lib().pp_bam_walk_geometry_(C.byref(c), C.byref(z), C.byref(g))
     return int(c.value), int(z.value), int(g.value)
 
 
@@ -1056,24 +699,11 @@ def bgzf_walk(data, start=0):
     """pp_bgzf_walk (no device needed): (blk_off, out_off, end) -- the offset of every BGZF block from `start` on, the sum of the
     ISIZEs in front of every block (one more entry: the sum of all), and the first byte not consumed.  A chain that breaks raises
     PolypolishError(ERR_ARG) with .n_blk = the blocks in front of the break and .end = its offset."""
-    L = lib()
-    b = _bam_bytes(data)
-    n, end = C.c_uint64(0), C.c_uint64(0)
-    bp = b.ctypes.data if len(b) else None
-    rc = L.pp_bgzf_walk(bp, len(b), int(start), None, None, 0, C.byref(n), C.byref(end))
-    if rc:
-        e = PolypolishError(rc, L.pp_bam_last_error().decode())
-        e.n_blk, e.end = int(n.value), int(end.value)
-        raise e
-    off, out = np.zeros(int(n.value), np.uint64), np.zeros(int(n.value) + 1, np.uint64)
-    if len(off):
-        rc = L.pp_bgzf_walk(bp, len(b), int(start), off.ctypes.data, out.ctypes.data, len(off), C.byref(n), C.byref(end))
-        if rc:
-            raise PolypolishError(rc, L.pp_bam_last_error().decode())
-    return off, out, int(end.value)
+    (off, out), end = _walk_host(lib().pp_bgzf_walk, data, start, (0, 1), "n_blk")
+    return off, out, end
 
 
-class Bgzf:
+class Bgzf(_Owned):
     """pp_bgzf_inflate: the BGZF blocks of a file inflated into one dense array in DEVICE memory, owned by this object.
       data, blk_off  mem = MEM_HOST: bytes / a uint8 array, and the blocks' offsets (None: the library walks the chain from offset 0);
                      MEM_DEVICE: data = (device address, n_bytes), blk_off = (device address of n uint64, n)
@@ -1083,28 +713,16 @@ class Bgzf:
       .kernel_ms()   HIP-event time of the stages so far (the context had set_profiling on); .stage_ms(): inflate | crc | walk (the
                      kernels of .bam_walk; "staging" is the same value under its earlier name)
     A failing call raises PolypolishError with .bad_block."""
+    _free, _kernel_ms = "pp_bgzf_free", "pp_bgzf_kernel_ms"
 
     def __init__(self, ctx, data, blk_off=None, mem=MEM_HOST):
         L = lib()
-        if mem == MEM_HOST:
-            b = _bam_bytes(data)
-            bp, n_bytes = (b.ctypes.data if len(b) else None), len(b)
-            o = None if blk_off is None else np.ascontiguousarray(blk_off, dtype=np.uint64)
-            n = 0 if o is None else len(o)
-            if o is not None and n == 0:
-                o = np.zeros(1, dtype=np.uint64)     # (an array without blocks still is one: no walk)
-            op = None if o is None else o.ctypes.data
-        else:
-            bp, n_bytes = int(data[0]), int(data[1])
-            op, n = (None, 0) if blk_off is None else (int(blk_off[0]), int(blk_off[1]))
-        self._p = C.c_void_p()
-        self._ctx = ctx
-        bad = C.c_uint64(0xFFFFFFFFFFFFFFFF)
+        bp, n_bytes, op, n, _keep = _bytes_and_offsets(data, blk_off, mem)
+        super().__init__(ctx)
+        bad = _no_index()
         rc = L.pp_bgzf_inflate(ctx._h, bp, n_bytes, op, n, mem, C.byref(self._p), C.byref(bad))
         if rc:
-            e = PolypolishError(rc, L.pp_last_error(ctx._h).decode())
-            e.bad_block = None if bad.value == 0xFFFFFFFFFFFFFFFF else int(bad.value)
-            raise e
+            _raise(rc, L.pp_last_error(ctx._h).decode(), bad_block=_index(bad))
         dev, nb = C.c_void_p(), C.c_uint64(0)
         L.pp_bgzf_bytes(self._p, C.byref(dev), C.byref(nb))
         self.bytes_ptr, self.n_bytes = dev.value or 0, int(nb.value)
@@ -1112,47 +730,22 @@ class Bgzf:
     def host(self, lo=0, hi=None):
         hi = self.n_bytes if hi is None else min(int(hi), self.n_bytes)
         lo = min(int(lo), hi)
-        arr = np.zeros(hi - lo, np.uint8)
-        if arr.size:
-            self._ctx._chk(lib().pp_ctx_download(self._ctx._h, arr.ctypes.data, self.bytes_ptr + lo, arr.nbytes))
-        return arr
+        return self._ctx.download(self.bytes_ptr + lo, hi - lo, np.uint8)
 
     def bam_walk(self, start=0):
         L = lib()
         n, end = C.c_uint64(0), C.c_uint64(0)
         rc = L.pp_bgzf_bam_walk(self._p, int(start), C.byref(n), C.byref(end))
         if rc:
-            e = PolypolishError(rc, L.pp_last_error(self._ctx._h).decode())
-            e.n_rec, e.end = int(n.value), int(end.value)
-            raise e
+            _raise(rc, L.pp_last_error(self._ctx._h).decode(), n_rec=int(n.value), end=int(end.value))
         return L.pp_bgzf_rec_off(self._p) or 0, int(n.value), int(end.value)
 
-    def kernel_ms(self):
-        ms = C.c_float()
-        self._ctx._chk(lib().pp_bgzf_kernel_ms(self._p, C.byref(ms)))
-        return float(ms.value)
-
     def stage_ms(self):
-        f = lib().pp_bgzf_stage_ms_
-        f.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        ms = (C.c_float * 3)()
-        if f(self._p, ms):
-            raise PolypolishError(ERR_ARG, "the context had no profiling on when the blocks were inflated")
-        return {"inflate": float(ms[0]), "crc": float(ms[1]), "staging": float(ms[2]), "walk": float(ms[2])}
-
-    def close(self):
-        if self._p:
-            lib().pp_bgzf_free(self._p)
-            self._p = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        ms = self._stage_ms("pp_bgzf_stage_ms_", ("inflate", "crc", "staging"), " when the blocks were inflated")
+        return dict(ms, walk=ms["staging"])
 
 
-class BamRecords:
+class BamRecords(_Owned):
     """pp_bam_records: the alignment records of uncompressed BAM bytes as a raw batch in DEVICE memory, owned by this object.
       data, rec_off  mem = MEM_HOST: bytes / a uint8 array, and the records' offsets (None: the library walks the chain from offset 0);
                      MEM_DEVICE: data = (device address, n_bytes), rec_off = (device address of n uint64, n)
@@ -1165,34 +758,22 @@ class BamRecords:
       .host()        numpy copies of the arrays, and "name_off" / "name_len"
       .kernel_ms()   HIP-event time of the decode's kernels (the context had set_profiling on)
     A failing call raises PolypolishError with .bad_record."""
+    _free, _kernel_ms = "pp_bam_free", "pp_bam_kernel_ms"
 
     def __init__(self, ctx, data, rec_off=None, ref_map=None, mem=MEM_HOST):
         L = lib()
-        if mem == MEM_HOST:
-            b = _bam_bytes(data)
-            bp, n_bytes = (b.ctypes.data if len(b) else None), len(b)
-            o = None if rec_off is None else np.ascontiguousarray(rec_off, dtype=np.uint64)
-            n = 0 if o is None else len(o)
-            if o is not None and n == 0:
-                o = np.zeros(1, dtype=np.uint64)     # (an array without records still is one: no walk)
-            op = None if o is None else o.ctypes.data
-        else:
-            bp, n_bytes = int(data[0]), int(data[1])
-            op, n = (None, 0) if rec_off is None else (int(rec_off[0]), int(rec_off[1]))
+        bp, n_bytes, op, n, _keep = _bytes_and_offsets(data, rec_off, mem)
         m = None if ref_map is None else np.ascontiguousarray(ref_map, dtype=np.uint32)
-        self._p = C.c_void_p()
-        self._ctx = ctx
-        bad = C.c_uint64(0xFFFFFFFFFFFFFFFF)
+        super().__init__(ctx)
+        bad = _no_index()
         rc = L.pp_bam_records(ctx._h, bp, n_bytes, op, n, mem, m.ctypes.data if m is not None else None, len(m) - 1 if m is not None else 0,
                               C.byref(self._p), C.byref(bad))
         if rc:
-            e = PolypolishError(rc, L.pp_last_error(ctx._h).decode())
-            e.bad_record = None if bad.value == 0xFFFFFFFFFFFFFFFF else int(bad.value)
-            raise e
-        out = RawBatch()
+            _raise(rc, L.pp_last_error(ctx._h).decode(), bad_record=_index(bad))
+        out = self._view = RawBatch()
         L.pp_bam_raw(self._p, C.byref(out))
         self.n_rec, self.seq_bytes, self.n_cig_total = int(out.n_rec), int(out.seq_bytes), int(out.n_cig_total)
-        self._ptrs = {name: (C.cast(getattr(out, name), C.c_void_p).value or 0) for name, _ in RAW_FIELDS}
+        self._ptrs = _ptrs_of(out, RAW_FIELDS)
         self.read_id_ptr = L.pp_bam_read_id(self._p) or 0
         nb, nbytes, no, nl = C.c_void_p(), C.c_uint64(0), C.c_void_p(), C.c_void_p()
         L.pp_bam_names(self._p, C.byref(nb), C.byref(nbytes), C.byref(no), C.byref(nl))
@@ -1200,8 +781,7 @@ class BamRecords:
         self.n_bytes = int(nbytes.value)
         zp, n_al = C.c_void_p(), C.c_uint64(0)
         L.pp_bam_pass(self._p, C.byref(zp), C.byref(n_al))
-        self.zp = (np.ctypeslib.as_array(C.cast(zp, C.POINTER(C.c_uint8)), shape=(int(n_al.value),)).copy() if n_al.value
-                   else np.zeros(0, np.uint8))
+        self.zp = _host(zp.value, n_al.value, np.uint8)
 
     def raw(self):
         return dict(self._ptrs, n_rec=self.n_rec, seq_bytes=self.seq_bytes, n_cig_total=self.n_cig_total)
@@ -1209,34 +789,11 @@ class BamRecords:
     def names(self):
         return {"names": self._names, "n": self.n_rec, "n_bytes": self.n_bytes}
 
-    def _down(self, addr, n, dt):
-        arr = np.zeros(int(n), dtype=dt)
-        if arr.size and addr:
-            self._ctx._chk(lib().pp_ctx_download(self._ctx._h, arr.ctypes.data, addr, arr.nbytes))
-        return arr
-
     def host(self):
-        sizes = {"seq": self.seq_bytes, "cigar": self.n_cig_total}
-        out = {name: self._down(self._ptrs[name], sizes.get(name, self.n_rec), dt) for name, dt in RAW_FIELDS}
-        out["name_off"] = self._down(self._names[1], self.n_rec, np.uint64)
-        out["name_len"] = self._down(self._names[2], self.n_rec, np.uint32)
+        out = _read_batch(self._view, RAW_FIELDS, self._ctx)
+        out["name_off"] = self._ctx.download(self._names[1], self.n_rec, np.uint64)
+        out["name_len"] = self._ctx.download(self._names[2], self.n_rec, np.uint32)
         return out
-
-    def kernel_ms(self):
-        ms = C.c_float()
-        self._ctx._chk(lib().pp_bam_kernel_ms(self._p, C.byref(ms)))
-        return float(ms.value)
-
-    def close(self):
-        if self._p:
-            lib().pp_bam_free(self._p)
-            self._p = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _report_dict(rep):
@@ -1255,23 +812,11 @@ def filter_records(ctx, raw1, raw2, orientation="auto", low=0.1, high=99.9, mem=
     "n_cig_total").  contig is the RNAME as an id, compared for equality only: names that are not in the assembly need distinct
     ids.  Returns {"pass": (p1, p2), "counts": [(alignments, reads)] * 2, "report": dict}; p1 / p2 (uint8, one per aligned
     record) are gate_records' `passed`."""
-    L = lib()
-    batches, keep, n_rec = (RawBatch * 2)(), [], []
-    for f, raw in enumerate((raw1, raw2)):
-        if mem != MEM_DEVICE:
-            arrs = {k: np.ascontiguousarray(raw[k], dtype=dt) for k, dt in FILTER_RAW_FIELDS}
-            keep.append(arrs)
-            n, n_cig_total = len(arrs["flag"]), len(arrs["cigar"])
-            ptrs = {k: v.ctypes.data for k, v in arrs.items()}
-        else:
-            ptrs, n, n_cig_total = raw, int(raw["n_rec"]), int(raw["n_cig_total"])
-        batches[f] = RawBatch(n, ptrs["flag"], ptrs["read_id"], ptrs["contig"], ptrs["ref_start"], ptrs.get("nm"), ptrs.get("seq_off"),
-                              ptrs.get("seq_len"), ptrs["cig_off"], ptrs["n_cig"], ptrs.get("seq"), int(raw["seq_bytes"]) if mem == MEM_DEVICE else 0,
-                              ptrs["cigar"], n_cig_total)
-        n_rec.append(n)
-    passed = [np.zeros(n, dtype=np.uint8) for n in n_rec]  # (room for every record: the aligned ones are a prefix of it)
+    pairs = [_raw_batch(raw, mem != MEM_DEVICE, FILTER_RAW_FIELDS) for raw in (raw1, raw2)]  # (the arrays stay alive in here)
+    batches = (RawBatch * 2)(*[b for b, _ in pairs])
+    passed = [np.zeros(int(b.n_rec), dtype=np.uint8) for b in batches]  # (room for every record: the aligned ones are a prefix of it)
     cnt, rep = (FilterFileCounts * 2)(), FilterReport()
-    ctx._chk(L.pp_filter_records(ctx._h, batches, mem, orientation.encode(), low, high, passed[0].ctypes.data, passed[1].ctypes.data, cnt, C.byref(rep)))
+    ctx._chk(lib().pp_filter_records(ctx._h, batches, mem, orientation.encode(), low, high, passed[0].ctypes.data, passed[1].ctypes.data, cnt, C.byref(rep)))
     return {"pass": tuple(p[:int(c.alignments)].copy() for p, c in zip(passed, cnt)),
             "counts": [(int(c.alignments), int(c.reads)) for c in cnt], "report": _report_dict(rep)}
 
@@ -1298,102 +843,67 @@ def comm_unique_id() -> bytes:
     return buf.raw
 
 
-class FilterLoaded:
+# pp_filter_file's arrays; "cigar" holds n_cig_total entries, "grp_off" n_reads + 1, every other one n_aln
+_FILTER_FILE_FIELDS = (("ref_id", np.uint32), ("ref_start", np.uint32), ("flags", np.uint32), ("ref_end", np.uint64), ("cig_off", np.uint64),
+                       ("n_cig", np.uint32), ("cigar", np.uint32), ("read", np.uint32), ("grp_off", np.uint32), ("grp_idx", np.uint32))
+
+
+class _FilterLoad(_Owned):
+    """what FilterLoaded and FilterLoadedDevice share: .counts from the load's pp_filter_file_counts, and .input / .n_reads /
+    .files from the pp_filter_input the library hands out, read with `get` (_host or Context.download), without `skip`"""
+
+    def _loaded(self, rc, fc, msg):
+        self.counts = [(c.alignments, c.reads) if c.loaded else None for c in fc]
+        if rc:
+            self._p = C.c_void_p()
+            raise PolypolishError(rc, msg())
+
+    def _read_input(self, input_fn, get, skip):
+        self.input = FilterInput()
+        input_fn(self._p, C.byref(self.input))
+        self.n_reads = int(self.input.n_reads)
+        self.files = []
+        for d in self.input.file:
+            sizes = {"cigar": int(d.n_cig_total), "grp_off": self.n_reads + 1}
+            self.files.append({k: get(getattr(d, k), sizes.get(k, int(d.n_aln)), dt) for k, dt in _FILTER_FILE_FIELDS if k not in skip})
+
+
+class FilterLoaded(_FilterLoad):
     """Host half of the filter (pp_filter_load / pp_filter_write; no GPU needed): `files[f]` holds the SoA
     of pp_filter_file as numpy copies, `counts[f]` = (alignments, distinct read names)."""
+    _free = "pp_filter_loaded_free"
 
     def __init__(self, in1, in2):
         L = lib()
-        self._h = C.c_void_p()
+        super().__init__()
         err = C.create_string_buffer(1400)
         fc = (FilterFileCounts * 2)()
-        rc = L.pp_filter_load(str(in1).encode(), str(in2).encode(), C.byref(self._h), fc, err, 1400)
-        self.counts = [(c.alignments, c.reads) if c.loaded else None for c in fc]
-        if rc:
-            self._h = C.c_void_p()
-            raise PolypolishError(rc, err.value.decode())
-        self.input = FilterInput()
-        L.pp_filter_loaded_input(self._h, C.byref(self.input))
-        self.n_reads = int(self.input.n_reads)
-        self.files = []
-        for f in range(2):
-            d = self.input.file[f]
-            n = int(d.n_aln)
-
-            def arr(ptr, cnt, dt):
-                if not cnt or not ptr:
-                    return np.zeros(0, dtype=dt)
-                return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(np.ctypeslib.as_ctypes_type(dt))), shape=(cnt,)).copy()
-            self.files.append({
-                "ref_id": arr(d.ref_id, n, np.uint32), "ref_start": arr(d.ref_start, n, np.uint32),
-                "flags": arr(d.flags, n, np.uint32), "cig_off": arr(d.cig_off, n, np.uint64),
-                "n_cig": arr(d.n_cig, n, np.uint32), "cigar": arr(d.cigar, int(d.n_cig_total), np.uint32),
-                "read": arr(d.read, n, np.uint32), "grp_off": arr(d.grp_off, self.n_reads + 1, np.uint32),
-                "grp_idx": arr(d.grp_idx, n, np.uint32)})
+        rc = L.pp_filter_load(str(in1).encode(), str(in2).encode(), C.byref(self._p), fc, err, 1400)
+        self._loaded(rc, fc, lambda: err.value.decode())
+        self._read_input(L.pp_filter_loaded_input, _host, ("ref_end",))
 
     def write(self, f, passed, path):
         passed = np.ascontiguousarray(passed, dtype=np.uint8)
         err = C.create_string_buffer(1400)
         p_, f_ = C.c_uint64(), C.c_uint64()
-        rc = lib().pp_filter_write(self._h, f, passed.ctypes.data, str(path).encode(), C.byref(p_), C.byref(f_), err, 1400)
+        rc = lib().pp_filter_write(self._p, f, passed.ctypes.data, str(path).encode(), C.byref(p_), C.byref(f_), err, 1400)
         if rc:
             raise PolypolishError(rc, err.value.decode())
         return p_.value, f_.value
 
-    def close(self):
-        if self._h:
-            lib().pp_filter_loaded_free(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class FilterLoadedDevice:
+class FilterLoadedDevice(_FilterLoad):
     """pp_filter_load_device: the same load on the GPU; `files[f]` holds copies of the device arrays
     (ref_end instead of the CIGAR arrays), `counts[f]` = (alignments, distinct read names)."""
+    _free = "pp_filter_dev_free"
 
     def __init__(self, ctx, in1, in2):
         L = lib()
-        self._h = C.c_void_p()
+        super().__init__()
         fc = (FilterFileCounts * 2)()
-        rc = L.pp_filter_load_device(ctx._h, str(in1).encode(), str(in2).encode(), C.byref(self._h), fc)
-        self.counts = [(c.alignments, c.reads) if c.loaded else None for c in fc]
-        if rc:
-            self._h = C.c_void_p()
-            raise PolypolishError(rc, L.pp_last_error(ctx._h).decode())
-        self.input = FilterInput()
-        L.pp_filter_dev_input(self._h, C.byref(self.input))
-        self.n_reads = int(self.input.n_reads)
-        self.files = []
-        for f in range(2):
-            d = self.input.file[f]
-            n = int(d.n_aln)
-
-            def arr(ptr, cnt, dt):
-                a = np.zeros(cnt, dtype=dt)
-                if cnt and ptr:
-                    ctx._chk(L.pp_ctx_download(ctx._h, a.ctypes.data, ptr, a.nbytes))
-                return a
-            self.files.append({
-                "ref_id": arr(d.ref_id, n, np.uint32), "ref_start": arr(d.ref_start, n, np.uint32),
-                "flags": arr(d.flags, n, np.uint32), "ref_end": arr(d.ref_end, n, np.uint64),
-                "read": arr(d.read, n, np.uint32), "grp_off": arr(d.grp_off, self.n_reads + 1, np.uint32),
-                "grp_idx": arr(d.grp_idx, n, np.uint32)})
-
-    def close(self):
-        if self._h:
-            lib().pp_filter_dev_free(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        rc = L.pp_filter_load_device(ctx._h, str(in1).encode(), str(in2).encode(), C.byref(self._p), fc)
+        self._loaded(rc, fc, lambda: L.pp_last_error(ctx._h).decode())
+        self._read_input(L.pp_filter_dev_input, ctx.download, ("cig_off", "n_cig", "cigar"))
 
 
 class Context:
@@ -1420,6 +930,13 @@ class Context:
     def _chk(self, rc):
         if rc:
             raise PolypolishError(rc, lib().pp_last_error(self._h).decode())
+
+    def download(self, addr, n, dtype):
+        """n items of DEVICE memory at addr as a numpy array (pp_ctx_download); zeros when n == 0 or there is no address"""
+        arr = np.zeros(int(n), dtype=dtype)
+        if arr.size and addr:
+            self._chk(lib().pp_ctx_download(self._h, arr.ctypes.data, addr, arr.nbytes))
+        return arr
 
     def sync(self):
         self._chk(lib().pp_ctx_sync(self._h))
@@ -1497,10 +1014,7 @@ class Context:
         """(internal hook, pp_ctx_trust_mirrors_) every window-order mirror this context is given counts as one of the library's
         own: it is not compared with the arrays before the kernels read the records through it.  For callers that lay their
         batches out exactly as the library's ingests do (bench.py's resident job; tests/test_synthjob_cpu.py checks that it does)."""
-        f = lib().pp_ctx_trust_mirrors_
-        f.argtypes = [C.c_void_p, C.c_int]
-        f.restype = C.c_int
-        self._chk(f(self._h, int(bool(on))))
+        self._chk(lib().pp_ctx_trust_mirrors_(self._h, int(bool(on))))
 
     def took_direct_path(self):
         """True when the last pp_polish_finish took its bulk straight from the window-order mirror (pp_aln_batch.wo_run_end)."""
@@ -1663,18 +1177,14 @@ class Context:
                                                orientation.encode(), low, high, C.byref(opt), C.byref(rep), C.byref(out)))
         data = C.string_at(out.data, out.len) if out.len else b""
         lib().pp_bytes_free(C.byref(out))
-        return data, {"before": rep.before_count, "after": rep.after_count, "low": rep.low_threshold,
-                      "high": rep.high_threshold, "orientation": ("fr", "rf", "ff", "rr")[rep.orientation],
-                      "counts": list(rep.orientation_counts)}
+        return data, _report_dict(rep)
 
     def filter_files(self, in1, in2, out1, out2, orientation="auto", low=0.1, high=99.9, quiet=True):
         rep = FilterReport()
         self._chk(lib().pp_filter_files(self._h, str(in1).encode(), str(in2).encode(), str(out1).encode(),
                                         str(out2).encode(), orientation.encode(), low, high, int(quiet),
                                         C.byref(rep)))
-        return {"before": rep.before_count, "after": rep.after_count, "low": rep.low_threshold,
-                "high": rep.high_threshold, "orientation": ("fr", "rf", "ff", "rr")[rep.orientation],
-                "counts": list(rep.orientation_counts)}
+        return _report_dict(rep)
 
 
 _default_ctx = None

@@ -212,3 +212,127 @@ def test_a_second_decode_on_the_context_keeps_nothing(pp, ctx):
     bl, ol = bm.lay_out(large)
     check(pp, ctx, bl, ol)
     assert np.array_equal(check(pp, ctx, bs, os_)["seq"], want["seq"])
+
+
+# ---- the binding's shared helpers: one handle base, one download, one batch read-back ------------------------------------------------
+NO_PROFILING = {     # the library's text when kernel_ms() is asked of an object made without profiling
+    "BamOffsets": "pp_bam_offs_kernel_ms: the context had no profiling on when the chain was walked (pp_ctx_set_profiling)",
+    "BamRecords": "pp_bam_kernel_ms: the context had no profiling on when the records were decoded (pp_ctx_set_profiling)",
+    "Names": "pp_names_kernel_ms: the context had no profiling on at the table's last pp_names_ids (pp_ctx_set_profiling)",
+    "GatedBatch": "pp_gated_kernel_ms: the context had no profiling on when the batch was gated (pp_ctx_set_profiling)",
+    "PreparedBatch": "pp_prepared_kernel_ms: the context had no profiling on when the batch was prepared (pp_ctx_set_profiling)"}
+
+
+def _fetch(pp, c, addr, n, dt):
+    """n items at a device address, through pp_ctx_download spelled by hand"""
+    a = np.zeros(int(n), dt)
+    if a.size:
+        assert addr and pp.lib().pp_ctx_download(c._h, a.ctypes.data, addr, a.nbytes) == 0
+    return a
+
+
+def _fetch_batch(pp, c, ptrs, fields, n, seq_bytes, n_cig_total):
+    sizes = {"seq": seq_bytes, "cigar": n_cig_total}
+    return {k: _fetch(pp, c, ptrs[k], sizes.get(k, n), dt) for k, dt in fields}
+
+
+def _same_arrays(got, want):
+    assert list(got) == list(want)
+    for k in want:
+        a, b = np.asarray(got[k]), np.asarray(want[k])
+        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), k
+
+
+@pytest.mark.parametrize("profiling", (False, True))
+def test_every_owned_object_reads_back_what_a_hand_written_download_reads(pp, profiling):
+    """BamOffsets -> BamRecords -> Names.ids -> gate_records -> prepare_batch on device addresses, over three records -- an aligned
+    one, a secondary one of the same read with SEQ "*", an unaligned one (zp is shorter than n_rec) -- and over a BAM that is a
+    header only: host() of every object is what pp_ctx_download gives for the same pointers, the values are the models', close()
+    twice is harmless, and kernel_ms() needs the context's profiling."""
+    import gate_model as gm
+    import names_model as nm
+    from layout_check import same_records
+    M = (8 << 4)
+    recs = [bm.record(b"a", 0, 0, 5, [M], "ACGTACGT", bm.aux("NM", "C", 0)), bm.record(b"a", 256, 0, 20, [M], "", bm.aux("NM", "C", 1)),
+            bm.record(b"u", 4, -1, -1, [], "ACGT")]
+    hdr = bm.header_bytes([("c0", 64)], "@HD\tVN:1.6\n")
+    data = hdr + bm.lay_out(recs)[0]
+    at = bm.header(data)["records_at"]
+    want_off = np.array(bm.walk(data, at)[0], np.uint64)
+    want_raw = bm.decode(data, want_off)
+    want_raw["read_id"] = np.array(nm.ids({}, [b"a", b"a", b"u"]), np.uint64)
+    want_gate = gm.gate(want_raw)
+    assert len(want_off) == 3 and len(want_raw["zp"]) == 2 and want_raw["seq_len"].tolist() == [8, 0, 4] and want_gate["counts"] == (2, 2, 1)
+    contig_off = np.array([0, 64], np.uint64)
+    c = pp.Context(0)
+    c.set_profiling(profiling)
+    made = []
+    try:
+        (dp, nb), _, keep = on_device(data, want_off)
+        offs = pp.BamOffsets(c, (dp, nb), at, pp.MEM_DEVICE)
+        made.append(offs)
+        assert (offs.n_rec, offs.end) == (3, len(data))
+        got = offs.host()
+        assert got.dtype == np.uint64 and np.array_equal(got, want_off) and np.array_equal(got, _fetch(pp, c, offs.ptr, 3, np.uint64))
+
+        rec = pp.BamRecords(c, (dp, nb), (offs.ptr, offs.n_rec), None, pp.MEM_DEVICE)
+        made.append(rec)
+        table = pp.Names(c)
+        made.append(table)
+        ids = table.ids(**rec.names(), mem=pp.MEM_DEVICE, out=rec.read_id_ptr)
+        assert ids.dtype == np.uint64 and np.array_equal(ids, want_raw["read_id"]) and table.count == 2
+        assert np.array_equal(ids, _fetch(pp, c, rec.read_id_ptr, 3, np.uint64))
+        raw, names = rec.raw(), rec.names()["names"]
+        by_hand = _fetch_batch(pp, c, raw, pp.RAW_FIELDS, 3, rec.seq_bytes, rec.n_cig_total)
+        by_hand["name_off"], by_hand["name_len"] = _fetch(pp, c, names[1], 3, np.uint64), _fetch(pp, c, names[2], 3, np.uint32)
+        got = rec.host()
+        _same_arrays(got, by_hand)
+        bm.same(got, want_raw)
+        assert rec.zp.dtype == np.uint8 and np.array_equal(rec.zp, want_raw["zp"])
+
+        g = pp.gate_records(c, raw, mem=pp.MEM_DEVICE)
+        made.append(g)
+        got = g.host()
+        _same_arrays(got, _fetch_batch(pp, c, g.ptrs(), pp.REC_FIELDS, g.n_aln, g.seq_bytes, g.n_cig_total))
+        gm.same(got, want_gate["recs"])
+        assert g.counts == want_gate["counts"] and np.array_equal(g.orig(), want_gate["orig"]) and g.orig().dtype == np.uint32
+
+        p = pp.prepare_batch(c, contig_off, g.n_aln, g.ptrs(), g.seq_bytes, g.n_cig_total, pp.MEM_DEVICE)
+        made.append(p)
+        ptrs = p.ptrs()
+        by_hand = _fetch_batch(pp, c, ptrs, pp.REC_FIELDS, p.n_aln, p.seq_bytes, p.n_cig_total)
+        by_hand["seq4"] = _fetch(pp, c, ptrs["seq4"], (p.seq_bytes + 1) // 2, np.uint8)
+        by_hand["wo"] = _fetch(pp, c, ptrs["wo"], p.n_aln, pp.WO_DTYPE)
+        by_hand["wo_runs"] = np.array([p.n_aln], np.uint64)
+        got = p.host()
+        _same_arrays(got, by_hand)
+        src = want_gate["recs"]     # (same_records wants seq arrays of one length: the prepared rooms may take more than the gate's)
+        assert len(got["seq"]) >= len(src["seq"])
+        same_records(dict(src, seq=np.concatenate([src["seq"], np.zeros(len(got["seq"]) - len(src["seq"]), np.uint8)])), got)
+
+        # a BAM that is its header only, through the host forms: no record, and an offsets array without entries is still one
+        none = pp.BamOffsets(c, hdr, len(hdr))
+        made.append(none)
+        assert (none.n_rec, none.end) == (0, len(hdr)) and none.host().dtype == np.uint64 and len(none.host()) == 0
+        empty = pp.BamRecords(c, hdr, none.host())
+        made.append(empty)
+        got = empty.host()
+        bm.same(got, bm.decode(hdr, []))
+        _same_arrays(got, dict(_fetch_batch(pp, c, empty.raw(), pp.RAW_FIELDS, 0, 0, 0), name_off=np.zeros(0, np.uint64), name_len=np.zeros(0, np.uint32)))
+        assert (empty.n_rec, empty.seq_bytes, empty.n_cig_total, len(empty.zp)) == (0, 0, 0, 0)
+
+        for o in made:
+            if profiling and o is not empty:   # (a decode of no records runs no kernel and times none: it answers as without profiling)
+                ms = o.kernel_ms()
+                assert isinstance(ms, float) and ms >= 0, o
+            else:
+                with pytest.raises(pp.PolypolishError) as e:
+                    o.kernel_ms()
+                assert (e.value.code, e.value.msg) == (pp.ERR_ARG, NO_PROFILING[type(o).__name__]), o
+        del keep
+    finally:
+        for o in made[::-1]:
+            o.close()
+            o.close()
+            assert not o._p
+        c.close()

@@ -340,11 +340,8 @@ def test_slices_of_a_sam_file_start_on_read_group_boundaries(tmp_path):
     QNAME is empty; header, empty and unaligned lines neither join nor close a group).  Every cut the driver would make
     is checked against the grouping of the whole file, and the ingest of the slices, one after the other, gives the
     records of the whole file (same k per record)."""
-    import ctypes as C
     import polypolish_amd as pp
     L = pp.lib()
-    L.pp_sam_group_cut_.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64]
-    L.pp_sam_group_cut_.restype = C.c_uint64
     rng = np.random.default_rng(5)
     lines = ["@HD\tVN:1.6", "@SQ\tSN:c1\tLN:5000"]
     seq = "ACGT" * 10

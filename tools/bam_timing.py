@@ -12,7 +12,6 @@ a vectorised numpy encoder, one byte array per file, resident in HBM (an allocat
   tokenizer_stages_ms  (--text) the device tokenizer's own stage timers on the SAM text of the same job
 --out FILE writes the line to FILE as well.  Measurement only: no threshold is attached to any of it."""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -95,15 +94,6 @@ def encode_bam(S, lo, hi, chunk=1 << 18):
     return out, off.astype(np.uint64)
 
 
-def stage_ms(obj, hook, n):
-    f = getattr(pp.lib(), hook)
-    f.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-    ms = (C.c_float * n)()
-    if f(obj._p, ms):
-        raise RuntimeError("the context had no profiling on")
-    return [float(x) for x in ms]
-
-
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--mbp", type=float, default=5.0, help="assembly size (configs[1]: 5)")
@@ -134,14 +124,14 @@ def main():
         table = pp.Names(ctx)
         for tb, to, n_bytes, n_rec in files:
             rec = pp.BamRecords(ctx, (tb.data_ptr(), n_bytes), (to.data_ptr(), n_rec), None, pp.MEM_DEVICE)
-            ms = [x + y for x, y in zip(ms, stage_ms(rec, "pp_bam_stage_ms_", 3))]
-            ln = rec._down(rec._ptrs["seq_len"], rec.n_rec, np.uint32).astype(np.int64)
+            ms = [x + y for x, y in zip(ms, rec._stage_ms("pp_bam_stage_ms_", ("pass_a", "scans", "pass_b")).values())]
+            ln = ctx.download(rec._ptrs["seq_len"], rec.n_rec, np.uint32).astype(np.int64)
             b_bytes += int(((ln + 1) // 2).sum()) + rec.seq_bytes + 8 * rec.n_cig_total + 44 * rec.n_rec
             table.ids(**rec.names(), mem=pp.MEM_DEVICE, out=rec.read_id_ptr)
             names_ms += table.kernel_ms()
             g = pp.gate_records(ctx, rec.raw(), mem=pp.MEM_DEVICE)
-            gate_ms += stage_ms(g, "pp_gated_stage_ms_", 3)[2]
-            h_len = g._down(g._ptrs["seq_len"], g.n_aln, np.uint32)
+            gate_ms += g._stage_ms("pp_gated_stage_ms_", ("gates", "placement", "copy"))["copy"]
+            h_len = ctx.download(g._ptrs["seq_len"], g.n_aln, np.uint32)
             gate_bytes += int(h_len.sum(dtype=np.int64)) + g.seq_bytes + 8 * g.n_cig_total
             g.close()
             rec.close()

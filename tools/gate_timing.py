@@ -9,7 +9,6 @@ unaligned ones too, secondary records with SEQ "*"), one pp_raw_batch per file, 
   tokenizer_stages_ms   the tokenizer's own stage timers (bin/polypolish polish, PP_TIMING=1) on the SAM text of the same job
 --out FILE writes the line to FILE as well.  Measurement only: no threshold is attached to any of it."""
 import argparse
-import ctypes as C
 import json
 import os
 import re
@@ -39,15 +38,6 @@ def raw_of(job, lo, hi):
     ptrs = {k: v.data_ptr() for k, v in keep.items()}
     ptrs.update(n_rec=hi - lo, seq_bytes=keep["seq"].numel(), n_cig_total=keep["cigar"].numel())
     return ptrs, keep
-
-
-def stage_ms(g):
-    f = pp.lib().pp_gated_stage_ms_
-    f.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-    ms = (C.c_float * 3)()
-    if f(g._p, ms):
-        raise RuntimeError("the context had no profiling on")
-    return [float(x) for x in ms]
 
 
 def tokenizer_stages(job, tmp):
@@ -88,8 +78,8 @@ def main():
             ptrs, keep = raw_of(job, lo, hi)
             g = pp.gate_records(ctx, ptrs, mem=pp.MEM_DEVICE)
             tot += g.kernel_ms()
-            copy_ms += stage_ms(g)[2]
-            h_len = g._down(g._ptrs["seq_len"], g.n_aln, np.uint32)
+            copy_ms += g._stage_ms("pp_gated_stage_ms_", ("gates", "placement", "copy"))["copy"]
+            h_len = ctx.download(g._ptrs["seq_len"], g.n_aln, np.uint32)
             copy_bytes += int(h_len.sum(dtype=np.int64)) + g.seq_bytes + 8 * g.n_cig_total
             p = pp.prepare_batch(ctx, job["contig_off"], g.n_aln, g.ptrs(), g.seq_bytes, g.n_cig_total, pp.MEM_DEVICE)
             prep_ms += p.kernel_ms()

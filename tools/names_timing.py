@@ -44,12 +44,8 @@ def qnames(read):
 
 
 def stage_ms(table):
-    f = pp.lib().pp_names_stage_ms_
-    f.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-    ms = (C.c_float * 5)()
-    if f(table._p, ms):
-        raise RuntimeError("the context had no profiling on")
-    return dict(zip(("lookup", "rehash", "insert_rank", "entries_bytes", "ids"), (round(float(x), 4) for x in ms)))
+    ms = table._stage_ms("pp_names_stage_ms_", ("lookup", "rehash", "insert_rank", "entries_bytes", "ids"))
+    return {k: round(v, 4) for k, v in ms.items()}
 
 
 def on_device(call, dev):
