@@ -461,6 +461,50 @@ void pp_bam_pass(const pp_bam *b, const uint8_t **zp, uint64_t *n_aligned); /* H
 int pp_bam_kernel_ms(const pp_bam *b, float *ms);
 void pp_bam_free(pp_bam *b);
 
+/* The WRITE side of the record chain for a caller who holds BAM: the filter's verdicts written back as a BAM file, on the device --
+ * what `polypolish filter` does with SAM text (filter_sam, src/filter.rs:296-343: every line again, ZP:Z:fail appended to the aligned
+ * ones that failed), for records.  The files it makes go back through pp_bgzf_inflate ... pp_bam_records into polish: the reference's
+ * two-command workflow.  No command writes BAM either: this is a library call.
+ *   inputs       bytes[0, n_bytes): uncompressed BAM; records_at: where its header ends (pp_bam_header); rec_off[0, n_rec): the records,
+ *                as for pp_bam_records not necessarily adjacent, ordered or distinct; pass[0, n_pass): HOST memory whatever `mem`, one
+ *                byte per ALIGNED record (flag & 4 == 0) in index order -- the numbering of pp_filter_records' pass1 / pass2.
+ *   the stream   U' = bytes[0, records_at), then per record r in index order its 4 + block_size bytes as they are; an aligned record
+ *                whose verdict is 0 has block_size + 8 in its first word and the eight bytes 5A 50 5A 66 61 69 6C 00 (ZP, type Z,
+ *                "fail", NUL) behind its last byte.  An unaligned record is copied and takes no verdict (filter_sam's !a.is_aligned()
+ *                branch).  A failing record that already carries ZP:Z:fail gets a second one: the reference pushes the field without
+ *                looking.  `pass` is the FILTER'S OWN verdict, NOT ANDed with pp_bam_pass: a record that came with the tag and passes
+ *                keeps its one tag, exactly as its SAM line would.
+ *   the file     U' cut every 65,280 bytes (0xff00, htslib's payload size; the last piece is shorter, an empty U' has none), each piece
+ *                one BGZF block around one STORED DEFLATE block: the 18-byte header 1f 8b 08 04 00000000 00 ff 0600 42 43 0200 BSIZE
+ *                with BSIZE = len + 30, then 01 LEN ~LEN, the bytes, CRC32, ISIZE -- len + 31 bytes, so block b starts at b * 65,311 --
+ *                and the 28-byte EOF block behind the last one.  Level-0 BGZF, which every BAM reader takes; no compression.
+ *   memory       mem = PP_MEM_HOST or PP_MEM_DEVICE holds for `bytes` and `rec_off`.  Host bytes are uploaded and the copy is released
+ *                before the call returns; device bytes are borrowed for the call only.  The object owns the output only.
+ *   validation   on the device before anything is read through a record, with no sum that could wrap; no byte outside [0, n_bytes) is
+ *                loaded, by a wide load either: a PP_MEM_DEVICE array may end where its allocation ends.  PP_ERR_ARG with *bad_record
+ *                (may be NULL) = the first such record in index order, and no object: a rec_off outside the array or the array ending
+ *                inside the block_size word; block_size < 32; a record running past n_bytes (pp_bam_walk's three verdicts).  Also
+ *                PP_ERR_ARG: records_at > n_bytes, null arguments, PP_MEM_PEER, pass == NULL with aligned records present, n_pass other
+ *                than the number of aligned records -- reported only once the records are free of the defects above, as pp_batch_gate
+ *                does.  PP_ERR_LIMIT: 2^32-1 or more records, n_bytes >= 2^40, a block_size above 0xFFFFFFF7 (*bad_record = it).
+ *   edge cases   n_rec == 0 yields the framed header alone; n_rec == 0 with records_at == 0 the EOF block alone.
+ * The context's stream has been synchronised when the call returns: host inputs may be released.
+ *   pp_bam_out_bytes      the file (DEVICE, borrowed until pp_bam_out_free): pp_bgzf_inflate(..., blk_off[b] = b * 65,311, PP_MEM_DEVICE)
+ *                         reads it back
+ *   pp_bam_out_counts     aligned records that passed, that failed, and the blocks without the EOF block
+ *   pp_bam_out_write      downloads the file in slices and writes it to `path`; a path that cannot be created or written: PP_ERR_QUIT
+ *                         "unable to write alignments to ..." in pp_last_error(ctx), the code and the words of pp_filter_write
+ *   pp_bam_out_kernel_ms  as pp_gated_kernel_ms
+ * The object belongs to its context and is freed before it. */
+typedef struct pp_bam_out pp_bam_out;
+int pp_bam_tagged(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, uint64_t records_at, const uint64_t *rec_off, uint64_t n_rec,
+                  int mem, const uint8_t *pass, uint64_t n_pass, pp_bam_out **out, uint64_t *bad_record);
+void pp_bam_out_bytes(const pp_bam_out *o, const uint8_t **dev, uint64_t *n_bytes); /* DEVICE, borrowed until pp_bam_out_free */
+void pp_bam_out_counts(const pp_bam_out *o, uint64_t *pass_count, uint64_t *fail_count, uint64_t *n_blocks); /* n_blocks without the EOF block */
+int pp_bam_out_write(const pp_bam_out *o, const char *path); /* download in slices, write the file */
+int pp_bam_out_kernel_ms(const pp_bam_out *o, float *ms);
+void pp_bam_out_free(pp_bam_out *o);
+
 /* Per-contig figures the reference prints to stderr (src/polish.rs:206-227). */
 typedef struct {
     uint64_t polished_len;     /* bytes of the polished sequence                      */

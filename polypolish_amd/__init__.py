@@ -796,6 +796,51 @@ class BamRecords(_Owned):
         return out
 
 
+class BamTagged(_Owned):
+    """pp_bam_tagged: the filter's verdicts written back as a BAM file (level-0 BGZF) in DEVICE memory, owned by this object.
+      data, rec_off  mem = MEM_HOST: bytes / a uint8 array of uncompressed BAM, and the records' offsets; MEM_DEVICE: data = (device
+                     address, n_bytes), rec_off = (device address of n uint64, n), both borrowed for the call
+      records_at     where the header ends (bam_header(...)["records_at"])
+      passed         None or one byte per ALIGNED record (host): the filter's own verdict, filter_records(...)["pass"][f] -- not ANDed
+                     with BamRecords.zp
+      .n_bytes, .bytes_ptr   the file: Bgzf(ctx, (t.bytes_ptr, t.n_bytes), (blk_off_ptr, n_blocks), mem=MEM_DEVICE) with blk_off[b] =
+                     b * 65,311 reads it back
+      .counts        (passed, failed, blocks without the EOF block)
+      .host(lo, hi)  a numpy copy of the file's bytes [lo, hi) (a download)
+      .write(path)   pp_bam_out_write: the file on disk
+      .kernel_ms()   HIP-event time of the kernels (the context had set_profiling on); .stage_ms(): pass_a | scans | pass_b
+    A failing call raises PolypolishError with .bad_record."""
+    _free, _kernel_ms = "pp_bam_out_free", "pp_bam_out_kernel_ms"
+
+    def __init__(self, ctx, data, records_at, rec_off, passed, mem=MEM_HOST):
+        L = lib()
+        bp, n_bytes, op, n, _keep = _bytes_and_offsets(data, rec_off, mem)
+        v = None if passed is None else np.ascontiguousarray(passed, dtype=np.uint8)
+        super().__init__(ctx)
+        bad = _no_index()
+        rc = L.pp_bam_tagged(ctx._h, bp, n_bytes, int(records_at), op, n, mem, v.ctypes.data if v is not None else None,
+                             len(v) if v is not None else 0, C.byref(self._p), C.byref(bad))
+        if rc:
+            _raise(rc, L.pp_last_error(ctx._h).decode(), bad_record=_index(bad))
+        dev, nb = C.c_void_p(), C.c_uint64(0)
+        L.pp_bam_out_bytes(self._p, C.byref(dev), C.byref(nb))
+        self.bytes_ptr, self.n_bytes = dev.value or 0, int(nb.value)
+        p, f, k = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L.pp_bam_out_counts(self._p, C.byref(p), C.byref(f), C.byref(k))
+        self.counts = (int(p.value), int(f.value), int(k.value))
+
+    def host(self, lo=0, hi=None):
+        hi = self.n_bytes if hi is None else min(int(hi), self.n_bytes)
+        lo = min(int(lo), hi)
+        return self._ctx.download(self.bytes_ptr + lo, hi - lo, np.uint8)
+
+    def write(self, path):
+        self._ctx._chk(lib().pp_bam_out_write(self._p, os.fsencode(path)))
+
+    def stage_ms(self):
+        return self._stage_ms("pp_bam_out_stage_ms_", ("pass_a", "scans", "pass_b"), " when the records were tagged")
+
+
 def _report_dict(rep):
     return {"before": int(rep.before_count), "after": int(rep.after_count), "low": int(rep.low_threshold), "high": int(rep.high_threshold),
             "orientation": ("fr", "rf", "ff", "rr")[rep.orientation] if 0 <= rep.orientation < 4 else None,

@@ -145,6 +145,12 @@ SIGNATURES = {
     "pp_bam_pass": (None, [_vp, _pvp, _pu64]),
     "pp_bam_kernel_ms": (_i, [_vp, _pf32]),
     "pp_bam_free": (None, [_vp]),
+    "pp_bam_tagged": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _i, _vp, _u64, _pvp, _pu64]),
+    "pp_bam_out_bytes": (None, [_vp, _pvp, _pu64]),
+    "pp_bam_out_counts": (None, [_vp, _pu64, _pu64, _pu64]),
+    "pp_bam_out_write": (_i, [_vp, _str]),
+    "pp_bam_out_kernel_ms": (_i, [_vp, _pf32]),
+    "pp_bam_out_free": (None, [_vp]),
     "pp_polish_set_emit": (_i, [_vp, _vp, _vp]),
     "pp_polish_begin": (_i, [_vp, _u32, _vp, _vp, _i, _P(Params)]),
     "pp_polish_add": (_i, [_vp, _P(AlnBatch), _i]),
@@ -226,6 +232,7 @@ HOOKS = {
     "pp_names_stage_ms_": (_i, [_vp, _pf32]),       # float[5]
     "pp_bgzf_stage_ms_": (_i, [_vp, _pf32]),        # float[3]
     "pp_bam_stage_ms_": (_i, [_vp, _pf32]),         # float[3]
+    "pp_bam_out_stage_ms_": (_i, [_vp, _pf32]),     # float[3]
     "pp_bam_offs_stage_ms_": (_i, [_vp, _pf32]),    # float[3]
     "pp_bam_offs_stats_": (_i, [_vp, _pu64]),       # uint64[4]
     "pp_bam_walk_geometry_": (None, [_pu32] * 3),

@@ -1,0 +1,529 @@
+// pp_bam_out.hip -- pp_bam_tagged: the filter's verdicts written back as a BAM file, on the device.  The WRITE side of the record chain
+// for a caller who holds BAM: from the uncompressed BAM bytes in device memory, the records' offsets and one verdict byte per aligned
+// record it makes what `polypolish filter` makes of SAM text (filter_sam, src/filter.rs:296-343) -- every record again, ZP:Z:fail
+// appended to the aligned ones that failed -- framed as level-0 BGZF, as bytes in device memory; pp_bam_out_write puts them on disk.
+//
+// The uncompressed output U' is bytes[0, records_at), then per record r in index order its 4 + block_size bytes; a failing record has
+// block_size + 8 in its first word and the eight bytes Z P Z f a i l NUL behind its last.  The file is U' cut every 65,280 bytes,
+// each piece one BGZF block around one stored DEFLATE block (pp_bgzf_host.h: len + 31 bytes, block b at b * 65,311), then the EOF block.
+//   k_tag_scan    pass A, one lane per record: the record's range (pp_bam_host::step_kind: the walk's own verdict, nothing read
+//                 through an offset before it is checked, no sum that could wrap), the flag at record offset 18, and the
+//                 workgroups' numbers of aligned records.  A defect is status[0] = record << 8 | kind by atomicMin: the first
+//                 record in index order wins; a block_size that + 8 does not fit its word the same way in status[1]
+//   k_tag_len     the aligned records numbered by the workgroup scan of pp_dev.h over k_colscan's bases, the verdict at that rank,
+//                 the output length block_size + 8 fail (the 4 bytes of the word are added per index: the sum of a workgroup stays
+//                 inside the scan's 64 bits whatever the records hold); its sums, then start[R]: where source R starts in U', R = 0
+//                 the header as a pseudo-record, R = r + 1 record r, start[n_rec + 1] = |U'|
+//   k_tag_frame   pass B, the hot kernel: ONE WORKGROUP PER OUTPUT BLOCK.  The block's whole image -- header, stored-block prefix,
+//                 payload, footer -- is put together in LDS at the 16-byte phase of its place in the file (b * 65,311 is odd):
+//                 wave 0 finds the source that covers the block's first byte (a 64-ary search in start[], four rounds for 2^24
+//                 records), the workgroup takes the starts inside the block into LDS (at most 1,814: a record is 36 bytes or more),
+//                 then every lane owns 16-byte pieces of the image.  A piece that lies inside one source's verbatim bytes is one
+//                 16-byte load at the source's alignment; a piece over a seam (a record's end, the appended bytes, the patched
+//                 block_size word, the block's own header and footer) touches at most two sources and is put together from one
+//                 load of at most 16 bytes per source that stays inside the array.  A lane's four pieces are loaded level by
+//                 level (the records' offsets, then the bytes), so it waits for two round trips and not for two per piece.  The
+//                 CRC32 runs over LDS: every lane the byte table over 68 bytes (17 words apart: no bank conflict),
+//                 slices counted from the payload's END so that every right-hand side of the combination tree has a length known to
+//                 the compiler (pp_crc.h), six steps in the wave and four over the sixteen waves.  The image then leaves with 16-byte
+//                 aligned stores, its first and last bytes byte by byte.  Every input byte is read from memory once and every output
+//                 byte written once.  Workgroup n_blocks writes the EOF block.
+// No byte outside [0, n_bytes) is loaded: a wide load is issued only inside a record that pass A found inside the array, or inside
+// the header (records_at <= n_bytes).
+#include "pp_bam_host.h"
+#include "pp_bgzf_host.h"
+#include "pp_crc.h"
+#include "pp_dev.h"
+
+#include <fcntl.h>
+#include <unistd.h>
+
+struct pp_bam_out {
+    pp_ctx *ctx = nullptr;
+    void *d_out = nullptr;  // DEVICE: the file
+    uint64_t n_out = 0;
+    uint64_t pass_count = 0, fail_count = 0, n_blocks = 0;
+    bool timed = false;
+    float ms[3] = {0.f, 0.f, 0.f};  // pass A | the scans | pass B
+};
+
+namespace {
+
+namespace hb = pp_bgzf_host;
+
+constexpr u32 TAG_BLOCK = 1024;           // records per workgroup of pass A, threads of pass B
+constexpr u32 PAY = hb::STORE_PAYLOAD, HEAD = hb::STORE_HEAD, BLK = hb::STORE_BLOCK;
+constexpr u32 IMG16 = (15u + BLK + 15u) / 16u;  // the image of a block at any 16-byte phase, in 16-byte pieces
+constexpr u32 TRIPS = (IMG16 + TAG_BLOCK - 1u) / TAG_BLOCK;  // pieces per lane
+constexpr u32 REL_CAP = 2048;             // starts inside one block kept in LDS (at most 65,280 / 36 + 1, and one behind)
+constexpr u32 REL_FAR = 0x7FFFFFFFu;      // a start that far behind the block's first byte, or none
+constexpr u32 SLICE = 68;                 // bytes per lane of the CRC: 17 words, so that the lanes' words fall into 32 banks
+constexpr u64 TAG_BYTES = 0x006C6961665A505Aull;  // Z P Z f a i l NUL, low byte first
+constexpr u32 TL_BLOCK_SIZE = 1;          // status[1]: block_size + 8 does not fit 32 bits
+
+__device__ __forceinline__ u32 ld32(const u8 *__restrict__ p, u64 at) {  // four bytes at any alignment, inside a checked range
+    u32 w;
+    __builtin_memcpy(&w, p + at, 4);
+    return w;
+}
+
+// ---- pass A ----------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(TAG_BLOCK) void k_tag_scan(u32 n_rec, const u8 *__restrict__ B, u64 N, const u64 *__restrict__ rec_off,
+                                                        u8 *__restrict__ aligned, u64 *__restrict__ blk_al, u64 *__restrict__ status) {
+    __shared__ u64 s_w[TAG_BLOCK / 64];
+    const u64 r = (u64)blockIdx.x * TAG_BLOCK + threadIdx.x;
+    u32 al = 0;
+    if (r < n_rec) {
+        const u64 o = rec_off[r];
+        const u64 left = o <= N ? N - o : 0;  // (an offset behind the array: the walk's "ends inside the block_size word")
+        const u32 bs = left >= 4 ? ld32(B, o) : 0u;
+        const u32 kind = pp_bam_host::step_kind(left, bs);
+        if (kind) report(status, (r << 8) | kind);
+        else {
+            if (bs > 0xFFFFFFF7u) report(status + 1, (r << 8) | TL_BLOCK_SIZE);
+            al = (B[o + 18u] & 4u) ? 0u : 1u;  // the flag's low byte: inside the 32 bytes of the fixed part
+        }
+        aligned[r] = (u8)al;
+    }
+    u64 total;
+    (void)block_scan_excl64<TAG_BLOCK>(al, s_w, &total);
+    if (threadIdx.x == 0) blk_al[blockIdx.x] = total;
+}
+
+// PLACE == false: the workgroups' output bytes (without the 4 of each block_size word) and failing records (blk2: two words per
+// workgroup).  PLACE == true: blk2 holds their exclusive scan: start[R] of every source.
+template <bool PLACE>
+__global__ __launch_bounds__(TAG_BLOCK) void k_tag_len(u32 n_rec, const u8 *__restrict__ B, const u64 *__restrict__ rec_off, const u8 *__restrict__ aligned,
+                                                       const u64 *__restrict__ al_base, const u8 *__restrict__ pass, u64 records_at,
+                                                       u64 *__restrict__ blk2, u64 *__restrict__ start) {
+    __shared__ u64 s_w[TAG_BLOCK / 64];
+    const u64 r = (u64)blockIdx.x * TAG_BLOCK + threadIdx.x;
+    const u32 al = r < n_rec ? aligned[r] : 0u;
+    u64 t_al, t_len, t_fail;
+    const u64 rank = al_base[blockIdx.x] + block_scan_excl64<TAG_BLOCK>(al, s_w, &t_al);
+    const u32 fail = (al && pass[rank] == 0) ? 1u : 0u;
+    const u32 len = r < n_rec ? ld32(B, rec_off[r]) + 8u * fail : 0u;  // (block_size <= 0xFFFFFFF7: pass A)
+    const u64 ex_len = block_scan_excl64<TAG_BLOCK>(len, s_w, &t_len);
+    (void)block_scan_excl64<TAG_BLOCK>(fail, s_w, &t_fail);
+    u64 *const mine = blk2 + 2ull * blockIdx.x;
+    if (!PLACE) {
+        if (threadIdx.x == 0) { mine[0] = t_len; mine[1] = t_fail; }
+        return;
+    }
+    if (r >= n_rec) return;
+    const u64 at = records_at + 4ull * r + mine[0] + ex_len;
+    if (r == 0) start[0] = 0;
+    start[r + 1] = at;
+    if (r + 1 == n_rec) start[r + 2] = at + 4ull + len;
+}
+
+// ---- pass B ----------------------------------------------------------------------------------------------------------------------
+struct Piece16 {  // sixteen bytes of the image, low byte first
+    u64 lo, hi;
+    // `v` holds bytes for the positions at, at + 1, ... (its low byte first); those below `end` are taken
+    __device__ __forceinline__ void put(u64 v_lo, u64 v_hi, u32 at, u32 end) {
+        const u32 sh = 8u * at;  // < 128
+        u64 a, b;
+        if (sh == 0) { a = v_lo; b = v_hi; }
+        else if (sh < 64u) { a = v_lo << sh; b = (v_hi << sh) | (v_lo >> (64u - sh)); }
+        else { a = 0; b = v_lo << (sh - 64u); }
+        if (end < 8u) { a &= (1ull << (8u * end)) - 1ull; b = 0; }
+        else if (end < 16u) b &= (1ull << (8u * (end - 8u))) - 1ull;
+        lo |= a;
+        hi |= b;
+    }
+};
+
+// sixteen bytes from `at`, of which `need` >= 1 are wanted and lie inside the array; the array's last bytes byte by byte
+__device__ __forceinline__ void load16(const u8 *__restrict__ B, u64 N, u64 at, u32 need, u64 *lo, u64 *hi) {
+    if (N - at >= 16u) {
+        u64 v[2];
+        __builtin_memcpy(v, B + at, 16);  // (any alignment: one global_load_dwordx4)
+        *lo = v[0];
+        *hi = v[1];
+    } else {
+        u64 a = 0, b = 0;
+        for (u32 j = 0; j < need; j++) {
+            if (j < 8u) a |= (u64)B[at + j] << (8u * j); else b |= (u64)B[at + j] << (8u * (j - 8u));
+        }
+        *lo = a;
+        *hi = b;
+    }
+}
+
+struct FrameArgs {
+    const u8 *bytes;
+    u64 n_bytes;
+    const u64 *rec_off;
+    const u64 *start;  // n_rec + 2 entries
+    u32 n_rec;
+    u64 total;         // |U'|
+    u64 n_blocks;
+    u8 *out;
+};
+
+__global__ __launch_bounds__(TAG_BLOCK, 8) void k_tag_frame(FrameArgs A) {
+    __shared__ uint4 s_img[IMG16];
+    __shared__ u32 s_rel[REL_CAP];
+    __shared__ u32 s_tab[256];
+    __shared__ u32 s_wave[TAG_BLOCK / 64];
+    __shared__ u64 s_first[2];
+    const u64 b = blockIdx.x;
+    const u32 t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    u8 *const dst = A.out + b * (u64)BLK;
+    if (b == A.n_blocks) {  // the EOF block, behind the last block's last byte
+        if (t < hb::EOF_SIZE) A.out[A.total + (u64)hb::STORE_EXTRA * A.n_blocks + t] = hb::eof_byte(t);
+        return;
+    }
+    const u8 *__restrict__ const B = A.bytes;
+    const u64 *__restrict__ const start = A.start;
+    const u64 lo = b * (u64)PAY;
+    const u32 len = (u32)min((u64)PAY, A.total - lo);
+    const u32 ph = (u32)((b * (u64)BLK) & 15u);  // image byte i is block byte i - ph
+    u8 *const img8 = (u8 *)s_img;
+    const u32 *const img32 = (const u32 *)s_img;
+
+    // ---- the source that covers the block's first byte: the last R with start[R] <= lo (start[0] = 0, start[n_rec + 1] = |U'| > lo)
+    crc_table_fill(s_tab, t, TAG_BLOCK);
+    if (wave == 0) {
+        u64 a = 0, z = (u64)A.n_rec + 2u;
+        while (z - a > 1u) {  // (every round cuts the range to a 64th, rounded up)
+            const u64 step = (z - a + 63u) / 64u, at = a + lane * step;
+            const u64 m = __ballot(at < z && start[at] <= lo);  // a prefix of the lanes, lane 0 among them
+            const u32 h = 63u - (u32)__clzll(m);
+            a += h * step;
+            z = min(z, a + step);
+        }
+        if (lane == 0) { s_first[0] = a; s_first[1] = lo - start[a]; }
+    }
+    __syncthreads();
+    const u64 R0 = s_first[0], back = s_first[1];  // the block's first byte is byte `back` of source R0
+    // ---- the starts behind it, relative to the block: s_rel[i] belongs to source R0 + 1 + i; one of the first 1,815 lies behind the block
+    u32 n_rel = 0;
+    for (u32 base = 0; base < REL_CAP; base += TAG_BLOCK) {
+        const u64 R = R0 + 1u + base + t;
+        s_rel[base + t] = R <= (u64)A.n_rec + 1u ? (u32)min(start[R] - lo, (u64)REL_FAR) : REL_FAR;
+        n_rel = base + TAG_BLOCK;
+        __syncthreads();
+        if (s_rel[n_rel - 1u] >= len) break;  // (the same for every thread)
+    }
+    // the number of starts at or below payload offset q: q belongs to source R0 + that number
+    auto source_of = [&](u32 q) {
+        u32 at = 0, n = n_rel;
+        while (n) {
+            const u32 half = n >> 1;
+            if (s_rel[at + half] <= q) { at += half + 1u; n -= half + 1u; }
+            else n = half;
+        }
+        return at;
+    };
+
+    // a piece over a seam: the block's own head and foot, a record's end, the appended bytes, the patched word.  Its payload bytes lie
+    // in at most two sources (a record is 36 bytes or more); what both need is loaded together: their starts and offsets, then their
+    // block_size words and bytes.
+    auto seam = [&](u32 k) {
+        Piece16 Q{0, 0};
+        const int j0 = (int)(16u * k) - (int)ph;  // the piece's first byte in the block
+        u32 i = 0;
+        for (; i < 16u && j0 + (int)i < (int)HEAD; i++)
+            if (j0 + (int)i >= 0) Q.put(hb::store_head_byte((u32)(j0 + (int)i), len), 0, i, i + 1u);
+        const int end_in = min((int)16, (int)(HEAD + len) - j0);  // the payload's bytes of this piece: [i, i_end); the foot stays zero
+        const u32 i_end = end_in > 0 ? (u32)end_in : 0u;
+        if (i >= i_end) return Q;
+        const u32 q = (u32)(j0 + (int)i) - HEAD;
+        const u64 Ra = R0 + source_of(q), last = (u64)A.n_rec + 1u;
+        const u64 u0 = lo + q, u1 = u0 + (i_end - i);  // the bytes of U' this piece holds
+        u64 Sx[3], ox[2] = {0, 0}, v_lo[2] = {0, 0}, v_hi[2] = {0, 0};
+        u32 bsx[2] = {0, 0};
+#pragma unroll
+        for (u32 s = 0; s < 3u; s++) Sx[s] = start[min(Ra + s, last)];
+        if (A.n_rec) {
+#pragma unroll
+            for (u32 s = 0; s < 2u; s++) ox[s] = A.rec_off[min(max(Ra + s, (u64)1) - 1u, (u64)A.n_rec - 1u)];
+        }
+#pragma unroll
+        for (u32 s = 0; s < 2u; s++) {
+            const u64 R = Ra + s, S = Sx[s], a = max(u0, S), z = min(u1, Sx[s + 1u]);
+            if (R > A.n_rec || a >= z) continue;
+            if (R == 0) load16(B, A.n_bytes, a, (u32)(z - a), &v_lo[s], &v_hi[s]);  // the header: its bytes are where they were
+            else {
+                bsx[s] = ld32(B, ox[s]);
+                const u64 from = ox[s] + (max(a, S + 4u) - S);  // (behind the record's bytes where the piece holds only appended ones)
+                if (from < A.n_bytes) load16(B, A.n_bytes, from, (u32)min((u64)16, A.n_bytes - from), &v_lo[s], &v_hi[s]);
+            }
+        }
+#pragma unroll
+        for (u32 s = 0; s < 2u; s++) {
+            const u64 R = Ra + s, S = Sx[s], E = Sx[s + 1u], a = max(u0, S), z = min(u1, E);
+            if (R > A.n_rec || a >= z) continue;
+            if (R == 0) {
+                Q.put(v_lo[s], v_hi[s], i + (u32)(a - u0), i + (u32)(z - u0));
+                continue;
+            }
+            const u64 bs = bsx[s], body = S + 4u, tail = body + bs;  // the word | the record's bytes | the appended bytes
+            if (a < body) Q.put((u64)(bsx[s] + (E - S != 4ull + bs ? 8u : 0u)) >> (8u * (u32)(a - S)), 0, i + (u32)(a - u0), i + (u32)(min(z, body) - u0));
+            const u64 va = max(a, body), vz = min(z, tail);
+            if (va < vz) Q.put(v_lo[s], v_hi[s], i + (u32)(va - u0), i + (u32)(vz - u0));
+            const u64 ta = max(a, tail);
+            if (ta < z) Q.put(TAG_BYTES >> (8u * (u32)(ta - tail)), 0, i + (u32)(ta - u0), i + (u32)(z - u0));
+        }
+        return Q;
+    };
+
+    // ---- the image, 16 bytes per lane and trip.  The loads of all four trips are issued level by level -- the records' offsets, then
+    // the bytes -- so that a lane waits for two round trips, not for two per trip.
+    const u32 n_piece = (ph + len + hb::STORE_EXTRA + 15u) / 16u;
+    u64 at[TRIPS], o[TRIPS];   // the piece's first byte in its source; the source record's index, then its offset (the header: 0)
+    u32 fast = 0, in_rec = 0;  // per trip: one load does it; ... from a record
+#pragma unroll
+    for (u32 j = 0; j < TRIPS; j++) {
+        const u32 k = t + j * TAG_BLOCK;
+        const int q0 = (int)(16u * k) - (int)ph - (int)HEAD;  // the piece's first byte in the payload
+        at[j] = 0;
+        o[j] = 0;
+        if (k < n_piece && q0 >= 0 && (u32)q0 + 16u <= len) {
+            const u32 idx = source_of((u32)q0), e = s_rel[idx];
+            const u64 d = idx ? (u64)((u32)q0 - s_rel[idx - 1u]) : (u64)(u32)q0 + back;  // the piece's first byte in its source
+            if (R0 + idx == 0) {  // the header
+                if ((u32)q0 + 16u <= e) { at[j] = d; fast |= 1u << j; }
+            } else if (d >= 4u && (u32)q0 + 24u <= e) {  // behind the block_size word, in front of the last 8 bytes whatever they are
+                at[j] = d;
+                o[j] = R0 + idx - 1u;
+                fast |= 1u << j;
+                in_rec |= 1u << j;
+            }
+        }
+    }
+#pragma unroll
+    for (u32 j = 0; j < TRIPS; j++)
+        if ((in_rec >> j) & 1u) o[j] = A.rec_off[o[j]];
+    Piece16 P[TRIPS];
+#pragma unroll
+    for (u32 j = 0; j < TRIPS; j++) {
+        P[j] = Piece16{0, 0};
+        if ((fast >> j) & 1u) load16(B, A.n_bytes, o[j] + at[j], 16, &P[j].lo, &P[j].hi);
+    }
+#pragma unroll
+    for (u32 j = 0; j < TRIPS; j++) {
+        const u32 k = t + j * TAG_BLOCK;
+        if (k >= n_piece) break;
+        if (!((fast >> j) & 1u)) P[j] = seam(k);
+        s_img[k] = make_uint4((u32)P[j].lo, (u32)(P[j].lo >> 32), (u32)P[j].hi, (u32)(P[j].hi >> 32));
+    }
+    __syncthreads();
+
+    // ---- the CRC32 of the payload: thread T owns the 68 bytes that end 68 (1023 - T) bytes in front of the payload's end
+    const int p0 = (int)(ph + HEAD), p1 = p0 + (int)len;
+    const int hi_at = p1 - (int)(SLICE * (TAG_BLOCK - 1u - t)), lo_at = hi_at - (int)SLICE;
+    u32 c = 0;  // the CRC32 of no bytes
+    if (hi_at > p0) {
+        c = 0xFFFFFFFFu;
+        if (lo_at >= p0) {
+            const u32 w0 = (u32)lo_at >> 2, sh = (u32)lo_at & 3u;  // (sh: the same for every thread)
+            u32 prev = img32[w0];
+#pragma unroll
+            for (u32 j = 0; j < SLICE / 4u; j++) {
+                const u32 next = img32[w0 + j + 1u];
+                c = crc_word(s_tab, c, __builtin_amdgcn_alignbyte(next, prev, sh));
+                prev = next;
+            }
+        } else {
+            for (int i = p0; i < hi_at; i++) c = crc_byte(s_tab, c, img8[i]);
+        }
+        c = ~c;
+    }
+    constexpr X8N2K<SLICE, 10> MUL = X8N2K<SLICE, 10>();  // x^(8 * 68 * 2^k): a right-hand side of 2^k whole slices
+#pragma unroll
+    for (u32 k = 0; k < 6u; k++) {  // lane i takes in lane i + 2^k: crc(A B) = crc(A) x^(8 |B|) + crc(B)
+        const u32 c2 = __shfl_down(c, 1u << k, 64);
+        if ((lane & ((2u << k) - 1u)) == 0) c = multmodp(MUL.v[k], c) ^ c2;
+    }
+    if (lane == 0) s_wave[wave] = c;
+    __syncthreads();
+    if (wave == 0) {
+        c = lane < TAG_BLOCK / 64u ? s_wave[lane] : 0u;
+#pragma unroll
+        for (u32 k = 0; k < 4u; k++) {
+            const u32 c2 = __shfl_down(c, 1u << k, 64);
+            if ((lane & ((2u << k) - 1u)) == 0) c = multmodp(MUL.v[6u + k], c) ^ c2;
+        }
+        const u32 crc = __shfl(c, 0, 64);
+        if (lane < 8u) img8[p1 + (int)lane] = (u8)((lane < 4u ? crc : len) >> (8u * (lane & 3u)));  // CRC32, ISIZE
+    }
+    __syncthreads();
+
+    // ---- out: 16-byte aligned stores, the first and the last piece byte by byte
+    u8 *const out16 = dst - ph;
+    const u32 img_end = ph + len + hb::STORE_EXTRA;
+    for (u32 k = t; k < n_piece; k += TAG_BLOCK) {
+        if ((k == 0 && ph) || 16u * k + 16u > img_end) {
+            for (u32 i = max(16u * k, ph); i < min(16u * k + 16u, img_end); i++) out16[i] = img8[i];
+        } else *(uint4 *)(out16 + 16u * k) = s_img[k];
+    }
+}
+
+}  // namespace
+
+extern "C" void pp_bam_out_free(pp_bam_out *o) {
+    if (!o) return;
+    if (o->ctx) (void)hipSetDevice(o->ctx->device);
+    if (o->d_out) (void)hipFree(o->d_out);
+    delete o;
+}
+
+extern "C" void pp_bam_out_bytes(const pp_bam_out *o, const uint8_t **dev, uint64_t *n_bytes) {
+    if (dev) *dev = o ? (const uint8_t *)o->d_out : nullptr;
+    if (n_bytes) *n_bytes = o ? o->n_out : 0;
+}
+
+extern "C" void pp_bam_out_counts(const pp_bam_out *o, uint64_t *pass_count, uint64_t *fail_count, uint64_t *n_blocks) {
+    if (pass_count) *pass_count = o ? o->pass_count : 0;
+    if (fail_count) *fail_count = o ? o->fail_count : 0;
+    if (n_blocks) *n_blocks = o ? o->n_blocks : 0;
+}
+
+extern "C" int pp_bam_out_kernel_ms(const pp_bam_out *o, float *ms) {
+    if (!o || !ms) return PP_ERR_ARG;
+    if (!o->timed) return o->ctx->fail(PP_ERR_ARG, "pp_bam_out_kernel_ms: the context had no profiling on when the records were tagged (pp_ctx_set_profiling)");
+    *ms = o->ms[0] + o->ms[1] + o->ms[2];
+    return PP_OK;
+}
+
+// (internal hook, not part of the header: tools/bam_tag_timing.py) the same time by stage: pass A | the scans | pass B
+extern "C" int pp_bam_out_stage_ms_(const pp_bam_out *o, float *ms3) {
+    if (!o || !ms3 || !o->timed) return PP_ERR_ARG;
+    for (int i = 0; i < 3; i++) ms3[i] = o->ms[i];
+    return PP_OK;
+}
+
+// the file in slices through a host buffer; a path that cannot be created or written: as pp_filter_write
+extern "C" int pp_bam_out_write(const pp_bam_out *o, const char *path) {
+    if (!o || !o->ctx) return PP_ERR_ARG;
+    pp_ctx *ctx = o->ctx;
+    if (!path) return ctx->fail(PP_ERR_ARG, "pp_bam_out_write: null argument");
+    PP_HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
+    if (fd < 0) return ctx->fail(PP_ERR_QUIT, "unable to write alignments to \"%s\"", path);
+    constexpr size_t PIECE = (size_t)64 << 20;
+    std::vector<uint8_t> buf((size_t)std::min<uint64_t>(o->n_out, PIECE));
+    int rc = PP_OK;
+    for (uint64_t at = 0; at < o->n_out && !rc; at += PIECE) {
+        const size_t n = (size_t)std::min<uint64_t>(PIECE, o->n_out - at);
+        const hipError_t e = hipMemcpy(buf.data(), (const uint8_t *)o->d_out + at, n, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { rc = ctx->fail(PP_ERR_HIP, "pp_bam_out_write: hipMemcpy failed: %s", hipGetErrorString(e)); break; }
+        for (size_t done = 0; done < n;) {
+            const ssize_t w = write(fd, buf.data() + done, n - done);
+            if (w <= 0) { rc = ctx->fail(PP_ERR_QUIT, "unable to write alignments to \"%s\"", path); break; }
+            done += (size_t)w;
+        }
+    }
+    if (close(fd) != 0 && !rc) rc = ctx->fail(PP_ERR_QUIT, "unable to write alignments to \"%s\"", path);
+    return rc;
+}
+
+extern "C" int pp_bam_tagged(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, uint64_t records_at, const uint64_t *rec_off, uint64_t n_rec,
+                             int mem, const uint8_t *pass, uint64_t n_pass, pp_bam_out **out, uint64_t *bad_record) {
+    if (!ctx) return PP_ERR_ARG;
+    if (int rdy = pp_ctx_wait(ctx)) return rdy;
+    if (bad_record) *bad_record = ~0ull;
+    if (!out) return ctx->fail(PP_ERR_ARG, "pp_bam_tagged: null argument");
+    *out = nullptr;
+    if (mem != PP_MEM_HOST && mem != PP_MEM_DEVICE)
+        return ctx->fail(PP_ERR_ARG, "pp_bam_tagged: the bytes must be host memory or memory of the context's device");
+    if ((n_bytes && !bytes) || (n_rec && !rec_off)) return ctx->fail(PP_ERR_ARG, "pp_bam_tagged: null bytes with n_bytes > 0, or null rec_off with n_rec > 0");
+    if (records_at > n_bytes) return ctx->fail(PP_ERR_ARG, "pp_bam_tagged: records_at %llu lies behind the %llu bytes", (unsigned long long)records_at, (unsigned long long)n_bytes);
+    if (n_rec >= 0xFFFFFFFFull) return ctx->fail(PP_ERR_LIMIT, "more than 2^32-1 alignments in one batch");
+    if (n_bytes >= (1ull << 40)) return ctx->fail(PP_ERR_LIMIT, "pp_bam_tagged: 2^40 or more bytes in one call");
+    PP_HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const u32 n = (u32)n_rec;
+
+    pp_bam_out *P = new pp_bam_out;
+    P->ctx = ctx;
+    std::unique_ptr<pp_bam_out, void (*)(pp_bam_out *)> guard(P, pp_bam_out_free);  // (every early return releases what was made so far)
+    CallScratch T;  // the copy of host bytes and the per-record arrays: released when the call returns
+    StageTimer timer(ctx, ctx->profiling != 0);
+    int rc;
+    const u8 *d_bytes = nullptr;
+    const u64 *d_rec_off = nullptr;
+    if ((rc = on_device(ctx, T, mem, (const u8 *)bytes, (size_t)n_bytes, &d_bytes)) || (rc = on_device(ctx, T, mem, (const u64 *)rec_off, (size_t)n, &d_rec_off)))
+        return rc;
+    const u32 nb = std::max(1u, (n + TAG_BLOCK - 1u) / TAG_BLOCK);
+    void *d_aligned, *d_blk_al, *d_al_base, *d_blk2, *d_blk2off, *d_start, *d_status, *d_pass;
+    if ((rc = T.get(ctx, &d_aligned, (size_t)n)) || (rc = T.get(ctx, &d_blk_al, (size_t)nb * 8)) || (rc = T.get(ctx, &d_al_base, ((size_t)nb + 1) * 8)) ||
+        (rc = T.get(ctx, &d_blk2, (size_t)nb * 16)) || (rc = T.get(ctx, &d_blk2off, ((size_t)nb + 1) * 16)) || (rc = T.get(ctx, &d_start, ((size_t)n + 2) * 8)) ||
+        (rc = T.get(ctx, &d_status, 16)))
+        return rc;
+
+    // ---- pass A: the ranges, the aligned records ----
+    u64 n_al = 0, u_total = records_at, n_fail = 0;
+    if (n) {
+        PP_HIPCHK(ctx, hipMemsetAsync(d_status, 0xFF, 16, st));
+        if ((rc = timer.begin(0))) return rc;
+        hipLaunchKernelGGL(k_tag_scan, dim3(nb), dim3(TAG_BLOCK), 0, st, n, d_bytes, (u64)n_bytes, d_rec_off, (u8 *)d_aligned, (u64 *)d_blk_al, (u64 *)d_status);
+        if ((rc = timer.end()) || (rc = timer.begin(1))) return rc;
+        hipLaunchKernelGGL(k_colscan<1>, dim3(1), dim3(1024), 0, st, (const u64 *)d_blk_al, (u64)nb, (u64 *)d_al_base);
+        if ((rc = timer.end())) return rc;
+        PP_HIPCHK(ctx, hipGetLastError());
+        u64 status[2] = {~0ull, ~0ull};
+        if ((rc = fetch(ctx, d_status, status, 2)) || (rc = fetch(ctx, (const u64 *)d_al_base + nb, &n_al))) return rc;
+        if (status[0] != ~0ull) {
+            const u64 r = status[0] >> 8;
+            const u32 kind = (u32)(status[0] & 0xFFu);
+            if (bad_record) *bad_record = r;
+            return ctx->fail(PP_ERR_ARG, "pp_bam_tagged: record %llu %s", (unsigned long long)r,
+                             kind == pp_bam_host::W_CUT ? "has an offset outside the bytes, or the bytes end inside its block_size"
+                             : kind == pp_bam_host::W_SMALL ? "has a block_size below the 32 bytes of its fixed part" : "runs past the end of the bytes");
+        }
+        if (status[1] != ~0ull) {
+            if (bad_record) *bad_record = status[1] >> 8;
+            return ctx->fail(PP_ERR_LIMIT, "pp_bam_tagged: record %llu has a block_size above 0xFFFFFFF7", (unsigned long long)(status[1] >> 8));
+        }
+    }
+    if (n_al && !pass) return ctx->fail(PP_ERR_ARG, "pp_bam_tagged: null pass with %llu aligned records", (unsigned long long)n_al);
+    if (n_pass != n_al)
+        return ctx->fail(PP_ERR_ARG, "pp_bam_tagged: %llu verdicts for %llu aligned records", (unsigned long long)n_pass, (unsigned long long)n_al);
+
+    // ---- the verdicts (host memory whatever `mem`), the lengths, the starts ----
+    if ((rc = T.get(ctx, &d_pass, (size_t)n_al))) return rc;
+    if (n_al) PP_HIPCHK(ctx, hipMemcpyAsync(d_pass, pass, (size_t)n_al, hipMemcpyHostToDevice, st));
+    if (n) {
+        if ((rc = timer.begin(1))) return rc;
+        hipLaunchKernelGGL(k_tag_len<false>, dim3(nb), dim3(TAG_BLOCK), 0, st, n, d_bytes, d_rec_off, (const u8 *)d_aligned, (const u64 *)d_al_base,
+                           (const u8 *)d_pass, (u64)records_at, (u64 *)d_blk2, (u64 *)nullptr);
+        hipLaunchKernelGGL(k_colscan<2>, dim3(1), dim3(1024), 0, st, (const u64 *)d_blk2, (u64)nb, (u64 *)d_blk2off);
+        hipLaunchKernelGGL(k_tag_len<true>, dim3(nb), dim3(TAG_BLOCK), 0, st, n, d_bytes, d_rec_off, (const u8 *)d_aligned, (const u64 *)d_al_base,
+                           (const u8 *)d_pass, (u64)records_at, (u64 *)d_blk2off, (u64 *)d_start);
+        if ((rc = timer.end())) return rc;
+        PP_HIPCHK(ctx, hipGetLastError());
+        u64 totals[2] = {0, 0};
+        if ((rc = fetch(ctx, (const u64 *)d_blk2off + 2ull * nb, totals, 2))) return rc;
+        u_total = records_at + 4ull * n + totals[0];
+        n_fail = totals[1];
+    } else {  // the header alone
+        const u64 two[2] = {0, records_at};
+        PP_HIPCHK(ctx, hipMemcpyAsync(d_start, two, sizeof two, hipMemcpyHostToDevice, st));
+        PP_HIPCHK(ctx, hipStreamSynchronize(st));
+    }
+
+    // ---- pass B: the blocks ----
+    const u64 n_blocks = (u_total + PAY - 1u) / PAY;
+    P->n_out = u_total + (u64)hb::STORE_EXTRA * n_blocks + hb::EOF_SIZE;
+    P->n_blocks = n_blocks;
+    P->pass_count = n_al - n_fail;
+    P->fail_count = n_fail;
+    PP_HIPCHK(ctx, hipMalloc(&P->d_out, (size_t)P->n_out));
+    if ((rc = timer.begin(2))) return rc;
+    hipLaunchKernelGGL(k_tag_frame, dim3((unsigned)(n_blocks + 1u)), dim3(TAG_BLOCK), 0, st,
+                       FrameArgs{d_bytes, (u64)n_bytes, d_rec_off, (const u64 *)d_start, n, u_total, n_blocks, (u8 *)P->d_out});
+    if ((rc = timer.end())) return rc;
+    PP_HIPCHK(ctx, hipGetLastError());
+    PP_HIPCHK(ctx, hipStreamSynchronize(st));  // host inputs may be released, the scratch goes away
+    if (timer.on) {
+        if ((rc = timer.sums(P->ms, 3))) return rc;
+        P->timed = true;
+    }
+    guard.release();
+    *out = P;
+    return PP_OK;
+}

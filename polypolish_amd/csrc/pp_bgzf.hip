@@ -22,9 +22,10 @@
 //                   code; nothing is written outside the block's room.  The kernel has no barrier instruction in it.
 //   k_bgzf_crc      one wave per block: every lane runs the byte-table CRC32 (table in LDS) over its 64th of the block's output, the
 //                   lanes' values are combined pairwise by multiplication by x^(8 n) mod P (zlib's crc32_combine: a 32-entry table
-//                   of x^(2^k)), lane 0 compares with the footer.  A kernel of its own: its time is a stage of pp_bgzf_kernel_ms.
+//                   of x^(2^k); pp_crc.h, shared with the BGZF writer of pp_bam_out.hip), lane 0 compares with the footer.  A kernel of its own: its time is a stage of pp_bgzf_kernel_ms.
 // No byte outside [0, n_bytes) is loaded: a wide load is issued only where the payload has that many bytes left.
 #include "pp_bgzf_host.h"
+#include "pp_crc.h"
 #include "pp_dev.h"
 
 extern "C" char *pp_bam_msg_buf_(size_t *cap);  // pp_bam.hip: the per-thread message behind pp_bam_last_error()
@@ -53,39 +54,6 @@ __constant__ uint8_t LEN_EXTRA[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 
 __constant__ uint16_t DIST_BASE[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
 __constant__ uint8_t DIST_EXTRA[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13};
 __constant__ uint8_t CL_ORDER[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-
-// ---- CRC32 (reflected, P = 0xEDB88320) and its combination, after zlib's crc32_combine -------------------------------------------------
-constexpr u32 CRC_POLY = 0xEDB88320u;
-__host__ __device__ constexpr u32 multmodp(u32 a, u32 b) {  // a(x) * b(x) mod P; bit 31 is x^0
-    u32 m = 1u << 31, p = 0;
-    for (int i = 0; i < 32; i++) {
-        if (a & m) {
-            p ^= b;
-            if ((a & (m - 1)) == 0) break;
-        }
-        m >>= 1;
-        b = (b & 1u) ? (b >> 1) ^ CRC_POLY : b >> 1;
-    }
-    return p;
-}
-struct X2N {
-    u32 v[32];  // x^(2^k) mod P
-    constexpr X2N() : v{} {
-        u32 p = 1u << 30;  // x^1
-        v[0] = p;
-        for (int n = 1; n < 32; n++) v[n] = p = multmodp(p, p);
-    }
-};
-__constant__ X2N X2N_TAB = X2N();
-__device__ u32 x8n_modp(u32 n) {  // x^(8 n) mod P
-    u32 p = 1u << 31, k = 3;
-    while (n) {
-        if (n & 1u) p = multmodp(X2N_TAB.v[k & 31u], p);
-        n >>= 1;
-        k++;
-    }
-    return p;
-}
 
 // ---- the headers -----------------------------------------------------------------------------------------------------------------------
 struct BlkInfo {  // what k_bgzf_head writes per block

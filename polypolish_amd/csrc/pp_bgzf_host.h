@@ -2,6 +2,8 @@
 // with no HIP in it, so that a stand-alone program can run the walk under a sanitizer (tools/bgzf_host_check.cpp).  block() is also
 // what the device runs per block before anything is read through a block's offset (k_bgzf_head): one definition for both sides.
 // Nothing here reads a byte outside [0, n_bytes) or forms a sum that could wrap: every length is compared with what is LEFT.
+// The WRITING twin: the constants and bytes of a block around one stored DEFLATE block, which pp_bam_tagged frames its output with
+// on the device (pp_bam_out.hip takes the head's and the EOF block's bytes from here), and store_block(), the same block in plain C++.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -62,6 +64,48 @@ PP_BGZF_HD inline uint32_t block(const uint8_t *bytes, uint64_t n_bytes, uint64_
     out->pay_len = total - 12 - xlen - 8;
     out->isize = isize;
     return H_OK;
+}
+
+// ---- writing: one BGZF block around one STORED DEFLATE block (level 0), what pp_bam_tagged frames its output with (pp_bam_out.hip) ----
+// 1f 8b 08 04 | MTIME 0 | XFL 0 | OS ff | XLEN 6 | B C 2 0 BSIZE | 01 LEN ~LEN | the bytes | CRC32 | ISIZE: len + 31 bytes, BSIZE = len + 30
+constexpr uint32_t STORE_PAYLOAD = 0xff00;  // htslib's payload size: the output is cut every 65,280 bytes
+constexpr uint32_t STORE_HEAD = 23;         // the 18 bytes of the header and 01 LEN ~LEN
+constexpr uint32_t STORE_EXTRA = 31;        // ... and CRC32, ISIZE behind the bytes
+constexpr uint32_t STORE_BLOCK = STORE_PAYLOAD + STORE_EXTRA;  // block b of a file starts at b * 65,311
+constexpr uint32_t EOF_SIZE = 28;
+
+// byte j < 18 of a block's header, total = the whole block's bytes
+PP_BGZF_HD inline uint8_t head_byte(uint32_t j, uint32_t total) {
+    if (j < 8) return (uint8_t)(0x0000000004088b1full >> (8 * j));
+    if (j < 16) return (uint8_t)(0x000243420006ff00ull >> (8 * (j - 8)));
+    return (uint8_t)((total - 1) >> (8 * (j - 16)));
+}
+// byte j < STORE_HEAD of the block that stores `len` bytes
+PP_BGZF_HD inline uint8_t store_head_byte(uint32_t j, uint32_t len) {
+    if (j < 18) return head_byte(j, len + STORE_EXTRA);
+    if (j == 18) return 1;  // BFINAL, BTYPE 0
+    const uint32_t w = j < 21 ? len : ~len;
+    return (uint8_t)(w >> (8 * ((j - 19) & 1)));
+}
+// byte j < EOF_SIZE of the empty block that ends a file: the header, an empty fixed-code block (03 00), CRC32 0, ISIZE 0
+PP_BGZF_HD inline uint8_t eof_byte(uint32_t j) { return j < 18 ? head_byte(j, EOF_SIZE) : (j == 18 ? 3 : 0); }
+
+inline uint32_t crc32_bitwise(const uint8_t *data, uint32_t len) {
+    uint32_t c = 0xFFFFFFFFu;
+    for (uint32_t i = 0; i < len; i++) {
+        c ^= data[i];
+        for (int k = 0; k < 8; k++) c = (c & 1u) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
+    }
+    return ~c;
+}
+
+// the block that stores data[0, len), len <= STORE_PAYLOAD, into out[0, len + STORE_EXTRA); returns its size
+inline uint32_t store_block(const uint8_t *data, uint32_t len, uint8_t *out) {
+    for (uint32_t j = 0; j < STORE_HEAD; j++) out[j] = store_head_byte(j, len);
+    if (len) memcpy(out + STORE_HEAD, data, len);
+    const uint32_t foot[2] = {crc32_bitwise(data, len), len};
+    for (uint32_t j = 0; j < 8; j++) out[STORE_HEAD + len + j] = (uint8_t)(foot[j >> 2] >> (8 * (j & 3)));
+    return len + STORE_EXTRA;
 }
 
 inline const char *defect_text(uint32_t code) {

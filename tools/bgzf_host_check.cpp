@@ -6,6 +6,7 @@
 // Every prefix of the file goes to the walk in a heap block of EXACTLY its length (so that a read past the cut is a read past the
 // allocation), then every prefix with one byte of its last 48 turned over; the program checks what tests/test_bgzf_model_cpu.py
 // checks -- a cut is refused or stops the walk at the cut, no block runs past it -- and the sanitizer checks every load.
+// First of all store_block(), the writing twin, runs at 0, 1, 65,279 and 65,280 bytes and each result goes through block() and the walk.
 #include "pp_bgzf_host.h"
 
 #include <cstdlib>
@@ -30,8 +31,46 @@ static int check(const uint8_t *p, uint64_t n, uint64_t *walked_ok) {
     return 0;
 }
 
+// store_block() at the lengths where the framing can go wrong: input and output in heap blocks of EXACTLY their lengths, the result
+// read back by the header's own step of the walk (block()), its stored-block prefix, payload, CRC32 (a second, table-free form) and ISIZE
+static int check_store(uint32_t len) {
+    namespace hb = pp_bgzf_host;
+    uint8_t *in = (uint8_t *)malloc(len ? len : 1), *out = (uint8_t *)malloc(len + hb::STORE_EXTRA);
+    for (uint32_t i = 0; i < len; i++) in[i] = (uint8_t)(i * 2654435761u >> 13);
+    const uint32_t n = hb::store_block(in, len, out);
+    hb::Block B;
+    int bad = 0;
+    if (n != len + hb::STORE_EXTRA || hb::block(out, n, 0, &B) || B.total != n || B.payload != 18 || B.pay_len != len + 5 || B.isize != len) bad = 1;
+    if (!bad && (out[18] != 1 || hb::le16(out + 19) != len || hb::le16(out + 21) != (~len & 0xFFFFu) || memcmp(out + hb::STORE_HEAD, in, len) != 0)) bad = 2;
+    uint32_t c = 0xFFFFFFFFu;  // the CRC32 once more, by the shifted polynomial per bit of the message
+    for (uint32_t i = 0; i < len * 8u; i++) c = ((c ^ (in[i >> 3] >> (i & 7u))) & 1u) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
+    if (!bad && hb::le32(out + hb::STORE_HEAD + len) != ~c) bad = 3;
+    uint64_t n_blk = 0, end = 0;
+    char msg[256];
+    if (!bad && (hb::walk(out, n, 0, nullptr, nullptr, 0, &n_blk, &end, msg, sizeof msg) || n_blk != 1 || end != n)) bad = 4;
+    free(in);
+    free(out);
+    if (bad) fprintf(stderr, "store_block(%u bytes): check %d failed\n", len, bad);
+    return bad;
+}
+
+static int check_eof() {
+    namespace hb = pp_bgzf_host;
+    uint8_t *e = (uint8_t *)malloc(hb::EOF_SIZE);
+    for (uint32_t j = 0; j < hb::EOF_SIZE; j++) e[j] = hb::eof_byte(j);
+    hb::Block B;
+    const int bad = hb::block(e, hb::EOF_SIZE, 0, &B) || B.total != hb::EOF_SIZE || B.pay_len != 2 || B.isize != 0 || e[18] != 3 || e[19] != 0;
+    free(e);
+    if (bad) fprintf(stderr, "the EOF block is not one\n");
+    return bad;
+}
+
 int main(int argc, char **argv) {
     if (argc != 2) return fprintf(stderr, "usage: %s FILE (a few BGZF blocks)\n", argv[0]), 2;
+    for (uint32_t len : {0u, 1u, pp_bgzf_host::STORE_PAYLOAD - 1u, pp_bgzf_host::STORE_PAYLOAD})
+        if (check_store(len)) return 1;
+    if (check_eof()) return 1;
+    printf("bgzf_host_check: store_block at 0, 1, 65279 and 65280 bytes reads back through block() and the walk\n");
     FILE *f = fopen(argv[1], "rb");
     if (!f) return perror(argv[1]), 2;
     std::vector<uint8_t> all;
