@@ -505,6 +505,46 @@ int pp_bam_out_write(const pp_bam_out *o, const char *path); /* download in slic
 int pp_bam_out_kernel_ms(const pp_bam_out *o, float *ms);
 void pp_bam_out_free(pp_bam_out *o);
 
+/* The COMPRESSOR of the record chain: bytes in device memory compressed into BGZF blocks, on the device.  pp_bam_tagged's level-0 file
+ * is 4.6 times the size of the BAM file that came in; pp_bam_out_deflate makes the same file compressed.  pp_bam_tagged's own bytes
+ * stay what they are.
+ *   the pieces   the bytes cut every 65,280 (0xff00; the last piece is shorter, no bytes give no piece), each piece one BGZF block
+ *                around ONE DEFLATE block with BFINAL = 1: the 18-byte header of pp_bam_tagged with the real BSIZE, the stream,
+ *                CRC32, ISIZE.  The blocks are dense, at any byte alignment, the 28-byte EOF block behind the last; an empty input
+ *                gives the EOF block alone.
+ *   the stream   defined byte for byte by a plain model (tests/bgzf_deflate_model.py) as a function of the piece's bytes alone: two
+ *                calls give identical bytes.  Match candidates come from a hash table of 2^13 entries over the piece's 4-byte groups,
+ *                read in strips of 256 positions (a candidate lies in an earlier strip of the same piece, never in another piece);
+ *                matches of 4 .. 258 bytes at distances up to 32,768; a greedy parse; length-limited Huffman codes (15 bits, 7 for the
+ *                code-length code), always complete; the exact bit costs of the stored, the fixed and the dynamic form decide, a tie
+ *                goes to the earlier of the three.  A block is therefore never longer than its piece + 31 bytes and the file never
+ *                longer than pp_bam_tagged's.  Every BGZF or gzip reader takes it.
+ *   memory       pp_bgzf_deflate: mem = PP_MEM_HOST or PP_MEM_DEVICE holds for `bytes`; host bytes are uploaded and the copy is
+ *                released before the call returns, device bytes are borrowed for the call only.  pp_bam_out_deflate reads the
+ *                payloads of the level-0 file where they lie (block b's at b * 65,311 + 23); the pp_bam_out stays valid and is the
+ *                caller's to free.  No byte outside [0, n_bytes) is loaded, by a wide load either.  The object owns the output only;
+ *                during the call the library holds one 65,344-byte slot per piece and the tokens of at most 1,024 pieces.
+ *   errors       PP_ERR_ARG: null arguments (bytes == NULL with n_bytes > 0, out == NULL, o == NULL), PP_MEM_PEER.  PP_ERR_LIMIT:
+ *                n_bytes >= 2^40.  There is nothing in the bytes themselves that could be refused.
+ * The context's stream has been synchronised when either call returns: host inputs may be released.
+ *   pp_bgzf_out_bytes      the file (DEVICE, borrowed until pp_bgzf_out_free)
+ *   pp_bgzf_out_blk_off    the blocks' offsets in the file (DEVICE, borrowed): *n_blk + 1 entries, the EOF block's offset last --
+ *                          exactly what pp_bgzf_inflate(file, n_bytes, blk_off, n_blk, PP_MEM_DEVICE, ...) takes to read the file back
+ *   pp_bgzf_out_counts     the blocks by form: stored, fixed, dynamic (the EOF block is not counted)
+ *   pp_bgzf_out_write      as pp_bam_out_write: downloads the file in slices and writes it to `path`; PP_ERR_QUIT "unable to write
+ *                          alignments to ..." for a path that cannot be created or written
+ *   pp_bgzf_out_kernel_ms  as pp_gated_kernel_ms
+ * The object belongs to its context and is freed before it. */
+typedef struct pp_bgzf_out pp_bgzf_out;
+int pp_bgzf_deflate(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, int mem, pp_bgzf_out **out); /* any bytes, cut every 65,280 */
+int pp_bam_out_deflate(pp_ctx *ctx, const pp_bam_out *o, pp_bgzf_out **out);                          /* the tagged file, compressed */
+void pp_bgzf_out_bytes(const pp_bgzf_out *o, const uint8_t **dev, uint64_t *n_bytes); /* DEVICE, borrowed until pp_bgzf_out_free */
+const uint64_t *pp_bgzf_out_blk_off(const pp_bgzf_out *o, uint64_t *n_blk); /* DEVICE, n_blk + 1 entries: the EOF block's offset last */
+void pp_bgzf_out_counts(const pp_bgzf_out *o, uint64_t *stored, uint64_t *fixed, uint64_t *dynamic);
+int pp_bgzf_out_write(const pp_bgzf_out *o, const char *path); /* download in slices, write the file */
+int pp_bgzf_out_kernel_ms(const pp_bgzf_out *o, float *ms);
+void pp_bgzf_out_free(pp_bgzf_out *o);
+
 /* Per-contig figures the reference prints to stderr (src/polish.rs:206-227). */
 typedef struct {
     uint64_t polished_len;     /* bytes of the polished sequence                      */

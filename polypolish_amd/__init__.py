@@ -808,6 +808,7 @@ class BamTagged(_Owned):
       .counts        (passed, failed, blocks without the EOF block)
       .host(lo, hi)  a numpy copy of the file's bytes [lo, hi) (a download)
       .write(path)   pp_bam_out_write: the file on disk
+      .deflate()     pp_bam_out_deflate: the same file compressed -> BgzfDeflated
       .kernel_ms()   HIP-event time of the kernels (the context had set_profiling on); .stage_ms(): pass_a | scans | pass_b
     A failing call raises PolypolishError with .bad_record."""
     _free, _kernel_ms = "pp_bam_out_free", "pp_bam_out_kernel_ms"
@@ -839,6 +840,57 @@ class BamTagged(_Owned):
 
     def stage_ms(self):
         return self._stage_ms("pp_bam_out_stage_ms_", ("pass_a", "scans", "pass_b"), " when the records were tagged")
+
+    def deflate(self):
+        return BgzfDeflated(self._ctx, tagged=self)
+
+
+class BgzfDeflated(_Owned):
+    """pp_bgzf_deflate / pp_bam_out_deflate: bytes compressed into a BGZF file in DEVICE memory, owned by this object.  The bytes are
+    cut every 65,280; each piece is one BGZF block around one DEFLATE block, the EOF block is the last (tests/bgzf_deflate_model.py
+    defines the bytes).
+      data           mem = MEM_HOST: bytes / a uint8 array; MEM_DEVICE: (device address, n_bytes), borrowed for the call; or
+                     tagged = a BamTagged (BamTagged.deflate()): the uncompressed stream of its level-0 file
+      .n_bytes, .bytes_ptr        the file
+      .n_blocks, .blk_off_ptr     the blocks without the EOF block, and the device address of n_blocks + 1 uint64 offsets (the EOF
+                     block's last): Bgzf(ctx, (z.bytes_ptr, z.n_bytes), (z.blk_off_ptr, z.n_blocks), mem=MEM_DEVICE) reads it back
+      .counts        blocks by form: (stored, fixed, dynamic)
+      .host(lo, hi)  a numpy copy of the file's bytes [lo, hi) (a download); .blk_off(): of the n_blocks + 1 offsets
+      .write(path)   pp_bgzf_out_write: the file on disk
+      .kernel_ms()   HIP-event time of the kernels (the context had set_profiling on); .stage_ms(): pieces | scan | place"""
+    _free, _kernel_ms = "pp_bgzf_out_free", "pp_bgzf_out_kernel_ms"
+
+    def __init__(self, ctx, data=None, mem=MEM_HOST, tagged=None):
+        L = lib()
+        super().__init__(ctx)
+        if tagged is not None:
+            rc = L.pp_bam_out_deflate(ctx._h, tagged._p, C.byref(self._p))
+        else:
+            bp, n_bytes, _, _, _keep = _bytes_and_offsets(data, None, mem)
+            rc = L.pp_bgzf_deflate(ctx._h, bp, n_bytes, mem, C.byref(self._p))
+        ctx._chk(rc)
+        dev, nb, k = C.c_void_p(), C.c_uint64(0), C.c_uint64(0)
+        L.pp_bgzf_out_bytes(self._p, C.byref(dev), C.byref(nb))
+        self.bytes_ptr, self.n_bytes = dev.value or 0, int(nb.value)
+        self.blk_off_ptr = L.pp_bgzf_out_blk_off(self._p, C.byref(k)) or 0
+        self.n_blocks = int(k.value)
+        s, f, d = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L.pp_bgzf_out_counts(self._p, C.byref(s), C.byref(f), C.byref(d))
+        self.counts = (int(s.value), int(f.value), int(d.value))
+
+    def host(self, lo=0, hi=None):
+        hi = self.n_bytes if hi is None else min(int(hi), self.n_bytes)
+        lo = min(int(lo), hi)
+        return self._ctx.download(self.bytes_ptr + lo, hi - lo, np.uint8)
+
+    def blk_off(self):
+        return self._ctx.download(self.blk_off_ptr, self.n_blocks + 1, np.uint64)
+
+    def write(self, path):
+        self._ctx._chk(lib().pp_bgzf_out_write(self._p, os.fsencode(path)))
+
+    def stage_ms(self):
+        return self._stage_ms("pp_bgzf_out_stage_ms_", ("pieces", "scan", "place"), " when the bytes were compressed")
 
 
 def _report_dict(rep):

@@ -151,6 +151,14 @@ SIGNATURES = {
     "pp_bam_out_write": (_i, [_vp, _str]),
     "pp_bam_out_kernel_ms": (_i, [_vp, _pf32]),
     "pp_bam_out_free": (None, [_vp]),
+    "pp_bgzf_deflate": (_i, [_vp, _vp, _u64, _i, _pvp]),
+    "pp_bam_out_deflate": (_i, [_vp, _vp, _pvp]),
+    "pp_bgzf_out_bytes": (None, [_vp, _pvp, _pu64]),
+    "pp_bgzf_out_blk_off": (_vp, [_vp, _pu64]),
+    "pp_bgzf_out_counts": (None, [_vp, _pu64, _pu64, _pu64]),
+    "pp_bgzf_out_write": (_i, [_vp, _str]),
+    "pp_bgzf_out_kernel_ms": (_i, [_vp, _pf32]),
+    "pp_bgzf_out_free": (None, [_vp]),
     "pp_polish_set_emit": (_i, [_vp, _vp, _vp]),
     "pp_polish_begin": (_i, [_vp, _u32, _vp, _vp, _i, _P(Params)]),
     "pp_polish_add": (_i, [_vp, _P(AlnBatch), _i]),
@@ -233,6 +241,7 @@ HOOKS = {
     "pp_bgzf_stage_ms_": (_i, [_vp, _pf32]),        # float[3]
     "pp_bam_stage_ms_": (_i, [_vp, _pf32]),         # float[3]
     "pp_bam_out_stage_ms_": (_i, [_vp, _pf32]),     # float[3]
+    "pp_bgzf_out_stage_ms_": (_i, [_vp, _pf32]),    # float[3]
     "pp_bam_offs_stage_ms_": (_i, [_vp, _pf32]),    # float[3]
     "pp_bam_offs_stats_": (_i, [_vp, _pu64]),       # uint64[4]
     "pp_bam_walk_geometry_": (None, [_pu32] * 3),

@@ -396,29 +396,33 @@ extern "C" int pp_bam_out_stage_ms_(const pp_bam_out *o, float *ms3) {
     return PP_OK;
 }
 
-// the file in slices through a host buffer; a path that cannot be created or written: as pp_filter_write
-extern "C" int pp_bam_out_write(const pp_bam_out *o, const char *path) {
-    if (!o || !o->ctx) return PP_ERR_ARG;
-    pp_ctx *ctx = o->ctx;
-    if (!path) return ctx->fail(PP_ERR_ARG, "pp_bam_out_write: null argument");
+// a file in device memory to `path`, in slices through a host buffer (pp_bam_out_write, pp_bgzf_out_write); a path that cannot be
+// created or written: as pp_filter_write
+int pp::write_device_file(pp_ctx *ctx, const char *who, const void *dev, uint64_t n, const char *path) {
     PP_HIPCHK(ctx, hipSetDevice(ctx->device));
     const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0666);
     if (fd < 0) return ctx->fail(PP_ERR_QUIT, "unable to write alignments to \"%s\"", path);
     constexpr size_t PIECE = (size_t)64 << 20;
-    std::vector<uint8_t> buf((size_t)std::min<uint64_t>(o->n_out, PIECE));
+    std::vector<uint8_t> buf((size_t)std::min<uint64_t>(n, PIECE));
     int rc = PP_OK;
-    for (uint64_t at = 0; at < o->n_out && !rc; at += PIECE) {
-        const size_t n = (size_t)std::min<uint64_t>(PIECE, o->n_out - at);
-        const hipError_t e = hipMemcpy(buf.data(), (const uint8_t *)o->d_out + at, n, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { rc = ctx->fail(PP_ERR_HIP, "pp_bam_out_write: hipMemcpy failed: %s", hipGetErrorString(e)); break; }
-        for (size_t done = 0; done < n;) {
-            const ssize_t w = write(fd, buf.data() + done, n - done);
+    for (uint64_t at = 0; at < n && !rc; at += PIECE) {
+        const size_t k = (size_t)std::min<uint64_t>(PIECE, n - at);
+        const hipError_t e = hipMemcpy(buf.data(), (const uint8_t *)dev + at, k, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { rc = ctx->fail(PP_ERR_HIP, "%s: hipMemcpy failed: %s", who, hipGetErrorString(e)); break; }
+        for (size_t done = 0; done < k;) {
+            const ssize_t w = write(fd, buf.data() + done, k - done);
             if (w <= 0) { rc = ctx->fail(PP_ERR_QUIT, "unable to write alignments to \"%s\"", path); break; }
             done += (size_t)w;
         }
     }
     if (close(fd) != 0 && !rc) rc = ctx->fail(PP_ERR_QUIT, "unable to write alignments to \"%s\"", path);
     return rc;
+}
+
+extern "C" int pp_bam_out_write(const pp_bam_out *o, const char *path) {
+    if (!o || !o->ctx) return PP_ERR_ARG;
+    if (!path) return o->ctx->fail(PP_ERR_ARG, "pp_bam_out_write: null argument");
+    return pp::write_device_file(o->ctx, "pp_bam_out_write", o->d_out, o->n_out, path);
 }
 
 extern "C" int pp_bam_tagged(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, uint64_t records_at, const uint64_t *rec_off, uint64_t n_rec,

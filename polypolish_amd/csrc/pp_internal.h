@@ -297,6 +297,8 @@ namespace pp {
 int dev_ensure(pp_ctx *ctx, DevBuf &b, size_t bytes);
 int dev_grow_keep(pp_ctx *ctx, DevBuf &b, size_t bytes, size_t used);
 void dev_free(DevBuf &b);
+// `n` bytes of device memory to the file `path`, in slices through a host buffer (pp_bam_out.hip; also behind pp_bgzf_out_write)
+int write_device_file(pp_ctx *ctx, const char *who, const void *dev, uint64_t n, const char *path);
 // start/stop a named kernel timer on the context's stream (no-ops unless profiling)
 void timer_begin(pp_ctx *ctx, const char *name);
 void timer_end(pp_ctx *ctx);

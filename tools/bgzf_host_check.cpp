@@ -1,16 +1,20 @@
 // bgzf_host_check.cpp -- a stand-alone program over the host walk behind pp_bgzf_walk (polypolish_amd/csrc/pp_bgzf_host.h), made to be
 // built with a sanitizer and run on a machine without a GPU:
-//   clang++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Ipolypolish_amd/csrc tools/bgzf_host_check.cpp -o bgzf_host_check
+//   clang++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Ipolypolish_amd/csrc tools/bgzf_host_check.cpp -o bgzf_host_check -lz
 //   python -c "import sys; sys.path.insert(0, 'tests'); import test_bgzf_model_cpu as t; open('three.bgzf', 'wb').write(t.three_blocks()[0])"
 //   ./bgzf_host_check three.bgzf
 // Every prefix of the file goes to the walk in a heap block of EXACTLY its length (so that a read past the cut is a read past the
 // allocation), then every prefix with one byte of its last 48 turned over; the program checks what tests/test_bgzf_model_cpu.py
 // checks -- a cut is refused or stops the walk at the cut, no block runs past it -- and the sanitizer checks every load.
 // First of all store_block(), the writing twin, runs at 0, 1, 65,279 and 65,280 bytes and each result goes through block() and the walk.
+// Then deflate_block(), the host twin of pp_bgzf_deflate's work on one piece (the code lengths, the header's run-length coding, the three
+// costs: the very functions the kernel runs), at 0, 1, 3, 4, 5, 65,279 and 65,280 bytes of zeros, noise and skewed counts; every result is
+// read back with zlib's inflate (link with -lz) and held against the input, its CRC32 and the bound of len + 31 bytes.
 #include "pp_bgzf_host.h"
 
 #include <cstdlib>
 #include <vector>
+#include <zlib.h>
 
 static int check(const uint8_t *p, uint64_t n, uint64_t *walked_ok) {
     char msg[256];
@@ -65,12 +69,59 @@ static int check_eof() {
     return bad;
 }
 
+// deflate_block() on `len` bytes of kind 0 = zeros, 1 = noise, 2 = skewed counts (byte value k about 1.6 times as often as k + 1: a
+// Huffman tree deeper than 15 levels at the full length, so the repair runs): input, output and what zlib inflates in heap blocks of
+// EXACTLY their lengths
+static int check_deflate(uint32_t len, int kind, uint32_t *forms) {
+    namespace hb = pp_bgzf_host;
+    uint8_t *in = (uint8_t *)malloc(len ? len : 1), *out = (uint8_t *)malloc(len + hb::STORE_EXTRA), *back = (uint8_t *)malloc(len ? len : 1);
+    uint32_t x = 12345u + len;
+    for (uint32_t i = 0; i < len; i++) {
+        x = x * 1664525u + 1013904223u;
+        uint32_t v = 0;
+        if (kind == 1) v = x >> 24;
+        if (kind == 2) for (uint32_t u = x >> 8; v < 40u && (u & 0xFFFFFFu) % 1000u < 618u; u = u * 2654435761u + 1u) v++;
+        in[i] = (uint8_t)v;
+    }
+    uint32_t type = 9;
+    const uint32_t n = hb::deflate_block(in, len, out, &type);
+    hb::Block B;
+    int bad = 0;
+    if (n > len + hb::STORE_EXTRA || type > hb::DF_DYNAMIC || hb::block(out, n, 0, &B) || B.total != n || B.payload != 18 || B.isize != len) bad = 1;
+    if (!bad) {
+        z_stream zs;
+        memset(&zs, 0, sizeof zs);
+        if (inflateInit2(&zs, -15) != Z_OK) bad = 2;
+        else {
+            zs.next_in = out + 18;
+            zs.avail_in = B.pay_len;
+            zs.next_out = back;
+            zs.avail_out = len;
+            if (inflate(&zs, Z_FINISH) != Z_STREAM_END || zs.total_out != len || zs.avail_in != 0 || memcmp(back, in, len) != 0) bad = 3;
+            inflateEnd(&zs);
+        }
+    }
+    if (!bad && hb::le32(out + n - 8) != (uint32_t)crc32(crc32(0L, Z_NULL, 0), in, len)) bad = 4;
+    if (!bad) forms[type]++;
+    free(in);
+    free(out);
+    free(back);
+    if (bad) fprintf(stderr, "deflate_block(%u bytes, kind %d): check %d failed\n", len, kind, bad);
+    return bad;
+}
+
 int main(int argc, char **argv) {
     if (argc != 2) return fprintf(stderr, "usage: %s FILE (a few BGZF blocks)\n", argv[0]), 2;
     for (uint32_t len : {0u, 1u, pp_bgzf_host::STORE_PAYLOAD - 1u, pp_bgzf_host::STORE_PAYLOAD})
         if (check_store(len)) return 1;
     if (check_eof()) return 1;
     printf("bgzf_host_check: store_block at 0, 1, 65279 and 65280 bytes reads back through block() and the walk\n");
+    uint32_t forms[3] = {0, 0, 0};
+    for (int kind = 0; kind < 3; kind++)
+        for (uint32_t len : {0u, 1u, 3u, 4u, 5u, pp_bgzf_host::STORE_PAYLOAD - 1u, pp_bgzf_host::STORE_PAYLOAD})
+            if (check_deflate(len, kind, forms)) return 1;
+    printf("bgzf_host_check: deflate_block at 0, 1, 3, 4, 5, 65279 and 65280 bytes of zeros, noise and skewed counts inflates back with zlib "
+           "(%u stored, %u fixed, %u dynamic)\n", forms[0], forms[1], forms[2]);
     FILE *f = fopen(argv[1], "rb");
     if (!f) return perror(argv[1]), 2;
     std::vector<uint8_t> all;
