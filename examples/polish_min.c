@@ -5,6 +5,7 @@
  *   gcc -std=c99 -Iinclude examples/polish_min.c -Lpolypolish_amd/_build -lpolypolish_hip \
  *       -Wl,-rpath,$PWD/polypolish_amd/_build -o polish_min
  *   ./polish_min assembly.fasta alignments_1.sam [alignments_2.sam ...] > polished.fasta
+ *   ./polish_min assembly.fasta alignments_1.bam [alignments_2.bam ...] > polished.fasta     (through pp_polish_files)
  */
 #include <inttypes.h>
 #include <stdio.h>
@@ -22,6 +23,27 @@ int main(int argc, char **argv) {
     char err[1024] = "";
     pp_ctx *ctx = NULL;
     if (pp_ctx_create(0, &ctx)) return fail("no MI355X context (there is no CPU fallback)", "");
+
+    /* BAM files (told by content) have no host half: the whole command driver takes them through the record chain on the device --
+     * inflate, walk, decode, gate, polish -- and hands back the FASTA.  SAM text goes the long way below. */
+    int kind = PP_ALN_SAM;
+    if (pp_aln_file_kind(argv[2], &kind)) return fail(argv[2], pp_bam_last_error());
+    if (kind != PP_ALN_SAM) {
+        pp_polish_options opt;
+        pp_bytes fasta;
+        opt.fraction_invalid = 0.2;
+        opt.fraction_valid = 0.5;
+        opt.max_errors = 10;
+        opt.min_depth = 5;
+        opt.careful = 0;
+        opt.debug_path = NULL;
+        opt.quiet = 1;
+        if (pp_polish_files(ctx, argv[1], (const char *const *)(argv + 2), argc - 2, &opt, &fasta)) return fail("polish", pp_last_error(ctx));
+        fwrite(fasta.data, 1, (size_t)fasta.len, stdout);
+        pp_bytes_free(&fasta);
+        pp_ctx_destroy(ctx);
+        return 0;
+    }
 
     /* load_assembly (src/polish.rs:89-101) */
     pp_assembly *a = NULL;

@@ -367,8 +367,8 @@ int pp_bgzf_kernel_ms(const pp_bgzf *z, float *ms);
 void pp_bgzf_free(pp_bgzf *z);
 
 /* The FRONT END of the record chain for a caller who holds BAM: the alignment records of UNCOMPRESSED BAM bytes as a pp_raw_batch,
- * decoded on the device.  A file's BGZF blocks are inflated by pp_bgzf_inflate above, whose bytes go in here as PP_MEM_DEVICE; no
- * command reads BAM: the reference reads SAM text only, and so does the CLI.  A BAM CIGAR word is len << 4 | op with MIDNSHP=X -> 0..8, bit for bit pp_raw_batch.cigar; l_seq 0 is
+ * decoded on the device.  A file's BGZF blocks are inflated by pp_bgzf_inflate above, whose bytes go in here as PP_MEM_DEVICE; the
+ * commands read BAM files through exactly these calls (pp_aln_file_kind below; the reference reads SAM text only).  A BAM CIGAR word is len << 4 | op with MIDNSHP=X -> 0..8, bit for bit pp_raw_batch.cigar; l_seq 0 is
  * SEQ "*"; a record's read_name is an (off, len) range into the bytes, which is what pp_names_ids(..., PP_MEM_DEVICE) takes.
  *
  * Two HOST helpers need no device.  Both are memory-safe for any bytes, never read outside [0, n_bytes) and form no sum that could
@@ -464,7 +464,7 @@ void pp_bam_free(pp_bam *b);
 /* The WRITE side of the record chain for a caller who holds BAM: the filter's verdicts written back as a BAM file, on the device --
  * what `polypolish filter` does with SAM text (filter_sam, src/filter.rs:296-343: every line again, ZP:Z:fail appended to the aligned
  * ones that failed), for records.  The files it makes go back through pp_bgzf_inflate ... pp_bam_records into polish: the reference's
- * two-command workflow.  No command writes BAM either: this is a library call.
+ * two-command workflow.  `filter` on BAM input writes its outputs with this call and pp_bam_out_deflate.
  *   inputs       bytes[0, n_bytes): uncompressed BAM; records_at: where its header ends (pp_bam_header); rec_off[0, n_rec): the records,
  *                as for pp_bam_records not necessarily adjacent, ordered or distinct; pass[0, n_pass): HOST memory whatever `mem`, one
  *                byte per ALIGNED record (flag & 4 == 0) in index order -- the numbering of pp_filter_records' pass1 / pass2.
@@ -544,6 +544,20 @@ void pp_bgzf_out_counts(const pp_bgzf_out *o, uint64_t *stored, uint64_t *fixed,
 int pp_bgzf_out_write(const pp_bgzf_out *o, const char *path); /* download in slices, write the file */
 int pp_bgzf_out_kernel_ms(const pp_bgzf_out *o, float *ms);
 void pp_bgzf_out_free(pp_bgzf_out *o);
+
+/* What an alignment file holds, told by its CONTENT: the commands (pp_polish_files, pp_filter_files, pp_filter_polish_files) take SAM
+ * text as before and BAM through the record chain above, and ask this.  HOST, no context; reads only the head of the file.
+ *   PP_ALN_SAM      anything that is neither of the two below, an empty file included: the text routes keep their own errors.  A
+ *                   path that is no regular file (a pipe, a process substitution) is not opened: it is text
+ *   PP_ALN_BAM      BGZF -- 1f 8b 08, FEXTRA, a BC subfield of SLEN 2 among the extra subfields (it need not be the first) -- whose
+ *                   inflated bytes start with BAM\1; the first block(s) are inflated on the host for those four bytes, no more
+ *   PP_ALN_BAM_RAW  the file itself starts with BAM\1: uncompressed BAM
+ * PP_ERR_QUIT with the message in pp_bam_last_error(): a gzip member without BC ("... is gzip-compressed but not BGZF"); BGZF whose
+ * content is not BAM, a bgzipped SAM ("... is BGZF-compressed but does not hold BAM"); a file that begins 1f 8b and ends before a whole
+ * gzip header; a path that cannot be read ("unable to load alignments from ...", the drivers' words).  PP_ERR_ARG: null arguments.
+ * Neither 0x1f nor 0x01 occurs in a valid SAM line: no SAM input changes its route. */
+enum { PP_ALN_SAM = 0, PP_ALN_BAM = 1, PP_ALN_BAM_RAW = 2 };
+int pp_aln_file_kind(const char *path, int *kind);
 
 /* Per-contig figures the reference prints to stderr (src/polish.rs:206-227). */
 typedef struct {
@@ -842,14 +856,19 @@ typedef struct {
 } pp_bytes;
 void pp_bytes_free(pp_bytes *b);
 
-/* polish::polish (src/polish.rs:26-38): FASTA text exactly as the reference prints to stdout. */
+/* polish::polish (src/polish.rs:26-38): FASTA text exactly as the reference prints to stdout.
+ * `sams` are SAM text files or -- all of them -- BAM files (pp_aln_file_kind; a mix is PP_ERR_QUIT).  BAM goes through the record
+ * chain on the device, file by file: pp_bgzf_inflate -> pp_bam_header -> pp_bgzf_bam_walk -> pp_bam_records -> pp_names ->
+ * pp_batch_gate(pass = pp_bam_pass) -> pp_polish_add; pp_batch_prepare in between with PP_BAM_PREPARE=1 in the environment.
+ * Messages about a BAM file name its path and the block or the record (1-based, counting all records); "no alignments in <path>"
+ * for a file without aligned records.  Order of errors: INTEGRATION.md section 6. */
 int pp_polish_files(pp_ctx *ctx, const char *assembly, const char *const *sams, int n_sams,
                     const pp_polish_options *opt, pp_bytes *fasta);
 
 /* polish::polish on SEVERAL GPUs from one process: the host ingest runs once, every context (one per device, see
  * pp_ctx_create) gets the full batches and the emit ranges of its units (pp_shard_plan_create), the contexts polish
  * side by side and the FASTA is assembled on the host.  Same bytes as pp_polish_files; --debug is not available.
- * The error text is on ctxs[0]. */
+ * The error text is on ctxs[0].  BAM input runs on one GPU: with n_ctx > 1 it is refused (PP_ERR_QUIT). */
 int pp_polish_files_multi(pp_ctx *const *ctxs, int n_ctx, const char *assembly, const char *const *sams, int n_sams,
                           const pp_polish_options *opt, pp_bytes *fasta);
 
@@ -934,14 +953,18 @@ int pp_filter_thresholds(pp_ctx *ctx, const char *orientation, double low, doubl
 int pp_filter_records(pp_ctx *ctx, const pp_raw_batch raw[2], int mem, const char *orientation, double low, double high,
                       uint8_t *pass1, uint8_t *pass2, pp_filter_file_counts counts[2], pp_filter_report *report);
 
-/* filter::filter (src/filter.rs:26-37). */
+/* filter::filter (src/filter.rs:26-37).  in1 / in2 are both SAM text or both BAM (pp_aln_file_kind; one of each is PP_ERR_QUIT).
+ * BAM in, compressed BAM out: two front ends, one QNAME table for both files, pp_filter_records, then per file pp_bam_tagged(pass =
+ * the filter's own verdict) -> pp_bam_out_deflate -> pp_bgzf_out_write.  The log is the text route's.  An aligned BAM record without
+ * NM is refused here too, because pp_bam_records refuses it (the text route never looks at NM). */
 int pp_filter_files(pp_ctx *ctx, const char *in1, const char *in2, const char *out1,
                     const char *out2, const char *orientation, double low, double high, int quiet,
                     pp_filter_report *report);
 
 /* filter + polish in one process: the filter's verdicts go straight into the polish ingest,
  * the tagged SAMs are written only if out1/out2 are given (both or neither).  The FASTA is byte-identical
- * to `filter` followed by `polish` on its outputs. */
+ * to `filter` followed by `polish` on its outputs.  Two BAM inputs are decoded once: the filter's verdicts ANDed with pp_bam_pass go
+ * into pp_batch_gate, and out1 / out2 are BAM files, those of pp_filter_files. */
 int pp_filter_polish_files(pp_ctx *ctx, const char *assembly, const char *in1, const char *in2,
                            const char *out1, const char *out2, const char *orientation, double low, double high,
                            const pp_polish_options *opt, pp_filter_report *report, pp_bytes *fasta);

@@ -703,6 +703,21 @@ def bgzf_walk(data, start=0):
     return off, out, end
 
 
+ALN_SAM, ALN_BAM, ALN_BAM_RAW = 0, 1, 2
+
+
+def aln_file_kind(path):
+    """pp_aln_file_kind (no device needed): ALN_SAM, ALN_BAM (BGZF that holds BAM) or ALN_BAM_RAW (uncompressed BAM), told by the
+    head of the file.  gzip that is not BGZF, BGZF that does not hold BAM, a file cut inside its gzip header and a path that cannot be
+    read raise PolypolishError(ERR_QUIT).  Context.polish_files / filter_files / filter_polish_files ask this themselves."""
+    L = lib()
+    kind = C.c_int(0)
+    rc = L.pp_aln_file_kind(os.fsencode(path), C.byref(kind))
+    if rc:
+        raise PolypolishError(rc, L.pp_bam_last_error().decode())
+    return int(kind.value)
+
+
 class Bgzf(_Owned):
     """pp_bgzf_inflate: the BGZF blocks of a file inflated into one dense array in DEVICE memory, owned by this object.
       data, blk_off  mem = MEM_HOST: bytes / a uint8 array, and the blocks' offsets (None: the library walks the chain from offset 0);
@@ -1253,6 +1268,8 @@ class Context:
     # ---- whole commands -----------------------------------------------------------------------
     def polish_files(self, assembly, sams, fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5,
                      careful=False, debug=None, quiet=True):
+        """polish::polish (pp_polish_files): the FASTA bytes.  `sams` are SAM text files, or all of them BAM files (BGZF or
+        uncompressed; told by content, aln_file_kind): those go through the record chain on the device, inside the driver."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         arr = (C.c_char_p * max(len(sams), 1))(*[str(s).encode() for s in sams])
@@ -1265,7 +1282,8 @@ class Context:
     def filter_polish_files(self, assembly, in1, in2, out1=None, out2=None, orientation="auto", low=0.1, high=99.9,
                             fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5, careful=False,
                             debug=None, quiet=True):
-        """filter + polish in one process (pp_filter_polish_files): returns (FASTA bytes, filter report)."""
+        """filter + polish in one process (pp_filter_polish_files): returns (FASTA bytes, filter report).  Two BAM inputs are decoded
+        once for both halves; out1 / out2 are then BAM files as well."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         rep, out = FilterReport(), Bytes()
@@ -1277,6 +1295,8 @@ class Context:
         return data, _report_dict(rep)
 
     def filter_files(self, in1, in2, out1, out2, orientation="auto", low=0.1, high=99.9, quiet=True):
+        """filter::filter (pp_filter_files): writes out1 / out2, returns the report.  in1 / in2 are both SAM text, or both BAM:
+        BAM in gives compressed BAM out (pp_bam_tagged -> pp_bam_out_deflate)."""
         rep = FilterReport()
         self._chk(lib().pp_filter_files(self._h, str(in1).encode(), str(in2).encode(), str(out1).encode(),
                                         str(out2).encode(), orientation.encode(), low, high, int(quiet),

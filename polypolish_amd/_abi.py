@@ -159,6 +159,7 @@ SIGNATURES = {
     "pp_bgzf_out_write": (_i, [_vp, _str]),
     "pp_bgzf_out_kernel_ms": (_i, [_vp, _pf32]),
     "pp_bgzf_out_free": (None, [_vp]),
+    "pp_aln_file_kind": (_i, [_str, _P(_i)]),
     "pp_polish_set_emit": (_i, [_vp, _vp, _vp]),
     "pp_polish_begin": (_i, [_vp, _u32, _vp, _vp, _i, _P(Params)]),
     "pp_polish_add": (_i, [_vp, _P(AlnBatch), _i]),

@@ -32,6 +32,7 @@ static const char *HELP_FILTER =
     "      --in2 <IN2>                  Input SAM file - first second in pairs\n"
     "      --out1 <OUT1>                Output SAM file - first read in pairs\n"
     "      --out2 <OUT2>                Output SAM file - first second in pairs\n"
+    "                                   (two BAM inputs are read as they are and give two BAM outputs)\n"
     "      --orientation <ORIENTATION>  Expected pair orientation [default: auto]\n"
     "      --low <LOW>                  Low percentile threshold [default: 0.1]\n"
     "      --high <HIGH>                High percentile threshold [default: 99.9]\n"
@@ -41,7 +42,7 @@ static const char *HELP_POLISH =
     "polish a long-read assembly using short-read alignments\n\n"
     "Usage: polypolish polish [OPTIONS] <ASSEMBLY> [SAM]...\n\n"
     "Arguments:\n  <ASSEMBLY>  Assembly to polish (one file in FASTA format)\n"
-    "  [SAM]...    Short read alignments (one or more files in SAM format)\n\n"
+    "  [SAM]...    Short read alignments (one or more files in SAM format, or all of them in BAM format)\n\n"
     "Options:\n"
     "      --debug <DEBUG>                        Optional file to store per-base information for debugging purposes\n"
     "  -i, --fraction_invalid <FRACTION_INVALID>  A base must make up less than this fraction of the read depth to be considered invalid [default: 0.2]\n"
@@ -55,7 +56,8 @@ static const char *HELP_FUSED =
     "filter paired-end alignments by insert size and polish with them, in one process\n\n"
     "Usage: polypolish filter-polish [OPTIONS] --in1 <IN1> --in2 <IN2> <ASSEMBLY>\n\n"
     "Options: those of `filter` (--out1/--out2 optional: write the tagged SAMs as well) and of `polish`.\n"
-    "The FASTA on stdout is byte-identical to `filter` followed by `polish` on its outputs.\n";
+    "The FASTA on stdout is byte-identical to `filter` followed by `polish` on its outputs.\n"
+    "--in1/--in2 are both SAM text or both BAM; with BAM the optional outputs are BAM as well.\n";
 
 static int usage_error(const char *msg) {
     fprintf(stderr, "error: %s\n\nFor more information, try '--help'.\n", msg);
@@ -257,6 +259,15 @@ int main(int argc, char **argv) {
         // the path has only ever run with several contexts on ONE device -- PP_SHARE_GPU=n, tests on a one-GPU box -- so it
         // stays opt-in until it has been run on a multi-GPU node.)
         const bool few = !getenv("PP_GPUS") && !getenv("PP_SHARE_GPU");
+        // BAM input runs on one GPU: asking for several is refused whatever the box has
+        const bool several = (getenv("PP_GPUS") && atoi(getenv("PP_GPUS")) > 1) || (getenv("PP_SHARE_GPU") && atoi(getenv("PP_SHARE_GPU")) > 1);
+        for (size_t i = 0; several && i < sams.size(); i++) {
+            int kind = PP_ALN_SAM;
+            if (pp_aln_file_kind(sams[i], &kind) == PP_OK && kind != PP_ALN_SAM) {
+                fprintf(stderr, "\nError: BAM input (\"%s\") runs on one GPU: polish it without PP_GPUS / PP_SHARE_GPU, or convert it to SAM text\n", sams[i]);
+                return 1;
+            }
+        }
         std::vector<int> devs = polish_devices(device, few);
         if (devs.size() > 1) {
             std::vector<pp_ctx *> cs(devs.size(), nullptr);

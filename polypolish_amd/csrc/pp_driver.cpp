@@ -8,6 +8,7 @@
 #include <chrono>
 #include <functional>
 #include <future>
+#include <memory>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -20,6 +21,7 @@
 
 #include "polypolish_hip.h"
 #include "pp_host.h"
+#include "pp_bam_files.h"
 
 namespace {
 
@@ -189,6 +191,11 @@ struct RankResult {
 constexpr int HAND_BACK = -1;
 int hand_back_if_text_defect(int rc) { return rc == PP_ERR_QUIT || rc == PP_ERR_PANIC || rc == PP_ERR_NOT_ASCII ? HAND_BACK : rc; }
 
+struct BamGiven { pp_assembly *a; ppb::BamFile *const *fronts; pp_names *rnames, *qnames; };
+// a gated batch that went into the job: its file, and where its records start among the job's (a device error names a job record)
+struct BamAdded { int file; uint64_t base, n; const pp_gated *g; };
+constexpr uint32_t KIND_BAD_CONTIG = 4;  // DE_BAD_CONTIG (pp_internal.h), as pp_polish_error_record reports it
+
 // Everything one `polish` command allocates, opens or starts.  release() gives all of it back -- uploads in flight are joined
 // before the batches they read are freed, the FASTA buffer's toucher before the buffer -- and the destructor calls it: every
 // way out of the driver is a plain return.
@@ -205,6 +212,8 @@ struct PolishJob {
     // resume_log_at >= 0: the second look at an input the device tokenizer handed back, on the host ingest only.  The banner,
     // the assembly section and the lines of the files before that one are on stderr already: the log resumes at that file.
     int resume_log_at;
+    // BAM files that pp_filter_polish_files has opened and decoded already (all borrowed), or NULL
+    const BamGiven *given = nullptr;
     int handed_back_at = -1;  // the file at which this look ended with HAND_BACK
     pp_ctx *ctx = ctxs[0];    // carries the error text
     // Several contexts: every GPU uploads and tokenizes its own slice of each file (`sharded`), so a byte of text crosses
@@ -237,6 +246,16 @@ struct PolishJob {
     std::vector<pp_ingest *> gs;      // ... or one per file
     pp_dev_ingest *dg = nullptr;
     std::vector<pp_dev_ingest *> dgs;       // sharded ingest: one per context
+    // BAM input (all files of a command are of one kind): the record chain on the device, file by file (ingest_file_bam).  The gated
+    // batches (and the prepared ones, PP_BAM_PREPARE=1) live until pp_polish_finish has returned.
+    bool bam = given != nullptr;
+    std::vector<int> kinds;  // pp_aln_file_kind of every file
+    std::vector<std::unique_ptr<ppb::BamFile>> fronts;
+    pp_names *rnames = nullptr, *qnames = nullptr;  // RNAME -> contig index (seeded with the assembly's names); QNAME -> read_id
+    std::vector<pp_gated *> gated;
+    std::vector<pp_prepared *> prepared;
+    std::vector<BamAdded> added;
+    bool bam_prepare = getenv("PP_BAM_PREPARE") && atoi(getenv("PP_BAM_PREPARE")) != 0;
     std::vector<std::future<int>> pending;  // the upload of the file before
     bool begun = false;                     // pp_polish_begin has run on ctx
     uint64_t alignment_total = 0;
@@ -290,7 +309,18 @@ struct PolishJob {
         pp_ingest_free(g);
         pp_dev_ingest_free(dg);
         for (pp_dev_ingest *x : dgs) pp_dev_ingest_free(x);
-        pp_assembly_free(a);
+        for (pp_prepared *x : prepared) pp_prepared_free(x);
+        for (pp_gated *x : gated) pp_gated_free(x);
+        prepared.clear();
+        gated.clear();
+        added.clear();
+        fronts.clear();
+        if (!given) {
+            pp_names_free(qnames);
+            pp_names_free(rnames);
+        }
+        qnames = rnames = nullptr;
+        if (!given) pp_assembly_free(a);
         if (out_toucher.joinable()) out_toucher.join();
         free(out);
         pieces.clear();
@@ -336,6 +366,22 @@ int check_options_and_inputs(PolishJob &J) {
         snprintf(J.err, sizeof J.err, "\"%s\" file does not exist", path);
         return set_err(J.ctx, PP_ERR_QUIT, J.err);
     }
+    // SAM text or BAM, told by the files' heads (pp_aln_file_kind); all files of a command are of one kind
+    J.kinds.assign((size_t)J.n_sams, J.given ? PP_ALN_BAM : PP_ALN_SAM);
+    int first_sam = -1, first_bam = -1;
+    for (int i = 0; i < J.n_sams; i++) {
+        if (!J.given)
+            if (int rc = ppb::file_kind(J.ctx, J.sams[i], &J.kinds[(size_t)i])) return rc;
+        int &first = J.kinds[(size_t)i] == PP_ALN_SAM ? first_sam : first_bam;
+        if (first < 0) first = i;
+    }
+    if (first_sam >= 0 && first_bam >= 0)
+        return ppb::fail(J.ctx, PP_ERR_QUIT, "the alignment files of one command must all be SAM text or all be BAM: \"%s\" is SAM text, \"%s\" is BAM",
+                         J.sams[first_sam], J.sams[first_bam]);
+    J.bam = first_bam >= 0;
+    if (J.bam && J.multi)
+        return ppb::fail(J.ctx, PP_ERR_QUIT, "BAM input (\"%s\") runs on one GPU: polish it without PP_GPUS / several contexts, or convert it to SAM text",
+                         J.sams[first_bam]);
     // The device tokenizer uploads the SAM text as it is: map the files and pre-fault the mappings NOW, on background
     // threads, while the HIP runtime is still initialising (a copy out of an untouched mapping runs at a quarter of
     // the link's rate).
@@ -363,7 +409,8 @@ void log_banner(const PolishJob &J) {
 // load_assembly, polish.rs:93-106
 int load_assembly(PolishJob &J) {
     J.log("Loading assembly\n");
-    if (int rc = pp_assembly_load(J.assembly, &J.a, J.err, sizeof J.err)) return set_err(J.ctx, rc, J.err);
+    if (J.given) J.a = J.given->a;  // (loaded for the filter's RNAME table already)
+    else if (int rc = pp_assembly_load(J.assembly, &J.a, J.err, sizeof J.err)) return set_err(J.ctx, rc, J.err);
     J.nc = pp_assembly_n_contigs(J.a);
     J.off = pp_assembly_offsets(J.a);
     J.names.resize(J.nc);
@@ -396,6 +443,20 @@ void reserve_fasta(PolishJob &J) {
 int create_ingests(PolishJob &J) {
     const pp_polish_options *opt = J.opt;
     int rc = PP_OK;
+    if (J.bam) {  // no ingest object: the two name tables of the record chain, and the job the gated batches are added to
+        if (J.given) {
+            J.rnames = J.given->rnames;
+            J.qnames = J.given->qnames;
+        } else {
+            rc = pp_names_create(J.ctx, J.nc, &J.rnames);
+            if (rc == PP_OK) rc = ppb::seed_names(J.rnames, J.a);
+            if (rc == PP_OK) rc = pp_names_create(J.ctx, 0, &J.qnames);
+        }
+        if (rc == PP_OK) rc = pp_polish_begin(J.ctx, J.nc, J.off, pp_assembly_bases(J.a), PP_MEM_HOST, &J.prm);
+        J.begun = rc == PP_OK;
+        J.lap("device ready, polish job open");
+        return rc;
+    }
     if (J.multi) pp_ctx_enable_peers_(J.ctxs, J.n_ctx);
     if (J.sharded) {
         J.dgs.assign((size_t)J.n_ctx, nullptr);
@@ -513,6 +574,156 @@ int ingest_file_host(PolishJob &J, int i, pp_sam_counts &c) {
     return PP_OK;
 }
 
+// ---- BAM: the record chain on the device (pp_bam_files.h -> pp_batch_gate -> pp_polish_add), file by file ----
+// The error pp_polish_finish left about a job record, said about the BAM record it came from: the path and the 1-based number
+// counting all records of the file; a good alignment on a reference the assembly lacks in the reference's own words.
+int bam_polish_error(PolishJob &J, int rc) {
+    pp_ctx *const ctx = J.ctx;
+    uint64_t record = 0;
+    uint32_t kind = 0;
+    if ((rc != PP_ERR_QUIT && rc != PP_ERR_PANIC) || !pp_polish_error_record(ctx, &record, &kind)) return rc;
+    const std::string said = pp_last_error(ctx);
+    for (const BamAdded &A : J.added) {
+        if (record < A.base || record - A.base >= A.n) continue;
+        pp_aln_batch b;
+        const uint32_t *orig = nullptr;
+        pp_gated_batch(A.g, &b, &orig);
+        uint32_t o = 0, contig = 0;
+        if (pp_ctx_download(ctx, &o, orig + (record - A.base), 4) != PP_OK || pp_ctx_download(ctx, &contig, b.contig + (record - A.base), 4) != PP_OK) break;
+        if (kind == KIND_BAD_CONTIG)
+            return ppb::fail(ctx, rc, "query name %s in SAM but not in assembly: \"%s\" (record %llu)", ppb::name_of(J.rnames, contig).c_str(),
+                             J.sams[A.file], (unsigned long long)o + 1);
+        return ppb::fail(ctx, rc, "%s: \"%s\" (record %llu)", said.c_str(), J.sams[A.file], (unsigned long long)o + 1);
+    }
+    return set_err(ctx, rc, said.c_str());
+}
+
+int bam_add_gated(PolishJob &J, int i, const pp_gated *g) {
+    pp_aln_batch b;
+    pp_gated_batch(g, &b, nullptr);
+    if (!b.n_aln) return PP_OK;
+    const uint64_t base = J.added.empty() ? 0 : J.added.back().base + J.added.back().n;
+    if (J.added.size() == 1) {
+        // The second batch makes the job gather its batches into arrays of its own: room for all of them at once -- the two that are
+        // known, scaled by the files' sizes on disk for the files still to come -- instead of arrays that grow with every file
+        // (an allocation and a copy of what the files before filled, per array).
+        pp_aln_batch first;
+        pp_gated_batch(J.added[0].g, &first, nullptr);
+        double known = 0, all = 0;
+        for (int f = 0; f < J.n_sams; f++) {
+            all += (double)J.sam_bytes[(size_t)f];
+            if (f <= i) known += (double)J.sam_bytes[(size_t)f];
+        }
+        const double scale = known > 0 && all > known ? std::min(64.0, all / known * 1.02) : 1.0;
+        if (int rc = pp_polish_reserve(J.ctx, (uint64_t)((double)(first.n_aln + b.n_aln) * scale) + 1024,
+                                       (uint64_t)((double)(first.seq_bytes + b.seq_bytes) * scale) + 4096,
+                                       (uint64_t)((double)(first.n_cig_total + b.n_cig_total) * scale) + 1024))
+            return rc;
+    }
+    J.added.push_back(BamAdded{i, base, b.n_aln, g});
+    if (J.bam_prepare) {  // the direct path (pp_batch_prepare); off by default: DESIGN.md sections 2 and 3 have what it costs and saves
+        pp_prepared *p = nullptr;
+        if (int rc = pp_batch_prepare(J.ctx, J.nc, J.off, &b, PP_MEM_DEVICE, &p)) return rc;
+        J.prepared.push_back(p);
+        pp_prepared_batch(p, &b);
+    }
+    return pp_polish_add(J.ctx, &b, PP_MEM_DEVICE);
+}
+
+// One BAM file: front end -> pp_batch_gate(pass = the ZP:Z:fail bytes, ANDed with the filter's verdicts where the caller brings them) ->
+// pp_polish_add.  The reference streams, so when the decode or the gate refuses record N (QUIT / PANIC) the records in front of N are
+// decoded, the group still pending there dropped -- the trailing run of aligned records with the last aligned record's QNAME --, the
+// rest gated and polished together with the earlier files' batches (what replay_records_before_defect does for text): an error
+// found on the way stands, otherwise N's.
+int ingest_file_bam(PolishJob &J, int i, pp_sam_counts &c) {
+    pp_ctx *const ctx = J.ctx;
+    ppb::BamFile *B = nullptr;
+    if (J.given) B = J.given->fronts[i];
+    else {
+        J.fronts.emplace_back(new ppb::BamFile);
+        B = J.fronts.back().get();
+        if (int rc = B->open(ctx, J.sams[i], J.kinds[(size_t)i], J.rnames, &J.lap)) return rc;
+    }
+    int standing = PP_OK;  // the refusal at N
+    std::string standing_msg;
+    auto stand = [&](int rc) { standing = rc; standing_msg = pp_last_error(ctx); };
+    auto defect = [](int rc) { return rc == PP_ERR_QUIT || rc == PP_ERR_PANIC; };
+    std::vector<uint16_t> flag;
+    std::vector<uint64_t> rid;
+    bool have_groups = false;
+    auto groups = [&]() {
+        if (have_groups) return (int)PP_OK;
+        have_groups = true;
+        return ppb::download_groups(*B, B->n_decoded, flag, rid);
+    };
+    uint64_t limit = B->n_rec;
+    if (!B->rec) {
+        uint64_t bad = 0;
+        int rc = B->decode(limit, J.qnames, &bad);
+        if (defect(rc)) {
+            stand(rc);
+            if ((rc = B->decode(bad, J.qnames, nullptr))) return rc;
+            if ((rc = groups())) return rc;
+            uint64_t last = bad;  // one past the last aligned record in front of N
+            while (last > 0 && (flag[last - 1] & 4)) last--;
+            limit = last ? last - 1 : bad;
+            for (uint64_t q = limit; last && q-- > 0;) {
+                if (flag[q] & 4) continue;
+                if (rid[q] != rid[last - 1]) break;
+                limit = q;
+            }
+        } else if (rc) return rc;
+        if (J.lap.on) J.lap(("decoded " + B->path).c_str());
+    }
+    pp_raw_batch raw;
+    pp_bam_raw(B->rec, &raw);
+    const uint8_t *pass = nullptr;
+    uint64_t n_aligned = 0;
+    pp_bam_pass(B->rec, &pass, &n_aligned);
+    std::vector<uint8_t> both;  // the filter's verdicts (the fused command) ANDed with the ZP:Z:fail bytes the file came with
+    if (J.pass && J.n_pass[i] >= n_aligned && (standing || J.n_pass[i] == n_aligned)) {
+        both.resize(n_aligned ? n_aligned : 1);
+        for (uint64_t q = 0; q < n_aligned; q++) both[q] = pass[q] && J.pass[i][q];
+        pass = both.data();
+    } else if (J.pass) {  // verdicts for another number of records: the gate says so
+        pass = J.pass[i];
+        n_aligned = J.n_pass[i];
+    }
+    pp_gated *g = nullptr;
+    for (int round = 0;; round++) {
+        uint64_t n_pass = n_aligned;
+        if (limit < B->n_decoded) {
+            if (int rc = groups()) return rc;
+            n_pass = 0;
+            for (uint64_t q = 0; q < limit; q++) n_pass += !(flag[q] & 4);
+        }
+        raw.n_rec = limit;
+        uint64_t at = 0;
+        const int rc = pp_batch_gate(ctx, &raw, PP_MEM_DEVICE, J.opt->max_errors, J.opt->careful, pass, n_pass, &g, &at);
+        if (rc == PP_OK) break;
+        if (!defect(rc) || round > 1) return rc;
+        if (int rg = groups()) return rg;
+        const std::string qname = ppb::name_of(J.qnames, rid[at]);
+        if (rc == PP_ERR_QUIT)
+            ppb::fail(ctx, rc, "no alignments for read %s contain sequence: \"%s\" (record %llu)", qname.c_str(), J.sams[i], (unsigned long long)at + 1);
+        else
+            ppb::fail(ctx, rc, "aligned record of read %s has an empty CIGAR: \"%s\" (record %llu)", qname.c_str(), J.sams[i], (unsigned long long)at + 1);
+        stand(rc);
+        limit = at;
+    }
+    J.gated.push_back(g);
+    pp_gated_counts(g, &c);
+    B->drop_records();  // the gate's output is its own
+    if (standing) {
+        int rc = bam_add_gated(J, i, g);
+        if (rc == PP_OK) rc = pp_polish_finish(ctx);
+        if (defect(rc)) return bam_polish_error(J, rc);  // the device's message stands
+        return set_err(ctx, standing, standing_msg.c_str());
+    }
+    if (c.alignments == 0) return ppb::fail(ctx, PP_ERR_QUIT, "no alignments in \"%s\"", J.sams[i]);
+    return bam_add_gated(J, i, g);
+}
+
 // load_alignments, polish.rs:109-134.  A device tokenizer that meets a defect in the text (or bytes outside ASCII, which the
 // host parsers must judge) only says so: which defect the reference reports FIRST also depends on what its CIGAR walk makes of
 // the records before it, and the host ingest works that out (replay_records_before_defect): HAND_BACK, at J.handed_back_at.
@@ -522,7 +733,10 @@ int load_alignments(PolishJob &J) {
     for (int i = 0; i < J.n_sams; i++) {
         pp_sam_counts c{0, 0, 0};
         if (i == J.resume_log_at) J.log.quiet = J.opt->quiet != 0;
-        const int rc = J.sharded ? ingest_file_sharded(J, i, c) : J.dev_ingest ? ingest_file_device(J, i, c) : ingest_file_host(J, i, c);
+        const int rc = J.bam       ? ingest_file_bam(J, i, c)
+                       : J.sharded ? ingest_file_sharded(J, i, c)
+                       : J.dev_ingest ? ingest_file_device(J, i, c)
+                                      : ingest_file_host(J, i, c);
         if (rc == HAND_BACK) J.handed_back_at = i;
         if (rc) return rc;
         J.log("%s: %s alignments from %s reads\n", J.sams[i], commas(c.alignments).c_str(), commas(c.reads).c_str());
@@ -573,6 +787,7 @@ int polish_on_one_context(PolishJob &J) {
         if (rc == PP_OK && (J.dev_ingest || J.g)) rc = pp_polish_add(ctx, &batch, J.dev_ingest ? PP_MEM_DEVICE : PP_MEM_HOST);
     }
     if (rc == PP_OK) rc = pp_polish_finish(ctx);
+    if (rc && J.bam) rc = bam_polish_error(J, rc);
     J.lap("uploaded + polished on device");
     if (rc == PP_OK && J.dbg) {
         rc = write_debug_tsv(ctx, J.dbg, J.names, 0, J.off[J.nc]);
@@ -922,14 +1137,15 @@ int polish_once(PolishJob &J, pp_bytes *fasta) {
 extern "C" uint64_t pp_sam_group_cut_(const char *text, uint64_t size, uint64_t from) { return group_cut(text, (size_t)size, (size_t)from); }
 
 static int polish_files_impl(pp_ctx *const *ctxs, int n_ctx, const char *assembly, const char *const *sams, int n_sams,
-                             const pp_polish_options *opt, pp_bytes *fasta, const uint8_t *const *pass, const uint64_t *n_pass) {
+                             const pp_polish_options *opt, pp_bytes *fasta, const uint8_t *const *pass, const uint64_t *n_pass,
+                             const BamGiven *given = nullptr) {
     if (!ctxs[0] || !assembly || !opt || !fasta || (n_sams > 0 && !sams)) return PP_ERR_ARG;
     fasta->data = nullptr;
     fasta->len = 0;
     // The second look, if the device tokenizer hands a file back: a job of its own on the host ingest, after everything of
     // the first has been released.
     for (int resume_log_at = -1;;) {
-        PolishJob job{ctxs, n_ctx, assembly, sams, n_sams, opt, pass, n_pass, resume_log_at};
+        PolishJob job{ctxs, n_ctx, assembly, sams, n_sams, opt, pass, n_pass, resume_log_at, given};
         const int rc = polish_once(job, fasta);
         if (rc != HAND_BACK) return rc;
         resume_log_at = job.handed_back_at;
@@ -940,6 +1156,13 @@ extern "C" int pp_polish_files_filtered_(pp_ctx *ctx, const char *assembly, cons
                                          const pp_polish_options *opt, pp_bytes *fasta,
                                          const uint8_t *const *pass, const uint64_t *n_pass) {
     return polish_files_impl(&ctx, 1, assembly, sams, n_sams, opt, fasta, pass, n_pass);
+}
+
+int ppb::polish_bam_fronts(pp_ctx *ctx, const char *assembly, pp_assembly *a, ppb::BamFile *const *fronts, pp_names *rnames, pp_names *qnames,
+                           const char *const *paths, int n, const pp_polish_options *opt, pp_bytes *fasta, const uint8_t *const *pass,
+                           const uint64_t *n_pass) {
+    const BamGiven given{a, fronts, rnames, qnames};
+    return polish_files_impl(&ctx, 1, assembly, paths, n, opt, fasta, pass, n_pass, &given);
 }
 
 extern "C" int pp_polish_files(pp_ctx *ctx, const char *assembly, const char *const *sams, int n_sams,

@@ -24,6 +24,7 @@
 
 #include "polypolish_hip.h"
 #include "pp_host.h"
+#include "pp_bam_files.h"
 
 using pph::HugeBuf;
 using pph::parallel_for;
@@ -943,6 +944,97 @@ int filter_write(pp_ctx *ctx, const Log &log, const FilterRun &R, const char *co
     return PP_OK;
 }
 
+// ---- BAM in, BAM out: the record chain on the device (pp_bam_files.h -> pp_filter_records -> pp_bam_tagged -> pp_bam_out_deflate) ----
+struct BamFilterRun {
+    pp_assembly *a = nullptr;                       // the fused command only: its names make the ref_map the polish needs
+    pp_names *rnames = nullptr, *qnames = nullptr;  // RNAME -> contig index; ONE QNAME table for both files (the filter joins across files)
+    ppb::BamFile F[2];
+    std::vector<uint8_t> own[2];  // the filter's OWN verdicts per aligned record (what the output files carry)
+    uint64_t n_al[2] = {0, 0};
+    pp_filter_file_counts fc[2] = {};
+    pp_filter_report rep = {};
+    ~BamFilterRun() {
+        pp_names_free(qnames);
+        pp_names_free(rnames);
+        pp_assembly_free(a);
+    }
+};
+
+// both inputs' kinds; *bam = both are BAM.  One BAM and one SAM input is refused.
+int filter_input_kinds(pp_ctx *ctx, const char *const ins[2], int kinds[2], bool *bam) {
+    for (int f = 0; f < 2; f++)
+        if (int rc = ppb::file_kind(ctx, ins[f], &kinds[f])) return rc;
+    *bam = kinds[0] != PP_ALN_SAM && kinds[1] != PP_ALN_SAM;
+    if (!*bam && (kinds[0] != PP_ALN_SAM || kinds[1] != PP_ALN_SAM)) {
+        const int s = kinds[0] == PP_ALN_SAM ? 0 : 1;
+        return ppb::fail(ctx, PP_ERR_QUIT, "--in1 and --in2 must both be SAM text or both be BAM: \"%s\" is SAM text, \"%s\" is BAM", ins[s], ins[1 - s]);
+    }
+    return PP_OK;
+}
+
+// filter_core for two BAM files: the log is the text route's, word for word
+int filter_core_bam(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char *const ins[2], const int kinds[2], const char *assembly,
+                    const char *orientation, double low, double high, BamFilterRun &R) {
+    log("Loading alignments\n");
+    int rc = PP_OK;
+    if (assembly) {
+        char err[1400] = "";
+        if ((rc = pp_assembly_load(assembly, &R.a, err, sizeof err))) return pp_ctx_set_error_(ctx, rc, err);
+        if ((rc = pp_names_create(ctx, pp_assembly_n_contigs(R.a), &R.rnames))) return rc;
+        if ((rc = ppb::seed_names(R.rnames, R.a))) return rc;
+    }
+    if ((rc = pp_names_create(ctx, 0, &R.qnames))) return rc;
+    pp_raw_batch raw[2];
+    for (int f = 0; f < 2; f++) {
+        if ((rc = R.F[f].open(ctx, ins[f], kinds[f], R.rnames, &lap))) return rc;
+        if ((rc = R.F[f].decode(R.F[f].n_rec, R.qnames, nullptr))) return rc;
+        pp_bam_raw(R.F[f].rec, &raw[f]);
+        const uint8_t *zp = nullptr;
+        pp_bam_pass(R.F[f].rec, &zp, &R.n_al[f]);
+        R.own[f].assign(R.n_al[f] ? R.n_al[f] : 1, 0);
+    }
+    lap("alignments loaded");
+    if (R.n_al[0] == 0) {
+        log("%s: 0 alignments from 0 reads\n", ins[0]);
+        return ppb::fail(ctx, PP_ERR_QUIT, "no alignments found in \"%s\"", ins[0]);
+    }
+    rc = pp_filter_records(ctx, raw, PP_MEM_DEVICE, orientation, low, high, R.own[0].data(), R.own[1].data(), R.fc, &R.rep);
+    for (int f = 0; f < 2; f++)
+        log("%s: %s alignments from %s reads\n", ins[f], commas(R.fc[f].alignments).c_str(), commas(R.fc[f].reads).c_str());
+    log("\nFinding insert size thresholds\n");
+    const uint64_t *oc = R.rep.orientation_counts;
+    if (rc && oc[0] + oc[1] + oc[2] + oc[3] == 0) return rc;  // (nothing was counted: the error is all there is to say)
+    static const char *ONAMES[4] = {"fr", "rf", "ff", "rr"};
+    for (int o = 0; o < 4; o++) log("%s: %s pairs\n", ONAMES[o], commas(oc[o]).c_str());
+    if (rc) return rc;
+    if (strcmp(orientation, "auto") == 0) log("\nAutomatically determined correct orientation: %s\n\n", ONAMES[R.rep.orientation & 3]);
+    else log("\nUser-specified correct orientation: %s\n\n", orientation);
+    log("Low threshold:  %u (%s)\nHigh threshold: %u (%s)\n\n", R.rep.low_threshold, percentile_name(low).c_str(), R.rep.high_threshold,
+        percentile_name(high).c_str());
+    lap("verdicts from the device");
+    return PP_OK;
+}
+
+// filter_sams for BAM: every record again, ZP:Z:fail appended where the filter's own verdict is 0, compressed, written
+int filter_write_bam(pp_ctx *ctx, const Log &log, const BamFilterRun &R, const char *const ins[2], const char *const outs[2]) {
+    log("Filtering SAM files\n");
+    for (int f = 0; f < 2; f++) {
+        const ppb::BamFile &F = R.F[f];
+        pp_bam_out *t = nullptr;
+        pp_bgzf_out *c = nullptr;
+        uint64_t bad = 0, p_ = 0, f_ = 0, blocks = 0;
+        int rc = pp_bam_tagged(ctx, F.bytes, F.n_bytes, F.records_at, F.rec_off, F.n_rec, F.mem, R.own[f].data(), R.n_al[f], &t, &bad);
+        if (rc == PP_OK) rc = pp_bam_out_deflate(ctx, t, &c);
+        if (rc == PP_OK) pp_bam_out_counts(t, &p_, &f_, &blocks);
+        pp_bam_out_free(t);
+        if (rc == PP_OK) rc = pp_bgzf_out_write(c, outs[f]);
+        pp_bgzf_out_free(c);
+        if (rc) return rc;
+        log("Filtering %s:\n  %s pass\n  %s fail\n\n", ins[f], commas(p_).c_str(), commas(f_).c_str());
+    }
+    return PP_OK;
+}
+
 int check_filter_options(pp_ctx *ctx, const char *const *names, int n_names, double low, double high) {
     // check_inputs, filter.rs:40-53
     for (int i = 0; i < n_names; i++)
@@ -965,9 +1057,22 @@ extern "C" int pp_filter_files(pp_ctx *ctx, const char *in1, const char *in2, co
     if (int rc = check_filter_options(ctx, f4, 4, low, high)) return rc;
     log("\nStarting Polypolish filter\n%s\n\nInput alignments:\n  %s\n  %s\n\nOutput alignments:\n  %s\n  %s\n\n"
         "Settings:\n  --orientation %s\n  --low %g\n  --high %g\n\n", pp_version(), in1, in2, out1, out2, orientation, low, high);
+    const char *ins[2] = {in1, in2}, *outs[2] = {out1, out2};
+    int kinds[2] = {PP_ALN_SAM, PP_ALN_SAM};
+    bool bam = false;
+    if (int rc = filter_input_kinds(ctx, ins, kinds, &bam)) return rc;
+    if (bam) {  // BAM in, compressed BAM out
+        BamFilterRun B;
+        if (int rc = filter_core_bam(ctx, log, lap, ins, kinds, nullptr, orientation, low, high, B)) return rc;
+        if (int rc = filter_write_bam(ctx, log, B, ins, outs)) return rc;
+        lap("filtered BAMs written");
+        if (report) *report = B.rep;
+        log("Finished!\nAlignments before filtering: %s\nAlignments after filtering:  %s\n\nTime to run: %s\n\n",
+            commas(B.rep.before_count).c_str(), commas(B.rep.after_count).c_str(), format_duration(lap.seconds()).c_str());
+        return PP_OK;
+    }
     FilterRun R;
     if (int rc = filter_core(ctx, log, lap, in1, in2, orientation, low, high, R)) return rc;
-    const char *ins[2] = {in1, in2}, *outs[2] = {out1, out2};
     uint64_t after = 0;
     if (int rc = filter_write(ctx, log, R, ins, outs, &after)) return rc;
     lap("filtered SAMs written");
@@ -997,9 +1102,25 @@ extern "C" int pp_filter_polish_files(pp_ctx *ctx, const char *assembly, const c
     if (int rc = check_filter_options(ctx, f4, out1 ? 4 : 2, low, high)) return rc;
     log("\nStarting Polypolish filter + polish (fused)\n%s\n\nInput alignments:\n  %s\n  %s\n\n"
         "Filter settings:\n  --orientation %s\n  --low %g\n  --high %g\n\n", pp_version(), in1, in2, orientation, low, high);
+    const char *ins[2] = {in1, in2}, *outs[2] = {out1, out2};
+    int kinds[2] = {PP_ALN_SAM, PP_ALN_SAM};
+    bool bam = false;
+    if (int rc = filter_input_kinds(ctx, ins, kinds, &bam)) return rc;
+    if (bam) {  // the records are decoded once: the filter's verdicts go into the gate, ANDed with the ZP:Z:fail bytes there
+        BamFilterRun B;
+        if (int rc = filter_core_bam(ctx, log, lap, ins, kinds, assembly, orientation, low, high, B)) return rc;
+        if (out1) {
+            if (int rc = filter_write_bam(ctx, log, B, ins, outs)) return rc;
+            lap("filtered BAMs written");
+        }
+        if (report) *report = B.rep;
+        log("Alignments before filtering: %s\nAlignments after filtering:  %s\n", commas(B.rep.before_count).c_str(), commas(B.rep.after_count).c_str());
+        const uint8_t *pass[2] = {B.own[0].data(), B.own[1].data()};
+        ppb::BamFile *fronts[2] = {&B.F[0], &B.F[1]};
+        return ppb::polish_bam_fronts(ctx, assembly, B.a, fronts, B.rnames, B.qnames, ins, 2, opt, fasta, pass, B.n_al);
+    }
     FilterRun R;
     if (int rc = filter_core(ctx, log, lap, in1, in2, orientation, low, high, R)) return rc;
-    const char *ins[2] = {in1, in2}, *outs[2] = {out1, out2};
     uint64_t after = 0;
     if (out1) {
         if (int rc = filter_write(ctx, log, R, ins, outs, &after)) return rc;

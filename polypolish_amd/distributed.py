@@ -153,6 +153,16 @@ def main(argv=None):
     ap.add_argument("assembly")
     ap.add_argument("sam", nargs="*")
     a = ap.parse_args(argv)
+    # BAM input runs on one GPU (`polypolish polish`, Context.polish_files): the ranks here share the host ingest of SAM text
+    for path in a.sam:
+        if not os.path.isfile(path):
+            continue
+        try:
+            kind = pp.aln_file_kind(path)
+        except pp.PolypolishError as e:
+            raise SystemExit(f"Error: {e.msg}")
+        if kind != pp.ALN_SAM:
+            raise SystemExit(f"Error: BAM input (\"{path}\") runs on one GPU: polish it with `polypolish polish`, or convert it to SAM text")
     # stdout carries the FASTA and nothing else: libraries that chat on fd 1 (gloo's "[Gloo] Rank ..." lines)
     # are pointed at stderr for the whole run
     sys.stdout.flush()
