@@ -12,7 +12,7 @@ OUT      := polypolish_amd/_build
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-function
 
 LIB  := $(OUT)/libpolypolish_hip.so
-OBJS := $(OUT)/pp_kernels.o $(OUT)/pp_filter.o $(OUT)/pp_tokenize.o $(OUT)/pp_filter_dev.o $(OUT)/pp_filter_rec.o $(OUT)/pp_comm.o $(OUT)/pp_shard_dev.o $(OUT)/pp_prepare.o $(OUT)/pp_gate.o $(OUT)/pp_names.o $(OUT)/pp_bam.o $(OUT)/pp_bam_walk.o $(OUT)/pp_bgzf.o $(OUT)/pp_bam_out.o $(OUT)/pp_bgzf_deflate.o $(OUT)/pp_ingest.o $(OUT)/pp_driver.o $(OUT)/pp_filter_host.o $(OUT)/pp_shard.o $(OUT)/pp_bam_files.o
+OBJS := $(OUT)/pp_kernels.o $(OUT)/pp_filter.o $(OUT)/pp_tokenize.o $(OUT)/pp_filter_dev.o $(OUT)/pp_filter_rec.o $(OUT)/pp_comm.o $(OUT)/pp_shard_dev.o $(OUT)/pp_prepare.o $(OUT)/pp_gate.o $(OUT)/pp_names.o $(OUT)/pp_bam.o $(OUT)/pp_bam_walk.o $(OUT)/pp_bgzf.o $(OUT)/pp_bam_out.o $(OUT)/pp_bgzf_deflate.o $(OUT)/pp_ingest.o $(OUT)/pp_driver.o $(OUT)/pp_driver_text.o $(OUT)/pp_driver_multi.o $(OUT)/pp_driver_bam.o $(OUT)/pp_filter_host.o $(OUT)/pp_shard.o $(OUT)/pp_bam_files.o
 
 all: $(LIB) bin/polypolish bin/polish_min oracle tools/_build/libsamgen.so
 
@@ -20,7 +20,7 @@ $(OUT)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/polypolish_hip.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(OUT)/%.o: $(CSRC)/%.cpp include/polypolish_hip.h $(CSRC)/pp_host.h $(CSRC)/pp_bam_files.h
+$(OUT)/%.o: $(CSRC)/%.cpp include/polypolish_hip.h $(CSRC)/pp_host.h $(CSRC)/pp_bam_files.h $(CSRC)/pp_driver.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(HIPFLAGS) -x c++ -c $< -o $@
 
@@ -59,7 +59,7 @@ variant: $(LIB)
 # the host side (parsers, filter loader and writer, planner, drivers) under AddressSanitizer; the device objects as they are:
 #   make asan && LD_PRELOAD=$$(hipcc -print-file-name=libclang_rt.asan-x86_64.so) ASAN_OPTIONS=detect_leaks=0 \
 #       PP_LIB_PATH=$(OUT)/asan/libpolypolish_hip.so python -m pytest tests -m "not gpu" -q
-HOSTSRC := pp_ingest pp_filter_host pp_shard pp_driver pp_bam_files
+HOSTSRC := pp_ingest pp_filter_host pp_shard pp_driver pp_driver_text pp_driver_multi pp_driver_bam pp_bam_files
 asan: $(LIB)
 	@mkdir -p $(OUT)/asan
 	for f in $(HOSTSRC); do $(HIPCC) --offload-arch=$(ARCH) -O1 -g -std=c++17 -ffp-contract=off -fPIC -Iinclude -I$(CSRC) \

@@ -1,7 +1,7 @@
 // pp_bam_files.h -- the front end of the command drivers for ONE BAM file (pp_bam_files.cpp): host code over the C ABI of
 // include/polypolish_hip.h only.  It joins the links of the record chain that the drivers share,
 //   file -> pp_bgzf_inflate -> pp_bam_header -> pp_names (ref_map) -> pp_bgzf_bam_walk -> pp_bam_records -> pp_names_ids (read_id),
-// and owns their objects.  pp_driver.cpp takes the records on through pp_batch_gate into the polish, pp_filter_host.cpp through
+// and owns their objects.  pp_driver_bam.cpp takes the records on through pp_batch_gate into the polish, pp_filter_host.cpp through
 // pp_filter_records into pp_bam_tagged / pp_bam_out_deflate.  From the compressed file on no alignment byte is decoded on the host.
 #pragma once
 #include <string>

@@ -1,0 +1,178 @@
+// pp_driver_bam.cpp -- the polish driver's BAM route: the record chain on the device (pp_bam_files.h -> pp_batch_gate ->
+// pp_polish_add), file by file, on one context.  The fronts and the name tables are the job's own, or the fused command's
+// (PolishJob::borrow), which has decoded the files for its filter already.
+#include "pp_driver.h"
+
+namespace ppd {
+
+constexpr uint32_t KIND_BAD_CONTIG = 4;  // DE_BAD_CONTIG (pp_internal.h), as pp_polish_error_record reports it
+
+void BamRoute::reset() {
+    for (pp_prepared *x : prepared) pp_prepared_free(x);
+    for (pp_gated *x : gated) pp_gated_free(x);
+    prepared.clear();
+    gated.clear();
+    added.clear();
+    fronts.clear();
+    opened.clear();
+    if (!borrowed) {
+        pp_names_free(qnames);
+        pp_names_free(rnames);
+    }
+    qnames = rnames = nullptr;
+}
+
+// no ingest object: the two name tables of the record chain, and the job the gated batches are added to
+int bam_create(PolishJob &J) {
+    BamRoute &R = J.bam;
+    int rc = PP_OK;
+    if (!R.borrowed) {
+        rc = pp_names_create(J.ctx, J.nc, &R.rnames);
+        if (rc == PP_OK) rc = ppb::seed_names(R.rnames, J.a);
+        if (rc == PP_OK) rc = pp_names_create(J.ctx, 0, &R.qnames);
+    }
+    if (rc == PP_OK) rc = begin_job(J, J.ctx);
+    J.lap("device ready, polish job open");
+    return rc;
+}
+
+// The error pp_polish_finish left about a job record, said about the BAM record it came from: the path and the 1-based number
+// counting all records of the file; a good alignment on a reference the assembly lacks in the reference's own words.
+int bam_polish_error(PolishJob &J, int rc) {
+    pp_ctx *const ctx = J.ctx;
+    uint64_t record = 0;
+    uint32_t kind = 0;
+    if ((rc != PP_ERR_QUIT && rc != PP_ERR_PANIC) || !pp_polish_error_record(ctx, &record, &kind)) return rc;
+    const std::string said = pp_last_error(ctx);
+    Origin o;
+    pp_aln_batch b;
+    uint32_t contig = 0;
+    if (!origin_of(J.bam.added, record, &o)) return set_err(ctx, rc, said.c_str());
+    pp_gated_batch(J.bam.gated[(size_t)o.s->source], &b, nullptr);
+    if (pp_ctx_download(ctx, &contig, b.contig + o.at, 4) != PP_OK) return set_err(ctx, rc, said.c_str());
+    if (kind == KIND_BAD_CONTIG)
+        return ppb::fail(ctx, rc, "query name %s in SAM but not in assembly: \"%s\" (record %llu)", ppb::name_of(J.bam.rnames, contig).c_str(),
+                         J.sams[o.s->source], (unsigned long long)o.record + 1);
+    return ppb::fail(ctx, rc, "%s: \"%s\" (record %llu)", said.c_str(), J.sams[o.s->source], (unsigned long long)o.record + 1);
+}
+
+static int bam_add_gated(PolishJob &J, int i, const pp_gated *g) {
+    BamRoute &R = J.bam;
+    pp_aln_batch b;
+    const uint32_t *orig = nullptr;
+    pp_gated_batch(g, &b, &orig);
+    if (!b.n_aln) return PP_OK;
+    if (R.added.size() == 1) {
+        // The second batch makes the job gather its batches into arrays of its own: room for all of them at once -- the two that are
+        // known, scaled by the files' sizes on disk for the files still to come -- instead of arrays that grow with every file
+        // (an allocation and a copy of what the files before filled, per array).
+        pp_aln_batch first;
+        pp_gated_batch(R.gated[(size_t)R.added[0].source], &first, nullptr);
+        const double known = bytes_on_disk(J, i + 1), all = bytes_on_disk(J, J.n_sams);
+        const double scale = known > 0 && all > known ? scale_to_all_files(all, known) : 1.0;
+        if (int rc = reserve_scaled(J.ctx, first.n_aln + b.n_aln, first.seq_bytes + b.seq_bytes, first.n_cig_total + b.n_cig_total, scale)) return rc;
+    }
+    R.added.push_back(Stretch{b.n_aln, orig, PP_MEM_DEVICE, J.ctx, 0, i});
+    if (R.prepare) {  // the direct path (pp_batch_prepare); off by default: DESIGN.md sections 2 and 3 have what it costs and saves
+        pp_prepared *p = nullptr;
+        if (int rc = pp_batch_prepare(J.ctx, J.nc, J.off, &b, PP_MEM_DEVICE, &p)) return rc;
+        R.prepared.push_back(p);
+        pp_prepared_batch(p, &b);
+    }
+    return pp_polish_add(J.ctx, &b, PP_MEM_DEVICE);
+}
+
+// One BAM file: front end -> pp_batch_gate(pass = the ZP:Z:fail bytes, ANDed with the filter's verdicts where the caller brings them) ->
+// pp_polish_add.  The reference streams, so when the decode or the gate refuses record N (QUIT / PANIC) the records in front of N are
+// decoded, the group still pending there dropped -- the trailing run of aligned records with the last aligned record's QNAME --, the
+// rest gated and polished together with the earlier files' batches (what replay_records_before_defect does for text): an error
+// found on the way stands, otherwise N's.
+int ingest_file_bam(PolishJob &J, int i, pp_sam_counts &c) {
+    pp_ctx *const ctx = J.ctx;
+    BamRoute &R = J.bam;
+    if (!R.borrowed) {
+        R.opened.emplace_back(new ppb::BamFile);
+        R.fronts.push_back(R.opened.back().get());
+        if (int rc = R.fronts[(size_t)i]->open(ctx, J.sams[i], R.kinds[(size_t)i], R.rnames, &J.lap)) return rc;
+    }
+    ppb::BamFile *const B = R.fronts[(size_t)i];
+    int standing = PP_OK;  // the refusal at N
+    std::string standing_msg;
+    auto stand = [&](int rc) { standing = rc; standing_msg = pp_last_error(ctx); };
+    auto defect = [](int rc) { return rc == PP_ERR_QUIT || rc == PP_ERR_PANIC; };
+    std::vector<uint16_t> flag;
+    std::vector<uint64_t> rid;
+    bool have_groups = false;
+    auto groups = [&]() {
+        if (have_groups) return (int)PP_OK;
+        have_groups = true;
+        return ppb::download_groups(*B, B->n_decoded, flag, rid);
+    };
+    uint64_t limit = B->n_rec;
+    if (!B->rec) {
+        uint64_t bad = 0;
+        int rc = B->decode(limit, R.qnames, &bad);
+        if (defect(rc)) {
+            stand(rc);
+            if ((rc = B->decode(bad, R.qnames, nullptr))) return rc;
+            if ((rc = groups())) return rc;
+            uint64_t last = bad;  // one past the last aligned record in front of N
+            while (last > 0 && (flag[last - 1] & 4)) last--;
+            limit = last ? last - 1 : bad;
+            for (uint64_t q = limit; last && q-- > 0;) {
+                if (flag[q] & 4) continue;
+                if (rid[q] != rid[last - 1]) break;
+                limit = q;
+            }
+        } else if (rc) return rc;
+        if (J.lap.on) J.lap(("decoded " + B->path).c_str());
+    }
+    pp_raw_batch raw;
+    pp_bam_raw(B->rec, &raw);
+    const uint8_t *pass = nullptr;
+    uint64_t n_aligned = 0;
+    pp_bam_pass(B->rec, &pass, &n_aligned);
+    std::vector<uint8_t> both;  // the filter's verdicts (the fused command) ANDed with the ZP:Z:fail bytes the file came with
+    if (J.pass && J.n_pass[i] >= n_aligned && (standing || J.n_pass[i] == n_aligned)) {
+        both.resize(n_aligned ? n_aligned : 1);
+        for (uint64_t q = 0; q < n_aligned; q++) both[q] = pass[q] && J.pass[i][q];
+        pass = both.data();
+    } else if (J.pass) {  // verdicts for another number of records: the gate says so
+        pass = J.pass[i];
+        n_aligned = J.n_pass[i];
+    }
+    pp_gated *g = nullptr;
+    for (int round = 0;; round++) {
+        uint64_t n_pass = n_aligned;
+        if (limit < B->n_decoded) {
+            if (int rc = groups()) return rc;
+            n_pass = 0;
+            for (uint64_t q = 0; q < limit; q++) n_pass += !(flag[q] & 4);
+        }
+        raw.n_rec = limit;
+        uint64_t at = 0;
+        const int rc = pp_batch_gate(ctx, &raw, PP_MEM_DEVICE, J.opt->max_errors, J.opt->careful, pass, n_pass, &g, &at);
+        if (rc == PP_OK) break;
+        if (!defect(rc) || round > 1) return rc;
+        if (int rg = groups()) return rg;
+        const std::string qname = ppb::name_of(R.qnames, rid[at]);
+        if (rc == PP_ERR_QUIT)
+            ppb::fail(ctx, rc, "no alignments for read %s contain sequence: \"%s\" (record %llu)", qname.c_str(), J.sams[i], (unsigned long long)at + 1);
+        else
+            ppb::fail(ctx, rc, "aligned record of read %s has an empty CIGAR: \"%s\" (record %llu)", qname.c_str(), J.sams[i], (unsigned long long)at + 1);
+        stand(rc);
+        limit = at;
+    }
+    R.gated.push_back(g);
+    pp_gated_counts(g, &c);
+    B->drop_records();  // the gate's output is its own
+    if (standing) {
+        int rc = bam_add_gated(J, i, g);
+        if (rc == PP_OK) rc = pp_polish_finish(ctx);
+        return replayed_or_refusal(ctx, bam_polish_error(J, rc), standing, standing_msg.c_str());
+    }
+    if (c.alignments == 0) return ppb::fail(ctx, PP_ERR_QUIT, "no alignments in \"%s\"", J.sams[i]);
+    return bam_add_gated(J, i, g);
+}
+
+}  // namespace ppd

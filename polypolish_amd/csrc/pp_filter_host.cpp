@@ -19,6 +19,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
+#include <functional>
 #include <string>
 #include <unordered_map>
 
@@ -765,27 +766,52 @@ extern "C" int pp_filter_write_text(const char *text, uint64_t size, const uint8
 
 namespace {
 
+// One filter run, SAM text or BAM: what it loaded, the verdicts and the report, each number filled in where it is known.
 struct FilterRun {
-    pp_filter_loaded *L = nullptr;  // host load ...
+    bool bam = false;
+    int kinds[2] = {PP_ALN_SAM, PP_ALN_SAM};
+    pp_filter_loaded *L = nullptr;  // SAM text: host load ...
     pp_filter_dev *DL = nullptr;    // ... or device load (PP_DEVICE_FILTER=1)
-    uint64_t n_aln[2] = {0, 0};
-    std::vector<uint8_t> pass[2];
-    uint64_t before = 0;
-    uint32_t lo = 0, hi = 0;
-    int correct = -1;
-    uint64_t counts[4] = {0, 0, 0, 0};
-    ~FilterRun() {
+    // BAM: the record chain on the device (pp_bam_files.h -> pp_filter_records -> pp_bam_tagged -> pp_bam_out_deflate)
+    pp_assembly *a = nullptr;                       // the fused command only: its names make the ref_map the polish needs
+    pp_names *rnames = nullptr, *qnames = nullptr;  // RNAME -> contig index; ONE QNAME table for both files (the filter joins across files)
+    ppb::BamFile F[2];
+    uint64_t n_aln[2] = {0, 0};    // aligned records per file
+    std::vector<uint8_t> pass[2];  // the filter's OWN verdict per aligned record (what the output files carry)
+    pp_filter_report rep = {};
+    void release_parse_memory() {
         pp_filter_loaded_free(L);
         pp_filter_dev_free(DL);
+        L = nullptr;
+        DL = nullptr;
+    }
+    ~FilterRun() {
+        release_parse_memory();
+        pp_names_free(qnames);
+        pp_names_free(rnames);
+        pp_assembly_free(a);
     }
 };
 
+// The insert-size section of the log, step by step as a core gets there (an error may end it after any step): 1 the pairs per
+// orientation, 2 the orientation that counts, 3 the thresholds
+const char *const ONAMES[4] = {"fr", "rf", "ff", "rr"};
+void log_insert_sizes(const Log &log, int step, const pp_filter_report &rep, const char *orientation, double low, double high) {
+    if (step == 1)
+        for (int o = 0; o < 4; o++) log("%s: %s pairs\n", ONAMES[o], commas(rep.orientation_counts[o]).c_str());
+    else if (step == 2 && strcmp(orientation, "auto") == 0) log("\nAutomatically determined correct orientation: %s\n\n", ONAMES[rep.orientation & 3]);
+    else if (step == 2) log("\nUser-specified correct orientation: %s\n\n", orientation);
+    else
+        log("Low threshold:  %u (%s)\nHigh threshold: %u (%s)\n\n", rep.low_threshold, percentile_name(low).c_str(), rep.high_threshold,
+            percentile_name(high).c_str());
+}
+
 // load_alignments + get_insert_size_thresholds + the pass/fail verdicts (filter.rs:26-34 without filter_sams)
-int filter_core(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char *in1, const char *in2, const char *orientation,
+int filter_core(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char *const ins[2], const char *orientation,
                 double low, double high, FilterRun &R) {
     auto set_err = [&](int code, const char *msg) { return pp_ctx_set_error_(ctx, code, msg); };
     log("Loading alignments\n");
-    const char *ins[2] = {in1, in2};
+    const char *in1 = ins[0], *in2 = ins[1];
     // PP_DEVICE_FILTER=1: load_alignments as kernels (pp_filter_dev.hip).  Default is the host loader: its parse
     // overlaps the HIP runtime's start-up, which the device loader has to wait for (measured: 0.86 s vs 1.07 s).
     bool dev_load = getenv("PP_DEVICE_FILTER") && atoi(getenv("PP_DEVICE_FILTER")) != 0;
@@ -813,7 +839,7 @@ int filter_core(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char *in
     const uint32_t n_reads = in.n_reads;
     R.n_aln[0] = in.file[0].n_aln;
     R.n_aln[1] = in.file[1].n_aln;
-    R.before = R.n_aln[0] + R.n_aln[1];
+    R.rep.before_count = R.n_aln[0] + R.n_aln[1];
     rc = pp_filter_begin(ctx, &in, dev_load ? PP_MEM_DEVICE : PP_MEM_HOST);
     if (rc) return rc;
 
@@ -824,7 +850,7 @@ int filter_core(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char *in
     rc = pp_filter_samples(ctx, orient.data(), insert.data());
     if (rc) return rc;
     lap("samples from the device");
-    uint64_t counts[4] = {0, 0, 0, 0};
+    uint64_t *const counts = R.rep.orientation_counts;
     const unsigned red_threads = std::max(1u, std::min({std::thread::hardware_concurrency(), 16u, n_reads / 65536u + 1u}));
     {   // orientation counts, a slice of the reads per thread
         std::vector<std::array<uint64_t, 4>> part(red_threads, std::array<uint64_t, 4>{0, 0, 0, 0});
@@ -842,8 +868,7 @@ int filter_core(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char *in
     if (counts[0] + counts[1] + counts[2] + counts[3] == 0)
         return set_err(PP_ERR_QUIT, "no one-alignment-per-read pairs available to determine orientation and "
                                     "insert size thresholds");
-    static const char *ONAMES[4] = {"fr", "rf", "ff", "rr"};
-    for (int o = 0; o < 4; o++) log("%s: %s pairs\n", ONAMES[o], commas(counts[o]).c_str());
+    log_insert_sizes(log, 1, R.rep, orientation, low, high);
     int correct = -1;
     if (strcmp(orientation, "auto") == 0) {  // auto_determine_orientation, filter.rs:238-246
         const uint64_t mx = *std::max_element(counts, counts + 4);
@@ -851,12 +876,12 @@ int filter_core(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char *in
         for (int o = 0; o < 4; o++)
             if (counts[o] == mx) { n_max++; correct = o; }
         if (n_max != 1) return set_err(PP_ERR_QUIT, "could not automatically determine read pair orientation");
-        log("\nAutomatically determined correct orientation: %s\n\n", ONAMES[correct]);
     } else {
         for (int o = 0; o < 4; o++)
             if (strcmp(orientation, ONAMES[o]) == 0) correct = o;
-        log("\nUser-specified correct orientation: %s\n\n", orientation);
     }
+    R.rep.orientation = correct;
+    log_insert_sizes(log, 2, R.rep, orientation, low, high);
     // get_percentile (filter.rs:249-259) is an order statistic of the correctly oriented pairs' insert sizes: taken
     // from a histogram (one per thread over its slice of the reads; sizes of 2^16 and more, if any, are kept as a list)
     // instead of gathering and partially sorting 3.3 M values on one core
@@ -896,9 +921,8 @@ int filter_core(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char *in
         std::nth_element(big.begin(), big.begin() + (long)k, big.end());
         return big[k];
     };
-    const uint32_t lo = order_stat(low), hi = order_stat(high);
-    log("Low threshold:  %u (%s)\nHigh threshold: %u (%s)\n\n", lo, percentile_name(low).c_str(), hi,
-        percentile_name(high).c_str());
+    const uint32_t lo = R.rep.low_threshold = order_stat(low), hi = R.rep.high_threshold = order_stat(high);
+    log_insert_sizes(log, 3, R.rep, orientation, low, high);
     lap("thresholds");
 
     // alignment_pass_qc for every alignment of both files (filter.rs:352-377)
@@ -906,8 +930,6 @@ int filter_core(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char *in
     rc = pp_filter_pairs(ctx, lo, hi, (uint8_t)correct, R.pass[0].data(), R.pass[1].data());
     if (rc) return rc;
     lap("pass flags from the device");
-    R.lo = lo; R.hi = hi; R.correct = correct;
-    for (int o = 0; o < 4; o++) R.counts[o] = counts[o];
     return PP_OK;
 }
 
@@ -944,22 +966,6 @@ int filter_write(pp_ctx *ctx, const Log &log, const FilterRun &R, const char *co
     return PP_OK;
 }
 
-// ---- BAM in, BAM out: the record chain on the device (pp_bam_files.h -> pp_filter_records -> pp_bam_tagged -> pp_bam_out_deflate) ----
-struct BamFilterRun {
-    pp_assembly *a = nullptr;                       // the fused command only: its names make the ref_map the polish needs
-    pp_names *rnames = nullptr, *qnames = nullptr;  // RNAME -> contig index; ONE QNAME table for both files (the filter joins across files)
-    ppb::BamFile F[2];
-    std::vector<uint8_t> own[2];  // the filter's OWN verdicts per aligned record (what the output files carry)
-    uint64_t n_al[2] = {0, 0};
-    pp_filter_file_counts fc[2] = {};
-    pp_filter_report rep = {};
-    ~BamFilterRun() {
-        pp_names_free(qnames);
-        pp_names_free(rnames);
-        pp_assembly_free(a);
-    }
-};
-
 // both inputs' kinds; *bam = both are BAM.  One BAM and one SAM input is refused.
 int filter_input_kinds(pp_ctx *ctx, const char *const ins[2], int kinds[2], bool *bam) {
     for (int f = 0; f < 2; f++)
@@ -973,10 +979,11 @@ int filter_input_kinds(pp_ctx *ctx, const char *const ins[2], int kinds[2], bool
 }
 
 // filter_core for two BAM files: the log is the text route's, word for word
-int filter_core_bam(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char *const ins[2], const int kinds[2], const char *assembly,
-                    const char *orientation, double low, double high, BamFilterRun &R) {
+int filter_core_bam(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char *const ins[2], const char *assembly,
+                    const char *orientation, double low, double high, FilterRun &R) {
     log("Loading alignments\n");
     int rc = PP_OK;
+    pp_filter_file_counts fc[2] = {};
     if (assembly) {
         char err[1400] = "";
         if ((rc = pp_assembly_load(assembly, &R.a, err, sizeof err))) return pp_ctx_set_error_(ctx, rc, err);
@@ -986,44 +993,41 @@ int filter_core_bam(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char
     if ((rc = pp_names_create(ctx, 0, &R.qnames))) return rc;
     pp_raw_batch raw[2];
     for (int f = 0; f < 2; f++) {
-        if ((rc = R.F[f].open(ctx, ins[f], kinds[f], R.rnames, &lap))) return rc;
+        if ((rc = R.F[f].open(ctx, ins[f], R.kinds[f], R.rnames, &lap))) return rc;
         if ((rc = R.F[f].decode(R.F[f].n_rec, R.qnames, nullptr))) return rc;
         pp_bam_raw(R.F[f].rec, &raw[f]);
         const uint8_t *zp = nullptr;
-        pp_bam_pass(R.F[f].rec, &zp, &R.n_al[f]);
-        R.own[f].assign(R.n_al[f] ? R.n_al[f] : 1, 0);
+        pp_bam_pass(R.F[f].rec, &zp, &R.n_aln[f]);
+        R.pass[f].assign(R.n_aln[f] ? R.n_aln[f] : 1, 0);
     }
     lap("alignments loaded");
-    if (R.n_al[0] == 0) {
+    if (R.n_aln[0] == 0) {
         log("%s: 0 alignments from 0 reads\n", ins[0]);
         return ppb::fail(ctx, PP_ERR_QUIT, "no alignments found in \"%s\"", ins[0]);
     }
-    rc = pp_filter_records(ctx, raw, PP_MEM_DEVICE, orientation, low, high, R.own[0].data(), R.own[1].data(), R.fc, &R.rep);
+    rc = pp_filter_records(ctx, raw, PP_MEM_DEVICE, orientation, low, high, R.pass[0].data(), R.pass[1].data(), fc, &R.rep);
     for (int f = 0; f < 2; f++)
-        log("%s: %s alignments from %s reads\n", ins[f], commas(R.fc[f].alignments).c_str(), commas(R.fc[f].reads).c_str());
+        log("%s: %s alignments from %s reads\n", ins[f], commas(fc[f].alignments).c_str(), commas(fc[f].reads).c_str());
     log("\nFinding insert size thresholds\n");
     const uint64_t *oc = R.rep.orientation_counts;
     if (rc && oc[0] + oc[1] + oc[2] + oc[3] == 0) return rc;  // (nothing was counted: the error is all there is to say)
-    static const char *ONAMES[4] = {"fr", "rf", "ff", "rr"};
-    for (int o = 0; o < 4; o++) log("%s: %s pairs\n", ONAMES[o], commas(oc[o]).c_str());
+    log_insert_sizes(log, 1, R.rep, orientation, low, high);
     if (rc) return rc;
-    if (strcmp(orientation, "auto") == 0) log("\nAutomatically determined correct orientation: %s\n\n", ONAMES[R.rep.orientation & 3]);
-    else log("\nUser-specified correct orientation: %s\n\n", orientation);
-    log("Low threshold:  %u (%s)\nHigh threshold: %u (%s)\n\n", R.rep.low_threshold, percentile_name(low).c_str(), R.rep.high_threshold,
-        percentile_name(high).c_str());
+    log_insert_sizes(log, 2, R.rep, orientation, low, high);
+    log_insert_sizes(log, 3, R.rep, orientation, low, high);
     lap("verdicts from the device");
     return PP_OK;
 }
 
 // filter_sams for BAM: every record again, ZP:Z:fail appended where the filter's own verdict is 0, compressed, written
-int filter_write_bam(pp_ctx *ctx, const Log &log, const BamFilterRun &R, const char *const ins[2], const char *const outs[2]) {
+int filter_write_bam(pp_ctx *ctx, const Log &log, const FilterRun &R, const char *const ins[2], const char *const outs[2]) {
     log("Filtering SAM files\n");
     for (int f = 0; f < 2; f++) {
         const ppb::BamFile &F = R.F[f];
         pp_bam_out *t = nullptr;
         pp_bgzf_out *c = nullptr;
         uint64_t bad = 0, p_ = 0, f_ = 0, blocks = 0;
-        int rc = pp_bam_tagged(ctx, F.bytes, F.n_bytes, F.records_at, F.rec_off, F.n_rec, F.mem, R.own[f].data(), R.n_al[f], &t, &bad);
+        int rc = pp_bam_tagged(ctx, F.bytes, F.n_bytes, F.records_at, F.rec_off, F.n_rec, F.mem, R.pass[f].data(), R.n_aln[f], &t, &bad);
         if (rc == PP_OK) rc = pp_bam_out_deflate(ctx, t, &c);
         if (rc == PP_OK) pp_bam_out_counts(t, &p_, &f_, &blocks);
         pp_bam_out_free(t);
@@ -1045,6 +1049,27 @@ int check_filter_options(pp_ctx *ctx, const char *const *names, int n_names, dou
     return PP_OK;
 }
 
+// What `filter` and `filter-polish` share: the options and the banner, the inputs' kinds, the core and -- where there are outputs --
+// the writer, for SAM text or BAM.  R then holds the verdicts and the report.
+int run_filter(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const std::function<void()> &banner, const char *assembly,
+               const char *const ins[2], const char *const outs[2], const char *orientation, double low, double high, FilterRun &R) {
+    const char *f4[4] = {ins[0], ins[1], outs[0], outs[1]};
+    if (int rc = check_filter_options(ctx, f4, outs[0] ? 4 : 2, low, high)) return rc;
+    banner();
+    if (int rc = filter_input_kinds(ctx, ins, R.kinds, &R.bam)) return rc;
+    if (int rc = R.bam ? filter_core_bam(ctx, log, lap, ins, assembly, orientation, low, high, R)
+                       : filter_core(ctx, log, lap, ins, orientation, low, high, R))
+        return rc;
+    if (outs[0]) {
+        if (int rc = R.bam ? filter_write_bam(ctx, log, R, ins, outs) : filter_write(ctx, log, R, ins, outs, &R.rep.after_count)) return rc;
+        lap(R.bam ? "filtered BAMs written" : "filtered SAMs written");
+    } else if (!R.bam) {  // (BAM: pp_filter_records has counted; SAM text without outputs: from the verdicts)
+        for (int f = 0; f < 2; f++)
+            for (uint64_t i = 0; i < R.n_aln[f]; i++) R.rep.after_count += R.pass[f][i];
+    }
+    return PP_OK;
+}
+
 }  // namespace
 
 extern "C" int pp_filter_files(pp_ctx *ctx, const char *in1, const char *in2, const char *out1,
@@ -1053,39 +1078,16 @@ extern "C" int pp_filter_files(pp_ctx *ctx, const char *in1, const char *in2, co
     if (!ctx || !in1 || !in2 || !out1 || !out2 || !orientation) return PP_ERR_ARG;
     Log log{quiet != 0};
     const pph::Lap lap{"", 28, false};
-    const char *f4[4] = {in1, in2, out1, out2};
-    if (int rc = check_filter_options(ctx, f4, 4, low, high)) return rc;
-    log("\nStarting Polypolish filter\n%s\n\nInput alignments:\n  %s\n  %s\n\nOutput alignments:\n  %s\n  %s\n\n"
-        "Settings:\n  --orientation %s\n  --low %g\n  --high %g\n\n", pp_version(), in1, in2, out1, out2, orientation, low, high);
     const char *ins[2] = {in1, in2}, *outs[2] = {out1, out2};
-    int kinds[2] = {PP_ALN_SAM, PP_ALN_SAM};
-    bool bam = false;
-    if (int rc = filter_input_kinds(ctx, ins, kinds, &bam)) return rc;
-    if (bam) {  // BAM in, compressed BAM out
-        BamFilterRun B;
-        if (int rc = filter_core_bam(ctx, log, lap, ins, kinds, nullptr, orientation, low, high, B)) return rc;
-        if (int rc = filter_write_bam(ctx, log, B, ins, outs)) return rc;
-        lap("filtered BAMs written");
-        if (report) *report = B.rep;
-        log("Finished!\nAlignments before filtering: %s\nAlignments after filtering:  %s\n\nTime to run: %s\n\n",
-            commas(B.rep.before_count).c_str(), commas(B.rep.after_count).c_str(), format_duration(lap.seconds()).c_str());
-        return PP_OK;
-    }
-    FilterRun R;
-    if (int rc = filter_core(ctx, log, lap, in1, in2, orientation, low, high, R)) return rc;
-    uint64_t after = 0;
-    if (int rc = filter_write(ctx, log, R, ins, outs, &after)) return rc;
-    lap("filtered SAMs written");
-    if (report) {
-        report->before_count = R.before;
-        report->after_count = after;
-        report->low_threshold = R.lo;
-        report->high_threshold = R.hi;
-        report->orientation = R.correct;
-        for (int o = 0; o < 4; o++) report->orientation_counts[o] = R.counts[o];
-    }
+    FilterRun R;  // BAM in: compressed BAM out
+    const int rc = run_filter(ctx, log, lap, [&] {
+        log("\nStarting Polypolish filter\n%s\n\nInput alignments:\n  %s\n  %s\n\nOutput alignments:\n  %s\n  %s\n\n"
+            "Settings:\n  --orientation %s\n  --low %g\n  --high %g\n\n", pp_version(), in1, in2, out1, out2, orientation, low, high);
+    }, nullptr, ins, outs, orientation, low, high, R);
+    if (rc) return rc;
+    if (report) *report = R.rep;
     log("Finished!\nAlignments before filtering: %s\nAlignments after filtering:  %s\n\nTime to run: %s\n\n",
-        commas(R.before).c_str(), commas(after).c_str(), format_duration(lap.seconds()).c_str());
+        commas(R.rep.before_count).c_str(), commas(R.rep.after_count).c_str(), format_duration(lap.seconds()).c_str());
     return PP_OK;
 }
 
@@ -1098,52 +1100,21 @@ extern "C" int pp_filter_polish_files(pp_ctx *ctx, const char *assembly, const c
         return pp_ctx_set_error_(ctx, PP_ERR_ARG, "pp_filter_polish_files: give both --out1 and --out2 or neither");
     Log log{opt->quiet != 0};
     const pph::Lap lap{"", 28, false};
-    const char *f4[4] = {in1, in2, out1, out2};
-    if (int rc = check_filter_options(ctx, f4, out1 ? 4 : 2, low, high)) return rc;
-    log("\nStarting Polypolish filter + polish (fused)\n%s\n\nInput alignments:\n  %s\n  %s\n\n"
-        "Filter settings:\n  --orientation %s\n  --low %g\n  --high %g\n\n", pp_version(), in1, in2, orientation, low, high);
     const char *ins[2] = {in1, in2}, *outs[2] = {out1, out2};
-    int kinds[2] = {PP_ALN_SAM, PP_ALN_SAM};
-    bool bam = false;
-    if (int rc = filter_input_kinds(ctx, ins, kinds, &bam)) return rc;
-    if (bam) {  // the records are decoded once: the filter's verdicts go into the gate, ANDed with the ZP:Z:fail bytes there
-        BamFilterRun B;
-        if (int rc = filter_core_bam(ctx, log, lap, ins, kinds, assembly, orientation, low, high, B)) return rc;
-        if (out1) {
-            if (int rc = filter_write_bam(ctx, log, B, ins, outs)) return rc;
-            lap("filtered BAMs written");
-        }
-        if (report) *report = B.rep;
-        log("Alignments before filtering: %s\nAlignments after filtering:  %s\n", commas(B.rep.before_count).c_str(), commas(B.rep.after_count).c_str());
-        const uint8_t *pass[2] = {B.own[0].data(), B.own[1].data()};
-        ppb::BamFile *fronts[2] = {&B.F[0], &B.F[1]};
-        return ppb::polish_bam_fronts(ctx, assembly, B.a, fronts, B.rnames, B.qnames, ins, 2, opt, fasta, pass, B.n_al);
-    }
     FilterRun R;
-    if (int rc = filter_core(ctx, log, lap, in1, in2, orientation, low, high, R)) return rc;
-    uint64_t after = 0;
-    if (out1) {
-        if (int rc = filter_write(ctx, log, R, ins, outs, &after)) return rc;
-        lap("filtered SAMs written");
-    } else {
-        for (int f = 0; f < 2; f++)
-            for (uint64_t i = 0; i < R.n_aln[f]; i++) after += R.pass[f][i];
-    }
-    if (report) {
-        report->before_count = R.before;
-        report->after_count = after;
-        report->low_threshold = R.lo;
-        report->high_threshold = R.hi;
-        report->orientation = R.correct;
-        for (int o = 0; o < 4; o++) report->orientation_counts[o] = R.counts[o];
-    }
-    log("Alignments before filtering: %s\nAlignments after filtering:  %s\n", commas(R.before).c_str(), commas(after).c_str());
-    // the verdicts go straight into the polish ingest; the filter's parse-time memory is released first
+    const int rc = run_filter(ctx, log, lap, [&] {
+        log("\nStarting Polypolish filter + polish (fused)\n%s\n\nInput alignments:\n  %s\n  %s\n\n"
+            "Filter settings:\n  --orientation %s\n  --low %g\n  --high %g\n\n", pp_version(), in1, in2, orientation, low, high);
+    }, assembly, ins, outs, orientation, low, high, R);
+    if (rc) return rc;
+    if (report) *report = R.rep;
+    log("Alignments before filtering: %s\nAlignments after filtering:  %s\n", commas(R.rep.before_count).c_str(), commas(R.rep.after_count).c_str());
+    // the verdicts go straight into the polish
     const uint8_t *pass[2] = {R.pass[0].data(), R.pass[1].data()};
-    const uint64_t n_pass[2] = {R.n_aln[0], R.n_aln[1]};
-    pp_filter_loaded_free(R.L);
-    R.L = nullptr;
-    pp_filter_dev_free(R.DL);
-    R.DL = nullptr;
-    return pp_polish_files_filtered_(ctx, assembly, ins, 2, opt, fasta, pass, n_pass);
+    if (R.bam) {  // the records were decoded once: the gate takes the verdicts, ANDed with the ZP:Z:fail bytes there
+        ppb::BamFile *fronts[2] = {&R.F[0], &R.F[1]};
+        return ppb::polish_bam_fronts(ctx, assembly, R.a, fronts, R.rnames, R.qnames, ins, 2, opt, fasta, pass, R.n_aln);
+    }
+    R.release_parse_memory();  // the filter's parse-time memory is released before the polish starts
+    return pp_polish_files_filtered_(ctx, assembly, ins, 2, opt, fasta, pass, R.n_aln);
 }

@@ -1,4 +1,4 @@
-// pp_host.h -- host-side utilities shared by the SAM ingest (pp_ingest.cpp) and the command drivers (pp_driver.cpp,
+// pp_host.h -- host-side utilities shared by the SAM ingest (pp_ingest.cpp) and the command drivers (pp_driver*.cpp,
 // pp_filter_host.cpp): huge-page growable arrays, a fork-join parallel_for, a read-only file mapping, the run log's
 // helpers, and the declarations of the library's internal entry points.
 #pragma once
