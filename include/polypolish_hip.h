@@ -19,8 +19,8 @@
  * device tokenizers over the uploaded text (pp_dev_ingest_*, pp_filter_load_device), and the whole
  * commands (pp_polish_files, pp_filter_files, pp_filter_polish_files).  A caller who holds alignment
  * RECORDS, not SAM text, has the record chain, every link on the device: pp_bam_records (uncompressed
- * BAM bytes -> raw records, the chain's front end) -> pp_names -> pp_filter_records -> pp_batch_gate ->
- * pp_batch_prepare -> pp_polish_*.
+ * BAM bytes -> raw records, the chain's front end) -> pp_names -> pp_filter_records -> (pp_batch_regroup, for
+ * a file whose reads do not stand together ->) pp_batch_gate -> pp_batch_prepare -> pp_polish_*.
  *
  * Conventions: plain pointers and sizes, no C++/torch types.  Every function returns PP_OK or a
  * PP_ERR_* code and never exits the process; pp_last_error() holds the message the reference
@@ -278,6 +278,39 @@ void pp_gated_counts(const pp_gated *g, pp_sam_counts *out); /* as add_to_pileup
 /* HIP-event time of the gate's kernels (not the upload of a host batch); PP_ERR_ARG unless the context had profiling on */
 int pp_gated_kernel_ms(const pp_gated *g, float *ms);
 void pp_gated_free(pp_gated *g);
+
+/* The step in front of the gate for a file whose reads do NOT stand together: a coordinate-sorted file (samtools sort) scatters a
+ * read's records, and the gate, like the reference, takes every run of adjacent aligned records with one read_id for a read of its
+ * own.  pp_batch_regroup brings the records of ONE file (one call per file, like the gate) together again, on the device:
+ *   order      output record j is raw record perm[j].  perm is the stable order of the records by the index of the first record
+ *              that carries the same read_id: groups stand in the order of their first record, inside a group the records keep
+ *              file order.  All records count, aligned or not: `flag` plays no part in the order.  Equality is equality of the
+ *              64-bit ids, no value is reserved.  A name-grouped file regroups to itself (n_moved, the number of j with
+ *              perm[j] != j, is 0), and regrouping is idempotent.  The order depends on the records alone.
+ *   the view   pp_regrouped_raw: the nine per-record arrays (flag, read_id, contig, ref_start, nm, seq_off, seq_len, cig_off,
+ *              n_cig) gathered through perm; seq and cigar are not moved (seq_off and cig_off are indirections already, and the
+ *              gate copies what it keeps).  PP_MEM_DEVICE: seq and cigar stay BORROWED from `raw`, which must outlive the
+ *              object; with n_moved == 0 the view is raw's own arrays and nothing is copied.  PP_MEM_HOST: everything is
+ *              uploaded and owned by the object.  What pp_batch_gate(..., PP_MEM_DEVICE, ...) makes of the view is, byte for
+ *              byte, what it makes of the same records laid out in that order by the caller; its orig[] and *bad_record are
+ *              indices into the VIEW: perm turns them back into raw's.
+ *   verdicts   pp_regrouped_pass carries a pass array (HOST, one byte per ALIGNED record of `raw`: the numbering of
+ *              pp_filter_records and pp_bam_pass) into the numbering of the regrouped batch: out[a'] = pass[a], where the
+ *              regrouped record with aligned rank a' is the raw record with aligned rank a (out may be pass only when
+ *              n_moved == 0).  n_pass other than the number of aligned records: PP_ERR_ARG.
+ *   counts     n_groups = the distinct read_ids.
+ * PP_ERR_ARG: null arguments, PP_MEM_PEER, a null per-record array in a non-empty batch (PP_MEM_HOST: seq / cigar, too).
+ * PP_ERR_LIMIT: n_rec >= 2^32-1.  Nothing in the records can be refused: offsets and lengths are copied, never followed, so the
+ * call is memory-safe for any contents.  n_rec == 0 gives an empty object.  The context's stream has been synchronised when the
+ * call returns.  pp_regrouped_kernel_ms: as pp_gated_kernel_ms.  The object belongs to its context and is freed before it. */
+typedef struct pp_regrouped pp_regrouped;
+int pp_batch_regroup(pp_ctx *ctx, const pp_raw_batch *raw, int mem, pp_regrouped **out);
+void pp_regrouped_raw(const pp_regrouped *g, pp_raw_batch *out); /* borrowed view, DEVICE memory */
+const uint32_t *pp_regrouped_perm(const pp_regrouped *g); /* DEVICE, n_rec entries */
+void pp_regrouped_counts(const pp_regrouped *g, uint64_t *n_groups, uint64_t *n_moved);
+int pp_regrouped_pass(const pp_regrouped *g, const uint8_t *pass, uint64_t n_pass, uint8_t *out); /* HOST arrays */
+int pp_regrouped_kernel_ms(const pp_regrouped *g, float *ms);
+void pp_regrouped_free(pp_regrouped *g);
 
 /* The step in front of the record chain for a caller who holds NAMES: pp_raw_batch.read_id is the QNAME and .contig the RNAME as
  * a number, equal names <=> equal ids, exactly (a hash value is no id: two names that collide would be one read).  A pp_names is
@@ -856,10 +889,20 @@ typedef struct {
 } pp_bytes;
 void pp_bytes_free(pp_bytes *b);
 
+/* Coordinate-sorted BAM for the file drivers below (the commands' --regroup): with `on` != 0, pp_polish_files and the polish half of
+ * pp_filter_polish_files put pp_batch_regroup between the decode and the gate of every BAM file, so that a read's records count as
+ * one read wherever they lie in the file (the filter joins them already, and writes in file order).  The state lives on the
+ * context, like pp_ctx_set_profiling's; off when the context is made.  Messages still name the file's own 1-based record.  With it
+ * on, SAM text is refused (PP_ERR_QUIT, "--regroup takes BAM input"), and a QUIT or PANIC of the decode (missing or negative NM) is
+ * reported at once, without the replay of the records in front.  Without it every command behaves as
+ * before: there is no switch on an @HD SO:coordinate header. */
+int pp_ctx_set_regroup(pp_ctx *ctx, int on);
+
 /* polish::polish (src/polish.rs:26-38): FASTA text exactly as the reference prints to stdout.
  * `sams` are SAM text files or -- all of them -- BAM files (pp_aln_file_kind; a mix is PP_ERR_QUIT).  BAM goes through the record
  * chain on the device, file by file: pp_bgzf_inflate -> pp_bam_header -> pp_bgzf_bam_walk -> pp_bam_records -> pp_names ->
- * pp_batch_gate(pass = pp_bam_pass) -> pp_polish_add; pp_batch_prepare in between with PP_BAM_PREPARE=1 in the environment.
+ * (pp_batch_regroup, with pp_ctx_set_regroup ->) pp_batch_gate(pass = pp_bam_pass) -> pp_polish_add; pp_batch_prepare in between
+ * with PP_BAM_PREPARE=1 in the environment.
  * Messages about a BAM file name its path and the block or the record (1-based, counting all records); "no alignments in <path>"
  * for a file without aligned records.  Order of errors: INTEGRATION.md section 6. */
 int pp_polish_files(pp_ctx *ctx, const char *assembly, const char *const *sams, int n_sams,

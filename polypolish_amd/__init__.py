@@ -12,6 +12,7 @@ call needs a HIP device and raises ``PolypolishError`` otherwise.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -522,6 +523,66 @@ def gate_records(ctx, raw: dict, max_errors=10, careful=False, passed=None, mem=
     (RAW_FIELDS); MEM_DEVICE: raw = their device addresses plus "n_rec", "seq_bytes", "n_cig_total".  passed: None or the
     filter's verdict byte of every aligned record (host).  A failing call raises PolypolishError with .bad_record."""
     return GatedBatch(ctx, raw, max_errors, careful, passed, mem)
+
+
+class Regrouped(_Owned):
+    """pp_batch_regroup: the raw records of ONE file with every read's records brought together (groups in the order of their first
+    record, file order inside a group), in DEVICE memory.  With mem = MEM_DEVICE seq and cigar stay borrowed from `raw`, which must
+    outlive this object, and when nothing moves the view is raw's own arrays.
+      .n_rec, .seq_bytes, .n_cig_total
+      .raw()               the device-address dict gate_records(..., mem=MEM_DEVICE) takes (valid until close())
+      .host()              numpy copies of the view's arrays
+      .perm()              np.uint32: output record j is raw record perm[j]
+      .counts()            (distinct read_ids, records that changed place)
+      .carry_pass(passed)  one byte per ALIGNED record of `raw` -> the same verdicts in the numbering of the regrouped records
+      .kernel_ms()         HIP-event time of the kernels (the context had set_profiling on); .stage_ms(): intern | sort | gather"""
+    _free, _kernel_ms = "pp_regrouped_free", "pp_regrouped_kernel_ms"
+
+    def __init__(self, ctx, raw, mem=MEM_HOST):
+        L = lib()
+        b, _keep = _raw_batch(raw, mem == MEM_HOST, RAW_FIELDS)
+        super().__init__(ctx)
+        ctx._chk(L.pp_batch_regroup(ctx._h, C.byref(b), mem, C.byref(self._p)))
+        out = self._view = RawBatch()
+        L.pp_regrouped_raw(self._p, C.byref(out))
+        self.n_rec, self.seq_bytes, self.n_cig_total = int(out.n_rec), int(out.seq_bytes), int(out.n_cig_total)
+        self._ptrs = _ptrs_of(out, RAW_FIELDS)
+
+    def raw(self):
+        return dict(self._ptrs, n_rec=self.n_rec, seq_bytes=self.seq_bytes, n_cig_total=self.n_cig_total)
+
+    def host(self):
+        return _read_batch(self._view, RAW_FIELDS, self._ctx)
+
+    def perm(self):
+        return self._ctx.download(lib().pp_regrouped_perm(self._p), self.n_rec, np.uint32)
+
+    def counts(self):
+        g, m = C.c_uint64(0), C.c_uint64(0)
+        lib().pp_regrouped_counts(self._p, C.byref(g), C.byref(m))
+        return int(g.value), int(m.value)
+
+    def carry_pass(self, passed):
+        v = np.ascontiguousarray(passed, dtype=np.uint8)
+        out = np.zeros(max(len(v), 1), dtype=np.uint8)
+        self._ctx._chk(lib().pp_regrouped_pass(self._p, v.ctypes.data if len(v) else None, len(v), out.ctypes.data))
+        return out[:len(v)]
+
+    def stage_ms(self):
+        return self._stage_ms("pp_regrouped_stage_ms_", ("intern", "sort", "gather"), " when the batch was regrouped")
+
+
+def regroup_records(ctx, raw: dict, mem=MEM_HOST):
+    """pp_batch_regroup on the raw records of ONE file (in front of gate_records, for a file whose reads do not stand together:
+    coordinate-sorted BAM).  raw and mem as gate_records takes them.  Returns a Regrouped."""
+    return Regrouped(ctx, raw, mem)
+
+
+def regroup_geometry():
+    """records per tile of the regroup's radix sort: the seam its tests are built on"""
+    t = C.c_uint32()
+    lib().pp_regroup_geometry_(C.byref(t))
+    return int(t.value)
 
 
 def pack_names(names):
@@ -1057,6 +1118,11 @@ class Context:
         """False/0 off, True/1 every kernel group, 2 only the dominant kernel (one event pair per job)."""
         lib().pp_ctx_set_profiling(self._h, int(on))
 
+    def set_regroup(self, on=True):
+        """pp_ctx_set_regroup: polish_files and the polish half of filter_polish_files regroup every BAM file's records in front of
+        the gate (coordinate-sorted BAM; the commands' --regroup)."""
+        self._chk(lib().pp_ctx_set_regroup(self._h, int(bool(on))))
+
     # ---- seam B -------------------------------------------------------------------------------
     def polish_begin(self, contig_off, bases_ptr, bases_mem, min_depth=5, fraction_valid=0.5, fraction_invalid=0.2):
         off = np.ascontiguousarray(contig_off, dtype=np.uint64)
@@ -1234,13 +1300,24 @@ class Context:
         return res
 
     def polish_raw(self, contig_off, bases, raws, max_errors=10, careful=False, passed=None, prepare=False, min_depth=5,
-                   fraction_valid=0.5, fraction_invalid=0.2, positions=False):
-        """The record chain gate -> (prepare) -> polish: raws = the raw records of every SAM file (host numpy, RAW_FIELDS), in
+                   fraction_valid=0.5, fraction_invalid=0.2, positions=False, regroup=False):
+        """The record chain (regroup ->) gate -> (prepare) -> polish: raws = the raw records of every SAM file (host numpy, RAW_FIELDS), in
         argv order; passed = None or one entry per file (None or the filter's verdicts).  Every file is gated on the device
-        (gate_records), the gated batches -- each through pp_batch_prepare when `prepare` -- are added one after the other.
+        (gate_records; with `regroup` behind regroup_records, the verdicts carried along: for files whose reads do not stand
+        together), the gated batches -- each through pp_batch_prepare when `prepare` -- are added one after the other.
         Returns what polish_records returns, plus "counts": (alignments, used, reads) per file."""
         bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        gated = [gate_records(self, raw, max_errors, careful, None if passed is None else passed[f]) for f, raw in enumerate(raws)]
+        gated = []
+        for f, raw in enumerate(raws):
+            v = None if passed is None else passed[f]
+            if regroup:
+                g = regroup_records(self, raw)
+                try:
+                    gated.append(gate_records(self, g.raw(), max_errors, careful, None if v is None else g.carry_pass(v), MEM_DEVICE))
+                finally:
+                    g.close()
+            else:
+                gated.append(gate_records(self, raw, max_errors, careful, v))
         batches = [prepare_batch(self, contig_off, g.n_aln, g.ptrs(), g.seq_bytes, g.n_cig_total, MEM_DEVICE) for g in gated] if prepare else gated
         lib().pp_polish_set_debug(self._h, int(positions) if positions else 0)
         try:
@@ -1266,30 +1343,46 @@ class Context:
         return _report_dict(rep)
 
     # ---- whole commands -----------------------------------------------------------------------
+    @contextlib.contextmanager
+    def _regrouping(self, regroup):
+        """regroup=True switches the context's regrouping on for one command; False leaves what set_regroup chose"""
+        if not regroup:
+            yield
+            return
+        was = bool(lib().pp_ctx_regroup_(self._h))
+        self.set_regroup(True)
+        try:
+            yield
+        finally:
+            self.set_regroup(was)
+
     def polish_files(self, assembly, sams, fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5,
-                     careful=False, debug=None, quiet=True):
+                     careful=False, debug=None, quiet=True, regroup=False):
         """polish::polish (pp_polish_files): the FASTA bytes.  `sams` are SAM text files, or all of them BAM files (BGZF or
-        uncompressed; told by content, aln_file_kind): those go through the record chain on the device, inside the driver."""
+        uncompressed; told by content, aln_file_kind): those go through the record chain on the device, inside the driver.
+        regroup: for this call, as set_regroup (coordinate-sorted BAM)."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         arr = (C.c_char_p * max(len(sams), 1))(*[str(s).encode() for s in sams])
         out = Bytes()
-        self._chk(lib().pp_polish_files(self._h, str(assembly).encode(), arr, len(sams), C.byref(opt), C.byref(out)))
+        with self._regrouping(regroup):
+            self._chk(lib().pp_polish_files(self._h, str(assembly).encode(), arr, len(sams), C.byref(opt), C.byref(out)))
         data = C.string_at(out.data, out.len) if out.len else b""
         lib().pp_bytes_free(C.byref(out))
         return data
 
     def filter_polish_files(self, assembly, in1, in2, out1=None, out2=None, orientation="auto", low=0.1, high=99.9,
                             fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5, careful=False,
-                            debug=None, quiet=True):
+                            debug=None, quiet=True, regroup=False):
         """filter + polish in one process (pp_filter_polish_files): returns (FASTA bytes, filter report).  Two BAM inputs are decoded
-        once for both halves; out1 / out2 are then BAM files as well."""
+        once for both halves; out1 / out2 are then BAM files as well.  regroup: for this call, as set_regroup (the polish half)."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         rep, out = FilterReport(), Bytes()
         enc = lambda x: str(x).encode() if x is not None else None
-        self._chk(lib().pp_filter_polish_files(self._h, enc(assembly), enc(in1), enc(in2), enc(out1), enc(out2),
-                                               orientation.encode(), low, high, C.byref(opt), C.byref(rep), C.byref(out)))
+        with self._regrouping(regroup):
+            self._chk(lib().pp_filter_polish_files(self._h, enc(assembly), enc(in1), enc(in2), enc(out1), enc(out2),
+                                                   orientation.encode(), low, high, C.byref(opt), C.byref(rep), C.byref(out)))
         data = C.string_at(out.data, out.len) if out.len else b""
         lib().pp_bytes_free(C.byref(out))
         return data, _report_dict(rep)
@@ -1315,10 +1408,11 @@ def _ctx():
 
 
 def polish(assembly, sam, debug=None, fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5,
-           careful=False) -> bytes:
-    """polish::polish (src/polish.rs:26-38): returns the FASTA bytes the reference prints to stdout."""
+           careful=False, regroup=False) -> bytes:
+    """polish::polish (src/polish.rs:26-38): returns the FASTA bytes the reference prints to stdout.  regroup: coordinate-sorted
+    BAM files (every read's records are brought together in front of the gate: the command's --regroup)."""
     return _ctx().polish_files(assembly, list(sam), fraction_invalid, fraction_valid, max_errors, min_depth, careful,
-                               debug)
+                               debug, regroup=regroup)
 
 
 def filter(in1, in2, out1, out2, orientation="auto", low=0.1, high=99.9):  # noqa: A001 (reference name)

@@ -117,6 +117,13 @@ SIGNATURES = {
     "pp_gated_counts": (None, [_vp, _P(SamCounts)]),
     "pp_gated_kernel_ms": (_i, [_vp, _pf32]),
     "pp_gated_free": (None, [_vp]),
+    "pp_batch_regroup": (_i, [_vp, _P(RawBatch), _i, _pvp]),
+    "pp_regrouped_raw": (None, [_vp, _P(RawBatch)]),
+    "pp_regrouped_perm": (_vp, [_vp]),
+    "pp_regrouped_counts": (None, [_vp, _pu64, _pu64]),
+    "pp_regrouped_pass": (_i, [_vp, _vp, _u64, _vp]),
+    "pp_regrouped_kernel_ms": (_i, [_vp, _pf32]),
+    "pp_regrouped_free": (None, [_vp]),
     "pp_names_create": (_i, [_vp, _u64, _pvp]),
     "pp_names_ids": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _i, _vp, _vp, _pu64]),
     "pp_names_count": (_u64, [_vp]),
@@ -218,6 +225,7 @@ SIGNATURES = {
     "pp_ingest_read_name": (_str, [_vp, _u64]),
     "pp_ingest_free": (None, [_vp]),
     "pp_bytes_free": (None, [_P(Bytes)]),
+    "pp_ctx_set_regroup": (_i, [_vp, _i]),
     "pp_polish_files": (_i, [_vp, _str, _P(_str), _i, _P(PolishOptions), _P(Bytes)]),
     "pp_polish_files_multi": (_i, [_pvp, _i, _str, _P(_str), _i, _P(PolishOptions), _P(Bytes)]),
     "pp_dev_ingest_create": (_i, [_vp, _vp, _u32, _i, _pvp]),
@@ -237,7 +245,10 @@ SIGNATURES = {
 # the internal hooks (not in the header) the binding, tools/ and tests/ call; one missing from a PP_LIB_PATH variant is skipped
 HOOKS = {
     "pp_ctx_trust_mirrors_": (_i, [_vp, _i]),
+    "pp_ctx_regroup_": (_i, [_vp]),
     "pp_gated_stage_ms_": (_i, [_vp, _pf32]),       # float[3]
+    "pp_regrouped_stage_ms_": (_i, [_vp, _pf32]),   # float[3]
+    "pp_regroup_geometry_": (None, [_pu32]),
     "pp_names_stage_ms_": (_i, [_vp, _pf32]),       # float[5]
     "pp_bgzf_stage_ms_": (_i, [_vp, _pf32]),        # float[3]
     "pp_bam_stage_ms_": (_i, [_vp, _pf32]),         # float[3]

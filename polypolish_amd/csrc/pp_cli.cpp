@@ -50,6 +50,7 @@ static const char *HELP_POLISH =
     "  -m, --max_errors <MAX_ERRORS>              Ignore alignments with more than this many mismatches and indels [default: 10]\n"
     "  -d, --min_depth <MIN_DEPTH>                A base must occur at least this many times in the pileup to be considered valid [default: 5]\n"
     "      --careful                              Ignore any reads with multiple alignments\n"
+    "      --regroup                              BAM files whose reads do not stand together (coordinate-sorted): bring every read's alignments together first\n"
     "  -h, --help                                 Print help\n  -V, --version                              Print version\n";
 
 static const char *HELP_FUSED =
@@ -57,7 +58,8 @@ static const char *HELP_FUSED =
     "Usage: polypolish filter-polish [OPTIONS] --in1 <IN1> --in2 <IN2> <ASSEMBLY>\n\n"
     "Options: those of `filter` (--out1/--out2 optional: write the tagged SAMs as well) and of `polish`.\n"
     "The FASTA on stdout is byte-identical to `filter` followed by `polish` on its outputs.\n"
-    "--in1/--in2 are both SAM text or both BAM; with BAM the optional outputs are BAM as well.\n";
+    "--in1/--in2 are both SAM text or both BAM; with BAM the optional outputs are BAM as well.\n"
+    "--regroup: coordinate-sorted BAM inputs (the polish brings every read's alignments together; the outputs keep file order).\n";
 
 static int usage_error(const char *msg) {
     fprintf(stderr, "error: %s\n\nFor more information, try '--help'.\n", msg);
@@ -233,12 +235,14 @@ int main(int argc, char **argv) {
 
     if (cmd == "polish") {
         pp_polish_options opt{0.2, 0.5, 10, 5, 0, nullptr, 0};
+        bool regroup = false;  // (not in the reference) BAM files whose reads do not stand together: pp_ctx_set_regroup
         const std::vector<OptSpec> specs = {{"--debug", 0, true, "<DEBUG>"},
                                             {"--fraction_invalid", 'i', true, "<FRACTION_INVALID>"},
                                             {"--fraction_valid", 'v', true, "<FRACTION_VALID>"},
                                             {"--max_errors", 'm', true, "<MAX_ERRORS>"},
                                             {"--min_depth", 'd', true, "<MIN_DEPTH>"},
-                                            {"--careful", 0, false, ""}};
+                                            {"--careful", 0, false, ""},
+                                            {"--regroup", 0, false, ""}};
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help) { fputs(HELP_POLISH, stdout); return 0; }
         if (P.version) { printf("polypolish-polish v0.6.1\n"); return 0; }
@@ -246,6 +250,7 @@ int main(int argc, char **argv) {
         if (perr.empty()) {
             opt.debug_path = P.value[0];
             opt.careful = P.value[5] != nullptr;
+            regroup = P.value[6] != nullptr;
             (void)(take_f64(P, specs, 1, opt.fraction_invalid, perr) && take_f64(P, specs, 2, opt.fraction_valid, perr) &&
                    take_u32(P, specs, 3, opt.max_errors, perr) && take_u32(P, specs, 4, opt.min_depth, perr));
         }
@@ -272,7 +277,7 @@ int main(int argc, char **argv) {
         if (devs.size() > 1) {
             std::vector<pp_ctx *> cs(devs.size(), nullptr);
             for (size_t d = 0; d < devs.size(); d++)
-                if (pp_ctx_create_async(devs[d], &cs[d])) return no_device(devs[d]);
+                if (pp_ctx_create_async(devs[d], &cs[d]) || pp_ctx_set_regroup(cs[d], regroup)) return no_device(devs[d]);
             pp_bytes fasta{nullptr, 0};
             int rc = pp_polish_files_multi(cs.data(), (int)cs.size(), assembly, sams.data(), (int)sams.size(), &opt, &fasta);
             for (size_t d = 0; d < devs.size(); d++)
@@ -289,6 +294,7 @@ int main(int argc, char **argv) {
         pp_ctx *ctx = nullptr;
         int rc = pp_ctx_create_async(device, &ctx);
         if (rc) return no_device(device);
+        pp_ctx_set_regroup(ctx, regroup);
         pp_bytes fasta{nullptr, 0};
         rc = pp_polish_files(ctx, assembly, sams.data(), (int)sams.size(), &opt, &fasta);
         if (pp_ctx_wait(ctx) != PP_OK) return no_device(device);
@@ -305,6 +311,7 @@ int main(int argc, char **argv) {
         pp_polish_options opt{0.2, 0.5, 10, 5, 0, nullptr, 0};
         const char *orientation = "auto";
         double low = 0.1, high = 99.9;
+        bool regroup = false;
         const std::vector<OptSpec> specs = {{"--in1", 0, true, "<IN1>"}, {"--in2", 0, true, "<IN2>"},
                                             {"--out1", 0, true, "<OUT1>"}, {"--out2", 0, true, "<OUT2>"},
                                             {"--orientation", 0, true, "<ORIENTATION>"}, {"--low", 0, true, "<LOW>"},
@@ -313,7 +320,8 @@ int main(int argc, char **argv) {
                                             {"--fraction_valid", 'v', true, "<FRACTION_VALID>"},
                                             {"--max_errors", 'm', true, "<MAX_ERRORS>"},
                                             {"--min_depth", 'd', true, "<MIN_DEPTH>"},
-                                            {"--careful", 0, false, ""}};
+                                            {"--careful", 0, false, ""},
+                                            {"--regroup", 0, false, ""}};
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help || P.version) { fputs(HELP_FUSED, stdout); return 0; }
         std::string perr = P.error;
@@ -321,6 +329,7 @@ int main(int argc, char **argv) {
             if (P.value[4]) orientation = P.value[4];
             opt.debug_path = P.value[7];
             opt.careful = P.value[12] != nullptr;
+            regroup = P.value[13] != nullptr;
             (void)(take_f64(P, specs, 5, low, perr) && take_f64(P, specs, 6, high, perr) &&
                    take_f64(P, specs, 8, opt.fraction_invalid, perr) && take_f64(P, specs, 9, opt.fraction_valid, perr) &&
                    take_u32(P, specs, 10, opt.max_errors, perr) && take_u32(P, specs, 11, opt.min_depth, perr));
@@ -334,6 +343,7 @@ int main(int argc, char **argv) {
         pp_ctx *ctx = nullptr;
         int rc = pp_ctx_create_async(device, &ctx);
         if (rc) return no_device(device);
+        pp_ctx_set_regroup(ctx, regroup);
         pp_bytes fasta{nullptr, 0};
         rc = pp_filter_polish_files(ctx, assembly, in1, in2, out1, out2, orientation, low, high, &opt, nullptr, &fasta);
         if (pp_ctx_wait(ctx) != PP_OK) return no_device(device);

@@ -1,7 +1,7 @@
 // pp_dev.h -- what the device translation units share that is not text: the typedefs, the range and room arithmetic of a batch,
 // the SEQ byte codes, the workgroup scans over the DPP wave scan of pp_wave.h, the multi-block exclusive scan, and the host
 // plumbing of one call (read-back, scratch, upload, stage timing).  Included by pp_devtext.h (the SAM tokenizers' text utilities)
-// and directly by the record chain: pp_bgzf.hip, pp_bam.hip, pp_names.hip, pp_filter_rec.hip (through pp_filter_group.h), pp_gate.hip and
+// and directly by the record chain: pp_bgzf.hip, pp_bam.hip, pp_names.hip, pp_filter_rec.hip and pp_regroup.hip (through pp_filter_group.h), pp_gate.hip and
 // pp_prepare.hip.  Everything lives in an anonymous namespace: each translation unit gets its own copies, and of the kernels that
 // are templates only those it launches.
 #pragma once

@@ -142,6 +142,9 @@ static int check_options_and_inputs(PolishJob &J) {
     if (first_sam >= 0 && first_bam >= 0)
         return ppb::fail(J.ctx, PP_ERR_QUIT, "the alignment files of one command must all be SAM text or all be BAM: \"%s\" is SAM text, \"%s\" is BAM",
                          J.sams[first_sam], J.sams[first_bam]);
+    if (first_sam >= 0 && pp_ctx_regroup_(J.ctx))
+        return ppb::fail(J.ctx, PP_ERR_QUIT, "--regroup takes BAM input: \"%s\" is SAM text (its records are regrouped on the device, which holds none of a text file)",
+                         J.sams[first_sam]);
     // the job's route, decided here and nowhere else
     const bool tokenize = J.resume_log_at < 0 && !off_by_env("PP_DEVICE_INGEST");
     J.route = first_bam >= 0 ? Route::BAM

@@ -94,6 +94,7 @@ struct BamRoute {
     pp_names *rnames = nullptr, *qnames = nullptr;      // RNAME -> contig index (seeded with the assembly's names); QNAME -> read_id
     bool borrowed = false;                              // fronts and tables are the fused command's: PolishJob::borrow
     std::vector<pp_gated *> gated;                      // [file]
+    std::vector<pp_regrouped *> regrouped;              // [file] with pp_ctx_set_regroup, else empty: kept for perm (view record -> file record)
     std::vector<pp_prepared *> prepared;
     std::vector<Stretch> added;  // the gated batches that went into the job
     bool prepare = getenv("PP_BAM_PREPARE") && atoi(getenv("PP_BAM_PREPARE")) != 0;

@@ -1,6 +1,7 @@
 // pp_driver_bam.cpp -- the polish driver's BAM route: the record chain on the device (pp_bam_files.h -> pp_batch_gate ->
-// pp_polish_add), file by file, on one context.  The fronts and the name tables are the job's own, or the fused command's
-// (PolishJob::borrow), which has decoded the files for its filter already.
+// pp_polish_add), file by file, on one context; with pp_ctx_set_regroup, pp_batch_regroup stands in front of the gate.  The fronts
+// and the name tables are the job's own, or the fused command's (PolishJob::borrow), which has decoded the files for its filter
+// already.
 #include "pp_driver.h"
 
 namespace ppd {
@@ -10,8 +11,10 @@ constexpr uint32_t KIND_BAD_CONTIG = 4;  // DE_BAD_CONTIG (pp_internal.h), as pp
 void BamRoute::reset() {
     for (pp_prepared *x : prepared) pp_prepared_free(x);
     for (pp_gated *x : gated) pp_gated_free(x);
+    for (pp_regrouped *x : regrouped) pp_regrouped_free(x);  // (before the fronts: an object never outlives the file it was made of)
     prepared.clear();
     gated.clear();
+    regrouped.clear();
     added.clear();
     fronts.clear();
     opened.clear();
@@ -36,6 +39,14 @@ int bam_create(PolishJob &J) {
     return rc;
 }
 
+// the file's own index of record `*at` of a regrouped view
+static int file_record(pp_ctx *ctx, const pp_regrouped *g, uint64_t *at) {
+    uint32_t p = 0;
+    if (int rc = pp_ctx_download(ctx, &p, pp_regrouped_perm(g) + *at, 4)) return rc;
+    *at = p;
+    return PP_OK;
+}
+
 // The error pp_polish_finish left about a job record, said about the BAM record it came from: the path and the 1-based number
 // counting all records of the file; a good alignment on a reference the assembly lacks in the reference's own words.
 int bam_polish_error(PolishJob &J, int rc) {
@@ -50,6 +61,7 @@ int bam_polish_error(PolishJob &J, int rc) {
     if (!origin_of(J.bam.added, record, &o)) return set_err(ctx, rc, said.c_str());
     pp_gated_batch(J.bam.gated[(size_t)o.s->source], &b, nullptr);
     if (pp_ctx_download(ctx, &contig, b.contig + o.at, 4) != PP_OK) return set_err(ctx, rc, said.c_str());
+    if (!J.bam.regrouped.empty() && file_record(ctx, J.bam.regrouped[(size_t)o.s->source], &o.record) != PP_OK) return set_err(ctx, rc, said.c_str());
     if (kind == KIND_BAD_CONTIG)
         return ppb::fail(ctx, rc, "query name %s in SAM but not in assembly: \"%s\" (record %llu)", ppb::name_of(J.bam.rnames, contig).c_str(),
                          J.sams[o.s->source], (unsigned long long)o.record + 1);
@@ -87,6 +99,10 @@ static int bam_add_gated(PolishJob &J, int i, const pp_gated *g) {
 // decoded, the group still pending there dropped -- the trailing run of aligned records with the last aligned record's QNAME --, the
 // rest gated and polished together with the earlier files' batches (what replay_records_before_defect does for text): an error
 // found on the way stands, otherwise N's.
+// With regrouping on, pp_batch_regroup stands between the decode and the gate: the gate sees the regrouped view, the verdicts go
+// through pp_regrouped_pass, and "in front of N" means in front of N in the REGROUPED sequence -- the reference's streaming order on
+// the file as a name-grouped one would have it.  The decode's own refusal is reported at once (no replay: what lies in front of a
+// record has no cheap meaning once records move), and every record a message names goes through perm back to the file's numbering.
 int ingest_file_bam(PolishJob &J, int i, pp_sam_counts &c) {
     pp_ctx *const ctx = J.ctx;
     BamRoute &R = J.bam;
@@ -96,6 +112,8 @@ int ingest_file_bam(PolishJob &J, int i, pp_sam_counts &c) {
         if (int rc = R.fronts[(size_t)i]->open(ctx, J.sams[i], R.kinds[(size_t)i], R.rnames, &J.lap)) return rc;
     }
     ppb::BamFile *const B = R.fronts[(size_t)i];
+    const bool regroup = pp_ctx_regroup_(ctx) != 0;
+    pp_raw_batch raw{};
     int standing = PP_OK;  // the refusal at N
     std::string standing_msg;
     auto stand = [&](int rc) { standing = rc; standing_msg = pp_last_error(ctx); };
@@ -106,12 +124,19 @@ int ingest_file_bam(PolishJob &J, int i, pp_sam_counts &c) {
     auto groups = [&]() {
         if (have_groups) return (int)PP_OK;
         have_groups = true;
-        return ppb::download_groups(*B, B->n_decoded, flag, rid);
+        if (!regroup) return ppb::download_groups(*B, B->n_decoded, flag, rid);
+        const uint64_t n = raw.n_rec;  // the regrouped view's: what the gate numbers
+        flag.assign(n ? n : 1, 0);
+        rid.assign(n ? n : 1, 0);
+        if (!n) return (int)PP_OK;
+        if (int rc = pp_ctx_download(ctx, flag.data(), raw.flag, n * 2)) return rc;
+        return pp_ctx_download(ctx, rid.data(), raw.read_id, n * 8);
     };
     uint64_t limit = B->n_rec;
     if (!B->rec) {
         uint64_t bad = 0;
         int rc = B->decode(limit, R.qnames, &bad);
+        if (defect(rc) && regroup) return rc;
         if (defect(rc)) {
             stand(rc);
             if ((rc = B->decode(bad, R.qnames, nullptr))) return rc;
@@ -127,7 +152,6 @@ int ingest_file_bam(PolishJob &J, int i, pp_sam_counts &c) {
         } else if (rc) return rc;
         if (J.lap.on) J.lap(("decoded " + B->path).c_str());
     }
-    pp_raw_batch raw;
     pp_bam_raw(B->rec, &raw);
     const uint8_t *pass = nullptr;
     uint64_t n_aligned = 0;
@@ -141,10 +165,26 @@ int ingest_file_bam(PolishJob &J, int i, pp_sam_counts &c) {
         pass = J.pass[i];
         n_aligned = J.n_pass[i];
     }
+    std::vector<uint8_t> carried;  // the verdicts in the regrouped numbering
+    const pp_regrouped *grouped = nullptr;
+    if (regroup) {
+        pp_regrouped *made = nullptr;
+        if (int rc = pp_batch_regroup(ctx, &raw, PP_MEM_DEVICE, &made)) return rc;
+        R.regrouped.push_back(made);
+        grouped = made;
+        pp_regrouped_raw(grouped, &raw);
+        if (pass) {
+            carried.resize(n_aligned ? n_aligned : 1);
+            if (int rc = pp_regrouped_pass(grouped, pass, n_aligned, carried.data())) return rc;
+            pass = carried.data();
+        }
+        if (J.lap.on) J.lap(("regrouped " + B->path).c_str());
+    }
+    const uint64_t n_view = raw.n_rec;
     pp_gated *g = nullptr;
     for (int round = 0;; round++) {
         uint64_t n_pass = n_aligned;
-        if (limit < B->n_decoded) {
+        if (limit < n_view) {
             if (int rc = groups()) return rc;
             n_pass = 0;
             for (uint64_t q = 0; q < limit; q++) n_pass += !(flag[q] & 4);
@@ -156,16 +196,21 @@ int ingest_file_bam(PolishJob &J, int i, pp_sam_counts &c) {
         if (!defect(rc) || round > 1) return rc;
         if (int rg = groups()) return rg;
         const std::string qname = ppb::name_of(R.qnames, rid[at]);
+        uint64_t said_at = at;  // the file's own record
+        if (grouped)
+            if (int rp = file_record(ctx, grouped, &said_at)) return rp;
         if (rc == PP_ERR_QUIT)
-            ppb::fail(ctx, rc, "no alignments for read %s contain sequence: \"%s\" (record %llu)", qname.c_str(), J.sams[i], (unsigned long long)at + 1);
+            ppb::fail(ctx, rc, "no alignments for read %s contain sequence: \"%s\" (record %llu)", qname.c_str(), J.sams[i], (unsigned long long)said_at + 1);
         else
-            ppb::fail(ctx, rc, "aligned record of read %s has an empty CIGAR: \"%s\" (record %llu)", qname.c_str(), J.sams[i], (unsigned long long)at + 1);
+            ppb::fail(ctx, rc, "aligned record of read %s has an empty CIGAR: \"%s\" (record %llu)", qname.c_str(), J.sams[i], (unsigned long long)said_at + 1);
         stand(rc);
         limit = at;
     }
     R.gated.push_back(g);
     pp_gated_counts(g, &c);
-    B->drop_records();  // the gate's output is its own
+    // the gate's output is its own.  (A regrouped view borrowed the records' seq and cigar: from here on nothing is read through it;
+    // the object stays for its perm, which it owns and which the messages about the job's records need.)
+    B->drop_records();
     if (standing) {
         int rc = bam_add_gated(J, i, g);
         if (rc == PP_OK) rc = pp_polish_finish(ctx);

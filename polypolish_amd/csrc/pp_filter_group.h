@@ -1,6 +1,6 @@
 // pp_filter_group.h -- the filter's read grouping behind the interning, shared by the two device loaders: pp_filter_dev.hip
 // (names in the SAM text) and pp_filter_rec.hip (the 64-bit ids of raw records).  Either interns its keys through an open-
-// addressing table of record indices -- rep[i] = the first record, over both files, that carries record i's key -- and scans
+// addressing table of record indices (the one over 64-bit ids is here: pp_regroup.hip interns a file's records with it, too) -- rep[i] = the first record, over both files, that carries record i's key -- and scans
 // "is its own representative" into id_scan; from there on nothing depends on what a key is: read numbers (the rank of a key's
 // first record), the files' group sizes, their scan, the scatter and the sort into file order.  Like pp_dev.h, which it
 // builds on, everything lives in an anonymous namespace: each translation unit gets its own copies of the kernels.
@@ -8,6 +8,52 @@
 #include "pp_dev.h"
 
 namespace {
+
+// ---- interning of 64-bit ids (pp_filter_rec.hip over both files' aligned records, pp_regroup.hip over one file's records): open
+// addressing over record indices, a slot holds record index + 1; the representative of an id is its first record ----
+__device__ __forceinline__ u32 hash_id(u64 x) {  // (the finaliser of MurmurHash3: every input bit reaches every output bit)
+    x ^= x >> 33;
+    x *= 0xff51afd7ed558ccdull;
+    x ^= x >> 33;
+    x *= 0xc4ceb9fe1a85ec53ull;
+    x ^= x >> 33;
+    return (u32)x;
+}
+
+__global__ __launch_bounds__(256) void k_rid_insert(u64 n, const u64 *__restrict__ ids, u32 *__restrict__ slots, u32 mask) {
+    const u64 me = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (me >= n) return;
+    const u64 a = ids[me];
+    u32 i = hash_id(a) & mask;
+    for (;;) {
+        // look before touching the slot with an atomic (the mate's id is usually there already)
+        u32 v = __atomic_load_n(&slots[i], __ATOMIC_RELAXED);
+        if (v == 0) v = atomicCAS(&slots[i], 0u, (u32)me + 1u);
+        if (v == 0) return;
+        if (ids[v - 1] == a) {  // a slot only ever moves to a smaller index of the SAME id
+            if ((u32)me + 1u < v) atomicMin(&slots[i], (u32)me + 1u);
+            return;
+        }
+        i = (i + 1) & mask;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_rid_find(u64 n, const u64 *__restrict__ ids, const u32 *__restrict__ slots, u32 mask,
+                                                  u32 *__restrict__ rep, u32 *__restrict__ is_rep) {
+    const u64 me = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (me >= n) return;
+    const u64 a = ids[me];
+    u32 i = hash_id(a) & mask;
+    for (;;) {
+        const u32 v = slots[i];  // (never 0 on the way: the id was inserted)
+        if (ids[v - 1] == a) {
+            rep[me] = v - 1;
+            is_rep[me] = (v - 1 == (u32)me);
+            return;
+        }
+        i = (i + 1) & mask;
+    }
+}
 
 // names of file 2 that file 1 holds as well (for the "alignments from N reads" line of file 2)
 __global__ __launch_bounds__(256) void k_mark_shared(u64 n0, u64 n, const u32 *__restrict__ rep, u32 *__restrict__ hit) {

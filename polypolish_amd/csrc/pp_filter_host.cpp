@@ -1057,6 +1057,8 @@ int run_filter(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const std::func
     if (int rc = check_filter_options(ctx, f4, outs[0] ? 4 : 2, low, high)) return rc;
     banner();
     if (int rc = filter_input_kinds(ctx, ins, R.kinds, &R.bam)) return rc;
+    if (assembly && !R.bam && pp_ctx_regroup_(ctx))  // (the fused command: refused before the filter has written anything)
+        return ppb::fail(ctx, PP_ERR_QUIT, "--regroup takes BAM input: \"%s\" is SAM text (its records are regrouped on the device, which holds none of a text file)", ins[0]);
     if (int rc = R.bam ? filter_core_bam(ctx, log, lap, ins, assembly, orientation, low, high, R)
                        : filter_core(ctx, log, lap, ins, orientation, low, high, R))
         return rc;

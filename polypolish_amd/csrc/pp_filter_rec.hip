@@ -10,7 +10,7 @@
 //                   for equality only), ref_end from the runs (Alignment::get_ref_end, alignment.rs:138-149; PP_OP_UNPARSEABLE ->
 //                   PP_REF_END_UNPARSEABLE) -- the later passes need no CIGAR -- and the id into the list of both files' ids.  A
 //                   CIGAR range outside the array is reported before anything is read through it
-//   k_rid_insert    the reference's HashMap<String, Vec<Alignment>> (filter.rs:91-145) over 64-bit keys: open addressing, a slot
+//   k_rid_insert    (pp_filter_group.h) the reference's HashMap<String, Vec<Alignment>> (filter.rs:91-145) over 64-bit keys: open addressing, a slot
 //   k_rid_find      holds record index + 1 (over both files, file 1 first), a key's representative is its first record.  Equality
 //                   is equality of the ids: no value is reserved.  The hash mixes all 64 bits (ids that differ only above bit 32,
 //                   or that are multiples of the table's capacity, spread like any others)
@@ -60,51 +60,6 @@ __global__ __launch_bounds__(256) void k_rec_compact(u32 n_rec, RecRaw R, const 
     ref_id[a] = R.contig[r];
     ref_end[a] = end;
     ids[base + a] = R.read_id[r];
-}
-
-// ---- id interning: open addressing over record indices; the representative of an id is its first record ----
-__device__ __forceinline__ u32 hash_id(u64 x) {  // (the finaliser of MurmurHash3: every input bit reaches every output bit)
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdull;
-    x ^= x >> 33;
-    x *= 0xc4ceb9fe1a85ec53ull;
-    x ^= x >> 33;
-    return (u32)x;
-}
-
-__global__ __launch_bounds__(256) void k_rid_insert(u64 n, const u64 *__restrict__ ids, u32 *__restrict__ slots, u32 mask) {
-    const u64 me = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (me >= n) return;
-    const u64 a = ids[me];
-    u32 i = hash_id(a) & mask;
-    for (;;) {
-        // look before touching the slot with an atomic (the mate's id is usually there already)
-        u32 v = __atomic_load_n(&slots[i], __ATOMIC_RELAXED);
-        if (v == 0) v = atomicCAS(&slots[i], 0u, (u32)me + 1u);
-        if (v == 0) return;
-        if (ids[v - 1] == a) {  // a slot only ever moves to a smaller index of the SAME id
-            if ((u32)me + 1u < v) atomicMin(&slots[i], (u32)me + 1u);
-            return;
-        }
-        i = (i + 1) & mask;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_rid_find(u64 n, const u64 *__restrict__ ids, const u32 *__restrict__ slots, u32 mask,
-                                                  u32 *__restrict__ rep, u32 *__restrict__ is_rep) {
-    const u64 me = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (me >= n) return;
-    const u64 a = ids[me];
-    u32 i = hash_id(a) & mask;
-    for (;;) {
-        const u32 v = slots[i];  // (never 0 on the way: the id was inserted)
-        if (ids[v - 1] == a) {
-            rep[me] = v - 1;
-            is_rep[me] = (v - 1 == (u32)me);
-            return;
-        }
-        i = (i + 1) & mask;
-    }
 }
 
 // The call's device memory: the context's grow-only buffers (pp_ctx::f_rec), handed out in the order of the requests -- the same

@@ -265,6 +265,8 @@ struct pp_ctx {
     // ---- filter job ----
     pp::DevBuf f_in[2][9], f_refend[2], f_pass[2], f_orient, f_insert, f_poisoned, f_list, f_blkcnt;
     pp::DevBuf f_rec[48];  // pp_filter_records: the call's arrays and scratch, in the order it asks for them (pp_filter_rec.hip)
+    pp::DevBuf g_rec[24];  // pp_batch_regroup: the call's scratch, in the order it asks for it (pp_regroup.hip)
+    bool regroup = false;  // pp_ctx_set_regroup: the file drivers regroup every BAM file's records in front of the gate
     pp::DevBuf f_thr;  // pp_filter_thresholds: orientation counts | the selection's state | its two histograms (THR_WORDS u32)
     pp_filter_input fdev{};
     const uint64_t *f_refend_ptr[2] = {nullptr, nullptr};

@@ -1759,6 +1759,7 @@ extern "C" void pp_ctx_destroy(pp_ctx *ctx) {
     for (auto &b : ctx->b_split) dev_free(b);
     for (auto &f : ctx->f_in) for (auto &b : f) dev_free(b);
     for (auto &b : ctx->f_rec) dev_free(b);
+    for (auto &b : ctx->g_rec) dev_free(b);
     timers_release(ctx);
     if (ctx->h_meta) (void)hipHostFree(ctx->h_meta);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
