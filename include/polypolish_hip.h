@@ -20,7 +20,9 @@
  * commands (pp_polish_files, pp_filter_files, pp_filter_polish_files).  A caller who holds alignment
  * RECORDS, not SAM text, has the record chain, every link on the device: pp_bam_records (uncompressed
  * BAM bytes -> raw records, the chain's front end) -> pp_names -> pp_filter_records -> (pp_batch_regroup, for
- * a file whose reads do not stand together ->) pp_batch_gate -> pp_batch_prepare -> pp_polish_*.
+ * a file whose reads do not stand together ->) pp_batch_gate -> pp_batch_prepare -> pp_polish_*.  pp_sam_records
+ * is the chain's second front end: SAM text -> the same raw records, for a caller who wants a link of the chain
+ * (or a step of their own) between the text and the gate.
  *
  * Conventions: plain pointers and sizes, no C++/torch types.  Every function returns PP_OK or a
  * PP_ERR_* code and never exits the process; pp_last_error() holds the message the reference
@@ -493,6 +495,57 @@ void pp_bam_names(const pp_bam *b, const uint8_t **bytes_dev, uint64_t *n_bytes,
 void pp_bam_pass(const pp_bam *b, const uint8_t **zp, uint64_t *n_aligned); /* HOST: one byte per ALIGNED record, 0 = carries ZP:Z:fail */
 int pp_bam_kernel_ms(const pp_bam *b, float *ms);
 void pp_bam_free(pp_bam *b);
+
+/* The SECOND front end of the record chain, for a caller who holds SAM TEXT (what `bwa mem` writes, the only format the reference
+ * reads): the lines of the text as a pp_raw_batch, decoded on the device -- the text twin of pp_bam_records.  The commands do not use
+ * it yet; their text routes are the fused ones (pp_dev_ingest_sam, pp_filter_load_device), which leave no raw records behind.
+ *   records      every line that is neither empty nor begins with '@' is a record, aligned or not, in file order.  Line ends are
+ *                "\n" or "\r\n"; a missing final newline is fine.  What a line is, Alignment::new decides (src/alignment.rs:49-98),
+ *                exactly as the two ingests follow it.
+ *   flag         the FLAG column;  ref_start = POS, less 1 when POS > 0
+ *   nm           starts at 0xFFFFFFFF; every field that begins with the bytes "NM:i:" sets it (case-sensitive, parse::<u32>: a
+ *                leading '+' is fine), the last one wins; still 0xFFFFFFFF behind the walk is legal on an unaligned line only
+ *   n_cig/cigar  get_expanded_cigar (src/alignment.rs:325-346) kept as runs len << 4 | op, packed densely in record order: "*" gives
+ *                no runs, a zero-length run vanishes, a run above 2^28-1 is cut into pieces of at most that
+ *   seq          is NOT copied.  The object owns one device copy of the text; raw.seq is that copy, raw.seq_off[r] the offset of
+ *                record r's SEQ column in it, raw.seq_bytes = n_bytes: no rooms, any case (the gate copies and upper-cases what it
+ *                keeps).  seq_len = the column's length, 0 for "*".  The name ranges point into the same copy.  So the caller's
+ *                `text` may be released when the call returns, with either `mem`; no byte outside [0, n_bytes) of the caller's array
+ *                is ever loaded; no byte behind n_bytes can change a result.  With PP_MEM_DEVICE the copy is one device-to-device copy.
+ *   read_id      zero until the caller fills it (pp_sam_read_id: DEVICE, n_rec entries): pp_names_ids over pp_sam_names with
+ *                PP_MEM_DEVICE and id64 = that array.  A record joins the read in front of it also when THAT record's QNAME is empty
+ *                (src/alignment.rs:255): a caller who interns names has to know.
+ *   contig       zero until the caller fills it (pp_sam_contig: DEVICE, n_rec entries): pp_names_ids over pp_sam_rnames with id32 =
+ *                that array, on a table seeded with the FASTA names (see pp_names)
+ *   lines        pp_sam_lines: DEVICE, n_rec entries, the 0-based line of record r -- what a later link's bad_record (through
+ *                pp_regrouped_perm where there is a regroup) turns into the file's own line
+ *   ZP:Z:fail    a field of exactly nine bytes, ZP:Z:fail ignoring ASCII case as the tokenizer matches it, clears the pass byte of that
+ *                aligned record (pp_sam_pass: HOST, one byte per ALIGNED record, what pp_batch_gate takes as `pass`)
+ *   refusals     the first refused line in file order wins, whatever its kind; *bad_line (may be NULL) = its 0-based index among all
+ *                lines; no object.  PP_ERR_QUIT (too few columns, missing NM tag on an aligned line, invalid CIGAR) and PP_ERR_PANIC
+ *                (FLAG, POS, an NM:i: value, a CIGAR run that overflows u32) with the sentence pp_ingest_sam has for that line, the
+ *                path "text" and the line numbered from 1: the device decides which line, the host parser then runs on that one line
+ *                (downloaded when the text is device memory).  PP_ERR_LIMIT, naming the line, for a line the reference takes but a raw
+ *                batch cannot hold: FLAG above 65535, POS above 2^32-1, an aligned line whose SEQ column is empty (not "*": seq_len 0
+ *                would turn it into one).  PP_ERR_LIMIT also for 2^32-1 or more lines and n_bytes >= 2^40.  PP_ERR_NOT_ASCII for a byte
+ *                >= 0x80 anywhere in the text, as pp_dev_ingest_sam answers it (no bad_line: which lines are valid UTF-8 is the host
+ *                parsers' to say).  PP_ERR_ARG: null arguments, PP_MEM_PEER, null text with n_bytes > 0.  n_bytes == 0, or a text of
+ *                header lines only, gives an empty object.
+ *   order        the reference streams: to get ITS order against the gate's own errors, gate the records in front of bad_line first.
+ *                `filter`'s new_quick never looks at NM; this decode does (as for the BAM route).
+ * The context's stream has been synchronised when the call returns.  pp_sam_kernel_ms: as pp_gated_kernel_ms (the kernels; the copy of
+ * the text is not among them).  The object belongs to its context and is freed before it. */
+typedef struct pp_sam pp_sam;
+int pp_sam_records(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, pp_sam **out, uint64_t *bad_line);
+void pp_sam_raw(const pp_sam *s, pp_raw_batch *out);      /* borrowed view, DEVICE; read_id / contig = the two arrays below */
+uint64_t *pp_sam_read_id(pp_sam *s);                      /* DEVICE, n_rec entries, zero until the caller fills it */
+uint32_t *pp_sam_contig(pp_sam *s);                       /* DEVICE, n_rec entries, zero until the caller fills it */
+void pp_sam_names(const pp_sam *s, const uint8_t **bytes_dev, uint64_t *n_bytes, const uint64_t **off, const uint32_t **len);  /* QNAME ranges: what pp_names_ids takes, id64 = pp_sam_read_id */
+void pp_sam_rnames(const pp_sam *s, const uint8_t **bytes_dev, uint64_t *n_bytes, const uint64_t **off, const uint32_t **len); /* RNAME ranges, id32 = pp_sam_contig */
+const uint32_t *pp_sam_lines(const pp_sam *s);            /* DEVICE, n_rec entries: 0-based line of record r, for messages of later links */
+void pp_sam_pass(const pp_sam *s, const uint8_t **zp, uint64_t *n_aligned); /* HOST, as pp_bam_pass */
+int pp_sam_kernel_ms(const pp_sam *s, float *ms);
+void pp_sam_free(pp_sam *s);
 
 /* The WRITE side of the record chain for a caller who holds BAM: the filter's verdicts written back as a BAM file, on the device --
  * what `polypolish filter` does with SAM text (filter_sam, src/filter.rs:296-343: every line again, ZP:Z:fail appended to the aligned

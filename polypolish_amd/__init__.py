@@ -596,7 +596,8 @@ def pack_names(names):
 class Names(_Owned):
     """pp_names: a set of byte strings with dense ids on the device -- QNAME -> pp_raw_batch.read_id, RNAME -> .contig.
       .ids(names)   names = a list of bytes / str, or (bytes, off, len): numpy arrays (mem = MEM_HOST) or device addresses
-                    (MEM_DEVICE, with n = names, n_bytes = bytes of the array, out = device address of n uint64).  Returns the
+                    (MEM_DEVICE, with n = names, n_bytes = bytes of the array, out = device address of n uint64 -- or, with
+                    out left None, out32 = device address of n uint32: SamRecords.contig_ptr).  Returns the
                     ids as a np.uint64 array: the number of distinct names in front of a name's first occurrence, over all calls.
                     A name whose range lies outside the array raises PolypolishError with .bad = its index.
       .count        distinct names held
@@ -608,8 +609,15 @@ class Names(_Owned):
         super().__init__(ctx)
         ctx._chk(lib().pp_names_create(ctx._h, int(expect), C.byref(self._p)))
 
-    def ids(self, names, mem=MEM_HOST, n=None, n_bytes=None, out=None):
+    def ids(self, names, mem=MEM_HOST, n=None, n_bytes=None, out=None, out32=None):
         L = lib()
+        if isinstance(names, tuple) and len(names) == 3 and mem != MEM_HOST and out is None and out32:
+            bp, op, lp = names      # the ids as n uint32 at out32 (pp_raw_batch.contig): id32 alone
+            bad = _no_index()
+            rc = L.pp_names_ids(self._p, bp, int(n_bytes), op, lp, int(n), mem, None, out32, C.byref(bad))
+            if rc:
+                _raise(rc, L.pp_last_error(self._ctx._h).decode(), bad=_index(bad))
+            return self._ctx.download(out32, int(n), np.uint32).astype(np.uint64)
         if isinstance(names, tuple) and len(names) == 3 and mem != MEM_HOST:
             bp, op, lp = names
             n, n_bytes = int(n), int(n_bytes)
@@ -870,6 +878,72 @@ class BamRecords(_Owned):
         out["name_off"] = self._ctx.download(self._names[1], self.n_rec, np.uint64)
         out["name_len"] = self._ctx.download(self._names[2], self.n_rec, np.uint32)
         return out
+
+
+class SamRecords(_Owned):
+    """pp_sam_records: the lines of SAM text as a raw batch in DEVICE memory, owned by this object -- the text twin of BamRecords.  The
+    object keeps its own device copy of the text: raw()["seq"] IS that copy (seq_off = the offset of a record's SEQ column in it, any
+    case, no rooms), and the name ranges point into it.
+      data           mem = MEM_HOST: bytes / a uint8 array; MEM_DEVICE: (device address, n_bytes), free again when the call returns
+      .n_rec, .seq_bytes (= .n_bytes, the text's), .n_cig_total
+      .raw()         the device-address dict gate_records / regroup_records / filter_records(..., mem=MEM_DEVICE) take
+      .names()       keyword arguments for Names.ids(mem=MEM_DEVICE, out=.read_id_ptr): the QNAMEs' ranges in the device copy
+      .rnames()      ... for Names.ids(mem=MEM_DEVICE, out32=.contig_ptr) on a table seeded with the FASTA names: the RNAMEs' ranges
+      .read_id_ptr, .contig_ptr   device addresses of raw()["read_id"] (n_rec uint64) and raw()["contig"] (n_rec uint32): zero until filled
+      .zp            np.uint8, one per ALIGNED record, 0 = the line carries ZP:Z:fail: gate_records' `passed` (AND the filter's)
+      .lines()       np.uint32: the 0-based line of every record (a later link's bad_record -> the file's own line)
+      .host()        numpy copies of the arrays, and "name_off" / "name_len" / "rname_off" / "rname_len" / "line"
+      .kernel_ms()   HIP-event time of the decode's kernels (the context had set_profiling on); .stage_ms(): copy | newline_index |
+                     scan | place | cigar
+    A refused text raises PolypolishError with .bad_record = the 0-based line (None where the refusal names none)."""
+    _free, _kernel_ms = "pp_sam_free", "pp_sam_kernel_ms"
+
+    def __init__(self, ctx, data, mem=MEM_HOST):
+        L = lib()
+        bp, n_bytes, _, _, _keep = _bytes_and_offsets(data, None, mem)
+        super().__init__(ctx)
+        bad = _no_index()
+        rc = L.pp_sam_records(ctx._h, bp, n_bytes, mem, C.byref(self._p), C.byref(bad))
+        if rc:
+            _raise(rc, L.pp_last_error(ctx._h).decode(), bad_record=_index(bad))
+        out = self._view = RawBatch()
+        L.pp_sam_raw(self._p, C.byref(out))
+        self.n_rec, self.seq_bytes, self.n_cig_total = int(out.n_rec), int(out.seq_bytes), int(out.n_cig_total)
+        self._ptrs = _ptrs_of(out, RAW_FIELDS)
+        self.read_id_ptr, self.contig_ptr = L.pp_sam_read_id(self._p) or 0, L.pp_sam_contig(self._p) or 0
+        self._ranges = []
+        for fn in (L.pp_sam_names, L.pp_sam_rnames):
+            nb, nbytes, no, nl = C.c_void_p(), C.c_uint64(0), C.c_void_p(), C.c_void_p()
+            fn(self._p, C.byref(nb), C.byref(nbytes), C.byref(no), C.byref(nl))
+            self._ranges.append((nb.value or 0, no.value or 0, nl.value or 0))
+            self.n_bytes = int(nbytes.value)
+        self._lines = L.pp_sam_lines(self._p) or 0
+        zp, n_al = C.c_void_p(), C.c_uint64(0)
+        L.pp_sam_pass(self._p, C.byref(zp), C.byref(n_al))
+        self.zp = _host(zp.value, n_al.value, np.uint8)
+
+    def raw(self):
+        return dict(self._ptrs, n_rec=self.n_rec, seq_bytes=self.seq_bytes, n_cig_total=self.n_cig_total)
+
+    def names(self):
+        return {"names": self._ranges[0], "n": self.n_rec, "n_bytes": self.n_bytes}
+
+    def rnames(self):
+        return {"names": self._ranges[1], "n": self.n_rec, "n_bytes": self.n_bytes}
+
+    def lines(self):
+        return self._ctx.download(self._lines, self.n_rec, np.uint32)
+
+    def host(self):
+        out = _read_batch(self._view, RAW_FIELDS, self._ctx)
+        for k, (_, off, ln) in zip(("name", "rname"), self._ranges):
+            out[k + "_off"] = self._ctx.download(off, self.n_rec, np.uint64)
+            out[k + "_len"] = self._ctx.download(ln, self.n_rec, np.uint32)
+        out["line"] = self.lines()
+        return out
+
+    def stage_ms(self):
+        return self._stage_ms("pp_sam_stage_ms_", ("copy", "newline_index", "scan", "place", "cigar"), " when the text was decoded")
 
 
 class BamTagged(_Owned):

@@ -152,6 +152,16 @@ SIGNATURES = {
     "pp_bam_pass": (None, [_vp, _pvp, _pu64]),
     "pp_bam_kernel_ms": (_i, [_vp, _pf32]),
     "pp_bam_free": (None, [_vp]),
+    "pp_sam_records": (_i, [_vp, _vp, _u64, _i, _pvp, _pu64]),
+    "pp_sam_raw": (None, [_vp, _P(RawBatch)]),
+    "pp_sam_read_id": (_vp, [_vp]),
+    "pp_sam_contig": (_vp, [_vp]),
+    "pp_sam_names": (None, [_vp, _pvp, _pu64, _pvp, _pvp]),
+    "pp_sam_rnames": (None, [_vp, _pvp, _pu64, _pvp, _pvp]),
+    "pp_sam_lines": (_vp, [_vp]),
+    "pp_sam_pass": (None, [_vp, _pvp, _pu64]),
+    "pp_sam_kernel_ms": (_i, [_vp, _pf32]),
+    "pp_sam_free": (None, [_vp]),
     "pp_bam_tagged": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _i, _vp, _u64, _pvp, _pu64]),
     "pp_bam_out_bytes": (None, [_vp, _pvp, _pu64]),
     "pp_bam_out_counts": (None, [_vp, _pu64, _pu64, _pu64]),
@@ -252,6 +262,7 @@ HOOKS = {
     "pp_names_stage_ms_": (_i, [_vp, _pf32]),       # float[5]
     "pp_bgzf_stage_ms_": (_i, [_vp, _pf32]),        # float[3]
     "pp_bam_stage_ms_": (_i, [_vp, _pf32]),         # float[3]
+    "pp_sam_stage_ms_": (_i, [_vp, _pf32]),         # float[5]
     "pp_bam_out_stage_ms_": (_i, [_vp, _pf32]),     # float[3]
     "pp_bgzf_out_stage_ms_": (_i, [_vp, _pf32]),    # float[3]
     "pp_bam_offs_stage_ms_": (_i, [_vp, _pf32]),    # float[3]

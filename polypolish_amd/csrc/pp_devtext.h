@@ -1,5 +1,5 @@
 // pp_devtext.h -- device-side text utilities shared by the SAM tokenizers (pp_tokenize.hip: polish ingest;
-// pp_filter_dev.hip: the filter's quick parse): newline index, tab search, integer parsing, the wave's lines through LDS.
+// pp_filter_dev.hip: the filter's quick parse; pp_sam.hip: text to raw records): newline index, tab search, integer parsing, the wave's lines through LDS.
 // What is not text -- typedefs, scans, the host helpers of a call -- is pp_dev.h's.  Everything lives in an anonymous
 // namespace: each translation unit gets its own copies of the kernels.
 #pragma once

@@ -494,6 +494,22 @@ extern "C" int pp_ingest_text_(pp_ingest *I, const char *path, const char *text,
     return ingest_impl(I, path, text, size, line_base, nullptr, 0, counts, err, errlen);
 }
 
+// Internal (pp_sam.hip's error path): Alignment::new on ONE line the device refused -- the code and the sentence pp_ingest_sam has
+// for it, the line numbered line_no (from 1).  PP_OK when this parser takes the line.
+extern "C" int pp_ingest_line_error_(const char *path, const char *line, size_t n, uint64_t line_no, char *err, size_t errlen) {
+    if (!path || (n && !line)) return PP_ERR_ARG;
+    static const pp_assembly no_contigs;  // (an aligned line that parses looks its RNAME up)
+    Chunk c;
+    c.beg = line;
+    c.end = line + n;
+    parse_chunk(c, &no_contigs);
+    if (!c.err_code || !err || !errlen) return c.err_code;
+    if (c.err_has_line) snprintf(err, errlen, "%s in \"%s\" (line %llu)", c.err_what.c_str(), path, (unsigned long long)line_no);
+    else if (c.err_what == NOT_UTF8) snprintf(err, errlen, "unable to load alignments from \"%s\"", path);
+    else snprintf(err, errlen, "%s", c.err_what.c_str());
+    return c.err_code;
+}
+
 // Internal (pp_driver.cpp, error path): was the failure of the last pp_ingest_sam somewhere the records before it are
 // known?  *cut = bytes of the file that hold exactly the read groups the reference had processed by then.
 extern "C" int pp_ingest_fail_cut_(const pp_ingest *I, uint64_t *cut) {
