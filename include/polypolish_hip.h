@@ -792,7 +792,15 @@ int pp_shard_assemble(const pp_shard_plan *plan, const uint8_t *const *rank_byte
  * memory (ctx may be NULL), PP_MEM_DEVICE -> the part is made by kernels on ctx's stream and lives on ctx's GPU.
  * The part is a pp_aln_batch of its own (offsets relative to its own seq / cigar arrays); orig[i] is the index of its
  * record i in `batch` (same memory kind as the part): a record number reported by a rank's pp_polish_finish is
- * rank-local, orig turns it back into the job's, and the job's first bad record is the minimum over the ranks. */
+ * rank-local, orig turns it back into the job's, and the job's first bad record is the minimum over the ranks.
+ * The part's seq array: every record in a room of its SEQ bytes up to the next multiple of PP_SEQ_ALIGN, the rooms one behind
+ * the other, zeros behind the read.  The rooms follow the order of `batch`'s seq array, slot by slot of PP_SEQ_ALIGN bytes (a
+ * window-grouped batch gives window-grouped parts), when every selected record that has SEQ bytes starts on a slot of its own
+ * inside that array -- as in every batch of the library's own producers --, otherwise the order of the records; host and
+ * device parts alike.  A record without SEQ bytes takes no room and claims no slot: its seq_off is that of the room of the
+ * record that starts in its slot (or, without one, of the next room).
+ * The part's window-order mirror is `batch`'s, restricted (with its run table); it counts as one of the library's own only
+ * when `batch`'s does: the restriction of a caller's mirror is compared with the arrays by pp_polish_add like the caller's. */
 typedef struct pp_shard_part pp_shard_part;
 int pp_shard_split(pp_ctx *ctx, const pp_shard_plan *plan, uint32_t dest, const pp_aln_batch *batch, int mem,
                    pp_shard_part **out);

@@ -378,14 +378,20 @@ class ShardPart(_Owned):
     its window's records plus those that reach in from the neighbours).  The batch is given as raw pointers
     (`ptrs`: field name -> address, host or device as `mem` says); `ctx` may be None for host memory.
       .n_aln, .seq_bytes, .n_cig_total, .ptrs (field name -> address of the part's arrays, same memory kind), .orig_ptr
-      .host() -> (recs dict of numpy arrays, orig) for a host part."""
+      .host() -> (recs dict of numpy arrays, orig) for a host part.
+    wo_idx_base (internal hook, pp_shard_split_view_): what the file_idx of the batch's mirror count from, for a batch that is
+    a view on records [lo, hi) of a larger one (the one-process multi-GPU driver's pieces)."""
     _free = "pp_shard_part_free"
 
-    def __init__(self, ctx, plan, dest, n_aln, ptrs, seq_bytes, n_cig_total, mem):
+    def __init__(self, ctx, plan, dest, n_aln, ptrs, seq_bytes, n_cig_total, mem, wo_idx_base=0):
         L = lib()
         b = aln_batch(n_aln, ptrs, seq_bytes, n_cig_total)  # (ptrs["wo_runs"]: the mirror's runs go along, restricted)
         super().__init__(ctx)  # (the context, and with it the part's device memory, stays alive)
-        rc = L.pp_shard_split(ctx._h if ctx is not None else None, plan._p, dest, C.byref(b), mem, C.byref(self._p))
+        h = ctx._h if ctx is not None else None
+        if wo_idx_base:
+            rc = L.pp_shard_split_view_(h, plan._p, dest, C.byref(b), mem, wo_idx_base, C.byref(self._p))
+        else:
+            rc = L.pp_shard_split(h, plan._p, dest, C.byref(b), mem, C.byref(self._p))
         if rc:
             raise PolypolishError(rc, L.pp_last_error(ctx._h).decode() if ctx is not None else "pp_shard_split failed")
         out, orig = AlnBatch(), C.c_void_p()
@@ -404,9 +410,9 @@ class ShardPart(_Owned):
         return _read_batch(self._view, REC_FIELDS, None, ("wo",)), _host(self.orig_ptr, self.n_aln, np.uint32)
 
 
-def shard_split_host(plan, dest, recs):
+def shard_split_host(plan, dest, recs, wo_idx_base=0):
     """Host numpy SoA -> (recs of the part, orig).  recs["wo"] (the window-order mirror, WO_DTYPE) goes along when it is there,
-    and recs["wo_runs"] (the ends of its runs) with it."""
+    and recs["wo_runs"] (the ends of its runs) with it.  wo_idx_base: see ShardPart."""
     keep = {k: np.ascontiguousarray(recs[k], dtype=dt) for k, dt in REC_FIELDS}
     ptrs = {k: v.ctypes.data for k, v in keep.items()}
     if "wo" in recs and len(recs["wo"]):
@@ -415,7 +421,7 @@ def shard_split_host(plan, dest, recs):
         if recs.get("wo_runs") is not None and len(recs["wo_runs"]):  # the mirror's runs: restricted along with it
             ptrs["wo_runs"] = recs["wo_runs"]
     part = ShardPart(None, plan, dest, len(keep["contig"]), ptrs, len(keep["seq"]),
-                     len(keep["cigar"]), MEM_HOST)
+                     len(keep["cigar"]), MEM_HOST, wo_idx_base)
     out = part.host()
     if "wo_runs" in part.ptrs and "wo" in out[0]:
         out[0]["wo_runs"] = part.ptrs["wo_runs"]
@@ -1068,13 +1074,15 @@ def filter_records(ctx, raw1, raw2, orientation="auto", low=0.1, high=99.9, mem=
             "counts": [(int(c.alignments), int(c.reads)) for c in cnt], "report": _report_dict(rep)}
 
 
-def shard_count(ctx, n_aln, contig_ptr, mem, n_contigs, ptrs=None):
-    """pp_shard_count: alignment records per contig of a batch given by pointers."""
+def shard_count(ctx, n_aln, contig_ptr, mem, n_contigs, ptrs=None, into=None):
+    """pp_shard_count: alignment records per contig of a batch given by pointers, ADDED to `into` (uint64, n_contigs; default:
+    zeros)."""
     p = ptrs or {}
     one = contig_ptr
     b = AlnBatch(n_aln, contig_ptr, p.get("ref_start", one), p.get("k", one), p.get("seq_off", one), p.get("seq_len", one),
                  p.get("cig_off", one), p.get("n_cig", one), p.get("seq", one), 0, p.get("cigar", one), 0)
-    cnt = np.zeros(n_contigs, dtype=np.uint64)
+    cnt = np.zeros(n_contigs, dtype=np.uint64) if into is None else into
+    assert cnt.dtype == np.uint64 and len(cnt) == n_contigs and cnt.flags.c_contiguous
     rc = lib().pp_shard_count(ctx._h if ctx is not None else None, C.byref(b), mem, n_contigs, cnt.ctypes.data)
     if rc:
         raise PolypolishError(rc, "pp_shard_count failed")

@@ -269,4 +269,5 @@ HOOKS = {
     "pp_bam_offs_stats_": (_i, [_vp, _pu64]),       # uint64[4]
     "pp_bam_walk_geometry_": (None, [_pu32] * 3),
     "pp_sam_group_cut_": (_u64, [_str, _u64, _u64]),
+    "pp_shard_split_view_": (_i, [_vp, _P(ShardPlan), _u32, _P(AlnBatch), _i, _u32, _pvp]),  # pp_shard_split + wo_idx_base
 }

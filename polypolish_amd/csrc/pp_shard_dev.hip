@@ -88,18 +88,21 @@ __global__ __launch_bounds__(256) void k_split_flag(u64 n, const u32 *__restrict
     // the order of the SEQ bytes in the source's seq array is kept (a window-grouped batch gives window-grouped parts):
     // the array as slots of PP_SEQ_ALIGN bytes, a selected record's room noted at its first slot, scanned by the caller.
     // A batch whose records do not start on slots of their own (not from this library's producers) says so in *bad and
-    // the part is laid out in the order of the records.
-    if (sel && slots) {
+    // the part is laid out in the order of the records.  A record without SEQ bytes takes no room and notes nothing: a note
+    // of 0 would wipe out the note of the record that starts in its slot, or not, as the threads happen to run.
+    if (sel && slots && seq_len[i]) {
         const u64 so = seq_off[i];
         if ((so & ((u64)PP_SEQ_ALIGN - 1u)) || (so >> 5) >= n_slots || atomicExch(&slots[so >> 5], seq_room(seq_len[i]) >> 5) != 0u) atomicOr(bad, 1u);
     }
 }
 
-// a selected record's place in the part's seq array: the scan of the slots in front of its own
+// a selected record's place in the part's seq array: the scan of the slots in front of its own (a record without SEQ bytes
+// noted nothing: it sits in front of the room of the record that starts in its slot -- whatever its seq_off says, a slot
+// of the array or the one behind its end)
 __global__ __launch_bounds__(256) void k_split_place(u64 n, const u32 *__restrict__ flag, const u64 *__restrict__ seq_off,
-                                                     const u32 *__restrict__ slot_scan, u64 *__restrict__ seq_scan) {
+                                                     const u32 *__restrict__ slot_scan, u64 n_slots, u64 *__restrict__ seq_scan) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && flag[i]) seq_scan[i] = (u64)slot_scan[seq_off[i] >> 5] << 5;
+    if (i < n && flag[i]) seq_scan[i] = (u64)slot_scan[min(seq_off[i] >> 5, n_slots)] << 5;
 }
 
 struct SplitOut {
@@ -243,12 +246,15 @@ struct HostUnits {
     UnitTable table(u32 n_contigs) const { return UnitTable{first.data(), lo.data(), hi.data(), rank.data(), n_contigs, fallback}; }
 };
 
-void set_view(pp_shard_part *P, uint64_t n, uint64_t seq_bytes, uint64_t n_cig_total) {
+// own: the source's mirror was one of the library's own -- then so is the part's (pp_polish_add takes it unchecked); the
+// restriction of anybody else's mirror is handed on as anybody's, and the polish compares it with the arrays before it reads
+// through it (k_split_wo / the host loop copy the source's entries, they do not look at the records)
+void set_view(pp_shard_part *P, uint64_t n, uint64_t seq_bytes, uint64_t n_cig_total, bool own) {
     pp_aln_batch &v = P->view;
     v.n_aln = n; v.seq_bytes = seq_bytes; v.n_cig_total = n_cig_total;
     v.seq4 = P->mem == PP_MEM_DEVICE ? (const u8 *)P->d[10] : nullptr;  // a device part brings the 4-bit mirror of its seq array
     v.wo = !P->has_wo || n == 0 ? nullptr : (P->mem == PP_MEM_DEVICE ? (const pp_wo_rec *)P->d[11] : P->h_wo.data());  // ... and both kinds the window-order mirror, when the source has one
-    pp_mirror_register_(P, v.wo, v.wo ? (size_t)n * sizeof(pp_wo_rec) : 0);  // (one of the library's own: pp_polish_add takes it unchecked)
+    pp_mirror_register_(P, own ? v.wo : nullptr, own && v.wo ? (size_t)n * sizeof(pp_wo_rec) : 0);
     v.wo_n_runs = v.wo ? (uint32_t)P->wo_runs.size() : 0;  // ... with its runs (a restriction of an ascending run is one)
     v.wo_run_end = v.wo_n_runs ? P->wo_runs.data() : nullptr;
     if (P->mem == PP_MEM_DEVICE) {
@@ -277,6 +283,10 @@ bool src_runs_ok(const pp_aln_batch *b, u32 wo_base) {
     return prev == b->n_aln;
 }
 
+bool src_mirror_own(const pp_aln_batch *b) {
+    return b->wo && b->n_aln && pp_mirror_trusted_(b->wo, (size_t)b->n_aln * sizeof(pp_wo_rec));
+}
+
 bool batch_ok(const pp_aln_batch *b) {
     return b && (b->n_aln == 0 || (b->contig && b->ref_start && b->k && b->seq_off && b->seq_len && b->cig_off && b->n_cig &&
                                   b->seq && b->cigar));
@@ -299,21 +309,34 @@ int split_host(pp_shard_part *P, const HostUnits &U, u32 n_contigs, u32 dest, co
     P->h_contig.reserve(cnt); P->h_ref_start.reserve(cnt); P->h_k.reserve(cnt); P->h_seq_len.reserve(cnt); P->h_n_cig.reserve(cnt);
     P->h_orig.reserve(cnt); P->h_seq_off.reserve(cnt); P->h_cig_off.reserve(cnt);
     P->h_seq.resize(seq_total + 64); P->h_cigar.resize(cig_total + 1);
-    // where the part's SEQ bytes go: in the order of the SOURCE's seq array (a window-grouped batch gives window-grouped
-    // parts), which for a batch in file order is the order of the records
+    // where the part's SEQ bytes go: in the order of the SOURCE's seq array, slot by slot of PP_SEQ_ALIGN bytes (a
+    // window-grouped batch gives window-grouped parts), when every selected record that has SEQ bytes starts on a slot of its
+    // own inside that array; otherwise in the order of the records.  A record without SEQ bytes takes no room and claims no
+    // slot: it sits in front of the room of the record that starts in its slot.  (What the kernels do: k_split_flag.)
     std::vector<uint64_t> picked;
     picked.reserve(cnt);
-    bool sorted = true;
     for (uint64_t i = 0; i < n; i++)
-        if (sel[i]) {
-            if (!picked.empty() && B->seq_off[i] < B->seq_off[picked.back()]) sorted = false;
-            picked.push_back(i);
-        }
+        if (sel[i]) picked.push_back(i);
+    const uint64_t n_slots = (B->seq_bytes + (uint64_t)PP_SEQ_ALIGN - 1) / (uint64_t)PP_SEQ_ALIGN;
+    bool by_slots = n_slots > 0 && n_slots < 0xFFFFFFF0ull;
+    auto slot_of = [&](uint32_t j) { return std::min<uint64_t>(B->seq_off[picked[j]] / (uint64_t)PP_SEQ_ALIGN, n_slots); };
+    auto has_seq = [&](uint32_t j) { return B->seq_len[picked[j]] != 0; };
+    std::vector<uint32_t> ord(cnt);
+    for (uint64_t j = 0; j < cnt; j++) ord[j] = (uint32_t)j;
+    if (by_slots) {
+        for (uint64_t j = 0; j < cnt && by_slots; j++)
+            if (has_seq((uint32_t)j) && (B->seq_off[picked[j]] % (uint64_t)PP_SEQ_ALIGN || B->seq_off[picked[j]] / (uint64_t)PP_SEQ_ALIGN >= n_slots)) by_slots = false;
+    }
+    if (by_slots) {
+        std::vector<uint32_t> by(ord);
+        auto less = [&](uint32_t a, uint32_t b) { return slot_of(a) != slot_of(b) ? slot_of(a) < slot_of(b) : (!has_seq(a) && has_seq(b)); };
+        if (!std::is_sorted(by.begin(), by.end(), less)) std::stable_sort(by.begin(), by.end(), less);  // (a batch in file order is)
+        for (uint64_t j = 1; j < cnt && by_slots; j++)
+            if (has_seq(by[j]) && has_seq(by[j - 1]) && slot_of(by[j]) == slot_of(by[j - 1])) by_slots = false;  // two in one slot
+        if (by_slots) ord.swap(by);
+    }
     std::vector<uint64_t> place(cnt);  // per part record: its offset in the part's seq array
     {
-        std::vector<uint32_t> ord(cnt);
-        for (uint64_t j = 0; j < cnt; j++) ord[j] = (uint32_t)j;
-        if (!sorted) std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return B->seq_off[picked[a]] < B->seq_off[picked[b]]; });
         uint64_t so = 0;
         for (uint64_t j = 0; j < cnt; j++) { place[ord[j]] = so; so += seq_room(B->seq_len[picked[ord[j]]]); }
     }
@@ -348,7 +371,7 @@ int split_host(pp_shard_part *P, const HostUnits &U, u32 n_contigs, u32 dest, co
         P->has_wo = ok && P->h_wo.size() == cnt;
         if (!P->has_wo) P->wo_runs.clear();
     }
-    set_view(P, cnt, seq_total, cig_total);
+    set_view(P, cnt, seq_total, cig_total, src_mirror_own(B));
     return PP_OK;
 }
 
@@ -356,7 +379,7 @@ int split_device(pp_shard_part *P, const HostUnits &U, u32 n_contigs, u32 dest, 
     pp_ctx *ctx = P->ctx;
     hipStream_t st = ctx->stream;
     const uint64_t n = B->n_aln;
-    if (n == 0) { set_view(P, 0, 0, 0); return PP_OK; }
+    if (n == 0) { set_view(P, 0, 0, 0, false); return PP_OK; }
     PP_HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc;
     // the unit table on the device (a few hundred bytes), and the scratch of this call: the context's own buffers, grow-only
@@ -403,7 +426,7 @@ int split_device(pp_shard_part *P, const HostUnits &U, u32 n_contigs, u32 dest, 
     if (by_slots && !bad && cnt) {  // the part's SEQ bytes in the order of the source's seq array
         if ((rc = scan_u32<u32>(ctx, sums, sums_off, (const u32 *)slots.p, n_slots, (u32 *)slot_scan.p))) return done(rc);
         hipLaunchKernelGGL(k_split_place, dim3(blocks), dim3(256), 0, st, (u64)n, (const u32 *)flag.p, (const u64 *)B->seq_off,
-                           (const u32 *)slot_scan.p, (u64 *)seq_scan.p);
+                           (const u32 *)slot_scan.p, (u64)n_slots, (u64 *)seq_scan.p);
     }
     const size_t esz[12] = {4, 4, 4, 8, 4, 8, 4, 1, 4, 4, 1, sizeof(pp_wo_rec)};
     const uint64_t ecnt[12] = {cnt, cnt, cnt, cnt, cnt, cnt, cnt, seq_total + 64, cig_total, cnt, (seq_total + 1) / 2 + 96, B->wo ? cnt : 0};
@@ -447,7 +470,7 @@ int split_device(pp_shard_part *P, const HostUnits &U, u32 n_contigs, u32 dest, 
         }
     }
     if (hipGetLastError() != hipSuccess) return done(ctx->fail(PP_ERR_HIP, "pp_shard_split: a kernel launch failed"));
-    set_view(P, cnt, seq_total, cig_total);
+    set_view(P, cnt, seq_total, cig_total, src_mirror_own(B));
     return done(PP_OK);  // synchronises: the part is complete when the call returns
 }
 

@@ -14,6 +14,7 @@ import torch.multiprocessing as mp
 import polypolish_amd as pp
 import synth
 from polypolish_amd import distributed as D
+from shard_model import _ref_span, _split_reference  # noqa: F401  (the plain routing rule: tests/shard_model.py)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -112,31 +113,6 @@ def test_assignment_is_balanced_and_assembly_restores_the_order():
         data, out_off = plan.assemble(rank_bytes, rank_offs)
         assert data == b"".join(marks)
         assert [int(x) for x in out_off] == [0] + list(np.cumsum([len(m) for m in marks]))
-
-
-def _ref_span(recs, i):
-    co, nc = int(recs["cig_off"][i]), int(recs["n_cig"][i])
-    ops = recs["cigar"][co:co + nc]
-    return max(1, int(sum(int(o) >> 4 for o in ops if (int(o) & 15) in (0, 2, 3, 7, 8))))
-
-
-def _split_reference(plan, dest, contig_off, recs):
-    """The routing rule in plain Python: a record goes to the rank of every unit its [ref_start, ref_start + span) touches."""
-    keep = []
-    nc = len(contig_off) - 1
-    last_rank = int(plan.unit_rank[-1])
-    for i in range(len(recs["contig"])):
-        c, rs, span = int(recs["contig"][i]), int(recs["ref_start"][i]), _ref_span(recs, i)
-        if c >= nc:
-            owners = {last_rank}
-        else:
-            us = [u for u in range(len(plan.unit_contig)) if plan.unit_contig[u] == c]
-            owners = {int(plan.unit_rank[u]) for u in us if rs < int(plan.unit_hi[u]) and rs + span > int(plan.unit_lo[u])}
-            if not owners:
-                owners = {int(plan.unit_rank[us[-1]])}
-        if dest in owners:
-            keep.append(i)
-    return np.array(keep, dtype=np.int64)
 
 
 @pytest.mark.parametrize("world", [2, 3, 8])
