@@ -24,17 +24,16 @@
 #include "pp_bam_host.h"
 #include "pp_dev.h"
 
-struct pp_bam {
-    pp_ctx *ctx = nullptr;
-    // flag read_id contig ref_start nm seq_off seq_len cig_off n_cig seq cigar name_off name_len
-    void *d[13] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    void *own_bytes = nullptr;         // the device copy of host bytes (the name ranges point into it)
-    const uint8_t *bytes = nullptr;    // DEVICE: own_bytes or the caller's
+struct pp_bam : DevOwner {
+    using DevOwner::DevOwner;
+    RawArrays a;
+    u64 *name_off = nullptr;           // the QNAME ranges, in `bytes`
+    u32 *name_len = nullptr;
+    const uint8_t *bytes = nullptr;    // DEVICE: the object's copy of host bytes, or the caller's
     uint64_t n_bytes = 0;
     pp_raw_batch view{};
     std::vector<uint8_t> pass;         // HOST: one byte per aligned record, 0 = ZP:Z:fail
-    bool timed = false;
-    float ms[3] = {0.f, 0.f, 0.f};     // pass A | the scans and the placement | pass B
+    StageMs<3> t;                      // pass A | the scans and the placement | pass B
 };
 
 namespace {
@@ -275,26 +274,19 @@ extern "C" int pp_bam_walk(const uint8_t *bytes, uint64_t n_bytes, uint64_t from
     return pp_bam_host::walk(bytes, n_bytes, from, (uint64_t *)rec_off, cap, (uint64_t *)n_rec, (uint64_t *)end, t_bam_msg, sizeof t_bam_msg);
 }
 
-extern "C" void pp_bam_free(pp_bam *b) {
-    if (!b) return;
-    if (b->ctx) (void)hipSetDevice(b->ctx->device);
-    for (void *q : b->d)
-        if (q) (void)hipFree(q);
-    if (b->own_bytes) (void)hipFree(b->own_bytes);
-    delete b;
-}
+extern "C" void pp_bam_free(pp_bam *b) { delete b; }
 
 extern "C" void pp_bam_raw(const pp_bam *b, pp_raw_batch *out) {
     if (out) *out = b ? b->view : pp_raw_batch{};
 }
 
-extern "C" uint64_t *pp_bam_read_id(pp_bam *b) { return b ? (uint64_t *)b->d[1] : nullptr; }
+extern "C" uint64_t *pp_bam_read_id(pp_bam *b) { return b ? (uint64_t *)b->a.read_id : nullptr; }
 
 extern "C" void pp_bam_names(const pp_bam *b, const uint8_t **bytes_dev, uint64_t *n_bytes, const uint64_t **off, const uint32_t **len) {
     if (bytes_dev) *bytes_dev = b ? b->bytes : nullptr;
     if (n_bytes) *n_bytes = b ? b->n_bytes : 0;
-    if (off) *off = b ? (const uint64_t *)b->d[11] : nullptr;
-    if (len) *len = b ? (const uint32_t *)b->d[12] : nullptr;
+    if (off) *off = b ? (const uint64_t *)b->name_off : nullptr;
+    if (len) *len = b ? b->name_len : nullptr;
 }
 
 extern "C" void pp_bam_pass(const pp_bam *b, const uint8_t **zp, uint64_t *n_aligned) {
@@ -303,18 +295,11 @@ extern "C" void pp_bam_pass(const pp_bam *b, const uint8_t **zp, uint64_t *n_ali
 }
 
 extern "C" int pp_bam_kernel_ms(const pp_bam *b, float *ms) {
-    if (!b || !ms) return PP_ERR_ARG;
-    if (!b->timed) return b->ctx->fail(PP_ERR_ARG, "pp_bam_kernel_ms: the context had no profiling on when the records were decoded (pp_ctx_set_profiling)");
-    *ms = b->ms[0] + b->ms[1] + b->ms[2];
-    return PP_OK;
+    return b ? b->t.total(b->ctx, "pp_bam_kernel_ms", "when the records were decoded", ms) : PP_ERR_ARG;
 }
 
 // (internal hook, not part of the header: tools/bam_timing.py) the same time by stage: pass A | scans and placement | pass B
-extern "C" int pp_bam_stage_ms_(const pp_bam *b, float *ms3) {
-    if (!b || !ms3 || !b->timed) return PP_ERR_ARG;
-    for (int i = 0; i < 3; i++) ms3[i] = b->ms[i];
-    return PP_OK;
-}
+extern "C" int pp_bam_stage_ms_(const pp_bam *b, float *ms3) { return b ? b->t.stages(ms3) : PP_ERR_ARG; }
 
 extern "C" int pp_bam_records(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, const uint64_t *rec_off, uint64_t n_rec, int mem,
                               const uint32_t *ref_map, uint32_t n_ref, pp_bam **out, uint64_t *bad_record) {
@@ -345,9 +330,7 @@ extern "C" int pp_bam_records(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_byte
     hipStream_t st = ctx->stream;
     const u32 n = (u32)n_rec;
 
-    pp_bam *P = new pp_bam;
-    P->ctx = ctx;
-    std::unique_ptr<pp_bam, void (*)(pp_bam *)> guard(P, pp_bam_free);  // (every early return releases what was made so far)
+    std::unique_ptr<pp_bam> P(new pp_bam(ctx));
     CallScratch T;
     StageTimer timer(ctx, ctx->profiling != 0);
     int rc;
@@ -355,30 +338,27 @@ extern "C" int pp_bam_records(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_byte
     BamSrc S{};
     S.n_bytes = n_bytes;
     S.n_ref = n_ref;
-    if (mem == PP_MEM_HOST) {
-        PP_HIPCHK(ctx, hipMalloc(&P->own_bytes, n_bytes ? (size_t)n_bytes : 16));
-        if (n_bytes) PP_HIPCHK(ctx, hipMemcpyAsync(P->own_bytes, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, st));
-        S.bytes = (const u8 *)P->own_bytes;
-    } else {
-        S.bytes = bytes;
+    S.bytes = bytes;
+    if (mem == PP_MEM_HOST) {  // the object's copy: the name ranges point into it
+        u8 *own;
+        if ((rc = P->alloc(own, (size_t)n_bytes))) return rc;
+        if (n_bytes) PP_HIPCHK(ctx, hipMemcpyAsync(own, bytes, (size_t)n_bytes, hipMemcpyHostToDevice, st));
+        S.bytes = own;
     }
     if ((rc = on_device(ctx, T, mem, (const u64 *)rec_off, n, &S.rec_off))) return rc;
     P->bytes = S.bytes;
     P->n_bytes = n_bytes;
     if (n == 0) {  // no records: an empty batch
         PP_HIPCHK(ctx, hipStreamSynchronize(st));
-        guard.release();
-        *out = P;
+        *out = P.release();
         return PP_OK;
     }
     if (ref_map && (rc = on_device(ctx, T, PP_MEM_HOST, ref_map, (size_t)n_ref + 1, &S.ref_map))) return rc;  // (host memory always)
 
     // ---- the per-record arrays ----
-    const size_t rbytes[13] = {(size_t)n * 2, (size_t)n * 8, (size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)n * 8, (size_t)n * 4,
-                               (size_t)n * 8, (size_t)n * 4, 0, 0, (size_t)n * 8, (size_t)n * 4};
-    for (int i = 0; i < 13; i++)
-        if (rbytes[i]) PP_HIPCHK(ctx, hipMalloc(&P->d[i], rbytes[i]));
-    PP_HIPCHK(ctx, hipMemsetAsync(P->d[1], 0, (size_t)n * 8, st));  // read_id: the caller's (pp_names_ids)
+    RawArrays &A = P->a;
+    if ((rc = A.alloc_records(*P, n)) || (rc = P->alloc(P->name_off, n)) || (rc = P->alloc(P->name_len, n))) return rc;
+    PP_HIPCHK(ctx, hipMemsetAsync(A.read_id, 0, (size_t)n * 8, st));  // read_id: the caller's (pp_names_ids)
     const u32 nb = (n + BAM_BLOCK - 1u) / BAM_BLOCK;
     void *d_zp, *d_pass, *d_blk3, *d_blk3off, *d_status;
     if ((rc = T.get(ctx, &d_zp, (size_t)n)) || (rc = T.get(ctx, &d_pass, (size_t)n)) || (rc = T.get(ctx, &d_blk3, (size_t)nb * 24)) ||
@@ -387,12 +367,11 @@ extern "C" int pp_bam_records(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_byte
     PP_HIPCHK(ctx, hipMemsetAsync(d_status, 0xFF, 16, st));
 
     // ---- pass A, and the sums ----
-    BamRec O{(uint16_t *)P->d[0], (u32 *)P->d[2], (u32 *)P->d[3], (u32 *)P->d[4], (u32 *)P->d[6], (u32 *)P->d[8], (u32 *)P->d[12], (u64 *)P->d[11],
-             (u8 *)d_zp};
+    BamRec O{A.flag, A.contig, A.ref_start, A.nm, A.seq_len, A.n_cig, P->name_len, P->name_off, (u8 *)d_zp};
     if ((rc = timer.begin(0))) return rc;
     hipLaunchKernelGGL(k_bam_scan, dim3((n + 255u) / 256u), dim3(256), 0, st, n, S, O, (u64 *)d_status);
     if ((rc = timer.end()) || (rc = timer.begin(1))) return rc;
-    hipLaunchKernelGGL(k_bam_place<false>, dim3(nb), dim3(BAM_BLOCK), 0, st, n, (const uint16_t *)P->d[0], (const u32 *)P->d[6], (const u32 *)P->d[8],
+    hipLaunchKernelGGL(k_bam_place<false>, dim3(nb), dim3(BAM_BLOCK), 0, st, n, (const uint16_t *)A.flag, (const u32 *)A.seq_len, (const u32 *)A.n_cig,
                        (const u8 *)d_zp, (u64 *)d_blk3, (u64 *)nullptr, (u64 *)nullptr, (u8 *)nullptr);
     hipLaunchKernelGGL(k_colscan<3>, dim3(1), dim3(1024), 0, st, (const u64 *)d_blk3, (u64)nb, (u64 *)d_blk3off);
     if ((rc = timer.end())) return rc;
@@ -412,34 +391,21 @@ extern "C" int pp_bam_records(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_byte
     if (total >= (1ull << 40)) return ctx->fail(PP_ERR_LIMIT, "more than 2^40 SEQ bytes in one batch");
 
     // ---- the places, pass B ----
-    PP_HIPCHK(ctx, hipMalloc(&P->d[9], (size_t)total + 64));
-    PP_HIPCHK(ctx, hipMalloc(&P->d[10], n_cig_total ? (size_t)n_cig_total * 4 : 16));
-    PP_HIPCHK(ctx, hipMemsetAsync((u8 *)P->d[9] + total, 0, 64, st));
+    if ((rc = P->alloc(A.seq, (size_t)total + 64)) || (rc = P->alloc(A.cigar, (size_t)n_cig_total))) return rc;
+    PP_HIPCHK(ctx, hipMemsetAsync(A.seq + total, 0, 64, st));
     if ((rc = timer.begin(1))) return rc;
-    hipLaunchKernelGGL(k_bam_place<true>, dim3(nb), dim3(BAM_BLOCK), 0, st, n, (const uint16_t *)P->d[0], (const u32 *)P->d[6], (const u32 *)P->d[8],
-                       (const u8 *)d_zp, (u64 *)d_blk3off, (u64 *)P->d[5], (u64 *)P->d[7], (u8 *)d_pass);
+    hipLaunchKernelGGL(k_bam_place<true>, dim3(nb), dim3(BAM_BLOCK), 0, st, n, (const uint16_t *)A.flag, (const u32 *)A.seq_len, (const u32 *)A.n_cig,
+                       (const u8 *)d_zp, (u64 *)d_blk3off, A.seq_off, A.cig_off, (u8 *)d_pass);
     if ((rc = timer.end()) || (rc = timer.begin(2))) return rc;
-    hipLaunchKernelGGL(k_bam_expand, dim3((unsigned)(((u64)n * 8u + 255u) / 256u)), dim3(256), 0, st, n, S.bytes, n_bytes, (const u64 *)P->d[11],
-                       (const u32 *)P->d[12], (const u32 *)P->d[6], (const u32 *)P->d[8], (const u64 *)P->d[5], (const u64 *)P->d[7], (u8 *)P->d[9],
-                       (u32 *)P->d[10]);
+    hipLaunchKernelGGL(k_bam_expand, dim3((unsigned)(((u64)n * 8u + 255u) / 256u)), dim3(256), 0, st, n, S.bytes, n_bytes, (const u64 *)P->name_off,
+                       (const u32 *)P->name_len, (const u32 *)A.seq_len, (const u32 *)A.n_cig, (const u64 *)A.seq_off, (const u64 *)A.cig_off, A.seq, A.cigar);
     if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     P->pass.resize((size_t)n_al);
     if (n_al) PP_HIPCHK(ctx, hipMemcpyAsync(P->pass.data(), d_pass, (size_t)n_al, hipMemcpyDeviceToHost, st));
     PP_HIPCHK(ctx, hipStreamSynchronize(st));  // host inputs may be released, the scratch goes away
-    if (timer.on) {
-        if ((rc = timer.sums(P->ms, 3))) return rc;
-        P->timed = true;
-    }
-    pp_raw_batch &V = P->view;
-    V.n_rec = n;
-    V.flag = (const uint16_t *)P->d[0]; V.read_id = (const uint64_t *)P->d[1]; V.contig = (const u32 *)P->d[2]; V.ref_start = (const u32 *)P->d[3];
-    V.nm = (const u32 *)P->d[4]; V.seq_off = (const uint64_t *)P->d[5]; V.seq_len = (const u32 *)P->d[6]; V.cig_off = (const uint64_t *)P->d[7];
-    V.n_cig = (const u32 *)P->d[8]; V.seq = (const u8 *)P->d[9];
-    V.seq_bytes = total;
-    V.cigar = (const u32 *)P->d[10];
-    V.n_cig_total = n_cig_total;
-    guard.release();
-    *out = P;
+    if ((rc = P->t.take(timer))) return rc;
+    P->view = A.view(n, total, n_cig_total);
+    *out = P.release();
     return PP_OK;
 }

@@ -38,13 +38,12 @@
 #include <fcntl.h>
 #include <unistd.h>
 
-struct pp_bam_out {
-    pp_ctx *ctx = nullptr;
-    void *d_out = nullptr;  // DEVICE: the file
+struct pp_bam_out : DevOwner {
+    using DevOwner::DevOwner;
+    uint8_t *d_out = nullptr;  // DEVICE: the file
     uint64_t n_out = 0;
     uint64_t pass_count = 0, fail_count = 0, n_blocks = 0;
-    bool timed = false;
-    float ms[3] = {0.f, 0.f, 0.f};  // pass A | the scans | pass B
+    StageMs<3> t;              // pass A | the scans | pass B
 };
 
 namespace {
@@ -364,15 +363,10 @@ __global__ __launch_bounds__(TAG_BLOCK, 8) void k_tag_frame(FrameArgs A) {
 
 }  // namespace
 
-extern "C" void pp_bam_out_free(pp_bam_out *o) {
-    if (!o) return;
-    if (o->ctx) (void)hipSetDevice(o->ctx->device);
-    if (o->d_out) (void)hipFree(o->d_out);
-    delete o;
-}
+extern "C" void pp_bam_out_free(pp_bam_out *o) { delete o; }
 
 extern "C" void pp_bam_out_bytes(const pp_bam_out *o, const uint8_t **dev, uint64_t *n_bytes) {
-    if (dev) *dev = o ? (const uint8_t *)o->d_out : nullptr;
+    if (dev) *dev = o ? o->d_out : nullptr;
     if (n_bytes) *n_bytes = o ? o->n_out : 0;
 }
 
@@ -383,18 +377,11 @@ extern "C" void pp_bam_out_counts(const pp_bam_out *o, uint64_t *pass_count, uin
 }
 
 extern "C" int pp_bam_out_kernel_ms(const pp_bam_out *o, float *ms) {
-    if (!o || !ms) return PP_ERR_ARG;
-    if (!o->timed) return o->ctx->fail(PP_ERR_ARG, "pp_bam_out_kernel_ms: the context had no profiling on when the records were tagged (pp_ctx_set_profiling)");
-    *ms = o->ms[0] + o->ms[1] + o->ms[2];
-    return PP_OK;
+    return o ? o->t.total(o->ctx, "pp_bam_out_kernel_ms", "when the records were tagged", ms) : PP_ERR_ARG;
 }
 
 // (internal hook, not part of the header: tools/bam_tag_timing.py) the same time by stage: pass A | the scans | pass B
-extern "C" int pp_bam_out_stage_ms_(const pp_bam_out *o, float *ms3) {
-    if (!o || !ms3 || !o->timed) return PP_ERR_ARG;
-    for (int i = 0; i < 3; i++) ms3[i] = o->ms[i];
-    return PP_OK;
-}
+extern "C" int pp_bam_out_stage_ms_(const pp_bam_out *o, float *ms3) { return o ? o->t.stages(ms3) : PP_ERR_ARG; }
 
 // a file in device memory to `path`, in slices through a host buffer (pp_bam_out_write, pp_bgzf_out_write); a path that cannot be
 // created or written: as pp_filter_write
@@ -442,9 +429,7 @@ extern "C" int pp_bam_tagged(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes
     hipStream_t st = ctx->stream;
     const u32 n = (u32)n_rec;
 
-    pp_bam_out *P = new pp_bam_out;
-    P->ctx = ctx;
-    std::unique_ptr<pp_bam_out, void (*)(pp_bam_out *)> guard(P, pp_bam_out_free);  // (every early return releases what was made so far)
+    std::unique_ptr<pp_bam_out> P(new pp_bam_out(ctx));
     CallScratch T;  // the copy of host bytes and the per-record arrays: released when the call returns
     StageTimer timer(ctx, ctx->profiling != 0);
     int rc;
@@ -516,18 +501,14 @@ extern "C" int pp_bam_tagged(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes
     P->n_blocks = n_blocks;
     P->pass_count = n_al - n_fail;
     P->fail_count = n_fail;
-    PP_HIPCHK(ctx, hipMalloc(&P->d_out, (size_t)P->n_out));
+    if ((rc = P->alloc(P->d_out, (size_t)P->n_out))) return rc;
     if ((rc = timer.begin(2))) return rc;
     hipLaunchKernelGGL(k_tag_frame, dim3((unsigned)(n_blocks + 1u)), dim3(TAG_BLOCK), 0, st,
                        FrameArgs{d_bytes, (u64)n_bytes, d_rec_off, (const u64 *)d_start, n, u_total, n_blocks, (u8 *)P->d_out});
     if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     PP_HIPCHK(ctx, hipStreamSynchronize(st));  // host inputs may be released, the scratch goes away
-    if (timer.on) {
-        if ((rc = timer.sums(P->ms, 3))) return rc;
-        P->timed = true;
-    }
-    guard.release();
-    *out = P;
+    if ((rc = P->t.take(timer))) return rc;
+    *out = P.release();
     return PP_OK;
 }

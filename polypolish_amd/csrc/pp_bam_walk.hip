@@ -31,13 +31,12 @@
 
 extern "C" char *pp_bam_msg_buf_(size_t *cap);  // pp_bam.hip: the per-thread message behind pp_bam_last_error()
 
-struct pp_bam_offs {
-    pp_ctx *ctx = nullptr;
-    void *d_off = nullptr;  // DEVICE: n_rec offsets
+struct pp_bam_offs : DevOwner {
+    using DevOwner::DevOwner;
+    u64 *d_off = nullptr;  // DEVICE: n_rec offsets
     uint64_t n_rec = 0, end = 0;
     uint64_t stats[4] = {0, 0, 0, 0};  // along the true chain: chunks on it | entered through a zone | on the slow path | passed through
-    bool timed = false;
-    float ms[3] = {0.f, 0.f, 0.f};  // the chunk tables | groups, chain and replay | scan and offsets
+    StageMs<3> t;          // the chunk tables | groups, chain and replay | scan and offsets
 };
 
 namespace {
@@ -262,31 +261,19 @@ int broken(pp_ctx *ctx, u32 kind, u64 n, u64 at, u32 bs, u64 n_bytes, uint64_t *
 
 }  // namespace
 
-extern "C" void pp_bam_offs_free(pp_bam_offs *o) {
-    if (!o) return;
-    if (o->ctx) (void)hipSetDevice(o->ctx->device);
-    if (o->d_off) (void)hipFree(o->d_off);
-    delete o;
-}
+extern "C" void pp_bam_offs_free(pp_bam_offs *o) { delete o; }
 
 extern "C" const uint64_t *pp_bam_offs_dev(const pp_bam_offs *o) { return o ? (const uint64_t *)o->d_off : nullptr; }
 
 extern "C" uint64_t pp_bam_offs_count(const pp_bam_offs *o) { return o ? o->n_rec : 0; }
 
 extern "C" int pp_bam_offs_kernel_ms(const pp_bam_offs *o, float *ms) {
-    if (!o || !ms) return PP_ERR_ARG;
-    if (!o->timed) return o->ctx->fail(PP_ERR_ARG, "pp_bam_offs_kernel_ms: the context had no profiling on when the chain was walked (pp_ctx_set_profiling)");
-    *ms = o->ms[0] + o->ms[1] + o->ms[2];
-    return PP_OK;
+    return o ? o->t.total(o->ctx, "pp_bam_offs_kernel_ms", "when the chain was walked", ms) : PP_ERR_ARG;
 }
 
 // (internal hooks, not part of the header: the tests and tools/bam_walk_timing.py) the same time by stage: the chunk tables | groups,
 // chain and replay | scan and offsets; the bytes per chunk, the offsets of a zone, the chunks per group; the path counts
-extern "C" int pp_bam_offs_stage_ms_(const pp_bam_offs *o, float *ms3) {
-    if (!o || !ms3 || !o->timed) return PP_ERR_ARG;
-    for (int i = 0; i < 3; i++) ms3[i] = o->ms[i];
-    return PP_OK;
-}
+extern "C" int pp_bam_offs_stage_ms_(const pp_bam_offs *o, float *ms3) { return o ? o->t.stages(ms3) : PP_ERR_ARG; }
 
 extern "C" void pp_bam_walk_geometry_(uint32_t *chunk, uint32_t *zone, uint32_t *group) {
     if (chunk) *chunk = WALK_C;
@@ -318,19 +305,16 @@ extern "C" int pp_bam_walk_device(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_
     PP_HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
 
-    pp_bam_offs *P = new pp_bam_offs;
-    P->ctx = ctx;
-    std::unique_ptr<pp_bam_offs, void (*)(pp_bam_offs *)> guard(P, pp_bam_offs_free);  // (every early return releases what was made so far)
+    std::unique_ptr<pp_bam_offs> P(new pp_bam_offs(ctx));
     CallScratch T;  // the copy of host bytes and the tables: released when the call returns
     StageTimer timer(ctx, ctx->profiling != 0);
     int rc;
-    if (from == n_bytes) {  // nothing to walk: no records
-        PP_HIPCHK(ctx, hipMalloc(&P->d_off, 16));
+    if (from == n_bytes) {  // nothing to walk: no records, and with profiling no time
+        if ((rc = P->alloc(P->d_off, 0))) return rc;
         PP_HIPCHK(ctx, hipStreamSynchronize(st));
         P->end = from;
-        P->timed = timer.on;
-        guard.release();
-        *out = P;
+        if ((rc = P->t.take(timer))) return rc;
+        *out = P.release();
         return PP_OK;
     }
     WalkSrc S{};
@@ -370,7 +354,7 @@ extern "C" int pp_bam_walk_device(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_
     if (n >= 0xFFFFFFFFull) return ctx->fail(PP_ERR_LIMIT, "more than 2^32-1 alignments in one batch");
 
     // ---- every chunk's entry and count, the offsets ----
-    PP_HIPCHK(ctx, hipMalloc(&P->d_off, n ? (size_t)n * 8 : 16));
+    if ((rc = P->alloc(P->d_off, (size_t)n))) return rc;
     if ((rc = timer.begin(1))) return rc;
     hipLaunchKernelGGL(k_bamwalk_replay, dim3((n_groups + 63u) / 64u), dim3(64), 0, st, S, n_groups, (const u64 *)d_gentry, (u64 *)d_centry, (u32 *)d_ccnt);
     if ((rc = timer.end()) || (rc = timer.begin(2))) return rc;
@@ -380,15 +364,11 @@ extern "C" int pp_bam_walk_device(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_
     if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     PP_HIPCHK(ctx, hipStreamSynchronize(st));  // host bytes may be released, the scratch goes away
-    if (timer.on) {
-        if ((rc = timer.sums(P->ms, 3))) return rc;
-        P->timed = true;
-    }
+    if ((rc = P->t.take(timer))) return rc;
     P->n_rec = n;
     P->end = res[R_END];
     for (int i = 0; i < 4; i++) P->stats[i] = res[R_STATS + i];
-    guard.release();
-    *out = P;
+    *out = P.release();
     *n_rec = n;
     *end = res[R_END];
     return PP_OK;

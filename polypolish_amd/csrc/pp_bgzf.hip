@@ -30,13 +30,12 @@
 
 extern "C" char *pp_bam_msg_buf_(size_t *cap);  // pp_bam.hip: the per-thread message behind pp_bam_last_error()
 
-struct pp_bgzf {
-    pp_ctx *ctx = nullptr;
-    void *d_out = nullptr;      // DEVICE: the inflated bytes
+struct pp_bgzf : DevOwner {
+    using DevOwner::DevOwner;
+    u8 *d_out = nullptr;          // DEVICE: the inflated bytes
     uint64_t n_out = 0;
     pp_bam_offs *offs = nullptr;  // pp_bgzf_bam_walk's record offsets (DEVICE)
-    bool timed = false;
-    float ms[3] = {0.f, 0.f, 0.f};  // header, scan and inflate | CRC | the kernels of pp_bgzf_bam_walk
+    StageMs<3> t;                 // header, scan and inflate | CRC | the kernels of pp_bgzf_bam_walk
 };
 
 namespace {
@@ -436,33 +435,23 @@ extern "C" int pp_bgzf_walk(const uint8_t *bytes, uint64_t n_bytes, uint64_t fro
 }
 
 extern "C" void pp_bgzf_free(pp_bgzf *z) {
-    if (!z) return;
-    if (z->ctx) (void)hipSetDevice(z->ctx->device);
-    if (z->d_out) (void)hipFree(z->d_out);
-    pp_bam_offs_free(z->offs);
+    if (z) pp_bam_offs_free(z->offs);
     delete z;
 }
 
 extern "C" void pp_bgzf_bytes(const pp_bgzf *z, const uint8_t **dev, uint64_t *n_bytes) {
-    if (dev) *dev = z ? (const uint8_t *)z->d_out : nullptr;
+    if (dev) *dev = z ? z->d_out : nullptr;
     if (n_bytes) *n_bytes = z ? z->n_out : 0;
 }
 
 extern "C" const uint64_t *pp_bgzf_rec_off(const pp_bgzf *z) { return z ? pp_bam_offs_dev(z->offs) : nullptr; }
 
 extern "C" int pp_bgzf_kernel_ms(const pp_bgzf *z, float *ms) {
-    if (!z || !ms) return PP_ERR_ARG;
-    if (!z->timed) return z->ctx->fail(PP_ERR_ARG, "pp_bgzf_kernel_ms: the context had no profiling on when the blocks were inflated (pp_ctx_set_profiling)");
-    *ms = z->ms[0] + z->ms[1] + z->ms[2];
-    return PP_OK;
+    return z ? z->t.total(z->ctx, "pp_bgzf_kernel_ms", "when the blocks were inflated", ms) : PP_ERR_ARG;
 }
 
 // (internal hook, not part of the header: tools/bgzf_timing.py) the same time by stage: header, scan and inflate | CRC | pp_bgzf_bam_walk's kernels
-extern "C" int pp_bgzf_stage_ms_(const pp_bgzf *z, float *ms3) {
-    if (!z || !ms3 || !z->timed) return PP_ERR_ARG;
-    for (int i = 0; i < 3; i++) ms3[i] = z->ms[i];
-    return PP_OK;
-}
+extern "C" int pp_bgzf_stage_ms_(const pp_bgzf *z, float *ms3) { return z ? z->t.stages(ms3) : PP_ERR_ARG; }
 
 extern "C" int pp_bgzf_inflate(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, const uint64_t *blk_off, uint64_t n_blk, int mem,
                                pp_bgzf **out, uint64_t *bad_block) {
@@ -493,18 +482,15 @@ extern "C" int pp_bgzf_inflate(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_byt
     hipStream_t st = ctx->stream;
     const u32 n = (u32)n_blk;
 
-    pp_bgzf *Z = new pp_bgzf;
-    Z->ctx = ctx;
-    std::unique_ptr<pp_bgzf, void (*)(pp_bgzf *)> guard(Z, pp_bgzf_free);  // (every early return releases what was made so far)
+    std::unique_ptr<pp_bgzf> Z(new pp_bgzf(ctx));  // (no offsets yet: plain delete on an early return)
     CallScratch T;  // the compressed copy and the per-block arrays: released when the call returns
     StageTimer timer(ctx, ctx->profiling != 0);
     int rc;
-    if (n == 0) {  // no blocks: an empty object
-        PP_HIPCHK(ctx, hipMalloc(&Z->d_out, 16));
+    if (n == 0) {  // no blocks: an empty object, and with profiling no time
+        if ((rc = Z->alloc(Z->d_out, 0))) return rc;
         PP_HIPCHK(ctx, hipStreamSynchronize(st));
-        if (timer.on) Z->timed = true;
-        guard.release();
-        *out = Z;
+        if ((rc = Z->t.take(timer))) return rc;
+        *out = Z.release();
         return PP_OK;
     }
     const u8 *d_bytes = nullptr;
@@ -533,7 +519,7 @@ extern "C" int pp_bgzf_inflate(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_byt
     if ((rc = fetch(ctx, d_status, &head_status)) || (rc = fetch(ctx, (const u64 *)d_out_off + n, &total))) return rc;
     // a block with a header defect stops the run in front of it: a stream defect in an earlier block is the first one
     const u32 n_run = head_status != ~0ull ? (u32)(head_status >> 8) : n;
-    PP_HIPCHK(ctx, hipMalloc(&Z->d_out, total ? (size_t)total : 16));
+    if ((rc = Z->alloc(Z->d_out, (size_t)total))) return rc;
     Z->n_out = total;
 
     // ---- the streams, the checksums ----
@@ -556,13 +542,8 @@ extern "C" int pp_bgzf_inflate(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_byt
         if (bad_block) *bad_block = status >> 8;
         return ctx->fail(PP_ERR_ARG, "pp_bgzf_inflate: block %llu %s", (unsigned long long)(status >> 8), defect_text((u32)(status & 0xFFu)));
     }
-    if (timer.on) {
-        if ((rc = timer.sums(Z->ms, 2))) return rc;
-        Z->ms[2] = 0.f;
-        Z->timed = true;
-    }
-    guard.release();
-    *out = Z;
+    if ((rc = Z->t.take(timer))) return rc;  // (stage 2 has no span here: zero)
+    *out = Z.release();
     return PP_OK;
 }
 
@@ -581,6 +562,6 @@ extern "C" int pp_bgzf_bam_walk(pp_bgzf *z, uint64_t from, uint64_t *n_rec, uint
         return rc == PP_ERR_ARG && msg[0] ? ctx->fail(rc, "pp_bgzf_bam_walk: %s", msg) : rc;  // (a chain that breaks: pp_bam_walk's words)
     }
     float ms = 0.f;
-    if (z->timed) z->ms[2] = ctx->profiling && pp_bam_offs_kernel_ms(z->offs, &ms) == PP_OK ? ms : 0.f;
+    if (z->t.timed) z->t.ms[2] = ctx->profiling && pp_bam_offs_kernel_ms(z->offs, &ms) == PP_OK ? ms : 0.f;
     return PP_OK;
 }

@@ -33,14 +33,13 @@
 #include "pp_crc.h"
 #include "pp_dev.h"
 
-struct pp_bgzf_out {
-    pp_ctx *ctx = nullptr;
-    void *d_out = nullptr;      // DEVICE: the file
-    void *d_blk_off = nullptr;  // DEVICE: n_blk + 1 offsets
+struct pp_bgzf_out : DevOwner {
+    using DevOwner::DevOwner;
+    u8 *d_out = nullptr;       // DEVICE: the file
+    u64 *d_blk_off = nullptr;  // DEVICE: n_blk + 1 offsets
     uint64_t n_out = 0, n_blk = 0;
     uint64_t counts[3] = {0, 0, 0};  // stored | fixed | dynamic
-    bool timed = false;
-    float ms[3] = {0.f, 0.f, 0.f};  // the pieces | the scan | the placing
+    StageMs<3> t;              // the pieces | the scan | the placing
 };
 
 namespace {
@@ -272,9 +271,7 @@ __global__ __launch_bounds__(DF_BLOCK) void k_df_place(const u8 *__restrict__ tm
 // the pieces at base + p * stride + head, `total` bytes in all, to an object
 int deflate_pieces(pp_ctx *ctx, const u8 *base, u64 stride, u64 head, u64 total, pp_bgzf_out **out) {
     hipStream_t st = ctx->stream;
-    pp_bgzf_out *P = new pp_bgzf_out;
-    P->ctx = ctx;
-    std::unique_ptr<pp_bgzf_out, void (*)(pp_bgzf_out *)> guard(P, pp_bgzf_out_free);  // (every early return releases what was made so far)
+    std::unique_ptr<pp_bgzf_out> P(new pp_bgzf_out(ctx));
     CallScratch T;
     StageTimer timer(ctx, ctx->profiling != 0);
     int rc;
@@ -284,7 +281,7 @@ int deflate_pieces(pp_ctx *ctx, const u8 *base, u64 stride, u64 head, u64 total,
     if ((rc = T.get(ctx, &d_tok, (size_t)grid * PAY * 4)) || (rc = T.get(ctx, &d_tmp, (size_t)n_pieces * SLOT)) || (rc = T.get(ctx, &d_meta, (size_t)n_pieces * 16)) ||
         (rc = T.get(ctx, &d_size, (size_t)n_pieces * 8)) || (rc = T.get(ctx, &d_counts, 24)))
         return rc;
-    PP_HIPCHK(ctx, hipMalloc(&P->d_blk_off, ((size_t)n_pieces + 1) * 8));
+    if ((rc = P->alloc(P->d_blk_off, (size_t)n_pieces + 1))) return rc;
     PP_HIPCHK(ctx, hipMemsetAsync(d_counts, 0, 24, st));
     if ((rc = timer.begin(0))) return rc;
     if (n_pieces)
@@ -298,34 +295,24 @@ int deflate_pieces(pp_ctx *ctx, const u8 *base, u64 stride, u64 head, u64 total,
     if ((rc = fetch(ctx, (const u64 *)P->d_blk_off + n_pieces, &eof_at)) || (rc = fetch(ctx, d_counts, P->counts, 3))) return rc;
     P->n_blk = n_pieces;
     P->n_out = eof_at + hb::EOF_SIZE;
-    PP_HIPCHK(ctx, hipMalloc(&P->d_out, (size_t)P->n_out));
+    if ((rc = P->alloc(P->d_out, (size_t)P->n_out))) return rc;
     if ((rc = timer.begin(2))) return rc;
     hipLaunchKernelGGL(k_df_place, dim3((unsigned)(n_pieces + 1u)), dim3(DF_BLOCK), 0, st, (const u8 *)d_tmp, (const uint4 *)d_meta, (const u64 *)P->d_blk_off,
                        n_pieces, (u8 *)P->d_out);
     if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     PP_HIPCHK(ctx, hipStreamSynchronize(st));  // host inputs may be released, the scratch goes away
-    if (timer.on) {
-        if ((rc = timer.sums(P->ms, 3))) return rc;
-        P->timed = true;
-    }
-    guard.release();
-    *out = P;
+    if ((rc = P->t.take(timer))) return rc;
+    *out = P.release();
     return PP_OK;
 }
 
 }  // namespace
 
-extern "C" void pp_bgzf_out_free(pp_bgzf_out *o) {
-    if (!o) return;
-    if (o->ctx) (void)hipSetDevice(o->ctx->device);
-    if (o->d_out) (void)hipFree(o->d_out);
-    if (o->d_blk_off) (void)hipFree(o->d_blk_off);
-    delete o;
-}
+extern "C" void pp_bgzf_out_free(pp_bgzf_out *o) { delete o; }
 
 extern "C" void pp_bgzf_out_bytes(const pp_bgzf_out *o, const uint8_t **dev, uint64_t *n_bytes) {
-    if (dev) *dev = o ? (const uint8_t *)o->d_out : nullptr;
+    if (dev) *dev = o ? o->d_out : nullptr;
     if (n_bytes) *n_bytes = o ? o->n_out : 0;
 }
 
@@ -341,18 +328,11 @@ extern "C" void pp_bgzf_out_counts(const pp_bgzf_out *o, uint64_t *stored, uint6
 }
 
 extern "C" int pp_bgzf_out_kernel_ms(const pp_bgzf_out *o, float *ms) {
-    if (!o || !ms) return PP_ERR_ARG;
-    if (!o->timed) return o->ctx->fail(PP_ERR_ARG, "pp_bgzf_out_kernel_ms: the context had no profiling on when the bytes were compressed (pp_ctx_set_profiling)");
-    *ms = o->ms[0] + o->ms[1] + o->ms[2];
-    return PP_OK;
+    return o ? o->t.total(o->ctx, "pp_bgzf_out_kernel_ms", "when the bytes were compressed", ms) : PP_ERR_ARG;
 }
 
 // (internal hook, not part of the header: tools/bgzf_deflate_timing.py) the same time by stage: the pieces | the scan | the placing
-extern "C" int pp_bgzf_out_stage_ms_(const pp_bgzf_out *o, float *ms3) {
-    if (!o || !ms3 || !o->timed) return PP_ERR_ARG;
-    for (int i = 0; i < 3; i++) ms3[i] = o->ms[i];
-    return PP_OK;
-}
+extern "C" int pp_bgzf_out_stage_ms_(const pp_bgzf_out *o, float *ms3) { return o ? o->t.stages(ms3) : PP_ERR_ARG; }
 
 extern "C" int pp_bgzf_out_write(const pp_bgzf_out *o, const char *path) {
     if (!o || !o->ctx) return PP_ERR_ARG;

@@ -1,9 +1,11 @@
 // pp_dev.h -- what the device translation units share that is not text: the typedefs, the range and room arithmetic of a batch,
-// the SEQ byte codes, the workgroup scans over the DPP wave scan of pp_wave.h, the multi-block exclusive scan, and the host
-// plumbing of one call (read-back, scratch, upload, stage timing).  Included by pp_devtext.h (the SAM tokenizers' text utilities)
-// and directly by the record chain: pp_bgzf.hip, pp_bam.hip, pp_names.hip, pp_filter_rec.hip and pp_regroup.hip (through pp_filter_group.h), pp_gate.hip and
-// pp_prepare.hip.  Everything lives in an anonymous namespace: each translation unit gets its own copies, and of the kernels that
-// are templates only those it launches.
+// the SEQ byte codes, the workgroup scans over the DPP wave scan of pp_wave.h, the multi-block exclusive scan, the host
+// plumbing of one call (read-back, scratch, upload, stage timing), and the host side of the record chain's owned objects (the
+// owner of their device memory, their stage times, the named arrays of a batch, a caller's batch checked and uploaded).  Included
+// by pp_devtext.h (the SAM tokenizers' text utilities) and directly by the record chain: pp_bgzf.hip, pp_bgzf_deflate.hip,
+// pp_bam.hip, pp_bam_walk.hip, pp_bam_out.hip, pp_names.hip, pp_filter_rec.hip and pp_regroup.hip (through pp_filter_group.h),
+// pp_gate.hip and pp_prepare.hip.  Everything lives in an anonymous namespace: each translation unit gets its own copies, and of
+// the kernels that are templates only those it launches.
 #pragma once
 #include "pp_internal.h"
 #include "pp_wave.h"
@@ -221,12 +223,57 @@ int fetch(pp_ctx *ctx, const void *dev, T *host, size_t n = 1) {
 
 struct CallScratch {  // device memory of one call, released when it returns
     std::vector<void *> p;
+    CallScratch() = default;
+    CallScratch(const CallScratch &) = delete;
+    CallScratch &operator=(const CallScratch &) = delete;
     ~CallScratch() { for (void *q : p) (void)hipFree(q); }
     int get(pp_ctx *ctx, void **out, size_t bytes) {
         *out = nullptr;
-        PP_HIPCHK(ctx, hipMalloc(out, bytes ? bytes : 16));
+        PP_HIPCHK(ctx, hipMalloc(out, std::max<size_t>(bytes, 16)));
         p.push_back(*out);
         return PP_OK;
+    }
+};
+
+// A call's device memory out of grow-only buffers of the context (pp_ctx::f_rec, g_rec), handed out in the order of the requests:
+// the same request of the next call finds its buffer again.  Nothing in them outlives the call.  [0], [1]: scan_u32's block sums
+struct CtxScratch {
+    pp_ctx *ctx;
+    pp::DevBuf *buf;
+    size_t n_buf, k = 2;
+    const char *who;
+    template <size_t N>
+    CtxScratch(pp_ctx *c, pp::DevBuf (&b)[N], const char *w) : ctx(c), buf(b), n_buf(N), who(w) {}
+    pp::DevBuf &sums() { return buf[0]; }
+    pp::DevBuf &sums_off() { return buf[1]; }
+    int get(pp_ctx *, void **out, size_t bytes) {
+        *out = nullptr;
+        if (k >= n_buf) return ctx->fail(PP_ERR_HIP, "%s: out of buffer slots", who);
+        if (int rc = pp::dev_ensure(ctx, buf[k], std::max<size_t>(bytes, 16))) return rc;
+        *out = buf[k++].p;
+        return PP_OK;
+    }
+};
+
+// The base of the record chain's C objects: the context and the device memory the object owns, freed with it.  A creator holds the
+// object in a std::unique_ptr until it hands it out: every early return frees what was made so far.  (Its get() is CallScratch's:
+// on_device uploads into the object.)
+struct DevOwner : CallScratch {
+    pp_ctx *const ctx;
+    explicit DevOwner(pp_ctx *c) : ctx(c) {}
+    ~DevOwner() { (void)hipSetDevice(ctx->device); }  // (in front of the base's hipFree)
+    template <class T>
+    int alloc(T *&a, size_t count) {
+        void *q;
+        const int rc = get(ctx, &q, count * sizeof(T));
+        a = (T *)q;
+        return rc;
+    }
+    void release(const void *a) {  // one allocation early; an array that is not the object's is left alone
+        const auto it = std::find(p.begin(), p.end(), a);
+        if (it == p.end()) return;
+        (void)hipFree(*it);
+        p.erase(it);
     }
 };
 
@@ -281,5 +328,127 @@ struct StageTimer {
         return PP_OK;
     }
 };
+
+// The time of an object's kernels by stage, kept when the context had profiling on.
+template <int K>
+struct StageMs {
+    bool timed = false;
+    float ms[K] = {};
+    int take(StageTimer &t) {  // (once the stream is synchronised)
+        if (!t.on) return PP_OK;
+        if (int rc = t.sums(ms, K)) return rc;
+        timed = true;
+        return PP_OK;
+    }
+    // pp_X_kernel_ms: the stages from `first` on; `when` finishes the sentence of an object made without profiling
+    int total(pp_ctx *ctx, const char *who, const char *when, float *out, int first = 0) const {
+        if (!out) return PP_ERR_ARG;
+        if (!timed) return ctx->fail(PP_ERR_ARG, "%s: the context had no profiling on %s (pp_ctx_set_profiling)", who, when);
+        *out = 0.f;
+        for (int i = first; i < K; i++) *out += ms[i];
+        return PP_OK;
+    }
+    int stages(float *out) const {  // pp_X_stage_ms_
+        if (!out || !timed) return PP_ERR_ARG;
+        std::copy(ms, ms + K, out);
+        return PP_OK;
+    }
+};
+
+// ---- the arrays of a batch: an object's own, and a caller's made device-readable -----------------------------
+struct RawArrays {  // pp_raw_batch
+    uint16_t *flag = nullptr;
+    u64 *read_id = nullptr, *seq_off = nullptr, *cig_off = nullptr;
+    u32 *contig = nullptr, *ref_start = nullptr, *nm = nullptr, *seq_len = nullptr, *n_cig = nullptr, *cigar = nullptr;
+    u8 *seq = nullptr;
+    int alloc_records(DevOwner &o, size_t n) {  // the nine arrays per record
+        int rc;
+        if ((rc = o.alloc(flag, n)) || (rc = o.alloc(read_id, n)) || (rc = o.alloc(contig, n)) || (rc = o.alloc(ref_start, n)) ||
+            (rc = o.alloc(nm, n)) || (rc = o.alloc(seq_off, n)) || (rc = o.alloc(seq_len, n)) || (rc = o.alloc(cig_off, n)))
+            return rc;
+        return o.alloc(n_cig, n);
+    }
+    pp_raw_batch view(u64 n, u64 seq_bytes, u64 n_cig_total) const {
+        return pp_raw_batch{n, flag, (const uint64_t *)read_id, contig, ref_start, nm, (const uint64_t *)seq_off, seq_len,
+                            (const uint64_t *)cig_off, n_cig, seq, seq_bytes, cigar, n_cig_total};
+    }
+};
+
+struct AlnArrays {  // pp_aln_batch without its mirrors
+    u32 *contig = nullptr, *ref_start = nullptr, *k = nullptr, *seq_len = nullptr, *n_cig = nullptr, *cigar = nullptr;
+    u64 *seq_off = nullptr, *cig_off = nullptr;
+    u8 *seq = nullptr;
+    int alloc_records(DevOwner &o, size_t n) {  // the seven arrays per record
+        int rc;
+        if ((rc = o.alloc(contig, n)) || (rc = o.alloc(ref_start, n)) || (rc = o.alloc(k, n)) || (rc = o.alloc(seq_off, n)) ||
+            (rc = o.alloc(seq_len, n)) || (rc = o.alloc(cig_off, n)))
+            return rc;
+        return o.alloc(n_cig, n);
+    }
+    pp_aln_batch view(u64 n, u64 seq_bytes, u64 n_cig_total) const {
+        pp_aln_batch V{};
+        V.n_aln = n;
+        V.contig = contig; V.ref_start = ref_start; V.k = k; V.seq_off = (const uint64_t *)seq_off; V.seq_len = seq_len;
+        V.cig_off = (const uint64_t *)cig_off; V.n_cig = n_cig; V.seq = seq; V.seq_bytes = seq_bytes; V.cigar = cigar;
+        V.n_cig_total = n_cig_total;
+        return V;
+    }
+};
+
+// What a callee reads of a caller's raw batch beyond flag, read_id, contig, ref_start, cig_off and n_cig
+enum : u32 { RAW_READS = 1 /* nm seq_off seq_len */, RAW_SEQ = 2, RAW_CIGAR = 4, RAW_ALL = 7, RAW_SEQ_LIMIT = 8 /* refuse 2^40 SEQ bytes */ };
+
+// the refusals every taker of a raw batch shares, in the order and with the sentences they always had
+int raw_check(pp_ctx *ctx, const char *who, const pp_raw_batch *raw, int mem, u32 which) {
+    if (mem != PP_MEM_HOST && mem != PP_MEM_DEVICE)
+        return ctx->fail(PP_ERR_ARG, "%s: the batch must be host memory or memory of the context's device", who);
+    if (raw->n_rec >= 0xFFFFFFFFull) return ctx->fail(PP_ERR_LIMIT, "more than 2^32-1 alignments in one batch");
+    if ((which & RAW_SEQ_LIMIT) && raw->seq_bytes >= (1ull << 40)) return ctx->fail(PP_ERR_LIMIT, "more than 2^40 SEQ bytes in one batch");
+    const bool reads = (which & RAW_READS) != 0;
+    if (raw->n_rec && (!raw->flag || !raw->read_id || !raw->contig || !raw->ref_start || !raw->cig_off || !raw->n_cig ||
+                       (reads && (!raw->nm || !raw->seq_off || !raw->seq_len)) || ((which & RAW_SEQ) && raw->seq_bytes && !raw->seq) ||
+                       ((which & RAW_CIGAR) && raw->n_cig_total && !raw->cigar)))
+        return ctx->fail(PP_ERR_ARG, "%s: null array in a non-empty batch", who);
+    return PP_OK;
+}
+
+// *dev = the batch with the arrays of `which` where the kernels can read them (on_device: uploads go to `scratch`), the others
+// null.  The order of the uploads is pp_filter_records's: its scratch is the context's, found again by that order.
+template <class S>
+int raw_on_device(pp_ctx *ctx, S &scratch, int mem, const pp_raw_batch *raw, u32 which, pp_raw_batch *dev) {
+    const size_t n = (size_t)raw->n_rec;
+    *dev = pp_raw_batch{};
+    dev->n_rec = raw->n_rec;
+    dev->seq_bytes = raw->seq_bytes;
+    dev->n_cig_total = raw->n_cig_total;
+    int rc;
+    if ((rc = on_device(ctx, scratch, mem, raw->flag, n, &dev->flag)) || (rc = on_device(ctx, scratch, mem, raw->read_id, n, &dev->read_id)) ||
+        (rc = on_device(ctx, scratch, mem, raw->cig_off, n, &dev->cig_off)) || (rc = on_device(ctx, scratch, mem, raw->contig, n, &dev->contig)) ||
+        (rc = on_device(ctx, scratch, mem, raw->ref_start, n, &dev->ref_start)) || (rc = on_device(ctx, scratch, mem, raw->n_cig, n, &dev->n_cig)))
+        return rc;
+    if ((which & RAW_READS) && ((rc = on_device(ctx, scratch, mem, raw->nm, n, &dev->nm)) || (rc = on_device(ctx, scratch, mem, raw->seq_off, n, &dev->seq_off)) ||
+                                (rc = on_device(ctx, scratch, mem, raw->seq_len, n, &dev->seq_len))))
+        return rc;
+    if ((which & RAW_SEQ) && (rc = on_device(ctx, scratch, mem, raw->seq, (size_t)raw->seq_bytes, &dev->seq))) return rc;
+    if ((which & RAW_CIGAR) && (rc = on_device(ctx, scratch, mem, raw->cigar, (size_t)raw->n_cig_total, &dev->cigar))) return rc;
+    return PP_OK;
+}
+
+// ... and the nine arrays of a caller's pp_aln_batch (the mirrors are not read)
+template <class S>
+int aln_on_device(pp_ctx *ctx, S &scratch, int mem, const pp_aln_batch *b, pp_aln_batch *dev) {
+    const size_t n = (size_t)b->n_aln;
+    *dev = pp_aln_batch{};
+    dev->n_aln = b->n_aln;
+    dev->seq_bytes = b->seq_bytes;
+    dev->n_cig_total = b->n_cig_total;
+    int rc;
+    if ((rc = on_device(ctx, scratch, mem, b->contig, n, &dev->contig)) || (rc = on_device(ctx, scratch, mem, b->ref_start, n, &dev->ref_start)) ||
+        (rc = on_device(ctx, scratch, mem, b->k, n, &dev->k)) || (rc = on_device(ctx, scratch, mem, b->seq_off, n, &dev->seq_off)) ||
+        (rc = on_device(ctx, scratch, mem, b->seq_len, n, &dev->seq_len)) || (rc = on_device(ctx, scratch, mem, b->cig_off, n, &dev->cig_off)) ||
+        (rc = on_device(ctx, scratch, mem, b->n_cig, n, &dev->n_cig)) || (rc = on_device(ctx, scratch, mem, b->seq, (size_t)b->seq_bytes, &dev->seq)))
+        return rc;
+    return on_device(ctx, scratch, mem, b->cigar, (size_t)b->n_cig_total, &dev->cigar);
+}
 
 }  // namespace

@@ -5,6 +5,8 @@
 #pragma once
 #include "pp_dev.h"
 
+#include <type_traits>
+
 namespace {
 
 constexpr u32 NL_BLOCK = 1024 * 64;  // bytes of text per block of the newline kernels (64 per thread)
@@ -121,6 +123,13 @@ constexpr u32 TOK_STAGE_S = 16 * 1024 - 64, TOK_STAGE_M = 26 * 1024 - 64, TOK_ST
 inline u32 tok_stage_for(u64 text_bytes, u64 n_lines) {
     const u64 need = n_lines ? (text_bytes / n_lines + 1) * 64 * 115 / 100 : 0;
     return need <= TOK_STAGE_S ? TOK_STAGE_S : (need <= TOK_STAGE_M ? TOK_STAGE_M : TOK_STAGE_L);
+}
+// launch(stage) with tok_stage_for's pick as a constant (decltype(stage)::value): a kernel over stage_wave_lines comes in the three sizes
+template <class F>
+void with_stage(u32 stage_bytes, F launch) {
+    if (stage_bytes == TOK_STAGE_S) launch(std::integral_constant<u32, TOK_STAGE_S>{});
+    else if (stage_bytes == TOK_STAGE_M) launch(std::integral_constant<u32, TOK_STAGE_M>{});
+    else launch(std::integral_constant<u32, TOK_STAGE_L>{});
 }
 
 template <u32 TOK_STAGE>

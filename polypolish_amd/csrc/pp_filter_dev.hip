@@ -277,16 +277,10 @@ extern "C" int pp_filter_load_device(pp_ctx *ctx, const char *in1, const char *i
             ENS(X.d_namelen, nl * 4); ENS(X.d_refoff, nl * 4); ENS(X.d_reflen, nl * 4); ENS(X.d_recofline, (nl + 1) * 4);
             FqLines O{(u32 *)X.d_isaln.p, (u32 *)X.d_flag.p, (u32 *)X.d_start.p, (u32 *)X.d_namelen.p, (u32 *)X.d_refoff.p,
                       (u32 *)X.d_reflen.p, (u64 *)X.d_end.p};
-            {
-                const u32 stage_bytes = tok_stage_for(size, nl);
-                const dim3 grid((unsigned)((nl + 63) / 64));
-                if (stage_bytes == TOK_STAGE_S) hipLaunchKernelGGL(k_fq_parse<TOK_STAGE_S>, grid, dim3(64), 0, st, d_text, size, (const u64 *)X.d_nl.p,
-                               X.n_nl, nl, O, d_status);
-                else if (stage_bytes == TOK_STAGE_M) hipLaunchKernelGGL(k_fq_parse<TOK_STAGE_M>, grid, dim3(64), 0, st, d_text, size, (const u64 *)X.d_nl.p,
-                               X.n_nl, nl, O, d_status);
-                else hipLaunchKernelGGL(k_fq_parse<TOK_STAGE_L>, grid, dim3(64), 0, st, d_text, size, (const u64 *)X.d_nl.p,
-                               X.n_nl, nl, O, d_status);
-            }
+            with_stage(tok_stage_for(size, nl), [&](auto stage) {
+                hipLaunchKernelGGL(k_fq_parse<decltype(stage)::value>, dim3((unsigned)((nl + 63) / 64)), dim3(64), 0, st, d_text, size,
+                                   (const u64 *)X.d_nl.p, X.n_nl, nl, O, d_status);
+            });
             if ((rc = scan_u32<u32>(ctx, D->d_sums, D->d_sumsoff, (const u32 *)X.d_isaln.p, nl, (u32 *)X.d_recofline.p))) return rc;
             if ((rc = fetch(ctx, (const u32 *)X.d_recofline.p + nl, &X.n_aln))) return rc;
         }

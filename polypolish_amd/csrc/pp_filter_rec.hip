@@ -62,23 +62,6 @@ __global__ __launch_bounds__(256) void k_rec_compact(u32 n_rec, RecRaw R, const 
     ids[base + a] = R.read_id[r];
 }
 
-// The call's device memory: the context's grow-only buffers (pp_ctx::f_rec), handed out in the order of the requests -- the same
-// request of the next job finds its buffer again.  Nothing in them outlives the call: every table is set up afresh.  (Not
-// pp_dev.h's CallScratch, which allocates per call and frees at return; the same get(), so that on_device takes either.)
-struct Scratch {
-    pp_ctx *ctx;
-    size_t k = 2;  // ([0], [1]: scan_u32's block sums)
-    pp::DevBuf &sums() { return ctx->f_rec[0]; }
-    pp::DevBuf &sums_off() { return ctx->f_rec[1]; }
-    int get(pp_ctx *, void **out, size_t bytes) {
-        *out = nullptr;
-        if (k >= sizeof ctx->f_rec / sizeof ctx->f_rec[0]) return ctx->fail(PP_ERR_HIP, "pp_filter_records: out of buffer slots");
-        if (int rc = pp::dev_ensure(ctx, ctx->f_rec[k], bytes ? bytes : 16)) return rc;
-        *out = ctx->f_rec[k++].p;
-        return PP_OK;
-    }
-};
-
 enum : int { SPAN_COMPACT = 0, SPAN_INTERN = 1, SPAN_GROUPS = 2 };
 static const char *const SPAN_NAME[3] = {"rec_compact", "rec_intern", "rec_groups"};
 
@@ -97,35 +80,25 @@ extern "C" int pp_filter_records(pp_ctx *ctx, const pp_raw_batch raw[2], int mem
     if (!report) report = &local_report;
     memset(counts, 0, 2 * sizeof(pp_filter_file_counts));
     memset(report, 0, sizeof *report);
-    for (int f = 0; f < 2; f++) {
-        const pp_raw_batch &B = raw[f];
-        if (B.n_rec >= 0xFFFFFFFFull) return ctx->fail(PP_ERR_LIMIT, "more than 2^32-1 alignments in one batch");
-        if (B.n_rec && (!B.flag || !B.read_id || !B.contig || !B.ref_start || !B.cig_off || !B.n_cig || (B.n_cig_total && !B.cigar)))
-            return ctx->fail(PP_ERR_ARG, "pp_filter_records: null array in a non-empty batch");
-    }
+    int rc;
+    for (int f = 0; f < 2; f++)  // (the filter reads no nm and no SEQ)
+        if ((rc = raw_check(ctx, "pp_filter_records", &raw[f], mem, RAW_CIGAR))) return rc;
     // check_inputs comes before anything is loaded (filter.rs:40-53)
     if (const char *msg = pph::percentile_options_error(low, high)) return ctx->fail(PP_ERR_QUIT, "%s", msg);
     PP_HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     uint8_t *const pass[2] = {pass1, pass2};
 
-    Scratch T{ctx};
+    CtxScratch T(ctx, ctx->f_rec, "pp_filter_records");
     StageTimer spans(ctx, ctx->profiling != 0);  // (pp_filter_begin starts the context's own timers afresh)
-    int rc;
     // ---- the source on the device ----
     RecRaw R[2];
     u32 n_rec[2];
     for (int f = 0; f < 2; f++) {
-        const pp_raw_batch &B = raw[f];
-        n_rec[f] = (u32)B.n_rec;
-        R[f] = RecRaw{B.flag, (const u64 *)B.read_id, (const u64 *)B.cig_off, B.contig, B.ref_start, B.n_cig, B.cigar, B.n_cig_total};
-        const size_t n = n_rec[f];
-        RecRaw &D = R[f];  // (a batch without records uploads nothing)
-        if (n && ((rc = on_device(ctx, T, mem, D.flag, n, &D.flag)) || (rc = on_device(ctx, T, mem, D.read_id, n, &D.read_id)) ||
-                  (rc = on_device(ctx, T, mem, D.cig_off, n, &D.cig_off)) || (rc = on_device(ctx, T, mem, D.contig, n, &D.contig)) ||
-                  (rc = on_device(ctx, T, mem, D.ref_start, n, &D.ref_start)) || (rc = on_device(ctx, T, mem, D.n_cig, n, &D.n_cig)) ||
-                  (rc = on_device(ctx, T, mem, D.cigar, (size_t)B.n_cig_total, &D.cigar))))
-            return rc;
+        pp_raw_batch D = raw[f];  // (a batch without records uploads nothing)
+        n_rec[f] = (u32)D.n_rec;
+        if (n_rec[f] && (rc = raw_on_device(ctx, T, mem, &raw[f], RAW_CIGAR, &D))) return rc;
+        R[f] = RecRaw{D.flag, (const u64 *)D.read_id, (const u64 *)D.cig_off, D.contig, D.ref_start, D.n_cig, D.cigar, D.n_cig_total};
     }
 
     // ---- the aligned records of either file, numbered in file order ----

@@ -25,14 +25,13 @@
 // reports its first offending record).
 #include "pp_dev.h"
 
-struct pp_gated {
-    pp_ctx *ctx = nullptr;
-    // contig ref_start k seq_off seq_len cig_off n_cig seq cigar orig
-    void *d[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+struct pp_gated : DevOwner {
+    using DevOwner::DevOwner;
+    AlnArrays a;
+    u32 *orig = nullptr;  // the raw index of every gated record
     pp_aln_batch view{};
     pp_sam_counts counts{};
-    bool timed = false;
-    float ms[3] = {0.f, 0.f, 0.f};  // ranks, groups, gates and scans | placement | SEQ and CIGAR copy
+    StageMs<3> t;         // ranks, groups, gates and scans | placement | SEQ and CIGAR copy
 };
 
 namespace {
@@ -254,17 +253,11 @@ __global__ __launch_bounds__(256) void k_gate_seq(u32 n_good, const u32 *__restr
 
 }  // namespace
 
-extern "C" void pp_gated_free(pp_gated *g) {
-    if (!g) return;
-    if (g->ctx) (void)hipSetDevice(g->ctx->device);
-    for (void *q : g->d)
-        if (q) (void)hipFree(q);
-    delete g;
-}
+extern "C" void pp_gated_free(pp_gated *g) { delete g; }
 
 extern "C" void pp_gated_batch(const pp_gated *g, pp_aln_batch *out, const uint32_t **orig) {
     if (out) *out = g ? g->view : pp_aln_batch{};
-    if (orig) *orig = g ? (const uint32_t *)g->d[9] : nullptr;
+    if (orig) *orig = g ? g->orig : nullptr;
 }
 
 extern "C" void pp_gated_counts(const pp_gated *g, pp_sam_counts *out) {
@@ -272,18 +265,11 @@ extern "C" void pp_gated_counts(const pp_gated *g, pp_sam_counts *out) {
 }
 
 extern "C" int pp_gated_kernel_ms(const pp_gated *g, float *ms) {
-    if (!g || !ms) return PP_ERR_ARG;
-    if (!g->timed) return g->ctx->fail(PP_ERR_ARG, "pp_gated_kernel_ms: the context had no profiling on when the batch was gated (pp_ctx_set_profiling)");
-    *ms = g->ms[0] + g->ms[1] + g->ms[2];
-    return PP_OK;
+    return g ? g->t.total(g->ctx, "pp_gated_kernel_ms", "when the batch was gated", ms) : PP_ERR_ARG;
 }
 
 // (internal hook, not part of the header: tools/gate_timing.py) the same time by stage: gates and scans | placement | SEQ and CIGAR copy
-extern "C" int pp_gated_stage_ms_(const pp_gated *g, float *ms3) {
-    if (!g || !ms3 || !g->timed) return PP_ERR_ARG;
-    for (int i = 0; i < 3; i++) ms3[i] = g->ms[i];
-    return PP_OK;
-}
+extern "C" int pp_gated_stage_ms_(const pp_gated *g, float *ms3) { return g ? g->t.stages(ms3) : PP_ERR_ARG; }
 
 extern "C" int pp_batch_gate(pp_ctx *ctx, const pp_raw_batch *raw, int mem, uint32_t max_errors, int careful, const uint8_t *pass,
                              uint64_t n_pass, pp_gated **out, uint64_t *bad_record) {
@@ -292,45 +278,30 @@ extern "C" int pp_batch_gate(pp_ctx *ctx, const pp_raw_batch *raw, int mem, uint
     if (bad_record) *bad_record = ~0ull;
     if (!raw || !out) return ctx->fail(PP_ERR_ARG, "pp_batch_gate: null argument");
     *out = nullptr;
-    if (mem != PP_MEM_HOST && mem != PP_MEM_DEVICE)
-        return ctx->fail(PP_ERR_ARG, "pp_batch_gate: the batch must be host memory or memory of the context's device");
-    if (raw->n_rec >= 0xFFFFFFFFull) return ctx->fail(PP_ERR_LIMIT, "more than 2^32-1 alignments in one batch");
-    if (raw->seq_bytes >= (1ull << 40)) return ctx->fail(PP_ERR_LIMIT, "more than 2^40 SEQ bytes in one batch");
-    if (raw->n_rec && (!raw->flag || !raw->read_id || !raw->contig || !raw->ref_start || !raw->nm || !raw->seq_off || !raw->seq_len ||
-                       !raw->cig_off || !raw->n_cig || (raw->seq_bytes && !raw->seq) || (raw->n_cig_total && !raw->cigar)))
-        return ctx->fail(PP_ERR_ARG, "pp_batch_gate: null array in a non-empty batch");
+    int rc;
+    if ((rc = raw_check(ctx, "pp_batch_gate", raw, mem, RAW_ALL | RAW_SEQ_LIMIT))) return rc;
     PP_HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const u32 n_rec = (u32)raw->n_rec;
 
-    pp_gated *P = new pp_gated;
-    P->ctx = ctx;
-    std::unique_ptr<pp_gated, void (*)(pp_gated *)> guard(P, pp_gated_free);  // (every early return releases what was made so far)
+    std::unique_ptr<pp_gated> P(new pp_gated(ctx));
     // a batch without aligned records gates to an empty batch -- unless it came with verdicts for records it does not have
     auto empty = [&]() -> int {
         PP_HIPCHK(ctx, hipStreamSynchronize(st));
         if (pass && n_pass != 0)
             return ctx->fail(PP_ERR_ARG, "pp_batch_gate: %llu filter verdicts for 0 aligned records", (unsigned long long)n_pass);
-        guard.release();
-        *out = P;
+        *out = P.release();
         return PP_OK;
     };
     if (n_rec == 0) return empty();
 
     CallScratch T;
     StageTimer timer(ctx, ctx->profiling != 0);
-    int rc;
     // ---- the source on the device ----
-    GateRaw R{};
-    R.seq_bytes = raw->seq_bytes;
-    R.n_cig_total = raw->n_cig_total;
-    if ((rc = on_device(ctx, T, mem, raw->flag, n_rec, &R.flag)) || (rc = on_device(ctx, T, mem, (const u64 *)raw->read_id, n_rec, &R.read_id)) ||
-        (rc = on_device(ctx, T, mem, raw->contig, n_rec, &R.contig)) || (rc = on_device(ctx, T, mem, raw->ref_start, n_rec, &R.ref_start)) ||
-        (rc = on_device(ctx, T, mem, raw->nm, n_rec, &R.nm)) || (rc = on_device(ctx, T, mem, (const u64 *)raw->seq_off, n_rec, &R.seq_off)) ||
-        (rc = on_device(ctx, T, mem, raw->seq_len, n_rec, &R.seq_len)) || (rc = on_device(ctx, T, mem, (const u64 *)raw->cig_off, n_rec, &R.cig_off)) ||
-        (rc = on_device(ctx, T, mem, raw->n_cig, n_rec, &R.n_cig)) || (rc = on_device(ctx, T, mem, raw->seq, (size_t)raw->seq_bytes, &R.seq)) ||
-        (rc = on_device(ctx, T, mem, raw->cigar, (size_t)raw->n_cig_total, &R.cigar)))
-        return rc;
+    pp_raw_batch D;
+    if ((rc = raw_on_device(ctx, T, mem, raw, RAW_ALL, &D))) return rc;
+    const GateRaw R{D.flag, (const u64 *)D.read_id, (const u64 *)D.seq_off, (const u64 *)D.cig_off, D.contig, D.ref_start, D.nm, D.seq_len, D.n_cig,
+                    D.cigar, D.seq, D.seq_bytes, D.n_cig_total};
 
     // ---- the aligned records ----
     const u32 nb_r = (n_rec + GATE_BLOCK - 1u) / GATE_BLOCK;
@@ -405,14 +376,14 @@ extern "C" int pp_batch_gate(pp_ctx *ctx, const pp_raw_batch *raw, int mem, uint
     P->counts.reads = n_groups;
 
     // ---- the result ----
-    const size_t obytes[10] = {(size_t)n_good * 4, (size_t)n_good * 4, (size_t)n_good * 4, (size_t)n_good * 8, (size_t)n_good * 4, (size_t)n_good * 8,
-                               (size_t)n_good * 4, (size_t)total + 64, (size_t)n_cig_out * 4, (size_t)n_good * 4};
-    for (int i = 0; i < 10; i++) PP_HIPCHK(ctx, hipMalloc(&P->d[i], obytes[i] ? obytes[i] : 16));
-    PP_HIPCHK(ctx, hipMemsetAsync((u8 *)P->d[7] + total, 0, 64, st));
-    void *d_desc;
+    AlnArrays &A = P->a;
+    if ((rc = A.alloc_records(*P, n_good)) || (rc = P->alloc(A.seq, (size_t)total + 64)) || (rc = P->alloc(A.cigar, (size_t)n_cig_out)) ||
+        (rc = P->alloc(P->orig, n_good)))
+        return rc;
+    PP_HIPCHK(ctx, hipMemsetAsync(A.seq + total, 0, 64, st));
+    void *d_desc;  // (the call's: nothing of the object points to it)
     if ((rc = T.get(ctx, &d_desc, (size_t)n_good * 8))) return rc;
-    O = GateOut{(u32 *)P->d[0], (u32 *)P->d[1], (u32 *)P->d[2], (u32 *)P->d[4], (u32 *)P->d[6], (u32 *)P->d[9], (u64 *)P->d[3], (u64 *)P->d[5],
-                (u64 *)d_desc};
+    O = GateOut{A.contig, A.ref_start, A.k, A.seq_len, A.n_cig, P->orig, A.seq_off, A.cig_off, (u64 *)d_desc};
     if ((rc = timer.begin(1))) return rc;
     if (n_good)
         hipLaunchKernelGGL(k_gate_place<true>, dim3(nb), dim3(GATE_BLOCK), 0, st, n_al, R, (const u32 *)d_rec_of, (const u32 *)d_grp_of,
@@ -420,24 +391,14 @@ extern "C" int pp_batch_gate(pp_ctx *ctx, const pp_raw_batch *raw, int mem, uint
                            (u64 *)d_status);
     if ((rc = timer.end()) || (rc = timer.begin(2))) return rc;
     if (n_good)
-        hipLaunchKernelGGL(k_gate_seq, dim3((unsigned)(((u64)n_good * 8u + 255u) / 256u)), dim3(256), 0, st, n_good, (const u32 *)P->d[4],
-                           (const u64 *)P->d[3], (const u64 *)d_desc, (const u32 *)P->d[6], (const u64 *)P->d[5], (const u32 *)P->d[9], R.cig_off,
-                           R.cigar, R.seq, R.seq_bytes, (u8 *)P->d[7], (u32 *)P->d[8]);
+        hipLaunchKernelGGL(k_gate_seq, dim3((unsigned)(((u64)n_good * 8u + 255u) / 256u)), dim3(256), 0, st, n_good, (const u32 *)A.seq_len,
+                           (const u64 *)A.seq_off, (const u64 *)d_desc, (const u32 *)A.n_cig, (const u64 *)A.cig_off, (const u32 *)P->orig, R.cig_off,
+                           R.cigar, R.seq, R.seq_bytes, A.seq, A.cigar);
     if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     PP_HIPCHK(ctx, hipStreamSynchronize(st));  // the source may be released, the scratch goes away
-    if (timer.on) {
-        if ((rc = timer.sums(P->ms, 3))) return rc;
-        P->timed = true;
-    }
-    pp_aln_batch &V = P->view;
-    V.n_aln = n_good;
-    V.contig = (const u32 *)P->d[0]; V.ref_start = (const u32 *)P->d[1]; V.k = (const u32 *)P->d[2]; V.seq_off = (const uint64_t *)P->d[3];
-    V.seq_len = (const u32 *)P->d[4]; V.cig_off = (const uint64_t *)P->d[5]; V.n_cig = (const u32 *)P->d[6]; V.seq = (const u8 *)P->d[7];
-    V.seq_bytes = total;
-    V.cigar = (const u32 *)P->d[8];
-    V.n_cig_total = n_cig_out;
-    guard.release();
-    *out = P;
+    if ((rc = P->t.take(timer))) return rc;
+    P->view = A.view(n_good, total, n_cig_out);
+    *out = P.release();
     return PP_OK;
 }

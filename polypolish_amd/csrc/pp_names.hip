@@ -233,8 +233,7 @@ struct pp_names {
     u64 cap = 0, count = 0, pool_used = 0;
     // scratch of a call (grow-only): hash found rep src_of | slot_of | blk2 blk2off | status | a host array's copies
     pp::DevBuf hash, found, rep, src_of, slot_of, blk2, blk2off, status, up_bytes, up_off, up_len, dn64, dn32;
-    bool timed = false;
-    float ms[NM_STAGES] = {0.f, 0.f, 0.f, 0.f, 0.f};  // the last call's kernels by stage
+    StageMs<NM_STAGES> t;  // the last call's kernels by stage
 };
 
 namespace {
@@ -373,19 +372,11 @@ extern "C" void pp_names_free(pp_names *T) {
 extern "C" uint64_t pp_names_count(const pp_names *T) { return T ? T->count : 0; }
 
 extern "C" int pp_names_kernel_ms(const pp_names *T, float *ms) {
-    if (!T || !ms) return PP_ERR_ARG;
-    if (!T->timed) return T->ctx->fail(PP_ERR_ARG, "pp_names_kernel_ms: the context had no profiling on at the table's last pp_names_ids (pp_ctx_set_profiling)");
-    *ms = 0.f;
-    for (float m : T->ms) *ms += m;
-    return PP_OK;
+    return T ? T->t.total(T->ctx, "pp_names_kernel_ms", "at the table's last pp_names_ids", ms) : PP_ERR_ARG;
 }
 
 // (internal hook, not part of the header: tools/names_timing.py) the same time by stage: lookup | rehash | insert, rank | entries, bytes | ids
-extern "C" int pp_names_stage_ms_(const pp_names *T, float *ms5) {
-    if (!T || !ms5 || !T->timed) return PP_ERR_ARG;
-    for (int i = 0; i < NM_STAGES; i++) ms5[i] = T->ms[i];
-    return PP_OK;
-}
+extern "C" int pp_names_stage_ms_(const pp_names *T, float *ms5) { return T ? T->t.stages(ms5) : PP_ERR_ARG; }
 
 extern "C" int pp_names_name(const pp_names *T, uint64_t id, uint8_t *out, uint32_t cap, uint32_t *len) {
     if (!T) return PP_ERR_ARG;
@@ -417,7 +408,7 @@ extern "C" int pp_names_ids(pp_names *T, const uint8_t *bytes, uint64_t n_bytes,
     PP_HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     StageTimer timer(ctx, ctx->profiling != 0);
-    T->timed = false;
+    T->t.timed = false;
     int rc;
 
     NmSrc S{bytes, n_bytes, (const u64 *)off, len};
@@ -464,9 +455,5 @@ extern "C" int pp_names_ids(pp_names *T, const uint8_t *bytes, uint64_t n_bytes,
         if (id32) PP_HIPCHK(ctx, hipMemcpyAsync(id32, T->dn32.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
     }
     PP_HIPCHK(ctx, hipStreamSynchronize(st));  // the caller's arrays may be released
-    if (timer.on) {
-        if ((rc = timer.sums(T->ms, NM_STAGES))) return rc;
-        T->timed = true;
-    }
-    return PP_OK;
+    return T->t.take(timer);
 }

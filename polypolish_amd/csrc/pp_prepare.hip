@@ -26,14 +26,14 @@
 #include "pp_dev.h"
 #include "pp_wo_home.h"
 
-struct pp_prepared {
-    pp_ctx *ctx = nullptr;
-    // contig ref_start k seq_off seq_len cig_off n_cig seq cigar seq4 wo
-    void *d[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint64_t run_end[1] = {0};  // the mirror's one run (pp_aln_batch.wo_run_end: HOST memory)
+struct pp_prepared : DevOwner {
+    using DevOwner::DevOwner;
+    AlnArrays a;
+    u8 *seq4 = nullptr;         // the 4-bit mirror of a.seq
+    pp_wo_rec *wo = nullptr;    // the window-order mirror of the records
+    uint64_t run_end = 0;       // the mirror's one run (pp_aln_batch.wo_run_end: HOST memory)
     pp_aln_batch view{};
-    bool timed = false;
-    float ms = 0.f;
+    StageMs<1> t;
 };
 
 namespace {
@@ -253,11 +253,7 @@ __global__ __launch_bounds__(256) void k_prep_copy(u32 n, const pp_wo_rec *__res
 }  // namespace
 
 extern "C" void pp_prepared_free(pp_prepared *p) {
-    if (!p) return;
-    pp_mirror_forget_(p);
-    if (p->ctx) (void)hipSetDevice(p->ctx->device);
-    for (void *q : p->d)
-        if (q) (void)hipFree(q);
+    if (p) pp_mirror_forget_(p);
     delete p;
 }
 
@@ -268,10 +264,7 @@ extern "C" void pp_prepared_batch(const pp_prepared *p, pp_aln_batch *out) {
 }
 
 extern "C" int pp_prepared_kernel_ms(const pp_prepared *p, float *ms) {
-    if (!p || !ms) return PP_ERR_ARG;
-    if (!p->timed) return p->ctx->fail(PP_ERR_ARG, "pp_prepared_kernel_ms: the context had no profiling on when the batch was prepared (pp_ctx_set_profiling)");
-    *ms = p->ms;
-    return PP_OK;
+    return p ? p->t.total(p->ctx, "pp_prepared_kernel_ms", "when the batch was prepared", ms) : PP_ERR_ARG;
 }
 
 extern "C" int pp_batch_prepare(pp_ctx *ctx, uint32_t n_contigs, const uint64_t *contig_off, const pp_aln_batch *b, int mem,
@@ -296,16 +289,12 @@ extern "C" int pp_batch_prepare(pp_ctx *ctx, uint32_t n_contigs, const uint64_t 
     const u32 n = (u32)b->n_aln;
     const u32 n_win = (u32)std::max<u64>(1, (G + pp::TILE - 1) / pp::TILE);
 
-    pp_prepared *P = new pp_prepared;
-    P->ctx = ctx;
-    std::unique_ptr<pp_prepared, void (*)(pp_prepared *)> guard(P, pp_prepared_free);  // (every early return releases what was made so far)
-    pp_aln_batch &V = P->view;
-    V.n_aln = n;
-    V.n_cig_total = b->n_cig_total;
+    std::unique_ptr<pp_prepared> P(new pp_prepared(ctx));
+    AlnArrays &A = P->a;
     if (n == 0) {  // an empty batch prepares to an empty batch
+        P->view = A.view(0, 0, b->n_cig_total);
         PP_HIPCHK(ctx, hipStreamSynchronize(st));
-        guard.release();
-        *out = P;
+        *out = P.release();
         return PP_OK;
     }
 
@@ -313,22 +302,12 @@ extern "C" int pp_batch_prepare(pp_ctx *ctx, uint32_t n_contigs, const uint64_t 
     StageTimer timer(ctx, ctx->profiling != 0);
     int rc;
     // ---- the source on the device ----
-    PrepSrc S{};
-    S.seq_bytes = b->seq_bytes;
-    S.n_cig_total = b->n_cig_total;
-    const u8 *src_seq;
-    if ((rc = on_device(ctx, T, mem, b->contig, n, &S.contig)) || (rc = on_device(ctx, T, mem, b->ref_start, n, &S.ref_start)) ||
-        (rc = on_device(ctx, T, mem, b->k, n, &S.k)) || (rc = on_device(ctx, T, mem, (const u64 *)b->seq_off, n, &S.seq_off)) ||
-        (rc = on_device(ctx, T, mem, b->seq_len, n, &S.seq_len)) || (rc = on_device(ctx, T, mem, (const u64 *)b->cig_off, n, &S.cig_off)) ||
-        (rc = on_device(ctx, T, mem, b->n_cig, n, &S.n_cig)) || (rc = on_device(ctx, T, mem, b->seq, (size_t)b->seq_bytes, &src_seq)) ||
-        (rc = on_device(ctx, T, mem, b->cigar, (size_t)b->n_cig_total, &S.cigar)))
-        return rc;
+    pp_aln_batch D;
+    if ((rc = aln_on_device(ctx, T, mem, b, &D))) return rc;
+    const PrepSrc S{D.contig, D.ref_start, D.k, D.seq_len, D.n_cig, D.cigar, (const u64 *)D.seq_off, (const u64 *)D.cig_off, D.seq_bytes, D.n_cig_total};
     // ---- the result's arrays (seq and seq4 once their size is known) ----
-    const size_t obytes[11] = {(size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)n * 8, (size_t)n * 4, (size_t)n * 8, (size_t)n * 4, 0,
-                               (size_t)b->n_cig_total * 4, 0, (size_t)n * sizeof(pp_wo_rec)};
-    for (int i = 0; i < 11; i++)
-        if (i != 7 && i != 9) PP_HIPCHK(ctx, hipMalloc(&P->d[i], obytes[i] ? obytes[i] : 16));
-    if (b->n_cig_total) PP_HIPCHK(ctx, hipMemcpyAsync(P->d[8], S.cigar, obytes[8], hipMemcpyDeviceToDevice, st));
+    if ((rc = A.alloc_records(*P, n)) || (rc = P->alloc(A.cigar, (size_t)b->n_cig_total)) || (rc = P->alloc(P->wo, n))) return rc;
+    if (b->n_cig_total) PP_HIPCHK(ctx, hipMemcpyAsync(A.cigar, S.cigar, (size_t)b->n_cig_total * 4, hipMemcpyDeviceToDevice, st));
     // ---- scratch ----
     const bool lds = n_win <= PREP_WIN_LDS;
     const u32 per_block = std::max<u32>(PREP_PER_BLOCK, (u32)((((u64)n + 1023u) / 1024u + 1023u) & ~1023ull));  // (at most 1024 rows)
@@ -344,8 +323,7 @@ extern "C" int pp_batch_prepare(pp_ctx *ctx, uint32_t n_contigs, const uint64_t 
     u32 *const d_flag = (u32 *)((u64 *)d_word + 1);
     PP_HIPCHK(ctx, hipMemcpyAsync(d_cofs, contig_off, ((size_t)n_contigs + 1) * 8, hipMemcpyHostToDevice, st));
     PP_HIPCHK(ctx, hipMemsetAsync(d_word, 0, 16, st));
-    PrepOut O{(u32 *)P->d[0], (u32 *)P->d[1], (u32 *)P->d[2], (u32 *)P->d[4], (u32 *)P->d[6], (u64 *)P->d[3], (u64 *)P->d[5],
-              (pp_wo_rec *)P->d[10], (u64 *)d_src, (u64 *)d_dst};
+    const PrepOut O{A.contig, A.ref_start, A.k, A.seq_len, A.n_cig, A.seq_off, A.cig_off, P->wo, (u64 *)d_src, (u64 *)d_dst};
 
     if ((rc = timer.begin(0))) return rc;
     // ---- placement ----
@@ -373,40 +351,32 @@ extern "C" int pp_batch_prepare(pp_ctx *ctx, uint32_t n_contigs, const uint64_t 
         hipLaunchKernelGGL(k_prep_place_g, dim3(g256), dim3(256), 0, st, (const u32 *)d_win, (const u32 *)d_units, n, (u64 *)d_mat, (const u64 *)d_wbase,
                            (const u32 *)d_wcbase, (const u32 *)d_flag, S, O);
     if ((rc = timer.end())) return rc;
-    u64 word[2] = {0, 0};
-    if ((rc = fetch(ctx, d_word, word, 2))) return rc;
-    const u32 flag = (u32)word[1];
+    struct { u64 units, flag; } got{0, 0};  // d_total | d_flag
+    if ((rc = fetch(ctx, d_word, &got))) return rc;
+    const u32 flag = (u32)got.flag;
     if (flag & PREP_LIM_BYTES) return ctx->fail(PP_ERR_LIMIT, "more than 2^40 SEQ bytes in one prepared batch");
     if (flag & PREP_LIM_WIN_RECORDS) return ctx->fail(PP_ERR_LIMIT, "more than 2^24 alignments start in one 2048-position window");
     if (flag & PREP_LIM_WIN_BYTES) return ctx->fail(PP_ERR_LIMIT, "more than 2^37 SEQ bytes start in one 2048-position window");
     // ---- the SEQ bytes and their 4-bit mirror ----
-    const u64 total = word[0] * (u64)PP_SEQ_ALIGN;  // a sum of rooms
-    PP_HIPCHK(ctx, hipMalloc(&P->d[7], (size_t)total + 64));
-    PP_HIPCHK(ctx, hipMalloc(&P->d[9], (size_t)(total / 2) + 96));
-    PP_HIPCHK(ctx, hipMemsetAsync((u8 *)P->d[7] + total, 0, 64, st));
-    PP_HIPCHK(ctx, hipMemsetAsync((u8 *)P->d[9] + total / 2, 0, 96, st));
+    const u64 total = got.units * (u64)PP_SEQ_ALIGN;  // a sum of rooms
+    if ((rc = P->alloc(A.seq, (size_t)total + 64)) || (rc = P->alloc(P->seq4, (size_t)(total / 2) + 96))) return rc;
+    PP_HIPCHK(ctx, hipMemsetAsync(A.seq + total, 0, 64, st));
+    PP_HIPCHK(ctx, hipMemsetAsync(P->seq4 + total / 2, 0, 96, st));
     if ((rc = timer.begin(0))) return rc;
     if (total)
-        hipLaunchKernelGGL(k_prep_copy, dim3((unsigned)(((u64)n + PREP_COPY_E - 1u) / PREP_COPY_E)), dim3(256), 0, st, n, (const pp_wo_rec *)P->d[10],
-                           (const u64 *)d_src, (const u64 *)d_dst, src_seq, (u64)b->seq_bytes, (u8 *)P->d[7], (u8 *)P->d[9]);
+        hipLaunchKernelGGL(k_prep_copy, dim3((unsigned)(((u64)n + PREP_COPY_E - 1u) / PREP_COPY_E)), dim3(256), 0, st, n, (const pp_wo_rec *)P->wo,
+                           (const u64 *)d_src, (const u64 *)d_dst, D.seq, (u64)b->seq_bytes, A.seq, P->seq4);
     if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     PP_HIPCHK(ctx, hipStreamSynchronize(st));  // the source may be released, the scratch goes away
-    if (timer.on) {
-        if ((rc = timer.sums(&P->ms, 1))) return rc;
-        P->timed = true;
-    }
-    V.contig = (const u32 *)P->d[0]; V.ref_start = (const u32 *)P->d[1]; V.k = (const u32 *)P->d[2]; V.seq_off = (const uint64_t *)P->d[3];
-    V.seq_len = (const u32 *)P->d[4]; V.cig_off = (const uint64_t *)P->d[5]; V.n_cig = (const u32 *)P->d[6]; V.seq = (const u8 *)P->d[7];
-    V.seq_bytes = total;
-    V.cigar = (const u32 *)P->d[8];
-    V.seq4 = (const u8 *)P->d[9];
-    V.wo = (const pp_wo_rec *)P->d[10];
-    P->run_end[0] = n;
+    if ((rc = P->t.take(timer))) return rc;
+    pp_aln_batch &V = P->view = A.view(n, total, b->n_cig_total);
+    V.seq4 = P->seq4;
+    V.wo = P->wo;
+    P->run_end = n;
     V.wo_n_runs = 1;
-    V.wo_run_end = P->run_end;
-    pp_mirror_register_(P, V.wo, (size_t)n * sizeof(pp_wo_rec));  // one of the library's own: pp_polish_add takes it unchecked
-    guard.release();
-    *out = P;
+    V.wo_run_end = &P->run_end;
+    pp_mirror_register_(P.get(), V.wo, (size_t)n * sizeof(pp_wo_rec));  // one of the library's own: pp_polish_add takes it unchecked
+    *out = P.release();
     return PP_OK;
 }

@@ -22,15 +22,13 @@
 
 #include <cstring>
 
-struct pp_regrouped {
-    pp_ctx *ctx = nullptr;
-    // flag read_id contig ref_start nm seq_off seq_len cig_off n_cig | seq cigar (PP_MEM_HOST) | perm
-    void *d[12] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+struct pp_regrouped : DevOwner {  // owns the upload of a host batch, the gathered arrays of a batch whose records moved, and perm
+    using DevOwner::DevOwner;
     pp_raw_batch view{};
+    u32 *perm = nullptr;
     uint64_t n_groups = 0, n_moved = 0, n_aligned = 0;
     std::vector<uint32_t> amap;  // aligned rank in the regrouped batch -> aligned rank in raw (empty: the identity)
-    bool timed = false;
-    float ms[3] = {0.f, 0.f, 0.f};  // intern | sort | gather, counts and the verdict map
+    StageMs<3> t;                // intern | sort | gather, counts and the verdict map
 };
 
 namespace {
@@ -39,7 +37,6 @@ constexpr u32 RG_BLOCK = 1024;                    // 16 waves ...
 constexpr u32 RG_ROUNDS = 4;                      // ... each takes 4 x 64 adjacent keys: round by round, lane by lane
 constexpr u32 RG_TILE = RG_BLOCK * RG_ROUNDS;     // keys per workgroup
 constexpr u32 RG_WAVES = RG_BLOCK / 64u;
-constexpr u32 RG_SIZE[9] = {2, 8, 4, 4, 4, 8, 4, 8, 4};  // bytes per element of the nine arrays
 
 // the place of the key that lane `lane` of wave `wave` takes in round `j` of its tile
 __device__ __forceinline__ u64 rg_index(u32 wave, u32 j, u32 lane) {
@@ -170,38 +167,17 @@ __global__ __launch_bounds__(256) void k_rg_map(u32 n, const uint16_t *__restric
     if (!(flag[p] & 4u)) amap[rank_new[j]] = rank_raw[p];
 }
 
-// the call's scratch: the context's grow-only buffers (pp_ctx::g_rec) in the order of the requests, as pp_filter_records keeps its own
-struct Scratch {
-    pp_ctx *ctx;
-    size_t k = 2;  // ([0], [1]: scan_u32's block sums)
-    pp::DevBuf &sums() { return ctx->g_rec[0]; }
-    pp::DevBuf &sums_off() { return ctx->g_rec[1]; }
-    int get(pp_ctx *, void **out, size_t bytes) {
-        *out = nullptr;
-        if (k >= sizeof ctx->g_rec / sizeof ctx->g_rec[0]) return ctx->fail(PP_ERR_HIP, "pp_batch_regroup: out of buffer slots");
-        if (int rc = pp::dev_ensure(ctx, ctx->g_rec[k], bytes ? bytes : 16)) return rc;
-        *out = ctx->g_rec[k++].p;
-        return PP_OK;
-    }
-};
-
 enum : int { RG_INTERN = 0, RG_SORT = 1, RG_GATHER = 2 };
 
 }  // namespace
 
-extern "C" void pp_regrouped_free(pp_regrouped *g) {
-    if (!g) return;
-    if (g->ctx) (void)hipSetDevice(g->ctx->device);
-    for (void *q : g->d)
-        if (q) (void)hipFree(q);
-    delete g;
-}
+extern "C" void pp_regrouped_free(pp_regrouped *g) { delete g; }
 
 extern "C" void pp_regrouped_raw(const pp_regrouped *g, pp_raw_batch *out) {
     if (out) *out = g ? g->view : pp_raw_batch{};
 }
 
-extern "C" const uint32_t *pp_regrouped_perm(const pp_regrouped *g) { return g ? (const uint32_t *)g->d[11] : nullptr; }
+extern "C" const uint32_t *pp_regrouped_perm(const pp_regrouped *g) { return g ? g->perm : nullptr; }
 
 extern "C" void pp_regrouped_counts(const pp_regrouped *g, uint64_t *n_groups, uint64_t *n_moved) {
     if (n_groups) *n_groups = g ? g->n_groups : 0;
@@ -223,19 +199,12 @@ extern "C" int pp_regrouped_pass(const pp_regrouped *g, const uint8_t *pass, uin
 }
 
 extern "C" int pp_regrouped_kernel_ms(const pp_regrouped *g, float *ms) {
-    if (!g || !ms) return PP_ERR_ARG;
-    if (!g->timed) return g->ctx->fail(PP_ERR_ARG, "pp_regrouped_kernel_ms: the context had no profiling on when the batch was regrouped (pp_ctx_set_profiling)");
-    *ms = g->ms[0] + g->ms[1] + g->ms[2];
-    return PP_OK;
+    return g ? g->t.total(g->ctx, "pp_regrouped_kernel_ms", "when the batch was regrouped", ms) : PP_ERR_ARG;
 }
 
 // (internal hooks, not part of the header: tools/regroup_timing.py, tests/test_regroup_gpu.py) the same time by stage: intern | sort |
 // gather; and the sort's tile, so that the tests can place their sizes around it
-extern "C" int pp_regrouped_stage_ms_(const pp_regrouped *g, float *ms3) {
-    if (!g || !ms3 || !g->timed) return PP_ERR_ARG;
-    for (int i = 0; i < 3; i++) ms3[i] = g->ms[i];
-    return PP_OK;
-}
+extern "C" int pp_regrouped_stage_ms_(const pp_regrouped *g, float *ms3) { return g ? g->t.stages(ms3) : PP_ERR_ARG; }
 extern "C" void pp_regroup_geometry_(uint32_t *tile) {
     if (tile) *tile = RG_TILE;
 }
@@ -245,57 +214,28 @@ extern "C" int pp_batch_regroup(pp_ctx *ctx, const pp_raw_batch *raw, int mem, p
     if (int rdy = pp_ctx_wait(ctx)) return rdy;
     if (!raw || !out) return ctx->fail(PP_ERR_ARG, "pp_batch_regroup: null argument");
     *out = nullptr;
-    if (mem != PP_MEM_HOST && mem != PP_MEM_DEVICE)
-        return ctx->fail(PP_ERR_ARG, "pp_batch_regroup: the batch must be host memory or memory of the context's device");
-    if (raw->n_rec >= 0xFFFFFFFFull) return ctx->fail(PP_ERR_LIMIT, "more than 2^32-1 alignments in one batch");
-    const void *src[9] = {raw->flag, raw->read_id, raw->contig, raw->ref_start, raw->nm, raw->seq_off, raw->seq_len, raw->cig_off, raw->n_cig};
-    if (raw->n_rec)
-        for (const void *q : src)
-            if (!q) return ctx->fail(PP_ERR_ARG, "pp_batch_regroup: null array in a non-empty batch");
-    if (mem == PP_MEM_HOST && ((raw->seq_bytes && !raw->seq) || (raw->n_cig_total && !raw->cigar)))
+    int rc;
+    if ((rc = raw_check(ctx, "pp_batch_regroup", raw, mem, RAW_READS))) return rc;
+    if (mem == PP_MEM_HOST && ((raw->seq_bytes && !raw->seq) || (raw->n_cig_total && !raw->cigar)))  // (seq and cigar are read to be copied only)
         return ctx->fail(PP_ERR_ARG, "pp_batch_regroup: null array in a non-empty batch");
     PP_HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const u32 n = (u32)raw->n_rec;
 
-    pp_regrouped *P = new pp_regrouped;
-    P->ctx = ctx;
-    std::unique_ptr<pp_regrouped, void (*)(pp_regrouped *)> guard(P, pp_regrouped_free);  // (every early return releases what was made so far)
-    P->view = *raw;
-    int rc;
+    std::unique_ptr<pp_regrouped> P(new pp_regrouped(ctx));
     // ---- the source on the device: a host batch is uploaded into memory of the object ----
-    if (mem == PP_MEM_HOST) {
-        P->view = pp_raw_batch{};
-        P->view.n_rec = n;
-        P->view.seq_bytes = raw->seq_bytes;
-        P->view.n_cig_total = raw->n_cig_total;
-        const void *from[11] = {src[0], src[1], src[2], src[3], src[4], src[5], src[6], src[7], src[8], raw->seq, raw->cigar};
-        size_t bytes[11];
-        for (int a = 0; a < 9; a++) bytes[a] = (size_t)n * RG_SIZE[a];
-        bytes[9] = (size_t)raw->seq_bytes;
-        bytes[10] = (size_t)raw->n_cig_total * 4;
-        for (int a = 0; a < 11; a++) {
-            PP_HIPCHK(ctx, hipMalloc(&P->d[a], bytes[a] ? bytes[a] : 16));
-            if (bytes[a]) PP_HIPCHK(ctx, hipMemcpyAsync(P->d[a], from[a], bytes[a], hipMemcpyHostToDevice, st));
-            if (a < 9) src[a] = P->d[a];
-        }
-        pp_raw_batch &V = P->view;
-        V.flag = (const uint16_t *)P->d[0]; V.read_id = (const uint64_t *)P->d[1]; V.contig = (const u32 *)P->d[2];
-        V.ref_start = (const u32 *)P->d[3]; V.nm = (const u32 *)P->d[4]; V.seq_off = (const uint64_t *)P->d[5];
-        V.seq_len = (const u32 *)P->d[6]; V.cig_off = (const uint64_t *)P->d[7]; V.n_cig = (const u32 *)P->d[8];
-        V.seq = (const u8 *)P->d[9]; V.cigar = (const u32 *)P->d[10];
-    }
+    if ((rc = raw_on_device(ctx, *P, mem, raw, RAW_ALL, &P->view))) return rc;
+    const pp_raw_batch src = P->view;
+    if ((rc = P->alloc(P->perm, n))) return rc;
     if (n == 0) {
-        PP_HIPCHK(ctx, hipMalloc(&P->d[11], 16));
         PP_HIPCHK(ctx, hipStreamSynchronize(st));
-        guard.release();
-        *out = P;
+        *out = P.release();
         return PP_OK;
     }
-    const uint16_t *const d_flag = (const uint16_t *)src[0];
-    const u64 *const d_id = (const u64 *)src[1];
+    const uint16_t *const d_flag = src.flag;
+    const u64 *const d_id = (const u64 *)src.read_id;
 
-    Scratch T{ctx};
+    CtxScratch T(ctx, ctx->g_rec, "pp_batch_regroup");
     StageTimer timer(ctx, ctx->profiling != 0);
     const unsigned gb = (unsigned)(((u64)n + 255u) / 256u);
     // ---- rep[i]: the first record with record i's id ----
@@ -311,8 +251,7 @@ extern "C" int pp_batch_regroup(pp_ctx *ctx, const pp_raw_batch *raw, int mem, p
     PP_HIPCHK(ctx, hipGetLastError());
 
     // ---- perm: the indices, sorted by rep, stable ----
-    PP_HIPCHK(ctx, hipMalloc(&P->d[11], (size_t)n * 4));
-    u32 *const d_perm = (u32 *)P->d[11];
+    u32 *const d_perm = P->perm;
     int passes = 0;
     for (u32 top = n - 1u; top; top >>= 8) passes++;
     const u32 n_tiles = (u32)(((u64)n + RG_TILE - 1u) / RG_TILE);
@@ -360,17 +299,10 @@ extern "C" int pp_batch_regroup(pp_ctx *ctx, const pp_raw_batch *raw, int mem, p
 
     // ---- the view: the source's own arrays when nothing moves, else the nine arrays through perm ----
     if (P->n_moved) {
-        RgArrays A{};
-        void *fresh[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        struct Drop {  // (the arrays the gather fills belong to the object only once it holds them)
-            void **p;
-            ~Drop() { for (int a = 0; a < 9; a++) if (p[a]) (void)hipFree(p[a]); }
-        } drop{fresh};
-        for (int a = 0; a < 9; a++) {
-            PP_HIPCHK(ctx, hipMalloc(&fresh[a], (size_t)n * RG_SIZE[a]));
-            A.in[a] = src[a];
-            A.out[a] = fresh[a];
-        }
+        RawArrays G;  // (the object's from the start: an early return frees them with it)
+        if ((rc = G.alloc_records(*P, n))) return rc;
+        const RgArrays A{{src.flag, src.read_id, src.contig, src.ref_start, src.nm, src.seq_off, src.seq_len, src.cig_off, src.n_cig},
+                         {G.flag, G.read_id, G.contig, G.ref_start, G.nm, G.seq_off, G.seq_len, G.cig_off, G.n_cig}};
         void *d_rank_new, *d_amap;
         if ((rc = T.get(ctx, &d_rank_new, ((size_t)n + 1) * 4)) || (rc = T.get(ctx, &d_amap, (size_t)std::max<u32>(1, n_al) * 4))) return rc;
         if ((rc = timer.begin(RG_GATHER))) return rc;
@@ -384,23 +316,14 @@ extern "C" int pp_batch_regroup(pp_ctx *ctx, const pp_raw_batch *raw, int mem, p
         P->amap.resize(n_al);
         if (n_al && (rc = fetch(ctx, d_amap, P->amap.data(), n_al))) return rc;
         PP_HIPCHK(ctx, hipStreamSynchronize(st));
-        for (int a = 0; a < 9; a++) {  // (an uploaded source array has been read: it gives way)
-            if (P->d[a]) (void)hipFree(P->d[a]);
-            P->d[a] = fresh[a];
-            fresh[a] = nullptr;
-        }
-        pp_raw_batch &V = P->view;
-        V.flag = (const uint16_t *)P->d[0]; V.read_id = (const uint64_t *)P->d[1]; V.contig = (const u32 *)P->d[2];
-        V.ref_start = (const u32 *)P->d[3]; V.nm = (const u32 *)P->d[4]; V.seq_off = (const uint64_t *)P->d[5];
-        V.seq_len = (const u32 *)P->d[6]; V.cig_off = (const uint64_t *)P->d[7]; V.n_cig = (const u32 *)P->d[8];
+        for (const void *q : A.in) P->release(q);  // (the stream is synchronised: an uploaded source array has been read and gives way)
+        P->view = G.view(n, src.seq_bytes, src.n_cig_total);
+        P->view.seq = src.seq;  // (not moved)
+        P->view.cigar = src.cigar;
     }
     PP_HIPCHK(ctx, hipStreamSynchronize(st));
-    if (timer.on) {
-        if ((rc = timer.sums(P->ms, 3))) return rc;
-        P->timed = true;
-    }
-    guard.release();
-    *out = P;
+    if ((rc = P->t.take(timer))) return rc;
+    *out = P.release();
     return PP_OK;
 }
 

@@ -26,16 +26,15 @@
 
 extern "C" int pp_ingest_line_error_(const char *path, const char *line, size_t n, uint64_t line_no, char *err, size_t errlen);
 
-struct pp_sam {
-    pp_ctx *ctx = nullptr;
-    // flag read_id contig ref_start nm seq_off seq_len cig_off n_cig cigar | name_off name_len rname_off rname_len line
-    void *d[15] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    void *text = nullptr;              // the owned device copy of the text, zeros behind n_bytes
+struct pp_sam : DevOwner {
+    using DevOwner::DevOwner;
+    RawArrays a;                       // a.seq: the owned device copy of the text, zeros behind n_bytes
+    u64 *name_off = nullptr, *rname_off = nullptr;  // the QNAME and RNAME ranges, in the text
+    u32 *name_len = nullptr, *rname_len = nullptr, *line = nullptr;
     uint64_t n_bytes = 0;
     pp_raw_batch view{};
     std::vector<uint8_t> pass;         // HOST: one byte per aligned record, 0 = ZP:Z:fail
-    bool timed = false;
-    float ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  // the device copy | newline index | scan | scans and compaction | CIGAR pack
+    StageMs<5> t;                      // the device copy | newline index | scan | scans and compaction | CIGAR pack
 };
 
 namespace {
@@ -218,58 +217,45 @@ const char *limit_text(u32 why) {
 
 }  // namespace
 
-extern "C" void pp_sam_free(pp_sam *s) {
-    if (!s) return;
-    if (s->ctx) (void)hipSetDevice(s->ctx->device);
-    for (void *q : s->d)
-        if (q) (void)hipFree(q);
-    if (s->text) (void)hipFree(s->text);
-    delete s;
-}
+extern "C" void pp_sam_free(pp_sam *s) { delete s; }
 
 extern "C" void pp_sam_raw(const pp_sam *s, pp_raw_batch *out) {
     if (out) *out = s ? s->view : pp_raw_batch{};
 }
 
-extern "C" uint64_t *pp_sam_read_id(pp_sam *s) { return s ? (uint64_t *)s->d[1] : nullptr; }
-extern "C" uint32_t *pp_sam_contig(pp_sam *s) { return s ? (uint32_t *)s->d[2] : nullptr; }
+extern "C" uint64_t *pp_sam_read_id(pp_sam *s) { return s ? (uint64_t *)s->a.read_id : nullptr; }
+extern "C" uint32_t *pp_sam_contig(pp_sam *s) { return s ? s->a.contig : nullptr; }
 
-static void sam_ranges(const pp_sam *s, int off_at, const uint8_t **bytes_dev, uint64_t *n_bytes, const uint64_t **off, const uint32_t **len) {
-    if (bytes_dev) *bytes_dev = s ? (const uint8_t *)s->text : nullptr;
+static void sam_ranges(const pp_sam *s, const u64 *r_off, const u32 *r_len, const uint8_t **bytes_dev, uint64_t *n_bytes, const uint64_t **off,
+                       const uint32_t **len) {
+    if (bytes_dev) *bytes_dev = s ? s->a.seq : nullptr;
     if (n_bytes) *n_bytes = s ? s->n_bytes : 0;
-    if (off) *off = s ? (const uint64_t *)s->d[off_at] : nullptr;
-    if (len) *len = s ? (const uint32_t *)s->d[off_at + 1] : nullptr;
+    if (off) *off = (const uint64_t *)r_off;
+    if (len) *len = r_len;
 }
 
 extern "C" void pp_sam_names(const pp_sam *s, const uint8_t **bytes_dev, uint64_t *n_bytes, const uint64_t **off, const uint32_t **len) {
-    sam_ranges(s, 10, bytes_dev, n_bytes, off, len);
+    sam_ranges(s, s ? s->name_off : nullptr, s ? s->name_len : nullptr, bytes_dev, n_bytes, off, len);
 }
 
 extern "C" void pp_sam_rnames(const pp_sam *s, const uint8_t **bytes_dev, uint64_t *n_bytes, const uint64_t **off, const uint32_t **len) {
-    sam_ranges(s, 12, bytes_dev, n_bytes, off, len);
+    sam_ranges(s, s ? s->rname_off : nullptr, s ? s->rname_len : nullptr, bytes_dev, n_bytes, off, len);
 }
 
-extern "C" const uint32_t *pp_sam_lines(const pp_sam *s) { return s ? (const uint32_t *)s->d[14] : nullptr; }
+extern "C" const uint32_t *pp_sam_lines(const pp_sam *s) { return s ? s->line : nullptr; }
 
 extern "C" void pp_sam_pass(const pp_sam *s, const uint8_t **zp, uint64_t *n_aligned) {
     if (zp) *zp = (s && !s->pass.empty()) ? s->pass.data() : nullptr;
     if (n_aligned) *n_aligned = s ? s->pass.size() : 0;
 }
 
-extern "C" int pp_sam_kernel_ms(const pp_sam *s, float *ms) {
-    if (!s || !ms) return PP_ERR_ARG;
-    if (!s->timed) return s->ctx->fail(PP_ERR_ARG, "pp_sam_kernel_ms: the context had no profiling on when the text was decoded (pp_ctx_set_profiling)");
-    *ms = s->ms[1] + s->ms[2] + s->ms[3] + s->ms[4];  // (the kernels: the copy of the text is no kernel)
-    return PP_OK;
+extern "C" int pp_sam_kernel_ms(const pp_sam *s, float *ms) {  // (from stage 1: the copy of the text is no kernel)
+    return s ? s->t.total(s->ctx, "pp_sam_kernel_ms", "when the text was decoded", ms, 1) : PP_ERR_ARG;
 }
 
 // (internal hook, not part of the header: tools/sam_records_timing.py) the time by stage: the device copy of the text | newline index |
 // scan | scans and compaction | CIGAR pack
-extern "C" int pp_sam_stage_ms_(const pp_sam *s, float *ms5) {
-    if (!s || !ms5 || !s->timed) return PP_ERR_ARG;
-    for (int i = 0; i < 5; i++) ms5[i] = s->ms[i];
-    return PP_OK;
-}
+extern "C" int pp_sam_stage_ms_(const pp_sam *s, float *ms5) { return s ? s->t.stages(ms5) : PP_ERR_ARG; }
 
 extern "C" int pp_sam_records(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, pp_sam **out, uint64_t *bad_line) {
     if (!ctx) return PP_ERR_ARG;
@@ -285,33 +271,29 @@ extern "C" int pp_sam_records(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes
     hipStream_t st = ctx->stream;
     const u64 size = n_bytes;
 
-    pp_sam *P = new pp_sam;
-    P->ctx = ctx;
-    std::unique_ptr<pp_sam, void (*)(pp_sam *)> guard(P, pp_sam_free);  // (every early return releases what was made so far)
+    std::unique_ptr<pp_sam> P(new pp_sam(ctx));
+    RawArrays &A = P->a;
     CallScratch T;
     NlBufs N;
     StageTimer timer(ctx, ctx->profiling != 0 && size != 0);
     int rc;
     // ---- the owned copy: the text, zeros up to a multiple of NL_BLOCK and 64 more ----
     const u64 n_blk = (size + NL_BLOCK - 1) / NL_BLOCK, padded = std::max<u64>(1, n_blk) * NL_BLOCK;
-    PP_HIPCHK(ctx, hipMalloc(&P->text, (size_t)(padded + 64)));
+    if ((rc = P->alloc(A.seq, (size_t)(padded + 64)))) return rc;
     if ((rc = timer.begin(0))) return rc;
-    if (size) PP_HIPCHK(ctx, hipMemcpyAsync(P->text, text, (size_t)size, mem == PP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
-    PP_HIPCHK(ctx, hipMemsetAsync((u8 *)P->text + size, 0, (size_t)(padded + 64 - size), st));
+    if (size) PP_HIPCHK(ctx, hipMemcpyAsync(A.seq, text, (size_t)size, mem == PP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+    PP_HIPCHK(ctx, hipMemsetAsync(A.seq + size, 0, (size_t)(padded + 64 - size), st));
     if ((rc = timer.end())) return rc;
-    const u8 *const d_text = (const u8 *)P->text;
+    const u8 *const d_text = A.seq;
     P->n_bytes = size;
-    pp_raw_batch &V = P->view;
-    V.seq = d_text;
-    V.seq_bytes = size;
-    auto done = [&]() {
-        guard.release();
-        *out = P;
+    auto done = [&](u64 n_rec, u64 n_cig_total) {  // (an empty batch: the text and no other array)
+        P->view = A.view(n_rec, size, n_cig_total);
+        *out = P.release();
         return PP_OK;
     };
     if (size == 0) {  // no text: an empty batch
         PP_HIPCHK(ctx, hipStreamSynchronize(st));
-        return done();
+        return done(0, 0);
     }
     // ---- the newline index ----
     u64 n_nl = 0;
@@ -335,16 +317,10 @@ extern "C" int pp_sam_records(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes
         return rc;
     PP_HIPCHK(ctx, hipMemsetAsync(d_status, 0xFF, 8, st));
     if ((rc = timer.begin(2))) return rc;
-    {
-        const u32 stage_bytes = tok_stage_for(size, n_lines);
-        const dim3 grid((unsigned)((n_lines + 63) / 64));
-        if (stage_bytes == TOK_STAGE_S) hipLaunchKernelGGL(k_sam_scan<TOK_STAGE_S>, grid, dim3(64), 0, st, d_text, size, d_nl, n_nl, n_lines,
-                                                           (SamLine *)d_rec, (u32 *)d_kind, (u64 *)d_status);
-        else if (stage_bytes == TOK_STAGE_M) hipLaunchKernelGGL(k_sam_scan<TOK_STAGE_M>, grid, dim3(64), 0, st, d_text, size, d_nl, n_nl, n_lines,
-                                                                (SamLine *)d_rec, (u32 *)d_kind, (u64 *)d_status);
-        else hipLaunchKernelGGL(k_sam_scan<TOK_STAGE_L>, grid, dim3(64), 0, st, d_text, size, d_nl, n_nl, n_lines, (SamLine *)d_rec,
-                                (u32 *)d_kind, (u64 *)d_status);
-    }
+    with_stage(tok_stage_for(size, n_lines), [&](auto stage) {
+        hipLaunchKernelGGL(k_sam_scan<decltype(stage)::value>, dim3((unsigned)((n_lines + 63) / 64)), dim3(64), 0, st, d_text, size, d_nl, n_nl,
+                           n_lines, (SamLine *)d_rec, (u32 *)d_kind, (u64 *)d_status);
+    });
     if ((rc = timer.end()) || (rc = timer.begin(3))) return rc;
     hipLaunchKernelGGL(k_sam_place<false>, dim3(nb), dim3(SAM_BLOCK), 0, st, n_lines, (const u32 *)d_kind, (const SamLine *)d_rec, d_nl, (u64 *)d_blk3,
                        SamOut{});
@@ -378,45 +354,32 @@ extern "C" int pp_sam_records(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes
     const u64 n_rec = totals[0], n_al = totals[1], n_cig_total = totals[2];
     if (n_rec == 0) {  // header lines only: an empty batch
         PP_HIPCHK(ctx, hipStreamSynchronize(st));
-        if (timer.on) {
-            if ((rc = timer.sums(P->ms, 5))) return rc;
-            P->timed = true;
-        }
-        return done();
+        if ((rc = P->t.take(timer))) return rc;
+        return done(0, 0);
     }
     const u32 n = (u32)n_rec;
 
     // ---- the per-record arrays, the CIGAR runs ----
-    const size_t rbytes[15] = {(size_t)n * 2, (size_t)n * 8, (size_t)n * 4, (size_t)n * 4, (size_t)n * 4, (size_t)n * 8, (size_t)n * 4, (size_t)n * 8,
-                               (size_t)n * 4, n_cig_total ? (size_t)n_cig_total * 4 : 16, (size_t)n * 8, (size_t)n * 4, (size_t)n * 8, (size_t)n * 4,
-                               (size_t)n * 4};
-    for (int i = 0; i < 15; i++) PP_HIPCHK(ctx, hipMalloc(&P->d[i], rbytes[i]));
-    PP_HIPCHK(ctx, hipMemsetAsync(P->d[1], 0, (size_t)n * 8, st));  // read_id and contig: the caller's (pp_names_ids)
-    PP_HIPCHK(ctx, hipMemsetAsync(P->d[2], 0, (size_t)n * 4, st));
+    if ((rc = A.alloc_records(*P, n)) || (rc = P->alloc(A.cigar, (size_t)n_cig_total)) || (rc = P->alloc(P->name_off, n)) ||
+        (rc = P->alloc(P->name_len, n)) || (rc = P->alloc(P->rname_off, n)) || (rc = P->alloc(P->rname_len, n)) || (rc = P->alloc(P->line, n)))
+        return rc;
+    PP_HIPCHK(ctx, hipMemsetAsync(A.read_id, 0, (size_t)n * 8, st));  // read_id and contig: the caller's (pp_names_ids)
+    PP_HIPCHK(ctx, hipMemsetAsync(A.contig, 0, (size_t)n * 4, st));
     void *d_pass;
     if ((rc = T.get(ctx, &d_pass, (size_t)n_al))) return rc;
-    SamOut O{(uint16_t *)P->d[0], (u32 *)P->d[3], (u32 *)P->d[4], (u32 *)P->d[6], (u32 *)P->d[8], (u32 *)P->d[11], (u32 *)P->d[13], (u32 *)P->d[14],
-             (u64 *)P->d[5], (u64 *)P->d[7], (u64 *)P->d[10], (u64 *)P->d[12], (u8 *)d_pass};
+    SamOut O{A.flag, A.ref_start, A.nm, A.seq_len, A.n_cig, P->name_len, P->rname_len, P->line,
+             A.seq_off, A.cig_off, P->name_off, P->rname_off, (u8 *)d_pass};
     if ((rc = timer.begin(3))) return rc;
     hipLaunchKernelGGL(k_sam_place<true>, dim3(nb), dim3(SAM_BLOCK), 0, st, n_lines, (const u32 *)d_kind, (const SamLine *)d_rec, d_nl,
                        (u64 *)d_blk3off, O);
     if ((rc = timer.end()) || (rc = timer.begin(4))) return rc;
-    hipLaunchKernelGGL(k_sam_cigar, dim3((n + 255u) / 256u), dim3(256), 0, st, n, d_text, d_nl, (const SamLine *)d_rec, (const u32 *)P->d[14],
-                       (const u64 *)P->d[7], (u32 *)P->d[9]);
+    hipLaunchKernelGGL(k_sam_cigar, dim3((n + 255u) / 256u), dim3(256), 0, st, n, d_text, d_nl, (const SamLine *)d_rec, (const u32 *)P->line,
+                       (const u64 *)A.cig_off, A.cigar);
     if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     P->pass.resize((size_t)n_al);
     if (n_al) PP_HIPCHK(ctx, hipMemcpyAsync(P->pass.data(), d_pass, (size_t)n_al, hipMemcpyDeviceToHost, st));
     PP_HIPCHK(ctx, hipStreamSynchronize(st));  // the caller's text may be released, the scratch goes away
-    if (timer.on) {
-        if ((rc = timer.sums(P->ms, 5))) return rc;
-        P->timed = true;
-    }
-    V.n_rec = n;
-    V.flag = (const uint16_t *)P->d[0]; V.read_id = (const uint64_t *)P->d[1]; V.contig = (const u32 *)P->d[2]; V.ref_start = (const u32 *)P->d[3];
-    V.nm = (const u32 *)P->d[4]; V.seq_off = (const uint64_t *)P->d[5]; V.seq_len = (const u32 *)P->d[6]; V.cig_off = (const uint64_t *)P->d[7];
-    V.n_cig = (const u32 *)P->d[8];
-    V.cigar = (const u32 *)P->d[9];
-    V.n_cig_total = n_cig_total;
-    return done();
+    if ((rc = P->t.take(timer))) return rc;
+    return done(n, n_cig_total);
 }

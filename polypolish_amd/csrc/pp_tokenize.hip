@@ -834,16 +834,10 @@ static int ingest_text(pp_dev_ingest *D, const char *path, const char *text, u64
         ENS(d_isaln, n_lines * 4);
         ENS(d_recofline, (n_lines + 1) * 4);
         ContigTable T{(const u32 *)D->t_slots.p, (const u32 *)D->t_off.p, (const u8 *)D->t_names.p, D->t_mask};
-        {
-            const u32 stage_bytes = tok_stage_for(size, n_lines);
-            const dim3 grid((unsigned)((n_lines + 63) / 64));
-            if (stage_bytes == TOK_STAGE_S) hipLaunchKernelGGL(k_tok_parse<TOK_STAGE_S>, grid, dim3(64), 0, st, d_text, size,
-                           (const u64 *)D->d_nl.p, n_nl, n_lines, T, (LineRec *)D->d_rec.p, (u32 *)D->d_isaln.p, d_status);
-            else if (stage_bytes == TOK_STAGE_M) hipLaunchKernelGGL(k_tok_parse<TOK_STAGE_M>, grid, dim3(64), 0, st, d_text, size,
-                           (const u64 *)D->d_nl.p, n_nl, n_lines, T, (LineRec *)D->d_rec.p, (u32 *)D->d_isaln.p, d_status);
-            else hipLaunchKernelGGL(k_tok_parse<TOK_STAGE_L>, grid, dim3(64), 0, st, d_text, size,
-                           (const u64 *)D->d_nl.p, n_nl, n_lines, T, (LineRec *)D->d_rec.p, (u32 *)D->d_isaln.p, d_status);
-        }
+        with_stage(tok_stage_for(size, n_lines), [&](auto stage) {
+            hipLaunchKernelGGL(k_tok_parse<decltype(stage)::value>, dim3((unsigned)((n_lines + 63) / 64)), dim3(64), 0, st, d_text, size,
+                               (const u64 *)D->d_nl.p, n_nl, n_lines, T, (LineRec *)D->d_rec.p, (u32 *)D->d_isaln.p, d_status);
+        });
         if ((rc = scan_u32<u32>(ctx, D->d_sums, D->d_sumsoff, (const u32 *)D->d_isaln.p, n_lines, (u32 *)D->d_recofline.p))) return rc;
         if ((rc = fetch(ctx, (const u32 *)D->d_recofline.p + n_lines, &n_aln))) return rc;
     }

@@ -220,7 +220,16 @@ NO_PROFILING = {     # the library's text when kernel_ms() is asked of an object
     "BamRecords": "pp_bam_kernel_ms: the context had no profiling on when the records were decoded (pp_ctx_set_profiling)",
     "Names": "pp_names_kernel_ms: the context had no profiling on at the table's last pp_names_ids (pp_ctx_set_profiling)",
     "GatedBatch": "pp_gated_kernel_ms: the context had no profiling on when the batch was gated (pp_ctx_set_profiling)",
-    "PreparedBatch": "pp_prepared_kernel_ms: the context had no profiling on when the batch was prepared (pp_ctx_set_profiling)"}
+    "PreparedBatch": "pp_prepared_kernel_ms: the context had no profiling on when the batch was prepared (pp_ctx_set_profiling)",
+    "SamRecords": "pp_sam_kernel_ms: the context had no profiling on when the text was decoded (pp_ctx_set_profiling)",
+    "Regrouped": "pp_regrouped_kernel_ms: the context had no profiling on when the batch was regrouped (pp_ctx_set_profiling)",
+    "Bgzf": "pp_bgzf_kernel_ms: the context had no profiling on when the blocks were inflated (pp_ctx_set_profiling)",
+    "BamTagged": "pp_bam_out_kernel_ms: the context had no profiling on when the records were tagged (pp_ctx_set_profiling)",
+    "BgzfDeflated": "pp_bgzf_out_kernel_ms: the context had no profiling on when the bytes were compressed (pp_ctx_set_profiling)"}
+STAGE_HOOKS = {      # the internal per-stage hook of a class, its stages, the first one kernel_ms() counts (PreparedBatch has no hook)
+    "BamOffsets": ("pp_bam_offs_stage_ms_", 3, 0), "BamRecords": ("pp_bam_stage_ms_", 3, 0), "Names": ("pp_names_stage_ms_", 5, 0),
+    "GatedBatch": ("pp_gated_stage_ms_", 3, 0), "SamRecords": ("pp_sam_stage_ms_", 5, 1), "Regrouped": ("pp_regrouped_stage_ms_", 3, 0),
+    "Bgzf": ("pp_bgzf_stage_ms_", 3, 0), "BamTagged": ("pp_bam_out_stage_ms_", 3, 0), "BgzfDeflated": ("pp_bgzf_out_stage_ms_", 3, 0)}
 
 
 def _fetch(pp, c, addr, n, dt):
@@ -248,9 +257,15 @@ def test_every_owned_object_reads_back_what_a_hand_written_download_reads(pp, pr
     """BamOffsets -> BamRecords -> Names.ids -> gate_records -> prepare_batch on device addresses, over three records -- an aligned
     one, a secondary one of the same read with SEQ "*", an unaligned one (zp is shorter than n_rec) -- and over a BAM that is a
     header only: host() of every object is what pp_ctx_download gives for the same pointers, the values are the models', close()
-    twice is harmless, and kernel_ms() needs the context's profiling."""
+    twice is harmless, and kernel_ms() needs the context's profiling.  The other five owned classes over the same records and over the
+    header alone: SamRecords on their SAM text, Regrouped, BamTagged -> BgzfDeflated -> Bgzf.  With profiling kernel_ms() is the
+    sum of the stages the class's hook reports -- pp_sam's without its first, the copy of the text."""
+    import bam_tag_model as tm
+    import bgzf_deflate_model as dm
     import gate_model as gm
     import names_model as nm
+    import regroup_model as rm
+    import sam_records_model as sm
     from layout_check import same_records
     M = (8 << 4)
     recs = [bm.record(b"a", 0, 0, 5, [M], "ACGTACGT", bm.aux("NM", "C", 0)), bm.record(b"a", 256, 0, 20, [M], "", bm.aux("NM", "C", 1)),
@@ -321,10 +336,74 @@ def test_every_owned_object_reads_back_what_a_hand_written_download_reads(pp, pr
         _same_arrays(got, dict(_fetch_batch(pp, c, empty.raw(), pp.RAW_FIELDS, 0, 0, 0), name_off=np.zeros(0, np.uint64), name_len=np.zeros(0, np.uint32)))
         assert (empty.n_rec, empty.seq_bytes, empty.n_cig_total, len(empty.zp)) == (0, 0, 0, 0)
 
+        # ---- the other five classes.  The same three records as SAM text, and a text that is its header only ----
+        head = b"@HD\tVN:1.6\n@SQ\tSN:c0\tLN:64\n"
+        three = head + (b"a\t0\tc0\t6\t60\t8M\t*\t0\t0\tACGTACGT\t*\tNM:i:0\n" b"a\t256\tc0\t21\t60\t8M\t*\t0\t0\t*\t*\tNM:i:1\n"
+                        b"u\t4\t*\t0\t0\t*\t*\t0\t0\tACGT\t*\n")
+        for text in (three, head):
+            sam = pp.SamRecords(c, text)
+            made.append(sam)
+            want = sm.decode(text)
+            by_hand = _fetch_batch(pp, c, sam.raw(), pp.RAW_FIELDS, sam.n_rec, sam.seq_bytes, sam.n_cig_total)
+            for k, r in (("name", sam.names()["names"]), ("rname", sam.rnames()["names"])):
+                by_hand[k + "_off"], by_hand[k + "_len"] = _fetch(pp, c, r[1], sam.n_rec, np.uint64), _fetch(pp, c, r[2], sam.n_rec, np.uint32)
+            by_hand["line"] = _fetch(pp, c, pp.lib().pp_sam_lines(sam._p), sam.n_rec, np.uint32)
+            got = sam.host()
+            _same_arrays(got, by_hand)
+            sm.same(got, want)
+            assert sam.zp.dtype == np.uint8 and np.array_equal(sam.zp, want["zp"])
+            assert (sam.n_rec, sam.seq_bytes, sam.n_cig_total) == (len(want["flag"]), len(text), len(want["cigar"]))
+        for k in ("flag", "ref_start", "nm", "seq_len", "n_cig", "cigar", "zp"):      # (the text says what the BAM records say)
+            assert np.array_equal(sm.decode(three)[k], want_raw[k]), k
+        assert sam.n_rec == 0 and sm.seq_bytes(sm.decode(three)) == [b"ACGTACGT", b"", b"ACGT"]
+
+        # regrouped: the three records from host memory (uploaded into the object; nothing moves), and the empty decode's null arrays
+        rg_empty = None
+        for src, raw_in, mem in ((want_raw, {k: want_raw[k] for k, _ in pp.RAW_FIELDS}, pp.MEM_HOST), (bm.decode(hdr, []), empty.raw(), pp.MEM_DEVICE)):
+            rg_empty = rg = pp.regroup_records(c, raw_in, mem)
+            made.append(rg)
+            want = rm.regroup(src)
+            got = rg.host()
+            _same_arrays(got, _fetch_batch(pp, c, rg.raw(), pp.RAW_FIELDS, rg.n_rec, rg.seq_bytes, rg.n_cig_total))
+            rm.same_raw(got, want["raw"])
+            assert np.array_equal(got["seq"], src["seq"]) and np.array_equal(got["cigar"], src["cigar"])
+            assert rg.counts() == want["counts"] and rg.perm().dtype == np.uint32 and np.array_equal(rg.perm(), want["perm"])
+        assert rg_empty.n_rec == 0 and rg_empty.raw() == empty.raw()
+
+        # tagged -> compressed -> inflated again: the three records with the second one failed, and the header alone
+        for b, rec_off, src, off, passed, mem in (((dp, nb), (offs.ptr, 3), data, want_off, [1, 0], pp.MEM_DEVICE),
+                                                  (hdr, none.host(), hdr, [], None, pp.MEM_HOST)):
+            u = tm.tagged(src, len(hdr), off, passed)
+            t = pp.BamTagged(c, b, len(hdr), rec_off, passed, mem)
+            made.append(t)
+            assert t.host().tobytes() == tm.frame(u) and np.array_equal(t.host(), _fetch(pp, c, t.bytes_ptr, t.n_bytes, np.uint8))
+            assert t.counts == ((1, 1, 1) if passed else (0, 0, 1))
+            z = t.deflate()
+            made.append(z)
+            want_file, want_blk, want_counts = dm.deflate_file(u)
+            assert z.host().tobytes() == want_file and np.array_equal(z.host(), _fetch(pp, c, z.bytes_ptr, z.n_bytes, np.uint8))
+            assert z.blk_off().tolist() == want_blk and np.array_equal(z.blk_off(), _fetch(pp, c, z.blk_off_ptr, z.n_blocks + 1, np.uint64))
+            assert list(z.counts) == want_counts
+            back = pp.Bgzf(c, (z.bytes_ptr, z.n_bytes), (z.blk_off_ptr, z.n_blocks), mem=pp.MEM_DEVICE)
+            made.append(back)
+            assert back.host().tobytes() == u and np.array_equal(back.host(), _fetch(pp, c, back.bytes_ptr, back.n_bytes, np.uint8))
+        no_blocks = pp.Bgzf(c, b"", [])
+        made.append(no_blocks)
+        assert no_blocks.n_bytes == 0 and len(no_blocks.host()) == 0
+
         for o in made:
-            if profiling and o is not empty:   # (a decode of no records runs no kernel and times none: it answers as without profiling)
+            # (a decode or a regroup of no records runs no kernel and times none: it answers as without profiling)
+            if profiling and o is not empty and o is not rg_empty:
                 ms = o.kernel_ms()
                 assert isinstance(ms, float) and ms >= 0, o
+                if type(o).__name__ in STAGE_HOOKS:      # kernel_ms() is the sum of the stages that count, in float as the library adds
+                    hook, n_stages, first = STAGE_HOOKS[type(o).__name__]
+                    stages = (C.c_float * n_stages)()
+                    assert getattr(pp.lib(), hook)(o._p, stages) == 0, o
+                    total = np.float32(0)
+                    for v in stages[first:]:
+                        total = np.float32(total + np.float32(v))
+                    assert ms == float(total), (o, ms, list(stages))
             else:
                 with pytest.raises(pp.PolypolishError) as e:
                     o.kernel_ms()
