@@ -22,7 +22,8 @@
  * BAM bytes -> raw records, the chain's front end) -> pp_names -> pp_filter_records -> (pp_batch_regroup, for
  * a file whose reads do not stand together ->) pp_batch_gate -> pp_batch_prepare -> pp_polish_*.  pp_sam_records
  * is the chain's second front end: SAM text -> the same raw records, for a caller who wants a link of the chain
- * (or a step of their own) between the text and the gate.
+ * (or a step of their own) between the text and the gate.  The chain writes the filter's verdicts back in
+ * either form: pp_bam_tagged as a BAM file, pp_sam_tagged as SAM text; pp_bgzf_deflate compresses both.
  *
  * Conventions: plain pointers and sizes, no C++/torch types.  Every function returns PP_OK or a
  * PP_ERR_* code and never exits the process; pp_last_error() holds the message the reference
@@ -630,6 +631,54 @@ void pp_bgzf_out_counts(const pp_bgzf_out *o, uint64_t *stored, uint64_t *fixed,
 int pp_bgzf_out_write(const pp_bgzf_out *o, const char *path); /* download in slices, write the file */
 int pp_bgzf_out_kernel_ms(const pp_bgzf_out *o, float *ms);
 void pp_bgzf_out_free(pp_bgzf_out *o);
+
+/* The WRITE side of the record chain for a caller who holds SAM TEXT: the filter's verdicts written back as text, on the device -- the
+ * text twin of pp_bam_tagged.  The output is, byte for byte and for every text and every `pass`, what pp_filter_write_text writes
+ * (filter_sam, src/filter.rs:309-349); that host routine is the definition, and it needs the whole text in host memory.
+ *   lines        are cut at '\n'; one trailing '\r' is dropped from a line's content.  Every output line ends in '\n': also a last
+ *                line without a newline, and one that ends in a bare '\r'.  An empty line stays an empty line; an empty text gives an
+ *                empty output.
+ *   aligned      a line is an ALIGNED RECORD when it is not empty, does not begin with '@', has a tab, and its second column parses
+ *                as parse::<u32> (a leading '+' is fine, 4294967296 is not) with bit 2 clear.  Nothing else about the line is looked
+ *                at: this is NOT the eleven-column predicate of pp_sam_records, and a line that decode would refuse is copied like any
+ *                other.  On any text pp_sam_records accepts the two agree.
+ *   pass         pass[0, n_pass): HOST memory whatever `mem`, one byte per aligned record in file order -- the numbering of pp_sam_pass
+ *                and of pp_filter_records' pass1 / pass2.  An aligned record whose byte is 0 gets the ten bytes "\tZP:Z:fail" between
+ *                its content and its '\n'; one that already carries the tag gets a second one (the reference pushes the field without
+ *                looking).  `pass` is the FILTER'S OWN verdict, not ANDed with pp_sam_pass.
+ *   the rest     header lines, unaligned lines, lines that are no records and bytes >= 0x80 are copied as they are.  There is nothing
+ *                in the bytes that could be refused.
+ *   memory       mem = PP_MEM_HOST or PP_MEM_DEVICE holds for `text`.  Host text is uploaded and the copy is released before the call
+ *                returns; device text is borrowed for the call only and read where it lies, at any alignment.  No byte outside
+ *                [0, n_bytes) is loaded, by a wide load either: a PP_MEM_DEVICE text may end where its allocation ends, and no byte
+ *                behind n_bytes can change a result.  pp_sam_tagged_records reads the pp_sam's own device copy of the text: no second
+ *                upload; the pp_sam stays valid and is the caller's to free.  The object owns the output only.
+ *   errors       PP_ERR_ARG: null arguments, PP_MEM_PEER, text == NULL with n_bytes > 0, pass == NULL with aligned records present,
+ *                n_pass other than the number of aligned records ("N verdicts for M aligned records", pp_filter_write_text's
+ *                sentence, in pp_last_error).  PP_ERR_LIMIT: n_bytes >= 2^40, 2^32-1 or more lines.  After a refusal there is no
+ *                object, and the context serves the next call.
+ *   geometry     pass A takes 1,024 lines per workgroup; pass B, the copy, gives every workgroup a tile of 16,384 OUTPUT bytes and
+ *                writes it with 16-byte stores aligned on the output (the allocation is rounded up to 16; spare bytes are zeros).  A
+ *                line longer than a tile spans workgroups; a tile in which more than 2,048 lines start takes a second, slower way
+ *                to the same bytes.
+ * The context's stream has been synchronised when either call returns: host inputs may be released.  Two calls on the same input give
+ * identical bytes.
+ *   pp_sam_out_bytes      the text (DEVICE, borrowed until pp_sam_out_free).  There is no compressor call of its own:
+ *                         pp_bgzf_deflate(ctx, dev, n_bytes, PP_MEM_DEVICE, ...) on these bytes makes the bgzipped file, and
+ *                         pp_bgzf_inflate with pp_bgzf_out_blk_off reads it back
+ *   pp_sam_out_counts     aligned records that passed, that failed, and the lines
+ *   pp_sam_out_write      as pp_bam_out_write: downloads the text in slices and writes it to `path`; PP_ERR_QUIT "unable to write
+ *                         alignments to ..." for a path that cannot be created or written, the code and the words of pp_filter_write
+ *   pp_sam_out_kernel_ms  as pp_gated_kernel_ms
+ * The object belongs to its context and is freed before it. */
+typedef struct pp_sam_out pp_sam_out;
+int pp_sam_tagged(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, const uint8_t *pass, uint64_t n_pass, pp_sam_out **out);
+int pp_sam_tagged_records(pp_ctx *ctx, const pp_sam *s, const uint8_t *pass, uint64_t n_pass, pp_sam_out **out); /* the object's own device copy of the text */
+void pp_sam_out_bytes(const pp_sam_out *o, const uint8_t **dev, uint64_t *n_bytes); /* DEVICE, borrowed until pp_sam_out_free */
+void pp_sam_out_counts(const pp_sam_out *o, uint64_t *pass_count, uint64_t *fail_count, uint64_t *n_lines);
+int pp_sam_out_write(const pp_sam_out *o, const char *path); /* download in slices, write the file */
+int pp_sam_out_kernel_ms(const pp_sam_out *o, float *ms);
+void pp_sam_out_free(pp_sam_out *o);
 
 /* What an alignment file holds, told by its CONTENT: the commands (pp_polish_files, pp_filter_files, pp_filter_polish_files) take SAM
  * text as before and BAM through the record chain above, and ask this.  HOST, no context; reads only the head of the file.

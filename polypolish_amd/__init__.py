@@ -901,6 +901,7 @@ class SamRecords(_Owned):
       .host()        numpy copies of the arrays, and "name_off" / "name_len" / "rname_off" / "rname_len" / "line"
       .kernel_ms()   HIP-event time of the decode's kernels (the context had set_profiling on); .stage_ms(): copy | newline_index |
                      scan | place | cigar
+      .tagged(pass_) pp_sam_tagged_records: the text with the filter's verdicts written back -> SamOut (no second upload)
     A refused text raises PolypolishError with .bad_record = the 0-based line (None where the refusal names none)."""
     _free, _kernel_ms = "pp_sam_free", "pp_sam_kernel_ms"
 
@@ -950,6 +951,10 @@ class SamRecords(_Owned):
 
     def stage_ms(self):
         return self._stage_ms("pp_sam_stage_ms_", ("copy", "newline_index", "scan", "place", "cigar"), " when the text was decoded")
+
+    def tagged(self, pass_):
+        """pp_sam_tagged_records: the object's own device copy of the text with the verdicts written back -> SamOut"""
+        return SamOut(self._ctx, pass_=pass_, records=self)
 
 
 class BamTagged(_Owned):
@@ -1047,6 +1052,70 @@ class BgzfDeflated(_Owned):
 
     def stage_ms(self):
         return self._stage_ms("pp_bgzf_out_stage_ms_", ("pieces", "scan", "place"), " when the bytes were compressed")
+
+
+class SamOut(_Owned):
+    """pp_sam_tagged / pp_sam_tagged_records: the filter's verdicts written back as SAM text in DEVICE memory, owned by this object --
+    byte for byte what pp_filter_write_text writes; the text twin of BamTagged.  Made by SamOut.tagged(ctx, text, pass_, mem=...) or
+    SamRecords.tagged(pass_).
+      text           mem = MEM_HOST: bytes / a uint8 array; MEM_DEVICE: (device address, n_bytes), borrowed for the call
+      pass_          None or one byte per ALIGNED line (host): the filter's own verdict, filter_records(...)["pass"][f]
+      .dev()         (device address, n_bytes) of the text: what Bgzf / BgzfDeflated / SamRecords take with mem=MEM_DEVICE
+      .bytes()       the text as bytes (a download)
+      .counts()      (passed, failed, lines)
+      .write(path)   pp_sam_out_write: the file on disk
+      .deflate()     pp_bgzf_deflate on the device bytes -> BgzfDeflated: the bgzipped file
+      .kernel_ms()   HIP-event time of the kernels (the context had set_profiling on); .stage_ms(): newline_index | pass_a | scans |
+                     pass_b"""
+    _free, _kernel_ms = "pp_sam_out_free", "pp_sam_out_kernel_ms"
+
+    def __init__(self, ctx, text=None, pass_=None, mem=MEM_HOST, records=None):
+        L = lib()
+        v = None if pass_ is None else np.ascontiguousarray(pass_, dtype=np.uint8)
+        vp, vn = (v.ctypes.data if v is not None and len(v) else None), (len(v) if v is not None else 0)
+        super().__init__(ctx)
+        if records is not None:
+            rc = L.pp_sam_tagged_records(ctx._h, records._p, vp, vn, C.byref(self._p))
+        else:
+            bp, n_bytes, _, _, _keep = _bytes_and_offsets(text, None, mem)
+            rc = L.pp_sam_tagged(ctx._h, bp, n_bytes, mem, vp, vn, C.byref(self._p))
+        ctx._chk(rc)
+        dev, nb = C.c_void_p(), C.c_uint64(0)
+        L.pp_sam_out_bytes(self._p, C.byref(dev), C.byref(nb))
+        self.bytes_ptr, self.n_bytes = dev.value or 0, int(nb.value)
+        p, f, k = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L.pp_sam_out_counts(self._p, C.byref(p), C.byref(f), C.byref(k))
+        self._counts = (int(p.value), int(f.value), int(k.value))
+
+    @classmethod
+    def tagged(cls, ctx, text, pass_, mem=MEM_HOST):
+        return cls(ctx, text, pass_, mem)
+
+    def dev(self):
+        return self.bytes_ptr, self.n_bytes
+
+    def bytes(self):
+        return self._ctx.download(self.bytes_ptr, self.n_bytes, np.uint8).tobytes()
+
+    def counts(self):
+        return self._counts
+
+    def write(self, path):
+        self._ctx._chk(lib().pp_sam_out_write(self._p, os.fsencode(path)))
+
+    def stage_ms(self):
+        return self._stage_ms("pp_sam_out_stage_ms_", ("newline_index", "pass_a", "scans", "pass_b"), " when the text was tagged")
+
+    def deflate(self):
+        return BgzfDeflated(self._ctx, self.dev(), mem=MEM_DEVICE)
+
+
+def sam_out_geometry():
+    """(lines per workgroup of pass A, output bytes per workgroup of pass B, bytes per store) of pp_sam_tagged: the seams its tests
+    are built on"""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    lib().pp_sam_out_geometry_(C.byref(a), C.byref(b), C.byref(c))
+    return int(a.value), int(b.value), int(c.value)
 
 
 def _report_dict(rep):

@@ -176,6 +176,13 @@ SIGNATURES = {
     "pp_bgzf_out_write": (_i, [_vp, _str]),
     "pp_bgzf_out_kernel_ms": (_i, [_vp, _pf32]),
     "pp_bgzf_out_free": (None, [_vp]),
+    "pp_sam_tagged": (_i, [_vp, _vp, _u64, _i, _vp, _u64, _pvp]),
+    "pp_sam_tagged_records": (_i, [_vp, _vp, _vp, _u64, _pvp]),
+    "pp_sam_out_bytes": (None, [_vp, _pvp, _pu64]),
+    "pp_sam_out_counts": (None, [_vp, _pu64, _pu64, _pu64]),
+    "pp_sam_out_write": (_i, [_vp, _str]),
+    "pp_sam_out_kernel_ms": (_i, [_vp, _pf32]),
+    "pp_sam_out_free": (None, [_vp]),
     "pp_aln_file_kind": (_i, [_str, _P(_i)]),
     "pp_polish_set_emit": (_i, [_vp, _vp, _vp]),
     "pp_polish_begin": (_i, [_vp, _u32, _vp, _vp, _i, _P(Params)]),
@@ -265,6 +272,8 @@ HOOKS = {
     "pp_sam_stage_ms_": (_i, [_vp, _pf32]),         # float[5]
     "pp_bam_out_stage_ms_": (_i, [_vp, _pf32]),     # float[3]
     "pp_bgzf_out_stage_ms_": (_i, [_vp, _pf32]),    # float[3]
+    "pp_sam_out_stage_ms_": (_i, [_vp, _pf32]),     # float[4]
+    "pp_sam_out_geometry_": (None, [_pu32] * 3),
     "pp_bam_offs_stage_ms_": (_i, [_vp, _pf32]),    # float[3]
     "pp_bam_offs_stats_": (_i, [_vp, _pu64]),       # uint64[4]
     "pp_bam_walk_geometry_": (None, [_pu32] * 3),

@@ -1,7 +1,8 @@
 // pp_sam.hip -- pp_sam_records: the lines of SAM TEXT as a pp_raw_batch, decoded on the device: the second front end of the record
 // chain names -> filter -> regroup -> gate -> prepare -> polish, the text twin of pp_bam_records (pp_bam.hip).  The two fused text
 // routes (pp_tokenize.hip: text -> gated pp_aln_batch; pp_filter_dev.hip: text -> the filter's input) leave no raw records behind;
-// this one leaves nothing else.
+// this one leaves nothing else.  The chain's write side for text is pp_sam_out.hip: pp_sam_tagged_records reads this object's copy
+// of the text (through pp_sam_names) and splices the filter's verdicts into it.
 //
 // The object owns ONE device copy of the text, padded with zeros behind its end as pp_devtext.h asks (the newline kernels read whole
 // blocks, stage_wave_lines and find_tab read a few bytes past a line).  Every kernel reads that copy and nothing else; raw.seq IS the
