@@ -680,6 +680,86 @@ int pp_sam_out_write(const pp_sam_out *o, const char *path); /* download in slic
 int pp_sam_out_kernel_ms(const pp_sam_out *o, float *ms);
 void pp_sam_out_free(pp_sam_out *o);
 
+/* The link BETWEEN the two formats: SAM TEXT encoded as uncompressed BAM, on the device.  The output -- the bytes, records_at and
+ * rec_off, all DEVICE memory -- is exactly what pp_bam_records, pp_bam_walk_device and pp_bam_tagged take with PP_MEM_DEVICE, so this
+ * call needs no tagging, framing or compressor of its own: pp_bam_tagged(pass) -> pp_bam_out_deflate -> pp_bgzf_out_write finish a
+ * compressed BAM file from text.  The bytes are restated by a plain model, tests/sam_bam_model.py.  The reference has no counterpart.
+ *
+ * pp_sam_header is the text twin of pp_bam_header: a HOST helper that needs no context and no device.  Lines are cut at '\n', one
+ * trailing '\r' is not content.  The header is the leading run of lines that begin with '@'; *header_end = the offset of the first
+ * line that is no header line (n_bytes when there is none).  Per line whose first column is exactly "@SQ", in file order: name_off[i] /
+ * name_len[i] = the range in `text` of the value of its first SN: field, ref_len[i] = the value of its first LN: field.  The arrays
+ * have `cap` entries; n_ref > cap: *n_ref is set all the same, the first cap entries are written and the call returns PP_ERR_ARG (as
+ * do null arguments).  PP_ERR_QUIT with the sentence in pp_bam_last_error() (per thread), naming the 1-based line: an @SQ line without
+ * SN: or with an empty one; without LN:, or with one that is not digits in 1 .. 2^31-1; a second @SQ line with the same name.  It is
+ * memory-safe for any bytes: it never reads outside [0, n_bytes), and a text cut at any byte is answered without a fault.
+ *
+ * pp_sam_bam:
+ *   memory       mem = PP_MEM_HOST or PP_MEM_DEVICE holds for `text`.  Host text is uploaded and the copy is released before the call
+ *                returns; device text is borrowed for the call only and read where it lies, at any alignment.  No byte outside
+ *                [0, n_bytes) is loaded, by a wide load either, and no byte behind n_bytes changes a result.  pp_sam_bam_records reads
+ *                the pp_sam's own device copy of the text: no second upload.  The object owns the output only (the bytes in an
+ *                allocation rounded up to 16, spare bytes zeros, and n_rec + 1 offsets).  The context's stream has been synchronised
+ *                when the call returns.  Two calls on the same text give the same bytes.
+ *   the header   BAM\1, l_text and the text's header lines, each ended by "\n" (a "\r" in front of it is dropped); n_ref and per @SQ
+ *                line in order l_name, the name, NUL, l_ref.  An empty text gives the 12-byte header; a text of header lines only the
+ *                header and no records.  *records_at = the header's length.
+ *   records      every line behind the header that is neither empty nor begins with '@' is a record, in file order; rec_off[r] = the
+ *                offset of record r's block_size word.  The columns are the eleven of SAM, split at tabs; every further column is an
+ *                aux field.  block_size | refID pos l_read_name mapq bin n_cigar_op flag l_seq next_refID next_pos tlen | name NUL |
+ *                CIGAR words | SEQ nibbles | QUAL | aux.
+ *   refID        RNAME / RNEXT "*" is -1, RNEXT "=" is the record's refID, any other name its index among the @SQ lines: pp_names_ids
+ *                over the two columns' ranges on a table seeded with the SN names in header order.
+ *   numbers      FLAG, POS, MAPQ, PNEXT: [+]digits; pos = POS - 1 and next_pos = PNEXT - 1 from a value in 0 .. 2^31, mapq 0 .. 255,
+ *                flag 0 .. 65535.  TLEN: [+-]digits in 32 signed bits.
+ *   bin          reg2bin(pos, end): end = pos + the CIGAR's reference length (M D N = X) when FLAG & 4 is clear and that length is
+ *                above 0, else pos + 1.  --end; for (shift, base) in (14, 4681) (17, 585) (20, 73) (23, 9) (26, 1): base + (pos >>
+ *                shift) at the first shift where pos >> shift == end >> shift, else 0; arithmetic shifts on signed values, so
+ *                (-1, 0) is 4680.
+ *   CIGAR        "*" is no word, else len << 4 | op per run of digits and one of MIDNSHP=X (0 .. 8).
+ *   SEQ, QUAL    SEQ "*" (or empty) is l_seq 0; else either case through =ACMGRSVTWYHKDBN, high nibble first, the spare low nibble
+ *                behind an odd length 0.  QUAL "*" is l_seq bytes 0xFF, else byte - 33.
+ *   aux          TAG:TYPE:VALUE in the line's order.  A: one byte.  i: [+-]digits, in the smallest type of C c S s I i that holds the
+ *                value.  Z: the bytes and a NUL.  H: as Z, an even number of hex digits.  f: a float32.  B: a sub-type of c C s S i I
+ *                f, a 32-bit count, the values ("B:c" alone is count 0).
+ *   a float      [+-]digits[.digits][(e|E)[+-]digits]: w = the digits without the point and without leading zeros as one integer,
+ *                e10 = the exponent less the digits behind the point; the value is (double)w * 10^e10 or (double)w / 10^-e10 in ONE
+ *                IEEE double operation, then rounded to float; a zero of any form is +-0.0.  That is C's strtod-then-float whenever w
+ *                has at most 15 digits and |e10| <= 22; beyond that the line is refused.
+ *   refusals     no object; the first refused line in file order wins, whatever its kind; *bad_line (may be NULL) = its 0-based index
+ *                among all lines; pp_last_error names the path "text", the 1-based line and the column or the aux tag.  Inside one
+ *                line the checks run in this order: the columns' number, QNAME, FLAG, POS, MAPQ, CIGAR (run by run, then the number
+ *                of runs), PNEXT, TLEN, SEQ, QUAL, the bin, the aux fields left to right, then RNAME and RNEXT.
+ *                PP_ERR_QUIT: fewer than 11 columns; a FLAG, POS, MAPQ, PNEXT or TLEN that is no number; a CIGAR that is not runs of
+ *                digits and an op; QUAL present with SEQ "*", of another length than SEQ, or with a byte below 33; an aux field that is
+ *                not XX:T:... (an empty field behind a trailing tab included), of unknown type, an A of other than one byte, an i that
+ *                is no number, an H of odd length or with a byte that is no hex digit, a B with an unknown sub-type, an empty element or
+ *                a value outside its sub-type; an RNAME or RNEXT that no @SQ line names; a line that begins with '@' behind the first
+ *                record (one in front of it is skipped).
+ *                PP_ERR_LIMIT, a valid line this encoder does not hold: a value beyond its field (FLAG, POS, MAPQ, PNEXT, TLEN, an i
+ *                outside -2^31 .. 2^32-1); a QNAME that is empty or longer than 254 bytes; more than 65,535 CIGAR runs, a run of 2^28
+ *                or more, a run of length 0 (the text's expansion drops it, a BAM word would keep it); a SEQ byte outside the table;
+ *                the bin's `end` above 2^29 (the bin has 16 bits); a float outside the rule above, inf
+ *                and nan included; a line of 2^31 or more bytes; 2^32-1 or more lines; n_bytes >= 2^40; an output of 2^40 bytes or more.
+ *                PP_ERR_NOT_ASCII for a byte >= 0x80 anywhere in the text, as pp_sam_records (no bad_line).  PP_ERR_ARG: null
+ *                arguments, PP_MEM_PEER, null text with n_bytes > 0.  A refusal of pp_sam_header comes through with its own code and
+ *                sentence.  After a refusal the context serves the next call.
+ *   NM           is not looked at: an aligned line without NM encodes like any other (`filter`'s new_quick never reads NM).  On any
+ *                text that both this call and pp_sam_records accept, record r of one is record r of the other.
+ *   geometry     pass B gives every workgroup a tile of 16,384 OUTPUT bytes, built in LDS and written with 16-byte stores aligned on
+ *                the output; a record longer than a tile spans workgroups.
+ * pp_bam_enc_bytes / pp_bam_enc_rec_off: borrowed until pp_bam_enc_free.  pp_bam_enc_kernel_ms: as pp_gated_kernel_ms, the
+ * pp_names_ids kernels included.  The object belongs to its context and is freed before it. */
+int pp_sam_header(const uint8_t *text, uint64_t n_bytes, uint32_t cap, uint32_t *n_ref, uint64_t *name_off, uint32_t *name_len,
+                  uint32_t *ref_len, uint64_t *header_end);
+typedef struct pp_bam_enc pp_bam_enc;
+int pp_sam_bam(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, pp_bam_enc **out, uint64_t *bad_line);
+int pp_sam_bam_records(pp_ctx *ctx, const pp_sam *s, pp_bam_enc **out, uint64_t *bad_line); /* the pp_sam's own device copy, no second upload */
+void pp_bam_enc_bytes(const pp_bam_enc *e, const uint8_t **dev, uint64_t *n_bytes, uint64_t *records_at); /* DEVICE: uncompressed BAM */
+const uint64_t *pp_bam_enc_rec_off(const pp_bam_enc *e, uint64_t *n_rec);                                /* DEVICE, n_rec entries */
+int pp_bam_enc_kernel_ms(const pp_bam_enc *e, float *ms);
+void pp_bam_enc_free(pp_bam_enc *e);
+
 /* What an alignment file holds, told by its CONTENT: the commands (pp_polish_files, pp_filter_files, pp_filter_polish_files) take SAM
  * text as before and BAM through the record chain above, and ask this.  HOST, no context; reads only the head of the file.
  *   PP_ALN_SAM      anything that is neither of the two below, an empty file included: the text routes keep their own errors.  A
@@ -1007,6 +1087,16 @@ void pp_bytes_free(pp_bytes *b);
  * reported at once, without the replay of the records in front.  Without it every command behaves as
  * before: there is no switch on an @HD SO:coordinate header. */
 int pp_ctx_set_regroup(pp_ctx *ctx, int on);
+
+/* Compressed BAM outputs from SAM text for the filter drivers below (the commands' --out_bam; not in the reference): with `on` != 0,
+ * pp_filter_files and pp_filter_polish_files with outputs named write, for two SAM TEXT inputs, every line again as a BAM record
+ * instead of as text: per file pp_sam_bam on the text the run holds in host memory, pp_bam_tagged with the filter's own verdicts,
+ * pp_bam_out_deflate, pp_bgzf_out_write.  Both files are encoded before either output is created: a line pp_sam_bam refuses ends the
+ * call with PP_ERR_QUIT (also where pp_sam_bam says PP_ERR_LIMIT or PP_ERR_NOT_ASCII) and leaves nothing behind; the message names the
+ * input's path, the 1-based line and --out_bam.  The counts, the log and the FASTA are what they are without it.  It changes nothing
+ * for BAM inputs (they write BAM already) and for pp_filter_polish_files without outputs.  The state lives on the context, like
+ * pp_ctx_set_regroup's; off when the context is made. */
+int pp_ctx_set_out_bam(pp_ctx *ctx, int on);
 
 /* polish::polish (src/polish.rs:26-38): FASTA text exactly as the reference prints to stdout.
  * `sams` are SAM text files or -- all of them -- BAM files (pp_aln_file_kind; a mix is PP_ERR_QUIT).  BAM goes through the record

@@ -902,6 +902,7 @@ class SamRecords(_Owned):
       .kernel_ms()   HIP-event time of the decode's kernels (the context had set_profiling on); .stage_ms(): copy | newline_index |
                      scan | place | cigar
       .tagged(pass_) pp_sam_tagged_records: the text with the filter's verdicts written back -> SamOut (no second upload)
+      .bam()         pp_sam_bam_records: the text encoded as uncompressed BAM -> BamEncoded (no second upload)
     A refused text raises PolypolishError with .bad_record = the 0-based line (None where the refusal names none)."""
     _free, _kernel_ms = "pp_sam_free", "pp_sam_kernel_ms"
 
@@ -955,6 +956,10 @@ class SamRecords(_Owned):
     def tagged(self, pass_):
         """pp_sam_tagged_records: the object's own device copy of the text with the verdicts written back -> SamOut"""
         return SamOut(self._ctx, pass_=pass_, records=self)
+
+    def bam(self):
+        """pp_sam_bam_records: the object's own device copy of the text encoded as uncompressed BAM -> BamEncoded"""
+        return BamEncoded(self._ctx, records=self)
 
 
 class BamTagged(_Owned):
@@ -1108,6 +1113,83 @@ class SamOut(_Owned):
 
     def deflate(self):
         return BgzfDeflated(self._ctx, self.dev(), mem=MEM_DEVICE)
+
+
+def sam_header(text):
+    """pp_sam_header (no device needed): {"names": [bytes], "name_off", "name_len", "ref_len": numpy arrays, "header_end": int} of SAM
+    text; a refused @SQ line raises PolypolishError(ERR_QUIT) with the 1-based line in its message."""
+    L = lib()
+    b = _bam_bytes(text)
+    bp = b.ctypes.data if len(b) else None
+    n_ref, end = C.c_uint32(0), C.c_uint64(0)
+    rc = L.pp_sam_header(bp, len(b), 0, C.byref(n_ref), None, None, None, C.byref(end))
+    n = int(n_ref.value)
+    off, ln, rl = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    if n and rc == ERR_ARG:
+        rc = L.pp_sam_header(bp, len(b), n, C.byref(n_ref), off.ctypes.data, ln.ctypes.data, rl.ctypes.data, C.byref(end))
+    if rc:
+        raise PolypolishError(rc, L.pp_bam_last_error().decode())
+    return {"names": [b[int(o):int(o) + int(k)].tobytes() for o, k in zip(off, ln)], "name_off": off, "name_len": ln, "ref_len": rl,
+            "header_end": int(end.value)}
+
+
+class BamEncoded(_Owned):
+    """pp_sam_bam / pp_sam_bam_records: SAM text encoded as uncompressed BAM in DEVICE memory, owned by this object
+    (tests/sam_bam_model.py defines the bytes).  Made by BamEncoded(ctx, text, mem=...) or SamRecords.bam().
+      text           mem = MEM_HOST: bytes / a uint8 array; MEM_DEVICE: (device address, n_bytes), borrowed for the call
+      .dev()         (device address, n_bytes) of the BAM bytes: what BamRecords / BamTagged / bam_walk_device take with MEM_DEVICE
+      .bytes()       the BAM bytes (a download)
+      .records_at    where the header ends
+      .n_rec, .rec_off_ptr   the records, and the device address of their n_rec uint64 offsets; .rec_off(): a numpy copy
+      .tagged(pass_) pp_bam_tagged on the device bytes -> BamTagged (then .deflate().write(path): the compressed file)
+      .records(ref_map)      pp_bam_records on the device bytes -> BamRecords
+      .kernel_ms()   HIP-event time of the kernels (the context had set_profiling on); .stage_ms(): newline_index | pass_a | names |
+                     scans | pass_b
+    A refused text raises PolypolishError with .bad_record = the 0-based line (None where the refusal names none)."""
+    _free, _kernel_ms = "pp_bam_enc_free", "pp_bam_enc_kernel_ms"
+
+    def __init__(self, ctx, text=None, mem=MEM_HOST, records=None):
+        L = lib()
+        super().__init__(ctx)
+        bad = _no_index()
+        if records is not None:
+            rc = L.pp_sam_bam_records(ctx._h, records._p, C.byref(self._p), C.byref(bad))
+        else:
+            bp, n_bytes, _, _, _keep = _bytes_and_offsets(text, None, mem)
+            rc = L.pp_sam_bam(ctx._h, bp, n_bytes, mem, C.byref(self._p), C.byref(bad))
+        if rc:
+            _raise(rc, L.pp_last_error(ctx._h).decode(), bad_record=_index(bad))
+        dev, nb, at, k = C.c_void_p(), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        L.pp_bam_enc_bytes(self._p, C.byref(dev), C.byref(nb), C.byref(at))
+        self.bytes_ptr, self.n_bytes, self.records_at = dev.value or 0, int(nb.value), int(at.value)
+        self.rec_off_ptr = L.pp_bam_enc_rec_off(self._p, C.byref(k)) or 0
+        self.n_rec = int(k.value)
+
+    def dev(self):
+        return self.bytes_ptr, self.n_bytes
+
+    def bytes(self):
+        return self._ctx.download(self.bytes_ptr, self.n_bytes, np.uint8).tobytes()
+
+    def rec_off(self):
+        return self._ctx.download(self.rec_off_ptr, self.n_rec, np.uint64)
+
+    def tagged(self, pass_):
+        return BamTagged(self._ctx, self.dev(), self.records_at, (self.rec_off_ptr, self.n_rec), pass_, mem=MEM_DEVICE)
+
+    def records(self, ref_map=None):
+        return BamRecords(self._ctx, self.dev(), (self.rec_off_ptr, self.n_rec), ref_map, mem=MEM_DEVICE)
+
+    def stage_ms(self):
+        return self._stage_ms("pp_bam_enc_stage_ms_", ("newline_index", "pass_a", "names", "scans", "pass_b"), " when the text was encoded")
+
+
+def sam_bam_geometry():
+    """(lines per workgroup of the placing kernel, output bytes per workgroup of pass B, bytes per store) of pp_sam_bam: the seams
+    its tests are built on"""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    lib().pp_sam_bam_geometry_(C.byref(a), C.byref(b), C.byref(c))
+    return int(a.value), int(b.value), int(c.value)
 
 
 def sam_out_geometry():
@@ -1273,6 +1355,11 @@ class Context:
         """pp_ctx_set_regroup: polish_files and the polish half of filter_polish_files regroup every BAM file's records in front of
         the gate (coordinate-sorted BAM; the commands' --regroup)."""
         self._chk(lib().pp_ctx_set_regroup(self._h, int(bool(on))))
+
+    def set_out_bam(self, on=True):
+        """pp_ctx_set_out_bam: filter_files / filter_polish_files write the outputs of SAM text inputs as compressed BAM (the
+        commands' --out_bam)."""
+        self._chk(lib().pp_ctx_set_out_bam(self._h, int(bool(on))))
 
     # ---- seam B -------------------------------------------------------------------------------
     def polish_begin(self, contig_off, bases_ptr, bases_mem, min_depth=5, fraction_valid=0.5, fraction_invalid=0.2):
@@ -1507,6 +1594,18 @@ class Context:
         finally:
             self.set_regroup(was)
 
+    @contextlib.contextmanager
+    def _writing_bam(self, out_bam):
+        """out_bam=True switches pp_ctx_set_out_bam on for one command and off again behind it"""
+        if not out_bam:
+            yield
+            return
+        self.set_out_bam(True)
+        try:
+            yield
+        finally:
+            self.set_out_bam(False)
+
     def polish_files(self, assembly, sams, fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5,
                      careful=False, debug=None, quiet=True, regroup=False):
         """polish::polish (pp_polish_files): the FASTA bytes.  `sams` are SAM text files, or all of them BAM files (BGZF or
@@ -1524,27 +1623,30 @@ class Context:
 
     def filter_polish_files(self, assembly, in1, in2, out1=None, out2=None, orientation="auto", low=0.1, high=99.9,
                             fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5, careful=False,
-                            debug=None, quiet=True, regroup=False):
+                            debug=None, quiet=True, regroup=False, out_bam=False):
         """filter + polish in one process (pp_filter_polish_files): returns (FASTA bytes, filter report).  Two BAM inputs are decoded
-        once for both halves; out1 / out2 are then BAM files as well.  regroup: for this call, as set_regroup (the polish half)."""
+        once for both halves; out1 / out2 are then BAM files as well.  regroup: for this call, as set_regroup (the polish half).
+        out_bam: for this call, as set_out_bam (SAM text inputs, out1 / out2 as compressed BAM)."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         rep, out = FilterReport(), Bytes()
         enc = lambda x: str(x).encode() if x is not None else None
-        with self._regrouping(regroup):
+        with self._regrouping(regroup), self._writing_bam(out_bam):
             self._chk(lib().pp_filter_polish_files(self._h, enc(assembly), enc(in1), enc(in2), enc(out1), enc(out2),
                                                    orientation.encode(), low, high, C.byref(opt), C.byref(rep), C.byref(out)))
         data = C.string_at(out.data, out.len) if out.len else b""
         lib().pp_bytes_free(C.byref(out))
         return data, _report_dict(rep)
 
-    def filter_files(self, in1, in2, out1, out2, orientation="auto", low=0.1, high=99.9, quiet=True):
+    def filter_files(self, in1, in2, out1, out2, orientation="auto", low=0.1, high=99.9, quiet=True, out_bam=False):
         """filter::filter (pp_filter_files): writes out1 / out2, returns the report.  in1 / in2 are both SAM text, or both BAM:
-        BAM in gives compressed BAM out (pp_bam_tagged -> pp_bam_out_deflate)."""
+        BAM in gives compressed BAM out (pp_bam_tagged -> pp_bam_out_deflate).  out_bam: for this call, as set_out_bam (SAM text
+        in, compressed BAM out through pp_sam_bam)."""
         rep = FilterReport()
-        self._chk(lib().pp_filter_files(self._h, str(in1).encode(), str(in2).encode(), str(out1).encode(),
-                                        str(out2).encode(), orientation.encode(), low, high, int(quiet),
-                                        C.byref(rep)))
+        with self._writing_bam(out_bam):
+            self._chk(lib().pp_filter_files(self._h, str(in1).encode(), str(in2).encode(), str(out1).encode(),
+                                            str(out2).encode(), orientation.encode(), low, high, int(quiet),
+                                            C.byref(rep)))
         return _report_dict(rep)
 
 

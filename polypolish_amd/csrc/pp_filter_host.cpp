@@ -966,6 +966,52 @@ int filter_write(pp_ctx *ctx, const Log &log, const FilterRun &R, const char *co
     return PP_OK;
 }
 
+// filter_sams with --out_bam: the text the run holds in host memory encoded as BAM on the device (pp_sam_bam), the filter's own
+// verdicts written into the records (pp_bam_tagged), compressed, written.  Both files are encoded before either output is created: a
+// line the encoder refuses leaves nothing behind.  The log is filter_write's, word for word.
+int filter_write_sam_bam(pp_ctx *ctx, const Log &log, const FilterRun &R, const char *const ins[2], const char *const outs[2],
+                         uint64_t *after) {
+    *after = 0;
+    log("Filtering SAM files\n");
+    pp_bam_enc *enc[2] = {nullptr, nullptr};
+    struct Free {
+        pp_bam_enc **e;
+        ~Free() { pp_bam_enc_free(e[0]); pp_bam_enc_free(e[1]); }
+    } free_enc{enc};
+    for (int f = 0; f < 2; f++) {
+        uint64_t size = 0, bad = 0;
+        const char *text = R.DL ? pp_filter_dev_text(R.DL, f, &size) : R.L->F[f].text.text;
+        if (!R.DL) size = R.L->F[f].text.size;
+        if (pp_sam_bam(ctx, (const uint8_t *)text, size, PP_MEM_HOST, &enc[f], &bad) != PP_OK) {
+            // the encoder's sentence names the path "text": the input's own path in its place
+            std::string said = pp_last_error(ctx);
+            const std::string path = std::string("\"") + ins[f] + "\"";
+            const size_t at = said.find("\"text\"");
+            if (at != std::string::npos) said.replace(at, 6, path);
+            else said += " in " + path;
+            return ppb::fail(ctx, PP_ERR_QUIT, "--out_bam: %s", said.c_str());
+        }
+    }
+    for (int f = 0; f < 2; f++) {
+        const uint8_t *dev = nullptr;
+        uint64_t n_bytes = 0, records_at = 0, n_rec = 0, bad = 0, p_ = 0, f_ = 0, blocks = 0;
+        pp_bam_enc_bytes(enc[f], &dev, &n_bytes, &records_at);
+        const uint64_t *rec_off = pp_bam_enc_rec_off(enc[f], &n_rec);
+        pp_bam_out *t = nullptr;
+        pp_bgzf_out *c = nullptr;
+        int rc = pp_bam_tagged(ctx, dev, n_bytes, records_at, rec_off, n_rec, PP_MEM_DEVICE, R.pass[f].data(), R.n_aln[f], &t, &bad);
+        if (rc == PP_OK) rc = pp_bam_out_deflate(ctx, t, &c);
+        if (rc == PP_OK) pp_bam_out_counts(t, &p_, &f_, &blocks);
+        pp_bam_out_free(t);
+        if (rc == PP_OK) rc = pp_bgzf_out_write(c, outs[f]);
+        pp_bgzf_out_free(c);
+        if (rc) return rc;
+        log("Filtering %s:\n  %s pass\n  %s fail\n\n", ins[f], commas(p_).c_str(), commas(f_).c_str());
+        *after += p_;
+    }
+    return PP_OK;
+}
+
 // both inputs' kinds; *bam = both are BAM.  One BAM and one SAM input is refused.
 int filter_input_kinds(pp_ctx *ctx, const char *const ins[2], int kinds[2], bool *bam) {
     for (int f = 0; f < 2; f++)
@@ -1063,8 +1109,11 @@ int run_filter(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const std::func
                        : filter_core(ctx, log, lap, ins, orientation, low, high, R))
         return rc;
     if (outs[0]) {
-        if (int rc = R.bam ? filter_write_bam(ctx, log, R, ins, outs) : filter_write(ctx, log, R, ins, outs, &R.rep.after_count)) return rc;
-        lap(R.bam ? "filtered BAMs written" : "filtered SAMs written");
+        const bool text_to_bam = !R.bam && pp_ctx_out_bam_(ctx);
+        if (int rc = R.bam ? filter_write_bam(ctx, log, R, ins, outs)
+                           : (text_to_bam ? filter_write_sam_bam(ctx, log, R, ins, outs, &R.rep.after_count) : filter_write(ctx, log, R, ins, outs, &R.rep.after_count)))
+            return rc;
+        lap(R.bam || text_to_bam ? "filtered BAMs written" : "filtered SAMs written");
     } else if (!R.bam) {  // (BAM: pp_filter_records has counted; SAM text without outputs: from the verdicts)
         for (int f = 0; f < 2; f++)
             for (uint64_t i = 0; i < R.n_aln[f]; i++) R.rep.after_count += R.pass[f][i];

@@ -13,7 +13,7 @@
 //   ST_TILE  = 16,384   output bytes per workgroup of pass B
 //   ST_STORE = 16       bytes per store of pass B, aligned on the OUTPUT
 //
-//   k_st_nl_count, k_st_nl_write   the newline index, as newline_index of pp_devtext.h (count per 64 KB block, scan, write) but on a
+//   k_in_nl_count, k_in_nl_write   (pp_textin.h) the newline index, as newline_index of pp_devtext.h (count per 64 KB block, scan, write) but on a
 //                 text that is BORROWED: not padded, at any alignment, bytes >= 0x80 welcome.  A thread's 64 bytes are four 16-byte
 //                 loads when they lie inside the text, single bytes at the text's end
 //   k_st_lines    pass A, one lane per line: the '\r', the predicate (the head of the line up to its second tab, eight bytes per step
@@ -37,7 +37,7 @@
 //                 with one 16-byte aligned store; the output's allocation is rounded up to 16, the last piece's spare bytes are zeros.
 // No byte outside [0, n_bytes) of the text is loaded, by a wide load either: every load is checked against the text's size or lies
 // inside a line's content.  No kernel keeps a register in scratch memory (.private_segment_fixed_size: 0 for all of them).
-#include "pp_dev.h"
+#include "pp_textin.h"
 
 #include <cstring>
 
@@ -51,7 +51,7 @@ struct pp_sam_out : DevOwner {
 
 namespace {
 
-constexpr u32 NL_BLOCK = 1024 * 64;  // bytes of text per workgroup of the newline kernels (64 per thread), as pp_devtext.h's
+constexpr u32 NL_BLOCK = IN_NL_BLOCK;  // bytes of text per workgroup of the newline kernels (pp_textin.h)
 constexpr u32 ST_LINES = 1024;    // lines per workgroup of pass A
 constexpr u32 ST_TILE = 16384;    // output bytes per workgroup of pass B
 constexpr u32 ST_STORE = 16;      // bytes per store of pass B
@@ -60,93 +60,7 @@ constexpr u32 ST_TRIPS = ST_TILE / ST_STORE / ST_THREADS;
 constexpr u32 ST_CAP = 2048;      // line starts of one tile kept in LDS (and one line end); a tile with more is searched in memory
 constexpr u64 TAG_LO = 0x61663A5A3A505A09ull, TAG_HI = 0x0A6C69ull;  // \t Z P : Z : f a | i l \n, low byte first
 
-__device__ __forceinline__ u32 nl_mask(u32 w) {  // bit 7 of every byte that is '\n'
-    const u32 x = w ^ 0x0A0A0A0Au;
-    return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;
-}
-
-// ---- the newline index of a borrowed text ------------------------------------------------------------------------------------------
-// the 64 bytes from `base` as sixteen words; those behind the text's end are zeros
-__device__ __forceinline__ void load64_in(const u8 *__restrict__ T, u64 size, u64 base, u32 w[16]) {
-    if (base < size && size - base >= 64u) {
-        uint4 q[4];
-        __builtin_memcpy(q, T + base, 64);  // (any alignment: four global_load_dwordx4)
-#pragma unroll
-        for (int v = 0; v < 4; v++) { w[4 * v] = q[v].x; w[4 * v + 1] = q[v].y; w[4 * v + 2] = q[v].z; w[4 * v + 3] = q[v].w; }
-        return;
-    }
-    const u32 left = base < size ? (u32)(size - base) : 0u;
-#pragma unroll
-    for (u32 i = 0; i < 16u; i++) {
-        u32 x = 0;
-#pragma unroll
-        for (u32 b = 0; b < 4u; b++)
-            if (4u * i + b < left) x |= (u32)T[base + 4u * i + b] << (8u * b);
-        w[i] = x;
-    }
-}
-
-__global__ __launch_bounds__(1024) void k_st_nl_count(const u8 *__restrict__ text, u64 size, u32 *__restrict__ blk_cnt) {
-    __shared__ u32 s_sum;
-    if (threadIdx.x == 0) s_sum = 0;
-    __syncthreads();
-    u32 w[16], v = 0;
-    load64_in(text, size, (u64)blockIdx.x * NL_BLOCK + (u64)threadIdx.x * 64u, w);
-#pragma unroll
-    for (u32 i = 0; i < 16u; i++) v += (u32)__popc(nl_mask(w[i]));
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63u) == 0 && v) atomicAdd(&s_sum, v);
-    __syncthreads();
-    if (threadIdx.x == 0) blk_cnt[blockIdx.x] = s_sum;
-}
-
-__global__ __launch_bounds__(1024) void k_st_nl_write(const u8 *__restrict__ text, u64 size, const u64 *__restrict__ blk_off,
-                                                      u64 *__restrict__ nl_pos) {
-    __shared__ u32 s_w[16];
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const u64 base = (u64)blockIdx.x * NL_BLOCK + (u64)threadIdx.x * 64u;
-    u32 w[16], n = 0;
-    load64_in(text, size, base, w);
-#pragma unroll
-    for (u32 i = 0; i < 16u; i++) n += (u32)__popc(nl_mask(w[i]));
-    const u32 inc = pp::wave_scan_incl(n);
-    if (lane == 63) s_w[wave] = inc;
-    __syncthreads();
-    u32 before = inc - n;
-    for (u32 i = 0; i < wave; i++) before += s_w[i];
-    if (!n) return;
-    u64 out = blk_off[blockIdx.x] + before;
-#pragma unroll
-    for (u32 i = 0; i < 16u; i++) {
-        u32 m = nl_mask(w[i]);
-        while (m) {
-            const u32 b = ((u32)__ffs((int)m) - 1u) >> 3;
-            m &= m - 1u;
-            nl_pos[out++] = base + 4u * i + b;
-        }
-    }
-}
-
 // ---- pass A ------------------------------------------------------------------------------------------------------------------------
-// the first '\t' in text[from, end), or end: eight bytes per step where eight lie inside the text (end <= size)
-__device__ __forceinline__ u64 find_tab_in(const u8 *__restrict__ T, u64 size, u64 from, u64 end) {
-    u64 i = from;
-    while (i < end) {
-        if (size - i >= 8u) {
-            u64 w;
-            __builtin_memcpy(&w, T + i, 8);
-            const u64 x = w ^ 0x0909090909090909ull;
-            const u64 m = (x - 0x0101010101010101ull) & ~x & 0x8080808080808080ull;  // bit 7 of the zero bytes (first one exact)
-            if (m) return min(end, i + ((u32)__ffsll((long long)m) - 1u) / 8u);
-            i += 8;
-        } else {
-            if (T[i] == (u8)'\t') return i;
-            i++;
-        }
-    }
-    return end;
-}
-
 // str::parse::<u32>() of text[a, b) (parse_u of pp_devtext.h on a column of any length), then bit 2 clear
 __device__ __forceinline__ bool flag_aligned(const u8 *__restrict__ T, u64 a, u64 b) {
     if (a == b) return false;
@@ -159,29 +73,6 @@ __device__ __forceinline__ bool flag_aligned(const u8 *__restrict__ T, u64 a, u6
         if (v > 0xFFFFFFFFull) return false;
     }
     return (v & 4u) == 0;
-}
-
-// a workgroup's exclusive prefix of 64-bit values (a line may be longer than 4 GB), *total its sum
-template <u32 BLOCK>
-__device__ __forceinline__ u64 block_scan_excl_u64(u64 v, u64 *s_w, u64 *total) {
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    u64 inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 t = __shfl_up(inc, o, 64);
-        if ((int)lane >= o) inc += t;
-    }
-    if (lane == 63u) s_w[wave] = inc;
-    __syncthreads();
-    u64 before = 0, sum = 0;
-#pragma unroll
-    for (u32 i = 0; i < BLOCK / 64u; i++) {
-        const u64 w = s_w[i];
-        before += i < wave ? w : 0ull;
-        sum += w;
-    }
-    __syncthreads();  // (s_w is used again)
-    *total = sum;
-    return before + inc - v;
 }
 
 __global__ __launch_bounds__(ST_LINES) void k_st_lines(const u8 *__restrict__ T, u64 size, const u64 *__restrict__ nl, u64 n_nl, u64 n_lines,
@@ -266,23 +157,6 @@ struct Piece16 {  // sixteen bytes of the output, low byte first
         hi |= b;
     }
 };
-
-// sixteen bytes of the text from `at`, of which `need` >= 1 are wanted and lie inside it; the text's last bytes byte by byte
-__device__ __forceinline__ void load16_in(const u8 *__restrict__ T, u64 size, u64 at, u32 need, u64 *lo, u64 *hi) {
-    if (size - at >= 16u) {
-        u64 v[2];
-        __builtin_memcpy(v, T + at, 16);  // (any alignment: one global_load_dwordx4)
-        *lo = v[0];
-        *hi = v[1];
-    } else {
-        u64 a = 0, b = 0;
-        for (u32 j = 0; j < need; j++) {
-            if (j < 8u) a |= (u64)T[at + j] << (8u * j); else b |= (u64)T[at + j] << (8u * (j - 8u));
-        }
-        *lo = a;
-        *hi = b;
-    }
-}
 
 // Sixteen output bytes from `o` that do not lie inside one line's content: the content's end, the tag, the newline, the lines behind,
 // stretch by stretch -- one load of at most 16 bytes per line the piece touches, shifted and masked into place, the tag and the newline
@@ -429,7 +303,7 @@ int tagged(pp_ctx *ctx, const char *who, const uint8_t *text, uint64_t n_bytes, 
     void *d_blk, *d_blkoff, *d_nl;
     if ((rc = T.get(ctx, &d_blk, (size_t)n_blk * 4)) || (rc = T.get(ctx, &d_blkoff, ((size_t)n_blk + 1) * 8))) return rc;
     if ((rc = timer.begin(0))) return rc;
-    hipLaunchKernelGGL(k_st_nl_count, dim3((unsigned)n_blk), dim3(1024), 0, st, d_text, size, (u32 *)d_blk);
+    hipLaunchKernelGGL(k_in_nl_count<false>, dim3((unsigned)n_blk), dim3(1024), 0, st, d_text, size, (u32 *)d_blk);
     hipLaunchKernelGGL(k_tscan<u64>, dim3(1), dim3(1024), 0, st, (const u32 *)d_blk, n_blk, (u64 *)d_blkoff);
     if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
@@ -439,7 +313,7 @@ int tagged(pp_ctx *ctx, const char *who, const uint8_t *text, uint64_t n_bytes, 
     const u64 n_lines = n_nl + (last != (u8)'\n' ? 1 : 0);
     if (n_lines >= 0xFFFFFFFFull) return ctx->fail(PP_ERR_LIMIT, "%s: 2^32-1 or more lines in one text", who);
     if ((rc = T.get(ctx, &d_nl, (size_t)std::max<u64>(1, n_nl) * 8)) || (rc = timer.begin(0))) return rc;
-    hipLaunchKernelGGL(k_st_nl_write, dim3((unsigned)n_blk), dim3(1024), 0, st, d_text, size, (const u64 *)d_blkoff, (u64 *)d_nl);
+    hipLaunchKernelGGL(k_in_nl_write, dim3((unsigned)n_blk), dim3(1024), 0, st, d_text, size, (const u64 *)d_blkoff, (u64 *)d_nl);
     if ((rc = timer.end())) return rc;
 
     // ---- pass A: the aligned records ----
