@@ -760,6 +760,55 @@ const uint64_t *pp_bam_enc_rec_off(const pp_bam_enc *e, uint64_t *n_rec);       
 int pp_bam_enc_kernel_ms(const pp_bam_enc *e, float *ms);
 void pp_bam_enc_free(pp_bam_enc *e);
 
+/* The opposite direction: uncompressed BAM decoded to SAM TEXT, on the device.  The result is a pp_sam_out, the object pp_sam_tagged
+ * makes: pp_sam_out_bytes / _counts / _write / _kernel_ms / _free and pp_bgzf_deflate on its bytes work on it unchanged.  The bytes are
+ * defined by a plain model, tests/bam_sam_model.py; they were not compared with `samtools view`.  For every CANONICAL text T -- plain
+ * decimals, upper-case SEQ, RNEXT "=" for a repeated name, floats in the "%g" form of a float32, no "\r", no empty line, a final
+ * "\n" -- pp_bam_sam(pp_sam_bam(T)) == T byte for byte.  The reference has no counterpart.
+ *   arguments    bytes[0, n_bytes), records_at, rec_off[0, n_rec): as pp_bam_tagged; mem = PP_MEM_HOST or PP_MEM_DEVICE holds for
+ *                `bytes` and `rec_off`.  Device bytes are borrowed for the call only; no byte outside [0, n_bytes) is loaded, by a wide
+ *                load either.  pp_bam_sam_encoded reads a pp_bam_enc's own device memory.  pass[0, n_pass): HOST memory, one byte per
+ *                ALIGNED record (flag & 4 == 0) in index order, pp_bam_tagged's numbering; pass == NULL with n_pass == 0: no verdicts,
+ *                nothing is appended.  The context's stream has been synchronised when the call returns; two calls on the same input
+ *                give identical bytes.
+ *   the header   bytes[0, records_at) must be a BAM header (pp_bam_header) that ends at records_at; with PP_MEM_DEVICE the library
+ *                downloads it.  The text starts as the l_text bytes of header text without trailing NULs, a "\n" appended where it is
+ *                not empty and does not end in one.  Where no line's first column is exactly "@SQ" and n_ref > 0, one line
+ *                "@SQ\tSN:<name>\tLN:<l_ref>" per reference follows, in order (htslib does the same): pp_sam_header of the output
+ *                gives back the BAM's reference table.
+ *   a record     one line QNAME FLAG RNAME POS MAPQ CIGAR RNEXT PNEXT TLEN SEQ QUAL and the aux fields, joined by tabs, ended by
+ *                "\n", in index order.  Numbers are plain decimals.  RNAME "*" for refID -1, else the name; RNEXT "*" for -1, "=" where
+ *                it equals a refID >= 0, else the name; POS = pos + 1, PNEXT = next_pos + 1.  CIGAR "*" for no word, else len and one
+ *                of MIDNSHP=X per word (a CG:B:I aux field is printed as the aux field it is).  SEQ "*" for l_seq 0, else the
+ *                nibbles through =ACMGRSVTWYHKDBN.  QUAL "*" where l_seq is 0 or its first byte is 0xFF, else byte + 33.
+ *   aux          in the record's order: A one byte; c C s S i I as TAG:i:<decimal>; Z and H their bytes; B as TAG:B:<sub> and
+ *                ",<value>" per element; f (also inside B) as C's printf("%g") of the float widened to double, exact over all of
+ *                float32.
+ *   verdicts     an aligned record whose byte is 0 gets the ten bytes "\tZP:Z:fail" in front of its "\n", also behind a tag that is
+ *                already there; unaligned records take no verdict.  NM is not looked at.
+ *   refusals     no object; the first refused record in index order wins, *bad_record (may be NULL) = its index; inside one record a
+ *                PP_ERR_ARG defect goes in front of a PP_ERR_LIMIT.
+ *                PP_ERR_ARG: pp_bam_tagged's three (a rec_off outside the array or ending inside the block_size word, block_size <
+ *                32, a record past n_bytes); pp_bam_records' inner defects (block_size below the sum of its parts, l_read_name == 0 or
+ *                a name without its NUL, a CIGAR op above 8, a refID or next_refID outside [-1, n_ref), an aux field that is cut or of
+ *                unknown type, a Z / H without NUL inside the record, a B of unknown sub-type or whose count runs past the record);
+ *                pos or next_pos below -1; bytes[0, records_at) that is no BAM header ending there; null arguments, PP_MEM_PEER.
+ *                Another number of verdicts than aligned records is PP_ERR_ARG too, reported only once the records are free of
+ *                defects.
+ *                PP_ERR_LIMIT, a valid record that has no SAM line: an empty QNAME, one that begins with '@' or holds a byte outside
+ *                0x21..0x7E; a used reference name that is empty, "*", "=" or holds a byte outside 0x21..0x7E; an A value outside
+ *                0x21..0x7E; a Z byte outside 0x20..0x7E; an H that is not an even number of hex digits; a tag that is not
+ *                [A-Za-z][A-Za-z0-9]; a QUAL byte above 93 where the first byte is not 0xFF; a float that is inf or nan; a reference
+ *                whose @SQ line would have to be written and cannot be (such a name, or l_ref outside 1 .. 2^31-1; no bad_record);
+ *                2^32-1 or more records; n_bytes >= 2^40; an output of 2^40 bytes or more.
+ *                Every line written is a line pp_sam_bam parses; pp_sam_bam's own capacity limits (a CIGAR run of length 0, an end
+ *                above 2^29, a float beyond 10^+-22) stay its own.  After a refusal the context serves the next call.
+ *   geometry     pass A takes 1,024 records per workgroup; pass B gives every workgroup a tile of 16,384 OUTPUT bytes, built in LDS
+ *                and written with 16-byte stores aligned on the output; a record longer than a tile spans workgroups. */
+int pp_bam_sam(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, uint64_t records_at, const uint64_t *rec_off, uint64_t n_rec,
+               int mem, const uint8_t *pass, uint64_t n_pass, pp_sam_out **out, uint64_t *bad_record);
+int pp_bam_sam_encoded(pp_ctx *ctx, const pp_bam_enc *e, const uint8_t *pass, uint64_t n_pass, pp_sam_out **out, uint64_t *bad_record);
+
 /* What an alignment file holds, told by its CONTENT: the commands (pp_polish_files, pp_filter_files, pp_filter_polish_files) take SAM
  * text as before and BAM through the record chain above, and ask this.  HOST, no context; reads only the head of the file.
  *   PP_ALN_SAM      anything that is neither of the two below, an empty file included: the text routes keep their own errors.  A
@@ -1097,6 +1146,15 @@ int pp_ctx_set_regroup(pp_ctx *ctx, int on);
  * for BAM inputs (they write BAM already) and for pp_filter_polish_files without outputs.  The state lives on the context, like
  * pp_ctx_set_regroup's; off when the context is made. */
 int pp_ctx_set_out_bam(pp_ctx *ctx, int on);
+
+/* Its mirror, SAM text outputs from BAM for the same drivers (the commands' --out_sam; not in the reference): with `on` != 0,
+ * pp_filter_files and pp_filter_polish_files with outputs named write, for two BAM inputs, every record as a line of SAM text instead
+ * of as a BAM record: per file pp_bam_sam on the bytes the run holds with the filter's own verdicts, then pp_sam_out_write.  Both
+ * files are decoded before either output is created: a record pp_bam_sam refuses ends the call with PP_ERR_QUIT and leaves nothing
+ * behind; the message names the input's path, the 1-based record and --out_sam.  The counts, the log and the FASTA are what they are
+ * without it.  It changes nothing for SAM text inputs (they write text already) and for pp_filter_polish_files without outputs; with
+ * pp_ctx_set_out_bam on as well, each flag speaks to its own kind of input.  Off when the context is made. */
+int pp_ctx_set_out_sam(pp_ctx *ctx, int on);
 
 /* polish::polish (src/polish.rs:26-38): FASTA text exactly as the reference prints to stdout.
  * `sams` are SAM text files or -- all of them -- BAM files (pp_aln_file_kind; a mix is PP_ERR_QUIT).  BAM goes through the record

@@ -1062,7 +1062,9 @@ class BgzfDeflated(_Owned):
 class SamOut(_Owned):
     """pp_sam_tagged / pp_sam_tagged_records: the filter's verdicts written back as SAM text in DEVICE memory, owned by this object --
     byte for byte what pp_filter_write_text writes; the text twin of BamTagged.  Made by SamOut.tagged(ctx, text, pass_, mem=...) or
-    SamRecords.tagged(pass_).
+    SamRecords.tagged(pass_).  pp_bam_sam / pp_bam_sam_encoded make the same object from uncompressed BAM
+    (tests/bam_sam_model.py defines the bytes): SamOut.from_bam(ctx, data, records_at, rec_off, pass_=None, mem=...) or
+    BamEncoded.sam(pass_); there pass_=None appends no tag at all, and a refused record raises PolypolishError with .bad_record.
       text           mem = MEM_HOST: bytes / a uint8 array; MEM_DEVICE: (device address, n_bytes), borrowed for the call
       pass_          None or one byte per ALIGNED line (host): the filter's own verdict, filter_records(...)["pass"][f]
       .dev()         (device address, n_bytes) of the text: what Bgzf / BgzfDeflated / SamRecords take with mem=MEM_DEVICE
@@ -1074,12 +1076,25 @@ class SamOut(_Owned):
                      pass_b"""
     _free, _kernel_ms = "pp_sam_out_free", "pp_sam_out_kernel_ms"
 
-    def __init__(self, ctx, text=None, pass_=None, mem=MEM_HOST, records=None):
+    def __init__(self, ctx, text=None, pass_=None, mem=MEM_HOST, records=None, bam=None, encoded=None):
         L = lib()
         v = None if pass_ is None else np.ascontiguousarray(pass_, dtype=np.uint8)
         vp, vn = (v.ctypes.data if v is not None and len(v) else None), (len(v) if v is not None else 0)
         super().__init__(ctx)
-        if records is not None:
+        if bam is not None or encoded is not None:
+            if v is not None and not len(v):
+                v = np.zeros(1, np.uint8)    # (no verdicts is None; an empty array still is an array of verdicts)
+                vp = v.ctypes.data
+            bad = _no_index()
+            if encoded is not None:
+                rc = L.pp_bam_sam_encoded(ctx._h, encoded._p, vp, vn, C.byref(self._p), C.byref(bad))
+            else:
+                data, records_at, rec_off = bam
+                bp, n_bytes, op, n, _keep = _bytes_and_offsets(data, rec_off, mem)
+                rc = L.pp_bam_sam(ctx._h, bp, n_bytes, int(records_at), op, n, mem, vp, vn, C.byref(self._p), C.byref(bad))
+            if rc:
+                _raise(rc, L.pp_last_error(ctx._h).decode(), bad_record=_index(bad))
+        elif records is not None:
             rc = L.pp_sam_tagged_records(ctx._h, records._p, vp, vn, C.byref(self._p))
         else:
             bp, n_bytes, _, _, _keep = _bytes_and_offsets(text, None, mem)
@@ -1095,6 +1110,11 @@ class SamOut(_Owned):
     @classmethod
     def tagged(cls, ctx, text, pass_, mem=MEM_HOST):
         return cls(ctx, text, pass_, mem)
+
+    @classmethod
+    def from_bam(cls, ctx, data, records_at, rec_off, pass_=None, mem=MEM_HOST):
+        """pp_bam_sam: data / rec_off as BamTagged takes them (MEM_DEVICE: (address, n_bytes) and (address of n uint64, n))"""
+        return cls(ctx, pass_=pass_, mem=mem, bam=(data, records_at, rec_off))
 
     def dev(self):
         return self.bytes_ptr, self.n_bytes
@@ -1143,6 +1163,7 @@ class BamEncoded(_Owned):
       .n_rec, .rec_off_ptr   the records, and the device address of their n_rec uint64 offsets; .rec_off(): a numpy copy
       .tagged(pass_) pp_bam_tagged on the device bytes -> BamTagged (then .deflate().write(path): the compressed file)
       .records(ref_map)      pp_bam_records on the device bytes -> BamRecords
+      .sam(pass_)    pp_bam_sam_encoded: the bytes decoded back to SAM text -> SamOut
       .kernel_ms()   HIP-event time of the kernels (the context had set_profiling on); .stage_ms(): newline_index | pass_a | names |
                      scans | pass_b
     A refused text raises PolypolishError with .bad_record = the 0-based line (None where the refusal names none)."""
@@ -1180,6 +1201,10 @@ class BamEncoded(_Owned):
     def records(self, ref_map=None):
         return BamRecords(self._ctx, self.dev(), (self.rec_off_ptr, self.n_rec), ref_map, mem=MEM_DEVICE)
 
+    def sam(self, pass_=None):
+        """pp_bam_sam_encoded: the bytes decoded back to SAM text -> SamOut"""
+        return SamOut(self._ctx, pass_=pass_, encoded=self)
+
     def stage_ms(self):
         return self._stage_ms("pp_bam_enc_stage_ms_", ("newline_index", "pass_a", "names", "scans", "pass_b"), " when the text was encoded")
 
@@ -1190,6 +1215,14 @@ def sam_bam_geometry():
     a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
     lib().pp_sam_bam_geometry_(C.byref(a), C.byref(b), C.byref(c))
     return int(a.value), int(b.value), int(c.value)
+
+
+def bam_sam_geometry():
+    """(records per workgroup of pass A, output bytes per workgroup of pass B, bytes per store, output bytes per lane and step of the
+    wide parts, lanes per record's group there) of pp_bam_sam: the seams its tests are built on"""
+    v = [C.c_uint32() for _ in range(5)]
+    lib().pp_bam_sam_geometry_(*[C.byref(x) for x in v])
+    return tuple(int(x.value) for x in v)
 
 
 def sam_out_geometry():
@@ -1360,6 +1393,11 @@ class Context:
         """pp_ctx_set_out_bam: filter_files / filter_polish_files write the outputs of SAM text inputs as compressed BAM (the
         commands' --out_bam)."""
         self._chk(lib().pp_ctx_set_out_bam(self._h, int(bool(on))))
+
+    def set_out_sam(self, on=True):
+        """pp_ctx_set_out_sam: filter_files / filter_polish_files write the outputs of BAM inputs as SAM text (the commands'
+        --out_sam)."""
+        self._chk(lib().pp_ctx_set_out_sam(self._h, int(bool(on))))
 
     # ---- seam B -------------------------------------------------------------------------------
     def polish_begin(self, contig_off, bases_ptr, bases_mem, min_depth=5, fraction_valid=0.5, fraction_invalid=0.2):
@@ -1606,6 +1644,18 @@ class Context:
         finally:
             self.set_out_bam(False)
 
+    @contextlib.contextmanager
+    def _writing_sam(self, out_sam):
+        """out_sam=True switches pp_ctx_set_out_sam on for one command and off again behind it"""
+        if not out_sam:
+            yield
+            return
+        self.set_out_sam(True)
+        try:
+            yield
+        finally:
+            self.set_out_sam(False)
+
     def polish_files(self, assembly, sams, fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5,
                      careful=False, debug=None, quiet=True, regroup=False):
         """polish::polish (pp_polish_files): the FASTA bytes.  `sams` are SAM text files, or all of them BAM files (BGZF or
@@ -1623,27 +1673,29 @@ class Context:
 
     def filter_polish_files(self, assembly, in1, in2, out1=None, out2=None, orientation="auto", low=0.1, high=99.9,
                             fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5, careful=False,
-                            debug=None, quiet=True, regroup=False, out_bam=False):
+                            debug=None, quiet=True, regroup=False, out_bam=False, out_sam=False):
         """filter + polish in one process (pp_filter_polish_files): returns (FASTA bytes, filter report).  Two BAM inputs are decoded
         once for both halves; out1 / out2 are then BAM files as well.  regroup: for this call, as set_regroup (the polish half).
-        out_bam: for this call, as set_out_bam (SAM text inputs, out1 / out2 as compressed BAM)."""
+        out_bam: for this call, as set_out_bam (SAM text inputs, out1 / out2 as compressed BAM).  out_sam: for this call, as
+        set_out_sam (BAM inputs, out1 / out2 as SAM text)."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         rep, out = FilterReport(), Bytes()
         enc = lambda x: str(x).encode() if x is not None else None
-        with self._regrouping(regroup), self._writing_bam(out_bam):
+        with self._regrouping(regroup), self._writing_bam(out_bam), self._writing_sam(out_sam):
             self._chk(lib().pp_filter_polish_files(self._h, enc(assembly), enc(in1), enc(in2), enc(out1), enc(out2),
                                                    orientation.encode(), low, high, C.byref(opt), C.byref(rep), C.byref(out)))
         data = C.string_at(out.data, out.len) if out.len else b""
         lib().pp_bytes_free(C.byref(out))
         return data, _report_dict(rep)
 
-    def filter_files(self, in1, in2, out1, out2, orientation="auto", low=0.1, high=99.9, quiet=True, out_bam=False):
+    def filter_files(self, in1, in2, out1, out2, orientation="auto", low=0.1, high=99.9, quiet=True, out_bam=False, out_sam=False):
         """filter::filter (pp_filter_files): writes out1 / out2, returns the report.  in1 / in2 are both SAM text, or both BAM:
         BAM in gives compressed BAM out (pp_bam_tagged -> pp_bam_out_deflate).  out_bam: for this call, as set_out_bam (SAM text
-        in, compressed BAM out through pp_sam_bam)."""
+        in, compressed BAM out through pp_sam_bam).  out_sam: for this call, as set_out_sam (BAM in, SAM text out through
+        pp_bam_sam)."""
         rep = FilterReport()
-        with self._writing_bam(out_bam):
+        with self._writing_bam(out_bam), self._writing_sam(out_sam):
             self._chk(lib().pp_filter_files(self._h, str(in1).encode(), str(in2).encode(), str(out1).encode(),
                                             str(out2).encode(), orientation.encode(), low, high, int(quiet),
                                             C.byref(rep)))

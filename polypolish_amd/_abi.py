@@ -190,6 +190,8 @@ SIGNATURES = {
     "pp_bam_enc_rec_off": (_vp, [_vp, _pu64]),
     "pp_bam_enc_kernel_ms": (_i, [_vp, _pf32]),
     "pp_bam_enc_free": (None, [_vp]),
+    "pp_bam_sam": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _i, _vp, _u64, _pvp, _pu64]),
+    "pp_bam_sam_encoded": (_i, [_vp, _vp, _vp, _u64, _pvp, _pu64]),
     "pp_aln_file_kind": (_i, [_str, _P(_i)]),
     "pp_polish_set_emit": (_i, [_vp, _vp, _vp]),
     "pp_polish_begin": (_i, [_vp, _u32, _vp, _vp, _i, _P(Params)]),
@@ -251,6 +253,7 @@ SIGNATURES = {
     "pp_bytes_free": (None, [_P(Bytes)]),
     "pp_ctx_set_regroup": (_i, [_vp, _i]),
     "pp_ctx_set_out_bam": (_i, [_vp, _i]),
+    "pp_ctx_set_out_sam": (_i, [_vp, _i]),
     "pp_polish_files": (_i, [_vp, _str, _P(_str), _i, _P(PolishOptions), _P(Bytes)]),
     "pp_polish_files_multi": (_i, [_pvp, _i, _str, _P(_str), _i, _P(PolishOptions), _P(Bytes)]),
     "pp_dev_ingest_create": (_i, [_vp, _vp, _u32, _i, _pvp]),
@@ -284,6 +287,7 @@ HOOKS = {
     "pp_sam_out_geometry_": (None, [_pu32] * 3),
     "pp_bam_enc_stage_ms_": (_i, [_vp, _pf32]),     # float[5]
     "pp_sam_bam_geometry_": (None, [_pu32] * 3),
+    "pp_bam_sam_geometry_": (None, [_pu32] * 5),
     "pp_bam_offs_stage_ms_": (_i, [_vp, _pf32]),    # float[3]
     "pp_bam_offs_stats_": (_i, [_vp, _pu64]),       # uint64[4]
     "pp_bam_walk_geometry_": (None, [_pu32] * 3),

@@ -34,6 +34,7 @@ static const char *HELP_FILTER =
     "      --out2 <OUT2>                Output SAM file - first second in pairs\n"
     "                                   (two BAM inputs are read as they are and give two BAM outputs)\n"
     "      --out_bam                    SAM text inputs: write the outputs as compressed BAM (not in the reference)\n"
+    "      --out_sam                    BAM inputs: write the outputs as SAM text (not in the reference)\n"
     "      --orientation <ORIENTATION>  Expected pair orientation [default: auto]\n"
     "      --low <LOW>                  Low percentile threshold [default: 0.1]\n"
     "      --high <HIGH>                High percentile threshold [default: 99.9]\n"
@@ -61,7 +62,8 @@ static const char *HELP_FUSED =
     "The FASTA on stdout is byte-identical to `filter` followed by `polish` on its outputs.\n"
     "--in1/--in2 are both SAM text or both BAM; with BAM the optional outputs are BAM as well.\n"
     "--regroup: coordinate-sorted BAM inputs (the polish brings every read's alignments together; the outputs keep file order).\n"
-    "--out_bam: SAM text inputs with --out1/--out2: write the outputs as compressed BAM.\n";
+    "--out_bam: SAM text inputs with --out1/--out2: write the outputs as compressed BAM.\n"
+    "--out_sam: BAM inputs with --out1/--out2: write the outputs as SAM text.\n";
 
 static int usage_error(const char *msg) {
     fprintf(stderr, "error: %s\n\nFor more information, try '--help'.\n", msg);
@@ -324,7 +326,8 @@ int main(int argc, char **argv) {
                                             {"--min_depth", 'd', true, "<MIN_DEPTH>"},
                                             {"--careful", 0, false, ""},
                                             {"--regroup", 0, false, ""},
-                                            {"--out_bam", 0, false, ""}};
+                                            {"--out_bam", 0, false, ""},
+                                            {"--out_sam", 0, false, ""}};
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help || P.version) { fputs(HELP_FUSED, stdout); return 0; }
         std::string perr = P.error;
@@ -348,6 +351,7 @@ int main(int argc, char **argv) {
         if (rc) return no_device(device);
         pp_ctx_set_regroup(ctx, regroup);
         pp_ctx_set_out_bam(ctx, P.value[14] != nullptr);
+        pp_ctx_set_out_sam(ctx, P.value[15] != nullptr);
         pp_bytes fasta{nullptr, 0};
         rc = pp_filter_polish_files(ctx, assembly, in1, in2, out1, out2, orientation, low, high, &opt, nullptr, &fasta);
         if (pp_ctx_wait(ctx) != PP_OK) return no_device(device);
@@ -366,7 +370,8 @@ int main(int argc, char **argv) {
         const std::vector<OptSpec> specs = {{"--in1", 0, true, "<IN1>"}, {"--in2", 0, true, "<IN2>"},
                                             {"--out1", 0, true, "<OUT1>"}, {"--out2", 0, true, "<OUT2>"},
                                             {"--orientation", 0, true, "<ORIENTATION>"}, {"--low", 0, true, "<LOW>"},
-                                            {"--high", 0, true, "<HIGH>"}, {"--out_bam", 0, false, ""}};
+                                            {"--high", 0, true, "<HIGH>"}, {"--out_bam", 0, false, ""},
+                                            {"--out_sam", 0, false, ""}};
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help) { fputs(HELP_FILTER, stdout); return 0; }
         if (P.version) { printf("polypolish-filter v0.6.1\n"); return 0; }
@@ -384,6 +389,7 @@ int main(int argc, char **argv) {
         int rc = pp_ctx_create_async(device, &ctx);
         if (rc) return no_device(device);
         pp_ctx_set_out_bam(ctx, P.value[7] != nullptr);
+        pp_ctx_set_out_sam(ctx, P.value[8] != nullptr);
         rc = pp_filter_files(ctx, in1, in2, out1, out2, orientation, low, high, 0, nullptr);
         if (pp_ctx_wait(ctx) != PP_OK) return no_device(device);
         if (rc) {

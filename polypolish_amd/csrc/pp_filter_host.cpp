@@ -1085,6 +1085,34 @@ int filter_write_bam(pp_ctx *ctx, const Log &log, const FilterRun &R, const char
     return PP_OK;
 }
 
+// filter_sams for BAM with --out_sam: every record as a line of SAM text on the device (pp_bam_sam), "\tZP:Z:fail" behind the lines
+// whose verdict is 0, written.  Both files are decoded before either output is created: a record the decoder refuses leaves nothing
+// behind.  The log is filter_write_bam's, word for word.
+int filter_write_bam_sam(pp_ctx *ctx, const Log &log, const FilterRun &R, const char *const ins[2], const char *const outs[2]) {
+    log("Filtering SAM files\n");
+    pp_sam_out *text[2] = {nullptr, nullptr};
+    struct Free {
+        pp_sam_out **t;
+        ~Free() { pp_sam_out_free(t[0]); pp_sam_out_free(t[1]); }
+    } free_text{text};
+    for (int f = 0; f < 2; f++) {
+        const ppb::BamFile &F = R.F[f];
+        uint64_t bad = ~0ull;
+        if (pp_bam_sam(ctx, F.bytes, F.n_bytes, F.records_at, F.rec_off, F.n_rec, F.mem, R.pass[f].data(), R.n_aln[f], &text[f], &bad) != PP_OK) {
+            const std::string said = pp_last_error(ctx);
+            if (bad != ~0ull) return ppb::fail(ctx, PP_ERR_QUIT, "--out_sam: \"%s\" (record %llu): %s", ins[f], (unsigned long long)(bad + 1), said.c_str());
+            return ppb::fail(ctx, PP_ERR_QUIT, "--out_sam: \"%s\": %s", ins[f], said.c_str());
+        }
+    }
+    for (int f = 0; f < 2; f++) {
+        uint64_t p_ = 0, f_ = 0, lines = 0;
+        pp_sam_out_counts(text[f], &p_, &f_, &lines);
+        if (int rc = pp_sam_out_write(text[f], outs[f])) return rc;
+        log("Filtering %s:\n  %s pass\n  %s fail\n\n", ins[f], commas(p_).c_str(), commas(f_).c_str());
+    }
+    return PP_OK;
+}
+
 int check_filter_options(pp_ctx *ctx, const char *const *names, int n_names, double low, double high) {
     // check_inputs, filter.rs:40-53
     for (int i = 0; i < n_names; i++)
@@ -1109,11 +1137,11 @@ int run_filter(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const std::func
                        : filter_core(ctx, log, lap, ins, orientation, low, high, R))
         return rc;
     if (outs[0]) {
-        const bool text_to_bam = !R.bam && pp_ctx_out_bam_(ctx);
-        if (int rc = R.bam ? filter_write_bam(ctx, log, R, ins, outs)
+        const bool text_to_bam = !R.bam && pp_ctx_out_bam_(ctx), bam_to_text = R.bam && pp_ctx_out_sam_(ctx);
+        if (int rc = R.bam ? (bam_to_text ? filter_write_bam_sam(ctx, log, R, ins, outs) : filter_write_bam(ctx, log, R, ins, outs))
                            : (text_to_bam ? filter_write_sam_bam(ctx, log, R, ins, outs, &R.rep.after_count) : filter_write(ctx, log, R, ins, outs, &R.rep.after_count)))
             return rc;
-        lap(R.bam || text_to_bam ? "filtered BAMs written" : "filtered SAMs written");
+        lap((R.bam && !bam_to_text) || text_to_bam ? "filtered BAMs written" : "filtered SAMs written");
     } else if (!R.bam) {  // (BAM: pp_filter_records has counted; SAM text without outputs: from the verdicts)
         for (int f = 0; f < 2; f++)
             for (uint64_t i = 0; i < R.n_aln[f]; i++) R.rep.after_count += R.pass[f][i];

@@ -267,6 +267,7 @@ struct pp_ctx {
     pp::DevBuf f_rec[48];  // pp_filter_records: the call's arrays and scratch, in the order it asks for them (pp_filter_rec.hip)
     pp::DevBuf g_rec[24];  // pp_batch_regroup: the call's scratch, in the order it asks for it (pp_regroup.hip)
     bool out_bam = false;  // pp_ctx_set_out_bam: the filter drivers write SAM text inputs back as compressed BAM
+    bool out_sam = false;  // pp_ctx_set_out_sam: the filter drivers write BAM inputs back as SAM text
     bool regroup = false;  // pp_ctx_set_regroup: the file drivers regroup every BAM file's records in front of the gate
     pp::DevBuf f_thr;  // pp_filter_thresholds: orientation counts | the selection's state | its two histograms (THR_WORDS u32)
     pp_filter_input fdev{};

@@ -393,6 +393,24 @@ extern "C" void pp_sam_out_geometry_(uint32_t *lines, uint32_t *tile, uint32_t *
     if (store) *store = ST_STORE;
 }
 
+// (internal, pp_bam_sam.hip: the link that makes the same object from BAM) an object with room for `alloc` bytes of text in device
+// memory, then what it holds; ms4: the stage times, or null where the context had no profiling on
+extern "C" int pp_sam_out_new_(pp_ctx *ctx, uint64_t alloc, pp_sam_out **out, uint8_t **d_out) {
+    std::unique_ptr<pp_sam_out> P(new pp_sam_out(ctx));
+    if (int rc = P->alloc(P->d_out, (size_t)std::max<uint64_t>(alloc, ST_STORE))) return rc;
+    *d_out = P->d_out;
+    *out = P.release();
+    return PP_OK;
+}
+extern "C" void pp_sam_out_set_(pp_sam_out *o, uint64_t n_out, uint64_t pass_count, uint64_t fail_count, uint64_t n_lines, const float *ms4) {
+    o->n_out = n_out;
+    o->pass_count = pass_count;
+    o->fail_count = fail_count;
+    o->n_lines = n_lines;
+    o->t.timed = ms4 != nullptr;
+    if (ms4) std::copy(ms4, ms4 + 4, o->t.ms);
+}
+
 extern "C" int pp_sam_out_write(const pp_sam_out *o, const char *path) {
     if (!o || !o->ctx) return PP_ERR_ARG;
     if (!path) return o->ctx->fail(PP_ERR_ARG, "pp_sam_out_write: null argument");
