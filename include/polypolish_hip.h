@@ -1093,6 +1093,55 @@ const char *pp_assembly_description(const pp_assembly *a, uint32_t i);
 const uint64_t *pp_assembly_offsets(const pp_assembly *a); /* n_contigs+1 */
 const uint8_t *pp_assembly_bases(const pp_assembly *a);
 
+/* ---- FASTA text -> contig bases on the device (pp_fasta.hip) ----------------------------------
+ * pp_fasta_records is load_fasta_not_gzipped + check_load_fasta (src/misc.rs:102-133, 56-75) exactly as pp_assembly_load restates
+ * them, this project's deviations included, for a caller who holds FASTA bytes: text[0, n_bytes) in host memory (PP_MEM_HOST: one
+ * staging copy) or in memory of the context's device (PP_MEM_DEVICE: read where it is, at any alignment).  The text is read once;
+ * the object owns its output only.  No byte outside [0, n_bytes) is loaded, by a wide load either: a device text may end where its
+ * allocation ends, and nothing behind n_bytes can change a result.
+ *   lines       end at "\n"; a "\r" directly in front of it is dropped, and so is one that is the text's last byte (as the host
+ *               loader's line reader does); any other "\r" is a byte of its line.  A missing final newline is fine; lines that are
+ *               empty after that are skipped.
+ *   headers     a line whose first byte is '>': name = what lies between '>' and the first Unicode White_Space character (multi-byte
+ *               forms included), description = everything behind that one character.  A header with an empty name opens no contig
+ *               and is dropped silently when a header or the end of the text follows.
+ *   sequence    every other line: its bytes are appended to the open contig, ASCII letters upper-cased, nothing stripped.
+ *   refusals    the first offending line in file order wins, whatever its kind; *bad_line (may be NULL) = its 0-based index among all
+ *               lines, ~0 where no line is to blame.  PP_ERR_QUIT "... is not correctly formatted": a sequence line with no named
+ *               header open.  PP_ERR_QUIT "unable to load ...": a header, or an offending sequence line, that is not valid UTF-8.
+ *               PP_ERR_LIMIT: a byte >= 0x80 in a sequence line that is valid UTF-8.  Behind the walk, in this order, PP_ERR_QUIT
+ *               "contains no sequences", "has an empty sequence", "has a duplicated name".  The path in every message is `text`.
+ *               The device decides which line is refused; the host loader's code then runs on that one line.
+ *   arguments   PP_ERR_ARG: null arguments, PP_MEM_PEER, a null text with n_bytes > 0.  PP_ERR_LIMIT: n_bytes >= 2^40.  (The limit of
+ *               2^32 - 4096 bases stays with pp_polish_begin.)
+ * The device does what is proportional to the text (line ends, line kinds, the bases compacted and upper-cased, the bases in front of
+ * every header, the header lines' ranges, the first offending byte); the host what is proportional to the headers.  The context's
+ * stream has been synchronised when the call returns.
+ *   pp_fasta_bases        the bases of all contigs, one behind the other (DEVICE, borrowed until pp_fasta_free): what
+ *                         pp_polish_begin(..., PP_MEM_DEVICE, ...) takes
+ *   pp_fasta_offsets      HOST, n_contigs + 1: contig i is bases[off[i], off[i + 1])
+ *   pp_fasta_kernel_ms    HIP-event time of the kernels (not of a host text's staging copy); PP_ERR_ARG unless the context had
+ *                         profiling on at pp_fasta_records
+ * The object belongs to its context and is freed before it. */
+typedef struct pp_fasta pp_fasta;
+int pp_fasta_records(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, pp_fasta **out, uint64_t *bad_line);
+void pp_fasta_bases(const pp_fasta *f, const uint8_t **dev, uint64_t *n_bases); /* DEVICE, borrowed */
+uint32_t pp_fasta_n_contigs(const pp_fasta *f);
+const uint64_t *pp_fasta_offsets(const pp_fasta *f); /* HOST, n_contigs + 1 */
+const char *pp_fasta_name(const pp_fasta *f, uint32_t i);
+const char *pp_fasta_description(const pp_fasta *f, uint32_t i);
+int pp_fasta_kernel_ms(const pp_fasta *f, float *ms);
+void pp_fasta_free(pp_fasta *f);
+
+/* pp_assembly_load through pp_fasta_records: the same pp_assembly (names, descriptions, offsets, index), its bases in device memory.
+ * A plain file is mapped and parsed as PP_MEM_HOST; a BGZF file (bgzip) is inflated by pp_bgzf_inflate and parsed from device memory;
+ * a gzip file that is not BGZF goes to pp_assembly_load unchanged.  The codes and messages are those of pp_assembly_load on the same
+ * file, byte for byte; a HIP failure is PP_ERR_HIP with the context's message.  The object belongs to the context and is freed before
+ * it.  pp_assembly_bases_device: the bases in DEVICE memory, NULL for an assembly whose bases are in host memory (pp_assembly_load,
+ * the gzip case); pp_assembly_bases on such an object downloads them once, on first use (not from two threads at once). */
+int pp_assembly_load_device(pp_ctx *ctx, const char *path, pp_assembly **out, char *err, size_t errlen);
+const uint8_t *pp_assembly_bases_device(const pp_assembly *a);
+
 typedef struct pp_ingest pp_ingest;
 int pp_ingest_create(const pp_assembly *a, uint32_t max_errors, int careful, pp_ingest **out);
 /* add_to_pileup's streaming half (src/alignment.rs:225-272): parse, group adjacent QNAMEs, apply

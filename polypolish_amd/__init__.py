@@ -962,6 +962,52 @@ class SamRecords(_Owned):
         return BamEncoded(self._ctx, records=self)
 
 
+class FastaRecords(_Owned):
+    """pp_fasta_records: FASTA text as contig bases in DEVICE memory, owned by this object -- the device twin of pp_assembly_load, next
+    to SamRecords.  The text is read once; the object owns its output only.
+      data           mem = MEM_HOST: bytes / a uint8 array; MEM_DEVICE: (device address, n_bytes), free again when the call returns
+      .bases         (device address, n_bases): the bases of all contigs one behind the other, upper-cased: what a polish job takes
+      .n_bases, .n_contigs
+      .offsets       np.uint64, n_contigs + 1: contig i is bases[offsets[i] : offsets[i + 1]]
+      .names, .descriptions   lists of bytes
+      .host()        {"bases": the bases as bytes (one download), "offsets", "names", "descriptions"}
+      .kernel_ms()   HIP-event time of the kernels (the context had set_profiling on); .stage_ms(): copy | sums | place | headers
+    A refused text raises PolypolishError with .bad_record = the 0-based line (None where the refusal names none)."""
+    _free, _kernel_ms = "pp_fasta_free", "pp_fasta_kernel_ms"
+
+    def __init__(self, ctx, data, mem=MEM_HOST):
+        L = lib()
+        bp, n_bytes, _, _, _keep = _bytes_and_offsets(data, None, mem)
+        super().__init__(ctx)
+        bad = _no_index()
+        rc = L.pp_fasta_records(ctx._h, bp, n_bytes, mem, C.byref(self._p), C.byref(bad))
+        if rc:
+            _raise(rc, L.pp_last_error(ctx._h).decode(), bad_record=_index(bad))
+        dev, nb = C.c_void_p(), C.c_uint64(0)
+        L.pp_fasta_bases(self._p, C.byref(dev), C.byref(nb))
+        self.n_bases, self.n_contigs = int(nb.value), int(L.pp_fasta_n_contigs(self._p))
+        self.bases = (dev.value or 0, self.n_bases)
+        self.offsets = _host(L.pp_fasta_offsets(self._p), self.n_contigs + 1, np.uint64)
+        self.names = [L.pp_fasta_name(self._p, i) for i in range(self.n_contigs)]
+        self.descriptions = [L.pp_fasta_description(self._p, i) for i in range(self.n_contigs)]
+
+    def host(self):
+        b = self._ctx.download(self.bases[0], self.n_bases, np.uint8).tobytes() if self.n_bases else b""
+        return {"bases": b, "offsets": self.offsets, "names": self.names, "descriptions": self.descriptions}
+
+    def stage_ms(self):
+        return self._stage_ms("pp_fasta_stage_ms_", ("copy", "sums", "place", "headers"), " when the text was parsed")
+
+
+def fasta_geometry():
+    """(bytes per lane, bytes per tile T, bytes per workgroup W) of pp_fasta_records: the seams its tests aim at.  Tiles are cut at
+    multiples of the lane's bytes of ADDRESS: a device text whose first byte lies s bytes behind such a multiple has its seams at
+    the text offsets k * T - s."""
+    a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    lib().pp_fasta_geometry_(C.byref(a), C.byref(b), C.byref(c))
+    return int(a.value), int(b.value), int(c.value)
+
+
 class BamTagged(_Owned):
     """pp_bam_tagged: the filter's verdicts written back as a BAM file (level-0 BGZF) in DEVICE memory, owned by this object.
       data, rec_off  mem = MEM_HOST: bytes / a uint8 array of uncompressed BAM, and the records' offsets; MEM_DEVICE: data = (device

@@ -162,7 +162,7 @@ SIGNATURES = {
     "pp_sam_pass": (None, [_vp, _pvp, _pu64]),
     "pp_sam_kernel_ms": (_i, [_vp, _pf32]),
     "pp_sam_free": (None, [_vp]),
-    "pp_bam_tagged": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _i, _vp, _u64, _pvp, _pu64]),
+        "pp_bam_tagged": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _i, _vp, _u64, _pvp, _pu64]),
     "pp_bam_out_bytes": (None, [_vp, _pvp, _pu64]),
     "pp_bam_out_counts": (None, [_vp, _pu64, _pu64, _pu64]),
     "pp_bam_out_write": (_i, [_vp, _str]),
@@ -244,6 +244,16 @@ SIGNATURES = {
     "pp_assembly_description": (_str, [_vp, _u32]),
     "pp_assembly_offsets": (_pu64, [_vp]),
     "pp_assembly_bases": (_P(_u8), [_vp]),
+    "pp_fasta_records": (_i, [_vp, _vp, _u64, _i, _pvp, _pu64]),
+    "pp_fasta_bases": (None, [_vp, _pvp, _pu64]),
+    "pp_fasta_n_contigs": (_u32, [_vp]),
+    "pp_fasta_offsets": (_vp, [_vp]),
+    "pp_fasta_name": (_str, [_vp, _u32]),
+    "pp_fasta_description": (_str, [_vp, _u32]),
+    "pp_fasta_kernel_ms": (_i, [_vp, _pf32]),
+    "pp_fasta_free": (None, [_vp]),
+    "pp_assembly_load_device": (_i, [_vp, _str, _pvp, _str, _sz]),
+    "pp_assembly_bases_device": (_vp, [_vp]),
     "pp_ingest_create": (_i, [_vp, _u32, _i, _pvp]),
     "pp_ingest_sam": (_i, [_vp, _str, _P(SamCounts), _str, _sz]),
     "pp_ingest_sam_filtered": (_i, [_vp, _str, _vp, _u64, _P(SamCounts), _str, _sz]),
@@ -281,6 +291,8 @@ HOOKS = {
     "pp_bgzf_stage_ms_": (_i, [_vp, _pf32]),        # float[3]
     "pp_bam_stage_ms_": (_i, [_vp, _pf32]),         # float[3]
     "pp_sam_stage_ms_": (_i, [_vp, _pf32]),         # float[5]
+    "pp_fasta_stage_ms_": (_i, [_vp, _pf32]),       # float[4]
+    "pp_fasta_geometry_": (None, [_pu32] * 3),
     "pp_bam_out_stage_ms_": (_i, [_vp, _pf32]),     # float[3]
     "pp_bgzf_out_stage_ms_": (_i, [_vp, _pf32]),    # float[3]
     "pp_sam_out_stage_ms_": (_i, [_vp, _pf32]),     # float[4]

@@ -60,6 +60,14 @@ int file_kind(pp_ctx *ctx, const char *path, int *kind);
 int seed_names(pp_names *t, const pp_assembly *a);
 // the name behind an id of `t`, for a message
 std::string name_of(const pp_names *t, uint64_t id);
+// The commands' loader of the assembly.  PP_DEVICE_FASTA=1 in the environment and one context: pp_assembly_load_device, the bases stay
+// in device memory (begin_job of pp_driver.h hands them to pp_polish_begin as PP_MEM_DEVICE); otherwise pp_assembly_load.  Off by
+// default, like PP_DEVICE_FILTER and PP_BAM_PREPARE; the codes and the messages are the same either way.
+inline int load_assembly_file(pp_ctx *ctx, int n_ctx, const char *path, pp_assembly **out, char *err, size_t errlen) {
+    const char *e = getenv("PP_DEVICE_FASTA");
+    if (e && atoi(e) != 0 && n_ctx == 1) return pp_assembly_load_device(ctx, path, out, err, errlen);
+    return pp_assembly_load(path, out, err, errlen);
+}
 
 // polish::polish over BAM files that a caller has opened and decoded already (pp_filter_polish_files decodes once): fronts[i] for
 // paths[i], pass[i] the filter's own verdicts for its aligned records (the driver ANDs them with pp_bam_pass), `a` the loaded assembly, rnames / qnames

@@ -182,7 +182,7 @@ static void log_banner(const PolishJob &J) {
 static int load_assembly(PolishJob &J) {
     J.log("Loading assembly\n");
     if (!J.a_borrowed)  // (else: loaded for the filter's RNAME table already)
-        if (int rc = pp_assembly_load(J.assembly, &J.a, J.err, sizeof J.err)) return set_err(J.ctx, rc, J.err);
+        if (int rc = ppb::load_assembly_file(J.ctx, J.n_ctx, J.assembly, &J.a, J.err, sizeof J.err)) return set_err(J.ctx, rc, J.err);
     J.nc = pp_assembly_n_contigs(J.a);
     J.off = pp_assembly_offsets(J.a);
     J.names.resize(J.nc);

@@ -186,7 +186,11 @@ struct PolishJob {
 inline int set_err(pp_ctx *ctx, int code, const char *msg) { return pp_ctx_set_error_(ctx, code, msg); }
 // run f(d) for every context on its own thread; the first failure (lowest d) is returned, its text put on ctxs[0]
 int on_all(PolishJob &J, const std::function<int(int)> &f);
-inline int begin_job(PolishJob &J, pp_ctx *ctx) { return pp_polish_begin(ctx, J.nc, J.off, pp_assembly_bases(J.a), PP_MEM_HOST, &J.prm); }
+// (an assembly loaded through the device link, PP_DEVICE_FASTA=1 and one context: its bases are in that context's device memory)
+inline int begin_job(PolishJob &J, pp_ctx *ctx) {
+    const uint8_t *dev = J.n_ctx == 1 ? pp_assembly_bases_device(J.a) : nullptr;
+    return pp_polish_begin(ctx, J.nc, J.off, dev ? dev : pp_assembly_bases(J.a), dev ? PP_MEM_DEVICE : PP_MEM_HOST, &J.prm);
+}
 // Room in the job for all files at once, from the batches that are known: their sizes times `scale` = what all files take on disk
 // over what the known ones take, 2 % over and 64 at the most (scale_to_all_files); the caller decides when that is worth asking.
 double bytes_on_disk(const PolishJob &J, int n_files);

@@ -1032,7 +1032,7 @@ int filter_core_bam(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char
     pp_filter_file_counts fc[2] = {};
     if (assembly) {
         char err[1400] = "";
-        if ((rc = pp_assembly_load(assembly, &R.a, err, sizeof err))) return pp_ctx_set_error_(ctx, rc, err);
+        if ((rc = ppb::load_assembly_file(ctx, 1, assembly, &R.a, err, sizeof err))) return pp_ctx_set_error_(ctx, rc, err);
         if ((rc = pp_names_create(ctx, pp_assembly_n_contigs(R.a), &R.rnames))) return rc;
         if ((rc = ppb::seed_names(R.rnames, R.a))) return rc;
     }

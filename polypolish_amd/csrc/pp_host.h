@@ -231,6 +231,26 @@ inline void prefetch_drop_all(const void *owner) {  // whatever `owner` had pref
     }
 }
 
+// char::is_whitespace (Unicode White_Space: what `splitn(2, char::is_whitespace)` splits a FASTA header at, misc.rs:118-120)
+// at the start of the valid UTF-8 text p[0 .. left): the bytes of that character, 0 if it is not whitespace.
+// U+0009-000D, 0020, 0085, 00A0, 1680, 2000-200A, 2028, 2029, 202F, 205F, 3000.  (pp_ingest.cpp's load_fasta and pp_fasta_host.h)
+inline size_t rust_ws_len(const char *p, size_t left) {
+    const unsigned char c = (unsigned char)p[0];
+    if (c == ' ' || (c >= 0x09 && c <= 0x0D)) return 1;
+    if (c == 0xC2 && left >= 2) {
+        const unsigned char d = (unsigned char)p[1];
+        return d == 0x85 || d == 0xA0 ? 2 : 0;
+    }
+    if (left >= 3) {
+        const unsigned char d = (unsigned char)p[1], e = (unsigned char)p[2];
+        if (c == 0xE1 && d == 0x9A && e == 0x80) return 3;
+        if (c == 0xE2 && d == 0x80 && ((e >= 0x80 && e <= 0x8A) || e == 0xA8 || e == 0xA9 || e == 0xAF)) return 3;
+        if (c == 0xE2 && d == 0x81 && e == 0x9F) return 3;
+        if (c == 0xE3 && d == 0x80 && e == 0x80) return 3;
+    }
+    return 0;
+}
+
 // BufRead::lines() yields an error for a line that is not valid UTF-8, and every loader of the reference turns that into
 // "unable to load ..." (src/alignment.rs:238-240, src/filter.rs:119-121, src/misc.rs:109-111).  Lines are ASCII in
 // practice: eight bytes at a time until a byte with its top bit set shows up, the full check (overlong forms, surrogates,

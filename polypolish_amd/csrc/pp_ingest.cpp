@@ -92,25 +92,7 @@ struct LineReader {
     }
 };
 
-// char::is_whitespace (Unicode White_Space: what `splitn(2, char::is_whitespace)` splits a FASTA header at, misc.rs:118-120)
-// at the start of the valid UTF-8 text p[0 .. left): the bytes of that character, 0 if it is not whitespace.
-// U+0009-000D, 0020, 0085, 00A0, 1680, 2000-200A, 2028, 2029, 202F, 205F, 3000.
-inline size_t rust_ws_len(const char *p, size_t left) {
-    const unsigned char c = (unsigned char)p[0];
-    if (c == ' ' || (c >= 0x09 && c <= 0x0D)) return 1;
-    if (c == 0xC2 && left >= 2) {
-        const unsigned char d = (unsigned char)p[1];
-        return d == 0x85 || d == 0xA0 ? 2 : 0;
-    }
-    if (left >= 3) {
-        const unsigned char d = (unsigned char)p[1], e = (unsigned char)p[2];
-        if (c == 0xE1 && d == 0x9A && e == 0x80) return 3;
-        if (c == 0xE2 && d == 0x80 && ((e >= 0x80 && e <= 0x8A) || e == 0xA8 || e == 0xA9 || e == 0xAF)) return 3;
-        if (c == 0xE2 && d == 0x81 && e == 0x9F) return 3;
-        if (c == 0xE3 && d == 0x80 && e == 0x80) return 3;
-    }
-    return 0;
-}
+using pph::rust_ws_len;  // char::is_whitespace at the start of a header's text (pp_host.h)
 
 // str::parse::<uN>(): optional '+', ASCII digits, overflow is an error
 bool parse_unsigned(const char *s, size_t n, uint64_t max, uint64_t &out) {
@@ -155,11 +137,19 @@ inline int op_code(char c) {
 }  // namespace
 
 // =================================================================================================
+extern "C" int pp_fasta_records_named_(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, const char *path, pp_fasta **out,
+                                       uint64_t *bad_line);
+extern "C" int pp_fasta_download_(const pp_fasta *f, uint8_t *host);
+
 struct pp_assembly {
     std::vector<std::string> names, descs;
     std::vector<uint64_t> off;
-    HugeBuf<uint8_t> bases;  // (anonymous huge pages: a 250 Mbp assembly is not zero-filled before it is written)
+    // (anonymous huge pages: a 250 Mbp assembly is not zero-filled before it is written)  Of an assembly made by
+    // pp_assembly_load_device: empty until pp_assembly_bases asks for the bases in host memory.
+    mutable HugeBuf<uint8_t> bases;
     std::unordered_map<std::string, uint32_t> index;
+    pp_fasta *dev = nullptr;  // pp_assembly_load_device: the bases in device memory, owned
+    ~pp_assembly() { pp_fasta_free(dev); }
 };
 
 namespace {
@@ -277,7 +267,76 @@ extern "C" uint32_t pp_assembly_n_contigs(const pp_assembly *a) { return a ? (ui
 extern "C" const char *pp_assembly_name(const pp_assembly *a, uint32_t i) { return a->names[i].c_str(); }
 extern "C" const char *pp_assembly_description(const pp_assembly *a, uint32_t i) { return a->descs[i].c_str(); }
 extern "C" const uint64_t *pp_assembly_offsets(const pp_assembly *a) { return a->off.data(); }
-extern "C" const uint8_t *pp_assembly_bases(const pp_assembly *a) { return a->bases.data(); }
+extern "C" const uint8_t *pp_assembly_bases(const pp_assembly *a) {
+    if (a->dev && a->bases.empty() && a->off.back() > 0) {  // the first use of a device assembly's bases on the host: one download
+        a->bases.resize((size_t)a->off.back());
+        if (pp_fasta_download_(a->dev, a->bases.data()) != PP_OK) {
+            a->bases.resize(0);
+            return nullptr;
+        }
+    }
+    return a->bases.data();
+}
+
+extern "C" const uint8_t *pp_assembly_bases_device(const pp_assembly *a) {
+    const uint8_t *dev = nullptr;
+    if (a && a->dev) pp_fasta_bases(a->dev, &dev, nullptr);
+    return dev;
+}
+
+// pp_assembly_load through the device link.  is_file_gzipped's two refusals come first, in load_fasta's words; a gzip file that is no
+// BGZF chain, or one the device inflate refuses, is the host loader's.
+extern "C" int pp_assembly_load_device(pp_ctx *ctx, const char *path, pp_assembly **out, char *err, size_t errlen) {
+    if (!ctx || !path || !out) return PP_ERR_ARG;
+    *out = nullptr;
+    auto say = [&](int code, const char *fmt) {
+        if (err && errlen) snprintf(err, errlen, fmt, path);
+        return code;
+    };
+    FILE *f = fopen(path, "rb");
+    if (!f) return say(PP_ERR_QUIT, "unable to open \"%s\"");
+    unsigned char magic[2];
+    const size_t got = fread(magic, 1, 2, f);
+    fclose(f);
+    if (got != 2) return say(PP_ERR_QUIT, "\"%s\" is too small");
+    pph::FileText mapped;
+    if (!mapped.open_file(path)) return say(PP_ERR_QUIT, "unable to load \"%s\"");
+    const uint8_t *bytes = (const uint8_t *)mapped.text;
+    pp_fasta *fa = nullptr;
+    int rc;
+    if (magic[0] == 31 && magic[1] == 139) {
+        uint64_t n_blk = 0, end = 0;
+        pp_bgzf *z = nullptr;
+        if (pp_bgzf_walk(bytes, mapped.size, 0, nullptr, nullptr, 0, &n_blk, &end) != PP_OK || end != mapped.size ||
+            pp_bgzf_inflate(ctx, bytes, mapped.size, nullptr, 0, PP_MEM_HOST, &z, nullptr) != PP_OK) {
+            mapped.close_file();
+            return pp_assembly_load(path, out, err, errlen);
+        }
+        const uint8_t *dev = nullptr;
+        uint64_t n = 0;
+        pp_bgzf_bytes(z, &dev, &n);
+        rc = pp_fasta_records_named_(ctx, dev, n, PP_MEM_DEVICE, path, &fa, nullptr);
+        pp_bgzf_free(z);
+    } else {
+        rc = pp_fasta_records_named_(ctx, bytes, mapped.size, PP_MEM_HOST, path, &fa, nullptr);
+    }
+    if (rc != PP_OK) {
+        if (err && errlen) snprintf(err, errlen, "%s", pp_last_error(ctx));
+        return rc;
+    }
+    pp_assembly *a = new pp_assembly();
+    a->dev = fa;
+    const uint32_t nc = pp_fasta_n_contigs(fa);
+    const uint64_t *off = pp_fasta_offsets(fa);
+    a->off.assign(off, off + nc + 1);
+    for (uint32_t i = 0; i < nc; i++) {
+        a->names.emplace_back(pp_fasta_name(fa, i));
+        a->descs.emplace_back(pp_fasta_description(fa, i));
+        a->index.emplace(a->names.back(), i);
+    }
+    *out = a;
+    return PP_OK;
+}
 
 // =================================================================================================
 struct pp_ingest {
