@@ -20,7 +20,7 @@ $(OUT)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/polypolish_hip.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(OUT)/%.o: $(CSRC)/%.cpp include/polypolish_hip.h $(CSRC)/pp_host.h $(CSRC)/pp_bam_files.h $(CSRC)/pp_driver.h
+$(OUT)/%.o: $(CSRC)/%.cpp include/polypolish_hip.h $(CSRC)/pp_host.h $(CSRC)/pp_bam_files.h $(CSRC)/pp_driver.h $(CSRC)/pp_aln_kind_host.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(HIPFLAGS) -x c++ -c $< -o $@
 

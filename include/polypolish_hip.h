@@ -498,8 +498,9 @@ int pp_bam_kernel_ms(const pp_bam *b, float *ms);
 void pp_bam_free(pp_bam *b);
 
 /* The SECOND front end of the record chain, for a caller who holds SAM TEXT (what `bwa mem` writes, the only format the reference
- * reads): the lines of the text as a pp_raw_batch, decoded on the device -- the text twin of pp_bam_records.  The commands do not use
- * it yet; their text routes are the fused ones (pp_dev_ingest_sam, pp_filter_load_device), which leave no raw records behind.
+ * reads): the lines of the text as a pp_raw_batch, decoded on the device -- the text twin of pp_bam_records.  The commands use
+ * it with pp_ctx_set_text_chain (their --text_chain); without it their text routes are the fused ones (pp_dev_ingest_sam,
+ * pp_filter_load_device), which leave no raw records behind.
  *   records      every line that is neither empty nor begins with '@' is a record, aligned or not, in file order.  Line ends are
  *                "\n" or "\r\n"; a missing final newline is fine.  What a line is, Alignment::new decides (src/alignment.rs:49-98),
  *                exactly as the two ingests follow it.
@@ -538,6 +539,14 @@ void pp_bam_free(pp_bam *b);
  * the text is not among them).  The object belongs to its context and is freed before it. */
 typedef struct pp_sam pp_sam;
 int pp_sam_records(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, pp_sam **out, uint64_t *bad_line);
+/* pp_sam_records over the first n_lines lines of the text only -- the text twin of a BAM decode with a record limit: what a driver
+ * replays when line N = n_lines is refused and the reference, which streams, has taken the lines in front of it already.  The whole
+ * text is still copied (uploaded, for host memory) and its newlines indexed -- that finds where line n_lines starts, and it is the
+ * cost of the call whatever n_lines is --; from there on the object's copy is set to zeros, so no such byte is loaded by the scan, the
+ * placing or the CIGAR pass, and none of them -- a byte >= 0x80 or a malformed line included -- changes a result or a refusal.
+ * Refusals speak as pp_sam_records_lines.  The object is the one pp_sam_records makes of the prefix: n_bytes and
+ * raw.seq_bytes are the prefix's length.  n_lines at or beyond the text's line count: pp_sam_records.  n_lines == 0: an empty object. */
+int pp_sam_records_lines(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, uint64_t n_lines, pp_sam **out, uint64_t *bad_line);
 void pp_sam_raw(const pp_sam *s, pp_raw_batch *out);      /* borrowed view, DEVICE; read_id / contig = the two arrays below */
 uint64_t *pp_sam_read_id(pp_sam *s);                      /* DEVICE, n_rec entries, zero until the caller fills it */
 uint32_t *pp_sam_contig(pp_sam *s);                       /* DEVICE, n_rec entries, zero until the caller fills it */
@@ -545,6 +554,10 @@ void pp_sam_names(const pp_sam *s, const uint8_t **bytes_dev, uint64_t *n_bytes,
 void pp_sam_rnames(const pp_sam *s, const uint8_t **bytes_dev, uint64_t *n_bytes, const uint64_t **off, const uint32_t **len); /* RNAME ranges, id32 = pp_sam_contig */
 const uint32_t *pp_sam_lines(const pp_sam *s);            /* DEVICE, n_rec entries: 0-based line of record r, for messages of later links */
 void pp_sam_pass(const pp_sam *s, const uint8_t **zp, uint64_t *n_aligned); /* HOST, as pp_bam_pass */
+/* 1 and *line (may be NULL) = the 0-based line of the first EMPTY line of the decoded text -- no bytes, or "\r" only --, 0 when it has
+ * none (or s is NULL).  The decode skips such a line as polish::polish does; filter::filter quits on it (src/filter.rs:126-130), so the
+ * filter drivers ask.  Taken by the scan that classifies every line: no pass of its own. */
+int pp_sam_first_empty_line(const pp_sam *s, uint64_t *line);
 int pp_sam_kernel_ms(const pp_sam *s, float *ms);
 void pp_sam_free(pp_sam *s);
 
@@ -822,6 +835,11 @@ int pp_bam_sam_encoded(pp_ctx *ctx, const pp_bam_enc *e, const uint8_t *pass, ui
  * Neither 0x1f nor 0x01 occurs in a valid SAM line: no SAM input changes its route. */
 enum { PP_ALN_SAM = 0, PP_ALN_BAM = 1, PP_ALN_BAM_RAW = 2 };
 int pp_aln_file_kind(const char *path, int *kind);
+enum { PP_ALN_SAM_BGZF = 3 }; /* pp_aln_file_kind_text only */
+/* pp_aln_file_kind for a caller who reads bgzipped SAM text as well (the commands with pp_ctx_set_text_chain): the same answers and
+ * refusals, except that BGZF whose inflated head is not BAM\1 -- fewer than four bytes of content included -- is PP_ALN_SAM_BGZF
+ * instead of a refusal.  gzip that is not BGZF stays refused. */
+int pp_aln_file_kind_text(const char *path, int *kind);
 
 /* Per-contig figures the reference prints to stderr (src/polish.rs:206-227). */
 typedef struct {
@@ -1205,11 +1223,29 @@ int pp_ctx_set_out_bam(pp_ctx *ctx, int on);
  * pp_ctx_set_out_bam on as well, each flag speaks to its own kind of input.  Off when the context is made. */
 int pp_ctx_set_out_sam(pp_ctx *ctx, int on);
 
+/* SAM text through the record chain for the file drivers below (the commands' --text_chain; not in the reference): with `on` != 0,
+ * SAM text inputs of pp_polish_files, pp_filter_files and pp_filter_polish_files take the route BAM takes, file by file on one
+ * context: (pp_bgzf_inflate, for bgzipped text ->) pp_sam_records -> pp_names_ids twice (RNAME on the table seeded with the FASTA
+ * names, QNAME) -> (pp_filter_records) -> (pp_batch_regroup, with pp_ctx_set_regroup) -> pp_batch_gate(pass = pp_sam_pass, ANDed with
+ * the filter's verdicts in the fused command) -> (pp_batch_prepare, PP_BAM_PREPARE=1) -> pp_polish_add.  The raw records exist on this
+ * route, so pp_ctx_set_regroup is accepted on text (coordinate-sorted SAM), bgzipped text is read (pp_aln_file_kind_text; the filter's
+ * outputs are then bgzipped text as well: pp_sam_tagged_records -> pp_bgzf_deflate) and pp_ctx_set_out_bam encodes from the decoded
+ * object (pp_sam_bam_records: no second upload).  The log, the counts and the FASTA are those of the run without it on any text that
+ * run accepts.  Messages name the input's path and the file's own 1-based line, "<path>" (line N), counting all lines; their order is
+ * the BAM route's (the replay of the lines in front of a refused one; under regrouping the decode's refusal
+ * at once).  Refused by name with PP_ERR_QUIT: more than one context, a mix of text and BAM, gzip that is not BGZF, an empty line for
+ * the filter, and a byte >= 0x80 in a bgzipped file or under regrouping -- a plain text file without regrouping continues on the
+ * fused route (PP_TIMING=1 says so).  pp_sam_records' limits stand (PP_ERR_LIMIT), and the filter looks at NM as on the BAM route.
+ * Off when the context is made and off by default in the commands: the fused routes are the measured default, and what they refuse
+ * is pinned by tests. */
+int pp_ctx_set_text_chain(pp_ctx *ctx, int on);
+
 /* polish::polish (src/polish.rs:26-38): FASTA text exactly as the reference prints to stdout.
  * `sams` are SAM text files or -- all of them -- BAM files (pp_aln_file_kind; a mix is PP_ERR_QUIT).  BAM goes through the record
  * chain on the device, file by file: pp_bgzf_inflate -> pp_bam_header -> pp_bgzf_bam_walk -> pp_bam_records -> pp_names ->
  * (pp_batch_regroup, with pp_ctx_set_regroup ->) pp_batch_gate(pass = pp_bam_pass) -> pp_polish_add; pp_batch_prepare in between
- * with PP_BAM_PREPARE=1 in the environment.
+ * with PP_BAM_PREPARE=1 in the environment.  SAM text takes the fused routes, or with pp_ctx_set_text_chain the same chain behind
+ * pp_sam_records (messages then name the path and the 1-based line).
  * Messages about a BAM file name its path and the block or the record (1-based, counting all records); "no alignments in <path>"
  * for a file without aligned records.  Order of errors: INTEGRATION.md section 6. */
 int pp_polish_files(pp_ctx *ctx, const char *assembly, const char *const *sams, int n_sams,

@@ -778,7 +778,7 @@ def bgzf_walk(data, start=0):
     return off, out, end
 
 
-ALN_SAM, ALN_BAM, ALN_BAM_RAW = 0, 1, 2
+ALN_SAM, ALN_BAM, ALN_BAM_RAW, ALN_SAM_BGZF = 0, 1, 2, 3
 
 
 def aln_file_kind(path):
@@ -788,6 +788,17 @@ def aln_file_kind(path):
     L = lib()
     kind = C.c_int(0)
     rc = L.pp_aln_file_kind(os.fsencode(path), C.byref(kind))
+    if rc:
+        raise PolypolishError(rc, L.pp_bam_last_error().decode())
+    return int(kind.value)
+
+
+def aln_file_kind_text(path):
+    """pp_aln_file_kind_text (no device needed): aln_file_kind for a caller who reads bgzipped SAM text as well -- BGZF that does not
+    hold BAM is ALN_SAM_BGZF instead of an error.  What the commands ask with text_chain=True."""
+    L = lib()
+    kind = C.c_int(0)
+    rc = L.pp_aln_file_kind_text(os.fsencode(path), C.byref(kind))
     if rc:
         raise PolypolishError(rc, L.pp_bam_last_error().decode())
     return int(kind.value)
@@ -891,6 +902,8 @@ class SamRecords(_Owned):
     object keeps its own device copy of the text: raw()["seq"] IS that copy (seq_off = the offset of a record's SEQ column in it, any
     case, no rooms), and the name ranges point into it.
       data           mem = MEM_HOST: bytes / a uint8 array; MEM_DEVICE: (device address, n_bytes), free again when the call returns
+      n_lines        None, or pp_sam_records_lines: the first n_lines lines only; nothing from line n_lines on is looked at, and the
+                     object is that of the prefix (.n_bytes = the prefix's length)
       .n_rec, .seq_bytes (= .n_bytes, the text's), .n_cig_total
       .raw()         the device-address dict gate_records / regroup_records / filter_records(..., mem=MEM_DEVICE) take
       .names()       keyword arguments for Names.ids(mem=MEM_DEVICE, out=.read_id_ptr): the QNAMEs' ranges in the device copy
@@ -898,6 +911,7 @@ class SamRecords(_Owned):
       .read_id_ptr, .contig_ptr   device addresses of raw()["read_id"] (n_rec uint64) and raw()["contig"] (n_rec uint32): zero until filled
       .zp            np.uint8, one per ALIGNED record, 0 = the line carries ZP:Z:fail: gate_records' `passed` (AND the filter's)
       .lines()       np.uint32: the 0-based line of every record (a later link's bad_record -> the file's own line)
+      .first_empty_line()   pp_sam_first_empty_line: the 0-based line of the first empty (or "\r"-only) line, None without one
       .host()        numpy copies of the arrays, and "name_off" / "name_len" / "rname_off" / "rname_len" / "line"
       .kernel_ms()   HIP-event time of the decode's kernels (the context had set_profiling on); .stage_ms(): copy | newline_index |
                      scan | place | cigar
@@ -906,12 +920,15 @@ class SamRecords(_Owned):
     A refused text raises PolypolishError with .bad_record = the 0-based line (None where the refusal names none)."""
     _free, _kernel_ms = "pp_sam_free", "pp_sam_kernel_ms"
 
-    def __init__(self, ctx, data, mem=MEM_HOST):
+    def __init__(self, ctx, data, mem=MEM_HOST, n_lines=None):
         L = lib()
         bp, n_bytes, _, _, _keep = _bytes_and_offsets(data, None, mem)
         super().__init__(ctx)
         bad = _no_index()
-        rc = L.pp_sam_records(ctx._h, bp, n_bytes, mem, C.byref(self._p), C.byref(bad))
+        if n_lines is None:
+            rc = L.pp_sam_records(ctx._h, bp, n_bytes, mem, C.byref(self._p), C.byref(bad))
+        else:
+            rc = L.pp_sam_records_lines(ctx._h, bp, n_bytes, mem, int(n_lines), C.byref(self._p), C.byref(bad))
         if rc:
             _raise(rc, L.pp_last_error(ctx._h).decode(), bad_record=_index(bad))
         out = self._view = RawBatch()
@@ -941,6 +958,10 @@ class SamRecords(_Owned):
 
     def lines(self):
         return self._ctx.download(self._lines, self.n_rec, np.uint32)
+
+    def first_empty_line(self):
+        line = C.c_uint64(0)
+        return int(line.value) if lib().pp_sam_first_empty_line(self._p, C.byref(line)) else None
 
     def host(self):
         out = _read_batch(self._view, RAW_FIELDS, self._ctx)
@@ -1435,6 +1456,11 @@ class Context:
         the gate (coordinate-sorted BAM; the commands' --regroup)."""
         self._chk(lib().pp_ctx_set_regroup(self._h, int(bool(on))))
 
+    def set_text_chain(self, on=True):
+        """pp_ctx_set_text_chain: polish_files, filter_files and filter_polish_files take SAM text inputs, plain or bgzipped, through
+        the record chain on the device (the commands' --text_chain); regrouping is then accepted on text."""
+        self._chk(lib().pp_ctx_set_text_chain(self._h, int(bool(on))))
+
     def set_out_bam(self, on=True):
         """pp_ctx_set_out_bam: filter_files / filter_polish_files write the outputs of SAM text inputs as compressed BAM (the
         commands' --out_bam)."""
@@ -1679,6 +1705,19 @@ class Context:
             self.set_regroup(was)
 
     @contextlib.contextmanager
+    def _chaining_text(self, text_chain):
+        """text_chain=True switches pp_ctx_set_text_chain on for one command; False leaves what set_text_chain chose"""
+        if not text_chain:
+            yield
+            return
+        was = bool(lib().pp_ctx_text_chain_(self._h))
+        self.set_text_chain(True)
+        try:
+            yield
+        finally:
+            self.set_text_chain(was)
+
+    @contextlib.contextmanager
     def _writing_bam(self, out_bam):
         """out_bam=True switches pp_ctx_set_out_bam on for one command and off again behind it"""
         if not out_bam:
@@ -1703,15 +1742,16 @@ class Context:
             self.set_out_sam(False)
 
     def polish_files(self, assembly, sams, fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5,
-                     careful=False, debug=None, quiet=True, regroup=False):
+                     careful=False, debug=None, quiet=True, regroup=False, text_chain=False):
         """polish::polish (pp_polish_files): the FASTA bytes.  `sams` are SAM text files, or all of them BAM files (BGZF or
         uncompressed; told by content, aln_file_kind): those go through the record chain on the device, inside the driver.
-        regroup: for this call, as set_regroup (coordinate-sorted BAM)."""
+        regroup: for this call, as set_regroup (coordinate-sorted BAM).  text_chain: for this call, as set_text_chain (SAM text,
+        plain or bgzipped, through the record chain as well)."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         arr = (C.c_char_p * max(len(sams), 1))(*[str(s).encode() for s in sams])
         out = Bytes()
-        with self._regrouping(regroup):
+        with self._regrouping(regroup), self._chaining_text(text_chain):
             self._chk(lib().pp_polish_files(self._h, str(assembly).encode(), arr, len(sams), C.byref(opt), C.byref(out)))
         data = C.string_at(out.data, out.len) if out.len else b""
         lib().pp_bytes_free(C.byref(out))
@@ -1719,29 +1759,31 @@ class Context:
 
     def filter_polish_files(self, assembly, in1, in2, out1=None, out2=None, orientation="auto", low=0.1, high=99.9,
                             fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5, careful=False,
-                            debug=None, quiet=True, regroup=False, out_bam=False, out_sam=False):
+                            debug=None, quiet=True, regroup=False, out_bam=False, out_sam=False, text_chain=False):
         """filter + polish in one process (pp_filter_polish_files): returns (FASTA bytes, filter report).  Two BAM inputs are decoded
         once for both halves; out1 / out2 are then BAM files as well.  regroup: for this call, as set_regroup (the polish half).
         out_bam: for this call, as set_out_bam (SAM text inputs, out1 / out2 as compressed BAM).  out_sam: for this call, as
-        set_out_sam (BAM inputs, out1 / out2 as SAM text)."""
+        set_out_sam (BAM inputs, out1 / out2 as SAM text).  text_chain: for this call, as set_text_chain."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         rep, out = FilterReport(), Bytes()
         enc = lambda x: str(x).encode() if x is not None else None
-        with self._regrouping(regroup), self._writing_bam(out_bam), self._writing_sam(out_sam):
+        with self._regrouping(regroup), self._writing_bam(out_bam), self._writing_sam(out_sam), self._chaining_text(text_chain):
             self._chk(lib().pp_filter_polish_files(self._h, enc(assembly), enc(in1), enc(in2), enc(out1), enc(out2),
                                                    orientation.encode(), low, high, C.byref(opt), C.byref(rep), C.byref(out)))
         data = C.string_at(out.data, out.len) if out.len else b""
         lib().pp_bytes_free(C.byref(out))
         return data, _report_dict(rep)
 
-    def filter_files(self, in1, in2, out1, out2, orientation="auto", low=0.1, high=99.9, quiet=True, out_bam=False, out_sam=False):
+    def filter_files(self, in1, in2, out1, out2, orientation="auto", low=0.1, high=99.9, quiet=True, out_bam=False, out_sam=False,
+                     text_chain=False):
         """filter::filter (pp_filter_files): writes out1 / out2, returns the report.  in1 / in2 are both SAM text, or both BAM:
         BAM in gives compressed BAM out (pp_bam_tagged -> pp_bam_out_deflate).  out_bam: for this call, as set_out_bam (SAM text
         in, compressed BAM out through pp_sam_bam).  out_sam: for this call, as set_out_sam (BAM in, SAM text out through
-        pp_bam_sam)."""
+        pp_bam_sam).  text_chain: for this call, as set_text_chain (SAM text, plain or bgzipped, through the record chain; bgzipped
+        in gives bgzipped out)."""
         rep = FilterReport()
-        with self._writing_bam(out_bam), self._writing_sam(out_sam):
+        with self._writing_bam(out_bam), self._writing_sam(out_sam), self._chaining_text(text_chain):
             self._chk(lib().pp_filter_files(self._h, str(in1).encode(), str(in2).encode(), str(out1).encode(),
                                             str(out2).encode(), orientation.encode(), low, high, int(quiet),
                                             C.byref(rep)))
@@ -1759,11 +1801,12 @@ def _ctx():
 
 
 def polish(assembly, sam, debug=None, fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5,
-           careful=False, regroup=False) -> bytes:
+           careful=False, regroup=False, text_chain=False) -> bytes:
     """polish::polish (src/polish.rs:26-38): returns the FASTA bytes the reference prints to stdout.  regroup: coordinate-sorted
-    BAM files (every read's records are brought together in front of the gate: the command's --regroup)."""
+    BAM files (every read's records are brought together in front of the gate: the command's --regroup).  text_chain: SAM text,
+    plain or bgzipped, through the record chain as well (the command's --text_chain; regroup then takes text too)."""
     return _ctx().polish_files(assembly, list(sam), fraction_invalid, fraction_valid, max_errors, min_depth, careful,
-                               debug, regroup=regroup)
+                               debug, regroup=regroup, text_chain=text_chain)
 
 
 def filter(in1, in2, out1, out2, orientation="auto", low=0.1, high=99.9):  # noqa: A001 (reference name)

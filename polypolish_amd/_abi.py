@@ -153,6 +153,7 @@ SIGNATURES = {
     "pp_bam_kernel_ms": (_i, [_vp, _pf32]),
     "pp_bam_free": (None, [_vp]),
     "pp_sam_records": (_i, [_vp, _vp, _u64, _i, _pvp, _pu64]),
+    "pp_sam_records_lines": (_i, [_vp, _vp, _u64, _i, _u64, _pvp, _pu64]),
     "pp_sam_raw": (None, [_vp, _P(RawBatch)]),
     "pp_sam_read_id": (_vp, [_vp]),
     "pp_sam_contig": (_vp, [_vp]),
@@ -160,6 +161,7 @@ SIGNATURES = {
     "pp_sam_rnames": (None, [_vp, _pvp, _pu64, _pvp, _pvp]),
     "pp_sam_lines": (_vp, [_vp]),
     "pp_sam_pass": (None, [_vp, _pvp, _pu64]),
+    "pp_sam_first_empty_line": (_i, [_vp, _pu64]),
     "pp_sam_kernel_ms": (_i, [_vp, _pf32]),
     "pp_sam_free": (None, [_vp]),
         "pp_bam_tagged": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _i, _vp, _u64, _pvp, _pu64]),
@@ -193,6 +195,7 @@ SIGNATURES = {
     "pp_bam_sam": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _i, _vp, _u64, _pvp, _pu64]),
     "pp_bam_sam_encoded": (_i, [_vp, _vp, _vp, _u64, _pvp, _pu64]),
     "pp_aln_file_kind": (_i, [_str, _P(_i)]),
+    "pp_aln_file_kind_text": (_i, [_str, _P(_i)]),
     "pp_polish_set_emit": (_i, [_vp, _vp, _vp]),
     "pp_polish_begin": (_i, [_vp, _u32, _vp, _vp, _i, _P(Params)]),
     "pp_polish_add": (_i, [_vp, _P(AlnBatch), _i]),
@@ -264,6 +267,7 @@ SIGNATURES = {
     "pp_ctx_set_regroup": (_i, [_vp, _i]),
     "pp_ctx_set_out_bam": (_i, [_vp, _i]),
     "pp_ctx_set_out_sam": (_i, [_vp, _i]),
+    "pp_ctx_set_text_chain": (_i, [_vp, _i]),
     "pp_polish_files": (_i, [_vp, _str, _P(_str), _i, _P(PolishOptions), _P(Bytes)]),
     "pp_polish_files_multi": (_i, [_pvp, _i, _str, _P(_str), _i, _P(PolishOptions), _P(Bytes)]),
     "pp_dev_ingest_create": (_i, [_vp, _vp, _u32, _i, _pvp]),
@@ -284,6 +288,7 @@ SIGNATURES = {
 HOOKS = {
     "pp_ctx_trust_mirrors_": (_i, [_vp, _i]),
     "pp_ctx_regroup_": (_i, [_vp]),
+    "pp_ctx_text_chain_": (_i, [_vp]),
     "pp_gated_stage_ms_": (_i, [_vp, _pf32]),       # float[3]
     "pp_regrouped_stage_ms_": (_i, [_vp, _pf32]),   # float[3]
     "pp_regroup_geometry_": (None, [_pu32]),

@@ -1,17 +1,18 @@
 // pp_bam_files.cpp -- pp_aln_file_kind (SAM text, BAM or uncompressed BAM, told by the file's head) and the command drivers' front
-// end for one BAM file (pp_bam_files.h).  Host code over the C ABI only: every alignment byte behind the compressed file is produced
+// ends for one BAM file and for one file of SAM text (pp_bam_files.h).  Host code over the C ABI only: every alignment byte behind the compressed file is produced
 // and consumed on the device by the links this file joins.
 #include "pp_bam_files.h"
 
-#include <zlib.h>
+#include "pp_aln_kind_host.h"
 
 #include <cstdarg>
+
+static_assert(pp_aln_host::SAM == PP_ALN_SAM && pp_aln_host::BAM == PP_ALN_BAM && pp_aln_host::BAM_RAW == PP_ALN_BAM_RAW &&
+                  pp_aln_host::SAM_BGZF == PP_ALN_SAM_BGZF, "pp_aln_kind_host.h numbers the kinds as the header does");
 
 extern "C" char *pp_bam_msg_buf_(size_t *cap);  // pp_bam.hip: the per-thread message behind pp_bam_last_error()
 
 namespace {
-
-uint32_t le16(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
 
 // up to cap bytes of the file from `at`; -1: the file cannot be read
 ssize_t read_at(int fd, uint64_t at, uint8_t *buf, size_t cap) {
@@ -34,12 +35,13 @@ const char *words(const char *msg) {
 
 }  // namespace
 
-extern "C" int pp_aln_file_kind(const char *path, int *kind) {
+// pp_aln_file_kind; with_text (pp_aln_file_kind_text): BGZF whose content is not BAM is bgzipped SAM text, not a refusal
+static int aln_file_kind(const char *path, int *kind, bool with_text) {
     size_t cap = 0;
     char *msg = pp_bam_msg_buf_(&cap);
     msg[0] = 0;
     if (!path || !kind) {
-        snprintf(msg, cap, "pp_aln_file_kind: null argument");
+        snprintf(msg, cap, "%s: null argument", with_text ? "pp_aln_file_kind_text" : "pp_aln_file_kind");
         return PP_ERR_ARG;
     }
     *kind = PP_ALN_SAM;
@@ -54,75 +56,30 @@ extern "C" int pp_aln_file_kind(const char *path, int *kind) {
     struct stat st;
     if (stat(path, &st) != 0) return quit(UNABLE);
     if (!S_ISREG(st.st_mode)) return PP_OK;  // a pipe is never opened just to look at it: text
-    const int fd = open(path, O_RDONLY);
-    if (fd < 0) return quit(UNABLE);
-    std::vector<uint8_t> buf(65536);  // a BGZF block is at most 64 KiB
-    const uint8_t *h = buf.data();
-    ssize_t n = read_at(fd, 0, buf.data(), buf.size());
-    auto leave = [&](int rc) {
-        close(fd);
-        return rc;
-    };
-    if (n < 0) return leave(quit(UNABLE));
-    if (n >= 4 && memcmp(h, "BAM\1", 4) == 0) {
-        *kind = PP_ALN_BAM_RAW;
-        return leave(PP_OK);
-    }
-    if (n < 2 || h[0] != 0x1f || h[1] != 0x8b) return leave(PP_OK);
-    // a gzip member: BGZF, if it has the BC subfield; the first four inflated bytes say whether it is BAM.  (The header is read here
-    // and not by pp_bgzf_host::block: that one wants the whole block inside the bytes, and a file cut inside its first block is still
-    // told by its head -- the inflate then names the truncation.)
-    uint8_t got[4] = {0, 0, 0, 0};
-    unsigned n_got = 0;
-    bool defect = false;  // something pp_bgzf_inflate will name: the block is not looked into here
-    uint64_t at = 0;
-    for (int b = 0; n_got < 4 && b < 64; b++) {
-        if (b) {
-            n = read_at(fd, at, buf.data(), buf.size());
-            if (n < 0) return leave(quit(UNABLE));
-            if (n == 0) break;
+    // the walk is pp_aln_kind_host.h's, over a window of the file read with pread
+    struct FileSrc {
+        int fd;
+        std::vector<uint8_t> buf;
+        const uint8_t *at(uint64_t off, size_t *n) {
+            const ssize_t r = read_at(fd, off, buf.data(), buf.size());
+            *n = r < 0 ? 0 : (size_t)r;
+            return r < 0 ? nullptr : buf.data();
         }
-        const bool first = b == 0;
-        if (n < 10) { if (first) return leave(quit(CUT)); defect = true; break; }
-        if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || !(h[3] & 4)) { if (first) return leave(quit(NOT_BGZF)); defect = true; break; }
-        if (n < 12) { if (first) return leave(quit(CUT)); defect = true; break; }
-        const uint32_t xlen = le16(h + 10);
-        if ((uint64_t)n - 12 < xlen) { if (first) return leave(quit(CUT)); defect = true; break; }
-        uint32_t p = 0, bsize = 0;
-        bool found = false, malformed = false;
-        while (xlen - p >= 4) {  // SI1 SI2 SLEN data, as pp_bgzf_walk goes through them
-            const uint32_t slen = le16(h + 12 + p + 2);
-            if (slen > xlen - p - 4) { malformed = true; break; }
-            if (!found && h[12 + p] == 'B' && h[12 + p + 1] == 'C' && slen == 2) {
-                bsize = le16(h + 12 + p + 4);
-                found = true;
-            }
-            p += 4 + slen;
-        }
-        if (malformed || p != xlen || !found) { if (first) return leave(quit(NOT_BGZF)); defect = true; break; }
-        const uint32_t total = bsize + 1, head = 12 + xlen;
-        if (total < head + 8) { defect = true; break; }
-        const uint32_t avail = (uint32_t)std::min<uint64_t>((uint64_t)n, total - 8) - head;  // payload bytes at hand (head <= n)
-        z_stream zs;
-        memset(&zs, 0, sizeof zs);
-        if (inflateInit2(&zs, -15) != Z_OK) return leave(quit(UNABLE));
-        zs.next_in = (Bytef *)(h + head);
-        zs.avail_in = avail;
-        zs.next_out = got + n_got;
-        zs.avail_out = 4 - n_got;
-        const int r = inflate(&zs, Z_SYNC_FLUSH);
-        n_got = 4 - zs.avail_out;
-        inflateEnd(&zs);
-        if (r != Z_OK && r != Z_STREAM_END && r != Z_BUF_ERROR) { defect = true; break; }
-        if ((uint64_t)n < total) { defect = true; break; }  // the file ends inside this block
-        at += total;
+    } src{open(path, O_RDONLY), std::vector<uint8_t>(pp_aln_host::WINDOW)};
+    if (src.fd < 0) return quit(UNABLE);
+    const int answer = pp_aln_host::kind_of(src, kind, with_text);
+    close(src.fd);
+    switch (answer) {
+    case pp_aln_host::OK: return PP_OK;
+    case pp_aln_host::NOT_BGZF: return quit(NOT_BGZF);
+    case pp_aln_host::NOT_BAM: return quit(NOT_BAM);
+    case pp_aln_host::CUT: return quit(CUT);
+    default: return quit(UNABLE);
     }
-    close(fd);
-    if (memcmp(got, "BAM\1", n_got) != 0) return quit(NOT_BAM);
-    if (n_got < 4 && !defect) return quit(NOT_BAM);  // fewer than four bytes of content
-    *kind = PP_ALN_BAM;
-    return PP_OK;
 }
+
+extern "C" int pp_aln_file_kind(const char *path, int *kind) { return aln_file_kind(path, kind, false); }
+extern "C" int pp_aln_file_kind_text(const char *path, int *kind) { return aln_file_kind(path, kind, true); }
 
 namespace ppb {
 
@@ -160,12 +117,7 @@ int BamFile::open(pp_ctx *c, const char *p, int k, pp_names *rnames, const pph::
     const uint8_t *hb = nullptr;
     uint64_t hn = 0;
     if (kind == PP_ALN_BAM) {
-        uint64_t bad = 0;
-        if (int rc = pp_bgzf_inflate(ctx, (const uint8_t *)file.text, file.size, nullptr, 0, PP_MEM_HOST, &z, &bad)) {
-            if (rc != PP_ERR_ARG) return rc;
-            const std::string why = words(pp_last_error(ctx));
-            return fail(ctx, rc, "invalid BGZF data in \"%s\" (block %llu): %s", p, (unsigned long long)bad + 1, why.c_str());
-        }
+        if (int rc = inflate_file(ctx, p, file, &z)) return rc;
         file.close_file();  // the compressed bytes are not needed again
         file.fallback = {};
         pp_bgzf_bytes(z, &bytes, &n_bytes);
@@ -237,6 +189,87 @@ int BamFile::open(pp_ctx *c, const char *p, int k, pp_names *rnames, const pph::
     return PP_OK;
 }
 
+int inflate_file(pp_ctx *ctx, const char *path, const pph::FileText &file, pp_bgzf **z) {
+    uint64_t bad = 0;
+    const int rc = pp_bgzf_inflate(ctx, (const uint8_t *)file.text, file.size, nullptr, 0, PP_MEM_HOST, z, &bad);
+    if (rc != PP_ERR_ARG) return rc;
+    const std::string why = words(pp_last_error(ctx));
+    return fail(ctx, rc, "invalid BGZF data in \"%s\" (block %llu): %s", path, (unsigned long long)bad + 1, why.c_str());
+}
+
+void TextFile::drop_records() {
+    pp_sam_free(rec);
+    rec = nullptr;
+    n_decoded = 0;
+    pp_bgzf_free(z);
+    z = nullptr;
+    file.close_file();
+    file.fallback = {};
+}
+
+int TextFile::open(pp_ctx *c, const char *p, int k, pp_names *names, const pph::Lap *l) {
+    ctx = c;
+    path = p;
+    kind = k;
+    rnames = names;
+    lap = l;
+    struct stat st;
+    if (stat(p, &st) == 0 && !S_ISREG(st.st_mode))
+        return fail(ctx, PP_ERR_QUIT, "--text_chain reads regular files: \"%s\" is none (a pipe or a process substitution can be read once, and the replay of the lines in front of a refused one reads the file again)", p);
+    return PP_OK;
+}
+
+// Read (and inflate) the file, decode its first `limit` lines, intern the names.  The library's sentence about a refused line names
+// the path "text": the file's own path in its place.
+int TextFile::decode(uint64_t limit, pp_names *qnames, uint64_t *bad) {
+    drop_records();
+    line_of.clear();
+    auto lapped = [&](const char *what) {
+        if (lap && lap->on) (*lap)((std::string(what) + " " + path).c_str());
+    };
+    const char *p = path.c_str();
+    if (!file.open_file(p)) return fail(ctx, PP_ERR_QUIT, "unable to load alignments from \"%s\"", p);
+    const uint8_t *bytes = (const uint8_t *)file.text;
+    uint64_t n_bytes = file.size;
+    int mem = PP_MEM_HOST;
+    if (kind == PP_ALN_SAM_BGZF) {
+        if (int rc = inflate_file(ctx, p, file, &z)) return rc;
+        file.close_file();
+        file.fallback = {};
+        pp_bgzf_bytes(z, &bytes, &n_bytes);
+        mem = PP_MEM_DEVICE;
+        lapped("read + inflated");
+    }
+    uint64_t b = ~0ull;
+    const int rc = limit == ~0ull ? pp_sam_records(ctx, bytes, n_bytes, mem, &rec, &b) : pp_sam_records_lines(ctx, bytes, n_bytes, mem, limit, &rec, &b);
+    if (bad) *bad = b;
+    pp_bgzf_free(z);  // the object has its own copy
+    z = nullptr;
+    file.close_file();
+    file.fallback = {};
+    if (rc) {
+        std::string said = pp_last_error(ctx);
+        const size_t at = said.find("\"text\"");
+        if (at != std::string::npos) said.replace(at, 6, "\"" + path + "\"");
+        else if (rc == PP_ERR_NOT_ASCII) said = "\"" + path + "\" holds bytes outside ASCII, which the text chain does not read";
+        return pp_ctx_set_error_(ctx, rc, said.c_str());
+    }
+    pp_raw_batch view;
+    pp_sam_raw(rec, &view);
+    n_decoded = view.n_rec;
+    if (!n_decoded) return PP_OK;
+    line_of.resize((size_t)n_decoded);
+    if (int rd = pp_ctx_download(ctx, line_of.data(), pp_sam_lines(rec), n_decoded * 4)) return rd;
+    const uint8_t *nb = nullptr;
+    uint64_t nn = 0;
+    const uint64_t *noff = nullptr;
+    const uint32_t *nlen = nullptr;
+    pp_sam_rnames(rec, &nb, &nn, &noff, &nlen);
+    if (int rn = pp_names_ids(rnames, nb, nn, noff, nlen, n_decoded, PP_MEM_DEVICE, nullptr, pp_sam_contig(rec), nullptr)) return rn;
+    pp_sam_names(rec, &nb, &nn, &noff, &nlen);
+    return pp_names_ids(qnames, nb, nn, noff, nlen, n_decoded, PP_MEM_DEVICE, pp_sam_read_id(rec), nullptr, nullptr);
+}
+
 int BamFile::decode(uint64_t limit, pp_names *qnames, uint64_t *bad) {
     pp_bam_free(rec);
     rec = nullptr;
@@ -262,18 +295,18 @@ int BamFile::decode(uint64_t limit, pp_names *qnames, uint64_t *bad) {
     return pp_names_ids(qnames, nb, nn, noff, nlen, limit, PP_MEM_DEVICE, pp_bam_read_id(rec), nullptr, nullptr);
 }
 
-int download_groups(const BamFile &B, uint64_t n, std::vector<uint16_t> &flag, std::vector<uint64_t> &read_id) {
+int download_groups(const Front &B, uint64_t n, std::vector<uint16_t> &flag, std::vector<uint64_t> &read_id) {
     flag.assign(n ? n : 1, 0);
     read_id.assign(n ? n : 1, 0);
     if (!n) return PP_OK;
     pp_raw_batch raw;
-    pp_bam_raw(B.rec, &raw);
+    B.raw(&raw);
     if (int rc = pp_ctx_download(B.ctx, flag.data(), raw.flag, n * 2)) return rc;
     return pp_ctx_download(B.ctx, read_id.data(), raw.read_id, n * 8);
 }
 
 int file_kind(pp_ctx *ctx, const char *path, int *kind) {
-    const int rc = pp_aln_file_kind(path, kind);
+    const int rc = pp_ctx_text_chain_(ctx) ? pp_aln_file_kind_text(path, kind) : pp_aln_file_kind(path, kind);
     if (rc == PP_ERR_QUIT && strncmp(pp_bam_last_error(), "unable to load", 14) == 0) {
         *kind = PP_ALN_SAM;
         return PP_OK;

@@ -35,6 +35,7 @@ static const char *HELP_FILTER =
     "                                   (two BAM inputs are read as they are and give two BAM outputs)\n"
     "      --out_bam                    SAM text inputs: write the outputs as compressed BAM (not in the reference)\n"
     "      --out_sam                    BAM inputs: write the outputs as SAM text (not in the reference)\n"
+    "      --text_chain                 SAM text inputs, plain or bgzipped, through the record chain on the device (not in the reference)\n"
     "      --orientation <ORIENTATION>  Expected pair orientation [default: auto]\n"
     "      --low <LOW>                  Low percentile threshold [default: 0.1]\n"
     "      --high <HIGH>                High percentile threshold [default: 99.9]\n"
@@ -53,6 +54,7 @@ static const char *HELP_POLISH =
     "  -d, --min_depth <MIN_DEPTH>                A base must occur at least this many times in the pileup to be considered valid [default: 5]\n"
     "      --careful                              Ignore any reads with multiple alignments\n"
     "      --regroup                              BAM files whose reads do not stand together (coordinate-sorted): bring every read's alignments together first\n"
+    "      --text_chain                           SAM text, plain or bgzipped, through the record chain on the device; --regroup then takes text as well (not in the reference)\n"
     "  -h, --help                                 Print help\n  -V, --version                              Print version\n";
 
 static const char *HELP_FUSED =
@@ -63,7 +65,8 @@ static const char *HELP_FUSED =
     "--in1/--in2 are both SAM text or both BAM; with BAM the optional outputs are BAM as well.\n"
     "--regroup: coordinate-sorted BAM inputs (the polish brings every read's alignments together; the outputs keep file order).\n"
     "--out_bam: SAM text inputs with --out1/--out2: write the outputs as compressed BAM.\n"
-    "--out_sam: BAM inputs with --out1/--out2: write the outputs as SAM text.\n";
+    "--out_sam: BAM inputs with --out1/--out2: write the outputs as SAM text.\n"
+    "--text_chain: SAM text inputs, plain or bgzipped, through the record chain on the device; --regroup then takes text as well (not in the reference).\n";
 
 static int usage_error(const char *msg) {
     fprintf(stderr, "error: %s\n\nFor more information, try '--help'.\n", msg);
@@ -240,13 +243,15 @@ int main(int argc, char **argv) {
     if (cmd == "polish") {
         pp_polish_options opt{0.2, 0.5, 10, 5, 0, nullptr, 0};
         bool regroup = false;  // (not in the reference) BAM files whose reads do not stand together: pp_ctx_set_regroup
+        bool text_chain = false;  // (not in the reference) SAM text through the record chain: pp_ctx_set_text_chain
         const std::vector<OptSpec> specs = {{"--debug", 0, true, "<DEBUG>"},
                                             {"--fraction_invalid", 'i', true, "<FRACTION_INVALID>"},
                                             {"--fraction_valid", 'v', true, "<FRACTION_VALID>"},
                                             {"--max_errors", 'm', true, "<MAX_ERRORS>"},
                                             {"--min_depth", 'd', true, "<MIN_DEPTH>"},
                                             {"--careful", 0, false, ""},
-                                            {"--regroup", 0, false, ""}};
+                                            {"--regroup", 0, false, ""},
+                                            {"--text_chain", 0, false, ""}};
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help) { fputs(HELP_POLISH, stdout); return 0; }
         if (P.version) { printf("polypolish-polish v0.6.1\n"); return 0; }
@@ -255,6 +260,7 @@ int main(int argc, char **argv) {
             opt.debug_path = P.value[0];
             opt.careful = P.value[5] != nullptr;
             regroup = P.value[6] != nullptr;
+            text_chain = P.value[7] != nullptr;
             (void)(take_f64(P, specs, 1, opt.fraction_invalid, perr) && take_f64(P, specs, 2, opt.fraction_valid, perr) &&
                    take_u32(P, specs, 3, opt.max_errors, perr) && take_u32(P, specs, 4, opt.min_depth, perr));
         }
@@ -272,8 +278,13 @@ int main(int argc, char **argv) {
         const bool several = (getenv("PP_GPUS") && atoi(getenv("PP_GPUS")) > 1) || (getenv("PP_SHARE_GPU") && atoi(getenv("PP_SHARE_GPU")) > 1);
         for (size_t i = 0; several && i < sams.size(); i++) {
             int kind = PP_ALN_SAM;
-            if (pp_aln_file_kind(sams[i], &kind) == PP_OK && kind != PP_ALN_SAM) {
+            if ((text_chain ? pp_aln_file_kind_text(sams[i], &kind) : pp_aln_file_kind(sams[i], &kind)) != PP_OK) continue;
+            if (kind == PP_ALN_BAM || kind == PP_ALN_BAM_RAW) {
                 fprintf(stderr, "\nError: BAM input (\"%s\") runs on one GPU: polish it without PP_GPUS / PP_SHARE_GPU, or convert it to SAM text\n", sams[i]);
+                return 1;
+            }
+            if (text_chain) {
+                fprintf(stderr, "\nError: SAM text on the record chain (--text_chain, \"%s\") runs on one GPU: polish it without PP_GPUS / PP_SHARE_GPU, or without --text_chain\n", sams[i]);
                 return 1;
             }
         }
@@ -281,7 +292,7 @@ int main(int argc, char **argv) {
         if (devs.size() > 1) {
             std::vector<pp_ctx *> cs(devs.size(), nullptr);
             for (size_t d = 0; d < devs.size(); d++)
-                if (pp_ctx_create_async(devs[d], &cs[d]) || pp_ctx_set_regroup(cs[d], regroup)) return no_device(devs[d]);
+                if (pp_ctx_create_async(devs[d], &cs[d]) || pp_ctx_set_regroup(cs[d], regroup) || pp_ctx_set_text_chain(cs[d], text_chain)) return no_device(devs[d]);
             pp_bytes fasta{nullptr, 0};
             int rc = pp_polish_files_multi(cs.data(), (int)cs.size(), assembly, sams.data(), (int)sams.size(), &opt, &fasta);
             for (size_t d = 0; d < devs.size(); d++)
@@ -299,6 +310,7 @@ int main(int argc, char **argv) {
         int rc = pp_ctx_create_async(device, &ctx);
         if (rc) return no_device(device);
         pp_ctx_set_regroup(ctx, regroup);
+        pp_ctx_set_text_chain(ctx, text_chain);
         pp_bytes fasta{nullptr, 0};
         rc = pp_polish_files(ctx, assembly, sams.data(), (int)sams.size(), &opt, &fasta);
         if (pp_ctx_wait(ctx) != PP_OK) return no_device(device);
@@ -327,7 +339,8 @@ int main(int argc, char **argv) {
                                             {"--careful", 0, false, ""},
                                             {"--regroup", 0, false, ""},
                                             {"--out_bam", 0, false, ""},
-                                            {"--out_sam", 0, false, ""}};
+                                            {"--out_sam", 0, false, ""},
+                                            {"--text_chain", 0, false, ""}};
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help || P.version) { fputs(HELP_FUSED, stdout); return 0; }
         std::string perr = P.error;
@@ -352,6 +365,7 @@ int main(int argc, char **argv) {
         pp_ctx_set_regroup(ctx, regroup);
         pp_ctx_set_out_bam(ctx, P.value[14] != nullptr);
         pp_ctx_set_out_sam(ctx, P.value[15] != nullptr);
+        pp_ctx_set_text_chain(ctx, P.value[16] != nullptr);
         pp_bytes fasta{nullptr, 0};
         rc = pp_filter_polish_files(ctx, assembly, in1, in2, out1, out2, orientation, low, high, &opt, nullptr, &fasta);
         if (pp_ctx_wait(ctx) != PP_OK) return no_device(device);
@@ -371,7 +385,7 @@ int main(int argc, char **argv) {
                                             {"--out1", 0, true, "<OUT1>"}, {"--out2", 0, true, "<OUT2>"},
                                             {"--orientation", 0, true, "<ORIENTATION>"}, {"--low", 0, true, "<LOW>"},
                                             {"--high", 0, true, "<HIGH>"}, {"--out_bam", 0, false, ""},
-                                            {"--out_sam", 0, false, ""}};
+                                            {"--out_sam", 0, false, ""}, {"--text_chain", 0, false, ""}};
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help) { fputs(HELP_FILTER, stdout); return 0; }
         if (P.version) { printf("polypolish-filter v0.6.1\n"); return 0; }
@@ -390,6 +404,7 @@ int main(int argc, char **argv) {
         if (rc) return no_device(device);
         pp_ctx_set_out_bam(ctx, P.value[7] != nullptr);
         pp_ctx_set_out_sam(ctx, P.value[8] != nullptr);
+        pp_ctx_set_text_chain(ctx, P.value[9] != nullptr);
         rc = pp_filter_files(ctx, in1, in2, out1, out2, orientation, low, high, 0, nullptr);
         if (pp_ctx_wait(ctx) != PP_OK) return no_device(device);
         if (rc) {

@@ -131,29 +131,36 @@ static int check_options_and_inputs(PolishJob &J) {
     }
     // SAM text or BAM, told by the files' heads (pp_aln_file_kind); all files of a command are of one kind
     std::vector<int> &kinds = J.bam.kinds;
-    kinds.assign((size_t)J.n_sams, J.bam.borrowed ? PP_ALN_BAM : PP_ALN_SAM);
+    // (with pp_ctx_set_text_chain, pp_aln_file_kind_text: bgzipped SAM text is text.  The second look at a text the chain handed
+    // back is the host ingest's, as without it.)
+    const bool text_chain = pp_ctx_text_chain_(J.ctx) != 0 && J.resume_log_at < 0;
+    kinds.assign((size_t)J.n_sams, J.bam.borrowed ? J.bam.fronts[0]->kind : PP_ALN_SAM);
     int first_sam = -1, first_bam = -1;
     for (int i = 0; i < J.n_sams; i++) {
         if (!J.bam.borrowed)
             if (int rc = ppb::file_kind(J.ctx, J.sams[i], &kinds[(size_t)i])) return rc;
-        int &first = kinds[(size_t)i] == PP_ALN_SAM ? first_sam : first_bam;
+        int &first = ppb::is_text(kinds[(size_t)i]) ? first_sam : first_bam;
         if (first < 0) first = i;
     }
     if (first_sam >= 0 && first_bam >= 0)
         return ppb::fail(J.ctx, PP_ERR_QUIT, "the alignment files of one command must all be SAM text or all be BAM: \"%s\" is SAM text, \"%s\" is BAM",
                          J.sams[first_sam], J.sams[first_bam]);
-    if (first_sam >= 0 && pp_ctx_regroup_(J.ctx))
+    if (first_sam >= 0 && pp_ctx_regroup_(J.ctx) && !text_chain)
         return ppb::fail(J.ctx, PP_ERR_QUIT, "--regroup takes BAM input: \"%s\" is SAM text (its records are regrouped on the device, which holds none of a text file)",
                          J.sams[first_sam]);
     // the job's route, decided here and nowhere else
     const bool tokenize = J.resume_log_at < 0 && !off_by_env("PP_DEVICE_INGEST");
     J.route = first_bam >= 0 ? Route::BAM
+              : text_chain   ? Route::TEXT_CHAIN
               : J.n_ctx > 1  ? (tokenize ? Route::SHARDED : Route::MULTI_HOST)
               : tokenize     ? Route::TOKENIZER
                              : (off_by_env("PP_STREAM_ADDS") ? Route::HOST_ONE : Route::HOST_STREAMED);
     if (J.route == Route::BAM && J.n_ctx > 1)
         return ppb::fail(J.ctx, PP_ERR_QUIT, "BAM input (\"%s\") runs on one GPU: polish it without PP_GPUS / several contexts, or convert it to SAM text",
                          J.sams[first_bam]);
+    if (J.route == Route::TEXT_CHAIN && J.n_ctx > 1)
+        return ppb::fail(J.ctx, PP_ERR_QUIT, "SAM text on the record chain (--text_chain, \"%s\") runs on one GPU: polish it without PP_GPUS / several contexts, or without --text_chain",
+                         J.sams[first_sam]);
     // The device tokenizer uploads the SAM text as it is: map the files and pre-fault the mappings NOW, on background
     // threads, while the HIP runtime is still initialising (a copy out of an untouched mapping runs at a quarter of
     // the link's rate).
@@ -218,7 +225,8 @@ static int create_ingests(PolishJob &J) {
     if (several_contexts(J.route)) pp_ctx_enable_peers_(J.ctxs, J.n_ctx);
     int rc = PP_OK;
     switch (J.route) {
-    case Route::BAM: return bam_create(J);
+    case Route::BAM:
+    case Route::TEXT_CHAIN: return bam_create(J);
     case Route::SHARDED: rc = sharded_create(J); break;
     case Route::TOKENIZER: rc = tokenizer_create(J); break;
     case Route::HOST_ONE: rc = pp_ingest_create(J.a, J.opt->max_errors, J.opt->careful, &J.text.g); break;
@@ -230,14 +238,15 @@ static int create_ingests(PolishJob &J) {
 }
 static int ingest_file(PolishJob &J, int i, pp_sam_counts &c) {
     switch (J.route) {
-    case Route::BAM: return ingest_file_bam(J, i, c);
+    case Route::BAM:
+    case Route::TEXT_CHAIN: return ingest_file_bam(J, i, c);
     case Route::SHARDED: return ingest_file_sharded(J, i, c);
     case Route::TOKENIZER: return ingest_file_device(J, i, c);
     default: return ingest_file_host(J, i, c);
     }
 }
-static int hand_over_batches(PolishJob &J) { return J.route == Route::BAM ? (int)PP_OK : text_hand_over(J); }  // (BAM: added file by file)
-static int said_about_its_source(PolishJob &J, int rc) { return J.route == Route::BAM ? bam_polish_error(J, rc) : rc; }
+static int hand_over_batches(PolishJob &J) { return chained(J.route) ? (int)PP_OK : text_hand_over(J); }  // (the chain: added file by file)
+static int said_about_its_source(PolishJob &J, int rc) { return chained(J.route) ? bam_polish_error(J, rc) : rc; }
 
 // load_alignments, polish.rs:109-134.  A device tokenizer that meets a defect in the text (or bytes outside ASCII, which the
 // host parsers must judge) only says so: which defect the reference reports FIRST also depends on what its CIGAR walk makes of
@@ -411,7 +420,7 @@ extern "C" int pp_polish_files_filtered_(pp_ctx *ctx, const char *assembly, cons
     return polish_files_impl(&ctx, 1, assembly, sams, n_sams, opt, fasta, pass, n_pass);
 }
 
-int ppb::polish_bam_fronts(pp_ctx *ctx, const char *assembly, pp_assembly *a, ppb::BamFile *const *fronts, pp_names *rnames, pp_names *qnames,
+int ppb::polish_bam_fronts(pp_ctx *ctx, const char *assembly, pp_assembly *a, ppb::Front *const *fronts, pp_names *rnames, pp_names *qnames,
                            const char *const *paths, int n, const pp_polish_options *opt, pp_bytes *fasta, const uint8_t *const *pass,
                            const uint64_t *n_pass) {
     const BamGiven given{a, fronts, rnames, qnames};

@@ -25,7 +25,9 @@ namespace ppd __attribute__((visibility("hidden"))) {
 // its units (MULTI_HOST).  Host ingest on one context: one ingest object per SAM file, and the batch of file i goes to the device
 // (pp_polish_begin + pp_polish_add on a helper thread) while file i+1 is parsed (HOST_STREAMED) -- the reference streams its files
 // one after the other as well (alignment.rs:238-265) --, or all files in one object (HOST_ONE, PP_STREAM_ADDS=0).
-enum class Route { TOKENIZER, HOST_ONE, HOST_STREAMED, SHARDED, MULTI_HOST, BAM };
+// TEXT_CHAIN (pp_ctx_set_text_chain): SAM text, plain or bgzipped, on the BAM route's code behind a text front (ppb::TextFile).
+enum class Route { TOKENIZER, HOST_ONE, HOST_STREAMED, SHARDED, MULTI_HOST, BAM, TEXT_CHAIN };
+inline bool chained(Route r) { return r == Route::BAM || r == Route::TEXT_CHAIN; }
 inline bool tokenizes(Route r) { return r == Route::TOKENIZER || r == Route::SHARDED; }
 inline bool several_contexts(Route r) { return r == Route::SHARDED || r == Route::MULTI_HOST; }
 
@@ -83,14 +85,14 @@ struct MultiRoute {
     ~MultiRoute() { reset(); }
 };
 
-// BAM files that pp_filter_polish_files has opened and decoded already, with the assembly and the tables behind them
-struct BamGiven { pp_assembly *a; ppb::BamFile *const *fronts; pp_names *rnames, *qnames; };
-// BAM input (all files of a command are of one kind): the record chain on the device, file by file (ingest_file_bam).  The gated
-// batches (and the prepared ones, PP_BAM_PREPARE=1) live until pp_polish_finish has returned.
+// Files that pp_filter_polish_files has opened and decoded already, with the assembly and the tables behind them
+struct BamGiven { pp_assembly *a; ppb::Front *const *fronts; pp_names *rnames, *qnames; };
+// BAM input, or SAM text on the chain (all files of a command are of one kind): the record chain on the device, file by file
+// (ingest_file_bam).  The gated batches (and the prepared ones, PP_BAM_PREPARE=1) live until pp_polish_finish has returned.
 struct BamRoute {
-    std::vector<int> kinds;  // pp_aln_file_kind of every file
-    std::vector<ppb::BamFile *> fronts;                 // [file], as the files are opened -- or all of them, borrowed
-    std::vector<std::unique_ptr<ppb::BamFile>> opened;  // the ones this job opened
+    std::vector<int> kinds;  // pp_aln_file_kind(_text) of every file
+    std::vector<ppb::Front *> fronts;                   // [file], as the files are opened -- or all of them, borrowed
+    std::vector<std::unique_ptr<ppb::Front>> opened;    // the ones this job opened
     pp_names *rnames = nullptr, *qnames = nullptr;      // RNAME -> contig index (seeded with the assembly's names); QNAME -> read_id
     bool borrowed = false;                              // fronts and tables are the fused command's: PolishJob::borrow
     std::vector<pp_gated *> gated;                      // [file]

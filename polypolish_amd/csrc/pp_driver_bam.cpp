@@ -1,5 +1,6 @@
 // pp_driver_bam.cpp -- the polish driver's BAM route: the record chain on the device (pp_bam_files.h -> pp_batch_gate ->
-// pp_polish_add), file by file, on one context; with pp_ctx_set_regroup, pp_batch_regroup stands in front of the gate.  The fronts
+// pp_polish_add), file by file, on one context; with pp_ctx_set_regroup, pp_batch_regroup stands in front of the gate.  SAM text on
+// the chain (Route::TEXT_CHAIN) is the same code behind ppb::TextFile: a front says "record N" or "line N" for itself.  The fronts
 // and the name tables are the job's own, or the fused command's (PolishJob::borrow), which has decoded the files for its filter
 // already.
 #include "pp_driver.h"
@@ -63,9 +64,9 @@ int bam_polish_error(PolishJob &J, int rc) {
     if (pp_ctx_download(ctx, &contig, b.contig + o.at, 4) != PP_OK) return set_err(ctx, rc, said.c_str());
     if (!J.bam.regrouped.empty() && file_record(ctx, J.bam.regrouped[(size_t)o.s->source], &o.record) != PP_OK) return set_err(ctx, rc, said.c_str());
     if (kind == KIND_BAD_CONTIG)
-        return ppb::fail(ctx, rc, "query name %s in SAM but not in assembly: \"%s\" (record %llu)", ppb::name_of(J.bam.rnames, contig).c_str(),
-                         J.sams[o.s->source], (unsigned long long)o.record + 1);
-    return ppb::fail(ctx, rc, "%s: \"%s\" (record %llu)", said.c_str(), J.sams[o.s->source], (unsigned long long)o.record + 1);
+        return ppb::fail(ctx, rc, "query name %s in SAM but not in assembly: \"%s\" (%s)", ppb::name_of(J.bam.rnames, contig).c_str(),
+                         J.sams[o.s->source], J.bam.fronts[(size_t)o.s->source]->where(o.record).c_str());
+    return ppb::fail(ctx, rc, "%s: \"%s\" (%s)", said.c_str(), J.sams[o.s->source], J.bam.fronts[(size_t)o.s->source]->where(o.record).c_str());
 }
 
 static int bam_add_gated(PolishJob &J, int i, const pp_gated *g) {
@@ -94,6 +95,17 @@ static int bam_add_gated(PolishJob &J, int i, const pp_gated *g) {
     return pp_polish_add(J.ctx, &b, PP_MEM_DEVICE);
 }
 
+// A text on the chain that holds a byte >= 0x80: whether its lines are valid UTF-8 is the host parsers' to say.  Plain text files
+// without regrouping go on where they would go without pp_ctx_set_text_chain -- the host ingest, the log resuming at this file as
+// after a tokenizer's hand-back; a bgzipped file, or regrouping, has no such route: refused, naming the path.
+static int text_outside_ascii(PolishJob &J, int i, int rc) {
+    bool plain = !J.bam.borrowed && !pp_ctx_regroup_(J.ctx);
+    for (int k : J.bam.kinds) plain = plain && k == PP_ALN_SAM;
+    if (!plain) return set_err(J.ctx, PP_ERR_QUIT, std::string(pp_last_error(J.ctx)).c_str());  // (the front's sentence names the path)
+    if (J.lap.on) J.lap((std::string("text chain: bytes outside ASCII in ") + J.sams[i] + ", continuing on the host ingest").c_str());
+    return HAND_BACK;
+}
+
 // One BAM file: front end -> pp_batch_gate(pass = the ZP:Z:fail bytes, ANDed with the filter's verdicts where the caller brings them) ->
 // pp_polish_add.  The reference streams, so when the decode or the gate refuses record N (QUIT / PANIC) the records in front of N are
 // decoded, the group still pending there dropped -- the trailing run of aligned records with the last aligned record's QNAME --, the
@@ -106,12 +118,18 @@ static int bam_add_gated(PolishJob &J, int i, const pp_gated *g) {
 int ingest_file_bam(PolishJob &J, int i, pp_sam_counts &c) {
     pp_ctx *const ctx = J.ctx;
     BamRoute &R = J.bam;
-    if (!R.borrowed) {
-        R.opened.emplace_back(new ppb::BamFile);
-        R.fronts.push_back(R.opened.back().get());
-        if (int rc = R.fronts[(size_t)i]->open(ctx, J.sams[i], R.kinds[(size_t)i], R.rnames, &J.lap)) return rc;
+    if (!R.borrowed && J.route == Route::TEXT_CHAIN) {
+        ppb::TextFile *T = new ppb::TextFile;
+        R.opened.emplace_back(T);
+        R.fronts.push_back(T);
+        if (int rc = T->open(ctx, J.sams[i], R.kinds[(size_t)i], R.rnames, &J.lap)) return rc;
+    } else if (!R.borrowed) {
+        ppb::BamFile *F = new ppb::BamFile;
+        R.opened.emplace_back(F);
+        R.fronts.push_back(F);
+        if (int rc = F->open(ctx, J.sams[i], R.kinds[(size_t)i], R.rnames, &J.lap)) return rc;
     }
-    ppb::BamFile *const B = R.fronts[(size_t)i];
+    ppb::Front *const B = R.fronts[(size_t)i];
     const bool regroup = pp_ctx_regroup_(ctx) != 0;
     pp_raw_batch raw{};
     int standing = PP_OK;  // the refusal at N
@@ -132,18 +150,20 @@ int ingest_file_bam(PolishJob &J, int i, pp_sam_counts &c) {
         if (int rc = pp_ctx_download(ctx, flag.data(), raw.flag, n * 2)) return rc;
         return pp_ctx_download(ctx, rid.data(), raw.read_id, n * 8);
     };
-    uint64_t limit = B->n_rec;
-    if (!B->rec) {
+    uint64_t limit = ~0ull;  // in records; ~0: all that are decoded
+    if (!B->decoded()) {
         uint64_t bad = 0;
-        int rc = B->decode(limit, R.qnames, &bad);
+        int rc = B->decode(B->all_units(), R.qnames, &bad);
+        if (rc == PP_ERR_NOT_ASCII) return text_outside_ascii(J, i, rc);
         if (defect(rc) && regroup) return rc;
         if (defect(rc)) {
             stand(rc);
-            if ((rc = B->decode(bad, R.qnames, nullptr))) return rc;
+            if ((rc = B->decode(bad, R.qnames, nullptr)) || (rc = B->group_reads())) return rc;
             if ((rc = groups())) return rc;
-            uint64_t last = bad;  // one past the last aligned record in front of N
+            const uint64_t front = B->n_decoded;  // the records in front of N
+            uint64_t last = front;                // one past the last aligned record among them
             while (last > 0 && (flag[last - 1] & 4)) last--;
-            limit = last ? last - 1 : bad;
+            limit = last ? last - 1 : front;
             for (uint64_t q = limit; last && q-- > 0;) {
                 if (flag[q] & 4) continue;
                 if (rid[q] != rid[last - 1]) break;
@@ -152,10 +172,12 @@ int ingest_file_bam(PolishJob &J, int i, pp_sam_counts &c) {
         } else if (rc) return rc;
         if (J.lap.on) J.lap(("decoded " + B->path).c_str());
     }
-    pp_bam_raw(B->rec, &raw);
+    if (int rc = B->group_reads()) return rc;  // (behind the filter, where the fused command has run one; before anybody reads read_id here)
+    B->raw(&raw);
+    limit = std::min(limit, B->n_decoded);
     const uint8_t *pass = nullptr;
     uint64_t n_aligned = 0;
-    pp_bam_pass(B->rec, &pass, &n_aligned);
+    B->pass(&pass, &n_aligned);
     std::vector<uint8_t> both;  // the filter's verdicts (the fused command) ANDed with the ZP:Z:fail bytes the file came with
     if (J.pass && J.n_pass[i] >= n_aligned && (standing || J.n_pass[i] == n_aligned)) {
         both.resize(n_aligned ? n_aligned : 1);
@@ -200,9 +222,9 @@ int ingest_file_bam(PolishJob &J, int i, pp_sam_counts &c) {
         if (grouped)
             if (int rp = file_record(ctx, grouped, &said_at)) return rp;
         if (rc == PP_ERR_QUIT)
-            ppb::fail(ctx, rc, "no alignments for read %s contain sequence: \"%s\" (record %llu)", qname.c_str(), J.sams[i], (unsigned long long)said_at + 1);
+            ppb::fail(ctx, rc, "no alignments for read %s contain sequence: \"%s\" (%s)", qname.c_str(), J.sams[i], B->where(said_at).c_str());
         else
-            ppb::fail(ctx, rc, "aligned record of read %s has an empty CIGAR: \"%s\" (record %llu)", qname.c_str(), J.sams[i], (unsigned long long)said_at + 1);
+            ppb::fail(ctx, rc, "aligned record of read %s has an empty CIGAR: \"%s\" (%s)", qname.c_str(), J.sams[i], B->where(said_at).c_str());
         stand(rc);
         limit = at;
     }

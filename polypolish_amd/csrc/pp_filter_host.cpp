@@ -776,6 +776,10 @@ struct FilterRun {
     pp_assembly *a = nullptr;                       // the fused command only: its names make the ref_map the polish needs
     pp_names *rnames = nullptr, *qnames = nullptr;  // RNAME -> contig index; ONE QNAME table for both files (the filter joins across files)
     ppb::BamFile F[2];
+    bool chain_text = false;       // SAM text on the same chain (pp_ctx_set_text_chain): its fronts
+    bool left_chain = false;       // ... which a byte >= 0x80 made the run leave: the polish half stays off it as well
+    ppb::TextFile T[2];
+    ppb::Front *front(int f) { return bam ? (ppb::Front *)&F[f] : (ppb::Front *)&T[f]; }
     uint64_t n_aln[2] = {0, 0};    // aligned records per file
     std::vector<uint8_t> pass[2];  // the filter's OWN verdict per aligned record (what the output files carry)
     pp_filter_report rep = {};
@@ -808,9 +812,9 @@ void log_insert_sizes(const Log &log, int step, const pp_filter_report &rep, con
 
 // load_alignments + get_insert_size_thresholds + the pass/fail verdicts (filter.rs:26-34 without filter_sams)
 int filter_core(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char *const ins[2], const char *orientation,
-                double low, double high, FilterRun &R) {
+                double low, double high, FilterRun &R, bool loading_logged = false) {
     auto set_err = [&](int code, const char *msg) { return pp_ctx_set_error_(ctx, code, msg); };
-    log("Loading alignments\n");
+    if (!loading_logged) log("Loading alignments\n");
     const char *in1 = ins[0], *in2 = ins[1];
     // PP_DEVICE_FILTER=1: load_alignments as kernels (pp_filter_dev.hip).  Default is the host loader: its parse
     // overlaps the HIP runtime's start-up, which the device loader has to wait for (measured: 0.86 s vs 1.07 s).
@@ -980,9 +984,10 @@ int filter_write_sam_bam(pp_ctx *ctx, const Log &log, const FilterRun &R, const 
     } free_enc{enc};
     for (int f = 0; f < 2; f++) {
         uint64_t size = 0, bad = 0;
-        const char *text = R.DL ? pp_filter_dev_text(R.DL, f, &size) : R.L->F[f].text.text;
-        if (!R.DL) size = R.L->F[f].text.size;
-        if (pp_sam_bam(ctx, (const uint8_t *)text, size, PP_MEM_HOST, &enc[f], &bad) != PP_OK) {
+        const char *text = R.chain_text ? nullptr : R.DL ? pp_filter_dev_text(R.DL, f, &size) : R.L->F[f].text.text;
+        if (!R.DL && !R.chain_text) size = R.L->F[f].text.size;
+        // (on the chain the decoded object has the text on the device already: no second upload)
+        if ((R.chain_text ? pp_sam_bam_records(ctx, R.T[f].rec, &enc[f], &bad) : pp_sam_bam(ctx, (const uint8_t *)text, size, PP_MEM_HOST, &enc[f], &bad)) != PP_OK) {
             // the encoder's sentence names the path "text": the input's own path in its place
             std::string said = pp_last_error(ctx);
             const std::string path = std::string("\"") + ins[f] + "\"";
@@ -1016,15 +1021,39 @@ int filter_write_sam_bam(pp_ctx *ctx, const Log &log, const FilterRun &R, const 
 int filter_input_kinds(pp_ctx *ctx, const char *const ins[2], int kinds[2], bool *bam) {
     for (int f = 0; f < 2; f++)
         if (int rc = ppb::file_kind(ctx, ins[f], &kinds[f])) return rc;
-    *bam = kinds[0] != PP_ALN_SAM && kinds[1] != PP_ALN_SAM;
-    if (!*bam && (kinds[0] != PP_ALN_SAM || kinds[1] != PP_ALN_SAM)) {
-        const int s = kinds[0] == PP_ALN_SAM ? 0 : 1;
+    *bam = !ppb::is_text(kinds[0]) && !ppb::is_text(kinds[1]);
+    if (!*bam && (!ppb::is_text(kinds[0]) || !ppb::is_text(kinds[1]))) {
+        const int s = ppb::is_text(kinds[0]) ? 0 : 1;
         return ppb::fail(ctx, PP_ERR_QUIT, "--in1 and --in2 must both be SAM text or both be BAM: \"%s\" is SAM text, \"%s\" is BAM", ins[s], ins[1 - s]);
     }
     return PP_OK;
 }
 
-// filter_core for two BAM files: the log is the text route's, word for word
+// what filter_core_bam returns for texts on the chain that are to go on where they go without pp_ctx_set_text_chain (not a PP_ERR_* code)
+constexpr int OFF_THE_CHAIN = -1;
+
+// A text on the chain, decoded for the filter.  filter::filter quits on an empty line (filter.rs:126-130), which the decode skips as
+// polish::polish does: refused here in the text route's own words, and in its order -- when the decode refuses line N, the lines
+// in front of N are asked for an empty one first.  A byte >= 0x80: OFF_THE_CHAIN where the fused text route can take over (plain text
+// files, no regrouping), else refused, naming the path.
+int decode_text_for_filter(pp_ctx *ctx, FilterRun &R, int f, bool may_leave) {
+    ppb::TextFile &T = R.T[f];
+    uint64_t bad = ~0ull, empty = 0;
+    int rc = T.decode(T.all_units(), R.qnames, &bad);
+    if (rc == PP_ERR_NOT_ASCII && may_leave) return OFF_THE_CHAIN;
+    if (rc == PP_ERR_NOT_ASCII) return pp_ctx_set_error_(ctx, PP_ERR_QUIT, std::string(pp_last_error(ctx)).c_str());  // (the front's sentence names the path)
+    if (rc && bad != ~0ull) {
+        const std::string said = pp_last_error(ctx);
+        if (T.decode(bad, R.qnames, nullptr) != PP_OK || !pp_sam_first_empty_line(T.rec, &empty)) return pp_ctx_set_error_(ctx, rc, said.c_str());
+        rc = PP_OK;
+    }
+    if (rc) return rc;
+    if (pp_sam_first_empty_line(T.rec, &empty))
+        return ppb::fail(ctx, PP_ERR_QUIT, "too few columns in \"%s\" (line %llu)", T.path.c_str(), (unsigned long long)empty + 1);
+    return PP_OK;
+}
+
+// filter_core for two BAM files, or two texts on the chain: the log is the text route's, word for word
 int filter_core_bam(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char *const ins[2], const char *assembly,
                     const char *orientation, double low, double high, FilterRun &R) {
     log("Loading alignments\n");
@@ -1035,15 +1064,23 @@ int filter_core_bam(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char
         if ((rc = ppb::load_assembly_file(ctx, 1, assembly, &R.a, err, sizeof err))) return pp_ctx_set_error_(ctx, rc, err);
         if ((rc = pp_names_create(ctx, pp_assembly_n_contigs(R.a), &R.rnames))) return rc;
         if ((rc = ppb::seed_names(R.rnames, R.a))) return rc;
+    } else if (R.chain_text) {  // (a text's RNAMEs are interned, seeded or not: the filter only asks whether two are the same)
+        if ((rc = pp_names_create(ctx, 0, &R.rnames))) return rc;
     }
     if ((rc = pp_names_create(ctx, 0, &R.qnames))) return rc;
     pp_raw_batch raw[2];
+    const bool may_leave = R.kinds[0] == PP_ALN_SAM && R.kinds[1] == PP_ALN_SAM && !(assembly && pp_ctx_regroup_(ctx));
     for (int f = 0; f < 2; f++) {
-        if ((rc = R.F[f].open(ctx, ins[f], R.kinds[f], R.rnames, &lap))) return rc;
-        if ((rc = R.F[f].decode(R.F[f].n_rec, R.qnames, nullptr))) return rc;
-        pp_bam_raw(R.F[f].rec, &raw[f]);
+        if (R.chain_text) {
+            if ((rc = R.T[f].open(ctx, ins[f], R.kinds[f], R.rnames, &lap))) return rc;
+            if ((rc = decode_text_for_filter(ctx, R, f, may_leave))) return rc;
+        } else {
+            if ((rc = R.F[f].open(ctx, ins[f], R.kinds[f], R.rnames, &lap))) return rc;
+            if ((rc = R.F[f].decode(R.F[f].n_rec, R.qnames, nullptr))) return rc;
+        }
+        R.front(f)->raw(&raw[f]);
         const uint8_t *zp = nullptr;
-        pp_bam_pass(R.F[f].rec, &zp, &R.n_aln[f]);
+        R.front(f)->pass(&zp, &R.n_aln[f]);
         R.pass[f].assign(R.n_aln[f] ? R.n_aln[f] : 1, 0);
     }
     lap("alignments loaded");
@@ -1113,6 +1150,35 @@ int filter_write_bam_sam(pp_ctx *ctx, const Log &log, const FilterRun &R, const 
     return PP_OK;
 }
 
+// filter_sams for texts on the chain: the decoded object's own copy of the text with "\tZP:Z:fail" behind the lines whose verdict is 0
+// (pp_sam_tagged_records), written as text -- or, for a bgzipped input, compressed on the device first (pp_bgzf_deflate): the output's
+// kind follows the input's, as BAM in gives BAM out.  Both files are made before either output is created.
+int filter_write_chain_text(pp_ctx *ctx, const Log &log, const FilterRun &R, const char *const ins[2], const char *const outs[2]) {
+    log("Filtering SAM files\n");
+    pp_sam_out *text[2] = {nullptr, nullptr};
+    pp_bgzf_out *packed[2] = {nullptr, nullptr};
+    struct Free {
+        pp_sam_out **t;
+        pp_bgzf_out **c;
+        ~Free() { for (int f = 0; f < 2; f++) { pp_sam_out_free(t[f]); pp_bgzf_out_free(c[f]); } }
+    } free_all{text, packed};
+    for (int f = 0; f < 2; f++) {
+        if (int rc = pp_sam_tagged_records(ctx, R.T[f].rec, R.pass[f].data(), R.n_aln[f], &text[f])) return rc;
+        if (R.kinds[f] != PP_ALN_SAM_BGZF) continue;
+        const uint8_t *dev = nullptr;
+        uint64_t n = 0;
+        pp_sam_out_bytes(text[f], &dev, &n);
+        if (int rc = pp_bgzf_deflate(ctx, dev, n, PP_MEM_DEVICE, &packed[f])) return rc;
+    }
+    for (int f = 0; f < 2; f++) {
+        uint64_t p_ = 0, f_ = 0, lines = 0;
+        pp_sam_out_counts(text[f], &p_, &f_, &lines);
+        if (int rc = packed[f] ? pp_bgzf_out_write(packed[f], outs[f]) : pp_sam_out_write(text[f], outs[f])) return rc;
+        log("Filtering %s:\n  %s pass\n  %s fail\n\n", ins[f], commas(p_).c_str(), commas(f_).c_str());
+    }
+    return PP_OK;
+}
+
 int check_filter_options(pp_ctx *ctx, const char *const *names, int n_names, double low, double high) {
     // check_inputs, filter.rs:40-53
     for (int i = 0; i < n_names; i++)
@@ -1131,18 +1197,34 @@ int run_filter(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const std::func
     if (int rc = check_filter_options(ctx, f4, outs[0] ? 4 : 2, low, high)) return rc;
     banner();
     if (int rc = filter_input_kinds(ctx, ins, R.kinds, &R.bam)) return rc;
-    if (assembly && !R.bam && pp_ctx_regroup_(ctx))  // (the fused command: refused before the filter has written anything)
+    R.chain_text = !R.bam && pp_ctx_text_chain_(ctx) != 0;
+    if (assembly && !R.bam && pp_ctx_regroup_(ctx) && !R.chain_text)  // (the fused command: refused before the filter has written anything)
         return ppb::fail(ctx, PP_ERR_QUIT, "--regroup takes BAM input: \"%s\" is SAM text (its records are regrouped on the device, which holds none of a text file)", ins[0]);
-    if (int rc = R.bam ? filter_core_bam(ctx, log, lap, ins, assembly, orientation, low, high, R)
-                       : filter_core(ctx, log, lap, ins, orientation, low, high, R))
-        return rc;
+    int rc = R.bam || R.chain_text ? filter_core_bam(ctx, log, lap, ins, assembly, orientation, low, high, R)
+                                   : filter_core(ctx, log, lap, ins, orientation, low, high, R);
+    if (rc == OFF_THE_CHAIN) {  // bytes outside ASCII: the fused text route, as without pp_ctx_set_text_chain
+        if (lap.on) lap("text chain: bytes outside ASCII, continuing on the fused text route");
+        R.chain_text = false;
+        R.left_chain = true;
+        for (int f = 0; f < 2; f++) R.T[f].drop_records();
+        pp_names_free(R.qnames);
+        pp_names_free(R.rnames);
+        pp_assembly_free(R.a);
+        R.qnames = R.rnames = nullptr;
+        R.a = nullptr;
+        rc = filter_core(ctx, log, lap, ins, orientation, low, high, R, true);
+    }
+    if (rc) return rc;
     if (outs[0]) {
         const bool text_to_bam = !R.bam && pp_ctx_out_bam_(ctx), bam_to_text = R.bam && pp_ctx_out_sam_(ctx);
-        if (int rc = R.bam ? (bam_to_text ? filter_write_bam_sam(ctx, log, R, ins, outs) : filter_write_bam(ctx, log, R, ins, outs))
-                           : (text_to_bam ? filter_write_sam_bam(ctx, log, R, ins, outs, &R.rep.after_count) : filter_write(ctx, log, R, ins, outs, &R.rep.after_count)))
-            return rc;
+        uint64_t after = 0;  // (the chain: pp_filter_records has counted)
+        if (int rw = R.bam ? (bam_to_text ? filter_write_bam_sam(ctx, log, R, ins, outs) : filter_write_bam(ctx, log, R, ins, outs))
+                     : text_to_bam ? filter_write_sam_bam(ctx, log, R, ins, outs, R.chain_text ? &after : &R.rep.after_count)
+                     : R.chain_text ? filter_write_chain_text(ctx, log, R, ins, outs)
+                                    : filter_write(ctx, log, R, ins, outs, &R.rep.after_count))
+            return rw;
         lap((R.bam && !bam_to_text) || text_to_bam ? "filtered BAMs written" : "filtered SAMs written");
-    } else if (!R.bam) {  // (BAM: pp_filter_records has counted; SAM text without outputs: from the verdicts)
+    } else if (!R.bam && !R.chain_text) {  // (the chain: pp_filter_records has counted; SAM text without outputs: from the verdicts)
         for (int f = 0; f < 2; f++)
             for (uint64_t i = 0; i < R.n_aln[f]; i++) R.rep.after_count += R.pass[f][i];
     }
@@ -1190,10 +1272,13 @@ extern "C" int pp_filter_polish_files(pp_ctx *ctx, const char *assembly, const c
     log("Alignments before filtering: %s\nAlignments after filtering:  %s\n", commas(R.rep.before_count).c_str(), commas(R.rep.after_count).c_str());
     // the verdicts go straight into the polish
     const uint8_t *pass[2] = {R.pass[0].data(), R.pass[1].data()};
-    if (R.bam) {  // the records were decoded once: the gate takes the verdicts, ANDed with the ZP:Z:fail bytes there
-        ppb::BamFile *fronts[2] = {&R.F[0], &R.F[1]};
+    if (R.bam || R.chain_text) {  // the records were decoded once: the gate takes the verdicts, ANDed with the ZP:Z:fail bytes there
+        ppb::Front *fronts[2] = {R.front(0), R.front(1)};
         return ppb::polish_bam_fronts(ctx, assembly, R.a, fronts, R.rnames, R.qnames, ins, 2, opt, fasta, pass, R.n_aln);
     }
     R.release_parse_memory();  // the filter's parse-time memory is released before the polish starts
-    return pp_polish_files_filtered_(ctx, assembly, ins, 2, opt, fasta, pass, R.n_aln);
+    if (R.left_chain) pp_ctx_set_text_chain(ctx, 0);  // (the polish half would only decode the file to learn what the filter knows)
+    const int rp = pp_polish_files_filtered_(ctx, assembly, ins, 2, opt, fasta, pass, R.n_aln);
+    if (R.left_chain) pp_ctx_set_text_chain(ctx, 1);
+    return rp;
 }

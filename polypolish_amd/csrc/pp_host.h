@@ -31,6 +31,8 @@ int pp_ctx_device_(const pp_ctx *ctx);                          // the device a 
 int pp_ctx_out_bam_(const pp_ctx *ctx);                         // what pp_ctx_set_out_bam was given (the filter drivers)
 int pp_ctx_out_sam_(const pp_ctx *ctx);                         // what pp_ctx_set_out_sam was given (the filter drivers)
 int pp_ctx_regroup_(const pp_ctx *ctx);                         // what pp_ctx_set_regroup was given (the file drivers)
+int pp_ctx_text_chain_(const pp_ctx *ctx);                      // what pp_ctx_set_text_chain was given (the file drivers)
+int pp_sam_empty_qname_rule_(pp_sam *s);                        // pp_sam.hip: read_id as the reference groups behind an empty QNAME (the text front, for the gate)
 void pp_ctx_enable_peers_(pp_ctx *const *ctxs, int n);          // peer access between the contexts' devices, best effort (PP_MEM_PEER copies)
 void *pp_host_pinned_alloc_(pp_ctx *ctx, uint64_t bytes);       // pinned host memory for the --debug TSV's chunks ...
 void pp_host_pinned_free_(void *p);                             // ... and its release

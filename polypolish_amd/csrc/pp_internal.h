@@ -269,6 +269,7 @@ struct pp_ctx {
     bool out_bam = false;  // pp_ctx_set_out_bam: the filter drivers write SAM text inputs back as compressed BAM
     bool out_sam = false;  // pp_ctx_set_out_sam: the filter drivers write BAM inputs back as SAM text
     bool regroup = false;  // pp_ctx_set_regroup: the file drivers regroup every BAM file's records in front of the gate
+    bool text_chain = false;  // pp_ctx_set_text_chain: the file drivers take SAM text through the record chain (pp_sam_records)
     pp::DevBuf f_thr;  // pp_filter_thresholds: orientation counts | the selection's state | its two histograms (THR_WORDS u32)
     pp_filter_input fdev{};
     const uint64_t *f_refend_ptr[2] = {nullptr, nullptr};

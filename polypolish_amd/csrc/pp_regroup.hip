@@ -335,3 +335,12 @@ extern "C" int pp_ctx_set_regroup(pp_ctx *ctx, int on) {
 
 // (internal, the file drivers: pp_driver.cpp, pp_driver_bam.cpp)
 extern "C" int pp_ctx_regroup_(const pp_ctx *ctx) { return ctx && ctx->regroup ? 1 : 0; }
+
+extern "C" int pp_ctx_set_text_chain(pp_ctx *ctx, int on) {
+    if (!ctx) return PP_ERR_ARG;
+    ctx->text_chain = on != 0;
+    return PP_OK;
+}
+
+// (internal, the file drivers: pp_driver.cpp, pp_filter_host.cpp)
+extern "C" int pp_ctx_text_chain_(const pp_ctx *ctx) { return ctx && ctx->text_chain ? 1 : 0; }

@@ -35,6 +35,8 @@ struct pp_sam : DevOwner {
     uint64_t n_bytes = 0;
     pp_raw_batch view{};
     std::vector<uint8_t> pass;         // HOST: one byte per aligned record, 0 = ZP:Z:fail
+    uint64_t first_empty = ~0ull;      // the first line without a byte (or with "\r" only), 0-based; ~0: none
+    uint64_t first_nameless = ~0ull;   // the first record line whose QNAME is empty; ~0: none (pp_sam_empty_qname_rule_ has work only then)
     StageMs<5> t;                      // the device copy | newline index | scan | scans and compaction | CIGAR pack
 };
 
@@ -57,11 +59,13 @@ struct SamOut {  // the per-record arrays (device memory)
     u8 *pass;
 };
 
-// Alignment::new on one line.  kind[li] is written for every line; rec[li] for the records.
+// Alignment::new on one line.  kind[li] is written for every line; rec[li] for the records.  status[0]: the first refused line;
+// status[1]: the first empty line (pp_sam_first_empty_line), which this parse skips; status[2]: the first record with an empty QNAME.
 __device__ __forceinline__ void sam_parse_line(const u8 *L, u32 n, u64 li, SamLine *__restrict__ rec, u32 *__restrict__ kind,
                                                u64 *__restrict__ status) {
     kind[li] = SK_SKIP;  // (a refused line, too: the scans behind this kernel run before anybody looks at the status)
-    if (n == 0 || L[0] == (u8)'@') return;  // alignment.rs:241
+    if (n == 0) { report(status + 1, li); return; }
+    if (L[0] == (u8)'@') return;  // alignment.rs:241
     const u64 refused = (li << 8) | SR_PARSE;
     u32 cs[11], cl[11], nc = 0, q = 0;
     while (nc < 11) {
@@ -119,6 +123,7 @@ __device__ __forceinline__ void sam_parse_line(const u8 *L, u32 n, u64 li, SamLi
     r.nm = nm;
     r.n_runs = n_runs;
     r.name_len = cl[0];
+    if (cl[0] == 0) report(status + 2, li);
     r.rname_off = cs[2];
     r.rname_len = cl[2];
     r.cig_off = cs[5];
@@ -258,19 +263,29 @@ extern "C" int pp_sam_kernel_ms(const pp_sam *s, float *ms) {  // (from stage 1:
 // scan | scans and compaction | CIGAR pack
 extern "C" int pp_sam_stage_ms_(const pp_sam *s, float *ms5) { return s ? s->t.stages(ms5) : PP_ERR_ARG; }
 
-extern "C" int pp_sam_records(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, pp_sam **out, uint64_t *bad_line) {
+extern "C" int pp_sam_first_empty_line(const pp_sam *s, uint64_t *line) {
+    if (!s || s->first_empty == ~0ull) return 0;
+    if (line) *line = s->first_empty;
+    return 1;
+}
+
+// pp_sam_records (line_limit = ~0) and pp_sam_records_lines: the first line_limit lines of the text.  Where the limit cuts, the text
+// behind the cut is zeroed in the object's copy and the call goes on as pp_sam_records of the prefix.
+static int sam_records(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, u64 line_limit, pp_sam **out, uint64_t *bad_line) {
+    const char *const sym = line_limit != ~0ull ? "pp_sam_records_lines" : "pp_sam_records";  // who the refusals speak as
     if (!ctx) return PP_ERR_ARG;
     if (int rdy = pp_ctx_wait(ctx)) return rdy;
     if (bad_line) *bad_line = ~0ull;
-    if (!out) return ctx->fail(PP_ERR_ARG, "pp_sam_records: null argument");
+    if (!out) return ctx->fail(PP_ERR_ARG, "%s: null argument", sym);
     *out = nullptr;
     if (mem != PP_MEM_HOST && mem != PP_MEM_DEVICE)
-        return ctx->fail(PP_ERR_ARG, "pp_sam_records: the text must be host memory or memory of the context's device");
-    if (n_bytes && !text) return ctx->fail(PP_ERR_ARG, "pp_sam_records: null text with n_bytes > 0");
-    if (n_bytes >= (1ull << 40)) return ctx->fail(PP_ERR_LIMIT, "pp_sam_records: the text is larger than the 1 TiB this decode indexes");
+        return ctx->fail(PP_ERR_ARG, "%s: the text must be host memory or memory of the context's device", sym);
+    if (n_bytes && !text) return ctx->fail(PP_ERR_ARG, "%s: null text with n_bytes > 0", sym);
+    if (n_bytes >= (1ull << 40)) return ctx->fail(PP_ERR_LIMIT, "%s: the text is larger than the 1 TiB this decode indexes", sym);
     PP_HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const u64 size = n_bytes;
+    const bool limited = line_limit != ~0ull;
+    u64 size = line_limit ? n_bytes : 0;  // (no line: no byte of the text is looked at)
 
     std::unique_ptr<pp_sam> P(new pp_sam(ctx));
     RawArrays &A = P->a;
@@ -286,8 +301,8 @@ extern "C" int pp_sam_records(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes
     PP_HIPCHK(ctx, hipMemsetAsync(A.seq + size, 0, (size_t)(padded + 64 - size), st));
     if ((rc = timer.end())) return rc;
     const u8 *const d_text = A.seq;
-    P->n_bytes = size;
     auto done = [&](u64 n_rec, u64 n_cig_total) {  // (an empty batch: the text and no other array)
+        P->n_bytes = size;
         P->view = A.view(n_rec, size, n_cig_total);
         *out = P.release();
         return PP_OK;
@@ -300,23 +315,35 @@ extern "C" int pp_sam_records(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes
     u64 n_nl = 0;
     u32 not_ascii = 0;
     if ((rc = timer.begin(1))) return rc;
-    if ((rc = newline_index(ctx, d_text, size, N.blk, N.blkoff, N.nl, &n_nl, &not_ascii))) return rc;
+    if ((rc = newline_index(ctx, d_text, size, N.blk, N.blkoff, N.nl, &n_nl, &not_ascii, limited))) return rc;
+    if (limited && line_limit <= n_nl) {
+        // Line line_limit starts behind newline line_limit - 1 (there may be no byte of it: the limit is the line count then).  From
+        // there on the copy is zeros, as behind the end of any text, and the prefix is the text: its first line_limit newlines are
+        // indexed already; whether IT holds a byte outside ASCII is asked again only where the whole text does.
+        u64 cut = 0;
+        if ((rc = fetch(ctx, (const u64 *)N.nl.p + (line_limit - 1), &cut))) return rc;
+        cut += 1;
+        if (cut < size) PP_HIPCHK(ctx, hipMemsetAsync(A.seq + cut, 0, (size_t)(size - cut), st));
+        size = cut;
+        n_nl = line_limit;
+        if (not_ascii && (rc = newline_index(ctx, d_text, size, N.blk, N.blkoff, N.nl, &n_nl, &not_ascii))) return rc;
+    }
     if ((rc = timer.end())) return rc;
     if (not_ascii)  // as pp_dev_ingest_sam: which lines are valid UTF-8 is the host parsers' to say
         return ctx->fail(PP_ERR_NOT_ASCII, "the text holds bytes outside ASCII: left to the host ingest");
     u8 last = 0;
     if ((rc = fetch(ctx, d_text + size - 1, &last))) return rc;
     const u64 n_lines = n_nl + (last != (u8)'\n' ? 1 : 0);
-    if (n_lines >= 0xFFFFFFFFull) return ctx->fail(PP_ERR_LIMIT, "pp_sam_records: 2^32-1 or more lines in one text");
+    if (n_lines >= 0xFFFFFFFFull) return ctx->fail(PP_ERR_LIMIT, "%s: 2^32-1 or more lines in one text", sym);
     const u64 *const d_nl = (const u64 *)N.nl.p;
 
     // ---- the scan, and the sums ----
     const u32 nb = (u32)((n_lines + SAM_BLOCK - 1) / SAM_BLOCK);
     void *d_rec, *d_kind, *d_blk3, *d_blk3off, *d_status;
     if ((rc = T.get(ctx, &d_rec, (size_t)n_lines * sizeof(SamLine))) || (rc = T.get(ctx, &d_kind, (size_t)n_lines * 4)) ||
-        (rc = T.get(ctx, &d_blk3, (size_t)nb * 24)) || (rc = T.get(ctx, &d_blk3off, ((size_t)nb + 1) * 24)) || (rc = T.get(ctx, &d_status, 8)))
+        (rc = T.get(ctx, &d_blk3, (size_t)nb * 24)) || (rc = T.get(ctx, &d_blk3off, ((size_t)nb + 1) * 24)) || (rc = T.get(ctx, &d_status, 24)))
         return rc;
-    PP_HIPCHK(ctx, hipMemsetAsync(d_status, 0xFF, 8, st));
+    PP_HIPCHK(ctx, hipMemsetAsync(d_status, 0xFF, 24, st));
     if ((rc = timer.begin(2))) return rc;
     with_stage(tok_stage_for(size, n_lines), [&](auto stage) {
         hipLaunchKernelGGL(k_sam_scan<decltype(stage)::value>, dim3((unsigned)((n_lines + 63) / 64)), dim3(64), 0, st, d_text, size, d_nl, n_nl,
@@ -328,14 +355,17 @@ extern "C" int pp_sam_records(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes
     hipLaunchKernelGGL(k_colscan<3>, dim3(1), dim3(1024), 0, st, (const u64 *)d_blk3, (u64)nb, (u64 *)d_blk3off);
     if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
-    u64 status = ~0ull, totals[3] = {0, 0, 0};
-    if ((rc = fetch(ctx, d_status, &status)) || (rc = fetch(ctx, (const u64 *)d_blk3off + 3ull * nb, totals, 3))) return rc;
+    u64 status2[3] = {~0ull, ~0ull, ~0ull}, totals[3] = {0, 0, 0};
+    if ((rc = fetch(ctx, d_status, status2, 3)) || (rc = fetch(ctx, (const u64 *)d_blk3off + 3ull * nb, totals, 3))) return rc;
+    const u64 status = status2[0];
+    P->first_empty = status2[1];
+    P->first_nameless = status2[2];
     if (status != ~0ull) {  // the first refused line: its bytes, and what the host parser says to them
         const u64 li = status >> 8;
         const u32 why = (u32)(status & 0xFFu);
         if (bad_line) *bad_line = li;
         if (why != SR_PARSE)
-            return ctx->fail(PP_ERR_LIMIT, "pp_sam_records: %s in \"text\" (line %llu)", limit_text(why), (unsigned long long)(li + 1));
+            return ctx->fail(PP_ERR_LIMIT, "%s: %s in \"text\" (line %llu)", sym, limit_text(why), (unsigned long long)(li + 1));
         u64 a = 0, b = size;
         if (li) {
             if ((rc = fetch(ctx, d_nl + (li - 1), &a))) return rc;
@@ -349,7 +379,7 @@ extern "C" int pp_sam_records(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes
         }
         char err[1024] = "";
         const int code = pp_ingest_line_error_("text", line.data(), line.size(), li + 1, err, sizeof err);
-        if (code == PP_OK) return ctx->fail(PP_ERR_HIP, "pp_sam_records: the device refused line %llu but the host ingest takes it", (unsigned long long)(li + 1));
+        if (code == PP_OK) return ctx->fail(PP_ERR_HIP, "%s: the device refused line %llu but the host ingest takes it", sym, (unsigned long long)(li + 1));
         return ctx->fail(code, "%s", err);
     }
     const u64 n_rec = totals[0], n_al = totals[1], n_cig_total = totals[2];
@@ -383,4 +413,47 @@ extern "C" int pp_sam_records(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes
     PP_HIPCHK(ctx, hipStreamSynchronize(st));  // the caller's text may be released, the scratch goes away
     if ((rc = P->t.take(timer))) return rc;
     return done(n, n_cig_total);
+}
+
+extern "C" int pp_sam_records(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, pp_sam **out, uint64_t *bad_line) {
+    return sam_records(ctx, text, n_bytes, mem, ~0ull, out, bad_line);
+}
+
+extern "C" int pp_sam_records_lines(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, uint64_t n_lines, pp_sam **out,
+                                    uint64_t *bad_line) {
+    return sam_records(ctx, text, n_bytes, mem, n_lines == ~0ull ? n_lines - 1 : n_lines, out, bad_line);
+}
+
+// (internal hook, the command drivers' text front: pp_bam_files.cpp)  The reference's grouping quirk on top of interned ids, for the
+// gate: an ALIGNED record joins the aligned record in front of it also when THAT one's QNAME is empty (src/alignment.rs:255), which
+// ids from a name table do not know.  Where the decoded text has a record with an empty QNAME -- the scan has noted the first --
+// read_id is rewritten as tests/names_model.empty_qname_rule has it: such a successor copies its predecessor's id, and a group that
+// follows with the id the group in front borrowed that way gets a fresh one (from 2^40 up).  One sequential walk on the host over
+// flag, name_len and read_id; a text without such a record (every text `bwa mem` writes) costs nothing.  Call it behind the QNAME
+// pp_names_ids, and behind a filter: filter::filter keys its reads by name and has no such rule.
+extern "C" int pp_sam_empty_qname_rule_(pp_sam *s) {
+    if (!s) return PP_ERR_ARG;
+    const uint64_t n = s->view.n_rec;
+    if (s->first_nameless == ~0ull || n == 0) return PP_OK;
+    s->first_nameless = ~0ull;  // (once)
+    pp_ctx *ctx = s->ctx;
+    PP_HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::vector<uint16_t> flag((size_t)n);
+    std::vector<u32> len((size_t)n);
+    std::vector<u64> id((size_t)n), was;
+    int rc;
+    if ((rc = fetch(ctx, s->a.flag, flag.data(), (size_t)n)) || (rc = fetch(ctx, s->name_len, len.data(), (size_t)n)) ||
+        (rc = fetch(ctx, s->a.read_id, id.data(), (size_t)n)))
+        return rc;
+    was = id;
+    u64 fresh = 1ull << 40, prev = ~0ull;
+    for (u64 r = 0; r < n; r++) {
+        if (flag[r] & 4) continue;
+        if (prev != ~0ull && (len[prev] == 0 || was[prev] == was[r])) id[r] = id[prev];
+        else if (prev != ~0ull && id[r] == id[prev]) id[r] = fresh++;
+        prev = r;
+    }
+    PP_HIPCHK(ctx, hipMemcpyAsync(s->a.read_id, id.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    PP_HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return PP_OK;
 }

@@ -150,9 +150,13 @@ def main(argv=None):
     ap.add_argument("-d", "--min_depth", type=int, default=5)
     ap.add_argument("--careful", action="store_true")
     ap.add_argument("--debug", default=None)
+    ap.add_argument("--text_chain", action="store_true")
     ap.add_argument("assembly")
     ap.add_argument("sam", nargs="*")
     a = ap.parse_args(argv)
+    if a.text_chain:    # (one context per command, as for BAM)
+        raise SystemExit("Error: SAM text on the record chain (--text_chain) runs on one GPU: polish it with `polypolish polish --text_chain`, "
+                         "or without --text_chain")
     # BAM input runs on one GPU (`polypolish polish`, Context.polish_files): the ranks here share the host ingest of SAM text
     for path in a.sam:
         if not os.path.isfile(path):
