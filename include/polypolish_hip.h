@@ -1195,6 +1195,47 @@ typedef struct {
 } pp_bytes;
 void pp_bytes_free(pp_bytes *b);
 
+/* ---- contig bases -> FASTA text on the device (pp_fasta_out.hip) ------------------------------
+ * pp_fasta_text is the mirror of pp_fasta_records and the link in front of pp_bgzf_deflate: the contigs' bytes, where they lie in
+ * device memory, as FASTA text at a chosen line width (not in the reference, which prints one line per contig).
+ * tests/fasta_text_model.py defines the bytes.
+ *   arguments   bases: the contigs' bytes one behind the other, contig c = bases[contig_off[c], contig_off[c + 1]) -- contig_off (HOST,
+ *               n_contigs + 1) is what pp_polish_result fills.  mem = PP_MEM_DEVICE: read where they lie, at any alignment (what
+ *               pp_polish_result_device returns); PP_MEM_HOST: one staging copy, released before the call returns.  Header c is
+ *               headers[header_off[c], header_off[c + 1]) (both HOST): the line without its '>' and without its newline.
+ *   the text    for each contig in order '>', the header, "\n", then the body.  width == 0: the contig's bytes and one "\n" (a contig
+ *               of no bytes gives an empty line): byte for byte what pp_polish_files returns.  width == W > 0: a contig of L bytes
+ *               gives ceil(L / W) lines of W bytes, the last one shorter, each ended by "\n"; L == 0 gives no body line at all.  The
+ *               bytes are copied as they are: nothing is upper-cased or checked.
+ *   memory      no byte outside bases[contig_off[0], contig_off[n_contigs]) and outside the header bytes is loaded, by a wide load
+ *               either: a device array may end where its allocation ends.
+ *   errors      all decided on the host before anything is uploaded.  PP_ERR_ARG: null arguments, PP_MEM_PEER, null bases with bytes
+ *               to copy, offsets that decrease, a header that holds "\n".  PP_ERR_LIMIT: a text of 2^40 bytes or more, width above
+ *               2^31 - 1.  n_contigs == 0 gives an empty text.
+ * The host does what is proportional to the contigs (the checks, a table per contig, the .fai rows), the device what is proportional
+ * to the text.  The context's stream has been synchronised when the call returns.
+ *   pp_fasta_out_bytes      the text (DEVICE, borrowed until pp_fasta_out_free): pp_bgzf_deflate(ctx, dev, n_bytes, PP_MEM_DEVICE, ...)
+ *                           makes the bgzipped file, pp_fasta_records reads it back
+ *   pp_fasta_out_fai        the text's .fai index (HOST, release with pp_bytes_free): per contig name \t L \t offset \t linebases \t
+ *                           linewidth \n -- name = the header up to its first space or tab, offset = the text offset of the contig's
+ *                           first base, linebases = min(L, W) (L with W == 0), linewidth = linebases + 1; "0 0" for L == 0
+ *   pp_fasta_out_write      as pp_bgzf_out_write: downloads the text in slices and writes it to `path`
+ *   pp_fasta_out_kernel_ms  as pp_fasta_kernel_ms
+ *   pp_bgzf_out_gzi         the .gzi index of ANY pp_bgzf_out (HOST, release with pp_bytes_free), little-endian: a uint64 count, then
+ *                           per block except the first its offset in the file and the uncompressed bytes in front of it (b * 65,280);
+ *                           no pair for the EOF block
+ * Both indexes follow the published formats (samtools faidx, bgzip -i) as this project reads them; they were not compared with
+ * htslib's own files.  The object belongs to its context and is freed before it. */
+typedef struct pp_fasta_out pp_fasta_out;
+int pp_fasta_text(pp_ctx *ctx, const uint8_t *bases, int mem, uint32_t n_contigs, const uint64_t *contig_off /* HOST, n+1 */,
+                  const uint8_t *headers /* HOST */, const uint64_t *header_off /* HOST, n+1 */, uint32_t width, pp_fasta_out **out);
+void pp_fasta_out_bytes(const pp_fasta_out *o, const uint8_t **dev, uint64_t *n_bytes); /* DEVICE, borrowed */
+int pp_fasta_out_fai(const pp_fasta_out *o, pp_bytes *fai);                             /* the .fai text, HOST */
+int pp_fasta_out_write(const pp_fasta_out *o, const char *path);                        /* download in slices, write */
+int pp_fasta_out_kernel_ms(const pp_fasta_out *o, float *ms);
+void pp_fasta_out_free(pp_fasta_out *o);
+int pp_bgzf_out_gzi(const pp_bgzf_out *z, pp_bytes *gzi); /* the .gzi of any pp_bgzf_out, HOST */
+
 /* Coordinate-sorted BAM for the file drivers below (the commands' --regroup): with `on` != 0, pp_polish_files and the polish half of
  * pp_filter_polish_files put pp_batch_regroup between the decode and the gate of every BAM file, so that a read's records count as
  * one read wherever they lie in the file (the filter joins them already, and writes in file order).  The state lives on the
@@ -1239,6 +1280,19 @@ int pp_ctx_set_out_sam(pp_ctx *ctx, int on);
  * Off when the context is made and off by default in the commands: the fused routes are the measured default, and what they refuse
  * is pinned by tests. */
 int pp_ctx_set_text_chain(pp_ctx *ctx, int on);
+
+/* The form of the polished FASTA that the file drivers below return (the commands' --wrap, --out_bgzf, --out, --index; not in the
+ * reference): with width >= 0 the pp_bytes of pp_polish_files, pp_polish_files_multi and pp_filter_polish_files are made by
+ * pp_fasta_text at that line width (0: one line per contig, today's bytes), and with bgzf != 0 they are that text compressed by
+ * pp_bgzf_deflate on the device bytes.  On one context the source is the polished bytes in device memory; on several contexts it is the
+ * host bytes the ranks' results were assembled into (PP_MEM_HOST), so no route is refused.  width < 0 switches the form off: the
+ * drivers then run exactly the code they ran before (bgzf is ignored).  PP_ERR_LIMIT: a width above 2^31 - 1.  The log does not
+ * change.  The state lives on the context, like pp_ctx_set_out_bam's; off when the context is made.
+ * pp_ctx_fasta_index: the indexes of the last text a driver made on this context with the form set -- the .fai of pp_fasta_out_fai,
+ * and with bgzf the .gzi of pp_bgzf_out_gzi (else empty); either argument may be NULL; release with pp_bytes_free.  PP_ERR_ARG when
+ * no such text was made. */
+int pp_ctx_set_fasta_form(pp_ctx *ctx, int64_t width, int bgzf);
+int pp_ctx_fasta_index(pp_ctx *ctx, pp_bytes *fai, pp_bytes *gzi);
 
 /* polish::polish (src/polish.rs:26-38): FASTA text exactly as the reference prints to stdout.
  * `sams` are SAM text files or -- all of them -- BAM files (pp_aln_file_kind; a mix is PP_ERR_QUIT).  BAM goes through the record

@@ -1029,6 +1029,72 @@ def fasta_geometry():
     return int(a.value), int(b.value), int(c.value)
 
 
+def _take_bytes(b):
+    """the bytes of a pp_bytes the library allocated, which is released"""
+    data = C.string_at(b.data, b.len) if b.len else b""
+    lib().pp_bytes_free(C.byref(b))
+    return data
+
+
+class FastaText(_Owned):
+    """pp_fasta_text: contig bases as FASTA text at a chosen line width in DEVICE memory, owned by this object -- the mirror of
+    FastaRecords and the link in front of BgzfDeflated (tests/fasta_text_model.py defines the bytes).
+      bases          mem = MEM_HOST: bytes / a uint8 array; MEM_DEVICE: (device address, n_bytes), borrowed for the call (what a
+                     polish job leaves behind); the contigs one behind the other
+      contig_off     n + 1 offsets into bases (host)
+      headers        n header lines (bytes) without their '>' and their newline
+      width          0: one line per contig, else the line width
+      .dev()         (device address, n_bytes) of the text: what BgzfDeflated / FastaRecords take with mem=MEM_DEVICE
+      .bytes()       the text as bytes (a download)
+      .fai()         its .fai index as bytes
+      .deflate()     pp_bgzf_deflate on the device bytes -> BgzfDeflated (.gzi(): its .gzi index)
+      .write(path)   pp_fasta_out_write: the text on disk
+      .kernel_ms()   HIP-event time of the kernel (the context had set_profiling on); .stage_ms(): copy | text"""
+    _free, _kernel_ms = "pp_fasta_out_free", "pp_fasta_out_kernel_ms"
+
+    def __init__(self, ctx, bases, contig_off, headers, width=0, mem=MEM_HOST):
+        L = lib()
+        bp, _, _, _, _keep = _bytes_and_offsets(bases, None, mem)
+        off = np.ascontiguousarray(contig_off, dtype=np.uint64)
+        n = len(off) - 1
+        hb = np.frombuffer(b"".join(headers) + b"\0", dtype=np.uint8)
+        ho = np.zeros(n + 1, dtype=np.uint64)
+        ho[1:] = np.cumsum([len(h) for h in headers], dtype=np.uint64)
+        super().__init__(ctx)
+        ctx._chk(L.pp_fasta_text(ctx._h, bp, mem, n, off.ctypes.data, hb.ctypes.data, ho.ctypes.data, int(width), C.byref(self._p)))
+        dev, nb = C.c_void_p(), C.c_uint64(0)
+        L.pp_fasta_out_bytes(self._p, C.byref(dev), C.byref(nb))
+        self.bytes_ptr, self.n_bytes = dev.value or 0, int(nb.value)
+
+    def dev(self):
+        return self.bytes_ptr, self.n_bytes
+
+    def bytes(self):
+        return self._ctx.download(self.bytes_ptr, self.n_bytes, np.uint8).tobytes() if self.n_bytes else b""
+
+    def fai(self):
+        b = Bytes()
+        self._ctx._chk(lib().pp_fasta_out_fai(self._p, C.byref(b)))
+        return _take_bytes(b)
+
+    def deflate(self):
+        return BgzfDeflated(self._ctx, self.dev(), mem=MEM_DEVICE)
+
+    def write(self, path):
+        self._ctx._chk(lib().pp_fasta_out_write(self._p, os.fsencode(path)))
+
+    def stage_ms(self):
+        return self._stage_ms("pp_fasta_out_stage_ms_", ("copy", "text"), " when the text was made")
+
+
+def fasta_out_geometry():
+    """(bytes per store S, bytes per workgroup G) of pp_fasta_text: a lane writes S bytes of TEXT with one aligned store, a workgroup
+    owns the text offsets [k * G, (k + 1) * G): the seams its tests aim at."""
+    a, b = C.c_uint32(), C.c_uint32()
+    lib().pp_fasta_out_geometry_(C.byref(a), C.byref(b))
+    return int(a.value), int(b.value)
+
+
 class BamTagged(_Owned):
     """pp_bam_tagged: the filter's verdicts written back as a BAM file (level-0 BGZF) in DEVICE memory, owned by this object.
       data, rec_off  mem = MEM_HOST: bytes / a uint8 array of uncompressed BAM, and the records' offsets; MEM_DEVICE: data = (device
@@ -1090,6 +1156,7 @@ class BgzfDeflated(_Owned):
       .counts        blocks by form: (stored, fixed, dynamic)
       .host(lo, hi)  a numpy copy of the file's bytes [lo, hi) (a download); .blk_off(): of the n_blocks + 1 offsets
       .write(path)   pp_bgzf_out_write: the file on disk
+      .gzi()         pp_bgzf_out_gzi: the file's .gzi index as bytes
       .kernel_ms()   HIP-event time of the kernels (the context had set_profiling on); .stage_ms(): pieces | scan | place"""
     _free, _kernel_ms = "pp_bgzf_out_free", "pp_bgzf_out_kernel_ms"
 
@@ -1121,6 +1188,12 @@ class BgzfDeflated(_Owned):
 
     def write(self, path):
         self._ctx._chk(lib().pp_bgzf_out_write(self._p, os.fsencode(path)))
+
+    def gzi(self):
+        """pp_bgzf_out_gzi: the file's .gzi index as bytes (per block except the first: its offset, the uncompressed bytes in front)"""
+        b = Bytes()
+        self._ctx._chk(lib().pp_bgzf_out_gzi(self._p, C.byref(b)))
+        return _take_bytes(b)
 
     def stage_ms(self):
         return self._stage_ms("pp_bgzf_out_stage_ms_", ("pieces", "scan", "place"), " when the bytes were compressed")
@@ -1718,6 +1791,52 @@ class Context:
             self.set_text_chain(was)
 
     @contextlib.contextmanager
+    def _fasta_form(self, wrap, bgzf, out, index):
+        """wrap= (a line width, 0: one line per contig), bgzf=, out= (a path) and index= of one command: pp_ctx_set_fasta_form for its
+        duration; behind it the FASTA the command returned is written to `out`, with `out`.fai (and `out`.gzi under bgzf) for index.
+        The command hands its bytes to the function this yields."""
+        if index and out is None:
+            raise PolypolishError(ERR_QUIT, "index=True needs out=<path>: the indexes are written next to the file")
+        L = lib()
+        on = wrap is not None or bgzf or index
+        if on:
+            self._chk(L.pp_ctx_set_fasta_form(self._h, int(wrap or 0), int(bool(bgzf))))
+        L.pp_ctx_set_fasta_out_name_(self._h, os.fsencode(out) if out is not None else None)
+
+        def deliver(data):
+            if out is None:
+                return
+            try:
+                with open(out, "wb") as f:
+                    f.write(data)
+                if index:
+                    fai, gzi = self.fasta_index()
+                    with open(os.fspath(out) + ".fai", "wb") as f:
+                        f.write(fai)
+                    if bgzf:
+                        with open(os.fspath(out) + ".gzi", "wb") as f:
+                            f.write(gzi)
+            except OSError:
+                raise PolypolishError(ERR_QUIT, f'unable to write the polished sequence to "{os.fspath(out)}"') from None
+        try:
+            yield deliver
+        finally:
+            if on:
+                L.pp_ctx_set_fasta_form(self._h, -1, 0)
+            L.pp_ctx_set_fasta_out_name_(self._h, None)
+
+    def set_fasta_form(self, width, bgzf=False):
+        """pp_ctx_set_fasta_form: polish_files and filter_polish_files return the FASTA made by pp_fasta_text at this line width (0:
+        one line per contig; None: off, the host loop as before), compressed by pp_bgzf_deflate with bgzf."""
+        self._chk(lib().pp_ctx_set_fasta_form(self._h, -1 if width is None else int(width), int(bool(bgzf))))
+
+    def fasta_index(self):
+        """pp_ctx_fasta_index: (.fai bytes, .gzi bytes) of the last FASTA a command made on this context with the form set"""
+        fai, gzi = Bytes(), Bytes()
+        self._chk(lib().pp_ctx_fasta_index(self._h, C.byref(fai), C.byref(gzi)))
+        return _take_bytes(fai), _take_bytes(gzi)
+
+    @contextlib.contextmanager
     def _writing_bam(self, out_bam):
         """out_bam=True switches pp_ctx_set_out_bam on for one command and off again behind it"""
         if not out_bam:
@@ -1742,37 +1861,43 @@ class Context:
             self.set_out_sam(False)
 
     def polish_files(self, assembly, sams, fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5,
-                     careful=False, debug=None, quiet=True, regroup=False, text_chain=False):
-        """polish::polish (pp_polish_files): the FASTA bytes.  `sams` are SAM text files, or all of them BAM files (BGZF or
+                     careful=False, debug=None, quiet=True, regroup=False, text_chain=False, wrap=None, bgzf=False, out=None,
+                     index=False):
+        """polish::polish (pp_polish_files): the FASTA bytes.  wrap / bgzf / out / index (not in the reference): the FASTA at a line
+        width (0: one line per contig) and bgzipped, made on the device (pp_fasta_text, pp_bgzf_deflate); also written to `out`,
+        with out.fai (and out.gzi) for index.  `sams` are SAM text files, or all of them BAM files (BGZF or
         uncompressed; told by content, aln_file_kind): those go through the record chain on the device, inside the driver.
         regroup: for this call, as set_regroup (coordinate-sorted BAM).  text_chain: for this call, as set_text_chain (SAM text,
         plain or bgzipped, through the record chain as well)."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         arr = (C.c_char_p * max(len(sams), 1))(*[str(s).encode() for s in sams])
-        out = Bytes()
-        with self._regrouping(regroup), self._chaining_text(text_chain):
-            self._chk(lib().pp_polish_files(self._h, str(assembly).encode(), arr, len(sams), C.byref(opt), C.byref(out)))
-        data = C.string_at(out.data, out.len) if out.len else b""
-        lib().pp_bytes_free(C.byref(out))
+        res = Bytes()
+        with self._regrouping(regroup), self._chaining_text(text_chain), self._fasta_form(wrap, bgzf, out, index) as deliver:
+            self._chk(lib().pp_polish_files(self._h, str(assembly).encode(), arr, len(sams), C.byref(opt), C.byref(res)))
+            data = _take_bytes(res)
+            deliver(data)
         return data
 
     def filter_polish_files(self, assembly, in1, in2, out1=None, out2=None, orientation="auto", low=0.1, high=99.9,
                             fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5, careful=False,
-                            debug=None, quiet=True, regroup=False, out_bam=False, out_sam=False, text_chain=False):
-        """filter + polish in one process (pp_filter_polish_files): returns (FASTA bytes, filter report).  Two BAM inputs are decoded
+                            debug=None, quiet=True, regroup=False, out_bam=False, out_sam=False, text_chain=False, wrap=None,
+                            bgzf=False, out=None, index=False):
+        """filter + polish in one process (pp_filter_polish_files): returns (FASTA bytes, filter report).  wrap / bgzf / out / index:
+        as polish_files.  Two BAM inputs are decoded
         once for both halves; out1 / out2 are then BAM files as well.  regroup: for this call, as set_regroup (the polish half).
         out_bam: for this call, as set_out_bam (SAM text inputs, out1 / out2 as compressed BAM).  out_sam: for this call, as
         set_out_sam (BAM inputs, out1 / out2 as SAM text).  text_chain: for this call, as set_text_chain."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
-        rep, out = FilterReport(), Bytes()
+        rep, res = FilterReport(), Bytes()
         enc = lambda x: str(x).encode() if x is not None else None
-        with self._regrouping(regroup), self._writing_bam(out_bam), self._writing_sam(out_sam), self._chaining_text(text_chain):
+        with self._regrouping(regroup), self._writing_bam(out_bam), self._writing_sam(out_sam), self._chaining_text(text_chain), \
+                self._fasta_form(wrap, bgzf, out, index) as deliver:
             self._chk(lib().pp_filter_polish_files(self._h, enc(assembly), enc(in1), enc(in2), enc(out1), enc(out2),
-                                                   orientation.encode(), low, high, C.byref(opt), C.byref(rep), C.byref(out)))
-        data = C.string_at(out.data, out.len) if out.len else b""
-        lib().pp_bytes_free(C.byref(out))
+                                                   orientation.encode(), low, high, C.byref(opt), C.byref(rep), C.byref(res)))
+            data = _take_bytes(res)
+            deliver(data)
         return data, _report_dict(rep)
 
     def filter_files(self, in1, in2, out1, out2, orientation="auto", low=0.1, high=99.9, quiet=True, out_bam=False, out_sam=False,
@@ -1801,12 +1926,13 @@ def _ctx():
 
 
 def polish(assembly, sam, debug=None, fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5,
-           careful=False, regroup=False, text_chain=False) -> bytes:
+           careful=False, regroup=False, text_chain=False, wrap=None, bgzf=False, out=None, index=False) -> bytes:
     """polish::polish (src/polish.rs:26-38): returns the FASTA bytes the reference prints to stdout.  regroup: coordinate-sorted
     BAM files (every read's records are brought together in front of the gate: the command's --regroup).  text_chain: SAM text,
-    plain or bgzipped, through the record chain as well (the command's --text_chain; regroup then takes text too)."""
+    plain or bgzipped, through the record chain as well (the command's --text_chain; regroup then takes text too).  wrap / bgzf / out /
+    index: the commands' --wrap, --out_bgzf, --out and --index (Context.polish_files)."""
     return _ctx().polish_files(assembly, list(sam), fraction_invalid, fraction_valid, max_errors, min_depth, careful,
-                               debug, regroup=regroup, text_chain=text_chain)
+                               debug, regroup=regroup, text_chain=text_chain, wrap=wrap, bgzf=bgzf, out=out, index=index)
 
 
 def filter(in1, in2, out1, out2, orientation="auto", low=0.1, high=99.9):  # noqa: A001 (reference name)

@@ -264,10 +264,19 @@ SIGNATURES = {
     "pp_ingest_read_name": (_str, [_vp, _u64]),
     "pp_ingest_free": (None, [_vp]),
     "pp_bytes_free": (None, [_P(Bytes)]),
+    "pp_fasta_text": (_i, [_vp, _vp, _i, _u32, _vp, _vp, _vp, _u32, _pvp]),
+    "pp_fasta_out_bytes": (None, [_vp, _pvp, _pu64]),
+    "pp_fasta_out_fai": (_i, [_vp, _P(Bytes)]),
+    "pp_fasta_out_write": (_i, [_vp, _str]),
+    "pp_fasta_out_kernel_ms": (_i, [_vp, _pf32]),
+    "pp_fasta_out_free": (None, [_vp]),
+    "pp_bgzf_out_gzi": (_i, [_vp, _P(Bytes)]),
     "pp_ctx_set_regroup": (_i, [_vp, _i]),
     "pp_ctx_set_out_bam": (_i, [_vp, _i]),
     "pp_ctx_set_out_sam": (_i, [_vp, _i]),
     "pp_ctx_set_text_chain": (_i, [_vp, _i]),
+    "pp_ctx_set_fasta_form": (_i, [_vp, C.c_int64, _i]),
+    "pp_ctx_fasta_index": (_i, [_vp, _P(Bytes), _P(Bytes)]),
     "pp_polish_files": (_i, [_vp, _str, _P(_str), _i, _P(PolishOptions), _P(Bytes)]),
     "pp_polish_files_multi": (_i, [_pvp, _i, _str, _P(_str), _i, _P(PolishOptions), _P(Bytes)]),
     "pp_dev_ingest_create": (_i, [_vp, _vp, _u32, _i, _pvp]),
@@ -298,6 +307,10 @@ HOOKS = {
     "pp_sam_stage_ms_": (_i, [_vp, _pf32]),         # float[5]
     "pp_fasta_stage_ms_": (_i, [_vp, _pf32]),       # float[4]
     "pp_fasta_geometry_": (None, [_pu32] * 3),
+    "pp_fasta_out_stage_ms_": (_i, [_vp, _pf32]),   # float[2]
+    "pp_fasta_out_geometry_": (None, [_pu32] * 2),
+    "pp_ctx_fasta_form_": (_i, [_vp, _P(C.c_int64), _P(_i)]),
+    "pp_ctx_set_fasta_out_name_": (_i, [_vp, _str]),
     "pp_bam_out_stage_ms_": (_i, [_vp, _pf32]),     # float[3]
     "pp_bgzf_out_stage_ms_": (_i, [_vp, _pf32]),    # float[3]
     "pp_sam_out_stage_ms_": (_i, [_vp, _pf32]),     # float[4]

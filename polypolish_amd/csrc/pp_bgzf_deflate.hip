@@ -32,6 +32,9 @@
 #include "pp_bgzf_host.h"
 #include "pp_crc.h"
 #include "pp_dev.h"
+#include "pp_fasta_out_host.h"
+
+#include <cstring>
 
 struct pp_bgzf_out : DevOwner {
     using DevOwner::DevOwner;
@@ -338,6 +341,26 @@ extern "C" int pp_bgzf_out_write(const pp_bgzf_out *o, const char *path) {
     if (!o || !o->ctx) return PP_ERR_ARG;
     if (!path) return o->ctx->fail(PP_ERR_ARG, "pp_bgzf_out_write: null argument");
     return pp::write_device_file(o->ctx, "pp_bgzf_out_write", o->d_out, o->n_out, path);
+}
+
+// the .gzi index of the file (pp_fasta_out_host.h: gzi): the blocks' offsets are downloaded, the pairs written on the host
+extern "C" int pp_bgzf_out_gzi(const pp_bgzf_out *z, pp_bytes *gzi) {
+    if (!z || !z->ctx) return PP_ERR_ARG;
+    pp_ctx *ctx = z->ctx;
+    if (!gzi) return ctx->fail(PP_ERR_ARG, "pp_bgzf_out_gzi: null argument");
+    static_assert(pp_fasta_out_host::GZI_PIECE == PAY, "the index counts the uncompressed bytes in the compressor's pieces");
+    gzi->data = nullptr;
+    gzi->len = 0;
+    PP_HIPCHK(ctx, hipSetDevice(ctx->device));
+    std::vector<uint64_t> off((size_t)z->n_blk + 1);
+    if (int rc = fetch(ctx, z->d_blk_off, off.data(), off.size())) return rc;
+    std::string s;
+    pp_fasta_out_host::gzi(off.data(), z->n_blk, s);
+    gzi->data = (uint8_t *)malloc(s.size() + 1);
+    if (!gzi->data) return ctx->fail(PP_ERR_HIP, "pp_bgzf_out_gzi: out of host memory");
+    memcpy(gzi->data, s.data(), s.size());
+    gzi->len = s.size();
+    return PP_OK;
 }
 
 extern "C" int pp_bgzf_deflate(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, int mem, pp_bgzf_out **out) {

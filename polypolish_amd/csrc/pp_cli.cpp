@@ -55,6 +55,10 @@ static const char *HELP_POLISH =
     "      --careful                              Ignore any reads with multiple alignments\n"
     "      --regroup                              BAM files whose reads do not stand together (coordinate-sorted): bring every read's alignments together first\n"
     "      --text_chain                           SAM text, plain or bgzipped, through the record chain on the device; --regroup then takes text as well (not in the reference)\n"
+    "      --out <PATH>                           Write the polished FASTA to PATH instead of stdout (not in the reference)\n"
+    "      --wrap <N>                             Line width of the polished FASTA, made on the device; 0: one line per contig (not in the reference)\n"
+    "      --out_bgzf                             Compress the polished FASTA into BGZF blocks on the device (not in the reference)\n"
+    "      --index                                With --out: write PATH.fai, and PATH.gzi with --out_bgzf (not in the reference)\n"
     "  -h, --help                                 Print help\n  -V, --version                              Print version\n";
 
 static const char *HELP_FUSED =
@@ -66,7 +70,11 @@ static const char *HELP_FUSED =
     "--regroup: coordinate-sorted BAM inputs (the polish brings every read's alignments together; the outputs keep file order).\n"
     "--out_bam: SAM text inputs with --out1/--out2: write the outputs as compressed BAM.\n"
     "--out_sam: BAM inputs with --out1/--out2: write the outputs as SAM text.\n"
-    "--text_chain: SAM text inputs, plain or bgzipped, through the record chain on the device; --regroup then takes text as well (not in the reference).\n";
+    "--text_chain: SAM text inputs, plain or bgzipped, through the record chain on the device; --regroup then takes text as well (not in the reference).\n"
+    "--out <PATH>: write the polished FASTA to PATH instead of stdout (not in the reference).\n"
+    "--wrap <N>: line width of the polished FASTA, made on the device; 0: one line per contig (not in the reference).\n"
+    "--out_bgzf: compress the polished FASTA into BGZF blocks on the device (not in the reference).\n"
+    "--index: with --out, write PATH.fai, and PATH.gzi with --out_bgzf (not in the reference).\n";
 
 static int usage_error(const char *msg) {
     fprintf(stderr, "error: %s\n\nFor more information, try '--help'.\n", msg);
@@ -176,6 +184,63 @@ static bool take_u32(const Parsed &P, const std::vector<OptSpec> &specs, size_t 
     return false;
 }
 
+// ---- the polished FASTA's form and place (not in the reference): --out, --wrap, --out_bgzf, --index ----
+struct FastaForm {
+    const char *out = nullptr;  // --out: the file instead of stdout
+    bool wrap = false, bgzf = false, index = false;
+    uint32_t width = 0;
+    bool any() const { return wrap || bgzf; }
+};
+// the four options at specs[k0 ..]; false + error text on a --wrap that is no number (take_u32's words) or above 2^31 - 1
+static bool take_fasta_form(const Parsed &P, const std::vector<OptSpec> &specs, size_t k0, FastaForm &F, std::string &err) {
+    F.out = P.value[k0];
+    F.wrap = P.value[k0 + 1] != nullptr;
+    F.bgzf = P.value[k0 + 2] != nullptr;
+    F.index = P.value[k0 + 3] != nullptr;
+    if (!take_u32(P, specs, k0 + 1, F.width, err)) return false;
+    if (F.width > 0x7FFFFFFFu) {
+        err = std::string("invalid value '") + P.value[k0 + 1] + "' for '" + opt_display(specs[k0 + 1]) + "': number too large to fit in target type";
+        return false;
+    }
+    return true;
+}
+static int refuse_index_without_out() {
+    fprintf(stderr, "\nError: --index needs --out <PATH>: the indexes are written next to the file (PATH.fai, PATH.gzi)\n");
+    return 1;
+}
+static bool write_file(const std::string &path, const uint8_t *data, uint64_t len) {
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const bool ok = (len == 0 || fwrite(data, 1, len, f) == len);
+    return (fclose(f) == 0) && ok;
+}
+// The FASTA of a command that succeeded: to --out (created only now; a failed run leaves nothing behind) or to stdout, the indexes
+// next to the file.  0, or 1 with the message on stderr.
+static int deliver_fasta(pp_ctx *ctx, const FastaForm &F, const pp_bytes &fasta) {
+    if (!F.out) {
+        fwrite(fasta.data, 1, fasta.len, stdout);
+        return 0;
+    }
+    bool ok = write_file(F.out, fasta.data, fasta.len);
+    if (ok && F.index) {
+        pp_bytes fai{nullptr, 0}, gzi{nullptr, 0};
+        ok = pp_ctx_fasta_index(ctx, &fai, &gzi) == PP_OK && write_file(std::string(F.out) + ".fai", fai.data, fai.len) &&
+             (!F.bgzf || write_file(std::string(F.out) + ".gzi", gzi.data, gzi.len));
+        if (!ok) { remove((std::string(F.out) + ".fai").c_str()); remove((std::string(F.out) + ".gzi").c_str()); }
+        pp_bytes_free(&fai);
+        pp_bytes_free(&gzi);
+    }
+    if (ok) return 0;
+    remove(F.out);
+    fprintf(stderr, "\nError: unable to write the polished sequence to \"%s\"\n", F.out);
+    return 1;
+}
+// the form on a context: --index alone still needs the text's table, so it takes the device link at width 0
+static void set_fasta_form(pp_ctx *ctx, const FastaForm &F) {
+    if (F.any() || F.index) pp_ctx_set_fasta_form(ctx, (int64_t)F.width, F.bgzf);
+    pp_ctx_set_fasta_out_name_(ctx, F.out);
+}
+
 static int no_device(int device) {
     fprintf(stderr, "\nError: no usable MI355X (HIP) device %d -- this build has no CPU path\n", device);
     return 1;
@@ -251,7 +316,12 @@ int main(int argc, char **argv) {
                                             {"--min_depth", 'd', true, "<MIN_DEPTH>"},
                                             {"--careful", 0, false, ""},
                                             {"--regroup", 0, false, ""},
-                                            {"--text_chain", 0, false, ""}};
+                                            {"--text_chain", 0, false, ""},
+                                            {"--out", 0, true, "<PATH>"},
+                                            {"--wrap", 0, true, "<N>"},
+                                            {"--out_bgzf", 0, false, ""},
+                                            {"--index", 0, false, ""}};
+        FastaForm form;
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help) { fputs(HELP_POLISH, stdout); return 0; }
         if (P.version) { printf("polypolish-polish v0.6.1\n"); return 0; }
@@ -262,9 +332,11 @@ int main(int argc, char **argv) {
             regroup = P.value[6] != nullptr;
             text_chain = P.value[7] != nullptr;
             (void)(take_f64(P, specs, 1, opt.fraction_invalid, perr) && take_f64(P, specs, 2, opt.fraction_valid, perr) &&
-                   take_u32(P, specs, 3, opt.max_errors, perr) && take_u32(P, specs, 4, opt.min_depth, perr));
+                   take_u32(P, specs, 3, opt.max_errors, perr) && take_u32(P, specs, 4, opt.min_depth, perr) &&
+                   take_fasta_form(P, specs, 8, form, perr));
         }
         if (!perr.empty()) return usage_error(perr.c_str());
+        if (form.index && !form.out) return refuse_index_without_out();
         const char *assembly = P.positional.empty() ? nullptr : P.positional[0];
         std::vector<const char *> sams(P.positional.begin() + (P.positional.empty() ? 0 : 1), P.positional.end());
         if (!assembly) return usage_error("the following required arguments were not provided:\n  <ASSEMBLY>");
@@ -293,6 +365,7 @@ int main(int argc, char **argv) {
             std::vector<pp_ctx *> cs(devs.size(), nullptr);
             for (size_t d = 0; d < devs.size(); d++)
                 if (pp_ctx_create_async(devs[d], &cs[d]) || pp_ctx_set_regroup(cs[d], regroup) || pp_ctx_set_text_chain(cs[d], text_chain)) return no_device(devs[d]);
+            set_fasta_form(cs[0], form);
             pp_bytes fasta{nullptr, 0};
             int rc = pp_polish_files_multi(cs.data(), (int)cs.size(), assembly, sams.data(), (int)sams.size(), &opt, &fasta);
             for (size_t d = 0; d < devs.size(); d++)
@@ -302,7 +375,7 @@ int main(int argc, char **argv) {
                 for (pp_ctx *c : cs) pp_ctx_destroy(c);
                 return rc == PP_ERR_PANIC ? 101 : 1;
             }
-            fwrite(fasta.data, 1, fasta.len, stdout);
+            if (deliver_fasta(cs[0], form, fasta)) return 1;
             return finish(0);
         }
         // the device initialises on a helper thread while the host loads and parses the inputs
@@ -311,6 +384,7 @@ int main(int argc, char **argv) {
         if (rc) return no_device(device);
         pp_ctx_set_regroup(ctx, regroup);
         pp_ctx_set_text_chain(ctx, text_chain);
+        set_fasta_form(ctx, form);
         pp_bytes fasta{nullptr, 0};
         rc = pp_polish_files(ctx, assembly, sams.data(), (int)sams.size(), &opt, &fasta);
         if (pp_ctx_wait(ctx) != PP_OK) return no_device(device);
@@ -319,7 +393,7 @@ int main(int argc, char **argv) {
             pp_ctx_destroy(ctx);
             return rc == PP_ERR_PANIC ? 101 : 1;
         }
-        fwrite(fasta.data, 1, fasta.len, stdout);
+        if (deliver_fasta(ctx, form, fasta)) return 1;
         return finish(0);
     }
 
@@ -340,7 +414,12 @@ int main(int argc, char **argv) {
                                             {"--regroup", 0, false, ""},
                                             {"--out_bam", 0, false, ""},
                                             {"--out_sam", 0, false, ""},
-                                            {"--text_chain", 0, false, ""}};
+                                            {"--text_chain", 0, false, ""},
+                                            {"--out", 0, true, "<PATH>"},
+                                            {"--wrap", 0, true, "<N>"},
+                                            {"--out_bgzf", 0, false, ""},
+                                            {"--index", 0, false, ""}};
+        FastaForm form;
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help || P.version) { fputs(HELP_FUSED, stdout); return 0; }
         std::string perr = P.error;
@@ -351,7 +430,8 @@ int main(int argc, char **argv) {
             regroup = P.value[13] != nullptr;
             (void)(take_f64(P, specs, 5, low, perr) && take_f64(P, specs, 6, high, perr) &&
                    take_f64(P, specs, 8, opt.fraction_invalid, perr) && take_f64(P, specs, 9, opt.fraction_valid, perr) &&
-                   take_u32(P, specs, 10, opt.max_errors, perr) && take_u32(P, specs, 11, opt.min_depth, perr));
+                   take_u32(P, specs, 10, opt.max_errors, perr) && take_u32(P, specs, 11, opt.min_depth, perr) &&
+                   take_fasta_form(P, specs, 17, form, perr));
             if (perr.empty() && P.positional.size() > 1) perr = std::string("unexpected argument '") + P.positional[1] + "' found";
         }
         if (!perr.empty()) return usage_error(perr.c_str());
@@ -359,6 +439,7 @@ int main(int argc, char **argv) {
         const char *assembly = P.positional.empty() ? nullptr : P.positional[0];
         if (!assembly || !in1 || !in2)
             return usage_error("the following required arguments were not provided:\n  --in1 <IN1> --in2 <IN2> <ASSEMBLY>");
+        if (form.index && !form.out) return refuse_index_without_out();
         pp_ctx *ctx = nullptr;
         int rc = pp_ctx_create_async(device, &ctx);
         if (rc) return no_device(device);
@@ -366,6 +447,7 @@ int main(int argc, char **argv) {
         pp_ctx_set_out_bam(ctx, P.value[14] != nullptr);
         pp_ctx_set_out_sam(ctx, P.value[15] != nullptr);
         pp_ctx_set_text_chain(ctx, P.value[16] != nullptr);
+        set_fasta_form(ctx, form);
         pp_bytes fasta{nullptr, 0};
         rc = pp_filter_polish_files(ctx, assembly, in1, in2, out1, out2, orientation, low, high, &opt, nullptr, &fasta);
         if (pp_ctx_wait(ctx) != PP_OK) return no_device(device);
@@ -374,7 +456,7 @@ int main(int argc, char **argv) {
             pp_ctx_destroy(ctx);
             return rc == PP_ERR_PANIC ? 101 : 1;
         }
-        fwrite(fasta.data, 1, fasta.len, stdout);
+        if (deliver_fasta(ctx, form, fasta)) return 1;
         return finish(0);
     }
 

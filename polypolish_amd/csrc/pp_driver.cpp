@@ -313,16 +313,32 @@ static int polish_on_one_context(PolishJob &J) {
     if (rc == PP_OK) rc = pp_polish_result_size(ctx, &J.total);
     // offsets and statistics now; the bytes go straight into the FASTA buffer below (contig by contig) when that is a
     // handful of copies, else through one copy of everything
-    J.direct_fetch = rc == PP_OK && J.fasta.buf && J.nc <= 256 && J.fasta.header_bytes + J.total + J.nc <= J.fasta.cap;
+    // (with pp_ctx_set_fasta_form the bytes stay on the device for pp_fasta_text)
+    J.direct_fetch = rc == PP_OK && (J.form_on || (J.fasta.buf && J.nc <= 256 && J.fasta.header_bytes + J.total + J.nc <= J.fasta.cap));
     if (!J.direct_fetch) J.polished.resize(J.total ? J.total : 1);
     if (rc == PP_OK) rc = pp_polish_result(ctx, J.direct_fetch ? nullptr : J.polished.data(), PP_MEM_HOST, J.out_off.data(), J.stats.data());
     return rc;
 }
 
+// print_polishing_info, polish.rs:206-227
+static void log_polishing_info(PolishJob &J, uint32_t c) {
+    const uint64_t *off = J.off;
+    const char *name = J.names[c];
+    const pp_contig_stats &s = J.stats[c];
+    const double len = (double)(off[c + 1] - off[c]);
+    const double changed_pct = 100.0 * (double)s.changed / len;
+    J.log("Polishing %s (%s bp):\n  mean read depth: %.1fx\n  %s bp %s a depth of zero (%.4f%% coverage)\n"
+          "  %s %s changed (%.4f%% of total positions)\n  estimated pre-polishing sequence accuracy: %.4f%% (%s)\n\n",
+          name, commas(off[c + 1] - off[c]).c_str(), s.depth_sum / len, commas(s.zero_depth).c_str(),
+          s.zero_depth == 1 ? "has" : "have", 100.0 * (len - (double)s.zero_depth) / len,
+          commas(s.changed).c_str(), s.changed == 1 ? "position" : "positions", changed_pct,
+          100.0 - changed_pct, qscore(100.0 - changed_pct).c_str());
+}
+
 // print_seq_to_stdout (polish.rs:196-203), one contig after the other in FASTA order, with print_polishing_info's lines
 static int write_fasta_and_log(PolishJob &J, pp_bytes *fasta) {
     const uint32_t nc = J.nc;
-    const uint64_t *off = J.off, *out_off = J.out_off.data();
+    const uint64_t *out_off = J.out_off.data();
     J.fasta.join();
     if (!J.fasta.buf || J.fasta.header_bytes + J.total + nc > J.fasta.cap) {  // (a job whose polished bytes outgrow the bound: a buffer of the exact size)
         free(J.fasta.buf);
@@ -346,16 +362,7 @@ static int write_fasta_and_log(PolishJob &J, pp_bytes *fasta) {
         } else memcpy(out + w, J.polished.data() + out_off[c], out_off[c + 1] - out_off[c]);
         w += out_off[c + 1] - out_off[c];
         out[w++] = '\n';
-        // print_polishing_info, polish.rs:206-227
-        const pp_contig_stats &s = J.stats[c];
-        const double len = (double)(off[c + 1] - off[c]);
-        const double changed_pct = 100.0 * (double)s.changed / len;
-        J.log("Polishing %s (%s bp):\n  mean read depth: %.1fx\n  %s bp %s a depth of zero (%.4f%% coverage)\n"
-              "  %s %s changed (%.4f%% of total positions)\n  estimated pre-polishing sequence accuracy: %.4f%% (%s)\n\n",
-              name, commas(off[c + 1] - off[c]).c_str(), s.depth_sum / len, commas(s.zero_depth).c_str(),
-              s.zero_depth == 1 ? "has" : "have", 100.0 * (len - (double)s.zero_depth) / len,
-              commas(s.changed).c_str(), s.changed == 1 ? "position" : "positions", changed_pct,
-              100.0 - changed_pct, qscore(100.0 - changed_pct).c_str());
+        log_polishing_info(J, c);
     }
     fasta->data = out;
     fasta->len = w;
@@ -364,9 +371,62 @@ static int write_fasta_and_log(PolishJob &J, pp_bytes *fasta) {
     return PP_OK;
 }
 
+// The same FASTA in the form pp_ctx_set_fasta_form chose, made on the device: the headers go up, pp_fasta_text writes the text at the
+// line width from the polished bytes where they lie -- in device memory on one context, in the host bytes the ranks' results were
+// assembled into on several --, pp_bgzf_deflate follows on the device bytes, and what is returned comes off the device in one copy.
+// The indexes stay with the context (pp_ctx_fasta_index).  The log's lines are write_fasta_and_log's.
+static int write_fasta_form_and_log(PolishJob &J, pp_bytes *fasta) {
+    const uint32_t nc = J.nc;
+    pp_ctx *const ctx = J.ctx;
+    std::string headers;
+    std::vector<uint64_t> header_off(nc + 1, 0);
+    for (uint32_t c = 0; c < nc; c++) {
+        const char *desc = pp_assembly_description(J.a, c);
+        headers += J.names[c];
+        if (desc[0]) { headers += ' '; headers += desc; }
+        headers += " polypolish";
+        header_off[c + 1] = headers.size();
+    }
+    const bool on_device = J.direct_fetch;
+    const uint8_t *src = on_device ? pp_polish_result_device(ctx) : J.polished.data();
+    pp_fasta_out *text = nullptr;
+    pp_bgzf_out *z = nullptr;
+    pp_bytes fai{nullptr, 0}, gzi{nullptr, 0};
+    const uint8_t *dev = nullptr;
+    uint64_t n = 0;
+    int rc = pp_fasta_text(ctx, src, on_device ? PP_MEM_DEVICE : PP_MEM_HOST, nc, J.out_off.data(), (const uint8_t *)headers.data(), header_off.data(),
+                           (uint32_t)J.form_width, &text);
+    if (rc == PP_OK) rc = pp_fasta_out_fai(text, &fai);
+    if (rc == PP_OK) pp_fasta_out_bytes(text, &dev, &n);
+    if (rc == PP_OK && J.form_bgzf) {
+        rc = pp_bgzf_deflate(ctx, dev, n, PP_MEM_DEVICE, &z);
+        if (rc == PP_OK) rc = pp_bgzf_out_gzi(z, &gzi);
+        if (rc == PP_OK) pp_bgzf_out_bytes(z, &dev, &n);
+    }
+    uint8_t *out = rc == PP_OK ? (uint8_t *)malloc((size_t)n + 1) : nullptr;
+    if (rc == PP_OK && !out) rc = set_err(ctx, PP_ERR_HIP, "out of host memory for the FASTA");
+    if (rc == PP_OK && n) rc = pp_ctx_download(ctx, out, dev, n);
+    if (rc == PP_OK) pp_ctx_keep_fasta_index_(ctx, fai.data, fai.len, gzi.data, gzi.len);
+    pp_bytes_free(&fai);
+    pp_bytes_free(&gzi);
+    pp_bgzf_out_free(z);
+    pp_fasta_out_free(text);
+    if (rc) {
+        free(out);
+        return rc;
+    }
+    for (uint32_t c = 0; c < nc; c++) log_polishing_info(J, c);
+    fasta->data = out;
+    fasta->len = n;
+    J.lap(J.form_bgzf ? "FASTA text made and compressed on the device" : "FASTA text made on the device");
+    return PP_OK;
+}
+
 // finished_message, polish.rs:76-90
 static void log_finished(const PolishJob &J) {
-    J.log("Finished!\nPolished sequence (to stdout):\n");
+    const char *to = pp_ctx_fasta_out_name_(J.ctx);
+    if (to[0]) J.log("Finished!\nPolished sequence (to %s):\n", to);
+    else J.log("Finished!\nPolished sequence (to stdout):\n");
     for (uint32_t c = 0; c < J.nc; c++) J.log("  %s_polypolish (%s bp)\n", J.names[c], commas(J.stats[c].polished_len).c_str());
     J.log("\nTime to run: %s\n\n", format_duration(J.lap.seconds()).c_str());
 }
@@ -379,14 +439,15 @@ static int polish_once(PolishJob &J, pp_bytes *fasta) {
     J.lap("driver entered");
     if (int rc = load_assembly(J)) return rc;
     J.lap("assembly loaded");
-    reserve_fasta(J);
+    J.form_on = pp_ctx_fasta_form_(J.ctx, &J.form_width, &J.form_bgzf) != 0;
+    if (!J.form_on) reserve_fasta(J);  // (the form's text is made on the device)
     if (int rc = load_alignments(J)) return rc;
     // polish_sequences, polish.rs:137-154 -- on the device
     J.log("Polishing assembly sequences\n");
     if (int rc = create_debug_file(J)) return rc;
     if (int rc = several_contexts(J.route) ? polish_on_several_contexts(J) : polish_on_one_context(J)) return rc;
     J.lap(J.direct_fetch ? "result: offsets fetched" : "result fetched");
-    if (int rc = write_fasta_and_log(J, fasta)) return rc;
+    if (int rc = J.form_on ? write_fasta_form_and_log(J, fasta) : write_fasta_and_log(J, fasta)) return rc;
     log_finished(J);
     J.release();
     J.lap("device and host buffers released");

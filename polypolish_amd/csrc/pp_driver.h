@@ -150,6 +150,9 @@ struct PolishJob {
     bool debug_set = false;  // pp_polish_set_debug was called on the contexts
     uint64_t total = 0;
     bool direct_fetch = false;
+    bool form_on = false;  // pp_ctx_set_fasta_form: the FASTA is made by pp_fasta_text (write_fasta_form_and_log), at this width ...
+    int64_t form_width = -1;
+    int form_bgzf = 0;     // ... and compressed by pp_bgzf_deflate
     std::vector<uint8_t> polished = std::vector<uint8_t>(1);
     std::vector<uint64_t> out_off;
     std::vector<pp_contig_stats> stats;

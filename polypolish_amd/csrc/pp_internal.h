@@ -270,6 +270,12 @@ struct pp_ctx {
     bool out_sam = false;  // pp_ctx_set_out_sam: the filter drivers write BAM inputs back as SAM text
     bool regroup = false;  // pp_ctx_set_regroup: the file drivers regroup every BAM file's records in front of the gate
     bool text_chain = false;  // pp_ctx_set_text_chain: the file drivers take SAM text through the record chain (pp_sam_records)
+    // pp_ctx_set_fasta_form: the file drivers return the polished FASTA through pp_fasta_text (fasta_width >= 0) and pp_bgzf_deflate
+    int64_t fasta_width = -1;
+    bool fasta_bgzf = false;
+    bool fasta_indexed = false;         // a driver has made such a text: fasta_fai / fasta_gzi are its indexes (pp_ctx_fasta_index)
+    std::string fasta_fai, fasta_gzi;
+    std::string fasta_out_name;         // pp_ctx_set_fasta_out_name_: where the caller will write the FASTA (the log's last section names it)
     pp::DevBuf f_thr;  // pp_filter_thresholds: orientation counts | the selection's state | its two histograms (THR_WORDS u32)
     pp_filter_input fdev{};
     const uint64_t *f_refend_ptr[2] = {nullptr, nullptr};

@@ -151,9 +151,17 @@ def main(argv=None):
     ap.add_argument("--careful", action="store_true")
     ap.add_argument("--debug", default=None)
     ap.add_argument("--text_chain", action="store_true")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--wrap", default=None)
+    ap.add_argument("--out_bgzf", action="store_true")
+    ap.add_argument("--index", action="store_true")
     ap.add_argument("assembly")
     ap.add_argument("sam", nargs="*")
     a = ap.parse_args(argv)
+    for flag, given in (("--out", a.out is not None), ("--wrap", a.wrap is not None), ("--out_bgzf", a.out_bgzf), ("--index", a.index)):
+        if given:    # (rank 0 writes the FASTA here as the ranks' bytes arrive; the device link makes it on one context)
+            raise SystemExit(f"Error: {flag} is not available here: rank 0 writes the FASTA itself; polish with `polypolish polish {flag}`, "
+                             f"which also runs on several GPUs (PP_GPUS)")
     if a.text_chain:    # (one context per command, as for BAM)
         raise SystemExit("Error: SAM text on the record chain (--text_chain) runs on one GPU: polish it with `polypolish polish --text_chain`, "
                          "or without --text_chain")
