@@ -599,11 +599,58 @@ void pp_sam_free(pp_sam *s);
 typedef struct pp_bam_out pp_bam_out;
 int pp_bam_tagged(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, uint64_t records_at, const uint64_t *rec_off, uint64_t n_rec,
                   int mem, const uint8_t *pass, uint64_t n_pass, pp_bam_out **out, uint64_t *bad_record);
+/* pp_bam_tagged with a header of the caller's: the stream starts with head[0, n_head) (HOST memory whatever `mem`; n_head == 0: with
+ * the first record) instead of bytes[0, records_at).  Everything else -- the records, the verdicts, the file, the validation, the
+ * refusals with records_at > n_bytes among them, the edge cases -- is pp_bam_tagged's contract word for word; also PP_ERR_ARG: head ==
+ * NULL with n_head > 0; PP_ERR_LIMIT: n_head >= 2^40.  With rec_off = pp_bam_sorted_rec_off, pass = what pp_bam_sorted_pass gives and
+ * head = pp_bam_sorted_head this call and pp_bam_out_deflate write the coordinate-sorted file without another pass over the records. */
+int pp_bam_tagged_head(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, uint64_t records_at, const uint64_t *rec_off, uint64_t n_rec,
+                       int mem, const uint8_t *pass, uint64_t n_pass, const uint8_t *head, uint64_t n_head, pp_bam_out **out,
+                       uint64_t *bad_record);
 void pp_bam_out_bytes(const pp_bam_out *o, const uint8_t **dev, uint64_t *n_bytes); /* DEVICE, borrowed until pp_bam_out_free */
 void pp_bam_out_counts(const pp_bam_out *o, uint64_t *pass_count, uint64_t *fail_count, uint64_t *n_blocks); /* n_blocks without the EOF block */
 int pp_bam_out_write(const pp_bam_out *o, const char *path); /* download in slices, write the file */
 int pp_bam_out_kernel_ms(const pp_bam_out *o, float *ms);
 void pp_bam_out_free(pp_bam_out *o);
+
+/* The COORDINATE ORDER of BAM records, on the device: what a caller needs to write pp_bam_tagged's file sorted (pp_bam_tagged_head).
+ *   inputs       bytes, n_bytes, records_at, rec_off, n_rec, mem: as pp_bam_tagged takes them; the records need not be adjacent, ordered
+ *                or distinct.  bytes[0, records_at) must be a BAM header (pp_bam_header) that ends at records_at; with PP_MEM_DEVICE
+ *                the library downloads it.
+ *   the key      64 bits per record.  High word: ref_id where it is >= 0, else 0xFFFFFFFF: unplaced records come last.  Low word:
+ *                (uint32_t)(pos + 1) << 1 | ((flag >> 4) & 1), in 32 bits: pos == 2^31 - 1 loses its top bit and sorts in front of
+ *                its reference (no reference is that long; it is not refused).  perm is the STABLE order of the indices by that key:
+ *                reference id, position, reverse strand, input order -- this library's reading of `samtools sort`'s coordinate
+ *                order, not compared with samtools.  pp_bam_sorted_perm[j] = the input record at place j; pp_bam_sorted_rec_off[j] =
+ *                rec_off[perm[j]].  Two calls give identical bytes, and sorting what is sorted moves nothing.
+ *   the header   pp_bam_sorted_head: bytes[0, records_at) with the first line of its text made to say SO:coordinate.  The text is
+ *                what stands in front of its trailing NULs.  A first line "@HD" (alone, or followed by a tab) has its first SO: field
+ *                replaced, or "\tSO:coordinate" appended where it has none; any other first line, and no text, gets
+ *                "@HD\tVN:1.6\tSO:coordinate\n" in front.  l_text is adjusted; the trailing NULs and the reference table are
+ *                kept byte for byte.  HOST memory of the object.
+ *   validation   the header first: what pp_bam_header refuses is refused with its code and words, a header that ends elsewhere than at
+ *                records_at with PP_ERR_ARG, a text that would pass 2^31 - 1 bytes with PP_ERR_LIMIT.  Then the records, on the
+ *                device before a field is read and with no sum that could wrap; no byte outside [0, n_bytes) is loaded, by a wide
+ *                load either.  PP_ERR_ARG with *bad_record (may be NULL) = the first such record in index order, and no object:
+ *                pp_bam_walk's three verdicts as pp_bam_tagged has them; pos < -1; ref_id < -1 or >= the header's n_ref.  Also
+ *                PP_ERR_ARG: records_at > n_bytes, null arguments, PP_MEM_PEER.  PP_ERR_LIMIT: 2^32-1 or more records, n_bytes >= 2^40.
+ *   edge cases   n_rec == 0 yields an empty permutation and the rewritten header.
+ *   pp_bam_sorted_counts     the places j with perm[j] != j, and the records with ref_id == -1
+ *   pp_bam_sorted_pass       as pp_regrouped_pass: pass (HOST, one byte per ALIGNED record of the input in index order) -> out (HOST,
+ *                            n_pass bytes, may be `pass` only where nothing moved), the same verdicts in the numbering of the
+ *                            sorted records; n_pass other than the number of aligned records: PP_ERR_ARG
+ *   pp_bam_sorted_kernel_ms  as pp_gated_kernel_ms
+ * The context's stream has been synchronised when the call returns.  The object belongs to its context and is freed before it. */
+typedef struct pp_bam_sorted pp_bam_sorted;
+int pp_bam_sort(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, uint64_t records_at, const uint64_t *rec_off, uint64_t n_rec,
+                int mem, pp_bam_sorted **out, uint64_t *bad_record);
+const uint32_t *pp_bam_sorted_perm(const pp_bam_sorted *s); /* DEVICE, n_rec entries */
+const uint64_t *pp_bam_sorted_rec_off(const pp_bam_sorted *s); /* DEVICE, n_rec entries: rec_off[perm[j]] */
+void pp_bam_sorted_head(const pp_bam_sorted *s, const uint8_t **head, uint64_t *n_head); /* HOST, borrowed until pp_bam_sorted_free */
+void pp_bam_sorted_counts(const pp_bam_sorted *s, uint64_t *n_moved, uint64_t *n_unplaced);
+int pp_bam_sorted_pass(const pp_bam_sorted *s, const uint8_t *pass, uint64_t n_pass, uint8_t *out); /* HOST arrays */
+int pp_bam_sorted_kernel_ms(const pp_bam_sorted *s, float *ms);
+void pp_bam_sorted_free(pp_bam_sorted *s);
 
 /* The COMPRESSOR of the record chain: bytes in device memory compressed into BGZF blocks, on the device.  pp_bam_tagged's level-0 file
  * is 4.6 times the size of the BAM file that came in; pp_bam_out_deflate makes the same file compressed.  pp_bam_tagged's own bytes
@@ -1236,6 +1283,32 @@ int pp_fasta_out_kernel_ms(const pp_fasta_out *o, float *ms);
 void pp_fasta_out_free(pp_fasta_out *o);
 int pp_bgzf_out_gzi(const pp_bgzf_out *z, pp_bytes *gzi); /* the .gzi of any pp_bgzf_out, HOST */
 
+/* The .bai of the file that pp_bam_tagged_head (or pp_bam_tagged, with n_head = records_at) makes of the same bytes, rec_off, mem and
+ * pass, made on the device; the records must stand in coordinate order (pp_bam_sorted_rec_off, pp_bam_sorted_pass).
+ *   offsets      record r starts in the stream at n_head + the sum over q < r of 4 + block_size_q + 8 fail_q; a stream offset u is the
+ *                virtual offset blk_off[u / 65,280] << 16 | u % 65,280.  blk_off[0, n_blk] (n_blk + 1 entries, HOST or DEVICE by
+ *                blk_mem): pp_bgzf_out_blk_off for the compressed file, b * 65,311 for the level-0 file; n_blk must be the stream's
+ *                number of blocks.  A record's end at a multiple of 65,280 is the start of the next block, offset 0: a reader's tell.
+ *   per record   beg = pos, end = pos + the lengths of its M D N = X runs, pos + 1 where that is 0 or the record is unmapped but
+ *                placed; bin = reg2bin(beg, end) of the SAM specification, section 5.3.
+ *   chunks       one per maximal run of consecutive records with one (ref_id, bin), from its first record's start to its last
+ *                record's end; a bin's chunks in file order, a reference's bins in ascending number.  No merging of small bins into
+ *                parents or of neighbouring chunks: a valid BAI, not `samtools index`'s bytes.
+ *   linear       ioffset[w] = the smallest start of a record overlapping window w (16,384 bases); n_intv = the last touched window
+ *                + 1; an untouched window takes the value of the next touched one.
+ *   pseudo-bin   37450 for every reference with records: {first record's start, last record's end}, {mapped, unmapped}; a
+ *                reference without records has n_bin = 0, n_intv = 0.  The trailing n_no_coor counts the records with ref_id == -1.
+ *   refusals     PP_ERR_ARG with *bad_record = the first such record in index order: pp_bam_tagged's three; a CIGAR that runs past
+ *                its block_size; then (n_pass first, as pp_bam_tagged) ref_id outside [-1, n_ref), ref_id >= 0 with pos < 0, a
+ *                record in front of its predecessor by (unsigned ref_id, pos; unplaced records are in order whatever their pos).
+ *                PP_ERR_LIMIT: end > 2^29 (*bad_record; BAI holds positions below 2^29, CSI is not written), a blk_off >= 2^48,
+ *                pp_bam_tagged's limits, more than 2^24 references, more than 2^27 windows in the linear index.  Also PP_ERR_ARG:
+ *                null arguments, PP_MEM_PEER, n_blk other than the stream's blocks.
+ * *bai is HOST memory: release with pp_bytes_free.  tests/bam_sort_model.py defines the bytes. */
+int pp_bam_index(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, uint64_t n_head, const uint64_t *rec_off, uint64_t n_rec,
+                 int mem, const uint8_t *pass, uint64_t n_pass, uint32_t n_ref,
+                 const uint64_t *blk_off, uint64_t n_blk, int blk_mem, pp_bytes *bai, uint64_t *bad_record);
+
 /* Coordinate-sorted BAM for the file drivers below (the commands' --regroup): with `on` != 0, pp_polish_files and the polish half of
  * pp_filter_polish_files put pp_batch_regroup between the decode and the gate of every BAM file, so that a read's records count as
  * one read wherever they lie in the file (the filter joins them already, and writes in file order).  The state lives on the
@@ -1280,6 +1353,18 @@ int pp_ctx_set_out_sam(pp_ctx *ctx, int on);
  * Off when the context is made and off by default in the commands: the fused routes are the measured default, and what they refuse
  * is pinned by tests. */
 int pp_ctx_set_text_chain(pp_ctx *ctx, int on);
+
+/* Sorted, indexed BAM from the filter drivers below (the commands' --sort_out and --out_bai): with `on` != 0 every BAM output of
+ * pp_filter_files and pp_filter_polish_files -- BAM inputs, or SAM text inputs with pp_ctx_set_out_bam -- is written in coordinate
+ * order behind the header that says SO:coordinate (pp_bam_sort -> pp_bam_sorted_pass -> pp_bam_tagged_head -> pp_bam_out_deflate), and
+ * with `index` != 0 "<output>.bai" (pp_bam_index) next to each.  Both files and both indexes are complete before any output is
+ * created: a record that the sort or the index refuses ("--sort_out: ..." with the input's path and the record, PP_ERR_QUIT) leaves
+ * nothing behind.  That holds for refusals only: the four files are then written one after the other, and a write that fails
+ * (PP_ERR_QUIT "unable to write alignments to ...") leaves the files written before it on disk.  The log and, for pp_filter_polish_files, the FASTA are the plain run's: the polish half takes the records it holds,
+ * whatever the order of the outputs.  Outputs that are SAM text -- the text routes without pp_ctx_set_out_bam, BAM inputs with
+ * pp_ctx_set_out_sam -- are refused by name (PP_ERR_QUIT) before an input is read.  index != 0 with on == 0: PP_ERR_ARG.  Off by
+ * default: without it the drivers run the code they ran. */
+int pp_ctx_set_sort_out(pp_ctx *ctx, int on, int index);
 
 /* The form of the polished FASTA that the file drivers below return (the commands' --wrap, --out_bgzf, --out, --index; not in the
  * reference): with width >= 0 the pp_bytes of pp_polish_files, pp_polish_files_multi and pp_filter_polish_files are made by

@@ -1102,6 +1102,7 @@ class BamTagged(_Owned):
       records_at     where the header ends (bam_header(...)["records_at"])
       passed         None or one byte per ALIGNED record (host): the filter's own verdict, filter_records(...)["pass"][f] -- not ANDed
                      with BamRecords.zp
+      head           None, or bytes (host): pp_bam_tagged_head -- the stream starts with them instead of data[0, records_at)
       .n_bytes, .bytes_ptr   the file: Bgzf(ctx, (t.bytes_ptr, t.n_bytes), (blk_off_ptr, n_blocks), mem=MEM_DEVICE) with blk_off[b] =
                      b * 65,311 reads it back
       .counts        (passed, failed, blocks without the EOF block)
@@ -1112,14 +1113,18 @@ class BamTagged(_Owned):
     A failing call raises PolypolishError with .bad_record."""
     _free, _kernel_ms = "pp_bam_out_free", "pp_bam_out_kernel_ms"
 
-    def __init__(self, ctx, data, records_at, rec_off, passed, mem=MEM_HOST):
+    def __init__(self, ctx, data, records_at, rec_off, passed, mem=MEM_HOST, head=None):
         L = lib()
         bp, n_bytes, op, n, _keep = _bytes_and_offsets(data, rec_off, mem)
         v = None if passed is None else np.ascontiguousarray(passed, dtype=np.uint8)
         super().__init__(ctx)
         bad = _no_index()
-        rc = L.pp_bam_tagged(ctx._h, bp, n_bytes, int(records_at), op, n, mem, v.ctypes.data if v is not None else None,
-                             len(v) if v is not None else 0, C.byref(self._p), C.byref(bad))
+        args = (ctx._h, bp, n_bytes, int(records_at), op, n, mem, v.ctypes.data if v is not None else None, len(v) if v is not None else 0)
+        if head is None:
+            rc = L.pp_bam_tagged(*args, C.byref(self._p), C.byref(bad))
+        else:
+            h = _bam_bytes(head)
+            rc = L.pp_bam_tagged_head(*args, h.ctypes.data if len(h) else None, len(h), C.byref(self._p), C.byref(bad))
         if rc:
             _raise(rc, L.pp_last_error(ctx._h).decode(), bad_record=_index(bad))
         dev, nb = C.c_void_p(), C.c_uint64(0)
@@ -1142,6 +1147,92 @@ class BamTagged(_Owned):
 
     def deflate(self):
         return BgzfDeflated(self._ctx, tagged=self)
+
+
+class BamSorted(_Owned):
+    """pp_bam_sort: the coordinate order of BAM records -- reference id, position, reverse strand, input order -- in DEVICE memory,
+    owned by this object.  data, records_at, rec_off and mem as BamTagged takes them.
+      .n_rec
+      .perm()              np.uint32: sorted record j is input record perm[j]; .perm_ptr its device address
+      .rec_off()           np.uint64: rec_off[perm[j]]; .rec_off_ptr its device address -- (s.rec_off_ptr, s.n_rec) is the rec_off of
+                           BamTagged(..., mem=MEM_DEVICE, head=s.head)
+      .head                bytes: the header with its first text line made to say SO:coordinate
+      .counts()            (records that changed place, records with ref_id == -1)
+      .carry_pass(passed)  one byte per ALIGNED input record -> the same verdicts in the numbering of the sorted records
+      .kernel_ms()         HIP-event time of the kernels (the context had set_profiling on); .stage_ms(): keys | sort | gather
+    A failing call raises PolypolishError with .bad_record."""
+    _free, _kernel_ms = "pp_bam_sorted_free", "pp_bam_sorted_kernel_ms"
+
+    def __init__(self, ctx, data, records_at, rec_off, mem=MEM_HOST):
+        L = lib()
+        bp, n_bytes, op, n, _keep = _bytes_and_offsets(data, rec_off, mem)
+        super().__init__(ctx)
+        bad = _no_index()
+        rc = L.pp_bam_sort(ctx._h, bp, n_bytes, int(records_at), op, n, mem, C.byref(self._p), C.byref(bad))
+        if rc:
+            _raise(rc, L.pp_last_error(ctx._h).decode(), bad_record=_index(bad))
+        self.n_rec = n
+        self.perm_ptr, self.rec_off_ptr = L.pp_bam_sorted_perm(self._p) or 0, L.pp_bam_sorted_rec_off(self._p) or 0
+        hp, hn = C.c_void_p(), C.c_uint64(0)
+        L.pp_bam_sorted_head(self._p, C.byref(hp), C.byref(hn))
+        self.head = _host(hp.value, int(hn.value), np.uint8).tobytes()
+
+    def perm(self):
+        return self._ctx.download(self.perm_ptr, self.n_rec, np.uint32)
+
+    def rec_off(self):
+        return self._ctx.download(self.rec_off_ptr, self.n_rec, np.uint64)
+
+    def counts(self):
+        m, u = C.c_uint64(0), C.c_uint64(0)
+        lib().pp_bam_sorted_counts(self._p, C.byref(m), C.byref(u))
+        return int(m.value), int(u.value)
+
+    def carry_pass(self, passed):
+        v = np.ascontiguousarray(passed, dtype=np.uint8)
+        out = np.zeros(max(len(v), 1), dtype=np.uint8)
+        self._ctx._chk(lib().pp_bam_sorted_pass(self._p, v.ctypes.data if len(v) else None, len(v), out.ctypes.data))
+        return out[:len(v)]
+
+    def stage_ms(self):
+        return self._stage_ms("pp_bam_sorted_stage_ms_", ("keys", "sort", "gather"), " when the records were sorted")
+
+
+class BamIndex(_Owned):
+    """pp_bam_index: the .bai of the file BamTagged(ctx, data, ..., rec_off, passed, mem, head=...) makes, made on the device.
+      data, rec_off, passed, mem   as BamTagged takes them; the records in coordinate order (BamSorted.rec_off_ptr, .carry_pass)
+      n_head         the header's length in the stream (len(head); records_at for a BamTagged without head)
+      n_ref          the header's references
+      blk_off        the file's n_blocks + 1 block offsets: a host array, or (device address, n_blocks) -- BgzfDeflated.blk_off_ptr
+      .bytes         the index
+    A failing call raises PolypolishError with .bad_record.  (The object owns nothing once it is made: close() does nothing.)"""
+
+    def __init__(self, ctx, data, n_head, rec_off, passed, n_ref, blk_off, mem=MEM_HOST):
+        L = lib()
+        bp, n_bytes, op, n, _keep = _bytes_and_offsets(data, rec_off, mem)
+        v = None if passed is None else np.ascontiguousarray(passed, dtype=np.uint8)
+        if isinstance(blk_off, tuple):
+            kp, n_blk, blk_mem, _kb = int(blk_off[0]), int(blk_off[1]), MEM_DEVICE, None
+        else:
+            _kb = np.ascontiguousarray(blk_off, dtype=np.uint64)
+            kp, n_blk, blk_mem = _kb.ctypes.data, len(_kb) - 1, MEM_HOST
+        super().__init__(ctx)
+        out, bad = Bytes(), _no_index()
+        rc = L.pp_bam_index(ctx._h, bp, n_bytes, int(n_head), op, n, mem, v.ctypes.data if v is not None else None, len(v) if v is not None else 0,
+                            int(n_ref), kp, n_blk, blk_mem, C.byref(out), C.byref(bad))
+        if rc:
+            _raise(rc, L.pp_last_error(ctx._h).decode(), bad_record=_index(bad))
+        self.bytes = _take_bytes(out)
+
+    def close(self):
+        pass
+
+    def stage_ms(self):
+        """scans | records | chunks | linear of the context's LAST pp_bam_index (the context had set_profiling on)"""
+        ms = (C.c_float * 4)()
+        if lib().pp_bam_index_stage_ms_(self._ctx._h, ms):
+            raise PolypolishError(ERR_ARG, "the context had no profiling on when the records were indexed")
+        return {k: float(v) for k, v in zip(("scans", "records", "chunks", "linear"), ms)}
 
 
 class BgzfDeflated(_Owned):
@@ -1848,6 +1939,22 @@ class Context:
         finally:
             self.set_out_bam(False)
 
+    def set_sort_out(self, on=True, index=False):
+        """pp_ctx_set_sort_out: the filter commands write their BAM outputs in coordinate order, with index a .bai next to each"""
+        self._chk(lib().pp_ctx_set_sort_out(self._h, int(bool(on)), int(bool(index))))
+
+    @contextlib.contextmanager
+    def _sorting_out(self, sort_out, out_bai):
+        """sort_out / out_bai switch pp_ctx_set_sort_out on for one command and off again behind it"""
+        if not sort_out and not out_bai:
+            yield
+            return
+        self.set_sort_out(sort_out, out_bai)
+        try:
+            yield
+        finally:
+            self.set_sort_out(False, False)
+
     @contextlib.contextmanager
     def _writing_sam(self, out_sam):
         """out_sam=True switches pp_ctx_set_out_sam on for one command and off again behind it"""
@@ -1882,18 +1989,19 @@ class Context:
     def filter_polish_files(self, assembly, in1, in2, out1=None, out2=None, orientation="auto", low=0.1, high=99.9,
                             fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5, careful=False,
                             debug=None, quiet=True, regroup=False, out_bam=False, out_sam=False, text_chain=False, wrap=None,
-                            bgzf=False, out=None, index=False):
+                            bgzf=False, out=None, index=False, sort_out=False, out_bai=False):
         """filter + polish in one process (pp_filter_polish_files): returns (FASTA bytes, filter report).  wrap / bgzf / out / index:
         as polish_files.  Two BAM inputs are decoded
         once for both halves; out1 / out2 are then BAM files as well.  regroup: for this call, as set_regroup (the polish half).
         out_bam: for this call, as set_out_bam (SAM text inputs, out1 / out2 as compressed BAM).  out_sam: for this call, as
-        set_out_sam (BAM inputs, out1 / out2 as SAM text).  text_chain: for this call, as set_text_chain."""
+        set_out_sam (BAM inputs, out1 / out2 as SAM text).  text_chain: for this call, as set_text_chain.  sort_out / out_bai: for
+        this call, as set_sort_out (BAM outputs in coordinate order, out1.bai / out2.bai next to them)."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         rep, res = FilterReport(), Bytes()
         enc = lambda x: str(x).encode() if x is not None else None
         with self._regrouping(regroup), self._writing_bam(out_bam), self._writing_sam(out_sam), self._chaining_text(text_chain), \
-                self._fasta_form(wrap, bgzf, out, index) as deliver:
+                self._sorting_out(sort_out, out_bai), self._fasta_form(wrap, bgzf, out, index) as deliver:
             self._chk(lib().pp_filter_polish_files(self._h, enc(assembly), enc(in1), enc(in2), enc(out1), enc(out2),
                                                    orientation.encode(), low, high, C.byref(opt), C.byref(rep), C.byref(res)))
             data = _take_bytes(res)
@@ -1901,14 +2009,15 @@ class Context:
         return data, _report_dict(rep)
 
     def filter_files(self, in1, in2, out1, out2, orientation="auto", low=0.1, high=99.9, quiet=True, out_bam=False, out_sam=False,
-                     text_chain=False):
+                     text_chain=False, sort_out=False, out_bai=False):
         """filter::filter (pp_filter_files): writes out1 / out2, returns the report.  in1 / in2 are both SAM text, or both BAM:
         BAM in gives compressed BAM out (pp_bam_tagged -> pp_bam_out_deflate).  out_bam: for this call, as set_out_bam (SAM text
         in, compressed BAM out through pp_sam_bam).  out_sam: for this call, as set_out_sam (BAM in, SAM text out through
         pp_bam_sam).  text_chain: for this call, as set_text_chain (SAM text, plain or bgzipped, through the record chain; bgzipped
-        in gives bgzipped out)."""
+        in gives bgzipped out).  sort_out / out_bai: for this call, as set_sort_out (BAM outputs in coordinate order, out1.bai /
+        out2.bai next to them; SAM text outputs are refused)."""
         rep = FilterReport()
-        with self._writing_bam(out_bam), self._writing_sam(out_sam), self._chaining_text(text_chain):
+        with self._writing_bam(out_bam), self._writing_sam(out_sam), self._chaining_text(text_chain), self._sorting_out(sort_out, out_bai):
             self._chk(lib().pp_filter_files(self._h, str(in1).encode(), str(in2).encode(), str(out1).encode(),
                                             str(out2).encode(), orientation.encode(), low, high, int(quiet),
                                             C.byref(rep)))

@@ -165,11 +165,20 @@ SIGNATURES = {
     "pp_sam_kernel_ms": (_i, [_vp, _pf32]),
     "pp_sam_free": (None, [_vp]),
         "pp_bam_tagged": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _i, _vp, _u64, _pvp, _pu64]),
+    "pp_bam_tagged_head": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _i, _vp, _u64, _vp, _u64, _pvp, _pu64]),
     "pp_bam_out_bytes": (None, [_vp, _pvp, _pu64]),
     "pp_bam_out_counts": (None, [_vp, _pu64, _pu64, _pu64]),
     "pp_bam_out_write": (_i, [_vp, _str]),
     "pp_bam_out_kernel_ms": (_i, [_vp, _pf32]),
     "pp_bam_out_free": (None, [_vp]),
+    "pp_bam_sort": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _i, _pvp, _pu64]),
+    "pp_bam_sorted_perm": (_vp, [_vp]),
+    "pp_bam_sorted_rec_off": (_vp, [_vp]),
+    "pp_bam_sorted_head": (None, [_vp, _pvp, _pu64]),
+    "pp_bam_sorted_counts": (None, [_vp, _pu64, _pu64]),
+    "pp_bam_sorted_pass": (_i, [_vp, _vp, _u64, _vp]),
+    "pp_bam_sorted_kernel_ms": (_i, [_vp, _pf32]),
+    "pp_bam_sorted_free": (None, [_vp]),
     "pp_bgzf_deflate": (_i, [_vp, _vp, _u64, _i, _pvp]),
     "pp_bam_out_deflate": (_i, [_vp, _vp, _pvp]),
     "pp_bgzf_out_bytes": (None, [_vp, _pvp, _pu64]),
@@ -271,10 +280,12 @@ SIGNATURES = {
     "pp_fasta_out_kernel_ms": (_i, [_vp, _pf32]),
     "pp_fasta_out_free": (None, [_vp]),
     "pp_bgzf_out_gzi": (_i, [_vp, _P(Bytes)]),
+    "pp_bam_index": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _i, _vp, _u64, _u32, _vp, _u64, _i, _P(Bytes), _pu64]),
     "pp_ctx_set_regroup": (_i, [_vp, _i]),
     "pp_ctx_set_out_bam": (_i, [_vp, _i]),
     "pp_ctx_set_out_sam": (_i, [_vp, _i]),
     "pp_ctx_set_text_chain": (_i, [_vp, _i]),
+    "pp_ctx_set_sort_out": (_i, [_vp, _i, _i]),
     "pp_ctx_set_fasta_form": (_i, [_vp, C.c_int64, _i]),
     "pp_ctx_fasta_index": (_i, [_vp, _P(Bytes), _P(Bytes)]),
     "pp_polish_files": (_i, [_vp, _str, _P(_str), _i, _P(PolishOptions), _P(Bytes)]),
@@ -312,6 +323,8 @@ HOOKS = {
     "pp_ctx_fasta_form_": (_i, [_vp, _P(C.c_int64), _P(_i)]),
     "pp_ctx_set_fasta_out_name_": (_i, [_vp, _str]),
     "pp_bam_out_stage_ms_": (_i, [_vp, _pf32]),     # float[3]
+    "pp_bam_sorted_stage_ms_": (_i, [_vp, _pf32]),  # float[3]
+    "pp_bam_index_stage_ms_": (_i, [_vp, _pf32]),   # float[4]
     "pp_bgzf_out_stage_ms_": (_i, [_vp, _pf32]),    # float[3]
     "pp_sam_out_stage_ms_": (_i, [_vp, _pf32]),     # float[4]
     "pp_sam_out_geometry_": (None, [_pu32] * 3),

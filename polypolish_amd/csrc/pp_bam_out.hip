@@ -3,6 +3,9 @@
 // record it makes what `polypolish filter` makes of SAM text (filter_sam, src/filter.rs:296-343) -- every record again, ZP:Z:fail
 // appended to the aligned ones that failed -- framed as level-0 BGZF, as bytes in device memory; pp_bam_out_write puts them on disk.
 //
+// pp_bam_tagged_head is the same call with a header of the caller's (HOST bytes, uploaded) as source 0 of the stream in the place of
+// bytes[0, records_at): one host function behind both symbols, one more pointer in the framing kernel's arguments.
+//
 // The uncompressed output U' is bytes[0, records_at), then per record r in index order its 4 + block_size bytes; a failing record has
 // block_size + 8 in its first word and the eight bytes Z P Z f a i l NUL behind its last.  The file is U' cut every 65,280 bytes,
 // each piece one BGZF block around one stored DEFLATE block (pp_bgzf_host.h: len + 31 bytes, block b at b * 65,311), then the EOF block.
@@ -31,9 +34,11 @@
 // No byte outside [0, n_bytes) is loaded: a wide load is issued only inside a record that pass A found inside the array, or inside
 // the header (records_at <= n_bytes).
 #include "pp_bam_host.h"
+#include "pp_bam_index_host.h"
 #include "pp_bgzf_host.h"
 #include "pp_crc.h"
 #include "pp_dev.h"
+#include "pp_rg_sort.h"
 
 #include <fcntl.h>
 #include <unistd.h>
@@ -153,6 +158,8 @@ __device__ __forceinline__ void load16(const u8 *__restrict__ B, u64 N, u64 at, 
 struct FrameArgs {
     const u8 *bytes;
     u64 n_bytes;
+    const u8 *head;    // source 0, the header: `bytes` itself (pp_bam_tagged) or the caller's header (pp_bam_tagged_head) ...
+    u64 n_head_cap;    // ... and the bytes that may be loaded from it
     const u64 *rec_off;
     const u64 *start;  // n_rec + 2 entries
     u32 n_rec;
@@ -244,7 +251,7 @@ __global__ __launch_bounds__(TAG_BLOCK, 8) void k_tag_frame(FrameArgs A) {
         for (u32 s = 0; s < 2u; s++) {
             const u64 R = Ra + s, S = Sx[s], a = max(u0, S), z = min(u1, Sx[s + 1u]);
             if (R > A.n_rec || a >= z) continue;
-            if (R == 0) load16(B, A.n_bytes, a, (u32)(z - a), &v_lo[s], &v_hi[s]);  // the header: its bytes are where they were
+            if (R == 0) load16(A.head, A.n_head_cap, a, (u32)(z - a), &v_lo[s], &v_hi[s]);  // the header: its bytes are where they were
             else {
                 bsx[s] = ld32(B, ox[s]);
                 const u64 from = ox[s] + (max(a, S + 4u) - S);  // (behind the record's bytes where the piece holds only appended ones)
@@ -300,7 +307,10 @@ __global__ __launch_bounds__(TAG_BLOCK, 8) void k_tag_frame(FrameArgs A) {
 #pragma unroll
     for (u32 j = 0; j < TRIPS; j++) {
         P[j] = Piece16{0, 0};
-        if ((fast >> j) & 1u) load16(B, A.n_bytes, o[j] + at[j], 16, &P[j].lo, &P[j].hi);
+        if ((fast >> j) & 1u) {
+            const bool rec = (in_rec >> j) & 1u;
+            load16(rec ? B : A.head, rec ? A.n_bytes : A.n_head_cap, o[j] + at[j], 16, &P[j].lo, &P[j].hi);
+        }
     }
 #pragma unroll
     for (u32 j = 0; j < TRIPS; j++) {
@@ -412,19 +422,24 @@ extern "C" int pp_bam_out_write(const pp_bam_out *o, const char *path) {
     return pp::write_device_file(o->ctx, "pp_bam_out_write", o->d_out, o->n_out, path);
 }
 
-extern "C" int pp_bam_tagged(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, uint64_t records_at, const uint64_t *rec_off, uint64_t n_rec,
-                             int mem, const uint8_t *pass, uint64_t n_pass, pp_bam_out **out, uint64_t *bad_record) {
+namespace {
+
+// pp_bam_tagged (the stream starts with bytes[0, records_at)) and pp_bam_tagged_head (with_head: it starts with the HOST bytes
+// head[0, n_head)): `who` words the refusals, which are the same
+int tagged(pp_ctx *ctx, const char *who, const uint8_t *bytes, uint64_t n_bytes, uint64_t records_at, const uint64_t *rec_off, uint64_t n_rec,
+           int mem, const uint8_t *pass, uint64_t n_pass, const uint8_t *head, uint64_t n_head, bool with_head, pp_bam_out **out, uint64_t *bad_record) {
     if (!ctx) return PP_ERR_ARG;
     if (int rdy = pp_ctx_wait(ctx)) return rdy;
     if (bad_record) *bad_record = ~0ull;
-    if (!out) return ctx->fail(PP_ERR_ARG, "pp_bam_tagged: null argument");
+    if (!out) return ctx->fail(PP_ERR_ARG, "%s: null argument", who);
     *out = nullptr;
     if (mem != PP_MEM_HOST && mem != PP_MEM_DEVICE)
-        return ctx->fail(PP_ERR_ARG, "pp_bam_tagged: the bytes must be host memory or memory of the context's device");
-    if ((n_bytes && !bytes) || (n_rec && !rec_off)) return ctx->fail(PP_ERR_ARG, "pp_bam_tagged: null bytes with n_bytes > 0, or null rec_off with n_rec > 0");
-    if (records_at > n_bytes) return ctx->fail(PP_ERR_ARG, "pp_bam_tagged: records_at %llu lies behind the %llu bytes", (unsigned long long)records_at, (unsigned long long)n_bytes);
+        return ctx->fail(PP_ERR_ARG, "%s: the bytes must be host memory or memory of the context's device", who);
+    if ((n_bytes && !bytes) || (n_rec && !rec_off)) return ctx->fail(PP_ERR_ARG, "%s: null bytes with n_bytes > 0, or null rec_off with n_rec > 0", who);
+    if (with_head && n_head && !head) return ctx->fail(PP_ERR_ARG, "%s: null head with n_head > 0", who);
+    if (records_at > n_bytes) return ctx->fail(PP_ERR_ARG, "%s: records_at %llu lies behind the %llu bytes", who, (unsigned long long)records_at, (unsigned long long)n_bytes);
     if (n_rec >= 0xFFFFFFFFull) return ctx->fail(PP_ERR_LIMIT, "more than 2^32-1 alignments in one batch");
-    if (n_bytes >= (1ull << 40)) return ctx->fail(PP_ERR_LIMIT, "pp_bam_tagged: 2^40 or more bytes in one call");
+    if (n_bytes >= (1ull << 40) || n_head >= (1ull << 40)) return ctx->fail(PP_ERR_LIMIT, "%s: 2^40 or more bytes in one call", who);
     PP_HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const u32 n = (u32)n_rec;
@@ -437,6 +452,12 @@ extern "C" int pp_bam_tagged(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes
     const u64 *d_rec_off = nullptr;
     if ((rc = on_device(ctx, T, mem, (const u8 *)bytes, (size_t)n_bytes, &d_bytes)) || (rc = on_device(ctx, T, mem, (const u64 *)rec_off, (size_t)n, &d_rec_off)))
         return rc;
+    const u8 *d_head = d_bytes;               // source 0 of the stream: the bytes' own header ...
+    u64 head_len = records_at, head_cap = n_bytes;
+    if (with_head) {                          // ... or the caller's
+        if ((rc = on_device(ctx, T, PP_MEM_HOST, (const u8 *)head, (size_t)n_head, &d_head))) return rc;
+        head_len = head_cap = n_head;
+    }
     const u32 nb = std::max(1u, (n + TAG_BLOCK - 1u) / TAG_BLOCK);
     void *d_aligned, *d_blk_al, *d_al_base, *d_blk2, *d_blk2off, *d_start, *d_status, *d_pass;
     if ((rc = T.get(ctx, &d_aligned, (size_t)n)) || (rc = T.get(ctx, &d_blk_al, (size_t)nb * 8)) || (rc = T.get(ctx, &d_al_base, ((size_t)nb + 1) * 8)) ||
@@ -445,7 +466,7 @@ extern "C" int pp_bam_tagged(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes
         return rc;
 
     // ---- pass A: the ranges, the aligned records ----
-    u64 n_al = 0, u_total = records_at, n_fail = 0;
+    u64 n_al = 0, u_total = head_len, n_fail = 0;
     if (n) {
         PP_HIPCHK(ctx, hipMemsetAsync(d_status, 0xFF, 16, st));
         if ((rc = timer.begin(0))) return rc;
@@ -460,18 +481,18 @@ extern "C" int pp_bam_tagged(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes
             const u64 r = status[0] >> 8;
             const u32 kind = (u32)(status[0] & 0xFFu);
             if (bad_record) *bad_record = r;
-            return ctx->fail(PP_ERR_ARG, "pp_bam_tagged: record %llu %s", (unsigned long long)r,
+            return ctx->fail(PP_ERR_ARG, "%s: record %llu %s", who, (unsigned long long)r,
                              kind == pp_bam_host::W_CUT ? "has an offset outside the bytes, or the bytes end inside its block_size"
                              : kind == pp_bam_host::W_SMALL ? "has a block_size below the 32 bytes of its fixed part" : "runs past the end of the bytes");
         }
         if (status[1] != ~0ull) {
             if (bad_record) *bad_record = status[1] >> 8;
-            return ctx->fail(PP_ERR_LIMIT, "pp_bam_tagged: record %llu has a block_size above 0xFFFFFFF7", (unsigned long long)(status[1] >> 8));
+            return ctx->fail(PP_ERR_LIMIT, "%s: record %llu has a block_size above 0xFFFFFFF7", who, (unsigned long long)(status[1] >> 8));
         }
     }
-    if (n_al && !pass) return ctx->fail(PP_ERR_ARG, "pp_bam_tagged: null pass with %llu aligned records", (unsigned long long)n_al);
+    if (n_al && !pass) return ctx->fail(PP_ERR_ARG, "%s: null pass with %llu aligned records", who, (unsigned long long)n_al);
     if (n_pass != n_al)
-        return ctx->fail(PP_ERR_ARG, "pp_bam_tagged: %llu verdicts for %llu aligned records", (unsigned long long)n_pass, (unsigned long long)n_al);
+        return ctx->fail(PP_ERR_ARG, "%s: %llu verdicts for %llu aligned records", who, (unsigned long long)n_pass, (unsigned long long)n_al);
 
     // ---- the verdicts (host memory whatever `mem`), the lengths, the starts ----
     if ((rc = T.get(ctx, &d_pass, (size_t)n_al))) return rc;
@@ -479,18 +500,18 @@ extern "C" int pp_bam_tagged(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes
     if (n) {
         if ((rc = timer.begin(1))) return rc;
         hipLaunchKernelGGL(k_tag_len<false>, dim3(nb), dim3(TAG_BLOCK), 0, st, n, d_bytes, d_rec_off, (const u8 *)d_aligned, (const u64 *)d_al_base,
-                           (const u8 *)d_pass, (u64)records_at, (u64 *)d_blk2, (u64 *)nullptr);
+                           (const u8 *)d_pass, head_len, (u64 *)d_blk2, (u64 *)nullptr);
         hipLaunchKernelGGL(k_colscan<2>, dim3(1), dim3(1024), 0, st, (const u64 *)d_blk2, (u64)nb, (u64 *)d_blk2off);
         hipLaunchKernelGGL(k_tag_len<true>, dim3(nb), dim3(TAG_BLOCK), 0, st, n, d_bytes, d_rec_off, (const u8 *)d_aligned, (const u64 *)d_al_base,
-                           (const u8 *)d_pass, (u64)records_at, (u64 *)d_blk2off, (u64 *)d_start);
+                           (const u8 *)d_pass, head_len, (u64 *)d_blk2off, (u64 *)d_start);
         if ((rc = timer.end())) return rc;
         PP_HIPCHK(ctx, hipGetLastError());
         u64 totals[2] = {0, 0};
         if ((rc = fetch(ctx, (const u64 *)d_blk2off + 2ull * nb, totals, 2))) return rc;
-        u_total = records_at + 4ull * n + totals[0];
+        u_total = head_len + 4ull * n + totals[0];
         n_fail = totals[1];
     } else {  // the header alone
-        const u64 two[2] = {0, records_at};
+        const u64 two[2] = {0, head_len};
         PP_HIPCHK(ctx, hipMemcpyAsync(d_start, two, sizeof two, hipMemcpyHostToDevice, st));
         PP_HIPCHK(ctx, hipStreamSynchronize(st));
     }
@@ -504,11 +525,432 @@ extern "C" int pp_bam_tagged(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes
     if ((rc = P->alloc(P->d_out, (size_t)P->n_out))) return rc;
     if ((rc = timer.begin(2))) return rc;
     hipLaunchKernelGGL(k_tag_frame, dim3((unsigned)(n_blocks + 1u)), dim3(TAG_BLOCK), 0, st,
-                       FrameArgs{d_bytes, (u64)n_bytes, d_rec_off, (const u64 *)d_start, n, u_total, n_blocks, (u8 *)P->d_out});
+                       FrameArgs{d_bytes, (u64)n_bytes, d_head, head_cap, d_rec_off, (const u64 *)d_start, n, u_total, n_blocks, (u8 *)P->d_out});
     if ((rc = timer.end())) return rc;
     PP_HIPCHK(ctx, hipGetLastError());
     PP_HIPCHK(ctx, hipStreamSynchronize(st));  // host inputs may be released, the scratch goes away
     if ((rc = P->t.take(timer))) return rc;
     *out = P.release();
+    return PP_OK;
+}
+
+}  // namespace
+
+extern "C" int pp_bam_tagged(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, uint64_t records_at, const uint64_t *rec_off, uint64_t n_rec,
+                             int mem, const uint8_t *pass, uint64_t n_pass, pp_bam_out **out, uint64_t *bad_record) {
+    return tagged(ctx, "pp_bam_tagged", bytes, n_bytes, records_at, rec_off, n_rec, mem, pass, n_pass, nullptr, 0, false, out, bad_record);
+}
+
+extern "C" int pp_bam_tagged_head(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, uint64_t records_at, const uint64_t *rec_off, uint64_t n_rec,
+                                  int mem, const uint8_t *pass, uint64_t n_pass, const uint8_t *head, uint64_t n_head, pp_bam_out **out,
+                                  uint64_t *bad_record) {
+    return tagged(ctx, "pp_bam_tagged_head", bytes, n_bytes, records_at, rec_off, n_rec, mem, pass, n_pass, head, n_head, true, out, bad_record);
+}
+
+// ---- pp_bam_index: the .bai of the file pp_bam_tagged_head makes of the same arguments -----------------------------------------------
+// The records' places in the stream are pass A and the scans above (start[]); a stream offset u is the virtual offset
+// blk_off[u / 65,280] << 16 | u % 65,280.  Then one lane per record:
+//   k_ix_rec     ref_id, pos, flag and the reference span of the CIGAR (M D N = X), read inside the record pass A found inside the
+//                array; a CIGAR that leaves its record is refused before a run is read
+//   k_ix_check   ref_id against n_ref, a placed record's pos, the order against the record in front, end against 2^29; the bin.  The
+//                first offender in index order by atomicMin
+//   k_ix_run     a record starts a chunk where (ref_id, bin) changes; the scan of these flags numbers the chunks
+//   k_ix_chunk   a chunk's key ref_id << 32 | bin, its first record's start and its last record's end
+//   k_ix_ref     per reference: the windows it touches (atomicMax), its first record's start and last record's end, mapped and
+//                unmapped records; the unplaced records
+//   k_ix_lin     the window minima (64-bit atomicMin; a long record loops over its windows); k_ix_fill: the fill from the right
+//   k_rg_hist / k_rg_scatter (pp_rg_sort.h)  the chunk table brought into (ref_id, bin) order, stable: a bin's chunks in file order
+// The host (pp_bam_index_host.h) writes the downloaded tables out.
+namespace {
+
+enum : u32 { IX_CIGAR = 8, IX_REF = 9, IX_PLACED = 10, IX_ORDER = 11, IX_END = 12 };
+constexpr u32 IX_MAX_END = 1u << 29;
+constexpr u64 IX_MAX_WINDOWS = 1ull << 27;  // 1 GiB of linear index
+constexpr u32 IX_MAX_REF = 1u << 24;
+
+enum : int { IX_SCANS = 0, IX_RECORDS = 1, IX_CHUNKS = 2, IX_LINEAR = 3 };
+
+struct IxRec { int32_t ref, pos; u32 end; };
+
+__global__ __launch_bounds__(256) void k_ix_rec(u32 n, const u8 *__restrict__ B, const u64 *__restrict__ rec_off, IxRec *__restrict__ rec,
+                                                uint16_t *__restrict__ flag, u64 *__restrict__ status) {
+    const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (r >= n) return;
+    const u64 o = rec_off[r];  // (pass A: the 4 + block_size >= 36 bytes from o on lie inside the array)
+    const u32 bs = ld32(B, o);
+    const int32_t ref = (int32_t)ld32(B, o + 4u), pos = (int32_t)ld32(B, o + 8u);
+    const u32 l_name = B[o + 12u], n_cig = (u32)B[o + 16u] | (u32)B[o + 17u] << 8, f = (u32)B[o + 18u] | (u32)B[o + 19u] << 8;
+    u64 span = 0;
+    if (32ull + l_name + 4ull * n_cig > bs) report(status, (r << 8) | IX_CIGAR);
+    else
+        for (u32 i = 0; i < n_cig; i++) {
+            const u32 w = ld32(B, o + 36u + l_name + 4ull * i), op = w & 15u;
+            if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) span += w >> 4;
+        }
+    const u64 e = (u64)(pos > 0 ? pos : 0) + ((span && !(f & 4u)) ? span : 1ull);
+    rec[r] = IxRec{ref, pos, (u32)min(e, (u64)0xFFFFFFFFu)};
+    flag[r] = (uint16_t)f;
+}
+
+__device__ __forceinline__ u32 reg2bin(u32 beg, u32 end) {  // the SAM specification, section 5.3
+    --end;
+    if (beg >> 14 == end >> 14) return 4681u + (beg >> 14);
+    if (beg >> 17 == end >> 17) return 585u + (beg >> 17);
+    if (beg >> 20 == end >> 20) return 73u + (beg >> 20);
+    if (beg >> 23 == end >> 23) return 9u + (beg >> 23);
+    if (beg >> 26 == end >> 26) return 1u + (beg >> 26);
+    return 0u;
+}
+
+__device__ __forceinline__ u64 ix_key(const IxRec &R) { return (u64)(u32)R.ref << 32 | (u64)(R.ref < 0 ? 0u : (u32)R.pos); }
+
+__global__ __launch_bounds__(256) void k_ix_check(u32 n, const IxRec *__restrict__ rec, u32 n_ref, u32 *__restrict__ bin, u64 *__restrict__ status) {
+    const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (r >= n) return;
+    const IxRec R = rec[r];
+    u32 kind = 0;
+    if (R.ref < -1 || (R.ref >= 0 && (u32)R.ref >= n_ref)) kind = IX_REF;
+    else if (R.ref >= 0 && R.pos < 0) kind = IX_PLACED;
+    else if (r > 0 && ix_key(R) < ix_key(rec[r - 1u])) kind = IX_ORDER;
+    else if (R.ref >= 0 && R.end > IX_MAX_END) kind = IX_END;
+    if (kind) report(status, (r << 8) | kind);
+    bin[r] = (!kind && R.ref >= 0) ? reg2bin((u32)R.pos, R.end) : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_ix_blk(u64 n, const u64 *__restrict__ blk_off, u64 *__restrict__ status) {
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (i < n && blk_off[i] >= pp_bam_index_host::MAX_COFFSET) report(status, i);
+}
+
+__global__ __launch_bounds__(256) void k_ix_run(u32 n, const IxRec *__restrict__ rec, const u32 *__restrict__ bin, u32 *__restrict__ head) {
+    const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (r >= n) return;
+    const int32_t ref = rec[r].ref;
+    head[r] = (ref >= 0 && (r == 0 || rec[r - 1u].ref != ref || bin[r - 1u] != bin[r])) ? 1u : 0u;
+}
+
+struct IxWhere {  // where the records stand in the file
+    const u64 *start;    // n + 2: start[r + 1] = record r's stream offset
+    const u64 *blk_off;  // n_blk + 1
+    __device__ __forceinline__ u64 at(u64 u) const { return blk_off[u / PAY] << 16 | (u % PAY); }
+};
+
+__global__ __launch_bounds__(256) void k_ix_chunk(u32 n, const IxRec *__restrict__ rec, const u32 *__restrict__ bin, const u32 *__restrict__ head,
+                                                  const u32 *__restrict__ cidx, IxWhere W, u64 *__restrict__ key, u64 *__restrict__ beg, u64 *__restrict__ end) {
+    const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (r >= n || rec[r].ref < 0) return;
+    const u32 c = cidx[r] + head[r] - 1u;  // (a placed record stands in or behind a run's first record)
+    if (head[r]) {
+        key[c] = (u64)(u32)rec[r].ref << 32 | bin[r];
+        beg[c] = W.at(W.start[r + 1u]);
+    }
+    if (r + 1u == n || head[r + 1u] || rec[r + 1u].ref < 0) end[c] = W.at(W.start[r + 2u]);
+}
+
+// The records stand in coordinate order, so a wave almost always holds one reference: its lanes' counts and window maximum then meet
+// in the wave (ballots, a shuffle maximum) and its first lane issues one atomic per word; a wave over a seam between two references
+// or with unplaced records falls back to one atomic per lane.  All of it is commutative: the bytes do not depend on the path.
+__global__ __launch_bounds__(256) void k_ix_ref(u32 n, const IxRec *__restrict__ rec, const uint16_t *__restrict__ flag, IxWhere W, u32 *__restrict__ n_intv,
+                                                u64 *__restrict__ ref_beg, u64 *__restrict__ ref_end, u64 *__restrict__ mapped, u64 *__restrict__ unmapped,
+                                                u64 *__restrict__ no_coor) {
+    const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+    const bool in = r < n;
+    const IxRec R = in ? rec[r] : IxRec{-1, 0, 1u};
+    const bool placed = in && R.ref >= 0, un = in && (flag[r] & 4u);
+    const u32 windows = placed ? ((R.end - 1u) >> 14) + 1u : 0u;
+    const u64 live = __ballot(in), m_placed = __ballot(placed);
+    const int32_t first = __shfl(R.ref, live ? (int)__builtin_ctzll(live) : 0, 64);
+    const bool one = live != 0 && m_placed == live && __ballot(in && R.ref == first) == live;  // (the same for every lane of the wave)
+    if (one) {
+        u32 w = windows;
+        for (int o = 32; o > 0; o >>= 1) w = max(w, (u32)__shfl_xor((int)w, o, 64));
+        const u64 m_un = __ballot(un);
+        if ((threadIdx.x & 63u) == (u32)__builtin_ctzll(live)) {
+            atomicMax(&n_intv[first], w);
+            const u64 k_un = (u64)__popcll(m_un), k_map = (u64)__popcll(live) - k_un;
+            if (k_map) atomicAdd(&mapped[first], k_map);
+            if (k_un) atomicAdd(&unmapped[first], k_un);
+        }
+    } else if (placed) {
+        atomicMax(&n_intv[R.ref], windows);
+        atomicAdd(un ? &unmapped[R.ref] : &mapped[R.ref], 1ull);
+    } else if (in) atomicAdd(no_coor, 1ull);
+    if (!placed) return;
+    if (r == 0 || rec[r - 1u].ref != R.ref) ref_beg[R.ref] = W.at(W.start[r + 1u]);
+    if (r + 1u == n || rec[r + 1u].ref != R.ref) ref_end[R.ref] = W.at(W.start[r + 2u]);
+}
+
+__global__ __launch_bounds__(256) void k_ix_lin(u32 n, const IxRec *__restrict__ rec, IxWhere W, const u64 *__restrict__ lin_off, u64 *__restrict__ lin) {
+    const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (r >= n || rec[r].ref < 0) return;
+    const IxRec R = rec[r];
+    const u64 v = W.at(W.start[r + 1u]), base = lin_off[R.ref];
+    // The records stand in (reference, position) order and their starts grow with r: a window that the record in front reaches too
+    // has a smaller start from it (or from one further in front), so only the windows behind that record's last one are this
+    // record's to write -- about one atomic per window and not one per record.  (The minimum stays: a record may reach further
+    // than a later one.)
+    u32 w = (u32)R.pos >> 14;
+    if (r > 0) {
+        const IxRec P = rec[r - 1u];
+        if (P.ref == R.ref) w = max(w, ((P.end - 1u) >> 14) + 1u);
+    }
+    for (; w <= (R.end - 1u) >> 14; w++) atomicMin(&lin[base + w], v);  // (w < n_intv[ref]: k_ix_ref took the maximum)
+}
+
+__global__ __launch_bounds__(256) void k_ix_fill(u32 n_ref, const u64 *__restrict__ lin_off, u64 *__restrict__ lin) {
+    const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (r >= n_ref) return;
+    u64 next = 0;
+    for (u64 w = lin_off[r + 1u]; w > lin_off[r]; w--) {  // from the right: an untouched window takes the next touched one's
+        const u64 v = lin[w - 1u];
+        if (v == ~0ull) lin[w - 1u] = next;
+        else next = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ix_gather(u32 n, const u32 *__restrict__ perm, const u64 *__restrict__ a, const u64 *__restrict__ b, u64 *__restrict__ oa,
+                                                   u64 *__restrict__ ob) {
+    const u64 j = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (j >= n) return;
+    const u32 p = perm[j];
+    oa[j] = a[p];
+    ob[j] = b[p];
+}
+
+}  // namespace
+
+extern "C" int pp_bam_index(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, uint64_t n_head, const uint64_t *rec_off, uint64_t n_rec, int mem,
+                            const uint8_t *pass, uint64_t n_pass, uint32_t n_ref, const uint64_t *blk_off, uint64_t n_blk, int blk_mem, pp_bytes *bai,
+                            uint64_t *bad_record) {
+    if (!ctx) return PP_ERR_ARG;
+    if (int rdy = pp_ctx_wait(ctx)) return rdy;
+    if (bad_record) *bad_record = ~0ull;
+    if (!bai) return ctx->fail(PP_ERR_ARG, "pp_bam_index: null argument");
+    bai->data = nullptr;
+    bai->len = 0;
+    if ((mem != PP_MEM_HOST && mem != PP_MEM_DEVICE) || (blk_mem != PP_MEM_HOST && blk_mem != PP_MEM_DEVICE))
+        return ctx->fail(PP_ERR_ARG, "pp_bam_index: the bytes and the block offsets must be host memory or memory of the context's device");
+    if ((n_bytes && !bytes) || (n_rec && !rec_off) || !blk_off) return ctx->fail(PP_ERR_ARG, "pp_bam_index: null bytes, rec_off or blk_off");
+    if (n_rec >= 0xFFFFFFFFull) return ctx->fail(PP_ERR_LIMIT, "more than 2^32-1 alignments in one batch");
+    if (n_bytes >= (1ull << 40) || n_head >= (1ull << 40)) return ctx->fail(PP_ERR_LIMIT, "pp_bam_index: 2^40 or more bytes in one call");
+    if (n_ref > IX_MAX_REF) return ctx->fail(PP_ERR_LIMIT, "pp_bam_index: more than 2^24 references");
+    if (n_blk >= (1ull << 32)) return ctx->fail(PP_ERR_LIMIT, "pp_bam_index: 2^32 or more blocks");
+    PP_HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const u32 n = (u32)n_rec;
+    CallScratch T;
+    CtxScratch S(ctx, ctx->g_rec, "pp_bam_index");  // (scan_u32's block sums)
+    StageTimer timer(ctx, ctx->profiling != 0);     // scans | records | chunks | linear (pp_bam_index_stage_ms_)
+    ctx->ix_timed = false;
+    int rc;
+    const u8 *d_bytes = nullptr;
+    const u64 *d_rec_off = nullptr, *d_blk = nullptr;
+    if ((rc = on_device(ctx, T, mem, (const u8 *)bytes, (size_t)n_bytes, &d_bytes)) || (rc = on_device(ctx, T, mem, (const u64 *)rec_off, (size_t)n, &d_rec_off)) ||
+        (rc = on_device(ctx, T, blk_mem, (const u64 *)blk_off, (size_t)n_blk + 1, &d_blk)))
+        return rc;
+    const u32 nb = std::max(1u, (n + TAG_BLOCK - 1u) / TAG_BLOCK);
+    const unsigned gb = std::max(1u, (unsigned)(((u64)n + 255u) / 256u));
+    void *d_aligned, *d_blk_al, *d_al_base, *d_blk2, *d_blk2off, *d_start, *d_status, *d_pass, *d_rec, *d_flag, *d_bin, *d_st2;
+    if ((rc = T.get(ctx, &d_aligned, (size_t)n)) || (rc = T.get(ctx, &d_blk_al, (size_t)nb * 8)) || (rc = T.get(ctx, &d_al_base, ((size_t)nb + 1) * 8)) ||
+        (rc = T.get(ctx, &d_blk2, (size_t)nb * 16)) || (rc = T.get(ctx, &d_blk2off, ((size_t)nb + 1) * 16)) || (rc = T.get(ctx, &d_start, ((size_t)n + 2) * 8)) ||
+        (rc = T.get(ctx, &d_status, 16)) || (rc = T.get(ctx, &d_rec, (size_t)n * sizeof(IxRec))) || (rc = T.get(ctx, &d_flag, (size_t)n * 2)) ||
+        (rc = T.get(ctx, &d_bin, (size_t)n * 4)) || (rc = T.get(ctx, &d_st2, 32)))
+        return rc;
+    PP_HIPCHK(ctx, hipMemsetAsync(d_status, 0xFF, 16, st));
+    PP_HIPCHK(ctx, hipMemsetAsync(d_st2, 0xFF, 32, st));
+
+    // ---- pass A and the scans, as pp_bam_tagged_head makes them: the records' ranges, the aligned records, start[] ----
+    u64 n_al = 0, u_total = n_head;
+    if (n) {
+        if ((rc = timer.begin(IX_SCANS))) return rc;
+        hipLaunchKernelGGL(k_tag_scan, dim3(nb), dim3(TAG_BLOCK), 0, st, n, d_bytes, (u64)n_bytes, d_rec_off, (u8 *)d_aligned, (u64 *)d_blk_al, (u64 *)d_status);
+        hipLaunchKernelGGL(k_colscan<1>, dim3(1), dim3(1024), 0, st, (const u64 *)d_blk_al, (u64)nb, (u64 *)d_al_base);
+        if ((rc = timer.end())) return rc;
+        PP_HIPCHK(ctx, hipGetLastError());
+        u64 status[2] = {~0ull, ~0ull};
+        if ((rc = fetch(ctx, d_status, status, 2)) || (rc = fetch(ctx, (const u64 *)d_al_base + nb, &n_al))) return rc;
+        if (status[0] != ~0ull) {
+            const u64 r = status[0] >> 8;
+            const u32 kind = (u32)(status[0] & 0xFFu);
+            if (bad_record) *bad_record = r;
+            return ctx->fail(PP_ERR_ARG, "pp_bam_index: record %llu %s", (unsigned long long)r,
+                             kind == pp_bam_host::W_CUT ? "has an offset outside the bytes, or the bytes end inside its block_size"
+                             : kind == pp_bam_host::W_SMALL ? "has a block_size below the 32 bytes of its fixed part" : "runs past the end of the bytes");
+        }
+        if (status[1] != ~0ull) {
+            if (bad_record) *bad_record = status[1] >> 8;
+            return ctx->fail(PP_ERR_LIMIT, "pp_bam_index: record %llu has a block_size above 0xFFFFFFF7", (unsigned long long)(status[1] >> 8));
+        }
+        if ((rc = timer.begin(IX_RECORDS))) return rc;
+        hipLaunchKernelGGL(k_ix_rec, dim3(gb), dim3(256), 0, st, n, d_bytes, d_rec_off, (IxRec *)d_rec, (uint16_t *)d_flag, (u64 *)d_st2);
+        if ((rc = timer.end())) return rc;
+        PP_HIPCHK(ctx, hipGetLastError());
+        u64 cig = ~0ull;
+        if ((rc = fetch(ctx, d_st2, &cig))) return rc;
+        if (cig != ~0ull) {
+            if (bad_record) *bad_record = cig >> 8;
+            return ctx->fail(PP_ERR_ARG, "pp_bam_index: the CIGAR of record %llu runs past its block_size", (unsigned long long)(cig >> 8));
+        }
+    }
+    if (n_al && !pass) return ctx->fail(PP_ERR_ARG, "pp_bam_index: null pass with %llu aligned records", (unsigned long long)n_al);
+    if (n_pass != n_al)
+        return ctx->fail(PP_ERR_ARG, "pp_bam_index: %llu verdicts for %llu aligned records", (unsigned long long)n_pass, (unsigned long long)n_al);
+    {
+        hipLaunchKernelGGL(k_ix_blk, dim3((unsigned)((n_blk + 256u) / 256u)), dim3(256), 0, st, (u64)n_blk + 1u, d_blk, (u64 *)d_st2 + 1);
+        PP_HIPCHK(ctx, hipGetLastError());
+        u64 far = ~0ull;
+        if ((rc = fetch(ctx, (const u64 *)d_st2 + 1, &far))) return rc;
+        if (far != ~0ull) return ctx->fail(PP_ERR_LIMIT, "pp_bam_index: block %llu starts at 2^48 or behind: a virtual offset cannot hold it", (unsigned long long)far);
+    }
+    if ((rc = T.get(ctx, &d_pass, (size_t)n_al))) return rc;
+    if (n_al) PP_HIPCHK(ctx, hipMemcpyAsync(d_pass, pass, (size_t)n_al, hipMemcpyHostToDevice, st));
+    if (n) {
+        if ((rc = timer.begin(IX_SCANS))) return rc;
+        hipLaunchKernelGGL(k_tag_len<false>, dim3(nb), dim3(TAG_BLOCK), 0, st, n, d_bytes, d_rec_off, (const u8 *)d_aligned, (const u64 *)d_al_base,
+                           (const u8 *)d_pass, (u64)n_head, (u64 *)d_blk2, (u64 *)nullptr);
+        hipLaunchKernelGGL(k_colscan<2>, dim3(1), dim3(1024), 0, st, (const u64 *)d_blk2, (u64)nb, (u64 *)d_blk2off);
+        hipLaunchKernelGGL(k_tag_len<true>, dim3(nb), dim3(TAG_BLOCK), 0, st, n, d_bytes, d_rec_off, (const u8 *)d_aligned, (const u64 *)d_al_base,
+                           (const u8 *)d_pass, (u64)n_head, (u64 *)d_blk2off, (u64 *)d_start);
+        if ((rc = timer.end()) || (rc = timer.begin(IX_RECORDS))) return rc;
+        hipLaunchKernelGGL(k_ix_check, dim3(gb), dim3(256), 0, st, n, (const IxRec *)d_rec, n_ref, (u32 *)d_bin, (u64 *)d_st2 + 2);
+        if ((rc = timer.end())) return rc;
+        PP_HIPCHK(ctx, hipGetLastError());
+        u64 totals[2] = {0, 0}, bad = ~0ull;
+        if ((rc = fetch(ctx, (const u64 *)d_blk2off + 2ull * nb, totals, 2)) || (rc = fetch(ctx, (const u64 *)d_st2 + 2, &bad))) return rc;
+        u_total = n_head + 4ull * n + totals[0];
+        if (bad != ~0ull) {
+            const u32 kind = (u32)(bad & 0xFFu);
+            if (bad_record) *bad_record = bad >> 8;
+            if (kind == IX_END) return ctx->fail(PP_ERR_LIMIT, "pp_bam_index: record %llu ends behind 2^29: BAI holds positions below 2^29", (unsigned long long)(bad >> 8));
+            return ctx->fail(PP_ERR_ARG, "pp_bam_index: record %llu %s", (unsigned long long)(bad >> 8),
+                             kind == IX_REF ? "has a reference id outside [-1, n_ref)" : kind == IX_PLACED ? "is placed on a reference at a negative position"
+                                                                                                        : "stands in front of the record before it: the records are not in coordinate order");
+        }
+    }
+    if (n_blk != (u_total + PAY - 1u) / PAY)
+        return ctx->fail(PP_ERR_ARG, "pp_bam_index: %llu block offsets and one for a stream of %llu bytes, which has %llu blocks", (unsigned long long)n_blk,
+                         (unsigned long long)u_total, (unsigned long long)((u_total + PAY - 1u) / PAY));
+
+    // ---- the tables ----
+    namespace ih = pp_bam_index_host;
+    std::vector<uint64_t> h_key, h_beg, h_end, h_lin, h_lin_off((size_t)n_ref + 1, 0), h_ref[4];
+    std::vector<u32> h_intv(n_ref, 0);
+    for (auto &v : h_ref) v.assign(n_ref, 0);
+    uint64_t n_chunk = 0, no_coor = 0;
+    if (n) {
+        const IxWhere W{(const u64 *)d_start, d_blk};
+        void *d_head, *d_cidx, *d_intv, *d_ref4, *d_nc;
+        if ((rc = T.get(ctx, &d_head, (size_t)n * 4)) || (rc = T.get(ctx, &d_cidx, ((size_t)n + 1) * 4)) || (rc = T.get(ctx, &d_intv, (size_t)n_ref * 4)) ||
+            (rc = T.get(ctx, &d_ref4, (size_t)n_ref * 32)) || (rc = T.get(ctx, &d_nc, 8)))
+            return rc;
+        u64 *const d_rb = (u64 *)d_ref4, *const d_re = d_rb + n_ref, *const d_map = d_re + n_ref, *const d_unm = d_map + n_ref;
+        PP_HIPCHK(ctx, hipMemsetAsync(d_intv, 0, std::max<size_t>((size_t)n_ref * 4, 16), st));
+        PP_HIPCHK(ctx, hipMemsetAsync(d_ref4, 0, std::max<size_t>((size_t)n_ref * 32, 16), st));
+        PP_HIPCHK(ctx, hipMemsetAsync(d_nc, 0, 8, st));
+        if ((rc = timer.begin(IX_CHUNKS))) return rc;
+        hipLaunchKernelGGL(k_ix_run, dim3(gb), dim3(256), 0, st, n, (const IxRec *)d_rec, (const u32 *)d_bin, (u32 *)d_head);
+        if ((rc = scan_u32<u32>(ctx, S.sums(), S.sums_off(), (const u32 *)d_head, (u64)n, (u32 *)d_cidx))) return rc;
+        if ((rc = timer.end()) || (rc = timer.begin(IX_LINEAR))) return rc;
+        hipLaunchKernelGGL(k_ix_ref, dim3(gb), dim3(256), 0, st, n, (const IxRec *)d_rec, (const uint16_t *)d_flag, W, (u32 *)d_intv, d_rb, d_re, d_map, d_unm, (u64 *)d_nc);
+        if ((rc = timer.end())) return rc;
+        PP_HIPCHK(ctx, hipGetLastError());
+        u32 nc32 = 0;
+        if ((rc = fetch(ctx, (const u32 *)d_cidx + n, &nc32)) || (rc = fetch(ctx, d_nc, &no_coor))) return rc;
+        n_chunk = nc32;
+        if (n_ref) {
+            if ((rc = fetch(ctx, d_intv, h_intv.data(), n_ref))) return rc;
+            for (int k = 0; k < 4; k++)
+                if ((rc = fetch(ctx, d_rb + (size_t)k * n_ref, h_ref[k].data(), n_ref))) return rc;
+        }
+        for (u32 r = 0; r < n_ref; r++) h_lin_off[r + 1] = h_lin_off[r] + h_intv[r];
+        const u64 n_win = h_lin_off[n_ref];
+        if (n_win > IX_MAX_WINDOWS) return ctx->fail(PP_ERR_LIMIT, "pp_bam_index: %llu windows of 16,384 bases in the linear index, above 2^27", (unsigned long long)n_win);
+        // the linear index
+        if (n_win) {
+            void *d_lin_off, *d_lin;
+            if ((rc = T.get(ctx, &d_lin_off, ((size_t)n_ref + 1) * 8)) || (rc = T.get(ctx, &d_lin, (size_t)n_win * 8))) return rc;
+            PP_HIPCHK(ctx, hipMemcpyAsync(d_lin_off, h_lin_off.data(), ((size_t)n_ref + 1) * 8, hipMemcpyHostToDevice, st));
+            PP_HIPCHK(ctx, hipMemsetAsync(d_lin, 0xFF, (size_t)n_win * 8, st));
+            if ((rc = timer.begin(IX_LINEAR))) return rc;
+            hipLaunchKernelGGL(k_ix_lin, dim3(gb), dim3(256), 0, st, n, (const IxRec *)d_rec, W, (const u64 *)d_lin_off, (u64 *)d_lin);
+            hipLaunchKernelGGL(k_ix_fill, dim3((n_ref + 255u) / 256u), dim3(256), 0, st, n_ref, (const u64 *)d_lin_off, (u64 *)d_lin);
+            if ((rc = timer.end())) return rc;
+            PP_HIPCHK(ctx, hipGetLastError());
+            h_lin.resize((size_t)n_win);
+            if ((rc = fetch(ctx, d_lin, h_lin.data(), (size_t)n_win))) return rc;
+        }
+        // the chunk table, then its order
+        if (n_chunk) {
+            const u32 m = (u32)n_chunk;
+            const unsigned gm = (unsigned)(((u64)m + 255u) / 256u);
+            const u32 m_tiles = (u32)(((u64)m + RG_TILE - 1u) / RG_TILE);
+            const u64 m_cnt = 256ull * m_tiles;
+            void *d_key[2], *d_beg, *d_end, *d_idx[2], *d_cnt, *d_off, *d_sb, *d_se;
+            if ((rc = T.get(ctx, &d_key[0], (size_t)m * 8)) || (rc = T.get(ctx, &d_key[1], (size_t)m * 8)) || (rc = T.get(ctx, &d_beg, (size_t)m * 8)) ||
+                (rc = T.get(ctx, &d_end, (size_t)m * 8)) || (rc = T.get(ctx, &d_idx[0], (size_t)m * 4)) || (rc = T.get(ctx, &d_idx[1], (size_t)m * 4)) ||
+                (rc = T.get(ctx, &d_cnt, (size_t)m_cnt * 4)) || (rc = T.get(ctx, &d_off, (size_t)(m_cnt + 1) * 4)) || (rc = T.get(ctx, &d_sb, (size_t)m * 8)) ||
+                (rc = T.get(ctx, &d_se, (size_t)m * 8)))
+                return rc;
+            if ((rc = timer.begin(IX_CHUNKS))) return rc;
+            hipLaunchKernelGGL(k_ix_chunk, dim3(gb), dim3(256), 0, st, n, (const IxRec *)d_rec, (const u32 *)d_bin, (const u32 *)d_head, (const u32 *)d_cidx, W,
+                               (u64 *)d_key[0], (u64 *)d_beg, (u64 *)d_end);
+            u32 shifts[6], passes = 0;
+            shifts[passes++] = 0;
+            shifts[passes++] = 8;  // bins are below 2^16
+            for (u32 top = n_ref - 1u, b = 0; top; top >>= 8, b++) shifts[passes++] = 32u + 8u * b;
+            const u32 *idx_in = nullptr;
+            for (u32 p = 0; p < passes; p++) {
+                const u64 *const key_in = (const u64 *)d_key[p & 1u];
+                u64 *const key_out = (u64 *)d_key[(p + 1u) & 1u];
+                u32 *const idx_out = (u32 *)d_idx[p & 1u];
+                hipLaunchKernelGGL(k_rg_hist<u64>, dim3(m_tiles), dim3(RG_BLOCK), 0, st, m, key_in, shifts[p], m_tiles, (u32 *)d_cnt);
+                if ((rc = scan_u32<u32>(ctx, S.sums(), S.sums_off(), (const u32 *)d_cnt, m_cnt, (u32 *)d_off))) return rc;
+                hipLaunchKernelGGL(k_rg_scatter<u64>, dim3(m_tiles), dim3(RG_BLOCK), 0, st, m, key_in, idx_in, shifts[p], m_tiles, (const u32 *)d_off, key_out, idx_out);
+                idx_in = idx_out;
+            }
+            hipLaunchKernelGGL(k_ix_gather, dim3(gm), dim3(256), 0, st, m, idx_in, (const u64 *)d_beg, (const u64 *)d_end, (u64 *)d_sb, (u64 *)d_se);
+            if ((rc = timer.end())) return rc;
+            PP_HIPCHK(ctx, hipGetLastError());
+            h_key.resize(m);
+            h_beg.resize(m);
+            h_end.resize(m);
+            if ((rc = fetch(ctx, d_key[passes & 1u], h_key.data(), m)) || (rc = fetch(ctx, d_sb, h_beg.data(), m)) || (rc = fetch(ctx, d_se, h_end.data(), m))) return rc;
+        }
+    }
+    PP_HIPCHK(ctx, hipStreamSynchronize(st));
+    if (timer.on) {
+        if ((rc = timer.sums(ctx->ix_ms, 4))) return rc;
+        ctx->ix_timed = true;
+    }
+    ih::Tables Tb;
+    Tb.n_ref = n_ref;
+    Tb.n_chunk = n_chunk;
+    Tb.chunk_key = h_key.data();
+    Tb.chunk_beg = h_beg.data();
+    Tb.chunk_end = h_end.data();
+    Tb.n_intv = h_intv.data();
+    Tb.lin_off = h_lin_off.data();
+    Tb.lin = h_lin.data();
+    Tb.ref_beg = h_ref[0].data();
+    Tb.ref_end = h_ref[1].data();
+    Tb.mapped = h_ref[2].data();
+    Tb.unmapped = h_ref[3].data();
+    Tb.n_no_coor = no_coor;
+    std::vector<uint8_t> file;
+    char msg[200];
+    msg[0] = 0;
+    if ((rc = ih::serialise(Tb, &file, msg, sizeof msg))) return ctx->fail(rc, "%s", msg);
+    bai->data = (uint8_t *)malloc(file.size() + 1);
+    if (!bai->data) return ctx->fail(PP_ERR_HIP, "pp_bam_index: out of host memory");
+    memcpy(bai->data, file.data(), file.size());
+    bai->len = file.size();
+    return PP_OK;
+}
+
+// (internal hook, not part of the header: tools/bam_sort_timing.py) the HIP-event time of the context's last pp_bam_index by stage:
+// scans | records | chunks | linear; PP_ERR_ARG where the context had no profiling on
+extern "C" int pp_bam_index_stage_ms_(const pp_ctx *ctx, float *ms4) {
+    if (!ctx || !ms4 || !ctx->ix_timed) return PP_ERR_ARG;
+    std::copy(ctx->ix_ms, ctx->ix_ms + 4, ms4);
     return PP_OK;
 }

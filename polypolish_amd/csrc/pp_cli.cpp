@@ -36,6 +36,8 @@ static const char *HELP_FILTER =
     "      --out_bam                    SAM text inputs: write the outputs as compressed BAM (not in the reference)\n"
     "      --out_sam                    BAM inputs: write the outputs as SAM text (not in the reference)\n"
     "      --text_chain                 SAM text inputs, plain or bgzipped, through the record chain on the device (not in the reference)\n"
+    "      --sort_out                   BAM outputs: write them in coordinate order, header SO:coordinate (not in the reference)\n"
+    "      --out_bai                    with --sort_out: write OUT1.bai and OUT2.bai next to the outputs (not in the reference)\n"
     "      --orientation <ORIENTATION>  Expected pair orientation [default: auto]\n"
     "      --low <LOW>                  Low percentile threshold [default: 0.1]\n"
     "      --high <HIGH>                High percentile threshold [default: 99.9]\n"
@@ -70,6 +72,7 @@ static const char *HELP_FUSED =
     "--regroup: coordinate-sorted BAM inputs (the polish brings every read's alignments together; the outputs keep file order).\n"
     "--out_bam: SAM text inputs with --out1/--out2: write the outputs as compressed BAM.\n"
     "--out_sam: BAM inputs with --out1/--out2: write the outputs as SAM text.\n"
+    "--sort_out: BAM outputs in coordinate order, header SO:coordinate; --out_bai: with it, OUT1.bai and OUT2.bai (not in the reference).\n"
     "--text_chain: SAM text inputs, plain or bgzipped, through the record chain on the device; --regroup then takes text as well (not in the reference).\n"
     "--out <PATH>: write the polished FASTA to PATH instead of stdout (not in the reference).\n"
     "--wrap <N>: line width of the polished FASTA, made on the device; 0: one line per contig (not in the reference).\n"
@@ -203,6 +206,10 @@ static bool take_fasta_form(const Parsed &P, const std::vector<OptSpec> &specs, 
         return false;
     }
     return true;
+}
+static int refuse_bai_without_sort() {
+    fprintf(stderr, "\nError: --out_bai needs --sort_out: a .bai indexes a coordinate-sorted BAM file\n");
+    return 1;
 }
 static int refuse_index_without_out() {
     fprintf(stderr, "\nError: --index needs --out <PATH>: the indexes are written next to the file (PATH.fai, PATH.gzi)\n");
@@ -418,7 +425,9 @@ int main(int argc, char **argv) {
                                             {"--out", 0, true, "<PATH>"},
                                             {"--wrap", 0, true, "<N>"},
                                             {"--out_bgzf", 0, false, ""},
-                                            {"--index", 0, false, ""}};
+                                            {"--index", 0, false, ""},
+                                            {"--sort_out", 0, false, ""},
+                                            {"--out_bai", 0, false, ""}};
         FastaForm form;
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help || P.version) { fputs(HELP_FUSED, stdout); return 0; }
@@ -440,9 +449,11 @@ int main(int argc, char **argv) {
         if (!assembly || !in1 || !in2)
             return usage_error("the following required arguments were not provided:\n  --in1 <IN1> --in2 <IN2> <ASSEMBLY>");
         if (form.index && !form.out) return refuse_index_without_out();
+        if (P.value[22] && !P.value[21]) return refuse_bai_without_sort();
         pp_ctx *ctx = nullptr;
         int rc = pp_ctx_create_async(device, &ctx);
         if (rc) return no_device(device);
+        pp_ctx_set_sort_out(ctx, P.value[21] != nullptr, P.value[22] != nullptr);
         pp_ctx_set_regroup(ctx, regroup);
         pp_ctx_set_out_bam(ctx, P.value[14] != nullptr);
         pp_ctx_set_out_sam(ctx, P.value[15] != nullptr);
@@ -467,7 +478,8 @@ int main(int argc, char **argv) {
                                             {"--out1", 0, true, "<OUT1>"}, {"--out2", 0, true, "<OUT2>"},
                                             {"--orientation", 0, true, "<ORIENTATION>"}, {"--low", 0, true, "<LOW>"},
                                             {"--high", 0, true, "<HIGH>"}, {"--out_bam", 0, false, ""},
-                                            {"--out_sam", 0, false, ""}, {"--text_chain", 0, false, ""}};
+                                            {"--out_sam", 0, false, ""}, {"--text_chain", 0, false, ""},
+                                            {"--sort_out", 0, false, ""}, {"--out_bai", 0, false, ""}};
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help) { fputs(HELP_FILTER, stdout); return 0; }
         if (P.version) { printf("polypolish-filter v0.6.1\n"); return 0; }
@@ -481,9 +493,11 @@ int main(int argc, char **argv) {
         const char *in1 = P.value[0], *in2 = P.value[1], *out1 = P.value[2], *out2 = P.value[3];
         if (!in1 || !in2 || !out1 || !out2)
             return usage_error("the following required arguments were not provided:\n  --in1 <IN1> --in2 <IN2> --out1 <OUT1> --out2 <OUT2>");
+        if (P.value[11] && !P.value[10]) return refuse_bai_without_sort();
         pp_ctx *ctx = nullptr;
         int rc = pp_ctx_create_async(device, &ctx);
         if (rc) return no_device(device);
+        pp_ctx_set_sort_out(ctx, P.value[10] != nullptr, P.value[11] != nullptr);
         pp_ctx_set_out_bam(ctx, P.value[7] != nullptr);
         pp_ctx_set_out_sam(ctx, P.value[8] != nullptr);
         pp_ctx_set_text_chain(ctx, P.value[9] != nullptr);

@@ -4,7 +4,7 @@
 // owner of their device memory, their stage times, the named arrays of a batch, a caller's batch checked and uploaded).  Included
 // by pp_devtext.h (the SAM tokenizers' text utilities), by pp_textin.h (a borrowed text's: pp_sam_out.hip, pp_sam_bam.hip) and
 // directly by the record chain: pp_bgzf.hip, pp_bgzf_deflate.hip,
-// pp_bam.hip, pp_bam_walk.hip, pp_bam_out.hip, pp_names.hip, pp_filter_rec.hip and pp_regroup.hip (through pp_filter_group.h),
+// pp_bam.hip, pp_bam_walk.hip, pp_bam_out.hip, pp_names.hip, pp_filter_rec.hip and pp_regroup.hip (through pp_filter_group.h), pp_bam_sort.hip (through pp_rg_sort.h),
 // pp_gate.hip and pp_prepare.hip.  Everything lives in an anonymous namespace: each translation unit gets its own copies, and of
 // the kernels that are templates only those it launches.
 #pragma once

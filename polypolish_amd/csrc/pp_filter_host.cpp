@@ -970,6 +970,113 @@ int filter_write(pp_ctx *ctx, const Log &log, const FilterRun &R, const char *co
     return PP_OK;
 }
 
+// One input's records where the writers below find them, as pp_bam_tagged takes them
+struct BamSrc {
+    const uint8_t *bytes;
+    uint64_t n_bytes, records_at;
+    const uint64_t *rec_off;
+    uint64_t n_rec;
+    int mem;
+};
+
+// The two BAM outputs of a filter run, for BAM inputs and for text inputs with --out_bam: per file the filter's own verdicts written
+// into the records (pp_bam_tagged), compressed, written, logged.  With pp_ctx_set_sort_out the records go out in coordinate order
+// behind the rewritten header (pp_bam_sort, pp_bam_sorted_pass, pp_bam_tagged_head), with its index a .bai (pp_bam_index) next to each
+// output, and BOTH files and both indexes are complete before any output is created: a record the sort or the index refuses leaves
+// nothing behind.  The log is the same lines either way.
+int write_bam_outs(pp_ctx *ctx, const Log &log, const FilterRun &R, const BamSrc src[2], const char *const ins[2], const char *const outs[2],
+                   uint64_t *after) {
+    int index = 0;
+    const bool sorted = pp_ctx_sort_out_(ctx, &index) != 0;
+    pp_bgzf_out *c[2] = {nullptr, nullptr};
+    pp_bytes bai[2] = {{nullptr, 0}, {nullptr, 0}};
+    struct Free {
+        pp_bgzf_out **c;
+        pp_bytes *bai;
+        ~Free() {
+            for (int f = 0; f < 2; f++) {
+                pp_bgzf_out_free(c[f]);
+                pp_bytes_free(&bai[f]);
+            }
+        }
+    } free_outs{c, bai};
+    uint64_t p_[2] = {0, 0}, f_[2] = {0, 0};
+    auto refused = [&](int f, uint64_t bad) {  // the library's sentence behind the flag's name and the input's path
+        const std::string said = pp_last_error(ctx);
+        if (bad != ~0ull) return ppb::fail(ctx, PP_ERR_QUIT, "--sort_out: \"%s\" (record %llu): %s", ins[f], (unsigned long long)(bad + 1), said.c_str());
+        return ppb::fail(ctx, PP_ERR_QUIT, "--sort_out: \"%s\": %s", ins[f], said.c_str());
+    };
+    auto make = [&](int f) -> int {
+        const BamSrc &S = src[f];
+        pp_bam_out *t = nullptr;
+        uint64_t bad = ~0ull, blocks = 0;
+        int rc;
+        if (!sorted) {
+            rc = pp_bam_tagged(ctx, S.bytes, S.n_bytes, S.records_at, S.rec_off, S.n_rec, S.mem, R.pass[f].data(), R.n_aln[f], &t, &bad);
+            if (rc == PP_OK) rc = pp_bam_out_deflate(ctx, t, &c[f]);
+            if (rc == PP_OK) pp_bam_out_counts(t, &p_[f], &f_[f], &blocks);
+            pp_bam_out_free(t);
+            return rc;
+        }
+        pp_bam_sorted *s = nullptr;
+        if (pp_bam_sort(ctx, S.bytes, S.n_bytes, S.records_at, S.rec_off, S.n_rec, S.mem, &s, &bad) != PP_OK) return refused(f, bad);
+        struct FreeSorted {
+            pp_bam_sorted *s;
+            ~FreeSorted() { pp_bam_sorted_free(s); }
+        } free_sorted{s};
+        std::vector<uint8_t> v(std::max<size_t>(R.n_aln[f], 1));
+        if ((rc = pp_bam_sorted_pass(s, R.pass[f].data(), R.n_aln[f], v.data()))) return rc;
+        const uint8_t *head = nullptr;
+        uint64_t n_head = 0;
+        pp_bam_sorted_head(s, &head, &n_head);
+        const uint64_t *off = pp_bam_sorted_rec_off(s);  // DEVICE memory ...
+        std::vector<uint64_t> host_off;
+        if (S.mem == PP_MEM_HOST) {                      // ... as the bytes are, or brought to where they are
+            host_off.resize(std::max<size_t>((size_t)S.n_rec, 1));
+            if (S.n_rec && (rc = pp_ctx_download(ctx, host_off.data(), off, S.n_rec * 8))) return rc;
+            off = host_off.data();
+        }
+        rc = pp_bam_tagged_head(ctx, S.bytes, S.n_bytes, S.records_at, off, S.n_rec, S.mem, v.data(), R.n_aln[f], head, n_head, &t, &bad);
+        if (rc == PP_OK) rc = pp_bam_out_deflate(ctx, t, &c[f]);
+        if (rc == PP_OK) pp_bam_out_counts(t, &p_[f], &f_[f], &blocks);
+        pp_bam_out_free(t);
+        if (rc || !index) return rc;
+        uint32_t n_ref = 0;
+        uint64_t at = 0, n_blk = 0;
+        (void)pp_bam_header(head, n_head, 0, &n_ref, nullptr, nullptr, nullptr, &at);  // (n_ref is what is asked for: no room for names)
+        const uint64_t *blk = pp_bgzf_out_blk_off(c[f], &n_blk);
+        if (pp_bam_index(ctx, S.bytes, S.n_bytes, n_head, off, S.n_rec, S.mem, v.data(), R.n_aln[f], n_ref, blk, n_blk, PP_MEM_DEVICE, &bai[f], &bad) != PP_OK)
+            return refused(f, bad);
+        return PP_OK;
+    };
+    auto put = [&](int f) -> int {
+        if (int rc = pp_bgzf_out_write(c[f], outs[f])) return rc;
+        if (sorted && index) {
+            const std::string path = std::string(outs[f]) + ".bai";
+            FILE *fh = fopen(path.c_str(), "wb");
+            const bool ok = fh && (bai[f].len == 0 || fwrite(bai[f].data, 1, (size_t)bai[f].len, fh) == bai[f].len);
+            if ((fh && fclose(fh) != 0) || !ok) return ppb::fail(ctx, PP_ERR_QUIT, "unable to write alignments to \"%s\"", path.c_str());
+        }
+        pp_bgzf_out_free(c[f]);
+        c[f] = nullptr;
+        log("Filtering %s:\n  %s pass\n  %s fail\n\n", ins[f], commas(p_[f]).c_str(), commas(f_[f]).c_str());
+        if (after) *after += p_[f];
+        return PP_OK;
+    };
+    if (sorted) {
+        for (int f = 0; f < 2; f++)
+            if (int rc = make(f)) return rc;
+        for (int f = 0; f < 2; f++)
+            if (int rc = put(f)) return rc;
+        return PP_OK;
+    }
+    for (int f = 0; f < 2; f++) {  // file by file: the first output is written while nothing of the second is held
+        if (int rc = make(f)) return rc;
+        if (int rc = put(f)) return rc;
+    }
+    return PP_OK;
+}
+
 // filter_sams with --out_bam: the text the run holds in host memory encoded as BAM on the device (pp_sam_bam), the filter's own
 // verdicts written into the records (pp_bam_tagged), compressed, written.  Both files are encoded before either output is created: a
 // line the encoder refuses leaves nothing behind.  The log is filter_write's, word for word.
@@ -997,24 +1104,13 @@ int filter_write_sam_bam(pp_ctx *ctx, const Log &log, const FilterRun &R, const 
             return ppb::fail(ctx, PP_ERR_QUIT, "--out_bam: %s", said.c_str());
         }
     }
+    BamSrc src[2];
     for (int f = 0; f < 2; f++) {
-        const uint8_t *dev = nullptr;
-        uint64_t n_bytes = 0, records_at = 0, n_rec = 0, bad = 0, p_ = 0, f_ = 0, blocks = 0;
-        pp_bam_enc_bytes(enc[f], &dev, &n_bytes, &records_at);
-        const uint64_t *rec_off = pp_bam_enc_rec_off(enc[f], &n_rec);
-        pp_bam_out *t = nullptr;
-        pp_bgzf_out *c = nullptr;
-        int rc = pp_bam_tagged(ctx, dev, n_bytes, records_at, rec_off, n_rec, PP_MEM_DEVICE, R.pass[f].data(), R.n_aln[f], &t, &bad);
-        if (rc == PP_OK) rc = pp_bam_out_deflate(ctx, t, &c);
-        if (rc == PP_OK) pp_bam_out_counts(t, &p_, &f_, &blocks);
-        pp_bam_out_free(t);
-        if (rc == PP_OK) rc = pp_bgzf_out_write(c, outs[f]);
-        pp_bgzf_out_free(c);
-        if (rc) return rc;
-        log("Filtering %s:\n  %s pass\n  %s fail\n\n", ins[f], commas(p_).c_str(), commas(f_).c_str());
-        *after += p_;
+        src[f] = BamSrc{nullptr, 0, 0, nullptr, 0, PP_MEM_DEVICE};
+        pp_bam_enc_bytes(enc[f], &src[f].bytes, &src[f].n_bytes, &src[f].records_at);
+        src[f].rec_off = pp_bam_enc_rec_off(enc[f], &src[f].n_rec);
     }
-    return PP_OK;
+    return write_bam_outs(ctx, log, R, src, ins, outs, after);
 }
 
 // both inputs' kinds; *bam = both are BAM.  One BAM and one SAM input is refused.
@@ -1105,21 +1201,12 @@ int filter_core_bam(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const char
 // filter_sams for BAM: every record again, ZP:Z:fail appended where the filter's own verdict is 0, compressed, written
 int filter_write_bam(pp_ctx *ctx, const Log &log, const FilterRun &R, const char *const ins[2], const char *const outs[2]) {
     log("Filtering SAM files\n");
+    BamSrc src[2];
     for (int f = 0; f < 2; f++) {
         const ppb::BamFile &F = R.F[f];
-        pp_bam_out *t = nullptr;
-        pp_bgzf_out *c = nullptr;
-        uint64_t bad = 0, p_ = 0, f_ = 0, blocks = 0;
-        int rc = pp_bam_tagged(ctx, F.bytes, F.n_bytes, F.records_at, F.rec_off, F.n_rec, F.mem, R.pass[f].data(), R.n_aln[f], &t, &bad);
-        if (rc == PP_OK) rc = pp_bam_out_deflate(ctx, t, &c);
-        if (rc == PP_OK) pp_bam_out_counts(t, &p_, &f_, &blocks);
-        pp_bam_out_free(t);
-        if (rc == PP_OK) rc = pp_bgzf_out_write(c, outs[f]);
-        pp_bgzf_out_free(c);
-        if (rc) return rc;
-        log("Filtering %s:\n  %s pass\n  %s fail\n\n", ins[f], commas(p_).c_str(), commas(f_).c_str());
+        src[f] = BamSrc{(const uint8_t *)F.bytes, F.n_bytes, F.records_at, F.rec_off, F.n_rec, F.mem};
     }
-    return PP_OK;
+    return write_bam_outs(ctx, log, R, src, ins, outs, nullptr);
 }
 
 // filter_sams for BAM with --out_sam: every record as a line of SAM text on the device (pp_bam_sam), "\tZP:Z:fail" behind the lines
@@ -1198,6 +1285,9 @@ int run_filter(pp_ctx *ctx, const Log &log, const pph::Lap &lap, const std::func
     banner();
     if (int rc = filter_input_kinds(ctx, ins, R.kinds, &R.bam)) return rc;
     R.chain_text = !R.bam && pp_ctx_text_chain_(ctx) != 0;
+    if (outs[0] && pp_ctx_sort_out_(ctx, nullptr) && (R.bam ? pp_ctx_out_sam_(ctx) != 0 : !pp_ctx_out_bam_(ctx)))  // (before an input is read)
+        return ppb::fail(ctx, PP_ERR_QUIT, "--sort_out takes BAM outputs: \"%s\" would be SAM text (%s)", outs[0],
+                         R.bam ? "--out_sam" : "SAM text inputs without --out_bam");
     if (assembly && !R.bam && pp_ctx_regroup_(ctx) && !R.chain_text)  // (the fused command: refused before the filter has written anything)
         return ppb::fail(ctx, PP_ERR_QUIT, "--regroup takes BAM input: \"%s\" is SAM text (its records are regrouped on the device, which holds none of a text file)", ins[0]);
     int rc = R.bam || R.chain_text ? filter_core_bam(ctx, log, lap, ins, assembly, orientation, low, high, R)

@@ -28,6 +28,7 @@
 extern "C" {
 int pp_ctx_set_error_(pp_ctx *ctx, int code, const char *msg);  // pp_ctx is opaque to the host files: its error text is stored through this hook
 int pp_ctx_device_(const pp_ctx *ctx);                          // the device a context runs on
+int pp_ctx_sort_out_(const pp_ctx *ctx, int *index);            // what pp_ctx_set_sort_out was given (the filter drivers)
 int pp_ctx_out_bam_(const pp_ctx *ctx);                         // what pp_ctx_set_out_bam was given (the filter drivers)
 int pp_ctx_out_sam_(const pp_ctx *ctx);                         // what pp_ctx_set_out_sam was given (the filter drivers)
 int pp_ctx_regroup_(const pp_ctx *ctx);                         // what pp_ctx_set_regroup was given (the file drivers)

@@ -267,6 +267,9 @@ struct pp_ctx {
     pp::DevBuf f_rec[48];  // pp_filter_records: the call's arrays and scratch, in the order it asks for them (pp_filter_rec.hip)
     pp::DevBuf g_rec[24];  // pp_batch_regroup: the call's scratch, in the order it asks for it (pp_regroup.hip)
     bool out_bam = false;  // pp_ctx_set_out_bam: the filter drivers write SAM text inputs back as compressed BAM
+    float ix_ms[4] = {0.f, 0.f, 0.f, 0.f};   // pp_bam_index: the stage times of the last call made with profiling on (pp_bam_index_stage_ms_)
+    bool ix_timed = false;
+    bool sort_out = false, out_bai = false;  // pp_ctx_set_sort_out: the filter drivers write BAM outputs in coordinate order, with a .bai
     bool out_sam = false;  // pp_ctx_set_out_sam: the filter drivers write BAM inputs back as SAM text
     bool regroup = false;  // pp_ctx_set_regroup: the file drivers regroup every BAM file's records in front of the gate
     bool text_chain = false;  // pp_ctx_set_text_chain: the file drivers take SAM text through the record chain (pp_sam_records)

@@ -5,20 +5,17 @@
 // in the order of their first record, file order inside a group.  perm[j] = the raw record that stands at place j, which is the
 // STABLE order of the records by rep[i] = the first record that carries record i's read_id.
 //   k_rid_insert / k_rid_find   (pp_filter_group.h) rep[] through an open-addressing table over the 64-bit ids, as pp_filter_records
-//   k_rg_hist      a least-significant-digit radix sort of the indices by rep[], 8 bits a pass, as many passes as n_rec - 1 has
-//   k_rg_scatter   bytes.  A pass: every tile of RG_TILE keys counts its 256 digits (LDS); the counts, laid out digit by digit and
-//                  inside a digit tile by tile, are scanned (scan_u32) into the place of every (digit, tile)'s first key; the scatter
-//                  ranks a key among the equal digits of its tile WITHOUT atomics -- lanes below it in its wave's round (64-bit
-//                  ballots, one per digit bit), the wave's earlier rounds, the tile's earlier waves (their counts through LDS) -- so
-//                  that a pass is stable and the order never depends on how atomics land.  The cost is linear in n_rec whatever the
-//                  groups' sizes (one group of all records included: every pass then moves every key to where it was)
+//   k_rg_hist      (pp_rg_sort.h, shared with pp_bam_sort) a least-significant-digit radix sort of the indices by rep[], 8 bits a
+//   k_rg_scatter   pass, as many passes as n_rec - 1 has bytes; stable and without atomics in the ranks.  The cost is linear in n_rec
+//                  whatever the groups' sizes (one group of all records included: every pass then moves every key to where it was)
 //   k_rg_count     groups (rep[i] == i) and moved records (perm[j] != j)
 //   k_rg_gather    the nine per-record arrays through perm: coalesced writes, random reads.  seq and cigar are not moved:
 //                  seq_off / cig_off are indirections already
-//   k_rg_aligned   !(flag & 4) of the raw and of the regrouped records; their scans give k_rg_map: aligned rank behind -> aligned
-//   k_rg_map       rank in front, which carries the filter's verdicts over (pp_regrouped_pass)
+//   k_rg_aligned   (pp_rg_sort.h) !(flag & 4) of the raw and of the regrouped records; their scans give k_rg_map: aligned rank behind
+//   k_rg_map       -> aligned rank in front, which carries the filter's verdicts over (pp_regrouped_pass)
 // Offsets and lengths are copied, never followed: nothing in the records can make the call read outside its arrays.
 #include "pp_filter_group.h"
+#include "pp_rg_sort.h"
 
 #include <cstring>
 
@@ -32,89 +29,6 @@ struct pp_regrouped : DevOwner {  // owns the upload of a host batch, the gather
 };
 
 namespace {
-
-constexpr u32 RG_BLOCK = 1024;                    // 16 waves ...
-constexpr u32 RG_ROUNDS = 4;                      // ... each takes 4 x 64 adjacent keys: round by round, lane by lane
-constexpr u32 RG_TILE = RG_BLOCK * RG_ROUNDS;     // keys per workgroup
-constexpr u32 RG_WAVES = RG_BLOCK / 64u;
-
-// the place of the key that lane `lane` of wave `wave` takes in round `j` of its tile
-__device__ __forceinline__ u64 rg_index(u32 wave, u32 j, u32 lane) {
-    return (u64)blockIdx.x * RG_TILE + wave * (64u * RG_ROUNDS) + j * 64u + lane;
-}
-
-__global__ __launch_bounds__(256) void k_rg_iota(u32 n, u32 *__restrict__ perm) {
-    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
-    if (i < n) perm[i] = (u32)i;
-}
-
-// cnt[digit * n_tiles + tile] = the tile's keys with that digit
-__global__ __launch_bounds__(RG_BLOCK) void k_rg_hist(u32 n, const u32 *__restrict__ key, u32 shift, u32 n_tiles, u32 *__restrict__ cnt) {
-    __shared__ u32 s_h[256];
-    if (threadIdx.x < 256u) s_h[threadIdx.x] = 0;
-    __syncthreads();
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (u32 j = 0; j < RG_ROUNDS; j++) {
-        const u64 i = rg_index(wave, j, lane);
-        if (i < n) atomicAdd(&s_h[(key[i] >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < 256u) cnt[(u64)threadIdx.x * n_tiles + blockIdx.x] = s_h[threadIdx.x];
-}
-
-// off[digit * n_tiles + tile] = where the tile's first key with that digit goes.  idx_in == nullptr: the keys stand in index order
-// (the first pass).
-__global__ __launch_bounds__(RG_BLOCK) void k_rg_scatter(u32 n, const u32 *__restrict__ key_in, const u32 *__restrict__ idx_in, u32 shift,
-                                                         u32 n_tiles, const u32 *__restrict__ off, u32 *__restrict__ key_out,
-                                                         u32 *__restrict__ idx_out) {
-    __shared__ u32 s_c[RG_WAVES][256];  // keys of wave w with digit d so far; then the place of the wave's first such key
-    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (u32 t = threadIdx.x; t < RG_WAVES * 256u; t += RG_BLOCK) (&s_c[0][0])[t] = 0;
-    __syncthreads();
-    const u64 below = (1ull << lane) - 1ull;
-    u32 key[RG_ROUNDS], at[RG_ROUNDS];  // at: the key's rank among its wave's keys with its digit
-    bool live[RG_ROUNDS];
-#pragma unroll
-    for (u32 j = 0; j < RG_ROUNDS; j++) {
-        const u64 i = rg_index(wave, j, lane);
-        live[j] = i < n;
-        key[j] = live[j] ? key_in[i] : 0u;
-        const u32 d = (key[j] >> shift) & 255u;
-        u64 peers = __ballot(live[j]);  // the round's live lanes with this lane's digit
-#pragma unroll
-        for (u32 b = 0; b < 8; b++) {
-            const u64 m = __ballot((d >> b) & 1u);
-            peers &= ((d >> b) & 1u) ? m : ~m;
-        }
-        // every lane reads the wave's count, then the digit's first lane adds the round's: a barrier between the two and behind
-        // them (all waves make all rounds), so that neither the hardware nor the compiler may take one for the other
-        at[j] = s_c[wave][d] + (u32)__popcll(peers & below);
-        __syncthreads();
-        if (live[j] && (peers & below) == 0) s_c[wave][d] += (u32)__popcll(peers);
-        __syncthreads();
-    }
-    if (threadIdx.x < 256u) {  // a digit each: the waves in order, on top of the tile's place
-        u32 run = off[(u64)threadIdx.x * n_tiles + blockIdx.x];
-#pragma unroll
-        for (u32 w = 0; w < RG_WAVES; w++) {
-            const u32 c = s_c[w][threadIdx.x];
-            s_c[w][threadIdx.x] = run;
-            run += c;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (u32 j = 0; j < RG_ROUNDS; j++) {
-        if (!live[j]) continue;
-        const u64 i = rg_index(wave, j, lane);
-        const u32 to = s_c[wave][(key[j] >> shift) & 255u] + at[j];
-        if (to < n) {  // (it is: the places come from the counts of these very keys)
-            key_out[to] = key[j];
-            idx_out[to] = idx_in ? idx_in[i] : (u32)i;
-        }
-    }
-}
 
 // counts[0] += groups, counts[1] += moved records: the waves' ballots meet in LDS, one atomic per workgroup and counter (a wave each
 // on two words was 1.3 ms of contention on 6.7 M records)
@@ -151,20 +65,6 @@ __global__ __launch_bounds__(256) void k_rg_gather(u32 n, const u32 *__restrict_
     ((u32 *)A.out[6])[j] = ((const u32 *)A.in[6])[p];
     ((u64 *)A.out[7])[j] = ((const u64 *)A.in[7])[p];
     ((u32 *)A.out[8])[j] = ((const u32 *)A.in[8])[p];
-}
-
-// perm == nullptr: the raw records' own order
-__global__ __launch_bounds__(256) void k_rg_aligned(u32 n, const uint16_t *__restrict__ flag, const u32 *__restrict__ perm, u32 *__restrict__ is_aln) {
-    const u64 j = (u64)blockIdx.x * 256u + threadIdx.x;
-    if (j < n) is_aln[j] = (flag[perm ? perm[j] : (u32)j] & 4u) ? 0u : 1u;
-}
-
-__global__ __launch_bounds__(256) void k_rg_map(u32 n, const uint16_t *__restrict__ flag, const u32 *__restrict__ perm, const u32 *__restrict__ rank_raw,
-                                                const u32 *__restrict__ rank_new, u32 *__restrict__ amap) {
-    const u64 j = (u64)blockIdx.x * 256u + threadIdx.x;
-    if (j >= n) return;
-    const u32 p = perm[j];
-    if (!(flag[p] & 4u)) amap[rank_new[j]] = rank_raw[p];
 }
 
 enum : int { RG_INTERN = 0, RG_SORT = 1, RG_GATHER = 2 };
@@ -270,9 +170,9 @@ extern "C" int pp_batch_regroup(pp_ctx *ctx, const pp_raw_batch *raw, int mem, p
         for (int p = 0; p < passes; p++) {
             const bool to_perm = ((passes - 1 - p) & 1) == 0;
             u32 *const key_out = (u32 *)d_key[p & 1], *const idx_out = to_perm ? d_perm : (u32 *)d_idx;
-            hipLaunchKernelGGL(k_rg_hist, dim3(n_tiles), dim3(RG_BLOCK), 0, st, n, key_in, 8u * p, n_tiles, (u32 *)d_cnt);
+            hipLaunchKernelGGL(k_rg_hist<u32>, dim3(n_tiles), dim3(RG_BLOCK), 0, st, n, key_in, 8u * p, n_tiles, (u32 *)d_cnt);
             if ((rc = scan_u32<u32>(ctx, T.sums(), T.sums_off(), (const u32 *)d_cnt, n_cnt, (u32 *)d_off))) return rc;
-            hipLaunchKernelGGL(k_rg_scatter, dim3(n_tiles), dim3(RG_BLOCK), 0, st, n, key_in, idx_in, 8u * p, n_tiles, (const u32 *)d_off, key_out, idx_out);
+            hipLaunchKernelGGL(k_rg_scatter<u32>, dim3(n_tiles), dim3(RG_BLOCK), 0, st, n, key_in, idx_in, 8u * p, n_tiles, (const u32 *)d_off, key_out, idx_out);
             key_in = key_out;
             idx_in = idx_out;
         }

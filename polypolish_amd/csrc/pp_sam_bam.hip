@@ -927,3 +927,17 @@ extern "C" int pp_ctx_set_out_bam(pp_ctx *ctx, int on) {
 
 // (internal, the filter drivers: pp_filter_host.cpp)
 extern "C" int pp_ctx_out_bam_(const pp_ctx *ctx) { return ctx && ctx->out_bam ? 1 : 0; }
+
+extern "C" int pp_ctx_set_sort_out(pp_ctx *ctx, int on, int index) {
+    if (!ctx) return PP_ERR_ARG;
+    if (index && !on) return ctx->fail(PP_ERR_ARG, "pp_ctx_set_sort_out: an index needs the sorted output (--out_bai needs --sort_out)");
+    ctx->sort_out = on != 0;
+    ctx->out_bai = index != 0;
+    return PP_OK;
+}
+
+// (internal, the filter drivers: pp_filter_host.cpp)
+extern "C" int pp_ctx_sort_out_(const pp_ctx *ctx, int *index) {
+    if (index) *index = ctx && ctx->out_bai ? 1 : 0;
+    return ctx && ctx->sort_out ? 1 : 0;
+}
