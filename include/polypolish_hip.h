@@ -982,6 +982,43 @@ void pp_debug_extra_free(pp_debug_extra *d);
 int pp_polish_debug_tsv(pp_ctx *ctx, const char *const *contig_names, uint64_t pos_lo, uint64_t pos_hi, uint8_t *out,
                         int out_mem, uint64_t cap, uint64_t *len, uint64_t *pos_next);
 
+/* ---- the polish's edits as VCF text on the device (pp_k_vcf.h; not in the reference) ----------
+ * pp_polish_vcf writes where the finished job changed the assembly, and to what, as VCF 4.2 text in device memory: a post-pass over
+ * what every job leaves on the context -- the assembly bases, the emit codes, the multi-byte winners' list and the polished bytes.
+ * Valid after a successful pp_polish_finish and until the next pp_polish_begin, with or without pp_polish_set_debug, whichever path
+ * the job took; the bytes depend on neither.  The batch's seq array is NOT read (the caller may have released it): ALT bytes come from
+ * the polished output.  tests/vcf_model.py defines the text:
+ *   header     "##fileformat=VCFv4.2\n", "##source=" pp_version() "\n", per contig in assembly order "##contig=<ID=name,length=L>\n",
+ *              then "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n"
+ *   edited     position p emits e(p), its bytes in the polished output (the winner without its '-': it may be empty); p is edited
+ *              iff e(p) is not exactly the one byte bases[p]
+ *   records    each maximal run [a, b) of edited positions inside ONE contig (runs never join across a contig boundary) is one line
+ *              name \t POS \t . \t REF \t ALT \t . \t . \t . \n, with R = bases[a..b), A = e(a)...e(b-1), positions local and 0-based:
+ *                  A not empty                        POS a+1   REF R                ALT A
+ *                  A empty, a > 0                     POS a     REF bases[a-1] R     ALT bases[a-1]   (the anchor is unedited)
+ *                  A empty, a == 0, b < L             POS 1     REF R bases[b]       ALT bases[b]
+ *                  A empty, the run is the contig     POS 1     REF R                ALT <DEL>
+ *              in assembly order.  Bytes are written as they are: nothing is re-cased, trimmed or normalised, and a name or an
+ *              assembly byte that VCF does not allow is written all the same.
+ * contig_names: one NUL-terminated name per contig.  Refusals, all but the last decided on the host before anything is launched:
+ * PP_ERR_ARG for a null argument, a context without a finished job (a job that ended in an error leaves none), a context with
+ * pp_polish_set_emit ranges (a rank's share has no defined runs at its edges), a name that holds a tab or a newline; PP_ERR_LIMIT
+ * for a text of 2^40 bytes or more (the header's share on the host; the records' once the device has scanned their lengths, before
+ * the text is allocated).  A job without an edit gives the header alone and *n_records == 0.  Returns with the context's stream
+ * synchronised.  The object belongs to its context (free it before the context); device memory beyond the text: 2 bytes per
+ * assembly position during the call (6 with multi-byte winners) and 40 per record.
+ *   pp_vcf_out_bytes      the text (DEVICE, borrowed until pp_vcf_out_free): pp_bgzf_deflate(ctx, dev, n_bytes, PP_MEM_DEVICE, ...)
+ *                         makes the bgzipped file
+ *   pp_vcf_out_write      as pp_fasta_out_write: downloads the text in slices and writes it to `path`
+ *   pp_vcf_out_kernel_ms  as pp_fasta_out_kernel_ms: the HIP-event spans of the call's stages on the stream (the host's read-backs and
+ *                         allocations between their launches lie inside them) */
+typedef struct pp_vcf_out pp_vcf_out;
+int pp_polish_vcf(pp_ctx *ctx, const char *const *contig_names, pp_vcf_out **out);
+void pp_vcf_out_bytes(const pp_vcf_out *o, const uint8_t **dev, uint64_t *n_bytes, uint64_t *n_records); /* DEVICE, borrowed */
+int pp_vcf_out_write(const pp_vcf_out *o, const char *path);                                             /* download in slices, write */
+int pp_vcf_out_kernel_ms(const pp_vcf_out *o, float *ms);
+void pp_vcf_out_free(pp_vcf_out *o);
+
 /* Per-kernel device time of the last pp_polish_finish, measured with HIP events on the context's
  * stream when profiling is enabled.  names[i] are static strings. */
 #define PP_MAX_KERNELS 16
@@ -1378,6 +1415,16 @@ int pp_ctx_set_sort_out(pp_ctx *ctx, int on, int index);
  * no such text was made. */
 int pp_ctx_set_fasta_form(pp_ctx *ctx, int64_t width, int bgzf);
 int pp_ctx_fasta_index(pp_ctx *ctx, pp_bytes *fai, pp_bytes *gzi);
+
+/* The polish's edits as a VCF file next to the FASTA (the commands' --vcf, --vcf_bgzf; not in the reference): with on != 0
+ * pp_polish_files, pp_filter_polish_files and pp_polish_files_multi on ONE context run pp_polish_vcf behind their polish, on every
+ * input route, and with bgzf != 0 pass the device text through pp_bgzf_deflate.  The file's bytes stay with the context:
+ * pp_ctx_vcf returns the file of the last such run that succeeded (HOST, release with pp_bytes_free; PP_ERR_ARG when there is none --
+ * a run that begins drops the file of the run before, a run that fails leaves none).  Several contexts are refused by name
+ * (PP_ERR_QUIT "--vcf runs on one GPU ...") before any input is looked at.  The FASTA, the log and every other output are the plain
+ * run's, byte for byte.  The state lives on the context, like pp_ctx_set_fasta_form's; off when the context is made. */
+int pp_ctx_set_vcf(pp_ctx *ctx, int on, int bgzf);
+int pp_ctx_vcf(pp_ctx *ctx, pp_bytes *vcf);
 
 /* polish::polish (src/polish.rs:26-38): FASTA text exactly as the reference prints to stdout.
  * `sams` are SAM text files or -- all of them -- BAM files (pp_aln_file_kind; a mix is PP_ERR_QUIT).  BAM goes through the record

@@ -1087,6 +1087,52 @@ class FastaText(_Owned):
         return self._stage_ms("pp_fasta_out_stage_ms_", ("copy", "text"), " when the text was made")
 
 
+class Vcf(_Owned):
+    """pp_polish_vcf: the edits of the context's finished polish job as VCF 4.2 text in DEVICE memory, owned by this object
+    (tests/vcf_model.py defines the bytes).  Valid after polish_finish and until the next polish_begin, with or without debug records.
+      names          one contig name (bytes / str) per contig of the job
+      .n_records     the records (runs of edited positions)
+      .dev()         (device address, n_bytes) of the text: what BgzfDeflated takes with mem=MEM_DEVICE
+      .bytes()       the text as bytes (a download)
+      .deflate()     pp_bgzf_deflate on the device bytes -> BgzfDeflated
+      .write(path)   pp_vcf_out_write: the text on disk
+      .kernel_ms()   HIP-event time of the kernels (the context had set_profiling on); .stage_ms(): mark | runs | records | text"""
+    _free, _kernel_ms = "pp_vcf_out_free", "pp_vcf_out_kernel_ms"
+
+    def __init__(self, ctx, names):
+        L = lib()
+        enc = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+        arr = (C.c_char_p * max(len(enc), 1))(*enc)
+        super().__init__(ctx)
+        ctx._chk(L.pp_polish_vcf(ctx._h, arr, C.byref(self._p)))
+        dev, nb, nr = C.c_void_p(), C.c_uint64(0), C.c_uint64(0)
+        L.pp_vcf_out_bytes(self._p, C.byref(dev), C.byref(nb), C.byref(nr))
+        self.bytes_ptr, self.n_bytes, self.n_records = dev.value or 0, int(nb.value), int(nr.value)
+
+    def dev(self):
+        return self.bytes_ptr, self.n_bytes
+
+    def bytes(self):
+        return self._ctx.download(self.bytes_ptr, self.n_bytes, np.uint8).tobytes() if self.n_bytes else b""
+
+    def deflate(self):
+        return BgzfDeflated(self._ctx, self.dev(), mem=MEM_DEVICE)
+
+    def write(self, path):
+        self._ctx._chk(lib().pp_vcf_out_write(self._p, os.fsencode(path)))
+
+    def stage_ms(self):
+        return self._stage_ms("pp_vcf_out_stage_ms_", ("mark", "runs", "records", "text"), " when the text was made")
+
+
+def vcf_geometry():
+    """(positions per thread, positions per workgroup, text bytes per store, text bytes per workgroup) of pp_polish_vcf: the position
+    passes cut the assembly, the text pass cuts the text -- the seams its tests aim at."""
+    v = [C.c_uint32() for _ in range(4)]
+    lib().pp_vcf_geometry_(*[C.byref(x) for x in v])
+    return tuple(int(x.value) for x in v)
+
+
 def fasta_out_geometry():
     """(bytes per store S, bytes per workgroup G) of pp_fasta_text: a lane writes S bytes of TEXT with one aligned store, a workgroup
     owns the text offsets [k * G, (k + 1) * G): the seams its tests aim at."""
@@ -1927,6 +1973,40 @@ class Context:
         self._chk(lib().pp_ctx_fasta_index(self._h, C.byref(fai), C.byref(gzi)))
         return _take_bytes(fai), _take_bytes(gzi)
 
+    def set_vcf(self, on=True, bgzf=False):
+        """pp_ctx_set_vcf: polish_files and filter_polish_files run pp_polish_vcf behind their polish (bgzf: pp_bgzf_deflate behind it);
+        vcf() fetches the file"""
+        self._chk(lib().pp_ctx_set_vcf(self._h, int(bool(on)), int(bool(bgzf))))
+
+    def vcf(self):
+        """pp_ctx_vcf: the VCF file (bytes) of the last command that made one on this context"""
+        b = Bytes()
+        self._chk(lib().pp_ctx_vcf(self._h, C.byref(b)))
+        return _take_bytes(b)
+
+    @contextlib.contextmanager
+    def _making_vcf(self, vcf, vcf_bgzf):
+        """vcf= (a path) and vcf_bgzf= of one command: pp_ctx_set_vcf for its duration; the function this yields writes the file once
+        the command has succeeded"""
+        if vcf_bgzf and vcf is None:
+            raise PolypolishError(ERR_QUIT, "vcf_bgzf=True needs vcf=<path>: it compresses the VCF file")
+        if vcf is None:
+            yield lambda: None
+            return
+        self.set_vcf(True, vcf_bgzf)
+
+        def deliver():
+            data = self.vcf()
+            try:
+                with open(vcf, "wb") as f:
+                    f.write(data)
+            except OSError:
+                raise PolypolishError(ERR_QUIT, f'unable to write the VCF to "{os.fspath(vcf)}"') from None
+        try:
+            yield deliver
+        finally:
+            self.set_vcf(False)
+
     @contextlib.contextmanager
     def _writing_bam(self, out_bam):
         """out_bam=True switches pp_ctx_set_out_bam on for one command and off again behind it"""
@@ -1969,42 +2049,48 @@ class Context:
 
     def polish_files(self, assembly, sams, fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5,
                      careful=False, debug=None, quiet=True, regroup=False, text_chain=False, wrap=None, bgzf=False, out=None,
-                     index=False):
+                     index=False, vcf=None, vcf_bgzf=False):
         """polish::polish (pp_polish_files): the FASTA bytes.  wrap / bgzf / out / index (not in the reference): the FASTA at a line
         width (0: one line per contig) and bgzipped, made on the device (pp_fasta_text, pp_bgzf_deflate); also written to `out`,
         with out.fai (and out.gzi) for index.  `sams` are SAM text files, or all of them BAM files (BGZF or
         uncompressed; told by content, aln_file_kind): those go through the record chain on the device, inside the driver.
         regroup: for this call, as set_regroup (coordinate-sorted BAM).  text_chain: for this call, as set_text_chain (SAM text,
-        plain or bgzipped, through the record chain as well)."""
+        plain or bgzipped, through the record chain as well).  vcf / vcf_bgzf (not in the reference): the polish's edits written to
+        the path `vcf` as VCF 4.2 made on the device (pp_polish_vcf), bgzipped with vcf_bgzf."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         arr = (C.c_char_p * max(len(sams), 1))(*[str(s).encode() for s in sams])
         res = Bytes()
-        with self._regrouping(regroup), self._chaining_text(text_chain), self._fasta_form(wrap, bgzf, out, index) as deliver:
+        with self._regrouping(regroup), self._chaining_text(text_chain), self._making_vcf(vcf, vcf_bgzf) as deliver_vcf, \
+                self._fasta_form(wrap, bgzf, out, index) as deliver:
             self._chk(lib().pp_polish_files(self._h, str(assembly).encode(), arr, len(sams), C.byref(opt), C.byref(res)))
             data = _take_bytes(res)
+            deliver_vcf()
             deliver(data)
         return data
 
     def filter_polish_files(self, assembly, in1, in2, out1=None, out2=None, orientation="auto", low=0.1, high=99.9,
                             fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5, careful=False,
                             debug=None, quiet=True, regroup=False, out_bam=False, out_sam=False, text_chain=False, wrap=None,
-                            bgzf=False, out=None, index=False, sort_out=False, out_bai=False):
+                            bgzf=False, out=None, index=False, sort_out=False, out_bai=False, vcf=None, vcf_bgzf=False):
         """filter + polish in one process (pp_filter_polish_files): returns (FASTA bytes, filter report).  wrap / bgzf / out / index:
         as polish_files.  Two BAM inputs are decoded
         once for both halves; out1 / out2 are then BAM files as well.  regroup: for this call, as set_regroup (the polish half).
         out_bam: for this call, as set_out_bam (SAM text inputs, out1 / out2 as compressed BAM).  out_sam: for this call, as
         set_out_sam (BAM inputs, out1 / out2 as SAM text).  text_chain: for this call, as set_text_chain.  sort_out / out_bai: for
-        this call, as set_sort_out (BAM outputs in coordinate order, out1.bai / out2.bai next to them)."""
+        this call, as set_sort_out (BAM outputs in coordinate order, out1.bai / out2.bai next to them).  vcf / vcf_bgzf: as
+        polish_files."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         rep, res = FilterReport(), Bytes()
         enc = lambda x: str(x).encode() if x is not None else None
         with self._regrouping(regroup), self._writing_bam(out_bam), self._writing_sam(out_sam), self._chaining_text(text_chain), \
-                self._sorting_out(sort_out, out_bai), self._fasta_form(wrap, bgzf, out, index) as deliver:
+                self._sorting_out(sort_out, out_bai), self._making_vcf(vcf, vcf_bgzf) as deliver_vcf, \
+                self._fasta_form(wrap, bgzf, out, index) as deliver:
             self._chk(lib().pp_filter_polish_files(self._h, enc(assembly), enc(in1), enc(in2), enc(out1), enc(out2),
                                                    orientation.encode(), low, high, C.byref(opt), C.byref(rep), C.byref(res)))
             data = _take_bytes(res)
+            deliver_vcf()
             deliver(data)
         return data, _report_dict(rep)
 

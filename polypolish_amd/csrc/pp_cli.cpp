@@ -61,6 +61,8 @@ static const char *HELP_POLISH =
     "      --wrap <N>                             Line width of the polished FASTA, made on the device; 0: one line per contig (not in the reference)\n"
     "      --out_bgzf                             Compress the polished FASTA into BGZF blocks on the device (not in the reference)\n"
     "      --index                                With --out: write PATH.fai, and PATH.gzi with --out_bgzf (not in the reference)\n"
+    "      --vcf <PATH>                           Write the polish's edits to PATH as VCF 4.2, made on the device (one GPU; not in the reference)\n"
+    "      --vcf_bgzf                             With --vcf: compress the VCF into BGZF blocks on the device (not in the reference)\n"
     "  -h, --help                                 Print help\n  -V, --version                              Print version\n";
 
 static const char *HELP_FUSED =
@@ -77,7 +79,9 @@ static const char *HELP_FUSED =
     "--out <PATH>: write the polished FASTA to PATH instead of stdout (not in the reference).\n"
     "--wrap <N>: line width of the polished FASTA, made on the device; 0: one line per contig (not in the reference).\n"
     "--out_bgzf: compress the polished FASTA into BGZF blocks on the device (not in the reference).\n"
-    "--index: with --out, write PATH.fai, and PATH.gzi with --out_bgzf (not in the reference).\n";
+    "--index: with --out, write PATH.fai, and PATH.gzi with --out_bgzf (not in the reference).\n"
+    "--vcf <PATH>: write the polish's edits to PATH as VCF 4.2, made on the device (not in the reference).\n"
+    "--vcf_bgzf: with --vcf, compress the VCF into BGZF blocks on the device (not in the reference).\n";
 
 static int usage_error(const char *msg) {
     fprintf(stderr, "error: %s\n\nFor more information, try '--help'.\n", msg);
@@ -215,6 +219,7 @@ static int refuse_index_without_out() {
     fprintf(stderr, "\nError: --index needs --out <PATH>: the indexes are written next to the file (PATH.fai, PATH.gzi)\n");
     return 1;
 }
+static int refuse_vcf_bgzf_without_vcf() { return usage_error("--vcf_bgzf needs --vcf <PATH>: it compresses the VCF file"); }
 static bool write_file(const std::string &path, const uint8_t *data, uint64_t len) {
     FILE *f = fopen(path.c_str(), "wb");
     if (!f) return false;
@@ -240,6 +245,18 @@ static int deliver_fasta(pp_ctx *ctx, const FastaForm &F, const pp_bytes &fasta)
     if (ok) return 0;
     remove(F.out);
     fprintf(stderr, "\nError: unable to write the polished sequence to \"%s\"\n", F.out);
+    return 1;
+}
+// The VCF of a command that succeeded (--vcf; pp_ctx_vcf), written before the FASTA is delivered: created only now, so a refused or
+// failed run leaves no file behind.  0, or 1 with the message on stderr.
+static int deliver_vcf(pp_ctx *ctx, const char *path) {
+    if (!path) return 0;
+    pp_bytes vcf{nullptr, 0};
+    const bool ok = pp_ctx_vcf(ctx, &vcf) == PP_OK && write_file(path, vcf.data, vcf.len);
+    pp_bytes_free(&vcf);
+    if (ok) return 0;
+    remove(path);
+    fprintf(stderr, "\nError: unable to write the VCF to \"%s\"\n", path);
     return 1;
 }
 // the form on a context: --index alone still needs the text's table, so it takes the device link at width 0
@@ -327,7 +344,9 @@ int main(int argc, char **argv) {
                                             {"--out", 0, true, "<PATH>"},
                                             {"--wrap", 0, true, "<N>"},
                                             {"--out_bgzf", 0, false, ""},
-                                            {"--index", 0, false, ""}};
+                                            {"--index", 0, false, ""},
+                                            {"--vcf", 0, true, "<PATH>"},
+                                            {"--vcf_bgzf", 0, false, ""}};
         FastaForm form;
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help) { fputs(HELP_POLISH, stdout); return 0; }
@@ -343,6 +362,9 @@ int main(int argc, char **argv) {
                    take_fasta_form(P, specs, 8, form, perr));
         }
         if (!perr.empty()) return usage_error(perr.c_str());
+        const char *vcf = P.value[12];
+        const bool vcf_bgzf = P.value[13] != nullptr;
+        if (vcf_bgzf && !vcf) return refuse_vcf_bgzf_without_vcf();
         if (form.index && !form.out) return refuse_index_without_out();
         const char *assembly = P.positional.empty() ? nullptr : P.positional[0];
         std::vector<const char *> sams(P.positional.begin() + (P.positional.empty() ? 0 : 1), P.positional.end());
@@ -355,6 +377,10 @@ int main(int argc, char **argv) {
         const bool few = !getenv("PP_GPUS") && !getenv("PP_SHARE_GPU");
         // BAM input runs on one GPU: asking for several is refused whatever the box has
         const bool several = (getenv("PP_GPUS") && atoi(getenv("PP_GPUS")) > 1) || (getenv("PP_SHARE_GPU") && atoi(getenv("PP_SHARE_GPU")) > 1);
+        if (several && vcf) {  // (refused before any file is opened, as BAM input below)
+            fprintf(stderr, "\nError: --vcf runs on one GPU: polish without PP_GPUS / PP_SHARE_GPU, or without --vcf\n");
+            return 1;
+        }
         for (size_t i = 0; several && i < sams.size(); i++) {
             int kind = PP_ALN_SAM;
             if ((text_chain ? pp_aln_file_kind_text(sams[i], &kind) : pp_aln_file_kind(sams[i], &kind)) != PP_OK) continue;
@@ -373,6 +399,7 @@ int main(int argc, char **argv) {
             for (size_t d = 0; d < devs.size(); d++)
                 if (pp_ctx_create_async(devs[d], &cs[d]) || pp_ctx_set_regroup(cs[d], regroup) || pp_ctx_set_text_chain(cs[d], text_chain)) return no_device(devs[d]);
             set_fasta_form(cs[0], form);
+            pp_ctx_set_vcf(cs[0], vcf != nullptr, vcf_bgzf);  // (several contexts: the driver refuses it by name)
             pp_bytes fasta{nullptr, 0};
             int rc = pp_polish_files_multi(cs.data(), (int)cs.size(), assembly, sams.data(), (int)sams.size(), &opt, &fasta);
             for (size_t d = 0; d < devs.size(); d++)
@@ -382,7 +409,7 @@ int main(int argc, char **argv) {
                 for (pp_ctx *c : cs) pp_ctx_destroy(c);
                 return rc == PP_ERR_PANIC ? 101 : 1;
             }
-            if (deliver_fasta(cs[0], form, fasta)) return 1;
+            if (deliver_vcf(cs[0], vcf) || deliver_fasta(cs[0], form, fasta)) return 1;
             return finish(0);
         }
         // the device initialises on a helper thread while the host loads and parses the inputs
@@ -392,6 +419,7 @@ int main(int argc, char **argv) {
         pp_ctx_set_regroup(ctx, regroup);
         pp_ctx_set_text_chain(ctx, text_chain);
         set_fasta_form(ctx, form);
+        pp_ctx_set_vcf(ctx, vcf != nullptr, vcf_bgzf);
         pp_bytes fasta{nullptr, 0};
         rc = pp_polish_files(ctx, assembly, sams.data(), (int)sams.size(), &opt, &fasta);
         if (pp_ctx_wait(ctx) != PP_OK) return no_device(device);
@@ -400,7 +428,7 @@ int main(int argc, char **argv) {
             pp_ctx_destroy(ctx);
             return rc == PP_ERR_PANIC ? 101 : 1;
         }
-        if (deliver_fasta(ctx, form, fasta)) return 1;
+        if (deliver_vcf(ctx, vcf) || deliver_fasta(ctx, form, fasta)) return 1;
         return finish(0);
     }
 
@@ -427,7 +455,9 @@ int main(int argc, char **argv) {
                                             {"--out_bgzf", 0, false, ""},
                                             {"--index", 0, false, ""},
                                             {"--sort_out", 0, false, ""},
-                                            {"--out_bai", 0, false, ""}};
+                                            {"--out_bai", 0, false, ""},
+                                            {"--vcf", 0, true, "<PATH>"},
+                                            {"--vcf_bgzf", 0, false, ""}};
         FastaForm form;
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help || P.version) { fputs(HELP_FUSED, stdout); return 0; }
@@ -450,6 +480,9 @@ int main(int argc, char **argv) {
             return usage_error("the following required arguments were not provided:\n  --in1 <IN1> --in2 <IN2> <ASSEMBLY>");
         if (form.index && !form.out) return refuse_index_without_out();
         if (P.value[22] && !P.value[21]) return refuse_bai_without_sort();
+        const char *vcf = P.value[23];
+        const bool vcf_bgzf = P.value[24] != nullptr;
+        if (vcf_bgzf && !vcf) return refuse_vcf_bgzf_without_vcf();
         pp_ctx *ctx = nullptr;
         int rc = pp_ctx_create_async(device, &ctx);
         if (rc) return no_device(device);
@@ -459,6 +492,7 @@ int main(int argc, char **argv) {
         pp_ctx_set_out_sam(ctx, P.value[15] != nullptr);
         pp_ctx_set_text_chain(ctx, P.value[16] != nullptr);
         set_fasta_form(ctx, form);
+        pp_ctx_set_vcf(ctx, vcf != nullptr, vcf_bgzf);
         pp_bytes fasta{nullptr, 0};
         rc = pp_filter_polish_files(ctx, assembly, in1, in2, out1, out2, orientation, low, high, &opt, nullptr, &fasta);
         if (pp_ctx_wait(ctx) != PP_OK) return no_device(device);
@@ -467,7 +501,7 @@ int main(int argc, char **argv) {
             pp_ctx_destroy(ctx);
             return rc == PP_ERR_PANIC ? 101 : 1;
         }
-        if (deliver_fasta(ctx, form, fasta)) return 1;
+        if (deliver_vcf(ctx, vcf) || deliver_fasta(ctx, form, fasta)) return 1;
         return finish(0);
     }
 

@@ -422,6 +422,32 @@ static int write_fasta_form_and_log(PolishJob &J, pp_bytes *fasta) {
     return PP_OK;
 }
 
+// The VCF of pp_ctx_set_vcf: pp_polish_vcf on the finished job, pp_bgzf_deflate on the device text with bgzf, one copy off the
+// device; the bytes stay with the context (pp_ctx_vcf).  Nothing is logged.
+static int make_vcf(PolishJob &J, int bgzf) {
+    pp_ctx *const ctx = J.ctx;
+    pp_vcf_out *text = nullptr;
+    pp_bgzf_out *z = nullptr;
+    const uint8_t *dev = nullptr;
+    uint64_t n = 0;
+    int rc = pp_polish_vcf(ctx, J.names.data(), &text);
+    if (rc == PP_OK) pp_vcf_out_bytes(text, &dev, &n, nullptr);
+    if (rc == PP_OK && bgzf) {
+        rc = pp_bgzf_deflate(ctx, dev, n, PP_MEM_DEVICE, &z);
+        if (rc == PP_OK) pp_bgzf_out_bytes(z, &dev, &n);
+    }
+    std::vector<uint8_t> host;
+    if (rc == PP_OK) {
+        host.resize((size_t)n + 1);
+        if (n) rc = pp_ctx_download(ctx, host.data(), dev, n);
+    }
+    if (rc == PP_OK) pp_ctx_keep_vcf_(ctx, host.data(), n);
+    pp_bgzf_out_free(z);
+    pp_vcf_out_free(text);
+    J.lap(bgzf ? "VCF made and compressed on the device" : "VCF made on the device");
+    return rc;
+}
+
 // finished_message, polish.rs:76-90
 static void log_finished(const PolishJob &J) {
     const char *to = pp_ctx_fasta_out_name_(J.ctx);
@@ -434,6 +460,11 @@ static void log_finished(const PolishJob &J) {
 // polish::polish (src/polish.rs:26-38) for one look at the input.  HAND_BACK: nothing was polished, the host ingest is to
 // take the input, its log resuming at file J.handed_back_at.
 static int polish_once(PolishJob &J, pp_bytes *fasta) {
+    int vcf_bgzf = 0;
+    const bool vcf_on = pp_ctx_vcf_form_(J.ctx, &vcf_bgzf) != 0;
+    pp_ctx_keep_vcf_(J.ctx, nullptr, 0);  // (the file of the run before)
+    if (vcf_on && J.n_ctx > 1)  // (a rank's share has no defined runs at its edges: pp_polish_vcf)
+        return set_err(J.ctx, PP_ERR_QUIT, "--vcf runs on one GPU: polish without PP_GPUS / several contexts, or without --vcf");
     if (int rc = check_options_and_inputs(J)) return rc;
     log_banner(J);
     J.lap("driver entered");
@@ -447,6 +478,8 @@ static int polish_once(PolishJob &J, pp_bytes *fasta) {
     if (int rc = create_debug_file(J)) return rc;
     if (int rc = several_contexts(J.route) ? polish_on_several_contexts(J) : polish_on_one_context(J)) return rc;
     J.lap(J.direct_fetch ? "result: offsets fetched" : "result fetched");
+    if (vcf_on)
+        if (int rc = make_vcf(J, vcf_bgzf)) return rc;
     if (int rc = J.form_on ? write_fasta_form_and_log(J, fasta) : write_fasta_and_log(J, fasta)) return rc;
     log_finished(J);
     J.release();

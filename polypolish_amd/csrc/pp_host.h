@@ -35,6 +35,8 @@ int pp_ctx_regroup_(const pp_ctx *ctx);                         // what pp_ctx_s
 int pp_ctx_text_chain_(const pp_ctx *ctx);                      // what pp_ctx_set_text_chain was given (the file drivers)
 int pp_ctx_fasta_form_(const pp_ctx *ctx, int64_t *width, int *bgzf);  // what pp_ctx_set_fasta_form was given; 1 when the form is on (the file drivers)
 void pp_ctx_keep_fasta_index_(pp_ctx *ctx, const uint8_t *fai, uint64_t n_fai, const uint8_t *gzi, uint64_t n_gzi);  // ... and the indexes of the text they made
+int pp_ctx_vcf_form_(const pp_ctx *ctx, int *bgzf);             // what pp_ctx_set_vcf was given; 1 when the VCF is on (the file drivers)
+void pp_ctx_keep_vcf_(pp_ctx *ctx, const uint8_t *data, uint64_t n);  // ... and the file they made (NULL: none -- a run begins)
 int pp_ctx_set_fasta_out_name_(pp_ctx *ctx, const char *path);  // the file the caller will write the FASTA to (NULL: stdout); the log names it
 const char *pp_ctx_fasta_out_name_(const pp_ctx *ctx);
 int pp_sam_empty_qname_rule_(pp_sam *s);                        // pp_sam.hip: read_id as the reference groups behind an empty QNAME (the text front, for the gate)

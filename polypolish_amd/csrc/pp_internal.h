@@ -278,6 +278,10 @@ struct pp_ctx {
     bool fasta_bgzf = false;
     bool fasta_indexed = false;         // a driver has made such a text: fasta_fai / fasta_gzi are its indexes (pp_ctx_fasta_index)
     std::string fasta_fai, fasta_gzi;
+    // pp_ctx_set_vcf: the file drivers run pp_polish_vcf behind their polish (and pp_bgzf_deflate behind it); vcf_bytes is the file
+    // of the last such run that succeeded (pp_ctx_vcf), dropped when the next run begins
+    bool vcf_on = false, vcf_bgzf = false, vcf_made = false;
+    std::string vcf_bytes;
     std::string fasta_out_name;         // pp_ctx_set_fasta_out_name_: where the caller will write the FASTA (the log's last section names it)
     pp::DevBuf f_thr;  // pp_filter_thresholds: orientation counts | the selection's state | its two histograms (THR_WORDS u32)
     pp_filter_input fdev{};

@@ -36,6 +36,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 
 // The kernels, in pipeline order (one translation unit: everything below is static or inlined)
 #include "pp_k_common.h"
@@ -46,6 +47,8 @@
 #include "pp_k_exact.h"
 #include "pp_k_emit.h"
 #include "pp_k_debug.h"
+#include "pp_k_vcf.h"
+#include "pp_vcf_host.h"
 #include <hip/hip_ext.h>
 
 // =============================================================================================
@@ -1640,6 +1643,217 @@ extern "C" int pp_polish_debug_tsv(pp_ctx *ctx, const char *const *contig_names,
     *len = written;
     *pos_next = p;
     return PP_OK;
+}
+
+// ---- the polish's edits as VCF text on the device (pp_k_vcf.h, pp_vcf_host.h) ---------------------------------------------
+struct pp_vcf_out {
+    pp_ctx *ctx = nullptr;
+    u8 *text = nullptr;  // DEVICE, n_text bytes (allocated up to a multiple of 16)
+    uint64_t n_text = 0, n_records = 0;
+    bool timed = false;
+    float ms[4] = {0.f, 0.f, 0.f, 0.f};  // mark | runs | records | text
+};
+
+namespace {
+struct VcfScratch {  // the call's device memory and timing events, released when it returns
+    std::vector<void *> p;
+    std::vector<hipEvent_t> ev;
+    ~VcfScratch() {
+        for (void *q : p) (void)hipFree(q);
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+    template <class T>
+    int get(pp_ctx *ctx, T *&a, size_t count) {
+        void *q = nullptr;
+        a = nullptr;
+        PP_HIPCHK(ctx, hipMalloc(&q, std::max<size_t>(count * sizeof(T), 16)));
+        p.push_back(q);
+        a = (T *)q;
+        return PP_OK;
+    }
+    int mark(pp_ctx *ctx) {  // an event on the stream (profiling only): stage s lies between marks s and s + 1
+        if (!ctx->profiling) return PP_OK;
+        hipEvent_t e = nullptr;
+        PP_HIPCHK(ctx, hipEventCreate(&e));
+        ev.push_back(e);
+        PP_HIPCHK(ctx, hipEventRecord(e, ctx->stream));
+        return PP_OK;
+    }
+};
+}  // namespace
+
+extern "C" void pp_vcf_out_free(pp_vcf_out *o) {
+    if (!o) return;
+    if (o->text) {
+        (void)hipSetDevice(o->ctx->device);
+        (void)hipFree(o->text);
+    }
+    delete o;
+}
+
+extern "C" void pp_vcf_out_bytes(const pp_vcf_out *o, const uint8_t **dev, uint64_t *n_bytes, uint64_t *n_records) {
+    if (dev) *dev = o ? o->text : nullptr;
+    if (n_bytes) *n_bytes = o ? o->n_text : 0;
+    if (n_records) *n_records = o ? o->n_records : 0;
+}
+
+extern "C" int pp_vcf_out_write(const pp_vcf_out *o, const char *path) {
+    if (!o || !o->ctx) return PP_ERR_ARG;
+    if (!path) return o->ctx->fail(PP_ERR_ARG, "pp_vcf_out_write: null argument");
+    return write_device_file(o->ctx, "pp_vcf_out_write", o->text, o->n_text, path);
+}
+
+extern "C" int pp_vcf_out_kernel_ms(const pp_vcf_out *o, float *ms) {
+    if (!o || !ms) return PP_ERR_ARG;
+    if (!o->timed) return o->ctx->fail(PP_ERR_ARG, "pp_vcf_out_kernel_ms: the context had no profiling on when the text was made (pp_ctx_set_profiling)");
+    *ms = o->ms[0] + o->ms[1] + o->ms[2] + o->ms[3];
+    return PP_OK;
+}
+
+// (internal hooks, not part of the header) the time by stage: mark | runs | records | text (tools/vcf_timing.py); the geometry:
+// positions per thread and per workgroup of the position passes, text bytes per store and per workgroup (the tests)
+extern "C" int pp_vcf_out_stage_ms_(const pp_vcf_out *o, float *ms4) {
+    if (!o || !ms4 || !o->timed) return PP_ERR_ARG;
+    std::copy(o->ms, o->ms + 4, ms4);
+    return PP_OK;
+}
+extern "C" void pp_vcf_geometry_(uint32_t *pos_per_thread, uint32_t *pos_per_workgroup, uint32_t *bytes_per_store, uint32_t *bytes_per_workgroup) {
+    if (pos_per_thread) *pos_per_thread = VCF_PPT;
+    if (pos_per_workgroup) *pos_per_workgroup = VCF_TILE;
+    if (bytes_per_store) *bytes_per_store = VCF_LANE;
+    if (bytes_per_workgroup) *bytes_per_workgroup = VCF_TEXT_WG;
+}
+
+extern "C" int pp_polish_vcf(pp_ctx *ctx, const char *const *contig_names, pp_vcf_out **out) {
+    if (!ctx) return PP_ERR_ARG;
+    if (int rdy = pp_ctx_wait(ctx)) return rdy;
+    if (out) *out = nullptr;
+    // ---- the host's part, all of it before anything is launched ----
+    pp_vcf_host::Plan plan;
+    char msg[256] = "";
+    const pp_vcf_host::JobState S{ctx->job_done, !ctx->emit.empty() || !ctx->run_full_of.empty()};
+    if (int code = pp_vcf_host::plan(out != nullptr, S, ctx->n_contigs, ctx->contig_off.data(), contig_names, pp_version(), plan, msg, sizeof msg))
+        return ctx->fail(code, "%s", msg);
+    PP_HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint64_t G = ctx->G, H = plan.header.size(), nm = ctx->n_multi;
+    const uint32_t nc = ctx->n_contigs;
+    std::unique_ptr<pp_vcf_out, void (*)(pp_vcf_out *)> P(new pp_vcf_out(), pp_vcf_out_free);
+    P->ctx = ctx;
+    VcfScratch T;
+    int rc;
+    uint64_t n_rec = 0, rec_bytes = 0;
+    VcfRec *d_rec = nullptr;
+    u64 *d_rec_at = nullptr, *d_noff = nullptr;
+    VcfJob J;
+    J.bases = ctx->d_bases; J.code = (const u8 *)ctx->b_code.p; J.out = (const u8 *)ctx->b_out.p; J.mlen = nullptr;
+    J.contig_off = (const u64 *)ctx->b_contig_off.p; J.nc = nc; J.G = G; J.total_out = ctx->total_out;
+    if ((rc = T.mark(ctx))) return rc;
+    if (G) {
+        const uint64_t nb = (G + VCF_TILE - 1) / VCF_TILE;  // (below 2^21: G is below 2^32)
+        u8 *d_flag = nullptr, *d_flag2 = nullptr;
+        u64 *d_bsum = nullptr, *d_boff = nullptr, *d_roff = nullptr;
+        u32 *d_mlen = nullptr;
+        if ((rc = T.get(ctx, d_flag, nb * VCF_TILE)) || (rc = T.get(ctx, d_flag2, nb * VCF_TILE)) || (rc = T.get(ctx, d_bsum, nb)) ||
+            (rc = T.get(ctx, d_boff, nb + 1)) || (rc = T.get(ctx, d_roff, nb + 1)))
+            return rc;
+        if (nm) {
+            if ((rc = T.get(ctx, d_mlen, G))) return rc;
+            hipLaunchKernelGGL(k_vcf_multi, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, st, (const MultiEnt *)ctx->b_multi.p, (u32)nm, J.code, (u64)G, d_mlen);
+            J.mlen = d_mlen;
+        }
+        hipLaunchKernelGGL(k_vcf_sum, dim3((unsigned)nb), dim3(VCF_THREADS), 0, st, J, d_bsum);
+        hipLaunchKernelGGL(k_dfmt_scan1, dim3(1), dim3(1024), 0, st, (const u64 *)d_bsum, (u64)nb, d_boff);
+        hipLaunchKernelGGL(k_vcf_mark, dim3((unsigned)nb), dim3(VCF_THREADS), 0, st, J, (const u64 *)d_boff, d_flag);
+        if ((rc = T.mark(ctx))) return rc;
+        hipLaunchKernelGGL(k_vcf_runs, dim3((unsigned)nb), dim3(VCF_THREADS), 0, st, J, (const u8 *)d_flag, d_flag2, d_bsum);
+        hipLaunchKernelGGL(k_dfmt_scan1, dim3(1), dim3(1024), 0, st, (const u64 *)d_bsum, (u64)nb, d_roff);
+        if ((rc = T.mark(ctx))) return rc;
+        PP_HIPCHK(ctx, hipGetLastError());
+        PP_HIPCHK(ctx, hipMemcpyAsync(&n_rec, d_roff + nb, 8, hipMemcpyDeviceToHost, st));
+        PP_HIPCHK(ctx, hipStreamSynchronize(st));
+        if (n_rec) {
+            const uint64_t nbr = (n_rec + VCF_THREADS - 1) / VCF_THREADS;
+            u64 *d_rsum = nullptr, *d_rsoff = nullptr;
+            if ((rc = T.get(ctx, d_rec, n_rec)) || (rc = T.get(ctx, d_rec_at, n_rec + 1)) || (rc = T.get(ctx, d_rsum, nbr)) ||
+                (rc = T.get(ctx, d_rsoff, nbr + 1)) || (rc = T.get(ctx, d_noff, (size_t)nc + 1)))
+                return rc;
+            PP_HIPCHK(ctx, hipMemsetAsync(d_rec, 0, n_rec * sizeof(VcfRec), st));
+            PP_HIPCHK(ctx, hipMemcpyAsync(d_noff, plan.name_off.data(), ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_vcf_recs, dim3((unsigned)nb), dim3(VCF_THREADS), 0, st, J, (const u8 *)d_flag2, (const u64 *)d_boff, (const u64 *)d_roff, (u64)n_rec, d_rec);
+            hipLaunchKernelGGL(k_vcf_reclen, dim3((unsigned)nbr), dim3(VCF_THREADS), 0, st, (const VcfRec *)d_rec, (u64)n_rec, J.contig_off, nc, (const u64 *)d_noff, d_rec_at, d_rsum);
+            hipLaunchKernelGGL(k_dfmt_scan1, dim3(1), dim3(1024), 0, st, (const u64 *)d_rsum, (u64)nbr, d_rsoff);
+            hipLaunchKernelGGL(k_vcf_recoff, dim3((unsigned)nbr), dim3(VCF_THREADS), 0, st, (u64)n_rec, (const u64 *)d_rsoff, (u64)H, d_rec_at);
+            PP_HIPCHK(ctx, hipGetLastError());
+            PP_HIPCHK(ctx, hipMemcpyAsync(&rec_bytes, d_rsoff + nbr, 8, hipMemcpyDeviceToHost, st));
+            PP_HIPCHK(ctx, hipStreamSynchronize(st));
+            P->n_records = n_rec;
+        }
+    } else {
+        if ((rc = T.mark(ctx)) || (rc = T.mark(ctx))) return rc;
+    }
+    if ((rc = T.mark(ctx))) return rc;
+    uint64_t n_text = 0;
+    if (int code = pp_vcf_host::text_size(H, rec_bytes, &n_text, msg, sizeof msg)) return ctx->fail(code, "%s", msg);
+    {
+        void *q = nullptr;
+        const size_t room = (size_t)((n_text + 15u) & ~15ull);
+        PP_HIPCHK(ctx, hipMalloc(&q, std::max<size_t>(room, 16)));
+        P->text = (u8 *)q;
+        P->n_text = n_text;
+        PP_HIPCHK(ctx, hipMemsetAsync(q, 0, std::max<size_t>(room, 16), st));
+    }
+    u8 *d_hdr = nullptr, *d_names = nullptr;
+    if ((rc = T.get(ctx, d_hdr, (size_t)((H + 15u) & ~15ull))) || (rc = T.get(ctx, d_names, plan.names.size()))) return rc;
+    PP_HIPCHK(ctx, hipMemcpyAsync(d_hdr, plan.header.data(), H, hipMemcpyHostToDevice, st));
+    if (!plan.names.empty()) PP_HIPCHK(ctx, hipMemcpyAsync(d_names, plan.names.data(), plan.names.size(), hipMemcpyHostToDevice, st));
+    {
+        VcfText X;
+        X.bases = J.bases; X.out = J.out; X.hdr = d_hdr; X.names = d_names;
+        X.name_off = d_noff;
+        X.contig_off = J.contig_off; X.rec_at = d_rec_at; X.rec = d_rec;
+        X.nc = nc; X.n_rec = n_rec; X.G = G; X.total_out = ctx->total_out; X.H = H; X.n_text = n_text;
+        const uint64_t nwg = (n_text + VCF_TEXT_WG - 1) / VCF_TEXT_WG;  // (below 2^26: the text is below 2^40)
+        hipLaunchKernelGGL(k_vcf_text, dim3((unsigned)nwg), dim3(VCF_THREADS), 0, st, X, P->text);
+        PP_HIPCHK(ctx, hipGetLastError());
+    }
+    if ((rc = T.mark(ctx))) return rc;
+    PP_HIPCHK(ctx, hipStreamSynchronize(st));  // the header's and the names' host bytes may go, the scratch goes away
+    if (ctx->profiling && T.ev.size() == 5) {
+        for (int s = 0; s < 4; s++) PP_HIPCHK(ctx, hipEventElapsedTime(&P->ms[s], T.ev[s], T.ev[s + 1]));
+        P->timed = true;
+    }
+    *out = P.release();
+    return PP_OK;
+}
+
+// ---- the file drivers' VCF (pp_driver.cpp) ----
+extern "C" int pp_ctx_set_vcf(pp_ctx *ctx, int on, int bgzf) {
+    if (!ctx) return PP_ERR_ARG;
+    ctx->vcf_on = on != 0;
+    ctx->vcf_bgzf = on != 0 && bgzf != 0;
+    return PP_OK;
+}
+extern "C" int pp_ctx_vcf(pp_ctx *ctx, pp_bytes *vcf) {
+    if (!ctx) return PP_ERR_ARG;
+    if (!vcf) return ctx->fail(PP_ERR_ARG, "pp_ctx_vcf: null argument");
+    *vcf = pp_bytes{nullptr, 0};
+    if (!ctx->vcf_made) return ctx->fail(PP_ERR_ARG, "pp_ctx_vcf: no driver has made a VCF with pp_ctx_set_vcf on this context");
+    vcf->data = (uint8_t *)malloc(ctx->vcf_bytes.size() + 1);
+    if (!vcf->data) return ctx->fail(PP_ERR_HIP, "pp_ctx_vcf: out of host memory");
+    memcpy(vcf->data, ctx->vcf_bytes.data(), ctx->vcf_bytes.size());
+    vcf->len = ctx->vcf_bytes.size();
+    return PP_OK;
+}
+// (internal, the file drivers) what pp_ctx_set_vcf was given; the file a driver made (data == NULL: none, the run begins or failed)
+extern "C" int pp_ctx_vcf_form_(const pp_ctx *ctx, int *bgzf) {
+    if (bgzf) *bgzf = ctx && ctx->vcf_bgzf ? 1 : 0;
+    return ctx && ctx->vcf_on ? 1 : 0;
+}
+extern "C" void pp_ctx_keep_vcf_(pp_ctx *ctx, const uint8_t *data, uint64_t n) {
+    ctx->vcf_made = data != nullptr;
+    ctx->vcf_bytes.assign(data ? (const char *)data : "", data ? (size_t)n : 0);
+    if (!data) ctx->vcf_bytes.shrink_to_fit();
 }
 
 // (internal, the drivers) pinned host memory for the --debug TSV's chunks
