@@ -1019,6 +1019,57 @@ int pp_vcf_out_write(const pp_vcf_out *o, const char *path);                    
 int pp_vcf_out_kernel_ms(const pp_vcf_out *o, float *ms);
 void pp_vcf_out_free(pp_vcf_out *o);
 
+/* ---- undecided regions: the per-position outcome as BED text and as a soft mask, on the device (pp_k_bed.h; not in the reference) ----
+ * A polish decides one of six outcomes per assembly position (PP_ST_*, src/pileup.rs:111-129).  pp_status_bed writes the runs of equal
+ * status as BED text in device memory; pp_polish_bed does so for the finished job's own status plane; pp_polish_masked gives a copy of
+ * the job's polished bytes in which the bytes of selected positions are in lower case (FASTA soft-masking).  tests/bed_model.py
+ * defines the bytes:
+ *   text       no header line.  Per record, in assembly order:  name \t start \t end \t word \n  -- start and end 0-based, half-open and
+ *              local to the contig; word is the reference's own: kept, changed, low_depth, none, multiple, too_close
+ *   record     a maximal run of consecutive positions of ONE contig (runs never join across a contig boundary) that share one status
+ *              whose bit (1 << PP_ST_x) is set in status_mask.  Two different selected statuses side by side are two records.
+ *              Names are written verbatim
+ *   masked     position p emits e(p) bytes of the polished output (the scan of the emitted lengths gives where); every byte 'A'..'Z'
+ *              emitted by a position whose status is selected becomes lower case, a multi-byte winner whole; a position that emits
+ *              nothing changes nothing; every other byte is the job's.  The job's own polished bytes stay as they are
+ * pp_status_bed: `status` holds G = contig_off[n_contigs] bytes (PP_MEM_HOST: uploaded; PP_MEM_DEVICE: read in place, at any
+ * alignment, and no byte outside [0, G) is loaded, by a wide load either: the array may end where its allocation ends); contig_off
+ * (HOST, n_contigs + 1 entries from 0 on) and contig_names (one NUL-terminated name per contig) as for pp_polish_vcf.  pp_polish_bed
+ * and pp_polish_masked are valid after a successful pp_polish_finish of a job that ran with pp_polish_set_debug(ctx, 1), and until the
+ * next pp_polish_begin, whichever path the job took.
+ * Refusals, decided on the host before anything is launched except the last two: PP_ERR_ARG for a null argument, PP_MEM_PEER, a mask of
+ * 0 or one with a bit above 5, contig_off[0] != 0, offsets that decrease, G >= 2^32, a name that holds a tab or a newline; for the two
+ * pp_polish_* calls a context without a finished job (a job that ended in an error leaves none), a job finished without
+ * pp_polish_set_debug(ctx, 1) (it kept no status), a context with pp_polish_set_emit ranges (a rank's share has no defined runs at its
+ * edges); a status byte above 5, *bad_pos = the first such position (a device check; bad_pos may be NULL); PP_ERR_LIMIT for a text of
+ * 2^40 bytes or more (known once the device has scanned the lines' lengths, before the text is allocated).  n_contigs == 0, or no
+ * selected position, gives an empty text and *n_records == 0.  Both calls return with the context's stream synchronised.  The objects
+ * belong to their context (free them before the context).  Device memory beyond the results: 24 bytes per record during pp_status_bed
+ * (G bytes more for a PP_MEM_HOST array); 4 bytes per position during pp_polish_masked when the job has multi-byte winners.
+ *   pp_bed_out_bytes      the text (DEVICE, borrowed until pp_bed_out_free): pp_bgzf_deflate(ctx, dev, n_bytes, PP_MEM_DEVICE, ...) makes
+ *                         the bgzipped file
+ *   pp_bed_out_counts     positions[s] = the positions of status s inside the records (their summed lengths)
+ *   pp_bed_out_write      as pp_vcf_out_write
+ *   pp_bed_out_kernel_ms  as pp_vcf_out_kernel_ms: the HIP-event spans of the call's stages (the context had pp_ctx_set_profiling on)
+ *   pp_masked_bytes       the bytes (DEVICE, borrowed until pp_masked_free), n_bytes = pp_polish_result_size: laid out as the job's own,
+ *                         pp_polish_result's contig_out_off holds for them */
+#define PP_BED_UNDECIDED ((1u << PP_ST_LOW_DEPTH) | (1u << PP_ST_NONE) | (1u << PP_ST_MULTIPLE) | (1u << PP_ST_TOO_CLOSE))
+typedef struct pp_bed_out pp_bed_out;
+int pp_status_bed(pp_ctx *ctx, const uint8_t *status, int mem, uint32_t n_contigs, const uint64_t *contig_off /*HOST*/,
+                  const char *const *contig_names, uint32_t status_mask, pp_bed_out **out, uint64_t *bad_pos);
+int pp_polish_bed(pp_ctx *ctx, const char *const *contig_names, uint32_t status_mask, pp_bed_out **out);
+void pp_bed_out_bytes(const pp_bed_out *o, const uint8_t **dev, uint64_t *n_bytes, uint64_t *n_records); /* DEVICE, borrowed */
+void pp_bed_out_counts(const pp_bed_out *o, uint64_t positions[6]);
+int pp_bed_out_write(const pp_bed_out *o, const char *path);
+int pp_bed_out_kernel_ms(const pp_bed_out *o, float *ms);
+void pp_bed_out_free(pp_bed_out *o);
+
+typedef struct pp_masked pp_masked;
+int pp_polish_masked(pp_ctx *ctx, uint32_t status_mask, pp_masked **out);
+void pp_masked_bytes(const pp_masked *o, const uint8_t **dev, uint64_t *n_bytes); /* DEVICE, borrowed */
+int pp_masked_kernel_ms(const pp_masked *o, float *ms);
+void pp_masked_free(pp_masked *o);
+
 /* Per-kernel device time of the last pp_polish_finish, measured with HIP events on the context's
  * stream when profiling is enabled.  names[i] are static strings. */
 #define PP_MAX_KERNELS 16
@@ -1425,6 +1476,20 @@ int pp_ctx_fasta_index(pp_ctx *ctx, pp_bytes *fai, pp_bytes *gzi);
  * run's, byte for byte.  The state lives on the context, like pp_ctx_set_fasta_form's; off when the context is made. */
 int pp_ctx_set_vcf(pp_ctx *ctx, int on, int bgzf);
 int pp_ctx_vcf(pp_ctx *ctx, pp_bytes *vcf);
+
+/* The undecided regions as a BED file next to the FASTA, and the FASTA soft-masked (the commands' --bed, --bed_bgzf, --soft_mask,
+ * --bed_status; not in the reference).  With pp_ctx_set_bed(on != 0) pp_polish_files, pp_filter_polish_files and
+ * pp_polish_files_multi on ONE context keep the job's per-position status (as for a --debug file; no TSV is written unless the
+ * options ask for one), run pp_polish_bed with status_mask behind their polish, on every input route, and with bgzf != 0 pass the
+ * device text through pp_bgzf_deflate; pp_ctx_bed returns the file of the last such run that succeeded (HOST, release with
+ * pp_bytes_free; PP_ERR_ARG when there is none -- a run that begins drops the file of the run before, a run that fails leaves none).
+ * With pp_ctx_set_soft_mask(status_mask != 0) the FASTA's sequence bytes come from pp_polish_masked in every form (plain, wrapped,
+ * bgzipped, indexed); headers, the log and a VCF of the same run are the plain run's, byte for byte; 0 switches it off.  Several
+ * contexts are refused by name (PP_ERR_QUIT "--bed runs on one GPU ...", "--soft_mask runs on one GPU ...") before any input is
+ * looked at.  PP_ERR_ARG: a mask of 0 with on != 0, a mask with a bit above 5.  The state lives on the context; off when it is made. */
+int pp_ctx_set_bed(pp_ctx *ctx, int on, uint32_t status_mask, int bgzf);
+int pp_ctx_bed(pp_ctx *ctx, pp_bytes *bed);
+int pp_ctx_set_soft_mask(pp_ctx *ctx, uint32_t status_mask);   /* 0 = off */
 
 /* polish::polish (src/polish.rs:26-38): FASTA text exactly as the reference prints to stdout.
  * `sams` are SAM text files or -- all of them -- BAM files (pp_aln_file_kind; a mix is PP_ERR_QUIT).  BAM goes through the record

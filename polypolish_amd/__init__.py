@@ -1133,6 +1133,113 @@ def vcf_geometry():
     return tuple(int(x.value) for x in v)
 
 
+STATUS_WORDS = ("kept", "changed", "low_depth", "none", "multiple", "too_close")  # PP_ST_* in order: the reference's own words
+BED_UNDECIDED = (1 << 2) | (1 << 3) | (1 << 4) | (1 << 5)  # PP_BED_UNDECIDED: low_depth, none, multiple, too_close
+
+
+def bed_status_mask(bed_status):
+    """the status mask of a bed_status= argument: None (the four undecided ones), an int mask, a comma-separated list of the six
+    words (the commands' --bed_status) or a sequence of them"""
+    if bed_status is None:
+        return BED_UNDECIDED
+    if isinstance(bed_status, (int, np.integer)):
+        return int(bed_status)
+    words = (bed_status.split(",") if bed_status else []) if isinstance(bed_status, str) else list(bed_status)
+    if not words:
+        raise PolypolishError(ERR_QUIT, "bed_status: an empty status list")
+    mask = 0
+    for w in words:
+        if w not in STATUS_WORDS:
+            raise PolypolishError(ERR_QUIT, f"bed_status: '{w}' is not one of {', '.join(STATUS_WORDS)}")
+        mask |= 1 << STATUS_WORDS.index(w)
+    return mask
+
+
+class StatusBed(_Owned):
+    """pp_polish_bed / pp_status_bed: the runs of equal per-position status as BED text in DEVICE memory, owned by this object
+    (tests/bed_model.py defines the bytes).
+      StatusBed(ctx, names, mask)                      of the context's finished job (it ran with debug records: polish_records(debug=True))
+      StatusBed(ctx, names, mask, status, contig_off)  of a caller's status bytes: a numpy uint8 array (mem=MEM_HOST) or a device
+                                                       address (mem=MEM_DEVICE); .bad_pos holds the first bad position when refused
+      names          one contig name (bytes / str) per contig;  mask: bits 1 << PP_ST_x (default: the four undecided ones)
+      .n_records, .n_bytes, .counts (positions per status inside the records)
+      .dev() / .bytes() / .deflate() / .write(path) / .kernel_ms() / .stage_ms() (runs | records | text): as Vcf"""
+    _free, _kernel_ms = "pp_bed_out_free", "pp_bed_out_kernel_ms"
+
+    def __init__(self, ctx, names, mask=BED_UNDECIDED, status=None, contig_off=None, mem=MEM_HOST):
+        L = lib()
+        enc = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+        arr = (C.c_char_p * max(len(enc), 1))(*enc)
+        super().__init__(ctx)
+        self.bad_pos = None
+        if status is None:
+            ctx._chk(L.pp_polish_bed(ctx._h, C.cast(arr, C.c_void_p), int(mask), C.byref(self._p)))
+        else:
+            off = np.ascontiguousarray(contig_off, dtype=np.uint64)
+            if mem == MEM_HOST:
+                keep = np.ascontiguousarray(status, dtype=np.uint8)
+                ptr = keep.ctypes.data if keep.size else C.addressof(C.c_uint8())  # (nobody reads it: any address but NULL)
+            else:
+                ptr = int(status)
+            bad = C.c_uint64(0)
+            rc = L.pp_status_bed(ctx._h, ptr, mem, len(off) - 1, off.ctypes.data, C.cast(arr, C.c_void_p), int(mask), C.byref(self._p), C.byref(bad))
+            if rc:
+                self.bad_pos = int(bad.value)
+                e = PolypolishError(rc, L.pp_last_error(ctx._h).decode())
+                e.bad_pos = self.bad_pos
+                raise e
+        dev, nb, nr = C.c_void_p(), C.c_uint64(0), C.c_uint64(0)
+        L.pp_bed_out_bytes(self._p, C.byref(dev), C.byref(nb), C.byref(nr))
+        self.bytes_ptr, self.n_bytes, self.n_records = dev.value or 0, int(nb.value), int(nr.value)
+        cnt = (C.c_uint64 * 6)()
+        L.pp_bed_out_counts(self._p, cnt)
+        self.counts = tuple(int(x) for x in cnt)
+
+    def dev(self):
+        return self.bytes_ptr, self.n_bytes
+
+    def bytes(self):
+        return self._ctx.download(self.bytes_ptr, self.n_bytes, np.uint8).tobytes() if self.n_bytes else b""
+
+    def deflate(self):
+        return BgzfDeflated(self._ctx, self.dev(), mem=MEM_DEVICE)
+
+    def write(self, path):
+        self._ctx._chk(lib().pp_bed_out_write(self._p, os.fsencode(path)))
+
+    def stage_ms(self):
+        return self._stage_ms("pp_bed_out_stage_ms_", ("runs", "records", "text"), " when the text was made")
+
+
+class Masked(_Owned):
+    """pp_polish_masked: a copy of the finished job's polished bytes in DEVICE memory in which every byte emitted by a position whose
+    status is selected by `mask` is in lower case (the job ran with debug records).  .dev(): (address, n_bytes); .bytes(): a download;
+    .kernel_ms(): the copy and the mask pass (the context had set_profiling on).  The job's own bytes are untouched."""
+    _free, _kernel_ms = "pp_masked_free", "pp_masked_kernel_ms"
+
+    def __init__(self, ctx, mask=BED_UNDECIDED):
+        L = lib()
+        super().__init__(ctx)
+        ctx._chk(L.pp_polish_masked(ctx._h, int(mask), C.byref(self._p)))
+        dev, nb = C.c_void_p(), C.c_uint64(0)
+        L.pp_masked_bytes(self._p, C.byref(dev), C.byref(nb))
+        self.bytes_ptr, self.n_bytes = dev.value or 0, int(nb.value)
+
+    def dev(self):
+        return self.bytes_ptr, self.n_bytes
+
+    def bytes(self):
+        return self._ctx.download(self.bytes_ptr, self.n_bytes, np.uint8).tobytes() if self.n_bytes else b""
+
+
+def bed_geometry():
+    """(positions per thread P, positions per workgroup T, text bytes per store, text bytes per workgroup) of pp_status_bed: the position
+    passes cut the status array, the text pass cuts the text -- the seams its tests aim at."""
+    v = [C.c_uint32() for _ in range(4)]
+    lib().pp_bed_geometry_(*[C.byref(x) for x in v])
+    return tuple(int(x.value) for x in v)
+
+
 def fasta_out_geometry():
     """(bytes per store S, bytes per workgroup G) of pp_fasta_text: a lane writes S bytes of TEXT with one aligned store, a workgroup
     owns the text offsets [k * G, (k + 1) * G): the seams its tests aim at."""
@@ -2007,6 +2114,54 @@ class Context:
         finally:
             self.set_vcf(False)
 
+    def set_bed(self, on=True, mask=BED_UNDECIDED, bgzf=False):
+        """pp_ctx_set_bed: polish_files and filter_polish_files keep the per-position status and run pp_polish_bed behind their polish
+        (bgzf: pp_bgzf_deflate behind it); bed() fetches the file"""
+        self._chk(lib().pp_ctx_set_bed(self._h, int(bool(on)), int(mask) if on else 0, int(bool(bgzf))))
+
+    def bed(self):
+        """pp_ctx_bed: the BED file (bytes) of the last command that made one on this context"""
+        b = Bytes()
+        self._chk(lib().pp_ctx_bed(self._h, C.byref(b)))
+        return _take_bytes(b)
+
+    def set_soft_mask(self, mask=BED_UNDECIDED):
+        """pp_ctx_set_soft_mask: the FASTA of polish_files and filter_polish_files has the bytes of positions with a selected status in
+        lower case (pp_polish_masked); 0 / None / False: off"""
+        self._chk(lib().pp_ctx_set_soft_mask(self._h, int(mask or 0)))
+
+    @contextlib.contextmanager
+    def _making_bed(self, bed, bed_bgzf, bed_status, soft_mask):
+        """bed= (a path), bed_bgzf=, bed_status= and soft_mask= of one command: pp_ctx_set_bed / pp_ctx_set_soft_mask for its duration;
+        the function this yields writes the BED once the command has succeeded"""
+        if bed_bgzf and bed is None:
+            raise PolypolishError(ERR_QUIT, "bed_bgzf=True needs bed=<path>: it compresses the BED file")
+        if bed_status is not None and bed is None and not soft_mask:
+            raise PolypolishError(ERR_QUIT, "bed_status= needs bed=<path> or soft_mask=True: it chooses what they select")
+        if bed is None and not soft_mask:
+            yield lambda: None
+            return
+        mask = bed_status_mask(bed_status)
+        if bed is not None:
+            self.set_bed(True, mask, bed_bgzf)
+        if soft_mask:
+            self.set_soft_mask(mask)
+
+        def deliver():
+            if bed is None:
+                return
+            data = self.bed()
+            try:
+                with open(bed, "wb") as f:
+                    f.write(data)
+            except OSError:
+                raise PolypolishError(ERR_QUIT, f'unable to write the BED to "{os.fspath(bed)}"') from None
+        try:
+            yield deliver
+        finally:
+            self.set_bed(False)
+            self.set_soft_mask(0)
+
     @contextlib.contextmanager
     def _writing_bam(self, out_bam):
         """out_bam=True switches pp_ctx_set_out_bam on for one command and off again behind it"""
@@ -2049,48 +2204,54 @@ class Context:
 
     def polish_files(self, assembly, sams, fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5,
                      careful=False, debug=None, quiet=True, regroup=False, text_chain=False, wrap=None, bgzf=False, out=None,
-                     index=False, vcf=None, vcf_bgzf=False):
+                     index=False, vcf=None, vcf_bgzf=False, bed=None, bed_bgzf=False, bed_status=None, soft_mask=False):
         """polish::polish (pp_polish_files): the FASTA bytes.  wrap / bgzf / out / index (not in the reference): the FASTA at a line
         width (0: one line per contig) and bgzipped, made on the device (pp_fasta_text, pp_bgzf_deflate); also written to `out`,
         with out.fai (and out.gzi) for index.  `sams` are SAM text files, or all of them BAM files (BGZF or
         uncompressed; told by content, aln_file_kind): those go through the record chain on the device, inside the driver.
         regroup: for this call, as set_regroup (coordinate-sorted BAM).  text_chain: for this call, as set_text_chain (SAM text,
         plain or bgzipped, through the record chain as well).  vcf / vcf_bgzf (not in the reference): the polish's edits written to
-        the path `vcf` as VCF 4.2 made on the device (pp_polish_vcf), bgzipped with vcf_bgzf."""
+        the path `vcf` as VCF 4.2 made on the device (pp_polish_vcf), bgzipped with vcf_bgzf.  bed / bed_bgzf / bed_status / soft_mask
+        (not in the reference): the runs of undecided positions written to the path `bed` as BED made on the device (pp_polish_bed),
+        bgzipped with bed_bgzf; soft_mask: their bases in lower case in the FASTA (pp_polish_masked); bed_status: the statuses both
+        select (bed_status_mask; default the four undecided ones)."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         arr = (C.c_char_p * max(len(sams), 1))(*[str(s).encode() for s in sams])
         res = Bytes()
         with self._regrouping(regroup), self._chaining_text(text_chain), self._making_vcf(vcf, vcf_bgzf) as deliver_vcf, \
-                self._fasta_form(wrap, bgzf, out, index) as deliver:
+                self._making_bed(bed, bed_bgzf, bed_status, soft_mask) as deliver_bed, self._fasta_form(wrap, bgzf, out, index) as deliver:
             self._chk(lib().pp_polish_files(self._h, str(assembly).encode(), arr, len(sams), C.byref(opt), C.byref(res)))
             data = _take_bytes(res)
             deliver_vcf()
+            deliver_bed()
             deliver(data)
         return data
 
     def filter_polish_files(self, assembly, in1, in2, out1=None, out2=None, orientation="auto", low=0.1, high=99.9,
                             fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5, careful=False,
                             debug=None, quiet=True, regroup=False, out_bam=False, out_sam=False, text_chain=False, wrap=None,
-                            bgzf=False, out=None, index=False, sort_out=False, out_bai=False, vcf=None, vcf_bgzf=False):
+                            bgzf=False, out=None, index=False, sort_out=False, out_bai=False, vcf=None, vcf_bgzf=False, bed=None,
+                            bed_bgzf=False, bed_status=None, soft_mask=False):
         """filter + polish in one process (pp_filter_polish_files): returns (FASTA bytes, filter report).  wrap / bgzf / out / index:
         as polish_files.  Two BAM inputs are decoded
         once for both halves; out1 / out2 are then BAM files as well.  regroup: for this call, as set_regroup (the polish half).
         out_bam: for this call, as set_out_bam (SAM text inputs, out1 / out2 as compressed BAM).  out_sam: for this call, as
         set_out_sam (BAM inputs, out1 / out2 as SAM text).  text_chain: for this call, as set_text_chain.  sort_out / out_bai: for
-        this call, as set_sort_out (BAM outputs in coordinate order, out1.bai / out2.bai next to them).  vcf / vcf_bgzf: as
-        polish_files."""
+        this call, as set_sort_out (BAM outputs in coordinate order, out1.bai / out2.bai next to them).  vcf / vcf_bgzf, bed /
+        bed_bgzf / bed_status / soft_mask: as polish_files."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         rep, res = FilterReport(), Bytes()
         enc = lambda x: str(x).encode() if x is not None else None
         with self._regrouping(regroup), self._writing_bam(out_bam), self._writing_sam(out_sam), self._chaining_text(text_chain), \
                 self._sorting_out(sort_out, out_bai), self._making_vcf(vcf, vcf_bgzf) as deliver_vcf, \
-                self._fasta_form(wrap, bgzf, out, index) as deliver:
+                self._making_bed(bed, bed_bgzf, bed_status, soft_mask) as deliver_bed, self._fasta_form(wrap, bgzf, out, index) as deliver:
             self._chk(lib().pp_filter_polish_files(self._h, enc(assembly), enc(in1), enc(in2), enc(out1), enc(out2),
                                                    orientation.encode(), low, high, C.byref(opt), C.byref(rep), C.byref(res)))
             data = _take_bytes(res)
             deliver_vcf()
+            deliver_bed()
             deliver(data)
         return data, _report_dict(rep)
 
@@ -2121,13 +2282,16 @@ def _ctx():
 
 
 def polish(assembly, sam, debug=None, fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5,
-           careful=False, regroup=False, text_chain=False, wrap=None, bgzf=False, out=None, index=False) -> bytes:
+           careful=False, regroup=False, text_chain=False, wrap=None, bgzf=False, out=None, index=False, bed=None, bed_bgzf=False,
+           bed_status=None, soft_mask=False) -> bytes:
     """polish::polish (src/polish.rs:26-38): returns the FASTA bytes the reference prints to stdout.  regroup: coordinate-sorted
     BAM files (every read's records are brought together in front of the gate: the command's --regroup).  text_chain: SAM text,
     plain or bgzipped, through the record chain as well (the command's --text_chain; regroup then takes text too).  wrap / bgzf / out /
-    index: the commands' --wrap, --out_bgzf, --out and --index (Context.polish_files)."""
+    index: the commands' --wrap, --out_bgzf, --out and --index; bed / bed_bgzf / bed_status / soft_mask: --bed, --bed_bgzf, --bed_status
+    and --soft_mask (Context.polish_files)."""
     return _ctx().polish_files(assembly, list(sam), fraction_invalid, fraction_valid, max_errors, min_depth, careful,
-                               debug, regroup=regroup, text_chain=text_chain, wrap=wrap, bgzf=bgzf, out=out, index=index)
+                               debug, regroup=regroup, text_chain=text_chain, wrap=wrap, bgzf=bgzf, out=out, index=index, bed=bed,
+                               bed_bgzf=bed_bgzf, bed_status=bed_status, soft_mask=soft_mask)
 
 
 def filter(in1, in2, out1, out2, orientation="auto", low=0.1, high=99.9):  # noqa: A001 (reference name)

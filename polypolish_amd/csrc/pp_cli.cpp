@@ -13,6 +13,7 @@
 
 #include "polypolish_hip.h"
 #include "pp_host.h"
+#include "pp_bed_host.h"
 
 static const char *HELP =
     "Polypolish (MI355X/gfx950 implementation, parity target v0.6.1)\n"
@@ -63,6 +64,11 @@ static const char *HELP_POLISH =
     "      --index                                With --out: write PATH.fai, and PATH.gzi with --out_bgzf (not in the reference)\n"
     "      --vcf <PATH>                           Write the polish's edits to PATH as VCF 4.2, made on the device (one GPU; not in the reference)\n"
     "      --vcf_bgzf                             With --vcf: compress the VCF into BGZF blocks on the device (not in the reference)\n"
+    "      --bed <PATH>                           Write the runs of undecided positions to PATH as BED, made on the device (one GPU; not in the reference)\n"
+    "      --bed_bgzf                             With --bed: compress the BED into BGZF blocks on the device (not in the reference)\n"
+    "      --soft_mask                            Write the bases of undecided positions in lower case (one GPU; not in the reference)\n"
+    "      --bed_status <LIST>                    The statuses --bed and --soft_mask select: a comma-separated list of kept, changed,\n"
+    "                                             low_depth, none, multiple, too_close [default: low_depth,none,multiple,too_close]\n"
     "  -h, --help                                 Print help\n  -V, --version                              Print version\n";
 
 static const char *HELP_FUSED =
@@ -81,7 +87,12 @@ static const char *HELP_FUSED =
     "--out_bgzf: compress the polished FASTA into BGZF blocks on the device (not in the reference).\n"
     "--index: with --out, write PATH.fai, and PATH.gzi with --out_bgzf (not in the reference).\n"
     "--vcf <PATH>: write the polish's edits to PATH as VCF 4.2, made on the device (not in the reference).\n"
-    "--vcf_bgzf: with --vcf, compress the VCF into BGZF blocks on the device (not in the reference).\n";
+    "--vcf_bgzf: with --vcf, compress the VCF into BGZF blocks on the device (not in the reference).\n"
+    "--bed <PATH>: write the runs of undecided positions to PATH as BED, made on the device (not in the reference).\n"
+    "--bed_bgzf: with --bed, compress the BED into BGZF blocks on the device (not in the reference).\n"
+    "--soft_mask: write the bases of undecided positions in lower case (not in the reference).\n"
+    "--bed_status <LIST>: the statuses --bed and --soft_mask select, a comma-separated list of kept, changed, low_depth, none,\n"
+    "multiple, too_close; default low_depth,none,multiple,too_close (not in the reference).\n";
 
 static int usage_error(const char *msg) {
     fprintf(stderr, "error: %s\n\nFor more information, try '--help'.\n", msg);
@@ -220,6 +231,33 @@ static int refuse_index_without_out() {
     return 1;
 }
 static int refuse_vcf_bgzf_without_vcf() { return usage_error("--vcf_bgzf needs --vcf <PATH>: it compresses the VCF file"); }
+// --bed, --bed_bgzf, --soft_mask, --bed_status: four options from k0 on.  false with the usage error in err
+struct BedForm {
+    const char *path = nullptr;
+    bool bgzf = false, soft_mask = false;
+    uint32_t mask = PP_BED_UNDECIDED;
+    bool any() const { return path || soft_mask; }
+};
+static bool take_bed_form(const Parsed &P, size_t k0, BedForm &B, std::string &err) {
+    B.path = P.value[k0];
+    B.bgzf = P.value[k0 + 1] != nullptr;
+    B.soft_mask = P.value[k0 + 2] != nullptr;
+    const char *list = P.value[k0 + 3];
+    if (B.bgzf && !B.path) { err = "--bed_bgzf needs --bed <PATH>: it compresses the BED file"; return false; }
+    if (list && !B.any()) { err = "--bed_status needs --bed <PATH> or --soft_mask: it chooses what they select"; return false; }
+    if (list) {
+        char msg[192] = "";
+        if (pp_bed_host::parse_status_list(list, strlen(list), &B.mask, msg, sizeof msg)) {
+            err = std::string("invalid value '") + list + "' for '--bed_status <LIST>': " + msg;
+            return false;
+        }
+    }
+    return true;
+}
+static void set_bed_form(pp_ctx *ctx, const BedForm &B) {
+    pp_ctx_set_bed(ctx, B.path != nullptr, B.mask, B.bgzf);
+    pp_ctx_set_soft_mask(ctx, B.soft_mask ? B.mask : 0u);
+}
 static bool write_file(const std::string &path, const uint8_t *data, uint64_t len) {
     FILE *f = fopen(path.c_str(), "wb");
     if (!f) return false;
@@ -257,6 +295,17 @@ static int deliver_vcf(pp_ctx *ctx, const char *path) {
     if (ok) return 0;
     remove(path);
     fprintf(stderr, "\nError: unable to write the VCF to \"%s\"\n", path);
+    return 1;
+}
+// ... and the BED (--bed; pp_ctx_bed), behind the VCF
+static int deliver_bed(pp_ctx *ctx, const char *path) {
+    if (!path) return 0;
+    pp_bytes bed{nullptr, 0};
+    const bool ok = pp_ctx_bed(ctx, &bed) == PP_OK && write_file(path, bed.data, bed.len);
+    pp_bytes_free(&bed);
+    if (ok) return 0;
+    remove(path);
+    fprintf(stderr, "\nError: unable to write the BED to \"%s\"\n", path);
     return 1;
 }
 // the form on a context: --index alone still needs the text's table, so it takes the device link at width 0
@@ -346,7 +395,11 @@ int main(int argc, char **argv) {
                                             {"--out_bgzf", 0, false, ""},
                                             {"--index", 0, false, ""},
                                             {"--vcf", 0, true, "<PATH>"},
-                                            {"--vcf_bgzf", 0, false, ""}};
+                                            {"--vcf_bgzf", 0, false, ""},
+                                            {"--bed", 0, true, "<PATH>"},
+                                            {"--bed_bgzf", 0, false, ""},
+                                            {"--soft_mask", 0, false, ""},
+                                            {"--bed_status", 0, true, "<LIST>"}};
         FastaForm form;
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help) { fputs(HELP_POLISH, stdout); return 0; }
@@ -365,6 +418,8 @@ int main(int argc, char **argv) {
         const char *vcf = P.value[12];
         const bool vcf_bgzf = P.value[13] != nullptr;
         if (vcf_bgzf && !vcf) return refuse_vcf_bgzf_without_vcf();
+        BedForm bed;
+        if (!take_bed_form(P, 14, bed, perr)) return usage_error(perr.c_str());
         if (form.index && !form.out) return refuse_index_without_out();
         const char *assembly = P.positional.empty() ? nullptr : P.positional[0];
         std::vector<const char *> sams(P.positional.begin() + (P.positional.empty() ? 0 : 1), P.positional.end());
@@ -379,6 +434,10 @@ int main(int argc, char **argv) {
         const bool several = (getenv("PP_GPUS") && atoi(getenv("PP_GPUS")) > 1) || (getenv("PP_SHARE_GPU") && atoi(getenv("PP_SHARE_GPU")) > 1);
         if (several && vcf) {  // (refused before any file is opened, as BAM input below)
             fprintf(stderr, "\nError: --vcf runs on one GPU: polish without PP_GPUS / PP_SHARE_GPU, or without --vcf\n");
+            return 1;
+        }
+        if (several && bed.any()) {
+            fprintf(stderr, "\nError: %s runs on one GPU: polish without PP_GPUS / PP_SHARE_GPU, or without %s\n", bed.path ? "--bed" : "--soft_mask", bed.path ? "--bed" : "--soft_mask");
             return 1;
         }
         for (size_t i = 0; several && i < sams.size(); i++) {
@@ -400,6 +459,7 @@ int main(int argc, char **argv) {
                 if (pp_ctx_create_async(devs[d], &cs[d]) || pp_ctx_set_regroup(cs[d], regroup) || pp_ctx_set_text_chain(cs[d], text_chain)) return no_device(devs[d]);
             set_fasta_form(cs[0], form);
             pp_ctx_set_vcf(cs[0], vcf != nullptr, vcf_bgzf);  // (several contexts: the driver refuses it by name)
+            set_bed_form(cs[0], bed);
             pp_bytes fasta{nullptr, 0};
             int rc = pp_polish_files_multi(cs.data(), (int)cs.size(), assembly, sams.data(), (int)sams.size(), &opt, &fasta);
             for (size_t d = 0; d < devs.size(); d++)
@@ -409,7 +469,7 @@ int main(int argc, char **argv) {
                 for (pp_ctx *c : cs) pp_ctx_destroy(c);
                 return rc == PP_ERR_PANIC ? 101 : 1;
             }
-            if (deliver_vcf(cs[0], vcf) || deliver_fasta(cs[0], form, fasta)) return 1;
+            if (deliver_vcf(cs[0], vcf) || deliver_bed(cs[0], bed.path) || deliver_fasta(cs[0], form, fasta)) return 1;
             return finish(0);
         }
         // the device initialises on a helper thread while the host loads and parses the inputs
@@ -420,6 +480,7 @@ int main(int argc, char **argv) {
         pp_ctx_set_text_chain(ctx, text_chain);
         set_fasta_form(ctx, form);
         pp_ctx_set_vcf(ctx, vcf != nullptr, vcf_bgzf);
+        set_bed_form(ctx, bed);
         pp_bytes fasta{nullptr, 0};
         rc = pp_polish_files(ctx, assembly, sams.data(), (int)sams.size(), &opt, &fasta);
         if (pp_ctx_wait(ctx) != PP_OK) return no_device(device);
@@ -428,7 +489,7 @@ int main(int argc, char **argv) {
             pp_ctx_destroy(ctx);
             return rc == PP_ERR_PANIC ? 101 : 1;
         }
-        if (deliver_vcf(ctx, vcf) || deliver_fasta(ctx, form, fasta)) return 1;
+        if (deliver_vcf(ctx, vcf) || deliver_bed(ctx, bed.path) || deliver_fasta(ctx, form, fasta)) return 1;
         return finish(0);
     }
 
@@ -457,7 +518,11 @@ int main(int argc, char **argv) {
                                             {"--sort_out", 0, false, ""},
                                             {"--out_bai", 0, false, ""},
                                             {"--vcf", 0, true, "<PATH>"},
-                                            {"--vcf_bgzf", 0, false, ""}};
+                                            {"--vcf_bgzf", 0, false, ""},
+                                            {"--bed", 0, true, "<PATH>"},
+                                            {"--bed_bgzf", 0, false, ""},
+                                            {"--soft_mask", 0, false, ""},
+                                            {"--bed_status", 0, true, "<LIST>"}};
         FastaForm form;
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help || P.version) { fputs(HELP_FUSED, stdout); return 0; }
@@ -483,6 +548,11 @@ int main(int argc, char **argv) {
         const char *vcf = P.value[23];
         const bool vcf_bgzf = P.value[24] != nullptr;
         if (vcf_bgzf && !vcf) return refuse_vcf_bgzf_without_vcf();
+        BedForm bed;
+        {
+            std::string berr;
+            if (!take_bed_form(P, 25, bed, berr)) return usage_error(berr.c_str());
+        }
         pp_ctx *ctx = nullptr;
         int rc = pp_ctx_create_async(device, &ctx);
         if (rc) return no_device(device);
@@ -493,6 +563,7 @@ int main(int argc, char **argv) {
         pp_ctx_set_text_chain(ctx, P.value[16] != nullptr);
         set_fasta_form(ctx, form);
         pp_ctx_set_vcf(ctx, vcf != nullptr, vcf_bgzf);
+        set_bed_form(ctx, bed);
         pp_bytes fasta{nullptr, 0};
         rc = pp_filter_polish_files(ctx, assembly, in1, in2, out1, out2, orientation, low, high, &opt, nullptr, &fasta);
         if (pp_ctx_wait(ctx) != PP_OK) return no_device(device);
@@ -501,7 +572,7 @@ int main(int argc, char **argv) {
             pp_ctx_destroy(ctx);
             return rc == PP_ERR_PANIC ? 101 : 1;
         }
-        if (deliver_vcf(ctx, vcf) || deliver_fasta(ctx, form, fasta)) return 1;
+        if (deliver_vcf(ctx, vcf) || deliver_bed(ctx, bed.path) || deliver_fasta(ctx, form, fasta)) return 1;
         return finish(0);
     }
 

@@ -285,7 +285,7 @@ static int create_debug_file(PolishJob &J) {
         fputs("name\tpos\tbase\tdepth\tinvalid\tvalid\tpileup\tstatus\tnew_base\n", J.dbg);
     }
     J.debug_set = true;
-    for (int d = 0; d < J.n_ctx; d++) pp_polish_set_debug(J.ctxs[d], J.dbg ? 1 : 0);
+    for (int d = 0; d < J.n_ctx; d++) pp_polish_set_debug(J.ctxs[d], J.dbg || J.wants_status() ? 1 : 0);  // (--bed, --soft_mask: the records without a file)
     return PP_OK;
 }
 // ... and closed once the contexts have written their lines; they keep no per-position records from here on
@@ -299,6 +299,38 @@ int close_debug_file(PolishJob &J, int rc, bool say) {
     return rc;
 }
 
+// the polished bytes in the context's device memory: the job's own, or their soft-masked copy (pp_ctx_set_soft_mask)
+static const uint8_t *polished_on_device(PolishJob &J) {
+    if (!J.masked) return pp_polish_result_device(J.ctx);
+    const uint8_t *dev = nullptr;
+    pp_masked_bytes(J.masked, &dev, nullptr);
+    return dev;
+}
+
+// The BED of pp_ctx_set_bed: pp_polish_bed on the finished job, pp_bgzf_deflate on the device text with bgzf, one copy off the
+// device into the job (J.bed_file).  Nothing is logged.
+static int make_bed(PolishJob &J) {
+    pp_ctx *const ctx = J.ctx;
+    pp_bed_out *text = nullptr;
+    pp_bgzf_out *z = nullptr;
+    const uint8_t *dev = nullptr;
+    uint64_t n = 0;
+    int rc = pp_polish_bed(ctx, J.names.data(), J.bed_mask, &text);
+    if (rc == PP_OK) pp_bed_out_bytes(text, &dev, &n, nullptr);
+    if (rc == PP_OK && J.bed_bgzf) {
+        rc = pp_bgzf_deflate(ctx, dev, n, PP_MEM_DEVICE, &z);
+        if (rc == PP_OK) pp_bgzf_out_bytes(z, &dev, &n);
+    }
+    if (rc == PP_OK) {  // (handed to the context once the whole run has succeeded: polish_once)
+        J.bed_file.resize((size_t)n);
+        if (n) rc = pp_ctx_download(ctx, J.bed_file.data(), dev, n);
+    }
+    pp_bgzf_out_free(z);
+    pp_bed_out_free(text);
+    J.lap(J.bed_bgzf ? "BED made and compressed on the device" : "BED made on the device");
+    return rc;
+}
+
 static int polish_on_one_context(PolishJob &J) {
     pp_ctx *const ctx = J.ctx;
     int rc = hand_over_batches(J);
@@ -309,6 +341,12 @@ static int polish_on_one_context(PolishJob &J) {
         rc = write_debug_tsv(ctx, J.dbg, J.names, 0, J.off[J.nc]);
         J.lap("--debug file written");
     }
+    // (the BED and the masked bytes read the job's status: made before the records are closed)
+    if (rc == PP_OK && J.bed_on) rc = make_bed(J);
+    if (rc == PP_OK && J.soft_mask) {
+        rc = pp_polish_masked(ctx, J.soft_mask, &J.masked);
+        J.lap("polished bytes soft-masked on the device");
+    }
     rc = close_debug_file(J, rc, false);
     if (rc == PP_OK) rc = pp_polish_result_size(ctx, &J.total);
     // offsets and statistics now; the bytes go straight into the FASTA buffer below (contig by contig) when that is a
@@ -316,7 +354,8 @@ static int polish_on_one_context(PolishJob &J) {
     // (with pp_ctx_set_fasta_form the bytes stay on the device for pp_fasta_text)
     J.direct_fetch = rc == PP_OK && (J.form_on || (J.fasta.buf && J.nc <= 256 && J.fasta.header_bytes + J.total + J.nc <= J.fasta.cap));
     if (!J.direct_fetch) J.polished.resize(J.total ? J.total : 1);
-    if (rc == PP_OK) rc = pp_polish_result(ctx, J.direct_fetch ? nullptr : J.polished.data(), PP_MEM_HOST, J.out_off.data(), J.stats.data());
+    if (rc == PP_OK) rc = pp_polish_result(ctx, J.direct_fetch || J.masked ? nullptr : J.polished.data(), PP_MEM_HOST, J.out_off.data(), J.stats.data());
+    if (rc == PP_OK && J.masked && !J.direct_fetch && J.total) rc = pp_ctx_download(ctx, J.polished.data(), polished_on_device(J), J.total);
     return rc;
 }
 
@@ -346,7 +385,7 @@ static int write_fasta_and_log(PolishJob &J, pp_bytes *fasta) {
         if (!J.fasta.buf) return set_err(J.ctx, PP_ERR_HIP, "out of host memory for the FASTA");
     }
     uint8_t *out = J.fasta.buf;
-    const uint8_t *d_polished = J.direct_fetch ? pp_polish_result_device(J.ctx) : nullptr;
+    const uint8_t *d_polished = J.direct_fetch ? polished_on_device(J) : nullptr;
     size_t w = 0;
     for (uint32_t c = 0; c < nc; c++) {
         const char *name = J.names[c], *desc = pp_assembly_description(J.a, c);
@@ -388,7 +427,7 @@ static int write_fasta_form_and_log(PolishJob &J, pp_bytes *fasta) {
         header_off[c + 1] = headers.size();
     }
     const bool on_device = J.direct_fetch;
-    const uint8_t *src = on_device ? pp_polish_result_device(ctx) : J.polished.data();
+    const uint8_t *src = on_device ? polished_on_device(J) : J.polished.data();
     pp_fasta_out *text = nullptr;
     pp_bgzf_out *z = nullptr;
     pp_bytes fai{nullptr, 0}, gzi{nullptr, 0};
@@ -465,6 +504,13 @@ static int polish_once(PolishJob &J, pp_bytes *fasta) {
     pp_ctx_keep_vcf_(J.ctx, nullptr, 0);  // (the file of the run before)
     if (vcf_on && J.n_ctx > 1)  // (a rank's share has no defined runs at its edges: pp_polish_vcf)
         return set_err(J.ctx, PP_ERR_QUIT, "--vcf runs on one GPU: polish without PP_GPUS / several contexts, or without --vcf");
+    J.bed_on = pp_ctx_bed_form_(J.ctx, &J.bed_mask, &J.bed_bgzf) != 0;
+    J.soft_mask = pp_ctx_soft_mask_(J.ctx);
+    pp_ctx_keep_bed_(J.ctx, nullptr, 0);  // (the file of the run before)
+    if (J.bed_on && J.n_ctx > 1)  // (the status plane of a rank is its share's: pp_polish_bed)
+        return set_err(J.ctx, PP_ERR_QUIT, "--bed runs on one GPU: polish without PP_GPUS / several contexts, or without --bed");
+    if (J.soft_mask && J.n_ctx > 1)
+        return set_err(J.ctx, PP_ERR_QUIT, "--soft_mask runs on one GPU: polish without PP_GPUS / several contexts, or without --soft_mask");
     if (int rc = check_options_and_inputs(J)) return rc;
     log_banner(J);
     J.lap("driver entered");
@@ -481,6 +527,10 @@ static int polish_once(PolishJob &J, pp_bytes *fasta) {
     if (vcf_on)
         if (int rc = make_vcf(J, vcf_bgzf)) return rc;
     if (int rc = J.form_on ? write_fasta_form_and_log(J, fasta) : write_fasta_and_log(J, fasta)) return rc;
+    if (J.bed_on) {  // (a run that fails leaves no file: pp_ctx_bed)
+        J.bed_file.push_back(0);
+        pp_ctx_keep_bed_(J.ctx, J.bed_file.data(), J.bed_file.size() - 1);
+    }
     log_finished(J);
     J.release();
     J.lap("device and host buffers released");

@@ -153,6 +153,14 @@ struct PolishJob {
     bool form_on = false;  // pp_ctx_set_fasta_form: the FASTA is made by pp_fasta_text (write_fasta_form_and_log), at this width ...
     int64_t form_width = -1;
     int form_bgzf = 0;     // ... and compressed by pp_bgzf_deflate
+    // pp_ctx_set_bed / pp_ctx_set_soft_mask (one context): the job keeps its per-position status; the BED is made and the masked bytes
+    // are taken before the records are closed (polish_on_one_context), the FASTA's sequence bytes then come from `masked`
+    bool bed_on = false;
+    uint32_t bed_mask = 0, soft_mask = 0;
+    int bed_bgzf = 0;
+    pp_masked *masked = nullptr;
+    std::vector<uint8_t> bed_file;  // the BED of this run (make_bed), the context's once the run has succeeded
+    bool wants_status() const { return bed_on || soft_mask != 0; }
     std::vector<uint8_t> polished = std::vector<uint8_t>(1);
     std::vector<uint64_t> out_off;
     std::vector<pp_contig_stats> stats;
@@ -177,6 +185,8 @@ struct PolishJob {
         (void)text.wait_pending();
         if (dbg) fclose(dbg);
         dbg = nullptr;
+        pp_masked_free(masked);
+        masked = nullptr;
         for (int d = 0; debug_set && d < n_ctx; d++) pp_polish_set_debug(ctxs[d], 0);
         debug_set = false;
         multi.reset();

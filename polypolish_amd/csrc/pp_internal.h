@@ -282,6 +282,11 @@ struct pp_ctx {
     // of the last such run that succeeded (pp_ctx_vcf), dropped when the next run begins
     bool vcf_on = false, vcf_bgzf = false, vcf_made = false;
     std::string vcf_bytes;
+    // pp_ctx_set_bed / pp_ctx_set_soft_mask: the file drivers keep the job's per-position status, run pp_polish_bed behind their polish
+    // (bed_bytes: the file of the last such run that succeeded, pp_ctx_bed) and take the FASTA's bytes from pp_polish_masked
+    bool bed_on = false, bed_bgzf = false, bed_made = false;
+    uint32_t bed_mask = 0, soft_mask = 0;  // soft_mask 0: off
+    std::string bed_bytes;
     std::string fasta_out_name;         // pp_ctx_set_fasta_out_name_: where the caller will write the FASTA (the log's last section names it)
     pp::DevBuf f_thr;  // pp_filter_thresholds: orientation counts | the selection's state | its two histograms (THR_WORDS u32)
     pp_filter_input fdev{};

@@ -49,6 +49,8 @@
 #include "pp_k_debug.h"
 #include "pp_k_vcf.h"
 #include "pp_vcf_host.h"
+#include "pp_bed_host.h"
+#include "pp_k_bed.h"
 #include <hip/hip_ext.h>
 
 // =============================================================================================
@@ -1680,6 +1682,31 @@ struct VcfScratch {  // the call's device memory and timing events, released whe
         return PP_OK;
     }
 };
+
+// The finished job as the post-passes read it (pp_polish_vcf, pp_polish_masked), and where each workgroup's emitted bytes begin: the
+// multi-byte winners' lengths as a table (J.mlen, when the job has any), the emitted bytes per workgroup of VCF_TILE positions
+// (d_bsum: nb words, free for the caller afterwards) and their scan (d_boff: nb + 1).  G > 0.
+VcfJob vcf_job_of(const pp_ctx *ctx) {
+    VcfJob J;
+    J.bases = ctx->d_bases; J.code = (const u8 *)ctx->b_code.p; J.out = (const u8 *)ctx->b_out.p; J.mlen = nullptr;
+    J.contig_off = (const u64 *)ctx->b_contig_off.p; J.nc = ctx->n_contigs; J.G = ctx->G; J.total_out = ctx->total_out;
+    return J;
+}
+int vcf_emit_offsets(pp_ctx *ctx, VcfScratch &T, VcfJob &J, uint64_t nb, u64 *&d_bsum, u64 *&d_boff) {
+    hipStream_t st = ctx->stream;
+    const uint64_t nm = ctx->n_multi;
+    int rc;
+    if ((rc = T.get(ctx, d_bsum, nb)) || (rc = T.get(ctx, d_boff, nb + 1))) return rc;
+    if (nm) {
+        u32 *d_mlen = nullptr;
+        if ((rc = T.get(ctx, d_mlen, J.G))) return rc;
+        hipLaunchKernelGGL(k_vcf_multi, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, st, (const MultiEnt *)ctx->b_multi.p, (u32)nm, J.code, (u64)J.G, d_mlen);
+        J.mlen = d_mlen;
+    }
+    hipLaunchKernelGGL(k_vcf_sum, dim3((unsigned)nb), dim3(VCF_THREADS), 0, st, J, d_bsum);
+    hipLaunchKernelGGL(k_dfmt_scan1, dim3(1), dim3(1024), 0, st, (const u64 *)d_bsum, (u64)nb, d_boff);
+    return PP_OK;
+}
 }  // namespace
 
 extern "C" void pp_vcf_out_free(pp_vcf_out *o) {
@@ -1736,7 +1763,7 @@ extern "C" int pp_polish_vcf(pp_ctx *ctx, const char *const *contig_names, pp_vc
         return ctx->fail(code, "%s", msg);
     PP_HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const uint64_t G = ctx->G, H = plan.header.size(), nm = ctx->n_multi;
+    const uint64_t G = ctx->G, H = plan.header.size();
     const uint32_t nc = ctx->n_contigs;
     std::unique_ptr<pp_vcf_out, void (*)(pp_vcf_out *)> P(new pp_vcf_out(), pp_vcf_out_free);
     P->ctx = ctx;
@@ -1745,25 +1772,15 @@ extern "C" int pp_polish_vcf(pp_ctx *ctx, const char *const *contig_names, pp_vc
     uint64_t n_rec = 0, rec_bytes = 0;
     VcfRec *d_rec = nullptr;
     u64 *d_rec_at = nullptr, *d_noff = nullptr;
-    VcfJob J;
-    J.bases = ctx->d_bases; J.code = (const u8 *)ctx->b_code.p; J.out = (const u8 *)ctx->b_out.p; J.mlen = nullptr;
-    J.contig_off = (const u64 *)ctx->b_contig_off.p; J.nc = nc; J.G = G; J.total_out = ctx->total_out;
+    VcfJob J = vcf_job_of(ctx);
     if ((rc = T.mark(ctx))) return rc;
     if (G) {
         const uint64_t nb = (G + VCF_TILE - 1) / VCF_TILE;  // (below 2^21: G is below 2^32)
         u8 *d_flag = nullptr, *d_flag2 = nullptr;
         u64 *d_bsum = nullptr, *d_boff = nullptr, *d_roff = nullptr;
-        u32 *d_mlen = nullptr;
-        if ((rc = T.get(ctx, d_flag, nb * VCF_TILE)) || (rc = T.get(ctx, d_flag2, nb * VCF_TILE)) || (rc = T.get(ctx, d_bsum, nb)) ||
-            (rc = T.get(ctx, d_boff, nb + 1)) || (rc = T.get(ctx, d_roff, nb + 1)))
+        if ((rc = T.get(ctx, d_flag, nb * VCF_TILE)) || (rc = T.get(ctx, d_flag2, nb * VCF_TILE)) || (rc = T.get(ctx, d_roff, nb + 1)) ||
+            (rc = vcf_emit_offsets(ctx, T, J, nb, d_bsum, d_boff)))
             return rc;
-        if (nm) {
-            if ((rc = T.get(ctx, d_mlen, G))) return rc;
-            hipLaunchKernelGGL(k_vcf_multi, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, st, (const MultiEnt *)ctx->b_multi.p, (u32)nm, J.code, (u64)G, d_mlen);
-            J.mlen = d_mlen;
-        }
-        hipLaunchKernelGGL(k_vcf_sum, dim3((unsigned)nb), dim3(VCF_THREADS), 0, st, J, d_bsum);
-        hipLaunchKernelGGL(k_dfmt_scan1, dim3(1), dim3(1024), 0, st, (const u64 *)d_bsum, (u64)nb, d_boff);
         hipLaunchKernelGGL(k_vcf_mark, dim3((unsigned)nb), dim3(VCF_THREADS), 0, st, J, (const u64 *)d_boff, d_flag);
         if ((rc = T.mark(ctx))) return rc;
         hipLaunchKernelGGL(k_vcf_runs, dim3((unsigned)nb), dim3(VCF_THREADS), 0, st, J, (const u8 *)d_flag, d_flag2, d_bsum);
@@ -1854,6 +1871,288 @@ extern "C" void pp_ctx_keep_vcf_(pp_ctx *ctx, const uint8_t *data, uint64_t n) {
     ctx->vcf_made = data != nullptr;
     ctx->vcf_bytes.assign(data ? (const char *)data : "", data ? (size_t)n : 0);
     if (!data) ctx->vcf_bytes.shrink_to_fit();
+}
+
+// ---- undecided regions: the status runs as BED text, the soft-masked polished bytes (pp_k_bed.h, pp_bed_host.h) ---------------
+struct pp_bed_out {
+    pp_ctx *ctx = nullptr;
+    u8 *text = nullptr;  // DEVICE, n_text bytes (allocated up to a multiple of 16)
+    uint64_t n_text = 0, n_records = 0;
+    uint64_t positions[6] = {0, 0, 0, 0, 0, 0};
+    bool timed = false;
+    float ms[3] = {0.f, 0.f, 0.f};  // runs | records | text
+};
+struct pp_masked {
+    pp_ctx *ctx = nullptr;
+    u8 *bytes = nullptr;  // DEVICE, n bytes
+    uint64_t n = 0;
+    bool timed = false;
+    float ms = 0.f;
+};
+
+extern "C" void pp_bed_out_free(pp_bed_out *o) {
+    if (!o) return;
+    if (o->text) {
+        (void)hipSetDevice(o->ctx->device);
+        (void)hipFree(o->text);
+    }
+    delete o;
+}
+extern "C" void pp_bed_out_bytes(const pp_bed_out *o, const uint8_t **dev, uint64_t *n_bytes, uint64_t *n_records) {
+    if (dev) *dev = o ? o->text : nullptr;
+    if (n_bytes) *n_bytes = o ? o->n_text : 0;
+    if (n_records) *n_records = o ? o->n_records : 0;
+}
+extern "C" void pp_bed_out_counts(const pp_bed_out *o, uint64_t positions[6]) {
+    if (!positions) return;
+    for (int s = 0; s < 6; s++) positions[s] = o ? o->positions[s] : 0;
+}
+extern "C" int pp_bed_out_write(const pp_bed_out *o, const char *path) {
+    if (!o || !o->ctx) return PP_ERR_ARG;
+    if (!path) return o->ctx->fail(PP_ERR_ARG, "pp_bed_out_write: null argument");
+    return write_device_file(o->ctx, "pp_bed_out_write", o->text, o->n_text, path);
+}
+extern "C" int pp_bed_out_kernel_ms(const pp_bed_out *o, float *ms) {
+    if (!o || !ms) return PP_ERR_ARG;
+    if (!o->timed) return o->ctx->fail(PP_ERR_ARG, "pp_bed_out_kernel_ms: the context had no profiling on when the text was made (pp_ctx_set_profiling)");
+    *ms = o->ms[0] + o->ms[1] + o->ms[2];
+    return PP_OK;
+}
+// (internal hooks, not part of the header) the time by stage: runs | records | text (tools/bed_timing.py); the geometry: positions
+// per thread and per workgroup of the position passes, text bytes per store and per workgroup (the tests)
+extern "C" int pp_bed_out_stage_ms_(const pp_bed_out *o, float *ms3) {
+    if (!o || !ms3 || !o->timed) return PP_ERR_ARG;
+    std::copy(o->ms, o->ms + 3, ms3);
+    return PP_OK;
+}
+extern "C" void pp_bed_geometry_(uint32_t *pos_per_thread, uint32_t *pos_per_workgroup, uint32_t *bytes_per_store, uint32_t *bytes_per_workgroup) {
+    if (pos_per_thread) *pos_per_thread = BED_PPT;
+    if (pos_per_workgroup) *pos_per_workgroup = BED_TILE;
+    if (bytes_per_store) *bytes_per_store = BED_LANE;
+    if (bytes_per_workgroup) *bytes_per_workgroup = BED_TEXT_WG;
+}
+
+// the passes over d_status (DEVICE, plan.G bytes, any alignment); the arguments have been judged (pp_bed_host::plan)
+static int status_bed_on_device(pp_ctx *ctx, const char *who, const u8 *d_status, uint32_t nc, const uint64_t *contig_off, const pp_bed_host::Plan &plan,
+                                uint32_t mask, pp_bed_out **out, uint64_t *bad_pos) {
+    hipStream_t st = ctx->stream;
+    const uint64_t G = plan.G;
+    std::unique_ptr<pp_bed_out, void (*)(pp_bed_out *)> P(new pp_bed_out(), pp_bed_out_free);
+    P->ctx = ctx;
+    VcfScratch T;
+    int rc;
+    char msg[256] = "";
+    uint64_t n_rec = 0, n_text = 0;
+    if ((rc = T.mark(ctx))) return rc;
+    if (G) {
+        const uint64_t nb = (G + BED_TILE - 1) / BED_TILE;  // (below 2^21: G is below 2^32)
+        u64 *d_coff = nullptr, *d_bcnt = nullptr, *d_roff = nullptr, *d_word = nullptr;  // d_word: the first bad position | positions per status
+        if ((rc = T.get(ctx, d_coff, (size_t)nc + 1)) || (rc = T.get(ctx, d_bcnt, nb)) || (rc = T.get(ctx, d_roff, nb + 1)) || (rc = T.get(ctx, d_word, 7)))
+            return rc;
+        uint64_t word[7] = {~0ull, 0, 0, 0, 0, 0, 0};
+        PP_HIPCHK(ctx, hipMemcpyAsync(d_coff, contig_off, ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, st));
+        PP_HIPCHK(ctx, hipMemcpyAsync(d_word, word, sizeof word, hipMemcpyHostToDevice, st));
+        BedJob J;
+        J.status = d_status; J.contig_off = d_coff; J.nc = nc; J.mask = mask; J.G = G;
+        hipLaunchKernelGGL(k_bed_runs, dim3((unsigned)nb), dim3(BED_THREADS), 0, st, J, d_bcnt, d_word);
+        hipLaunchKernelGGL(k_dfmt_scan1, dim3(1), dim3(1024), 0, st, (const u64 *)d_bcnt, (u64)nb, d_roff);
+        PP_HIPCHK(ctx, hipGetLastError());
+        PP_HIPCHK(ctx, hipMemcpyAsync(&n_rec, d_roff + nb, 8, hipMemcpyDeviceToHost, st));
+        PP_HIPCHK(ctx, hipMemcpyAsync(word, d_word, 8, hipMemcpyDeviceToHost, st));
+        if ((rc = T.mark(ctx))) return rc;
+        PP_HIPCHK(ctx, hipStreamSynchronize(st));
+        if (word[0] != ~0ull) {
+            if (bad_pos) *bad_pos = word[0];
+            return ctx->fail(PP_ERR_ARG, "%s: a status byte above 5 (PP_ST_TOO_CLOSE) at position %llu", who, (unsigned long long)word[0]);
+        }
+        if (n_rec) {
+            const uint64_t nbr = (n_rec + BED_THREADS - 1) / BED_THREADS;
+            BedRec *d_rec = nullptr;
+            u64 *d_rec_at = nullptr, *d_rsum = nullptr, *d_rsoff = nullptr, *d_noff = nullptr;
+            u8 *d_names = nullptr;
+            if ((rc = T.get(ctx, d_rec, n_rec)) || (rc = T.get(ctx, d_rec_at, n_rec + 1)) || (rc = T.get(ctx, d_rsum, nbr)) ||
+                (rc = T.get(ctx, d_rsoff, nbr + 1)) || (rc = T.get(ctx, d_noff, (size_t)nc + 1)) || (rc = T.get(ctx, d_names, plan.names.size())))
+                return rc;
+            PP_HIPCHK(ctx, hipMemsetAsync(d_rec, 0, n_rec * sizeof(BedRec), st));
+            PP_HIPCHK(ctx, hipMemcpyAsync(d_noff, plan.name_off.data(), ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, st));
+            if (!plan.names.empty()) PP_HIPCHK(ctx, hipMemcpyAsync(d_names, plan.names.data(), plan.names.size(), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_bed_recs, dim3((unsigned)nb), dim3(BED_THREADS), 0, st, J, (const u64 *)d_roff, (u64)n_rec, d_rec);
+            hipLaunchKernelGGL(k_bed_reclen, dim3((unsigned)nbr), dim3(BED_THREADS), 0, st, (const BedRec *)d_rec, (u64)n_rec, (const u64 *)d_coff, nc,
+                               (const u64 *)d_noff, d_rec_at, d_rsum, d_word + 1);
+            hipLaunchKernelGGL(k_dfmt_scan1, dim3(1), dim3(1024), 0, st, (const u64 *)d_rsum, (u64)nbr, d_rsoff);
+            hipLaunchKernelGGL(k_vcf_recoff, dim3((unsigned)nbr), dim3(VCF_THREADS), 0, st, (u64)n_rec, (const u64 *)d_rsoff, (u64)0, d_rec_at);
+            PP_HIPCHK(ctx, hipGetLastError());
+            PP_HIPCHK(ctx, hipMemcpyAsync(&n_text, d_rsoff + nbr, 8, hipMemcpyDeviceToHost, st));
+            PP_HIPCHK(ctx, hipMemcpyAsync(P->positions, d_word + 1, 6 * 8, hipMemcpyDeviceToHost, st));
+            if ((rc = T.mark(ctx))) return rc;
+            PP_HIPCHK(ctx, hipStreamSynchronize(st));
+            if (int code = pp_bed_host::text_size(who, n_text, msg, sizeof msg)) return ctx->fail(code, "%s", msg);
+            void *q = nullptr;
+            const size_t room = (size_t)((n_text + 15u) & ~15ull);
+            PP_HIPCHK(ctx, hipMalloc(&q, room));
+            P->text = (u8 *)q;
+            P->n_text = n_text;
+            P->n_records = n_rec;
+            PP_HIPCHK(ctx, hipMemsetAsync(q, 0, room, st));
+            BedText X;
+            X.names = d_names; X.name_off = d_noff; X.contig_off = d_coff; X.rec_at = d_rec_at; X.rec = d_rec;
+            X.nc = nc; X.n_rec = n_rec; X.n_text = n_text;
+            const uint64_t nwg = (n_text + BED_TEXT_WG - 1) / BED_TEXT_WG;  // (below 2^26: the text is below 2^40)
+            hipLaunchKernelGGL(k_bed_text, dim3((unsigned)nwg), dim3(BED_THREADS), 0, st, X, P->text);
+            PP_HIPCHK(ctx, hipGetLastError());
+        } else if ((rc = T.mark(ctx))) return rc;
+    } else if ((rc = T.mark(ctx)) || (rc = T.mark(ctx))) return rc;
+    if ((rc = T.mark(ctx))) return rc;
+    PP_HIPCHK(ctx, hipStreamSynchronize(st));  // the scratch goes away
+    if (ctx->profiling && T.ev.size() == 4) {
+        for (int s = 0; s < 3; s++) PP_HIPCHK(ctx, hipEventElapsedTime(&P->ms[s], T.ev[s], T.ev[s + 1]));
+        P->timed = true;
+    }
+    *out = P.release();
+    return PP_OK;
+}
+
+extern "C" int pp_status_bed(pp_ctx *ctx, const uint8_t *status, int mem, uint32_t n_contigs, const uint64_t *contig_off, const char *const *contig_names,
+                             uint32_t status_mask, pp_bed_out **out, uint64_t *bad_pos) {
+    if (!ctx) return PP_ERR_ARG;
+    if (int rdy = pp_ctx_wait(ctx)) return rdy;
+    if (out) *out = nullptr;
+    if (bad_pos) *bad_pos = 0;
+    pp_bed_host::Plan plan;
+    char msg[256] = "";
+    if (int code = pp_bed_host::plan("pp_status_bed", out != nullptr, status != nullptr, mem == PP_MEM_HOST || mem == PP_MEM_DEVICE, n_contigs, contig_off,
+                                     contig_names, status_mask, plan, msg, sizeof msg))
+        return ctx->fail(code, "%s", msg);
+    PP_HIPCHK(ctx, hipSetDevice(ctx->device));
+    VcfScratch T;
+    const u8 *d_status = status;
+    if (mem == PP_MEM_HOST && plan.G) {
+        u8 *up = nullptr;
+        if (int rc = T.get(ctx, up, (size_t)plan.G)) return rc;
+        PP_HIPCHK(ctx, hipMemcpyAsync(up, status, plan.G, hipMemcpyHostToDevice, ctx->stream));
+        d_status = up;
+    }
+    return status_bed_on_device(ctx, "pp_status_bed", d_status, n_contigs, contig_off, plan, status_mask, out, bad_pos);
+}
+
+static pp_bed_host::JobState bed_job_state(const pp_ctx *ctx) {
+    return pp_bed_host::JobState{ctx->job_done, ctx->job_debug && ctx->b_dbg_status.p != nullptr, !ctx->emit.empty() || !ctx->run_full_of.empty()};
+}
+
+extern "C" int pp_polish_bed(pp_ctx *ctx, const char *const *contig_names, uint32_t status_mask, pp_bed_out **out) {
+    if (!ctx) return PP_ERR_ARG;
+    if (int rdy = pp_ctx_wait(ctx)) return rdy;
+    if (out) *out = nullptr;
+    char msg[256] = "";
+    if (!out || !contig_names) return ctx->fail(PP_ERR_ARG, "pp_polish_bed: null argument");
+    if (int code = pp_bed_host::check_job("pp_polish_bed", bed_job_state(ctx), msg, sizeof msg)) return ctx->fail(code, "%s", msg);
+    pp_bed_host::Plan plan;
+    if (int code = pp_bed_host::plan("pp_polish_bed", true, true, true, ctx->n_contigs, ctx->contig_off.data(), contig_names, status_mask, plan, msg, sizeof msg))
+        return ctx->fail(code, "%s", msg);
+    PP_HIPCHK(ctx, hipSetDevice(ctx->device));
+    uint64_t bad = 0;
+    return status_bed_on_device(ctx, "pp_polish_bed", (const u8 *)ctx->b_dbg_status.p, ctx->n_contigs, ctx->contig_off.data(), plan, status_mask, out, &bad);
+}
+
+extern "C" void pp_masked_free(pp_masked *o) {
+    if (!o) return;
+    if (o->bytes) {
+        (void)hipSetDevice(o->ctx->device);
+        (void)hipFree(o->bytes);
+    }
+    delete o;
+}
+extern "C" void pp_masked_bytes(const pp_masked *o, const uint8_t **dev, uint64_t *n_bytes) {
+    if (dev) *dev = o ? o->bytes : nullptr;
+    if (n_bytes) *n_bytes = o ? o->n : 0;
+}
+extern "C" int pp_masked_kernel_ms(const pp_masked *o, float *ms) {
+    if (!o || !ms) return PP_ERR_ARG;
+    if (!o->timed) return o->ctx->fail(PP_ERR_ARG, "pp_masked_kernel_ms: the context had no profiling on when the bytes were made (pp_ctx_set_profiling)");
+    *ms = o->ms;
+    return PP_OK;
+}
+
+extern "C" int pp_polish_masked(pp_ctx *ctx, uint32_t status_mask, pp_masked **out) {
+    if (!ctx) return PP_ERR_ARG;
+    if (int rdy = pp_ctx_wait(ctx)) return rdy;
+    if (out) *out = nullptr;
+    char msg[256] = "";
+    if (!out) return ctx->fail(PP_ERR_ARG, "pp_polish_masked: null argument");
+    if (int code = pp_bed_host::check_job("pp_polish_masked", bed_job_state(ctx), msg, sizeof msg)) return ctx->fail(code, "%s", msg);
+    if (int code = pp_bed_host::check_mask("pp_polish_masked", status_mask, msg, sizeof msg)) return ctx->fail(code, "%s", msg);
+    PP_HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint64_t G = ctx->G, n = ctx->total_out;
+    std::unique_ptr<pp_masked, void (*)(pp_masked *)> P(new pp_masked(), pp_masked_free);
+    P->ctx = ctx;
+    VcfScratch T;
+    int rc;
+    if ((rc = T.mark(ctx))) return rc;
+    {
+        void *q = nullptr;
+        PP_HIPCHK(ctx, hipMalloc(&q, std::max<size_t>((size_t)n, 16)));
+        P->bytes = (u8 *)q;
+        P->n = n;
+    }
+    if (n) PP_HIPCHK(ctx, hipMemcpyAsync(P->bytes, ctx->b_out.p, n, hipMemcpyDeviceToDevice, st));
+    if (G && n) {
+        const uint64_t nb = (G + VCF_TILE - 1) / VCF_TILE;
+        VcfJob J = vcf_job_of(ctx);
+        u64 *d_bsum = nullptr, *d_boff = nullptr;
+        if ((rc = vcf_emit_offsets(ctx, T, J, nb, d_bsum, d_boff))) return rc;
+        hipLaunchKernelGGL(k_bed_mask, dim3((unsigned)nb), dim3(VCF_THREADS), 0, st, J, (const u64 *)d_boff, (const u8 *)ctx->b_dbg_status.p, status_mask, P->bytes);
+        PP_HIPCHK(ctx, hipGetLastError());
+    }
+    if ((rc = T.mark(ctx))) return rc;
+    PP_HIPCHK(ctx, hipStreamSynchronize(st));
+    if (ctx->profiling && T.ev.size() == 2) {
+        PP_HIPCHK(ctx, hipEventElapsedTime(&P->ms, T.ev[0], T.ev[1]));
+        P->timed = true;
+    }
+    *out = P.release();
+    return PP_OK;
+}
+
+// ---- the file drivers' BED and soft mask (pp_driver.cpp) ----
+extern "C" int pp_ctx_set_bed(pp_ctx *ctx, int on, uint32_t status_mask, int bgzf) {
+    if (!ctx) return PP_ERR_ARG;
+    char msg[256] = "";
+    if (on)
+        if (int code = pp_bed_host::check_mask("pp_ctx_set_bed", status_mask, msg, sizeof msg)) return ctx->fail(code, "%s", msg);
+    ctx->bed_on = on != 0;
+    ctx->bed_mask = on ? status_mask : 0u;
+    ctx->bed_bgzf = on != 0 && bgzf != 0;
+    return PP_OK;
+}
+extern "C" int pp_ctx_bed(pp_ctx *ctx, pp_bytes *bed) {
+    if (!ctx) return PP_ERR_ARG;
+    if (!bed) return ctx->fail(PP_ERR_ARG, "pp_ctx_bed: null argument");
+    *bed = pp_bytes{nullptr, 0};
+    if (!ctx->bed_made) return ctx->fail(PP_ERR_ARG, "pp_ctx_bed: no driver has made a BED with pp_ctx_set_bed on this context");
+    bed->data = (uint8_t *)malloc(ctx->bed_bytes.size() + 1);
+    if (!bed->data) return ctx->fail(PP_ERR_HIP, "pp_ctx_bed: out of host memory");
+    memcpy(bed->data, ctx->bed_bytes.data(), ctx->bed_bytes.size());
+    bed->len = ctx->bed_bytes.size();
+    return PP_OK;
+}
+extern "C" int pp_ctx_set_soft_mask(pp_ctx *ctx, uint32_t status_mask) {
+    if (!ctx) return PP_ERR_ARG;
+    if (status_mask & ~pp_bed_host::MASK_ALL) return ctx->fail(PP_ERR_ARG, "pp_ctx_set_soft_mask: a status mask with a bit above 5");
+    ctx->soft_mask = status_mask;
+    return PP_OK;
+}
+// (internal, the file drivers) what pp_ctx_set_bed / pp_ctx_set_soft_mask were given; the file a driver made (data == NULL: none)
+extern "C" int pp_ctx_bed_form_(const pp_ctx *ctx, uint32_t *status_mask, int *bgzf) {
+    if (status_mask) *status_mask = ctx ? ctx->bed_mask : 0u;
+    if (bgzf) *bgzf = ctx && ctx->bed_bgzf ? 1 : 0;
+    return ctx && ctx->bed_on ? 1 : 0;
+}
+extern "C" uint32_t pp_ctx_soft_mask_(const pp_ctx *ctx) { return ctx ? ctx->soft_mask : 0u; }
+extern "C" void pp_ctx_keep_bed_(pp_ctx *ctx, const uint8_t *data, uint64_t n) {
+    ctx->bed_made = data != nullptr;
+    ctx->bed_bytes.assign(data ? (const char *)data : "", data ? (size_t)n : 0);
+    if (!data) ctx->bed_bytes.shrink_to_fit();
 }
 
 // (internal, the drivers) pinned host memory for the --debug TSV's chunks

@@ -157,11 +157,18 @@ def main(argv=None):
     ap.add_argument("--index", action="store_true")
     ap.add_argument("--vcf", default=None)
     ap.add_argument("--vcf_bgzf", action="store_true")
+    ap.add_argument("--bed", default=None)
+    ap.add_argument("--bed_bgzf", action="store_true")
+    ap.add_argument("--soft_mask", action="store_true")
+    ap.add_argument("--bed_status", default=None)
     ap.add_argument("assembly")
     ap.add_argument("sam", nargs="*")
     a = ap.parse_args(argv)
     if a.vcf is not None or a.vcf_bgzf:    # (a rank's share has no defined runs at its edges: pp_polish_vcf)
         raise SystemExit("Error: --vcf runs on one GPU: polish with `polypolish polish --vcf`, or without --vcf")
+    for flag, given in (("--bed", a.bed is not None or a.bed_bgzf), ("--soft_mask", a.soft_mask), ("--bed_status", a.bed_status is not None)):
+        if given:    # (the status plane of a rank is its share's: pp_polish_bed)
+            raise SystemExit(f"Error: {flag} runs on one GPU: polish with `polypolish polish {flag}`, or without {flag}")
     for flag, given in (("--out", a.out is not None), ("--wrap", a.wrap is not None), ("--out_bgzf", a.out_bgzf), ("--index", a.index)):
         if given:    # (rank 0 writes the FASTA here as the ranks' bytes arrive; the device link makes it on one context)
             raise SystemExit(f"Error: {flag} is not available here: rank 0 writes the FASTA itself; polish with `polypolish polish {flag}`, "
