@@ -235,12 +235,13 @@ __device__ __forceinline__ void dfmt_line(const DfmtJob &J, u64 p, DfmtLine &L) 
     L.inv = J.counts[6ull * J.G + p];
     L.r0 = p ? J.rec_end[p - 1] : 0u;
     L.r1 = J.rec_end[p];
-    u32 n = 0, bytes = 0, winner = ~0u;
+    u32 n = 0, bytes = 0, winner = ~0u, valid_key = ~0u;
     for (u32 q = 0; q < 4u + (L.r1 - L.r0); q++) {
         DfmtItem it;
         if (dfmt_item(J, L.cnt, L.r0, q, it)) {
             n++;
             bytes += dfmt_item_len(it);
+            if (q >= 4u && it.klen >= 2u && it.count >= L.val) valid_key = J.rec[L.r0 + q - 4u];  // a valid key of two bytes or more
         } else if (q >= 4u) {
             winner = J.rec[L.r0 + q - 4u] - J.n_keys;
         }
@@ -259,6 +260,15 @@ __device__ __forceinline__ void dfmt_line(const DfmtJob &J, u64 p, DfmtLine &L) 
         L.nb_off = w.off;
         L.nb_len = w.len;
     } else L.nb_len = 0;
+    // A winner of two bytes or more that leaves at most one once its '-' are dropped (polish.rs:188: "C-", "--") has a one-byte
+    // code and no entry in the winners' list; new_base is the winner as the reads have it.  Where the status is "changed" exactly
+    // one item is valid, the winner: it is that key if a key of two bytes or more is valid.
+    if (code < 0x80u && L.st == (u32)PP_ST_CHANGED && valid_key != ~0u) {
+        const KeyRec k = J.keys[valid_key];
+        L.from_seq = 1;
+        L.nb_off = k.off;
+        L.nb_len = k.len;
+    }
     L.len = (u32)(J.name_off[lo + 1] - J.name_off[lo]) + dfmt_ndig(L.rel) + 1u + (dfmt_ndig(L.tenths / 10u) + 2u) + dfmt_ndig(L.inv) +
             dfmt_ndig(L.val) + L.items_len + dfmt_status_len(L.st) + L.nb_len + 9u;
 }

@@ -2,7 +2,6 @@
 whole and in chunks, the depth's one decimal, the order of a position's items, every ingest route of the CLI, several
 contexts in one process, the one-process-per-GPU launcher and a full-size job.  Byte for byte against the oracle's TSV
 (oracle/pp_oracle.c, the reference's src/polish.rs:230-266 and src/pileup.rs:137-166).  Needs an MI355X: `-m gpu`."""
-import ctypes as C
 import hashlib
 import os
 import subprocess
@@ -12,12 +11,12 @@ import numpy as np
 import pytest
 
 import synth
+from debug_tsv_util import HEADER, _diff, _raw, _write_job
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "bin", "polypolish")
-HEADER = b"name\tpos\tbase\tdepth\tinvalid\tvalid\tpileup\tstatus\tnew_base\n"
 OPTION_SETS = (dict(), dict(min_depth=2, fraction_invalid=0.1, max_errors=3), dict(careful=True))
 
 
@@ -34,26 +33,12 @@ def ctx(pp):
     c.close()
 
 
-def _diff(got, want):
-    gl, wl = got.split(b"\n"), want.split(b"\n")
-    return len(gl), len(wl), [(a, b) for a, b in zip(gl, wl) if a != b][:4]
-
-
 def _device_tsv(pp, ctx, fasta, sams, **kw):
     """ingest on the host, polish with the debug records kept on the device, the TSV through Context.debug_tsv"""
     names, _, off, bases, recs, _ = pp.ingest(fasta, sams, max_errors=kw.get("max_errors", 10), careful=kw.get("careful", False))
     res = ctx.polish_records(off, bases, recs, min_depth=kw.get("min_depth", 5), fraction_valid=kw.get("fraction_valid", 0.5),
                              fraction_invalid=kw.get("fraction_invalid", 0.2), debug=True)
     return names, off, res
-
-
-def _raw(pp, ctx, names, lo, hi, cap, mem=0, out=None):
-    arr = (C.c_char_p * len(names))(*[n.encode() for n in names])
-    buf = np.full(max(cap, 1), 0xEE, dtype=np.uint8) if out is None else None
-    n, nxt = C.c_uint64(), C.c_uint64()
-    rc = pp.lib().pp_polish_debug_tsv(ctx._h, C.cast(arr, C.c_void_p), lo, hi, buf.ctypes.data if out is None else out, mem, cap,
-                                      C.byref(n), C.byref(nxt))
-    return rc, buf, n.value, nxt.value
 
 
 # ---- 1. the ABI, whole and chunked ------------------------------------------------------------------------------------
@@ -102,21 +87,6 @@ def test_abi_whole_and_chunked(pp, ctx, orc, tmp_path, case):
 
 
 # ---- hand-built jobs ---------------------------------------------------------------------------------------------------
-def _write_job(tmp, contigs, alns, name="hand"):
-    """contigs: [(name, bytes)]; alns: [(qname, contig, pos0, cigar, seq)] -- consecutive records of one qname are one
-    read group (share 1/k)."""
-    fa, sam = os.path.join(tmp, f"{name}.fasta"), os.path.join(tmp, f"{name}.sam")
-    with open(fa, "w") as f:
-        for n, s in contigs:
-            f.write(f">{n}\n{s}\n")
-    with open(sam, "w") as f:
-        for n, s in contigs:
-            f.write(f"@SQ\tSN:{n}\tLN:{len(s)}\n")
-        for q, c, p, cig, seq in alns:
-            f.write(f"{q}\t0\t{c}\t{p + 1}\t60\t{cig}\t*\t0\t0\t{seq}\t*\tNM:i:0\n")
-    return fa, sam
-
-
 def _check_hand_job(pp, ctx, orc, fa, sam, **kw):
     want = orc.polish_files(fa, [sam], debug=True, **kw)
     body = want["debug"][len(HEADER):]
