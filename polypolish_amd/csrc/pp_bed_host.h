@@ -1,4 +1,4 @@
-// pp_bed_host.h -- the host part of pp_status_bed, pp_polish_bed and pp_polish_masked (pp_k_bed.h, pp_kernels.hip): plain C++ with no
+// pp_bed_host.h -- the host part of pp_status_bed, pp_polish_bed and pp_polish_masked (pp_k_bed.h, pp_polish_text.hip): plain C++ with no
 // HIP in it, as pp_vcf_host.h, so that a stand-alone program can run it under a sanitizer (tools/bed_host_check.cpp).  It holds the
 // argument checks, the name table the kernels read, the parse of a status list (the commands' --bed_status) and the arithmetic of one
 // BED line -- its length and its k-th byte -- as constexpr functions: the text kernel calls the very same ones, so the digit widths

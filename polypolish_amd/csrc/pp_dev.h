@@ -5,7 +5,8 @@
 // by pp_devtext.h (the SAM tokenizers' text utilities), by pp_textin.h (a borrowed text's: pp_sam_out.hip, pp_sam_bam.hip) and
 // directly by the record chain: pp_bgzf.hip, pp_bgzf_deflate.hip,
 // pp_bam.hip, pp_bam_walk.hip, pp_bam_out.hip, pp_names.hip, pp_filter_rec.hip and pp_regroup.hip (through pp_filter_group.h), pp_bam_sort.hip (through pp_rg_sort.h),
-// pp_gate.hip and pp_prepare.hip.  Everything lives in an anonymous namespace: each translation unit gets its own copies, and of
+// pp_gate.hip and pp_prepare.hip, and by the units that make text from finished work: pp_fasta_out.hip and pp_polish_text.hip (the
+// polish's TSV, VCF, BED and soft mask), both also through pp_cut16.h.  Everything lives in an anonymous namespace: each translation unit gets its own copies, and of
 // the kernels that are templates only those it launches.
 #pragma once
 #include "pp_internal.h"
@@ -234,6 +235,13 @@ struct CallScratch {  // device memory of one call, released when it returns
         p.push_back(*out);
         return PP_OK;
     }
+    template <class T>
+    int alloc(pp_ctx *ctx, T *&a, size_t count) {  // get(), typed: `count` elements
+        void *q;
+        const int rc = get(ctx, &q, count * sizeof(T));
+        a = (T *)q;
+        return rc;
+    }
 };
 
 // A call's device memory out of grow-only buffers of the context (pp_ctx::f_rec, g_rec), handed out in the order of the requests:
@@ -264,12 +272,7 @@ struct DevOwner : CallScratch {
     explicit DevOwner(pp_ctx *c) : ctx(c) {}
     ~DevOwner() { (void)hipSetDevice(ctx->device); }  // (in front of the base's hipFree)
     template <class T>
-    int alloc(T *&a, size_t count) {
-        void *q;
-        const int rc = get(ctx, &q, count * sizeof(T));
-        a = (T *)q;
-        return rc;
-    }
+    int alloc(T *&a, size_t count) { return CallScratch::alloc(ctx, a, count); }
     void release(const void *a) {  // one allocation early; an array that is not the object's is left alone
         const auto it = std::find(p.begin(), p.end(), a);
         if (it == p.end()) return;

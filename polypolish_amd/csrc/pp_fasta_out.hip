@@ -16,12 +16,13 @@
 //                  the line and the place in it, the 15 or 16 bases are one run of the source.  The source's alignment is whatever
 //                  the offsets make it: the run is taken from the one or two 16-byte pieces of ADDRESS that hold it, each with one
 //                  wide load where the piece lies wholly inside the bases, byte by byte behind the test otherwise; v_alignbyte shifts
-//                  the run into place, the "\n" goes in with three masks
+//                  the run into place (piece16, bytes_from: pp_cut16.h, shared with k_vcf_text), the "\n" goes in with three masks
 //   the seams      any other lane -- a header, a contig's end, several whole contigs, a width below 16 -- walks its 16 bytes one at a
 //                  time: one division when it enters a body, increments from there
 // No byte outside bases[0, contig_off[n] - contig_off[0]) and outside the header bytes is loaded, by a wide load either.  Plain C++,
 // vector stores, no cross-workgroup wait, nothing depends on the order in which lanes run.
 #include "pp_dev.h"
+#include "pp_cut16.h"
 #include "pp_fasta_out_host.h"
 
 #include <cstring>
@@ -49,32 +50,6 @@ __device__ __forceinline__ u32 contig_of(const fo::Row *__restrict__ rows, u32 l
         else hi = mid - 1u;
     }
     return lo;
-}
-
-// the 16 bytes at the 16-byte multiple of address q: one wide load where they all are bases, else those in [lo, hi) one by one
-__device__ __forceinline__ uint4 piece16(const u8 *q, const u8 *lo, const u8 *hi) {
-    if ((uintptr_t)q >= (uintptr_t)lo && (uintptr_t)q + 16u <= (uintptr_t)hi) return *(const uint4 *)q;
-    u32 w[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (u32 j = 0; j < 16; j++) {
-        const uintptr_t a = (uintptr_t)q + j;
-        if (a >= (uintptr_t)lo && a < (uintptr_t)hi) w[j >> 2] |= (u32) * (const u8 *)a << (8 * (j & 3));
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// bytes [a, a + 16) of the 32 bytes (p0, p1), a in 0..15
-__device__ __forceinline__ uint4 bytes_from(const uint4 p0, const uint4 p1, u32 a) {
-    u32 x0, x1, x2, x3, x4;
-    switch (a >> 2) {
-    case 0: x0 = p0.x; x1 = p0.y; x2 = p0.z; x3 = p0.w; x4 = p1.x; break;
-    case 1: x0 = p0.y; x1 = p0.z; x2 = p0.w; x3 = p1.x; x4 = p1.y; break;
-    case 2: x0 = p0.z; x1 = p0.w; x2 = p1.x; x3 = p1.y; x4 = p1.z; break;
-    default: x0 = p0.w; x1 = p1.x; x2 = p1.y; x3 = p1.z; x4 = p1.w; break;
-    }
-    const u32 s = a & 3u;
-    return make_uint4(__builtin_amdgcn_alignbyte(x1, x0, s), __builtin_amdgcn_alignbyte(x2, x1, s), __builtin_amdgcn_alignbyte(x3, x2, s),
-                      __builtin_amdgcn_alignbyte(x4, x3, s));
 }
 
 // the mask of the bytes below byte k (k in 0..16) of word i of 16 bytes

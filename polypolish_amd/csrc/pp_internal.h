@@ -152,6 +152,21 @@ struct MetaView {
     bool ok() const { return w[MW_STATUS] == ~0ull; }
 };
 
+// ---- what a finished job leaves on the device beside its bytes: written by the polish kernels (pp_kernels.hip), read back by
+// pp_polish_debug_extra and read in place by the text passes (pp_polish_text.hip) ----
+struct KeyRec {    // debug only: one distinct non-ACGT key of a position (len 0 = the deletion key "-")
+    unsigned long long off;
+    uint32_t pos, len, count, pad;
+};
+
+struct MultiEnt {  // a position whose polished string has 2+ bytes (an insertion won the vote)
+    unsigned long long off;  // absolute offset of the winning string in the seq array
+    uint32_t pos;  // global assembly position
+    uint32_t len;  // raw byte length of the string
+    uint32_t eff;  // bytes left after removing '-' (polish.rs:188)
+    uint32_t pad;
+};
+
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;

@@ -1,5 +1,5 @@
 // pp_k_bed.h -- pp_status_bed / pp_polish_bed: the runs of equal per-position status (PP_ST_*) as BED text, and pp_polish_masked: the
-// polished bytes with the bytes of selected positions in lower case; both made on the device.  Part of pp_kernels.hip (included there,
+// polished bytes with the bytes of selected positions in lower case; both made on the device.  Part of pp_polish_text.hip (included there,
 // behind pp_k_vcf.h, whose scan, contig search, record bisection and emitted-length passes it shares, and nowhere else: it defines
 // __global__ kernels).  Nothing here runs unless a caller asks for it: the polish pipeline itself is untouched.  tests/bed_model.py
 // defines the bytes; pp_bed_host.h holds the argument checks and one line's arithmetic (bed::line_len, bed::line_byte: constexpr, the
@@ -8,11 +8,11 @@
 // The BED passes, BED_TILE positions a workgroup, BED_PPT consecutive ones a thread.  A status byte above 5 is selected by no mask.
 //   k_bed_runs     a position STARTS a run iff its status is selected and it is its contig's first position or its predecessor's status
 //                  differs; it ENDS one iff it is selected and its contig's last position or its successor's status differs.  The
-//                  starts per workgroup                                    -> k_dfmt_scan1: the first record of each workgroup.
+//                  starts per workgroup                                    -> k_colscan<1>: the first record of each workgroup.
 //                  The first status byte above 5, if any, by atomicMin (the host refuses the call)
 //   k_bed_recs     every start writes (a, status, contig), every end b, into its record's row: a position's record is the scan of
 //                  the starts.  No thread walks a run
-//   k_bed_reclen   a thread a record: its line's length, the sums per workgroup -> k_dfmt_scan1; the positions per status
+//   k_bed_reclen   a thread a record: its line's length, the sums per workgroup -> k_colscan<1>; the positions per status
 //   k_vcf_recoff   (pp_k_vcf.h) where each line begins in the text
 //   k_bed_text     the OUTPUT is cut, as in k_vcf_text: a lane owns 16 bytes of text and writes them with one aligned 16-byte store;
 //                  it finds the record of its first byte by bisection and makes every byte from the record's row.  Lines are short
@@ -21,7 +21,7 @@
 // its allocation ends, so a thread takes its 8 bytes with one load only where they are 8-byte aligned and all inside the array.
 //
 // The mask pass, cut by POSITIONS (the status is per position; where a position's bytes lie in the output is the scan of the emitted
-// lengths, k_vcf_multi / k_vcf_sum / k_dfmt_scan1 as pp_polish_vcf runs them):
+// lengths, k_vcf_multi / k_vcf_sum / k_colscan<1> as pp_polish_vcf runs them):
 //   (copy)         the polished bytes are copied whole, device to device, at the memory's rate
 //   k_bed_mask     a thread reads the 8 codes and 8 status bytes of its positions (one 8-byte load each) and stores the lower-case form
 //                  of every byte 'A'..'Z' a selected position emits -- bytes only, each one written by the one thread that owns its
@@ -221,7 +221,7 @@ __global__ __launch_bounds__(BED_THREADS) void k_bed_text(BedText X, u8 *__restr
 }
 
 // ---- the mask pass: dst is a copy of J.out already ----
-// status: the job's own plane (256-byte aligned, G bytes); boff: where each workgroup's emitted bytes begin (k_vcf_sum, k_dfmt_scan1)
+// status: the job's own plane (256-byte aligned, G bytes); boff: where each workgroup's emitted bytes begin (k_vcf_sum, k_colscan<1>)
 __global__ __launch_bounds__(VCF_THREADS) void k_bed_mask(VcfJob J, const u64 *__restrict__ boff, const u8 *__restrict__ status, u32 mask,
                                                           u8 *__restrict__ dst) {
     __shared__ u64 s_w[VCF_THREADS / 64];

@@ -19,19 +19,6 @@ typedef uint8_t u8;
 enum { ROW_A = 0, ROW_C = 1, ROW_T = 2, ROW_G = 3, ROW_DEL = 4, ROW_OTH = 5, ROW_MIS = 6, ROW_COV = 7,
        ROW_DEF = 8, N_ROWS = 9 };
 
-struct KeyRec {    // debug only: one distinct non-ACGT key of a position (len 0 = the deletion key "-")
-    u64 off;
-    u32 pos, len, count, pad;
-};
-
-struct MultiEnt {  // a position whose polished string has 2+ bytes (an insertion won the vote)
-    u64 off;       // absolute offset of the winning string in the seq array
-    u32 pos;       // global assembly position
-    u32 len;       // raw byte length of the string
-    u32 eff;       // bytes left after removing '-' (polish.rs:188)
-    u32 pad;
-};
-
 // the job's metadata block (MetaWord, pp_internal.h): the status starts as "no error" (all ones: errors are combined with
 // atomicMin), the counters and sizes behind it start at zero -- one launch where two memsets left a gap between them
 // ... and the job's table of the vote's two thresholds for every INTEGER depth below VOTE_TAB_N (d_bankers is defined below):
@@ -154,10 +141,7 @@ __device__ __forceinline__ u32 wave_sum(u32 v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
-__device__ __forceinline__ u64 wave_sum64(u64 v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+// (wave_sum64, the same over 64-bit values, is pp_wave.h's: the text passes of pp_polish_text.hip sum with it too)
 
 // trim of a read without indels: index of the first base of the trailing homopolymer; the kept
 // entries are [0, start-1) (alignment.rs:364-378: pop the run, then one more)

@@ -1,15 +1,15 @@
 // pp_k_debug.h -- the --debug TSV, formatted on the device (write_debug_line, src/polish.rs:257-266; get_debug_line /
-// get_count_str, src/pileup.rs:137-166).  Part of pp_kernels.hip (included there, after pp_k_emit.h, and nowhere else: it
+// get_count_str, src/pileup.rs:137-166).  Part of pp_polish_text.hip (included there, behind pp_dev.h, and nowhere else: it
 // defines __global__ kernels).  Nothing here runs unless a caller asks for the TSV (pp_polish_debug_tsv): the polish
 // pipeline itself is untouched.
 //
 // What a line is made of is on the device after a job with debug records: depth, the seven planes of counts / thresholds,
 // the status, the emit code, the key records (KeyRec, atomic-append order) and the multi-byte winners (MultiEnt).
-//   once per job   k_dfmt_count / k_dfmt_bsum / k_dfmt_scan1 / k_dfmt_apply / k_dfmt_scatter: the key records and the
+//   once per job   k_dfmt_count / k_dfmt_bsum / k_colscan<1> (pp_dev.h) / k_dfmt_apply / k_dfmt_scatter: the key records and the
 //                  multi-byte winners grouped by position (count, exclusive scan, scatter): rec_end[p] = one past the
 //                  position's last entry of rec[], which holds record ids (< n_keys: a key, else a multi-byte winner)
 //   per chunk      k_dfmt_len: the length of every line of [p0, p0 + N), one thread a position, and the workgroups' sums;
-//                  k_dfmt_scan1: their exclusive scan (u64 line offsets); k_dfmt_write: every workgroup stages its lines
+//                  k_colscan<1>: their exclusive scan (u64 line offsets); k_dfmt_write: every workgroup stages its lines
 //                  in LDS, DFMT_WIN bytes at a time, and stores them with 16-byte stores where the destination allows.
 //                  Only the lines that end within the room are written; the workgroup that holds the last of them reports
 //                  how many positions and bytes that is.
@@ -59,8 +59,9 @@ __global__ __launch_bounds__(256) void k_dfmt_scatter(const KeyRec *__restrict__
     if (pos < G) rec[atomicAdd(&next[pos], 1u)] = (u32)i;
 }
 
-// exclusive scan of n u32 in place: block sums (DFMT_SCAN_PER x 256 elements a workgroup), one workgroup scans them, every
-// workgroup then scans its own elements on top of its base
+// exclusive scan of n u32 IN PLACE: block sums (DFMT_SCAN_PER x 256 elements a workgroup), one workgroup scans them (k_colscan<1>),
+// every workgroup then scans its own elements on top of its base.  (Not pp_dev.h's scan_u32: that one writes a second array, 4
+// more bytes per assembly position of a --debug job.)
 __global__ __launch_bounds__(256) void k_dfmt_bsum(const u32 *__restrict__ a, u64 n, u64 *__restrict__ bsum) {
     __shared__ u64 s_w[4];
     const u64 base = ((u64)blockIdx.x * 256u + threadIdx.x) * DFMT_SCAN_PER;
@@ -71,30 +72,6 @@ __global__ __launch_bounds__(256) void k_dfmt_bsum(const u32 *__restrict__ a, u6
     if ((threadIdx.x & 63u) == 0) s_w[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) bsum[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-// out[0..nb] = exclusive scan of in[0..nb): one workgroup, a stretch of the sums per thread
-__global__ __launch_bounds__(1024) void k_dfmt_scan1(const u64 *__restrict__ in, u64 nb, u64 *__restrict__ out) {
-    __shared__ u64 part[1024];
-    const u32 t = threadIdx.x;
-    const u64 per = (nb + 1023) / 1024;
-    const u64 lo = min(nb, (u64)t * per), hi = min(nb, lo + per);
-    u64 s = 0;
-    for (u64 i = lo; i < hi; i++) s += in[i];
-    part[t] = s;
-    __syncthreads();
-    for (u32 off = 1; off < 1024; off <<= 1) {
-        const u64 v = t >= off ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    u64 run = part[t] - s;
-    for (u64 i = lo; i < hi; i++) {
-        out[i] = run;
-        run += in[i];
-    }
-    if (t == 1023) out[nb] = part[1023];
 }
 
 __global__ __launch_bounds__(256) void k_dfmt_apply(u32 *__restrict__ a, u64 n, const u64 *__restrict__ boff) {
@@ -371,7 +348,7 @@ __global__ __launch_bounds__(DFMT_THREADS) void k_dfmt_len(DfmtJob J, u64 p0, u3
 }
 
 // ---- the write pass ----------------------------------------------------------------------------------------------------
-// boff: the workgroups' first bytes (k_dfmt_scan1 over k_dfmt_len's sums); room: bytes of dst that may be written.  res[0] =
+// boff: the workgroups' first bytes (k_colscan<1> over k_dfmt_len's sums); room: bytes of dst that may be written.  res[0] =
 // positions whose lines fit (from p0 on), res[1] = their bytes -- written by the thread of the last line that fits (the host
 // zeroes res: no line fits, no writer).
 __global__ __launch_bounds__(DFMT_THREADS) void k_dfmt_write(DfmtJob J, u64 p0, u32 N, const u32 *__restrict__ len,

@@ -1,20 +1,21 @@
 // pp_k_vcf.h -- pp_polish_vcf: the polish's edits as VCF text, made on the device from what a finished job leaves there: the assembly
-// bases, the emit codes (code_len, pp_k_emit.h), the multi-byte winners' list and the polished bytes.  Part of pp_kernels.hip
+// bases, the emit codes (code_len, pp_k_emit.h), the multi-byte winners' list and the polished bytes.  Part of pp_polish_text.hip
 // (included there, after pp_k_debug.h, and nowhere else: it defines __global__ kernels).  Nothing here runs unless a caller asks for
-// the VCF: the polish pipeline itself is untouched.  tests/vcf_model.py defines the bytes; pp_vcf_host.h builds the header.
+// the VCF: the polish pipeline itself is untouched.  tests/vcf_model.py defines the bytes; pp_vcf_host.h builds the header.  The
+// single-workgroup scan of the workgroups' sums is pp_dev.h's k_colscan<1>, the 16-byte cuts of k_vcf_text are pp_cut16.h's.
 //
 // The seq array is NOT read (a caller may have released it): a position's emitted bytes are the polished output at the scan of the
 // emitted lengths.  The passes, VCF_TILE positions a workgroup, VCF_PPT consecutive ones a thread:
 //   k_vcf_multi    the emitted length of every position whose code does not hold it (0xFF), from the multi-byte winners' list
-//   k_vcf_sum      the emitted bytes per workgroup                         -> k_dfmt_scan1: where each workgroup's bytes begin
+//   k_vcf_sum      the emitted bytes per workgroup                         -> k_colscan<1>: where each workgroup's bytes begin
 //   k_vcf_mark     a flag per position: EDITED iff it does not emit exactly its assembly byte (codes 1..127: the code itself; a
 //                  multi-byte code of one byte: that byte of the polished output)
 //   k_vcf_runs     the flags of the two neighbours and the contig table make run STARTS and ENDS (no run joins across a contig
-//                  boundary), and the starts per workgroup                 -> k_dfmt_scan1: the first record of each workgroup
+//                  boundary), and the starts per workgroup                 -> k_colscan<1>: the first record of each workgroup
 //   k_vcf_recs     every start writes (a, output offset of a), every end (b, output offset of b) into its record's row: a
 //                  position's record is the scan of the starts.  No thread walks a run
 //   k_vcf_reclen   a thread a record: its case (vcf_fields: the table in vcf_model.py), its line's length, the sums per workgroup
-//                                                                          -> k_dfmt_scan1
+//                                                                          -> k_colscan<1>
 //   k_vcf_recoff   where each line begins in the text
 //   k_vcf_text     the OUTPUT is cut, as in k_fasta_text: a lane owns 16 bytes of text and writes them with one aligned 16-byte
 //                  store; it finds the record of its first byte by bisection and takes every byte from where the record says it
@@ -24,6 +25,7 @@
 //                  many lanes as its text has 16-byte words.
 // Device memory beyond the text: 2 flag bytes per position, 4 more when the job has multi-byte winners, 40 bytes per record.
 #pragma once
+#include "pp_cut16.h"
 
 namespace pp {
 
@@ -323,38 +325,6 @@ __device__ __forceinline__ u32 vcf_byte(const VcfText &X, const VcfLine &L, u64 
     return k == 6u ? (u32)'\n' : ((k & 1u) ? (u32)'.' : (u32)'\t');
 }
 
-// the 16 bytes at the 16-byte multiple of address q: one wide load where they all lie in [lo, hi), else those that do, one by one
-__device__ __forceinline__ uint4 vcf_piece16(const u8 *q, const u8 *lo, const u8 *hi) {
-    if ((uintptr_t)q >= (uintptr_t)lo && (uintptr_t)q + 16u <= (uintptr_t)hi) return *(const uint4 *)q;
-    u32 w[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (u32 j = 0; j < 16; j++) {
-        const uintptr_t a = (uintptr_t)q + j;
-        if (a >= (uintptr_t)lo && a < (uintptr_t)hi) w[j >> 2] |= (u32) * (const u8 *)a << (8 * (j & 3));
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-// bytes [a, a + 16) of the 32 bytes (p0, p1), a in 0..15
-__device__ __forceinline__ uint4 vcf_bytes_from(const uint4 p0, const uint4 p1, u32 a) {
-    u32 x0, x1, x2, x3, x4;
-    switch (a >> 2) {
-    case 0: x0 = p0.x; x1 = p0.y; x2 = p0.z; x3 = p0.w; x4 = p1.x; break;
-    case 1: x0 = p0.y; x1 = p0.z; x2 = p0.w; x3 = p1.x; x4 = p1.y; break;
-    case 2: x0 = p0.z; x1 = p0.w; x2 = p1.x; x3 = p1.y; x4 = p1.z; break;
-    default: x0 = p0.w; x1 = p1.x; x2 = p1.y; x3 = p1.z; x4 = p1.w; break;
-    }
-    const u32 s = a & 3u;
-    return make_uint4(__builtin_amdgcn_alignbyte(x1, x0, s), __builtin_amdgcn_alignbyte(x2, x1, s), __builtin_amdgcn_alignbyte(x3, x2, s),
-                      __builtin_amdgcn_alignbyte(x4, x3, s));
-}
-// 16 bytes from src (any alignment), all of them inside [lo, hi)
-__device__ __forceinline__ uint4 vcf_copy16(const u8 *src, const u8 *lo, const u8 *hi) {
-    const u32 a = (u32)((uintptr_t)src & 15u);
-    const uint4 p0 = vcf_piece16(src - a, lo, hi);
-    const uint4 p1 = a ? vcf_piece16(src - a + 16, lo, hi) : make_uint4(0, 0, 0, 0);
-    return vcf_bytes_from(p0, p1, a);
-}
-
 // the largest r in [lo, hi] with rec_at[r] <= t (rec_at[lo] <= t)
 __device__ __forceinline__ u64 vcf_record_of(const u64 *__restrict__ rec_at, u64 lo, u64 hi, u64 t) {
     while (lo < hi) {
@@ -392,10 +362,10 @@ __global__ __launch_bounds__(VCF_THREADS) void k_vcf_text(VcfText X, u8 *__restr
                 // ---- the bulk: 16 bytes of one REF, or of one ALT that lies in the polished output ----
                 const u64 k0 = t0 - L.at, kr = L.nlen + 1u + L.F.nd + 3u, ka = kr + L.F.reflen + 1u;
                 if (k0 >= kr && k0 + VCF_LANE <= kr + L.F.reflen && L.F.ref_at + L.F.reflen <= X.G) {
-                    v = vcf_copy16(X.bases + L.F.ref_at + (k0 - kr), X.bases, X.bases + X.G);
+                    v = copy16(X.bases + L.F.ref_at + (k0 - kr), X.bases, X.bases + X.G);
                     done = true;
                 } else if (L.F.kind == 0u && k0 >= ka && k0 + VCF_LANE <= ka + L.F.altlen && L.F.alt_at + L.F.altlen <= X.total_out) {
-                    v = vcf_copy16(X.out + L.F.alt_at + (k0 - ka), X.out, X.out + X.total_out);
+                    v = copy16(X.out + L.F.alt_at + (k0 - ka), X.out, X.out + X.total_out);
                     done = true;
                 }
             }

@@ -1,4 +1,4 @@
-// pp_vcf_host.h -- the host part of pp_polish_vcf (pp_k_vcf.h, pp_kernels.hip): what is proportional to the number of contigs, plain
+// pp_vcf_host.h -- the host part of pp_polish_vcf (pp_k_vcf.h, pp_polish_text.hip): what is proportional to the number of contigs, plain
 // C++ with no HIP in it, as pp_fasta_out_host.h, so that a stand-alone program can run it under a sanitizer
 // (tools/vcf_host_check.cpp).  plan() judges the caller's arguments and the state of the context's job, and builds the VCF header and
 // the name table the kernels read.  tests/vcf_model.py defines the bytes.  It reads contig_off[0, n], names[0, n) and every name up

@@ -1,5 +1,6 @@
 // pp_wave.h -- the wave-wide scan shared by the polish kernels (pp_kernels.hip, through pp_k_common.h) and the workgroup scans of
-// pp_dev.h (the record chain: pp_bam.hip, pp_names.hip, pp_gate.hip).  Device code only.
+// pp_dev.h (the record chain: pp_bam.hip, pp_names.hip, pp_gate.hip), and the wave-wide 64-bit sum of the polish kernels and the
+// text passes (pp_polish_text.hip).  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,6 +19,12 @@ __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);   // row_shr:8
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);  // row_bcast:15 into rows 1 and 3
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);  // row_bcast:31 into rows 2 and 3
+    return v;
+}
+
+// The sum of a 64-bit value over the wave's 64 lanes, the same in every lane (a butterfly of shuffles).
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
 

@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 # the kernels' tile constants (polypolish_amd/csrc/pp_k_vcf.h: VCF_PPT, VCF_TILE, VCF_LANE, VCF_TEXT_WG), repeated here and checked
 # against the library's own report below
 PPT, TILE, LANE, TEXT_WG = 8, 2048, 16, 16384
-SCAN1_THREADS = 1024  # k_dfmt_scan1 (pp_k_debug.h): one thread scans ceil(workgroups / 1024) workgroup sums
+SCAN1_THREADS = 1024  # k_colscan<1> (pp_dev.h): one thread scans ceil(workgroups / 1024) workgroup sums
 
 
 @pytest.fixture(scope="module")

@@ -4,15 +4,17 @@ profiles/dev_common_isa.txt was made with -- per unit, before and after a change
     hipcc <the Makefile's HIPFLAGS> --cuda-device-only -S polypolish_amd/csrc/pp_gate.hip -o after/pp_gate.s
     python tools/isa_same.py before/pp_gate.s after/pp_gate.s
 One line per kernel: unit, name, instructions before, after, same yes/no; then the kernels that went away and those that came.
-A listing is split at the kernel symbols; directives and comments are dropped, branch labels lose their function number and
-mangled names their spelling, so that only the instructions and where the branches go are compared.  Exit status 1 if a kernel
+A listing is split at the kernel symbols; directives and comments are dropped, branch labels lose their function number,
+mangled names their spelling and string constants their number within the unit, so that only the instructions and where the
+branches go are compared.  Exit status 1 if a kernel
 differs or a new one appears."""
 import os
 import re
 import sys
 
 # a kernel that took another name on the way: the name before -> the name after
-RENAMED = {"k_gate_scan3": "k_colscan<3>", "k_bam_scan3": "k_colscan<3>", "k_nm_scan2": "k_colscan<2>"}
+RENAMED = {"k_gate_scan3": "k_colscan<3>", "k_bam_scan3": "k_colscan<3>", "k_nm_scan2": "k_colscan<2>",
+           "k_dfmt_scan1": "k_colscan<1>"}
 ARG = {"y": "u64", "j": "u32", "Lb0": "false", "Lb1": "true"}
 
 
@@ -33,12 +35,14 @@ def kernel_name(sym):
 def kernels(path):
     """{name: [normalised instruction and label lines]}"""
     out, cur = {}, None
-    for line in open(path):
+    text = open(path).read()
+    functions = set(re.findall(r"^\s*\.type\s+(_Z\w+),@function", text, re.M))  # (a table in constant memory is no kernel)
+    for line in text.splitlines():
         line = line.split(";")[0].rstrip()
         s = line.strip()
         m = re.match(r"(_Z\w+):$", s)
         if m:
-            cur = out.setdefault(kernel_name(m.group(1)), [])
+            cur = out.setdefault(kernel_name(m.group(1)), []) if m.group(1) in functions else None
             continue
         if s.startswith(".Lfunc_end"):
             cur = None
@@ -46,6 +50,7 @@ def kernels(path):
             continue
         s = re.sub(r"\.LBB\d+_", ".LBB_", s)
         s = re.sub(r"_Z\w+", "SYM", s)
+        s = re.sub(r"\.str(\.\d+)?@", ".str@", s)  # (string constants are numbered per unit, in the order of their first use)
         cur.append(" ".join(s.split()))
     return out
 
