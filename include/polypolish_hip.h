@@ -1070,6 +1070,52 @@ void pp_masked_bytes(const pp_masked *o, const uint8_t **dev, uint64_t *n_bytes)
 int pp_masked_kernel_ms(const pp_masked *o, float *ms);
 void pp_masked_free(pp_masked *o);
 
+/* ---- read depth: the per-position depth as bedGraph text, on the device (pp_k_depth.h; not in the reference) ----
+ * A polish computes a read depth for every assembly position: the double that PileupBase::add_seq accumulates from the reads' 1/k
+ * shares (src/pileup.rs:56-65).  pp_depth_bedgraph writes a caller's array of such depths as bedGraph text in device memory -- the
+ * format of `bedtools genomecov -bga` --, pp_polish_depth does so for the finished job's own depth plane.  tests/depth_model.py
+ * defines the bytes:
+ *   tenths(x)  the integer 10 x rounded from x's exact binary value, ties to even: what format!("{:.1}") and the --debug TSV print,
+ *              without the point (0 <= x < 2^32)
+ *   text       no header or track line.  Per record, in assembly order:  name \t start \t end \t value \n  -- start and end 0-based,
+ *              half-open and local to the contig; names are written verbatim
+ *   bin == 0   (runs) a record is a maximal run of consecutive positions of ONE contig (runs never join across a contig boundary)
+ *              that share one tenths value -- two doubles that print alike are one run, zero-depth runs are written like any other;
+ *              value = tenths / 10 '.' tenths % 10
+ *   bin == W   (bins, 1 <= W <= 2^24) per contig of length L one record per bin [kW, min((k+1)W, L)), k = 0 .. ceil(L/W) - 1, equal
+ *              neighbours not merged; value = the mean of the bin's depths as printed, to two decimals, in integer arithmetic: with
+ *              S the sum of the bin's tenths and n its length, q = 10 S / n rounded, ties to even, written q / 100 '.' and the two
+ *              digits of q % 100 -- exact and free of the order of the sum
+ *   summary    zero_positions: the positions whose tenths are 0; max_tenths; sum_tenths: over all positions
+ * pp_depth_bedgraph: `depth` holds G = contig_off[n_contigs] doubles (PP_MEM_HOST: uploaded; PP_MEM_DEVICE: read in place -- aligned
+ * to 8 bytes, and no byte outside [0, 8 G) is loaded, by a wide load either: the array may end where its allocation ends); contig_off
+ * and contig_names as for pp_status_bed.  pp_polish_depth is valid after a successful pp_polish_finish of a job that ran with
+ * pp_polish_set_debug(ctx, 1), and until the next pp_polish_begin, whichever path the job took.
+ * Refusals, decided on the host before anything is launched except the last two: PP_ERR_ARG for a null argument, PP_MEM_PEER,
+ * bin > 2^24, a device array that is not aligned to 8 bytes, contig_off[0] != 0, offsets that decrease, G >= 2^32, a name that holds a
+ * tab or a newline; for pp_polish_depth a context without a finished job (a job that ended in an error leaves none), a job finished
+ * without pp_polish_set_debug(ctx, 1) (it kept no depth), a context with pp_polish_set_emit ranges; a depth whose sign bit is set
+ * (-0.0 too), that is not a number, or is 2^32 or more, *bad_pos = the first such position (a device check; bad_pos may be NULL);
+ * PP_ERR_LIMIT for a text of 2^40 bytes or more (known once the device has scanned the lines' lengths, before the text is allocated).
+ * n_contigs == 0 gives an empty text, a contig of length 0 no record.  Both calls return with the context's stream synchronised.  The
+ * object belongs to its context (free it before the context).  Device memory beyond the result: no plane per position (the tenths
+ * are made again where a pass needs them), 8 bytes per workgroup of 2048 positions in the runs form, 8 bytes per bin in the bins
+ * form; per record 24 bytes for its row and 8 for its place in the text (8 G bytes more for a PP_MEM_HOST array).
+ *   pp_depth_out_bytes      the text (DEVICE, borrowed until pp_depth_out_free): pp_bgzf_deflate(ctx, dev, n_bytes, PP_MEM_DEVICE, ...)
+ *                           makes the bgzipped file
+ *   pp_depth_out_summary    the three numbers above (any of the pointers may be NULL)
+ *   pp_depth_out_write      as pp_vcf_out_write
+ *   pp_depth_out_kernel_ms  as pp_vcf_out_kernel_ms: the HIP-event spans of the call's stages (the context had pp_ctx_set_profiling on) */
+typedef struct pp_depth_out pp_depth_out;
+int pp_depth_bedgraph(pp_ctx *ctx, const double *depth, int mem, uint32_t n_contigs, const uint64_t *contig_off /*HOST*/,
+                      const char *const *contig_names, uint32_t bin, pp_depth_out **out, uint64_t *bad_pos);
+int pp_polish_depth(pp_ctx *ctx, const char *const *contig_names, uint32_t bin, pp_depth_out **out);
+void pp_depth_out_bytes(const pp_depth_out *o, const uint8_t **dev, uint64_t *n_bytes, uint64_t *n_records); /* DEVICE, borrowed */
+void pp_depth_out_summary(const pp_depth_out *o, uint64_t *zero_positions, uint64_t *max_tenths, uint64_t *sum_tenths);
+int pp_depth_out_write(const pp_depth_out *o, const char *path);
+int pp_depth_out_kernel_ms(const pp_depth_out *o, float *ms);
+void pp_depth_out_free(pp_depth_out *o);
+
 /* Per-kernel device time of the last pp_polish_finish, measured with HIP events on the context's
  * stream when profiling is enabled.  names[i] are static strings. */
 #define PP_MAX_KERNELS 16
@@ -1490,6 +1536,17 @@ int pp_ctx_vcf(pp_ctx *ctx, pp_bytes *vcf);
 int pp_ctx_set_bed(pp_ctx *ctx, int on, uint32_t status_mask, int bgzf);
 int pp_ctx_bed(pp_ctx *ctx, pp_bytes *bed);
 int pp_ctx_set_soft_mask(pp_ctx *ctx, uint32_t status_mask);   /* 0 = off */
+
+/* The read depth as a bedGraph file next to the FASTA (the commands' --depth, --depth_bin, --depth_bgzf; not in the reference).  With
+ * pp_ctx_set_depth(on != 0) pp_polish_files, pp_filter_polish_files and pp_polish_files_multi on ONE context keep the job's
+ * per-position records (as for a --debug file; no TSV is written unless the options ask for one), run pp_polish_depth with `bin`
+ * behind their polish, on every input route, and with bgzf != 0 pass the device text through pp_bgzf_deflate; pp_ctx_depth returns the
+ * file of the last such run that succeeded (HOST, release with pp_bytes_free; PP_ERR_ARG when there is none -- a run that begins drops
+ * the file of the run before, a run that fails leaves none).  The FASTA, the log and every other output are the plain run's, byte for
+ * byte.  Several contexts are refused by name (PP_ERR_QUIT "--depth runs on one GPU ...") before any input is looked at.  PP_ERR_ARG:
+ * bin > 2^24 with on != 0.  The state lives on the context; off when it is made. */
+int pp_ctx_set_depth(pp_ctx *ctx, int on, uint32_t bin, int bgzf);
+int pp_ctx_depth(pp_ctx *ctx, pp_bytes *depth);
 
 /* polish::polish (src/polish.rs:26-38): FASTA text exactly as the reference prints to stdout.
  * `sams` are SAM text files or -- all of them -- BAM files (pp_aln_file_kind; a mix is PP_ERR_QUIT).  BAM goes through the record

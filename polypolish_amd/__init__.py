@@ -1240,6 +1240,77 @@ def bed_geometry():
     return tuple(int(x.value) for x in v)
 
 
+class DepthTrack(_Owned):
+    """pp_polish_depth / pp_depth_bedgraph: a per-position read depth as bedGraph text in DEVICE memory, owned by this object
+    (tests/depth_model.py defines the bytes): the runs of equal printed depth (bin=0) or the mean printed depth of bins of `bin`
+    positions.
+      DepthTrack(ctx, names, bin)                     of the context's finished job (it ran with debug records: polish_records(debug=True))
+      DepthTrack(ctx, names, bin, depth, contig_off)  of a caller's depths: a numpy float64 array (mem=MEM_HOST) or a device address
+                                                      (mem=MEM_DEVICE); .bad_pos holds the first bad position when refused
+      names          one contig name (bytes / str) per contig
+      .n_records, .n_bytes
+      .bytes()       the text as bytes (a download);  .dev(): (device address, n_bytes);  .deflate(): pp_bgzf_deflate on the device bytes
+      .summary()     {"zero_positions", "max_tenths", "sum_tenths"}: positions that print 0.0, the largest and the summed tenths
+      .write(path)   pp_depth_out_write: the text on disk
+      .kernel_ms()   HIP-event time of the kernels (the context had set_profiling on); .stage_ms(): values | records | lengths | text
+      .close()       frees the text"""
+    _free, _kernel_ms = "pp_depth_out_free", "pp_depth_out_kernel_ms"
+
+    def __init__(self, ctx, names, bin=0, depth=None, contig_off=None, mem=MEM_HOST):  # noqa: A002 (the C argument's name)
+        L = lib()
+        enc = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+        arr = (C.c_char_p * max(len(enc), 1))(*enc)
+        super().__init__(ctx)
+        self.bad_pos = None
+        if depth is None:
+            ctx._chk(L.pp_polish_depth(ctx._h, C.cast(arr, C.c_void_p), int(bin), C.byref(self._p)))
+        else:
+            off = np.ascontiguousarray(contig_off, dtype=np.uint64)
+            if mem == MEM_HOST:
+                keep = np.ascontiguousarray(depth, dtype=np.float64)
+                ptr = keep.ctypes.data if keep.size else C.addressof(C.c_double())  # (nobody reads it: any address but NULL)
+            else:
+                ptr = int(depth)
+            bad = C.c_uint64(0)
+            rc = L.pp_depth_bedgraph(ctx._h, ptr, mem, len(off) - 1, off.ctypes.data, C.cast(arr, C.c_void_p), int(bin), C.byref(self._p), C.byref(bad))
+            if rc:
+                self.bad_pos = int(bad.value)
+                e = PolypolishError(rc, L.pp_last_error(ctx._h).decode())
+                e.bad_pos = self.bad_pos
+                raise e
+        dev, nb, nr = C.c_void_p(), C.c_uint64(0), C.c_uint64(0)
+        L.pp_depth_out_bytes(self._p, C.byref(dev), C.byref(nb), C.byref(nr))
+        self.bytes_ptr, self.n_bytes, self.n_records = dev.value or 0, int(nb.value), int(nr.value)
+
+    def dev(self):
+        return self.bytes_ptr, self.n_bytes
+
+    def bytes(self):
+        return self._ctx.download(self.bytes_ptr, self.n_bytes, np.uint8).tobytes() if self.n_bytes else b""
+
+    def summary(self):
+        z, m, s = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        lib().pp_depth_out_summary(self._p, C.byref(z), C.byref(m), C.byref(s))
+        return {"zero_positions": int(z.value), "max_tenths": int(m.value), "sum_tenths": int(s.value)}
+
+    def deflate(self):
+        return BgzfDeflated(self._ctx, self.dev(), mem=MEM_DEVICE)
+
+    def write(self, path):
+        self._ctx._chk(lib().pp_depth_out_write(self._p, os.fsencode(path)))
+
+    def stage_ms(self):
+        return self._stage_ms("pp_depth_out_stage_ms_", ("values", "records", "lengths", "text"), " when the text was made")
+
+
+def depth_geometry():
+    """(positions per thread P, positions per workgroup T, text bytes per store, text bytes per workgroup) of pp_depth_bedgraph: the
+    position passes cut the depth array, the text pass cuts the text -- the seams its tests aim at."""
+    v = [C.c_uint32() for _ in range(4)]
+    lib().pp_depth_geometry_(*[C.byref(x) for x in v])
+    return tuple(int(x.value) for x in v)
+
+
 def fasta_out_geometry():
     """(bytes per store S, bytes per workgroup G) of pp_fasta_text: a lane writes S bytes of TEXT with one aligned store, a workgroup
     owns the text offsets [k * G, (k + 1) * G): the seams its tests aim at."""
@@ -2162,6 +2233,53 @@ class Context:
             self.set_bed(False)
             self.set_soft_mask(0)
 
+    def depth_bedgraph(self, depth, contig_off, names, bin=0, mem=MEM_HOST):  # noqa: A002
+        """pp_depth_bedgraph: a caller's per-position depths (numpy float64, or a device address with mem=MEM_DEVICE) -> DepthTrack"""
+        return DepthTrack(self, names, bin, depth, contig_off, mem)
+
+    def polish_depth(self, names, bin=0):  # noqa: A002
+        """pp_polish_depth: the finished job's own depth plane (it ran with debug records) -> DepthTrack"""
+        return DepthTrack(self, names, bin)
+
+    def set_depth(self, on=True, bin=0, bgzf=False):  # noqa: A002
+        """pp_ctx_set_depth: polish_files and filter_polish_files keep the per-position depth and run pp_polish_depth behind their
+        polish (bgzf: pp_bgzf_deflate behind it); depth() fetches the file"""
+        self._chk(lib().pp_ctx_set_depth(self._h, int(bool(on)), int(bin) if on else 0, int(bool(bgzf))))
+
+    def depth(self):
+        """pp_ctx_depth: the depth track (bytes) of the last command that made one on this context"""
+        b = Bytes()
+        self._chk(lib().pp_ctx_depth(self._h, C.byref(b)))
+        return _take_bytes(b)
+
+    @contextlib.contextmanager
+    def _making_depth(self, depth, depth_bin, depth_bgzf):
+        """depth= (a path), depth_bin= and depth_bgzf= of one command: pp_ctx_set_depth for its duration; the function this yields
+        writes the file once the command has succeeded"""
+        if depth_bin is not None and depth is None:
+            raise PolypolishError(ERR_QUIT, "depth_bin= needs depth=<path>: it chooses the form of the depth track")
+        if depth_bgzf and depth is None:
+            raise PolypolishError(ERR_QUIT, "depth_bgzf=True needs depth=<path>: it compresses the depth track")
+        if depth is None:
+            yield lambda: None
+            return
+        w = 0 if depth_bin is None else depth_bin
+        if isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not 0 <= int(w) <= 1 << 24:
+            raise PolypolishError(ERR_QUIT, f"depth_bin: {w!r} is not an integer in 0..16777216")
+        self.set_depth(True, int(w), depth_bgzf)
+
+        def deliver():
+            data = self.depth()
+            try:
+                with open(depth, "wb") as f:
+                    f.write(data)
+            except OSError:
+                raise PolypolishError(ERR_QUIT, f'unable to write the depth track to "{os.fspath(depth)}"') from None
+        try:
+            yield deliver
+        finally:
+            self.set_depth(False)
+
     @contextlib.contextmanager
     def _writing_bam(self, out_bam):
         """out_bam=True switches pp_ctx_set_out_bam on for one command and off again behind it"""
@@ -2204,7 +2322,8 @@ class Context:
 
     def polish_files(self, assembly, sams, fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5,
                      careful=False, debug=None, quiet=True, regroup=False, text_chain=False, wrap=None, bgzf=False, out=None,
-                     index=False, vcf=None, vcf_bgzf=False, bed=None, bed_bgzf=False, bed_status=None, soft_mask=False):
+                     index=False, vcf=None, vcf_bgzf=False, bed=None, bed_bgzf=False, bed_status=None, soft_mask=False,
+                     depth=None, depth_bin=None, depth_bgzf=False):
         """polish::polish (pp_polish_files): the FASTA bytes.  wrap / bgzf / out / index (not in the reference): the FASTA at a line
         width (0: one line per contig) and bgzipped, made on the device (pp_fasta_text, pp_bgzf_deflate); also written to `out`,
         with out.fai (and out.gzi) for index.  `sams` are SAM text files, or all of them BAM files (BGZF or
@@ -2214,17 +2333,21 @@ class Context:
         the path `vcf` as VCF 4.2 made on the device (pp_polish_vcf), bgzipped with vcf_bgzf.  bed / bed_bgzf / bed_status / soft_mask
         (not in the reference): the runs of undecided positions written to the path `bed` as BED made on the device (pp_polish_bed),
         bgzipped with bed_bgzf; soft_mask: their bases in lower case in the FASTA (pp_polish_masked); bed_status: the statuses both
-        select (bed_status_mask; default the four undecided ones)."""
+        select (bed_status_mask; default the four undecided ones).  depth / depth_bin / depth_bgzf (not in the reference): the read
+        depth written to the path `depth` as bedGraph made on the device (pp_polish_depth) -- runs of equal depth, or with depth_bin=N
+        the mean of bins of N positions --, bgzipped with depth_bgzf."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         arr = (C.c_char_p * max(len(sams), 1))(*[str(s).encode() for s in sams])
         res = Bytes()
         with self._regrouping(regroup), self._chaining_text(text_chain), self._making_vcf(vcf, vcf_bgzf) as deliver_vcf, \
-                self._making_bed(bed, bed_bgzf, bed_status, soft_mask) as deliver_bed, self._fasta_form(wrap, bgzf, out, index) as deliver:
+                self._making_bed(bed, bed_bgzf, bed_status, soft_mask) as deliver_bed, \
+                self._making_depth(depth, depth_bin, depth_bgzf) as deliver_depth, self._fasta_form(wrap, bgzf, out, index) as deliver:
             self._chk(lib().pp_polish_files(self._h, str(assembly).encode(), arr, len(sams), C.byref(opt), C.byref(res)))
             data = _take_bytes(res)
             deliver_vcf()
             deliver_bed()
+            deliver_depth()
             deliver(data)
         return data
 
@@ -2232,26 +2355,28 @@ class Context:
                             fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5, careful=False,
                             debug=None, quiet=True, regroup=False, out_bam=False, out_sam=False, text_chain=False, wrap=None,
                             bgzf=False, out=None, index=False, sort_out=False, out_bai=False, vcf=None, vcf_bgzf=False, bed=None,
-                            bed_bgzf=False, bed_status=None, soft_mask=False):
+                            bed_bgzf=False, bed_status=None, soft_mask=False, depth=None, depth_bin=None, depth_bgzf=False):
         """filter + polish in one process (pp_filter_polish_files): returns (FASTA bytes, filter report).  wrap / bgzf / out / index:
         as polish_files.  Two BAM inputs are decoded
         once for both halves; out1 / out2 are then BAM files as well.  regroup: for this call, as set_regroup (the polish half).
         out_bam: for this call, as set_out_bam (SAM text inputs, out1 / out2 as compressed BAM).  out_sam: for this call, as
         set_out_sam (BAM inputs, out1 / out2 as SAM text).  text_chain: for this call, as set_text_chain.  sort_out / out_bai: for
         this call, as set_sort_out (BAM outputs in coordinate order, out1.bai / out2.bai next to them).  vcf / vcf_bgzf, bed /
-        bed_bgzf / bed_status / soft_mask: as polish_files."""
+        bed_bgzf / bed_status / soft_mask, depth / depth_bin / depth_bgzf: as polish_files."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         rep, res = FilterReport(), Bytes()
         enc = lambda x: str(x).encode() if x is not None else None
         with self._regrouping(regroup), self._writing_bam(out_bam), self._writing_sam(out_sam), self._chaining_text(text_chain), \
                 self._sorting_out(sort_out, out_bai), self._making_vcf(vcf, vcf_bgzf) as deliver_vcf, \
-                self._making_bed(bed, bed_bgzf, bed_status, soft_mask) as deliver_bed, self._fasta_form(wrap, bgzf, out, index) as deliver:
+                self._making_bed(bed, bed_bgzf, bed_status, soft_mask) as deliver_bed, \
+                self._making_depth(depth, depth_bin, depth_bgzf) as deliver_depth, self._fasta_form(wrap, bgzf, out, index) as deliver:
             self._chk(lib().pp_filter_polish_files(self._h, enc(assembly), enc(in1), enc(in2), enc(out1), enc(out2),
                                                    orientation.encode(), low, high, C.byref(opt), C.byref(rep), C.byref(res)))
             data = _take_bytes(res)
             deliver_vcf()
             deliver_bed()
+            deliver_depth()
             deliver(data)
         return data, _report_dict(rep)
 
@@ -2283,15 +2408,16 @@ def _ctx():
 
 def polish(assembly, sam, debug=None, fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5,
            careful=False, regroup=False, text_chain=False, wrap=None, bgzf=False, out=None, index=False, bed=None, bed_bgzf=False,
-           bed_status=None, soft_mask=False) -> bytes:
+           bed_status=None, soft_mask=False, depth=None, depth_bin=None, depth_bgzf=False) -> bytes:
     """polish::polish (src/polish.rs:26-38): returns the FASTA bytes the reference prints to stdout.  regroup: coordinate-sorted
     BAM files (every read's records are brought together in front of the gate: the command's --regroup).  text_chain: SAM text,
     plain or bgzipped, through the record chain as well (the command's --text_chain; regroup then takes text too).  wrap / bgzf / out /
     index: the commands' --wrap, --out_bgzf, --out and --index; bed / bed_bgzf / bed_status / soft_mask: --bed, --bed_bgzf, --bed_status
-    and --soft_mask (Context.polish_files)."""
+    and --soft_mask; depth / depth_bin / depth_bgzf: --depth, --depth_bin and --depth_bgzf (Context.polish_files)."""
     return _ctx().polish_files(assembly, list(sam), fraction_invalid, fraction_valid, max_errors, min_depth, careful,
                                debug, regroup=regroup, text_chain=text_chain, wrap=wrap, bgzf=bgzf, out=out, index=index, bed=bed,
-                               bed_bgzf=bed_bgzf, bed_status=bed_status, soft_mask=soft_mask)
+                               bed_bgzf=bed_bgzf, bed_status=bed_status, soft_mask=soft_mask, depth=depth, depth_bin=depth_bin,
+                               depth_bgzf=depth_bgzf)
 
 
 def filter(in1, in2, out1, out2, orientation="auto", low=0.1, high=99.9):  # noqa: A001 (reference name)

@@ -234,6 +234,13 @@ SIGNATURES = {
     "pp_masked_bytes": (None, [_vp, _pvp, _pu64]),
     "pp_masked_kernel_ms": (_i, [_vp, _pf32]),
     "pp_masked_free": (None, [_vp]),
+    "pp_depth_bedgraph": (_i, [_vp, _vp, _i, _u32, _vp, _vp, _u32, _pvp, _pu64]),
+    "pp_polish_depth": (_i, [_vp, _vp, _u32, _pvp]),
+    "pp_depth_out_bytes": (None, [_vp, _pvp, _pu64, _pu64]),
+    "pp_depth_out_summary": (None, [_vp, _pu64, _pu64, _pu64]),
+    "pp_depth_out_write": (_i, [_vp, _str]),
+    "pp_depth_out_kernel_ms": (_i, [_vp, _pf32]),
+    "pp_depth_out_free": (None, [_vp]),
     "pp_ctx_set_profiling": (_i, [_vp, _i]),
     "pp_polish_kernel_times": (_i, [_vp, _P(KernelTimes)]),
     "pp_polish_took_direct_path": (_i, [_vp]),
@@ -309,6 +316,8 @@ SIGNATURES = {
     "pp_ctx_set_bed": (_i, [_vp, _i, _u32, _i]),
     "pp_ctx_bed": (_i, [_vp, _P(Bytes)]),
     "pp_ctx_set_soft_mask": (_i, [_vp, _u32]),
+    "pp_ctx_set_depth": (_i, [_vp, _i, _u32, _i]),
+    "pp_ctx_depth": (_i, [_vp, _P(Bytes)]),
     "pp_polish_files": (_i, [_vp, _str, _P(_str), _i, _P(PolishOptions), _P(Bytes)]),
     "pp_polish_files_multi": (_i, [_pvp, _i, _str, _P(_str), _i, _P(PolishOptions), _P(Bytes)]),
     "pp_dev_ingest_create": (_i, [_vp, _vp, _u32, _i, _pvp]),
@@ -345,6 +354,8 @@ HOOKS = {
     "pp_vcf_geometry_": (None, [_pu32] * 4),
     "pp_bed_out_stage_ms_": (_i, [_vp, _pf32]),     # float[3]
     "pp_bed_geometry_": (None, [_pu32] * 4),
+    "pp_depth_out_stage_ms_": (_i, [_vp, _pf32]),   # float[4]
+    "pp_depth_geometry_": (None, [_pu32] * 4),
     "pp_ctx_fasta_form_": (_i, [_vp, _P(C.c_int64), _P(_i)]),
     "pp_ctx_set_fasta_out_name_": (_i, [_vp, _str]),
     "pp_bam_out_stage_ms_": (_i, [_vp, _pf32]),     # float[3]

@@ -69,6 +69,9 @@ static const char *HELP_POLISH =
     "      --soft_mask                            Write the bases of undecided positions in lower case (one GPU; not in the reference)\n"
     "      --bed_status <LIST>                    The statuses --bed and --soft_mask select: a comma-separated list of kept, changed,\n"
     "                                             low_depth, none, multiple, too_close [default: low_depth,none,multiple,too_close]\n"
+    "      --depth <PATH>                         Write the read depth to PATH as bedGraph, made on the device (one GPU; not in the reference)\n"
+    "      --depth_bin <N>                        With --depth: the mean depth of bins of N positions; 0: runs of equal depth [default: 0] (not in the reference)\n"
+    "      --depth_bgzf                           With --depth: compress the bedGraph into BGZF blocks on the device (not in the reference)\n"
     "  -h, --help                                 Print help\n  -V, --version                              Print version\n";
 
 static const char *HELP_FUSED =
@@ -92,7 +95,10 @@ static const char *HELP_FUSED =
     "--bed_bgzf: with --bed, compress the BED into BGZF blocks on the device (not in the reference).\n"
     "--soft_mask: write the bases of undecided positions in lower case (not in the reference).\n"
     "--bed_status <LIST>: the statuses --bed and --soft_mask select, a comma-separated list of kept, changed, low_depth, none,\n"
-    "multiple, too_close; default low_depth,none,multiple,too_close (not in the reference).\n";
+    "multiple, too_close; default low_depth,none,multiple,too_close (not in the reference).\n"
+    "--depth <PATH>: write the read depth to PATH as bedGraph, made on the device (not in the reference).\n"
+    "--depth_bin <N>: with --depth, the mean depth of bins of N positions; 0, the default: runs of equal depth (not in the reference).\n"
+    "--depth_bgzf: with --depth, compress the bedGraph into BGZF blocks on the device (not in the reference).\n";
 
 static int usage_error(const char *msg) {
     fprintf(stderr, "error: %s\n\nFor more information, try '--help'.\n", msg);
@@ -258,6 +264,24 @@ static void set_bed_form(pp_ctx *ctx, const BedForm &B) {
     pp_ctx_set_bed(ctx, B.path != nullptr, B.mask, B.bgzf);
     pp_ctx_set_soft_mask(ctx, B.soft_mask ? B.mask : 0u);
 }
+// --depth, --depth_bin, --depth_bgzf: three options from k0 on.  false with the usage error in err
+struct DepthForm {
+    const char *path = nullptr;
+    bool bgzf = false;
+    uint32_t bin = 0;
+};
+static bool take_depth_form(const Parsed &P, const std::vector<OptSpec> &specs, size_t k0, DepthForm &D, std::string &err) {
+    D.path = P.value[k0];
+    D.bgzf = P.value[k0 + 2] != nullptr;
+    if (P.value[k0 + 1] && !D.path) { err = "--depth_bin needs --depth <PATH>: it chooses the form of the depth track"; return false; }
+    if (D.bgzf && !D.path) { err = "--depth_bgzf needs --depth <PATH>: it compresses the depth track"; return false; }
+    if (!take_u32(P, specs, k0 + 1, D.bin, err)) return false;
+    if (D.bin > (1u << 24)) {
+        err = std::string("invalid value '") + P.value[k0 + 1] + "' for '" + opt_display(specs[k0 + 1]) + "': " + P.value[k0 + 1] + " is not in 0..=16777216";
+        return false;
+    }
+    return true;
+}
 static bool write_file(const std::string &path, const uint8_t *data, uint64_t len) {
     FILE *f = fopen(path.c_str(), "wb");
     if (!f) return false;
@@ -306,6 +330,17 @@ static int deliver_bed(pp_ctx *ctx, const char *path) {
     if (ok) return 0;
     remove(path);
     fprintf(stderr, "\nError: unable to write the BED to \"%s\"\n", path);
+    return 1;
+}
+// ... and the depth track (--depth; pp_ctx_depth), behind the BED
+static int deliver_depth(pp_ctx *ctx, const char *path) {
+    if (!path) return 0;
+    pp_bytes track{nullptr, 0};
+    const bool ok = pp_ctx_depth(ctx, &track) == PP_OK && write_file(path, track.data, track.len);
+    pp_bytes_free(&track);
+    if (ok) return 0;
+    remove(path);
+    fprintf(stderr, "\nError: unable to write the depth track to \"%s\"\n", path);
     return 1;
 }
 // the form on a context: --index alone still needs the text's table, so it takes the device link at width 0
@@ -399,7 +434,10 @@ int main(int argc, char **argv) {
                                             {"--bed", 0, true, "<PATH>"},
                                             {"--bed_bgzf", 0, false, ""},
                                             {"--soft_mask", 0, false, ""},
-                                            {"--bed_status", 0, true, "<LIST>"}};
+                                            {"--bed_status", 0, true, "<LIST>"},
+                                            {"--depth", 0, true, "<PATH>"},
+                                            {"--depth_bin", 0, true, "<N>"},
+                                            {"--depth_bgzf", 0, false, ""}};
         FastaForm form;
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help) { fputs(HELP_POLISH, stdout); return 0; }
@@ -420,6 +458,8 @@ int main(int argc, char **argv) {
         if (vcf_bgzf && !vcf) return refuse_vcf_bgzf_without_vcf();
         BedForm bed;
         if (!take_bed_form(P, 14, bed, perr)) return usage_error(perr.c_str());
+        DepthForm depth;
+        if (!take_depth_form(P, specs, 18, depth, perr)) return usage_error(perr.c_str());
         if (form.index && !form.out) return refuse_index_without_out();
         const char *assembly = P.positional.empty() ? nullptr : P.positional[0];
         std::vector<const char *> sams(P.positional.begin() + (P.positional.empty() ? 0 : 1), P.positional.end());
@@ -438,6 +478,10 @@ int main(int argc, char **argv) {
         }
         if (several && bed.any()) {
             fprintf(stderr, "\nError: %s runs on one GPU: polish without PP_GPUS / PP_SHARE_GPU, or without %s\n", bed.path ? "--bed" : "--soft_mask", bed.path ? "--bed" : "--soft_mask");
+            return 1;
+        }
+        if (several && depth.path) {
+            fprintf(stderr, "\nError: --depth runs on one GPU: polish without PP_GPUS / PP_SHARE_GPU, or without --depth\n");
             return 1;
         }
         for (size_t i = 0; several && i < sams.size(); i++) {
@@ -460,6 +504,7 @@ int main(int argc, char **argv) {
             set_fasta_form(cs[0], form);
             pp_ctx_set_vcf(cs[0], vcf != nullptr, vcf_bgzf);  // (several contexts: the driver refuses it by name)
             set_bed_form(cs[0], bed);
+            pp_ctx_set_depth(cs[0], depth.path != nullptr, depth.bin, depth.bgzf);
             pp_bytes fasta{nullptr, 0};
             int rc = pp_polish_files_multi(cs.data(), (int)cs.size(), assembly, sams.data(), (int)sams.size(), &opt, &fasta);
             for (size_t d = 0; d < devs.size(); d++)
@@ -469,7 +514,7 @@ int main(int argc, char **argv) {
                 for (pp_ctx *c : cs) pp_ctx_destroy(c);
                 return rc == PP_ERR_PANIC ? 101 : 1;
             }
-            if (deliver_vcf(cs[0], vcf) || deliver_bed(cs[0], bed.path) || deliver_fasta(cs[0], form, fasta)) return 1;
+            if (deliver_vcf(cs[0], vcf) || deliver_bed(cs[0], bed.path) || deliver_depth(cs[0], depth.path) || deliver_fasta(cs[0], form, fasta)) return 1;
             return finish(0);
         }
         // the device initialises on a helper thread while the host loads and parses the inputs
@@ -481,6 +526,7 @@ int main(int argc, char **argv) {
         set_fasta_form(ctx, form);
         pp_ctx_set_vcf(ctx, vcf != nullptr, vcf_bgzf);
         set_bed_form(ctx, bed);
+        pp_ctx_set_depth(ctx, depth.path != nullptr, depth.bin, depth.bgzf);
         pp_bytes fasta{nullptr, 0};
         rc = pp_polish_files(ctx, assembly, sams.data(), (int)sams.size(), &opt, &fasta);
         if (pp_ctx_wait(ctx) != PP_OK) return no_device(device);
@@ -489,7 +535,7 @@ int main(int argc, char **argv) {
             pp_ctx_destroy(ctx);
             return rc == PP_ERR_PANIC ? 101 : 1;
         }
-        if (deliver_vcf(ctx, vcf) || deliver_bed(ctx, bed.path) || deliver_fasta(ctx, form, fasta)) return 1;
+        if (deliver_vcf(ctx, vcf) || deliver_bed(ctx, bed.path) || deliver_depth(ctx, depth.path) || deliver_fasta(ctx, form, fasta)) return 1;
         return finish(0);
     }
 
@@ -522,7 +568,10 @@ int main(int argc, char **argv) {
                                             {"--bed", 0, true, "<PATH>"},
                                             {"--bed_bgzf", 0, false, ""},
                                             {"--soft_mask", 0, false, ""},
-                                            {"--bed_status", 0, true, "<LIST>"}};
+                                            {"--bed_status", 0, true, "<LIST>"},
+                                            {"--depth", 0, true, "<PATH>"},
+                                            {"--depth_bin", 0, true, "<N>"},
+                                            {"--depth_bgzf", 0, false, ""}};
         FastaForm form;
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help || P.version) { fputs(HELP_FUSED, stdout); return 0; }
@@ -549,9 +598,10 @@ int main(int argc, char **argv) {
         const bool vcf_bgzf = P.value[24] != nullptr;
         if (vcf_bgzf && !vcf) return refuse_vcf_bgzf_without_vcf();
         BedForm bed;
+        DepthForm depth;
         {
             std::string berr;
-            if (!take_bed_form(P, 25, bed, berr)) return usage_error(berr.c_str());
+            if (!take_bed_form(P, 25, bed, berr) || !take_depth_form(P, specs, 29, depth, berr)) return usage_error(berr.c_str());
         }
         pp_ctx *ctx = nullptr;
         int rc = pp_ctx_create_async(device, &ctx);
@@ -564,6 +614,7 @@ int main(int argc, char **argv) {
         set_fasta_form(ctx, form);
         pp_ctx_set_vcf(ctx, vcf != nullptr, vcf_bgzf);
         set_bed_form(ctx, bed);
+        pp_ctx_set_depth(ctx, depth.path != nullptr, depth.bin, depth.bgzf);
         pp_bytes fasta{nullptr, 0};
         rc = pp_filter_polish_files(ctx, assembly, in1, in2, out1, out2, orientation, low, high, &opt, nullptr, &fasta);
         if (pp_ctx_wait(ctx) != PP_OK) return no_device(device);
@@ -572,7 +623,7 @@ int main(int argc, char **argv) {
             pp_ctx_destroy(ctx);
             return rc == PP_ERR_PANIC ? 101 : 1;
         }
-        if (deliver_vcf(ctx, vcf) || deliver_bed(ctx, bed.path) || deliver_fasta(ctx, form, fasta)) return 1;
+        if (deliver_vcf(ctx, vcf) || deliver_bed(ctx, bed.path) || deliver_depth(ctx, depth.path) || deliver_fasta(ctx, form, fasta)) return 1;
         return finish(0);
     }
 

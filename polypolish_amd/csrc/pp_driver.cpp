@@ -285,7 +285,7 @@ static int create_debug_file(PolishJob &J) {
         fputs("name\tpos\tbase\tdepth\tinvalid\tvalid\tpileup\tstatus\tnew_base\n", J.dbg);
     }
     J.debug_set = true;
-    for (int d = 0; d < J.n_ctx; d++) pp_polish_set_debug(J.ctxs[d], J.dbg || J.wants_status() ? 1 : 0);  // (--bed, --soft_mask: the records without a file)
+    for (int d = 0; d < J.n_ctx; d++) pp_polish_set_debug(J.ctxs[d], J.dbg || J.wants_status() ? 1 : 0);  // (--bed, --soft_mask, --depth: the records without a file)
     return PP_OK;
 }
 // ... and closed once the contexts have written their lines; they keep no per-position records from here on
@@ -331,6 +331,30 @@ static int make_bed(PolishJob &J) {
     return rc;
 }
 
+// The depth track of pp_ctx_set_depth, as make_bed: pp_polish_depth on the finished job, pp_bgzf_deflate on the device text with bgzf, one
+// copy off the device into the job (J.depth_file).  Nothing is logged.
+static int make_depth(PolishJob &J) {
+    pp_ctx *const ctx = J.ctx;
+    pp_depth_out *text = nullptr;
+    pp_bgzf_out *z = nullptr;
+    const uint8_t *dev = nullptr;
+    uint64_t n = 0;
+    int rc = pp_polish_depth(ctx, J.names.data(), J.depth_bin, &text);
+    if (rc == PP_OK) pp_depth_out_bytes(text, &dev, &n, nullptr);
+    if (rc == PP_OK && J.depth_bgzf) {
+        rc = pp_bgzf_deflate(ctx, dev, n, PP_MEM_DEVICE, &z);
+        if (rc == PP_OK) pp_bgzf_out_bytes(z, &dev, &n);
+    }
+    if (rc == PP_OK) {  // (handed to the context once the whole run has succeeded: polish_once)
+        J.depth_file.resize((size_t)n);
+        if (n) rc = pp_ctx_download(ctx, J.depth_file.data(), dev, n);
+    }
+    pp_bgzf_out_free(z);
+    pp_depth_out_free(text);
+    J.lap(J.depth_bgzf ? "depth track made and compressed on the device" : "depth track made on the device");
+    return rc;
+}
+
 static int polish_on_one_context(PolishJob &J) {
     pp_ctx *const ctx = J.ctx;
     int rc = hand_over_batches(J);
@@ -343,6 +367,7 @@ static int polish_on_one_context(PolishJob &J) {
     }
     // (the BED and the masked bytes read the job's status: made before the records are closed)
     if (rc == PP_OK && J.bed_on) rc = make_bed(J);
+    if (rc == PP_OK && J.depth_on) rc = make_depth(J);
     if (rc == PP_OK && J.soft_mask) {
         rc = pp_polish_masked(ctx, J.soft_mask, &J.masked);
         J.lap("polished bytes soft-masked on the device");
@@ -511,6 +536,10 @@ static int polish_once(PolishJob &J, pp_bytes *fasta) {
         return set_err(J.ctx, PP_ERR_QUIT, "--bed runs on one GPU: polish without PP_GPUS / several contexts, or without --bed");
     if (J.soft_mask && J.n_ctx > 1)
         return set_err(J.ctx, PP_ERR_QUIT, "--soft_mask runs on one GPU: polish without PP_GPUS / several contexts, or without --soft_mask");
+    J.depth_on = pp_ctx_depth_form_(J.ctx, &J.depth_bin, &J.depth_bgzf) != 0;
+    pp_ctx_keep_depth_(J.ctx, nullptr, 0);  // (the file of the run before)
+    if (J.depth_on && J.n_ctx > 1)  // (the depth plane of a rank is its share's: pp_polish_depth)
+        return set_err(J.ctx, PP_ERR_QUIT, "--depth runs on one GPU: polish without PP_GPUS / several contexts, or without --depth");
     if (int rc = check_options_and_inputs(J)) return rc;
     log_banner(J);
     J.lap("driver entered");
@@ -530,6 +559,10 @@ static int polish_once(PolishJob &J, pp_bytes *fasta) {
     if (J.bed_on) {  // (a run that fails leaves no file: pp_ctx_bed)
         J.bed_file.push_back(0);
         pp_ctx_keep_bed_(J.ctx, J.bed_file.data(), J.bed_file.size() - 1);
+    }
+    if (J.depth_on) {  // (as the BED: pp_ctx_depth)
+        J.depth_file.push_back(0);
+        pp_ctx_keep_depth_(J.ctx, J.depth_file.data(), J.depth_file.size() - 1);
     }
     log_finished(J);
     J.release();

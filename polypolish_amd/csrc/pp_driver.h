@@ -160,7 +160,12 @@ struct PolishJob {
     int bed_bgzf = 0;
     pp_masked *masked = nullptr;
     std::vector<uint8_t> bed_file;  // the BED of this run (make_bed), the context's once the run has succeeded
-    bool wants_status() const { return bed_on || soft_mask != 0; }
+    // pp_ctx_set_depth (one context): the job keeps its per-position depth; the track is made next to the BED (make_depth)
+    bool depth_on = false;
+    uint32_t depth_bin = 0;
+    int depth_bgzf = 0;
+    std::vector<uint8_t> depth_file;  // the depth track of this run, the context's once the run has succeeded
+    bool wants_status() const { return bed_on || soft_mask != 0 || depth_on; }
     std::vector<uint8_t> polished = std::vector<uint8_t>(1);
     std::vector<uint64_t> out_off;
     std::vector<pp_contig_stats> stats;

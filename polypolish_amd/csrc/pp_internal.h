@@ -302,6 +302,11 @@ struct pp_ctx {
     bool bed_on = false, bed_bgzf = false, bed_made = false;
     uint32_t bed_mask = 0, soft_mask = 0;  // soft_mask 0: off
     std::string bed_bytes;
+    // pp_ctx_set_depth: the file drivers keep the job's per-position depth and run pp_polish_depth behind their polish (depth_bytes: the
+    // file of the last such run that succeeded, pp_ctx_depth)
+    bool depth_on = false, depth_bgzf = false, depth_made = false;
+    uint32_t depth_bin = 0;
+    std::string depth_bytes;
     std::string fasta_out_name;         // pp_ctx_set_fasta_out_name_: where the caller will write the FASTA (the log's last section names it)
     pp::DevBuf f_thr;  // pp_filter_thresholds: orientation counts | the selection's state | its two histograms (THR_WORDS u32)
     pp_filter_input fdev{};

@@ -1,13 +1,14 @@
 // pp_polish_text.hip -- the post-passes that make text from a finished polish job, each on the device: the --debug TSV
 // (pp_polish_debug_tsv, pp_k_debug.h), the edits as VCF (pp_polish_vcf, pp_k_vcf.h, pp_vcf_host.h), the undecided regions as BED and
-// the soft-masked polished bytes (pp_status_bed, pp_polish_bed, pp_polish_masked, pp_k_bed.h, pp_bed_host.h), and what the file
-// drivers keep of them on the context.  Nothing here runs unless a caller asks for it: the polish pipeline (pp_kernels.hip) is
+// the soft-masked polished bytes (pp_status_bed, pp_polish_bed, pp_polish_masked, pp_k_bed.h, pp_bed_host.h), the read depth as bedGraph
+// (pp_depth_bedgraph, pp_polish_depth, pp_k_depth.h, pp_depth_host.h), and what the file drivers keep of them on the context.  Nothing here runs unless a caller asks for it: the polish pipeline (pp_kernels.hip) is
 // untouched, and this unit reads of it only what a finished job leaves in the context (pp_internal.h).  The call's scratch, the
 // result objects' device memory and the stage times are pp_dev.h's (CallScratch, DevOwner, StageTimer, StageMs), the single-workgroup
 // scan of the workgroups' sums its k_colscan<1>.
 #include "pp_dev.h"
 #include "pp_vcf_host.h"
 #include "pp_bed_host.h"
+#include "pp_depth_host.h"
 
 #include <cstring>
 
@@ -15,6 +16,7 @@
 #include "pp_k_debug.h"
 #include "pp_k_vcf.h"
 #include "pp_k_bed.h"
+#include "pp_k_depth.h"
 
 using namespace pp;
 
@@ -573,4 +575,205 @@ extern "C" void pp_ctx_keep_bed_(pp_ctx *ctx, const uint8_t *data, uint64_t n) {
     ctx->bed_made = data != nullptr;
     ctx->bed_bytes.assign(data ? (const char *)data : "", data ? (size_t)n : 0);
     if (!data) ctx->bed_bytes.shrink_to_fit();
+}
+
+// ---- read depth: the per-position depth as bedGraph text, runs or bins (pp_k_depth.h, pp_depth_host.h) ----------------------------
+struct pp_depth_out : DevOwner {
+    using DevOwner::DevOwner;
+    u8 *text = nullptr;  // DEVICE, n_text bytes (allocated up to a multiple of 16)
+    uint64_t n_text = 0, n_records = 0;
+    uint64_t zero_positions = 0, max_tenths = 0, sum_tenths = 0;
+    StageMs<4> t;  // values | records | lengths | text
+};
+
+extern "C" void pp_depth_out_free(pp_depth_out *o) { delete o; }
+extern "C" void pp_depth_out_bytes(const pp_depth_out *o, const uint8_t **dev, uint64_t *n_bytes, uint64_t *n_records) {
+    if (dev) *dev = o ? o->text : nullptr;
+    if (n_bytes) *n_bytes = o ? o->n_text : 0;
+    if (n_records) *n_records = o ? o->n_records : 0;
+}
+extern "C" void pp_depth_out_summary(const pp_depth_out *o, uint64_t *zero_positions, uint64_t *max_tenths, uint64_t *sum_tenths) {
+    if (zero_positions) *zero_positions = o ? o->zero_positions : 0;
+    if (max_tenths) *max_tenths = o ? o->max_tenths : 0;
+    if (sum_tenths) *sum_tenths = o ? o->sum_tenths : 0;
+}
+extern "C" int pp_depth_out_write(const pp_depth_out *o, const char *path) {
+    if (!o || !o->ctx) return PP_ERR_ARG;
+    if (!path) return o->ctx->fail(PP_ERR_ARG, "pp_depth_out_write: null argument");
+    return write_device_file(o->ctx, "pp_depth_out_write", o->text, o->n_text, path);
+}
+extern "C" int pp_depth_out_kernel_ms(const pp_depth_out *o, float *ms) {
+    return o ? o->t.total(o->ctx, "pp_depth_out_kernel_ms", "when the text was made", ms) : PP_ERR_ARG;
+}
+// (internal hooks, not part of the header) the time by stage: values | records | lengths | text (tools/depth_timing.py); the geometry:
+// positions per thread and per workgroup of the position passes, text bytes per store and per workgroup (the tests)
+extern "C" int pp_depth_out_stage_ms_(const pp_depth_out *o, float *ms4) { return o ? o->t.stages(ms4) : PP_ERR_ARG; }
+extern "C" void pp_depth_geometry_(uint32_t *pos_per_thread, uint32_t *pos_per_workgroup, uint32_t *bytes_per_store, uint32_t *bytes_per_workgroup) {
+    if (pos_per_thread) *pos_per_thread = DEP_PPT;
+    if (pos_per_workgroup) *pos_per_workgroup = DEP_TILE;
+    if (bytes_per_store) *bytes_per_store = DEP_LANE;
+    if (bytes_per_workgroup) *bytes_per_workgroup = DEP_TEXT_WG;
+}
+
+// the passes over d_depth (DEVICE, plan.names.G doubles, aligned to 8 bytes); the arguments have been judged (pp_depth_host::plan)
+static int depth_on_device(pp_ctx *ctx, const char *who, const double *d_depth, uint32_t nc, const uint64_t *contig_off, const pp_depth_host::Plan &plan,
+                           uint32_t bin, pp_depth_out **out, uint64_t *bad_pos) {
+    hipStream_t st = ctx->stream;
+    const uint64_t G = plan.names.G;
+    std::unique_ptr<pp_depth_out> P(new pp_depth_out(ctx));
+    CallScratch T;
+    StageTimer timer(ctx, ctx->profiling != 0);
+    int rc;
+    char msg[256] = "";
+    if ((rc = timer.begin(0))) return rc;
+    if (G) {
+        const uint64_t nb = (G + DEP_TILE - 1) / DEP_TILE;  // (below 2^21: G is below 2^32)
+        uint64_t n_rec = bin ? plan.bin_base[nc] : 0, n_text = 0;
+        u64 *d_coff = nullptr, *d_bcnt = nullptr, *d_roff = nullptr, *d_word = nullptr, *d_binbase = nullptr, *d_bins = nullptr;
+        if ((rc = T.alloc(ctx, d_coff, (size_t)nc + 1)) || (rc = T.alloc(ctx, d_word, 4))) return rc;
+        uint64_t word[4] = {~0ull, 0, 0, 0};  // the first bad position | zero positions | the largest tenths | their sum
+        PP_HIPCHK(ctx, hipMemcpyAsync(d_coff, contig_off, ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, st));
+        PP_HIPCHK(ctx, hipMemcpyAsync(d_word, word, sizeof word, hipMemcpyHostToDevice, st));
+        DepJob J;
+        J.depth = d_depth; J.contig_off = d_coff; J.bin_base = nullptr; J.nc = nc; J.bin = bin; J.G = G;
+        if (bin) {
+            if ((rc = T.alloc(ctx, d_binbase, (size_t)nc + 1)) || (rc = T.alloc(ctx, d_bins, n_rec))) return rc;
+            PP_HIPCHK(ctx, hipMemcpyAsync(d_binbase, plan.bin_base.data(), ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, st));
+            PP_HIPCHK(ctx, hipMemsetAsync(d_bins, 0, n_rec * 8, st));
+            J.bin_base = d_binbase;
+            hipLaunchKernelGGL(k_dep_values<true>, dim3((unsigned)nb), dim3(DEP_THREADS), 0, st, J, (u64 *)nullptr, d_bins, d_word);
+            PP_HIPCHK(ctx, hipGetLastError());
+        } else {
+            if ((rc = T.alloc(ctx, d_bcnt, nb)) || (rc = T.alloc(ctx, d_roff, nb + 1))) return rc;
+            hipLaunchKernelGGL(k_dep_values<false>, dim3((unsigned)nb), dim3(DEP_THREADS), 0, st, J, d_bcnt, (u64 *)nullptr, d_word);
+            hipLaunchKernelGGL(k_colscan<1>, dim3(1), dim3(1024), 0, st, (const u64 *)d_bcnt, (u64)nb, d_roff);
+            PP_HIPCHK(ctx, hipGetLastError());
+            PP_HIPCHK(ctx, hipMemcpyAsync(&n_rec, d_roff + nb, 8, hipMemcpyDeviceToHost, st));
+        }
+        PP_HIPCHK(ctx, hipMemcpyAsync(word, d_word, sizeof word, hipMemcpyDeviceToHost, st));
+        if ((rc = next_stage(timer, 1))) return rc;
+        PP_HIPCHK(ctx, hipStreamSynchronize(st));
+        if (word[0] != ~0ull) {
+            if (bad_pos) *bad_pos = word[0];
+            return ctx->fail(PP_ERR_ARG, "%s: a depth that is negative, not a number or 2^32 and more at position %llu", who, (unsigned long long)word[0]);
+        }
+        P->zero_positions = word[1];
+        P->max_tenths = word[2];
+        P->sum_tenths = word[3];
+        // (G > 0: there is a record)
+        const uint64_t nbr = (n_rec + DEP_THREADS - 1) / DEP_THREADS;
+        const uint32_t frac = bin ? 2u : 1u;
+        DepRec *d_rec = nullptr;
+        u64 *d_rec_at = nullptr, *d_rsum = nullptr, *d_rsoff = nullptr, *d_noff = nullptr;
+        u8 *d_names = nullptr;
+        if ((rc = T.alloc(ctx, d_rec, n_rec)) || (rc = T.alloc(ctx, d_rec_at, n_rec + 1)) || (rc = T.alloc(ctx, d_rsum, nbr)) ||
+            (rc = T.alloc(ctx, d_rsoff, nbr + 1)) || (rc = T.alloc(ctx, d_noff, (size_t)nc + 1)) || (rc = T.alloc(ctx, d_names, plan.names.names.size())))
+            return rc;
+        PP_HIPCHK(ctx, hipMemcpyAsync(d_noff, plan.names.name_off.data(), ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, st));
+        if (!plan.names.names.empty()) PP_HIPCHK(ctx, hipMemcpyAsync(d_names, plan.names.names.data(), plan.names.names.size(), hipMemcpyHostToDevice, st));
+        if (bin) {
+            hipLaunchKernelGGL(k_dep_binrecs, dim3((unsigned)nbr), dim3(DEP_THREADS), 0, st, J, (const u64 *)d_bins, (u64)n_rec, d_rec);
+        } else {
+            PP_HIPCHK(ctx, hipMemsetAsync(d_rec, 0, n_rec * sizeof(DepRec), st));
+            hipLaunchKernelGGL(k_dep_recs, dim3((unsigned)nb), dim3(DEP_THREADS), 0, st, J, (const u64 *)d_roff, (u64)n_rec, d_rec);
+        }
+        PP_HIPCHK(ctx, hipGetLastError());
+        if ((rc = next_stage(timer, 2))) return rc;
+        hipLaunchKernelGGL(k_dep_reclen, dim3((unsigned)nbr), dim3(DEP_THREADS), 0, st, (const DepRec *)d_rec, (u64)n_rec, (const u64 *)d_coff, nc,
+                           (const u64 *)d_noff, frac, d_rec_at, d_rsum);
+        hipLaunchKernelGGL(k_colscan<1>, dim3(1), dim3(1024), 0, st, (const u64 *)d_rsum, (u64)nbr, d_rsoff);
+        hipLaunchKernelGGL(k_vcf_recoff, dim3((unsigned)nbr), dim3(VCF_THREADS), 0, st, (u64)n_rec, (const u64 *)d_rsoff, (u64)0, d_rec_at);
+        PP_HIPCHK(ctx, hipGetLastError());
+        PP_HIPCHK(ctx, hipMemcpyAsync(&n_text, d_rsoff + nbr, 8, hipMemcpyDeviceToHost, st));
+        if ((rc = next_stage(timer, 3))) return rc;
+        PP_HIPCHK(ctx, hipStreamSynchronize(st));
+        if (int code = pp_bed_host::text_size(who, n_text, msg, sizeof msg)) return ctx->fail(code, "%s", msg);
+        const size_t room = (size_t)((n_text + 15u) & ~15ull);
+        if ((rc = P->alloc(P->text, room))) return rc;
+        P->n_text = n_text;
+        P->n_records = n_rec;
+        PP_HIPCHK(ctx, hipMemsetAsync(P->text, 0, room, st));
+        DepText X;
+        X.names = d_names; X.name_off = d_noff; X.contig_off = d_coff; X.rec_at = d_rec_at; X.rec = d_rec;
+        X.nc = nc; X.frac = frac; X.n_rec = n_rec; X.n_text = n_text;
+        const uint64_t nwg = (n_text + DEP_TEXT_WG - 1) / DEP_TEXT_WG;  // (below 2^26: the text is below 2^40)
+        hipLaunchKernelGGL(k_dep_text, dim3((unsigned)nwg), dim3(DEP_THREADS), 0, st, X, P->text);
+        PP_HIPCHK(ctx, hipGetLastError());
+    }
+    if ((rc = timer.end())) return rc;
+    PP_HIPCHK(ctx, hipStreamSynchronize(st));  // the scratch goes away
+    if ((rc = P->t.take(timer))) return rc;
+    *out = P.release();
+    return PP_OK;
+}
+
+extern "C" int pp_depth_bedgraph(pp_ctx *ctx, const double *depth, int mem, uint32_t n_contigs, const uint64_t *contig_off, const char *const *contig_names,
+                                 uint32_t bin, pp_depth_out **out, uint64_t *bad_pos) {
+    if (!ctx) return PP_ERR_ARG;
+    if (int rdy = pp_ctx_wait(ctx)) return rdy;
+    if (out) *out = nullptr;
+    if (bad_pos) *bad_pos = 0;
+    pp_depth_host::Plan plan;
+    char msg[256] = "";
+    if (int code = pp_depth_host::plan("pp_depth_bedgraph", out != nullptr, depth != nullptr, mem == PP_MEM_HOST || mem == PP_MEM_DEVICE,
+                                       mem != PP_MEM_DEVICE || ((uintptr_t)depth & 7u) == 0u, n_contigs, contig_off, contig_names, bin, plan, msg, sizeof msg))
+        return ctx->fail(code, "%s", msg);
+    PP_HIPCHK(ctx, hipSetDevice(ctx->device));
+    CallScratch T;
+    const double *d_depth = depth;
+    if (mem == PP_MEM_HOST && plan.names.G) {
+        double *up = nullptr;
+        if (int rc = T.alloc(ctx, up, (size_t)plan.names.G)) return rc;
+        PP_HIPCHK(ctx, hipMemcpyAsync(up, depth, plan.names.G * 8, hipMemcpyHostToDevice, ctx->stream));
+        d_depth = up;
+    }
+    return depth_on_device(ctx, "pp_depth_bedgraph", d_depth, n_contigs, contig_off, plan, bin, out, bad_pos);
+}
+
+extern "C" int pp_polish_depth(pp_ctx *ctx, const char *const *contig_names, uint32_t bin, pp_depth_out **out) {
+    if (!ctx) return PP_ERR_ARG;
+    if (int rdy = pp_ctx_wait(ctx)) return rdy;
+    if (out) *out = nullptr;
+    char msg[256] = "";
+    if (!out || !contig_names) return ctx->fail(PP_ERR_ARG, "pp_polish_depth: null argument");
+    const pp_bed_host::JobState S{ctx->job_done, ctx->job_debug && ctx->b_dbg_depth.p != nullptr, !ctx->emit.empty() || !ctx->run_full_of.empty()};
+    if (int code = pp_bed_host::check_job("pp_polish_depth", S, msg, sizeof msg)) return ctx->fail(code, "%s", msg);
+    pp_depth_host::Plan plan;
+    if (int code = pp_depth_host::plan("pp_polish_depth", true, true, true, true, ctx->n_contigs, ctx->contig_off.data(), contig_names, bin, plan, msg, sizeof msg))
+        return ctx->fail(code, "%s", msg);
+    PP_HIPCHK(ctx, hipSetDevice(ctx->device));
+    uint64_t bad = 0;
+    return depth_on_device(ctx, "pp_polish_depth", (const double *)ctx->b_dbg_depth.p, ctx->n_contigs, ctx->contig_off.data(), plan, bin, out, &bad);
+}
+
+// ---- the file drivers' depth track (pp_driver.cpp) ----
+extern "C" int pp_ctx_set_depth(pp_ctx *ctx, int on, uint32_t bin, int bgzf) {
+    if (!ctx) return PP_ERR_ARG;
+    if (on && bin > pp_depth_host::BIN_MAX) return ctx->fail(PP_ERR_ARG, "pp_ctx_set_depth: a bin of more than 2^24 positions");
+    ctx->depth_on = on != 0;
+    ctx->depth_bin = on ? bin : 0u;
+    ctx->depth_bgzf = on != 0 && bgzf != 0;
+    return PP_OK;
+}
+extern "C" int pp_ctx_depth(pp_ctx *ctx, pp_bytes *depth) {
+    if (!ctx) return PP_ERR_ARG;
+    if (!depth) return ctx->fail(PP_ERR_ARG, "pp_ctx_depth: null argument");
+    *depth = pp_bytes{nullptr, 0};
+    if (!ctx->depth_made) return ctx->fail(PP_ERR_ARG, "pp_ctx_depth: no driver has made a depth track with pp_ctx_set_depth on this context");
+    depth->data = (uint8_t *)malloc(ctx->depth_bytes.size() + 1);
+    if (!depth->data) return ctx->fail(PP_ERR_HIP, "pp_ctx_depth: out of host memory");
+    memcpy(depth->data, ctx->depth_bytes.data(), ctx->depth_bytes.size());
+    depth->len = ctx->depth_bytes.size();
+    return PP_OK;
+}
+// (internal, the file drivers) what pp_ctx_set_depth was given; the file a driver made (data == NULL: none)
+extern "C" int pp_ctx_depth_form_(const pp_ctx *ctx, uint32_t *bin, int *bgzf) {
+    if (bin) *bin = ctx ? ctx->depth_bin : 0u;
+    if (bgzf) *bgzf = ctx && ctx->depth_bgzf ? 1 : 0;
+    return ctx && ctx->depth_on ? 1 : 0;
+}
+extern "C" void pp_ctx_keep_depth_(pp_ctx *ctx, const uint8_t *data, uint64_t n) {
+    ctx->depth_made = data != nullptr;
+    ctx->depth_bytes.assign(data ? (const char *)data : "", data ? (size_t)n : 0);
+    if (!data) ctx->depth_bytes.shrink_to_fit();
 }

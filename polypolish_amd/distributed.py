@@ -161,6 +161,9 @@ def main(argv=None):
     ap.add_argument("--bed_bgzf", action="store_true")
     ap.add_argument("--soft_mask", action="store_true")
     ap.add_argument("--bed_status", default=None)
+    ap.add_argument("--depth", default=None)
+    ap.add_argument("--depth_bin", default=None)
+    ap.add_argument("--depth_bgzf", action="store_true")
     ap.add_argument("assembly")
     ap.add_argument("sam", nargs="*")
     a = ap.parse_args(argv)
@@ -169,6 +172,8 @@ def main(argv=None):
     for flag, given in (("--bed", a.bed is not None or a.bed_bgzf), ("--soft_mask", a.soft_mask), ("--bed_status", a.bed_status is not None)):
         if given:    # (the status plane of a rank is its share's: pp_polish_bed)
             raise SystemExit(f"Error: {flag} runs on one GPU: polish with `polypolish polish {flag}`, or without {flag}")
+    if a.depth is not None or a.depth_bin is not None or a.depth_bgzf:    # (the depth plane of a rank is its share's: pp_polish_depth)
+        raise SystemExit("Error: --depth runs on one GPU: polish with `polypolish polish --depth`, or without --depth")
     for flag, given in (("--out", a.out is not None), ("--wrap", a.wrap is not None), ("--out_bgzf", a.out_bgzf), ("--index", a.index)):
         if given:    # (rank 0 writes the FASTA here as the ranks' bytes arrive; the device link makes it on one context)
             raise SystemExit(f"Error: {flag} is not available here: rank 0 writes the FASTA itself; polish with `polypolish polish {flag}`, "
