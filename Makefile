@@ -12,7 +12,7 @@ OUT      := polypolish_amd/_build
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -ffp-contract=off -fPIC -Iinclude -I$(CSRC) -Wall -Wno-unused-function
 
 LIB  := $(OUT)/libpolypolish_hip.so
-OBJS := $(OUT)/pp_kernels.o $(OUT)/pp_polish_text.o $(OUT)/pp_filter.o $(OUT)/pp_tokenize.o $(OUT)/pp_filter_dev.o $(OUT)/pp_filter_rec.o $(OUT)/pp_comm.o $(OUT)/pp_shard_dev.o $(OUT)/pp_prepare.o $(OUT)/pp_gate.o $(OUT)/pp_regroup.o $(OUT)/pp_names.o $(OUT)/pp_bam.o $(OUT)/pp_sam.o $(OUT)/pp_bam_walk.o $(OUT)/pp_bgzf.o $(OUT)/pp_bam_out.o $(OUT)/pp_bam_sort.o $(OUT)/pp_bgzf_deflate.o $(OUT)/pp_sam_out.o $(OUT)/pp_sam_bam.o $(OUT)/pp_bam_sam.o $(OUT)/pp_fasta.o $(OUT)/pp_fasta_out.o $(OUT)/pp_ingest.o $(OUT)/pp_driver.o $(OUT)/pp_driver_text.o $(OUT)/pp_driver_multi.o $(OUT)/pp_driver_bam.o $(OUT)/pp_filter_host.o $(OUT)/pp_shard.o $(OUT)/pp_bam_files.o
+OBJS := $(OUT)/pp_kernels.o $(OUT)/pp_polish_text.o $(OUT)/pp_filter.o $(OUT)/pp_tokenize.o $(OUT)/pp_filter_dev.o $(OUT)/pp_filter_rec.o $(OUT)/pp_comm.o $(OUT)/pp_shard_dev.o $(OUT)/pp_prepare.o $(OUT)/pp_gate.o $(OUT)/pp_regroup.o $(OUT)/pp_names.o $(OUT)/pp_bam.o $(OUT)/pp_sam.o $(OUT)/pp_bam_walk.o $(OUT)/pp_bgzf.o $(OUT)/pp_bam_out.o $(OUT)/pp_bam_sort.o $(OUT)/pp_tabix.o $(OUT)/pp_bgzf_deflate.o $(OUT)/pp_sam_out.o $(OUT)/pp_sam_bam.o $(OUT)/pp_bam_sam.o $(OUT)/pp_fasta.o $(OUT)/pp_fasta_out.o $(OUT)/pp_ingest.o $(OUT)/pp_driver.o $(OUT)/pp_driver_text.o $(OUT)/pp_driver_multi.o $(OUT)/pp_driver_bam.o $(OUT)/pp_filter_host.o $(OUT)/pp_shard.o $(OUT)/pp_bam_files.o
 
 all: $(LIB) bin/polypolish bin/polish_min oracle tools/_build/libsamgen.so
 

@@ -1443,6 +1443,56 @@ int pp_bam_index(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_bytes, uint64_t n
                  int mem, const uint8_t *pass, uint64_t n_pass, uint32_t n_ref,
                  const uint64_t *blk_off, uint64_t n_blk, int blk_mem, pp_bytes *bai, uint64_t *bad_record);
 
+/* ---- the .tbi of a bgzipped, position-sorted, tab-separated text, made on the device (pp_tabix.hip) ----------------------------
+ * pp_tabix_index indexes the file that pp_bgzf_deflate makes of `text`, so that tabix, bcftools, IGV and JBrowse can fetch a region
+ * from it: the polish's VCF, BED and bedGraph (pp_vcf_out_bytes, pp_bed_out_bytes, pp_depth_out_bytes), or any caller's own text.
+ * tests/tabix_model.py is the executable form of what follows.
+ *   arguments    text[0, n_bytes): the UNCOMPRESSED text.  mem = PP_MEM_HOST: uploaded; PP_MEM_DEVICE: read in place, at any alignment,
+ *                and no byte outside [0, n_bytes) is loaded, by a wide load either: the text may end where its allocation ends.
+ *                blk_off[0, n_blk] (HOST or DEVICE by blk_mem): pp_bgzf_out_blk_off of the file pp_bgzf_deflate makes of the same
+ *                text (b * 65,311 for a level-0 file); n_blk must be ceil(n_bytes / 65,280).
+ *   lines        the text is cut at every '\n'; last bytes without a '\n' are a line too.  A line whose first byte is '#' is a meta
+ *                line: skipped, not counted.  Every other line is a data line.  *bad_line is a 0-based line number of the text that
+ *                counts every line, meta lines included.
+ *   columns      column 1, up to the first tab, is the name: at least one byte, taken verbatim.  PP_TBX_BED: columns 2 and 3 are beg
+ *                and end, each 1 to 10 decimal digits; column 3 ends at a tab or at the line's end.  PP_TBX_VCF: column 2 is POS (1 to
+ *                10 digits, at least 1), beg = POS - 1, end = beg + the byte length of column 4 (REF), which is at least 1 and must be
+ *                closed by a tab.  INFO/END= is NOT read (pp_polish_vcf always writes '.' there): for a foreign VCF with END= this
+ *                differs from tabix, which takes the record's end from it.  In both presets end == beg counts as [beg, beg + 1), as
+ *                pp_bam_index does for a record without a span.
+ *   names        the distinct names in the order of their first line are the name list, each closed by a NUL; l_nm is the sum of
+ *                their lengths with the NULs.  A contig without a line is not listed, as in tabix.  The lines of one name must be
+ *                consecutive, and beg must not decrease inside a name.
+ *   offsets      a line starts at its first byte's stream offset and ends behind its '\n' (at n_bytes without one).  A stream offset
+ *                u is the virtual offset blk_off[u / 65,280] << 16 | u % 65,280, as in pp_bam_index: an end at a multiple of 65,280
+ *                is the next block's offset 0, and blk_off[n_blk] is the EOF block's.
+ *   tables       pp_bam_index's, with the name's index as the reference id: bin = reg2bin(beg, end); one chunk per maximal run of
+ *                consecutive lines with one (name, bin) -- a meta line between two data lines ends the run -- from its first line's
+ *                start to its last line's end; a bin's chunks in file order, a name's bins in ascending number, nothing merged; the
+ *                linear index over 16,384-base windows holds the smallest start of an overlapping line, an untouched window the next
+ *                touched one's; the pseudo-bin 37450 is {first line's start, last line's end}, {lines, 0}; the trailing n_no_coor
+ *                is 0.  The result is a valid .tbi, not tabix's bytes (tabix merges small bins and neighbouring chunks), the choice
+ *                pp_bam_index made for the .bai.
+ *   *raw         "TBI\1", then the int32 fields n_ref, format, col_seq, col_beg, col_end, meta = 35, skip = 0, l_nm and the names;
+ *                per name n_bin, the bins {bin, n_chunk, chunks}, n_intv, ioff[]; then the uint64 n_no_coor.  PP_TBX_VCF: format 2,
+ *                col_seq 1, col_beg 2, col_end 0; PP_TBX_BED: format 0x10000, col_seq 1, col_beg 2, col_end 3.  A text without a data
+ *                line has n_ref = 0 and l_nm = 0.  raw may be NULL.
+ *   *tbi         the same index as a BGZF file -- pp_bgzf_deflate of the raw bytes, EOF block included: the bytes of "<file>.tbi".
+ *   refusals     *bad_line = the first offender in line order.  PP_ERR_ARG: a null argument, PP_MEM_PEER, an unknown preset, n_blk
+ *                other than the stream's blocks; an empty data line, an empty name, a missing column, a number that is empty, holds
+ *                a non-digit or has more than 10 digits, POS 0, an empty REF, end < beg, beg below the beg of the line before it in
+ *                the same name, a name that comes back after another name (at the line where it comes back).  PP_ERR_LIMIT:
+ *                end > 2^29 (*bad_line; CSI is not written), a blk_off >= 2^48, n_bytes >= 2^40, more than 2^32 - 2 lines (meta
+ *                lines counted), more than 2^24 names, l_nm >= 2^31, more than 2^27 windows in the linear index.
+ * One lane parses a line whose columns are closed inside its first PP_TBX_LANE_BYTES bytes; a line with a longer name, ID or REF is
+ * parsed by a workgroup.  The bytes do not depend on which of the two took a line.  *tbi and *raw are HOST memory: release with
+ * pp_bytes_free.  The context's stream has been synchronised when the call returns. */
+#define PP_TBX_VCF 0 /* format 2,       col_seq 1, col_beg 2, col_end 0, meta '#', skip 0 */
+#define PP_TBX_BED 1 /* format 0x10000, col_seq 1, col_beg 2, col_end 3, meta '#', skip 0 (bedGraph too) */
+#define PP_TBX_LANE_BYTES 64
+int pp_tabix_index(pp_ctx *ctx, const uint8_t *text, uint64_t n_bytes, int mem, int preset, const uint64_t *blk_off, uint64_t n_blk,
+                   int blk_mem, pp_bytes *tbi, pp_bytes *raw /* may be NULL */, uint64_t *bad_line);
+
 /* Coordinate-sorted BAM for the file drivers below (the commands' --regroup): with `on` != 0, pp_polish_files and the polish half of
  * pp_filter_polish_files put pp_batch_regroup between the decode and the gate of every BAM file, so that a read's records count as
  * one read wherever they lie in the file (the filter joins them already, and writes in file order).  The state lives on the
@@ -1547,6 +1597,20 @@ int pp_ctx_set_soft_mask(pp_ctx *ctx, uint32_t status_mask);   /* 0 = off */
  * bin > 2^24 with on != 0.  The state lives on the context; off when it is made. */
 int pp_ctx_set_depth(pp_ctx *ctx, int on, uint32_t bin, int bgzf);
 int pp_ctx_depth(pp_ctx *ctx, pp_bytes *depth);
+
+/* The .tbi next to the bgzipped tracks (the commands' --vcf_tbi, --bed_tbi, --depth_tbi; not in the reference).  With
+ * pp_ctx_set_tbi(vcf, bed, depth) the file drivers above run pp_tabix_index behind pp_bgzf_deflate on the device text of each track
+ * whose flag is not 0, with the text and the block table where they lie in device memory; pp_ctx_tbi(which) returns the index of the
+ * last such run that succeeded (HOST, release with pp_bytes_free; PP_ERR_ARG when there is none, or for an unknown `which` -- a run
+ * that begins drops the indexes of the run before, a run that fails leaves none).  An index is made of a bgzipped track: a run with
+ * an index on whose track is off or not compressed (pp_ctx_set_vcf / _bed / _depth with bgzf != 0) is refused with PP_ERR_ARG before
+ * any input is looked at; several contexts are refused by the track's own name.  The tracks, the FASTA and the log's text are the
+ * run's without it.  The state lives on the context; off when it is made. */
+#define PP_TBI_VCF 0
+#define PP_TBI_BED 1
+#define PP_TBI_DEPTH 2
+int pp_ctx_set_tbi(pp_ctx *ctx, int vcf, int bed, int depth);
+int pp_ctx_tbi(pp_ctx *ctx, int which, pp_bytes *tbi);
 
 /* polish::polish (src/polish.rs:26-38): FASTA text exactly as the reference prints to stdout.
  * `sams` are SAM text files or -- all of them -- BAM files (pp_aln_file_kind; a mix is PP_ERR_QUIT).  BAM goes through the record

@@ -1459,6 +1459,41 @@ class BamIndex(_Owned):
         return {k: float(v) for k, v in zip(("scans", "records", "chunks", "linear"), ms)}
 
 
+TBX_VCF, TBX_BED = 0, 1
+TBI_TRACKS = ("vcf", "bed", "depth")  # PP_TBI_VCF, PP_TBI_BED, PP_TBI_DEPTH
+TBX_LANE_BYTES = 64  # PP_TBX_LANE_BYTES
+
+
+def tabix_index(ctx, text, preset, blk_off, mem=MEM_HOST, raw=True):
+    """pp_tabix_index: the .tbi of the file BgzfDeflated(ctx, text, mem) makes of a position-sorted, tab-separated text, made on the
+    device (tests/tabix_model.py defines the bytes).
+      text           the UNCOMPRESSED text.  mem = MEM_HOST: bytes / a uint8 array; MEM_DEVICE: (device address, n_bytes), borrowed
+      preset         TBX_VCF or TBX_BED (bedGraph too)
+      blk_off        the file's n_blocks + 1 block offsets: a host array, or (device address, n_blocks) -- BgzfDeflated.blk_off_ptr
+    -> (tbi, raw): the bytes of "<file>.tbi" and the index uncompressed (None with raw=False).  A failing call raises
+    PolypolishError with .bad_line."""
+    L = lib()
+    bp, n_bytes, _, _, _keep = _bytes_and_offsets(text, None, mem)
+    if isinstance(blk_off, tuple):
+        kp, n_blk, blk_mem, _kb = int(blk_off[0]), int(blk_off[1]), MEM_DEVICE, None
+    else:
+        _kb = np.ascontiguousarray(blk_off, dtype=np.uint64)
+        kp, n_blk, blk_mem = _kb.ctypes.data, len(_kb) - 1, MEM_HOST
+    tbi, rw, bad = Bytes(), Bytes(), _no_index()
+    rc = L.pp_tabix_index(ctx._h, bp, n_bytes, mem, int(preset), kp, n_blk, blk_mem, C.byref(tbi), C.byref(rw) if raw else None, C.byref(bad))
+    if rc:
+        _raise(rc, L.pp_last_error(ctx._h).decode(), bad_line=_index(bad))
+    return _take_bytes(tbi), (_take_bytes(rw) if raw else None)
+
+
+def tabix_stage_ms(ctx):
+    """newline index | rows | names | chunks | linear of the context's LAST pp_tabix_index (the context had set_profiling on)"""
+    ms = (C.c_float * 5)()
+    if lib().pp_tabix_stage_ms_(ctx._h, ms):
+        raise PolypolishError(ERR_ARG, "the context had no profiling on when the text was indexed")
+    return {k: float(v) for k, v in zip(("newlines", "rows", "names", "chunks", "linear"), ms)}
+
+
 class BgzfDeflated(_Owned):
     """pp_bgzf_deflate / pp_bam_out_deflate: bytes compressed into a BGZF file in DEVICE memory, owned by this object.  The bytes are
     cut every 65,280; each piece is one BGZF block around one DEFLATE block, the EOF block is the last (tests/bgzf_deflate_model.py
@@ -2280,6 +2315,52 @@ class Context:
         finally:
             self.set_depth(False)
 
+    def set_tbi(self, vcf=False, bed=False, depth=False):
+        """pp_ctx_set_tbi: polish_files and filter_polish_files run pp_tabix_index behind the pp_bgzf_deflate of the tracks named;
+        tbi(which) fetches an index"""
+        self._chk(lib().pp_ctx_set_tbi(self._h, int(bool(vcf)), int(bool(bed)), int(bool(depth))))
+
+    def tbi(self, which):
+        """pp_ctx_tbi: the .tbi (bytes) of the VCF, BED or depth track ("vcf" | "bed" | "depth", or PP_TBI_*) of the last command
+        that made one on this context"""
+        b = Bytes()
+        self._chk(lib().pp_ctx_tbi(self._h, TBI_TRACKS.index(which) if which in TBI_TRACKS else int(which), C.byref(b)))
+        return _take_bytes(b)
+
+    @contextlib.contextmanager
+    def _making_tbi(self, tbi, paths, bgzf):
+        """tbi= of one command -- True: every bgzipped track; or the tracks by name, "vcf", "bed", "depth" --: pp_ctx_set_tbi for its
+        duration; the function this yields writes <track path>.tbi once the command has succeeded and the tracks are written"""
+        if not tbi:
+            yield lambda: None
+            return
+        names = [t for t in TBI_TRACKS if bgzf[t] and paths[t] is not None] if tbi is True else ([tbi] if isinstance(tbi, str) else list(tbi))
+        for t in names:
+            if t not in TBI_TRACKS:
+                raise PolypolishError(ERR_QUIT, f"tbi: {t!r} is not one of vcf, bed, depth")
+            if not bgzf[t] or paths[t] is None:
+                raise PolypolishError(ERR_QUIT, f"tbi={t!r} needs {t}_bgzf=True: a .tbi indexes the bgzipped file")
+        if not names:
+            raise PolypolishError(ERR_QUIT, "tbi=True needs a bgzipped track (vcf_bgzf, bed_bgzf or depth_bgzf): a .tbi indexes a bgzipped file")
+        self.set_tbi(*[t in names for t in TBI_TRACKS])
+
+        def deliver():
+            for t in names:
+                to = os.fspath(paths[t]) + ".tbi"
+                data = self.tbi(t)
+                try:
+                    with open(to, "wb") as f:
+                        f.write(data)
+                except OSError:                                 # (no track and no index are left behind)
+                    for junk in (to, paths[t]):
+                        with contextlib.suppress(OSError):
+                            os.remove(junk)
+                    raise PolypolishError(ERR_QUIT, f'unable to write the index of the {t} track to "{to}"') from None
+        try:
+            yield deliver
+        finally:
+            self.set_tbi(False, False, False)
+
     @contextlib.contextmanager
     def _writing_bam(self, out_bam):
         """out_bam=True switches pp_ctx_set_out_bam on for one command and off again behind it"""
@@ -2323,7 +2404,7 @@ class Context:
     def polish_files(self, assembly, sams, fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5,
                      careful=False, debug=None, quiet=True, regroup=False, text_chain=False, wrap=None, bgzf=False, out=None,
                      index=False, vcf=None, vcf_bgzf=False, bed=None, bed_bgzf=False, bed_status=None, soft_mask=False,
-                     depth=None, depth_bin=None, depth_bgzf=False):
+                     depth=None, depth_bin=None, depth_bgzf=False, tbi=False):
         """polish::polish (pp_polish_files): the FASTA bytes.  wrap / bgzf / out / index (not in the reference): the FASTA at a line
         width (0: one line per contig) and bgzipped, made on the device (pp_fasta_text, pp_bgzf_deflate); also written to `out`,
         with out.fai (and out.gzi) for index.  `sams` are SAM text files, or all of them BAM files (BGZF or
@@ -2335,19 +2416,23 @@ class Context:
         bgzipped with bed_bgzf; soft_mask: their bases in lower case in the FASTA (pp_polish_masked); bed_status: the statuses both
         select (bed_status_mask; default the four undecided ones).  depth / depth_bin / depth_bgzf (not in the reference): the read
         depth written to the path `depth` as bedGraph made on the device (pp_polish_depth) -- runs of equal depth, or with depth_bin=N
-        the mean of bins of N positions --, bgzipped with depth_bgzf."""
+        the mean of bins of N positions --, bgzipped with depth_bgzf.  tbi (not in the reference): True, or some of "vcf", "bed",
+        "depth": the tabix index of those bgzipped tracks, made on the device (pp_tabix_index), written to <track path>.tbi."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         arr = (C.c_char_p * max(len(sams), 1))(*[str(s).encode() for s in sams])
         res = Bytes()
         with self._regrouping(regroup), self._chaining_text(text_chain), self._making_vcf(vcf, vcf_bgzf) as deliver_vcf, \
                 self._making_bed(bed, bed_bgzf, bed_status, soft_mask) as deliver_bed, \
-                self._making_depth(depth, depth_bin, depth_bgzf) as deliver_depth, self._fasta_form(wrap, bgzf, out, index) as deliver:
+                self._making_depth(depth, depth_bin, depth_bgzf) as deliver_depth, \
+                self._making_tbi(tbi, dict(vcf=vcf, bed=bed, depth=depth), dict(vcf=vcf_bgzf, bed=bed_bgzf, depth=depth_bgzf)) as deliver_tbi, \
+                self._fasta_form(wrap, bgzf, out, index) as deliver:
             self._chk(lib().pp_polish_files(self._h, str(assembly).encode(), arr, len(sams), C.byref(opt), C.byref(res)))
             data = _take_bytes(res)
             deliver_vcf()
             deliver_bed()
             deliver_depth()
+            deliver_tbi()
             deliver(data)
         return data
 
@@ -2355,14 +2440,14 @@ class Context:
                             fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5, careful=False,
                             debug=None, quiet=True, regroup=False, out_bam=False, out_sam=False, text_chain=False, wrap=None,
                             bgzf=False, out=None, index=False, sort_out=False, out_bai=False, vcf=None, vcf_bgzf=False, bed=None,
-                            bed_bgzf=False, bed_status=None, soft_mask=False, depth=None, depth_bin=None, depth_bgzf=False):
+                            bed_bgzf=False, bed_status=None, soft_mask=False, depth=None, depth_bin=None, depth_bgzf=False, tbi=False):
         """filter + polish in one process (pp_filter_polish_files): returns (FASTA bytes, filter report).  wrap / bgzf / out / index:
         as polish_files.  Two BAM inputs are decoded
         once for both halves; out1 / out2 are then BAM files as well.  regroup: for this call, as set_regroup (the polish half).
         out_bam: for this call, as set_out_bam (SAM text inputs, out1 / out2 as compressed BAM).  out_sam: for this call, as
         set_out_sam (BAM inputs, out1 / out2 as SAM text).  text_chain: for this call, as set_text_chain.  sort_out / out_bai: for
         this call, as set_sort_out (BAM outputs in coordinate order, out1.bai / out2.bai next to them).  vcf / vcf_bgzf, bed /
-        bed_bgzf / bed_status / soft_mask, depth / depth_bin / depth_bgzf: as polish_files."""
+        bed_bgzf / bed_status / soft_mask, depth / depth_bin / depth_bgzf, tbi: as polish_files."""
         opt = PolishOptions(fraction_invalid, fraction_valid, max_errors, min_depth, int(careful),
                             str(debug).encode() if debug else None, int(quiet))
         rep, res = FilterReport(), Bytes()
@@ -2370,13 +2455,16 @@ class Context:
         with self._regrouping(regroup), self._writing_bam(out_bam), self._writing_sam(out_sam), self._chaining_text(text_chain), \
                 self._sorting_out(sort_out, out_bai), self._making_vcf(vcf, vcf_bgzf) as deliver_vcf, \
                 self._making_bed(bed, bed_bgzf, bed_status, soft_mask) as deliver_bed, \
-                self._making_depth(depth, depth_bin, depth_bgzf) as deliver_depth, self._fasta_form(wrap, bgzf, out, index) as deliver:
+                self._making_depth(depth, depth_bin, depth_bgzf) as deliver_depth, \
+                self._making_tbi(tbi, dict(vcf=vcf, bed=bed, depth=depth), dict(vcf=vcf_bgzf, bed=bed_bgzf, depth=depth_bgzf)) as deliver_tbi, \
+                self._fasta_form(wrap, bgzf, out, index) as deliver:
             self._chk(lib().pp_filter_polish_files(self._h, enc(assembly), enc(in1), enc(in2), enc(out1), enc(out2),
                                                    orientation.encode(), low, high, C.byref(opt), C.byref(rep), C.byref(res)))
             data = _take_bytes(res)
             deliver_vcf()
             deliver_bed()
             deliver_depth()
+            deliver_tbi()
             deliver(data)
         return data, _report_dict(rep)
 
@@ -2408,16 +2496,17 @@ def _ctx():
 
 def polish(assembly, sam, debug=None, fraction_invalid=0.2, fraction_valid=0.5, max_errors=10, min_depth=5,
            careful=False, regroup=False, text_chain=False, wrap=None, bgzf=False, out=None, index=False, bed=None, bed_bgzf=False,
-           bed_status=None, soft_mask=False, depth=None, depth_bin=None, depth_bgzf=False) -> bytes:
+           bed_status=None, soft_mask=False, depth=None, depth_bin=None, depth_bgzf=False, tbi=False) -> bytes:
     """polish::polish (src/polish.rs:26-38): returns the FASTA bytes the reference prints to stdout.  regroup: coordinate-sorted
     BAM files (every read's records are brought together in front of the gate: the command's --regroup).  text_chain: SAM text,
     plain or bgzipped, through the record chain as well (the command's --text_chain; regroup then takes text too).  wrap / bgzf / out /
     index: the commands' --wrap, --out_bgzf, --out and --index; bed / bed_bgzf / bed_status / soft_mask: --bed, --bed_bgzf, --bed_status
-    and --soft_mask; depth / depth_bin / depth_bgzf: --depth, --depth_bin and --depth_bgzf (Context.polish_files)."""
+    and --soft_mask; depth / depth_bin / depth_bgzf: --depth, --depth_bin and --depth_bgzf; tbi: --bed_tbi and --depth_tbi
+    (Context.polish_files)."""
     return _ctx().polish_files(assembly, list(sam), fraction_invalid, fraction_valid, max_errors, min_depth, careful,
                                debug, regroup=regroup, text_chain=text_chain, wrap=wrap, bgzf=bgzf, out=out, index=index, bed=bed,
                                bed_bgzf=bed_bgzf, bed_status=bed_status, soft_mask=soft_mask, depth=depth, depth_bin=depth_bin,
-                               depth_bgzf=depth_bgzf)
+                               depth_bgzf=depth_bgzf, tbi=tbi)
 
 
 def filter(in1, in2, out1, out2, orientation="auto", low=0.1, high=99.9):  # noqa: A001 (reference name)

@@ -304,6 +304,7 @@ SIGNATURES = {
     "pp_fasta_out_free": (None, [_vp]),
     "pp_bgzf_out_gzi": (_i, [_vp, _P(Bytes)]),
     "pp_bam_index": (_i, [_vp, _vp, _u64, _u64, _vp, _u64, _i, _vp, _u64, _u32, _vp, _u64, _i, _P(Bytes), _pu64]),
+    "pp_tabix_index": (_i, [_vp, _vp, _u64, _i, _i, _vp, _u64, _i, _P(Bytes), _P(Bytes), _pu64]),
     "pp_ctx_set_regroup": (_i, [_vp, _i]),
     "pp_ctx_set_out_bam": (_i, [_vp, _i]),
     "pp_ctx_set_out_sam": (_i, [_vp, _i]),
@@ -318,6 +319,8 @@ SIGNATURES = {
     "pp_ctx_set_soft_mask": (_i, [_vp, _u32]),
     "pp_ctx_set_depth": (_i, [_vp, _i, _u32, _i]),
     "pp_ctx_depth": (_i, [_vp, _P(Bytes)]),
+    "pp_ctx_set_tbi": (_i, [_vp, _i, _i, _i]),
+    "pp_ctx_tbi": (_i, [_vp, _i, _P(Bytes)]),
     "pp_polish_files": (_i, [_vp, _str, _P(_str), _i, _P(PolishOptions), _P(Bytes)]),
     "pp_polish_files_multi": (_i, [_pvp, _i, _str, _P(_str), _i, _P(PolishOptions), _P(Bytes)]),
     "pp_dev_ingest_create": (_i, [_vp, _vp, _u32, _i, _pvp]),
@@ -361,6 +364,7 @@ HOOKS = {
     "pp_bam_out_stage_ms_": (_i, [_vp, _pf32]),     # float[3]
     "pp_bam_sorted_stage_ms_": (_i, [_vp, _pf32]),  # float[3]
     "pp_bam_index_stage_ms_": (_i, [_vp, _pf32]),   # float[4]
+    "pp_tabix_stage_ms_": (_i, [_vp, _pf32]),       # float[5]
     "pp_bgzf_out_stage_ms_": (_i, [_vp, _pf32]),    # float[3]
     "pp_sam_out_stage_ms_": (_i, [_vp, _pf32]),     # float[4]
     "pp_sam_out_geometry_": (None, [_pu32] * 3),

@@ -38,6 +38,7 @@
 #include "pp_bgzf_host.h"
 #include "pp_crc.h"
 #include "pp_dev.h"
+#include "pp_k_index.h"
 #include "pp_rg_sort.h"
 
 #include <fcntl.h>
@@ -554,23 +555,14 @@ extern "C" int pp_bam_tagged_head(pp_ctx *ctx, const uint8_t *bytes, uint64_t n_
 //                array; a CIGAR that leaves its record is refused before a run is read
 //   k_ix_check   ref_id against n_ref, a placed record's pos, the order against the record in front, end against 2^29; the bin.  The
 //                first offender in index order by atomicMin
-//   k_ix_run     a record starts a chunk where (ref_id, bin) changes; the scan of these flags numbers the chunks
-//   k_ix_chunk   a chunk's key ref_id << 32 | bin, its first record's start and its last record's end
-//   k_ix_ref     per reference: the windows it touches (atomicMax), its first record's start and last record's end, mapped and
-//                unmapped records; the unplaced records
-//   k_ix_lin     the window minima (64-bit atomicMin; a long record loops over its windows); k_ix_fill: the fill from the right
+// and the table stage that pp_tabix_index shares (pp_k_index.h: k_ix_run, k_ix_chunk, k_ix_ref, k_ix_lin, k_ix_fill, k_ix_gather):
 //   k_rg_hist / k_rg_scatter (pp_rg_sort.h)  the chunk table brought into (ref_id, bin) order, stable: a bin's chunks in file order
 // The host (pp_bam_index_host.h) writes the downloaded tables out.
 namespace {
 
 enum : u32 { IX_CIGAR = 8, IX_REF = 9, IX_PLACED = 10, IX_ORDER = 11, IX_END = 12 };
-constexpr u32 IX_MAX_END = 1u << 29;
-constexpr u64 IX_MAX_WINDOWS = 1ull << 27;  // 1 GiB of linear index
-constexpr u32 IX_MAX_REF = 1u << 24;
 
 enum : int { IX_SCANS = 0, IX_RECORDS = 1, IX_CHUNKS = 2, IX_LINEAR = 3 };
-
-struct IxRec { int32_t ref, pos; u32 end; };
 
 __global__ __launch_bounds__(256) void k_ix_rec(u32 n, const u8 *__restrict__ B, const u64 *__restrict__ rec_off, IxRec *__restrict__ rec,
                                                 uint16_t *__restrict__ flag, u64 *__restrict__ status) {
@@ -592,16 +584,6 @@ __global__ __launch_bounds__(256) void k_ix_rec(u32 n, const u8 *__restrict__ B,
     flag[r] = (uint16_t)f;
 }
 
-__device__ __forceinline__ u32 reg2bin(u32 beg, u32 end) {  // the SAM specification, section 5.3
-    --end;
-    if (beg >> 14 == end >> 14) return 4681u + (beg >> 14);
-    if (beg >> 17 == end >> 17) return 585u + (beg >> 17);
-    if (beg >> 20 == end >> 20) return 73u + (beg >> 20);
-    if (beg >> 23 == end >> 23) return 9u + (beg >> 23);
-    if (beg >> 26 == end >> 26) return 1u + (beg >> 26);
-    return 0u;
-}
-
 __device__ __forceinline__ u64 ix_key(const IxRec &R) { return (u64)(u32)R.ref << 32 | (u64)(R.ref < 0 ? 0u : (u32)R.pos); }
 
 __global__ __launch_bounds__(256) void k_ix_check(u32 n, const IxRec *__restrict__ rec, u32 n_ref, u32 *__restrict__ bin, u64 *__restrict__ status) {
@@ -620,101 +602,6 @@ __global__ __launch_bounds__(256) void k_ix_check(u32 n, const IxRec *__restrict
 __global__ __launch_bounds__(256) void k_ix_blk(u64 n, const u64 *__restrict__ blk_off, u64 *__restrict__ status) {
     const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
     if (i < n && blk_off[i] >= pp_bam_index_host::MAX_COFFSET) report(status, i);
-}
-
-__global__ __launch_bounds__(256) void k_ix_run(u32 n, const IxRec *__restrict__ rec, const u32 *__restrict__ bin, u32 *__restrict__ head) {
-    const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
-    if (r >= n) return;
-    const int32_t ref = rec[r].ref;
-    head[r] = (ref >= 0 && (r == 0 || rec[r - 1u].ref != ref || bin[r - 1u] != bin[r])) ? 1u : 0u;
-}
-
-struct IxWhere {  // where the records stand in the file
-    const u64 *start;    // n + 2: start[r + 1] = record r's stream offset
-    const u64 *blk_off;  // n_blk + 1
-    __device__ __forceinline__ u64 at(u64 u) const { return blk_off[u / PAY] << 16 | (u % PAY); }
-};
-
-__global__ __launch_bounds__(256) void k_ix_chunk(u32 n, const IxRec *__restrict__ rec, const u32 *__restrict__ bin, const u32 *__restrict__ head,
-                                                  const u32 *__restrict__ cidx, IxWhere W, u64 *__restrict__ key, u64 *__restrict__ beg, u64 *__restrict__ end) {
-    const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
-    if (r >= n || rec[r].ref < 0) return;
-    const u32 c = cidx[r] + head[r] - 1u;  // (a placed record stands in or behind a run's first record)
-    if (head[r]) {
-        key[c] = (u64)(u32)rec[r].ref << 32 | bin[r];
-        beg[c] = W.at(W.start[r + 1u]);
-    }
-    if (r + 1u == n || head[r + 1u] || rec[r + 1u].ref < 0) end[c] = W.at(W.start[r + 2u]);
-}
-
-// The records stand in coordinate order, so a wave almost always holds one reference: its lanes' counts and window maximum then meet
-// in the wave (ballots, a shuffle maximum) and its first lane issues one atomic per word; a wave over a seam between two references
-// or with unplaced records falls back to one atomic per lane.  All of it is commutative: the bytes do not depend on the path.
-__global__ __launch_bounds__(256) void k_ix_ref(u32 n, const IxRec *__restrict__ rec, const uint16_t *__restrict__ flag, IxWhere W, u32 *__restrict__ n_intv,
-                                                u64 *__restrict__ ref_beg, u64 *__restrict__ ref_end, u64 *__restrict__ mapped, u64 *__restrict__ unmapped,
-                                                u64 *__restrict__ no_coor) {
-    const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
-    const bool in = r < n;
-    const IxRec R = in ? rec[r] : IxRec{-1, 0, 1u};
-    const bool placed = in && R.ref >= 0, un = in && (flag[r] & 4u);
-    const u32 windows = placed ? ((R.end - 1u) >> 14) + 1u : 0u;
-    const u64 live = __ballot(in), m_placed = __ballot(placed);
-    const int32_t first = __shfl(R.ref, live ? (int)__builtin_ctzll(live) : 0, 64);
-    const bool one = live != 0 && m_placed == live && __ballot(in && R.ref == first) == live;  // (the same for every lane of the wave)
-    if (one) {
-        u32 w = windows;
-        for (int o = 32; o > 0; o >>= 1) w = max(w, (u32)__shfl_xor((int)w, o, 64));
-        const u64 m_un = __ballot(un);
-        if ((threadIdx.x & 63u) == (u32)__builtin_ctzll(live)) {
-            atomicMax(&n_intv[first], w);
-            const u64 k_un = (u64)__popcll(m_un), k_map = (u64)__popcll(live) - k_un;
-            if (k_map) atomicAdd(&mapped[first], k_map);
-            if (k_un) atomicAdd(&unmapped[first], k_un);
-        }
-    } else if (placed) {
-        atomicMax(&n_intv[R.ref], windows);
-        atomicAdd(un ? &unmapped[R.ref] : &mapped[R.ref], 1ull);
-    } else if (in) atomicAdd(no_coor, 1ull);
-    if (!placed) return;
-    if (r == 0 || rec[r - 1u].ref != R.ref) ref_beg[R.ref] = W.at(W.start[r + 1u]);
-    if (r + 1u == n || rec[r + 1u].ref != R.ref) ref_end[R.ref] = W.at(W.start[r + 2u]);
-}
-
-__global__ __launch_bounds__(256) void k_ix_lin(u32 n, const IxRec *__restrict__ rec, IxWhere W, const u64 *__restrict__ lin_off, u64 *__restrict__ lin) {
-    const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
-    if (r >= n || rec[r].ref < 0) return;
-    const IxRec R = rec[r];
-    const u64 v = W.at(W.start[r + 1u]), base = lin_off[R.ref];
-    // The records stand in (reference, position) order and their starts grow with r: a window that the record in front reaches too
-    // has a smaller start from it (or from one further in front), so only the windows behind that record's last one are this
-    // record's to write -- about one atomic per window and not one per record.  (The minimum stays: a record may reach further
-    // than a later one.)
-    u32 w = (u32)R.pos >> 14;
-    if (r > 0) {
-        const IxRec P = rec[r - 1u];
-        if (P.ref == R.ref) w = max(w, ((P.end - 1u) >> 14) + 1u);
-    }
-    for (; w <= (R.end - 1u) >> 14; w++) atomicMin(&lin[base + w], v);  // (w < n_intv[ref]: k_ix_ref took the maximum)
-}
-
-__global__ __launch_bounds__(256) void k_ix_fill(u32 n_ref, const u64 *__restrict__ lin_off, u64 *__restrict__ lin) {
-    const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
-    if (r >= n_ref) return;
-    u64 next = 0;
-    for (u64 w = lin_off[r + 1u]; w > lin_off[r]; w--) {  // from the right: an untouched window takes the next touched one's
-        const u64 v = lin[w - 1u];
-        if (v == ~0ull) lin[w - 1u] = next;
-        else next = v;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_ix_gather(u32 n, const u32 *__restrict__ perm, const u64 *__restrict__ a, const u64 *__restrict__ b, u64 *__restrict__ oa,
-                                                   u64 *__restrict__ ob) {
-    const u64 j = (u64)blockIdx.x * 256u + threadIdx.x;
-    if (j >= n) return;
-    const u32 p = perm[j];
-    oa[j] = a[p];
-    ob[j] = b[p];
 }
 
 }  // namespace

@@ -72,6 +72,9 @@ static const char *HELP_POLISH =
     "      --depth <PATH>                         Write the read depth to PATH as bedGraph, made on the device (one GPU; not in the reference)\n"
     "      --depth_bin <N>                        With --depth: the mean depth of bins of N positions; 0: runs of equal depth [default: 0] (not in the reference)\n"
     "      --depth_bgzf                           With --depth: compress the bedGraph into BGZF blocks on the device (not in the reference)\n"
+    "      --vcf_tbi                              With --vcf_bgzf: write PATH.tbi, the tabix index of the VCF, made on the device (not in the reference)\n"
+    "      --bed_tbi                              With --bed_bgzf: write PATH.tbi, the tabix index of the BED, made on the device (not in the reference)\n"
+    "      --depth_tbi                            With --depth_bgzf: write PATH.tbi, the tabix index of the bedGraph, made on the device (not in the reference)\n"
     "  -h, --help                                 Print help\n  -V, --version                              Print version\n";
 
 static const char *HELP_FUSED =
@@ -98,7 +101,9 @@ static const char *HELP_FUSED =
     "multiple, too_close; default low_depth,none,multiple,too_close (not in the reference).\n"
     "--depth <PATH>: write the read depth to PATH as bedGraph, made on the device (not in the reference).\n"
     "--depth_bin <N>: with --depth, the mean depth of bins of N positions; 0, the default: runs of equal depth (not in the reference).\n"
-    "--depth_bgzf: with --depth, compress the bedGraph into BGZF blocks on the device (not in the reference).\n";
+    "--depth_bgzf: with --depth, compress the bedGraph into BGZF blocks on the device (not in the reference).\n"
+    "--vcf_tbi, --bed_tbi, --depth_tbi: with --vcf_bgzf, --bed_bgzf, --depth_bgzf, write the track's tabix index to PATH.tbi, made on\n"
+    "the device (not in the reference).\n";
 
 static int usage_error(const char *msg) {
     fprintf(stderr, "error: %s\n\nFor more information, try '--help'.\n", msg);
@@ -282,6 +287,17 @@ static bool take_depth_form(const Parsed &P, const std::vector<OptSpec> &specs, 
     }
     return true;
 }
+// --vcf_tbi, --bed_tbi, --depth_tbi: three options from k0 on, each for a track that is written compressed.  false with the usage error in err
+struct TbiForm {
+    bool on[3] = {false, false, false};  // PP_TBI_VCF | _BED | _DEPTH
+};
+static bool take_tbi_form(const Parsed &P, size_t k0, bool vcf_bgzf, bool bed_bgzf, bool depth_bgzf, TbiForm &T, std::string &err) {
+    for (int w = 0; w < 3; w++) T.on[w] = P.value[k0 + w] != nullptr;
+    if (T.on[PP_TBI_VCF] && !vcf_bgzf) { err = "--vcf_tbi needs --vcf_bgzf: a .tbi indexes the bgzipped VCF file"; return false; }
+    if (T.on[PP_TBI_BED] && !bed_bgzf) { err = "--bed_tbi needs --bed_bgzf: a .tbi indexes the bgzipped BED file"; return false; }
+    if (T.on[PP_TBI_DEPTH] && !depth_bgzf) { err = "--depth_tbi needs --depth_bgzf: a .tbi indexes the bgzipped depth track"; return false; }
+    return true;
+}
 static bool write_file(const std::string &path, const uint8_t *data, uint64_t len) {
     FILE *f = fopen(path.c_str(), "wb");
     if (!f) return false;
@@ -309,36 +325,49 @@ static int deliver_fasta(pp_ctx *ctx, const FastaForm &F, const pp_bytes &fasta)
     fprintf(stderr, "\nError: unable to write the polished sequence to \"%s\"\n", F.out);
     return 1;
 }
+// The index of a track that was just written (--vcf_tbi, --bed_tbi, --depth_tbi; pp_ctx_tbi) to PATH.tbi.  An index that cannot be
+// written leaves no track and no index behind.  0, or 1 with the message on stderr.
+static int deliver_tbi(pp_ctx *ctx, int which, const char *path, const char *what) {
+    const std::string to = std::string(path) + ".tbi";
+    pp_bytes tbi{nullptr, 0};
+    const bool ok = pp_ctx_tbi(ctx, which, &tbi) == PP_OK && write_file(to, tbi.data, tbi.len);
+    pp_bytes_free(&tbi);
+    if (ok) return 0;
+    remove(to.c_str());
+    remove(path);
+    fprintf(stderr, "\nError: unable to write the index of the %s to \"%s\"\n", what, to.c_str());
+    return 1;
+}
 // The VCF of a command that succeeded (--vcf; pp_ctx_vcf), written before the FASTA is delivered: created only now, so a refused or
 // failed run leaves no file behind.  0, or 1 with the message on stderr.
-static int deliver_vcf(pp_ctx *ctx, const char *path) {
+static int deliver_vcf(pp_ctx *ctx, const char *path, bool tbi) {
     if (!path) return 0;
     pp_bytes vcf{nullptr, 0};
     const bool ok = pp_ctx_vcf(ctx, &vcf) == PP_OK && write_file(path, vcf.data, vcf.len);
     pp_bytes_free(&vcf);
-    if (ok) return 0;
+    if (ok) return tbi ? deliver_tbi(ctx, PP_TBI_VCF, path, "VCF") : 0;
     remove(path);
     fprintf(stderr, "\nError: unable to write the VCF to \"%s\"\n", path);
     return 1;
 }
 // ... and the BED (--bed; pp_ctx_bed), behind the VCF
-static int deliver_bed(pp_ctx *ctx, const char *path) {
+static int deliver_bed(pp_ctx *ctx, const char *path, bool tbi) {
     if (!path) return 0;
     pp_bytes bed{nullptr, 0};
     const bool ok = pp_ctx_bed(ctx, &bed) == PP_OK && write_file(path, bed.data, bed.len);
     pp_bytes_free(&bed);
-    if (ok) return 0;
+    if (ok) return tbi ? deliver_tbi(ctx, PP_TBI_BED, path, "BED") : 0;
     remove(path);
     fprintf(stderr, "\nError: unable to write the BED to \"%s\"\n", path);
     return 1;
 }
 // ... and the depth track (--depth; pp_ctx_depth), behind the BED
-static int deliver_depth(pp_ctx *ctx, const char *path) {
+static int deliver_depth(pp_ctx *ctx, const char *path, bool tbi) {
     if (!path) return 0;
     pp_bytes track{nullptr, 0};
     const bool ok = pp_ctx_depth(ctx, &track) == PP_OK && write_file(path, track.data, track.len);
     pp_bytes_free(&track);
-    if (ok) return 0;
+    if (ok) return tbi ? deliver_tbi(ctx, PP_TBI_DEPTH, path, "depth track") : 0;
     remove(path);
     fprintf(stderr, "\nError: unable to write the depth track to \"%s\"\n", path);
     return 1;
@@ -437,7 +466,10 @@ int main(int argc, char **argv) {
                                             {"--bed_status", 0, true, "<LIST>"},
                                             {"--depth", 0, true, "<PATH>"},
                                             {"--depth_bin", 0, true, "<N>"},
-                                            {"--depth_bgzf", 0, false, ""}};
+                                            {"--depth_bgzf", 0, false, ""},
+                                            {"--vcf_tbi", 0, false, ""},
+                                            {"--bed_tbi", 0, false, ""},
+                                            {"--depth_tbi", 0, false, ""}};
         FastaForm form;
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help) { fputs(HELP_POLISH, stdout); return 0; }
@@ -460,6 +492,8 @@ int main(int argc, char **argv) {
         if (!take_bed_form(P, 14, bed, perr)) return usage_error(perr.c_str());
         DepthForm depth;
         if (!take_depth_form(P, specs, 18, depth, perr)) return usage_error(perr.c_str());
+        TbiForm tbi;
+        if (!take_tbi_form(P, 21, vcf_bgzf, bed.bgzf, depth.bgzf, tbi, perr)) return usage_error(perr.c_str());
         if (form.index && !form.out) return refuse_index_without_out();
         const char *assembly = P.positional.empty() ? nullptr : P.positional[0];
         std::vector<const char *> sams(P.positional.begin() + (P.positional.empty() ? 0 : 1), P.positional.end());
@@ -505,6 +539,7 @@ int main(int argc, char **argv) {
             pp_ctx_set_vcf(cs[0], vcf != nullptr, vcf_bgzf);  // (several contexts: the driver refuses it by name)
             set_bed_form(cs[0], bed);
             pp_ctx_set_depth(cs[0], depth.path != nullptr, depth.bin, depth.bgzf);
+            pp_ctx_set_tbi(cs[0], tbi.on[PP_TBI_VCF], tbi.on[PP_TBI_BED], tbi.on[PP_TBI_DEPTH]);
             pp_bytes fasta{nullptr, 0};
             int rc = pp_polish_files_multi(cs.data(), (int)cs.size(), assembly, sams.data(), (int)sams.size(), &opt, &fasta);
             for (size_t d = 0; d < devs.size(); d++)
@@ -514,7 +549,7 @@ int main(int argc, char **argv) {
                 for (pp_ctx *c : cs) pp_ctx_destroy(c);
                 return rc == PP_ERR_PANIC ? 101 : 1;
             }
-            if (deliver_vcf(cs[0], vcf) || deliver_bed(cs[0], bed.path) || deliver_depth(cs[0], depth.path) || deliver_fasta(cs[0], form, fasta)) return 1;
+            if (deliver_vcf(cs[0], vcf, tbi.on[PP_TBI_VCF]) || deliver_bed(cs[0], bed.path, tbi.on[PP_TBI_BED]) || deliver_depth(cs[0], depth.path, tbi.on[PP_TBI_DEPTH]) || deliver_fasta(cs[0], form, fasta)) return 1;
             return finish(0);
         }
         // the device initialises on a helper thread while the host loads and parses the inputs
@@ -527,6 +562,7 @@ int main(int argc, char **argv) {
         pp_ctx_set_vcf(ctx, vcf != nullptr, vcf_bgzf);
         set_bed_form(ctx, bed);
         pp_ctx_set_depth(ctx, depth.path != nullptr, depth.bin, depth.bgzf);
+        pp_ctx_set_tbi(ctx, tbi.on[PP_TBI_VCF], tbi.on[PP_TBI_BED], tbi.on[PP_TBI_DEPTH]);
         pp_bytes fasta{nullptr, 0};
         rc = pp_polish_files(ctx, assembly, sams.data(), (int)sams.size(), &opt, &fasta);
         if (pp_ctx_wait(ctx) != PP_OK) return no_device(device);
@@ -535,7 +571,7 @@ int main(int argc, char **argv) {
             pp_ctx_destroy(ctx);
             return rc == PP_ERR_PANIC ? 101 : 1;
         }
-        if (deliver_vcf(ctx, vcf) || deliver_bed(ctx, bed.path) || deliver_depth(ctx, depth.path) || deliver_fasta(ctx, form, fasta)) return 1;
+        if (deliver_vcf(ctx, vcf, tbi.on[PP_TBI_VCF]) || deliver_bed(ctx, bed.path, tbi.on[PP_TBI_BED]) || deliver_depth(ctx, depth.path, tbi.on[PP_TBI_DEPTH]) || deliver_fasta(ctx, form, fasta)) return 1;
         return finish(0);
     }
 
@@ -571,7 +607,10 @@ int main(int argc, char **argv) {
                                             {"--bed_status", 0, true, "<LIST>"},
                                             {"--depth", 0, true, "<PATH>"},
                                             {"--depth_bin", 0, true, "<N>"},
-                                            {"--depth_bgzf", 0, false, ""}};
+                                            {"--depth_bgzf", 0, false, ""},
+                                            {"--vcf_tbi", 0, false, ""},
+                                            {"--bed_tbi", 0, false, ""},
+                                            {"--depth_tbi", 0, false, ""}};
         FastaForm form;
         const Parsed P = parse_args(argc, argv, 2, specs);
         if (P.help || P.version) { fputs(HELP_FUSED, stdout); return 0; }
@@ -603,6 +642,11 @@ int main(int argc, char **argv) {
             std::string berr;
             if (!take_bed_form(P, 25, bed, berr) || !take_depth_form(P, specs, 29, depth, berr)) return usage_error(berr.c_str());
         }
+        TbiForm tbi;
+        {
+            std::string terr;
+            if (!take_tbi_form(P, 32, vcf_bgzf, bed.bgzf, depth.bgzf, tbi, terr)) return usage_error(terr.c_str());
+        }
         pp_ctx *ctx = nullptr;
         int rc = pp_ctx_create_async(device, &ctx);
         if (rc) return no_device(device);
@@ -615,6 +659,7 @@ int main(int argc, char **argv) {
         pp_ctx_set_vcf(ctx, vcf != nullptr, vcf_bgzf);
         set_bed_form(ctx, bed);
         pp_ctx_set_depth(ctx, depth.path != nullptr, depth.bin, depth.bgzf);
+        pp_ctx_set_tbi(ctx, tbi.on[PP_TBI_VCF], tbi.on[PP_TBI_BED], tbi.on[PP_TBI_DEPTH]);
         pp_bytes fasta{nullptr, 0};
         rc = pp_filter_polish_files(ctx, assembly, in1, in2, out1, out2, orientation, low, high, &opt, nullptr, &fasta);
         if (pp_ctx_wait(ctx) != PP_OK) return no_device(device);
@@ -623,7 +668,7 @@ int main(int argc, char **argv) {
             pp_ctx_destroy(ctx);
             return rc == PP_ERR_PANIC ? 101 : 1;
         }
-        if (deliver_vcf(ctx, vcf) || deliver_bed(ctx, bed.path) || deliver_depth(ctx, depth.path) || deliver_fasta(ctx, form, fasta)) return 1;
+        if (deliver_vcf(ctx, vcf, tbi.on[PP_TBI_VCF]) || deliver_bed(ctx, bed.path, tbi.on[PP_TBI_BED]) || deliver_depth(ctx, depth.path, tbi.on[PP_TBI_DEPTH]) || deliver_fasta(ctx, form, fasta)) return 1;
         return finish(0);
     }
 

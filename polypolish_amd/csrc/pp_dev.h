@@ -2,7 +2,7 @@
 // the SEQ byte codes, the workgroup scans over the DPP wave scan of pp_wave.h, the multi-block exclusive scan, the host
 // plumbing of one call (read-back, scratch, upload, stage timing), and the host side of the record chain's owned objects (the
 // owner of their device memory, their stage times, the named arrays of a batch, a caller's batch checked and uploaded).  Included
-// by pp_devtext.h (the SAM tokenizers' text utilities), by pp_textin.h (a borrowed text's: pp_sam_out.hip, pp_sam_bam.hip) and
+// by pp_devtext.h (the SAM tokenizers' text utilities), by pp_textin.h (a borrowed text's: pp_sam_out.hip, pp_sam_bam.hip, pp_tabix.hip) and
 // directly by the record chain: pp_bgzf.hip, pp_bgzf_deflate.hip,
 // pp_bam.hip, pp_bam_walk.hip, pp_bam_out.hip, pp_names.hip, pp_filter_rec.hip and pp_regroup.hip (through pp_filter_group.h), pp_bam_sort.hip (through pp_rg_sort.h),
 // pp_gate.hip and pp_prepare.hip, and by the units that make text from finished work: pp_fasta_out.hip and pp_polish_text.hip (the

@@ -307,6 +307,18 @@ static const uint8_t *polished_on_device(PolishJob &J) {
     return dev;
 }
 
+// The .tbi of pp_ctx_set_tbi for one track: pp_tabix_index on the track's device text and on the block table of its pp_bgzf_deflate,
+// both read where they lie; one copy of the index into the job (J.tbi_file[which]).
+static int make_tbi(PolishJob &J, int which, int preset, const uint8_t *text, uint64_t n_text, const pp_bgzf_out *z) {
+    uint64_t n_blk = 0, bad = 0;
+    const uint64_t *blk = pp_bgzf_out_blk_off(z, &n_blk);
+    pp_bytes tbi{nullptr, 0};
+    const int rc = pp_tabix_index(J.ctx, text, n_text, PP_MEM_DEVICE, preset, blk, n_blk, PP_MEM_DEVICE, &tbi, nullptr, &bad);
+    if (rc == PP_OK) J.tbi_file[which].assign(tbi.data, tbi.data + tbi.len);
+    pp_bytes_free(&tbi);
+    return rc;
+}
+
 // The BED of pp_ctx_set_bed: pp_polish_bed on the finished job, pp_bgzf_deflate on the device text with bgzf, one copy off the
 // device into the job (J.bed_file).  Nothing is logged.
 static int make_bed(PolishJob &J) {
@@ -319,6 +331,7 @@ static int make_bed(PolishJob &J) {
     if (rc == PP_OK) pp_bed_out_bytes(text, &dev, &n, nullptr);
     if (rc == PP_OK && J.bed_bgzf) {
         rc = pp_bgzf_deflate(ctx, dev, n, PP_MEM_DEVICE, &z);
+        if (rc == PP_OK && J.tbi_on[PP_TBI_BED]) rc = make_tbi(J, PP_TBI_BED, PP_TBX_BED, dev, n, z);
         if (rc == PP_OK) pp_bgzf_out_bytes(z, &dev, &n);
     }
     if (rc == PP_OK) {  // (handed to the context once the whole run has succeeded: polish_once)
@@ -327,7 +340,7 @@ static int make_bed(PolishJob &J) {
     }
     pp_bgzf_out_free(z);
     pp_bed_out_free(text);
-    J.lap(J.bed_bgzf ? "BED made and compressed on the device" : "BED made on the device");
+    J.lap(J.tbi_on[PP_TBI_BED] ? "BED made, compressed and indexed on the device" : J.bed_bgzf ? "BED made and compressed on the device" : "BED made on the device");
     return rc;
 }
 
@@ -343,6 +356,7 @@ static int make_depth(PolishJob &J) {
     if (rc == PP_OK) pp_depth_out_bytes(text, &dev, &n, nullptr);
     if (rc == PP_OK && J.depth_bgzf) {
         rc = pp_bgzf_deflate(ctx, dev, n, PP_MEM_DEVICE, &z);
+        if (rc == PP_OK && J.tbi_on[PP_TBI_DEPTH]) rc = make_tbi(J, PP_TBI_DEPTH, PP_TBX_BED, dev, n, z);
         if (rc == PP_OK) pp_bgzf_out_bytes(z, &dev, &n);
     }
     if (rc == PP_OK) {  // (handed to the context once the whole run has succeeded: polish_once)
@@ -351,7 +365,9 @@ static int make_depth(PolishJob &J) {
     }
     pp_bgzf_out_free(z);
     pp_depth_out_free(text);
-    J.lap(J.depth_bgzf ? "depth track made and compressed on the device" : "depth track made on the device");
+    J.lap(J.tbi_on[PP_TBI_DEPTH] ? "depth track made, compressed and indexed on the device"
+          : J.depth_bgzf         ? "depth track made and compressed on the device"
+                                 : "depth track made on the device");
     return rc;
 }
 
@@ -498,6 +514,7 @@ static int make_vcf(PolishJob &J, int bgzf) {
     if (rc == PP_OK) pp_vcf_out_bytes(text, &dev, &n, nullptr);
     if (rc == PP_OK && bgzf) {
         rc = pp_bgzf_deflate(ctx, dev, n, PP_MEM_DEVICE, &z);
+        if (rc == PP_OK && J.tbi_on[PP_TBI_VCF]) rc = make_tbi(J, PP_TBI_VCF, PP_TBX_VCF, dev, n, z);
         if (rc == PP_OK) pp_bgzf_out_bytes(z, &dev, &n);
     }
     std::vector<uint8_t> host;
@@ -508,7 +525,7 @@ static int make_vcf(PolishJob &J, int bgzf) {
     if (rc == PP_OK) pp_ctx_keep_vcf_(ctx, host.data(), n);
     pp_bgzf_out_free(z);
     pp_vcf_out_free(text);
-    J.lap(bgzf ? "VCF made and compressed on the device" : "VCF made on the device");
+    J.lap(J.tbi_on[PP_TBI_VCF] ? "VCF made, compressed and indexed on the device" : bgzf ? "VCF made and compressed on the device" : "VCF made on the device");
     return rc;
 }
 
@@ -540,6 +557,12 @@ static int polish_once(PolishJob &J, pp_bytes *fasta) {
     pp_ctx_keep_depth_(J.ctx, nullptr, 0);  // (the file of the run before)
     if (J.depth_on && J.n_ctx > 1)  // (the depth plane of a rank is its share's: pp_polish_depth)
         return set_err(J.ctx, PP_ERR_QUIT, "--depth runs on one GPU: polish without PP_GPUS / several contexts, or without --depth");
+    for (int w = 0; w <= PP_TBI_DEPTH; w++) {
+        J.tbi_on[w] = pp_ctx_tbi_form_(J.ctx, w) != 0;
+        pp_ctx_keep_tbi_(J.ctx, w, nullptr, 0);  // (the index of the run before)
+    }
+    if ((J.tbi_on[PP_TBI_VCF] && !(vcf_on && vcf_bgzf)) || (J.tbi_on[PP_TBI_BED] && !(J.bed_on && J.bed_bgzf)) || (J.tbi_on[PP_TBI_DEPTH] && !(J.depth_on && J.depth_bgzf)))
+        return set_err(J.ctx, PP_ERR_ARG, "pp_ctx_set_tbi: a .tbi indexes a bgzipped track: switch the track on with bgzf (pp_ctx_set_vcf, pp_ctx_set_bed, pp_ctx_set_depth)");
     if (int rc = check_options_and_inputs(J)) return rc;
     log_banner(J);
     J.lap("driver entered");
@@ -564,6 +587,8 @@ static int polish_once(PolishJob &J, pp_bytes *fasta) {
         J.depth_file.push_back(0);
         pp_ctx_keep_depth_(J.ctx, J.depth_file.data(), J.depth_file.size() - 1);
     }
+    for (int w = 0; w <= PP_TBI_DEPTH; w++)  // (as the tracks: pp_ctx_tbi)
+        if (J.tbi_on[w]) pp_ctx_keep_tbi_(J.ctx, w, J.tbi_file[w].data(), J.tbi_file[w].size());
     log_finished(J);
     J.release();
     J.lap("device and host buffers released");

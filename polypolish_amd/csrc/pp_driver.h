@@ -165,6 +165,9 @@ struct PolishJob {
     uint32_t depth_bin = 0;
     int depth_bgzf = 0;
     std::vector<uint8_t> depth_file;  // the depth track of this run, the context's once the run has succeeded
+    // pp_ctx_set_tbi (one context): the .tbi of the bgzipped VCF | BED | depth track (PP_TBI_*), made where the track is made (make_tbi)
+    bool tbi_on[3] = {false, false, false};
+    std::vector<uint8_t> tbi_file[3];  // the indexes of this run, the context's once the run has succeeded
     bool wants_status() const { return bed_on || soft_mask != 0 || depth_on; }
     std::vector<uint8_t> polished = std::vector<uint8_t>(1);
     std::vector<uint64_t> out_off;

@@ -42,6 +42,8 @@ void pp_ctx_keep_bed_(pp_ctx *ctx, const uint8_t *data, uint64_t n);  // ... and
 uint32_t pp_ctx_soft_mask_(const pp_ctx *ctx);                  // what pp_ctx_set_soft_mask was given (0: off)
 int pp_ctx_depth_form_(const pp_ctx *ctx, uint32_t *bin, int *bgzf);  // what pp_ctx_set_depth was given; 1 when the depth track is on (the file drivers)
 void pp_ctx_keep_depth_(pp_ctx *ctx, const uint8_t *data, uint64_t n);  // ... and the file they made (NULL: none -- a run begins)
+int pp_ctx_tbi_form_(const pp_ctx *ctx, int which);  // what pp_ctx_set_tbi was given for PP_TBI_VCF | _BED | _DEPTH; 1 when that index is on
+void pp_ctx_keep_tbi_(pp_ctx *ctx, int which, const uint8_t *data, uint64_t n);  // ... and the index they made (NULL: none -- a run begins)
 int pp_ctx_set_fasta_out_name_(pp_ctx *ctx, const char *path);  // the file the caller will write the FASTA to (NULL: stdout); the log names it
 const char *pp_ctx_fasta_out_name_(const pp_ctx *ctx);
 int pp_sam_empty_qname_rule_(pp_sam *s);                        // pp_sam.hip: read_id as the reference groups behind an empty QNAME (the text front, for the gate)

@@ -284,6 +284,11 @@ struct pp_ctx {
     bool out_bam = false;  // pp_ctx_set_out_bam: the filter drivers write SAM text inputs back as compressed BAM
     float ix_ms[4] = {0.f, 0.f, 0.f, 0.f};   // pp_bam_index: the stage times of the last call made with profiling on (pp_bam_index_stage_ms_)
     bool ix_timed = false;
+    float tbx_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  // pp_tabix_index: the same, newline index | rows | names | chunks | linear (pp_tabix_stage_ms_)
+    bool tbx_timed = false;
+    bool tbi_on[3] = {false, false, false};    // pp_ctx_set_tbi: the .tbi of the bgzipped VCF | BED | depth track (the file drivers)
+    bool tbi_made[3] = {false, false, false};  // ... and the indexes of the last run that succeeded (pp_ctx_tbi)
+    std::string tbi_bytes[3];
     bool sort_out = false, out_bai = false;  // pp_ctx_set_sort_out: the filter drivers write BAM outputs in coordinate order, with a .bai
     bool out_sam = false;  // pp_ctx_set_out_sam: the filter drivers write BAM inputs back as SAM text
     bool regroup = false;  // pp_ctx_set_regroup: the file drivers regroup every BAM file's records in front of the gate

@@ -1,5 +1,5 @@
 // pp_textin.h -- device-side utilities for a text that is BORROWED: not padded, at any alignment, possibly ending where its allocation
-// ends (pp_sam_out.hip: pp_sam_tagged; pp_sam_bam.hip: pp_sam_bam).  pp_devtext.h's kernels read a padded copy; everything here checks
+// ends (pp_sam_out.hip: pp_sam_tagged; pp_sam_bam.hip: pp_sam_bam; pp_tabix.hip: pp_tabix_index).  pp_devtext.h's kernels read a padded copy; everything here checks
 // every load against the text's size, a wide load too: no byte outside [0, size) is loaded.  Anonymous namespace, as pp_dev.h.
 #pragma once
 #include "pp_dev.h"

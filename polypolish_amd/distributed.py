@@ -164,6 +164,9 @@ def main(argv=None):
     ap.add_argument("--depth", default=None)
     ap.add_argument("--depth_bin", default=None)
     ap.add_argument("--depth_bgzf", action="store_true")
+    ap.add_argument("--vcf_tbi", action="store_true")
+    ap.add_argument("--bed_tbi", action="store_true")
+    ap.add_argument("--depth_tbi", action="store_true")
     ap.add_argument("assembly")
     ap.add_argument("sam", nargs="*")
     a = ap.parse_args(argv)
@@ -174,6 +177,9 @@ def main(argv=None):
             raise SystemExit(f"Error: {flag} runs on one GPU: polish with `polypolish polish {flag}`, or without {flag}")
     if a.depth is not None or a.depth_bin is not None or a.depth_bgzf:    # (the depth plane of a rank is its share's: pp_polish_depth)
         raise SystemExit("Error: --depth runs on one GPU: polish with `polypolish polish --depth`, or without --depth")
+    for flag, given in (("--vcf_tbi", a.vcf_tbi), ("--bed_tbi", a.bed_tbi), ("--depth_tbi", a.depth_tbi)):
+        if given:    # (the index of a track that runs on one GPU: pp_tabix_index)
+            raise SystemExit(f"Error: {flag} runs on one GPU: polish with `polypolish polish {flag}`, or without {flag}")
     for flag, given in (("--out", a.out is not None), ("--wrap", a.wrap is not None), ("--out_bgzf", a.out_bgzf), ("--index", a.index)):
         if given:    # (rank 0 writes the FASTA here as the ranks' bytes arrive; the device link makes it on one context)
             raise SystemExit(f"Error: {flag} is not available here: rank 0 writes the FASTA itself; polish with `polypolish polish {flag}`, "
